@@ -17,10 +17,16 @@ or of the variable-length hit lists (--mode all) to rank 0.
 process, before anything touches the GPU) and forwards the child's JSON line; inside
 such a launch (RANK/WORLD_SIZE set, by this launcher or by the driver's) it runs as one rank.
 
-Prints ONE JSON line on rank 0.  At N=1 the line also carries, under "extra": the same
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints
+the headline.  With --full, at N=1, the line also carries the CPU baseline (the oracle on the
+host cores, with a parity check on a sample of the step's reads) and, under "extra": the same
 step on reads in shuffled order, C3 (matchAll, k=2, same index) and C5 (150 bp, 64-bit
 signatures, k=5, index rebuilt), each with its own ms/step, roofline and a check against
 the oracle, and the host-inclusive (pinned, double-buffered, packed) rate of C2.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 /
+float64): the fields of the records of a fixed, seeded sample of the reads (matchUnique), or
+of the hit records (--mode all), so that two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -401,6 +407,46 @@ def timed_all(torch, dist, m, rlib, bases, qual, patl, n, steps, warmup, world, 
     return dt, m.counters(), kt, nh[0], nroot[0], (hits_dev, hoff_dev)
 
 
+DUMP_ROWS = 1 << 20         # records per dumped array: 48 MB in all at most (--dump-outputs)
+DUMP_SEED = 20240
+
+
+def dump_sample(torch, count, dev):
+    """a fixed, seeded, ascending sample of range(count) (all of it when small): the same rows for the same arguments"""
+    idx = np.arange(count) if count <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(count, DUMP_ROWS, replace=False))
+    return idx, torch.from_numpy(idx.astype(np.int64)).to(dev)
+
+
+def unique_outputs(torch, info, score, n, dev):
+    """the matchUnique records of the sampled reads, field by field (include/real_hip.h: state:3@61, fragment:16@45,
+    errors:4@41, fileid:6@35, position:35@0), and their scores"""
+    idx, di = dump_sample(torch, n, dev)
+    rec = info[di].cpu().numpy().view(np.uint64)
+    field = lambda at, bits: ((rec >> np.uint64(at)) & np.uint64((1 << bits) - 1))
+    return {"read_index": idx.astype(np.float64), "state": field(61, 3).astype(np.float32), "fragment": field(45, 16).astype(np.float32),
+            "errors": field(41, 4).astype(np.float32), "fileid": field(35, 6).astype(np.float32),
+            "position": field(0, 35).astype(np.float64), "score": score[di].cpu().numpy().astype(np.float32)}
+
+
+def all_outputs(torch, rlib, hits_dev, hoff_dev, n_hits, n, dev):
+    """matchAll: the hit counts of the sampled reads, and the sampled hit records field by field"""
+    idx, di = dump_sample(torch, n, dev)
+    out = {"read_index": idx.astype(np.float64), "hit_count": (hoff_dev[1:][di] - hoff_dev[:-1][di]).cpu().numpy().astype(np.float64)}
+    _, dh = dump_sample(torch, n_hits, dev)
+    h = hits_dev.view(-1, 4)[:n_hits][dh].cpu().numpy().reshape(-1).view(rlib.HIT_DTYPE)
+    out.update({"hit_read": h["read"].astype(np.float64), "hit_pos": h["pos"].astype(np.float64), "hit_score": h["score"].astype(np.float32),
+                "hit_frag": h["frag"].astype(np.float32), "hit_k": h["k"].astype(np.float32), "hit_inverted": h["inverted"].astype(np.float32)})
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def roofline_block(ctr, kernel_ms, launches, patl, seedl, scores, kernel_name, hit_bytes_out=0, traffic=None):
     a_total = algorithmic_bytes(ctr, patl, seedl, scores, hit_bytes_out)
     a_launch = a_total / max(launches, 1)
@@ -446,13 +492,17 @@ def main():
     ap.add_argument("--scores", type=int, default=1)
     ap.add_argument("--prefix-bits", type=int, default=0)
     ap.add_argument("--table-kind", type=int, default=0, help="device bucket tables: 0 auto, 1 starts, 2 directory, 3 bucket rows (real_hip.h)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline and (auto) the side measurements under \"extra\"; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (a seeded sample, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the CPU baseline's main leg (0 = all the CPUs this process may run on); a second leg runs on 8")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU work the baseline sample is sized for (a bounded sample; 40 covers all 50M reads on 16 threads)")
     ap.add_argument("--mode", choices=["unique", "all", "ingest"], default="unique",
                     help="unique = BASELINE configs[1] (default, what the driver runs); all = configs[2] (matchAll)")
     ap.add_argument("--extras", choices=["auto", "on", "off"], default="auto",
-                    help="C3 / C5 / shuffled reads / host-inclusive side measurements in the line's \"extra\" (auto: at N=1 on the BASELINE workload)")
+                    help="C3 / C5 / shuffled reads / host-inclusive side measurements in the line's \"extra\" (auto: with --full, at N=1 on the BASELINE workload)")
     ap.add_argument("--extra-steps", type=int, default=5)
     ap.add_argument("--shuffle-reads", action="store_true", help="reads in random order instead of genpat's sorted order")
     ap.add_argument("--input-format", choices=["packed", "bytes"], default="packed",
@@ -464,6 +514,8 @@ def main():
                     help="N>1 rehearsal on a 1-GPU box: every rank uses cuda:0 and the gather runs over gloo on host copies")
     ap.add_argument("--launch-check", action="store_true", help="only check the launcher: ranks meet over gloo on the CPU, no GPU call")
     args = ap.parse_args()
+    if args.dump_outputs and (args.mode == "ingest" or args.host_buffers):
+        ap.error("--dump-outputs: the timed path of --mode unique or --mode all only")
 
     # ---- one process per GPU: start the ranks if nobody has
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -533,15 +585,15 @@ def main():
     n = args.reads
     bases, qual, true_pos, true_inv = gen_reads(torch, sym, n, args.patl, 0.02, 4 + rank, dev, shuffle=args.shuffle_reads)
     log("reads generated")
-    extras_on = (args.extras == "on") or (args.extras == "auto" and world == 1 and args.mode == "unique" and not args.host_buffers and
+    extras_on = (args.extras == "on") or (args.extras == "auto" and args.full and world == 1 and args.mode == "unique" and not args.host_buffers and
                                           (args.patl, args.seedl, args.totalk, args.scores) == (100, 32, 3, 1) and not args.shuffle_reads)
     # the CPU port keeps the six lists in host memory ((4 or 8) + 4 bytes per window and list): 144 GB for 3 Gbp with
     # 32-bit signatures, 216 GB with 64-bit ones -- the latter does not fit the box's 270 GiB with everything else
     host_index_gb = n_entries * 6 * ((4 if args.seedl <= 32 else 8) + 4) / 1e9
-    if host_index_gb > 180 and not args.no_cpu_baseline:
+    if args.full and host_index_gb > 180 and not args.no_cpu_baseline:
         log("cpu baseline skipped: the CPU port's index would take %.0f GB of host memory" % host_index_gb)
         args.no_cpu_baseline = True
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     sym_host = sym.cpu().numpy() if (want_cpu or (extras_on and rank == 0)) else None
     if not extras_on:
         del sym
@@ -557,8 +609,10 @@ def main():
 
     if args.mode == "all":
         packed = args.input_format == "packed" and (n * args.patl) % 4 == 0
-        dt, ctr, kt, nh, nroot, _ = timed_all(torch, dist, m, rlib, pack_bases(torch, bases, n, args.patl) if packed else bases, qual, args.patl, n,
-                                              args.steps, args.warmup, world, rank, dev, gather_dev, packed=packed)
+        dt, ctr, kt, nh, nroot, (hits_dev, hoff_dev) = timed_all(torch, dist, m, rlib, pack_bases(torch, bases, n, args.patl) if packed else bases, qual,
+                                                                 args.patl, n, args.steps, args.warmup, world, rank, dev, gather_dev, packed=packed)
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, all_outputs(torch, rlib, hits_dev, hoff_dev, nh, n, dev))
         if rank == 0:
             K = args.steps
             mk, ml = kt["match"]
@@ -589,6 +643,8 @@ def main():
     dt, ctr, (match_ms, match_n), (rep_ms, rep_n), (info, score) = timed_unique(
         torch, dist, m, rlib, pk if packed else bases, qual, args.patl, n, args.steps, args.warmup, world, rank, dev, gather_dev, log, packed=packed)
     log("timed steps done: %.1f ms/step" % (dt / args.steps * 1e3))
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, unique_outputs(torch, info, score, n, dev))
 
     if rank == 0:
         K = args.steps

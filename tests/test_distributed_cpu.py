@@ -139,3 +139,75 @@ def test_bench_two_rank_rehearsal_through_the_launcher():
     assert d["gather_exposed_ms_per_step"] < j["ms_per_step"]
     j = _bench_json(small + ["--mode", "all", "--totalk", "2"])
     assert j["n_gpus"] == 2 and j["config"]["hits_gathered_on_root_per_step"] > j["config"]["hits_per_step_rank0"] > 0
+
+
+def test_bench_dump_outputs_are_a_seeded_sample_of_the_records_as_floats(tmp_path):
+    """--dump-outputs: the step's records field by field (float32 / float64, 64 MB at most) for a fixed, seeded sample of the
+    reads -- the same rows for the same arguments -- and matchAll's hit counts and hit records likewise"""
+    import torch
+    import bench
+    from real_amd import lib as rlib
+    from real_amd.matcher import unpack_info
+    n = 3_000_000
+    rng = np.random.default_rng(5)
+    rec = ((rng.integers(0, 5, n, dtype=np.uint64) << np.uint64(61)) | (rng.integers(0, 1 << 16, n, dtype=np.uint64) << np.uint64(45)) |
+           (rng.integers(0, 16, n, dtype=np.uint64) << np.uint64(41)) | (rng.integers(0, 64, n, dtype=np.uint64) << np.uint64(35)) |
+           rng.integers(0, 1 << 35, n, dtype=np.uint64))
+    score = rng.standard_normal(n).astype(np.float32)
+    a, b = (bench.unique_outputs(torch, torch.from_numpy(rec.view(np.int64)), torch.from_numpy(score), n, "cpu") for _ in range(2))
+    assert all(a[k].dtype in (np.float32, np.float64) and a[k].tobytes() == b[k].tobytes() for k in a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    i = a["read_index"].astype(np.int64)
+    assert i.shape[0] == bench.DUMP_ROWS < n and np.all(np.diff(i) > 0)
+    for got, want in zip((a["state"], a["fragment"], a["errors"], a["fileid"], a["position"]), unpack_info(rec[i])):
+        assert np.array_equal(got.astype(np.int64), want)
+    assert np.array_equal(a["score"].view(np.uint32), score[i].view(np.uint32))
+
+    counts = rng.integers(0, 4, n)
+    hoff = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    n_hits = int(hoff[-1])
+    hits = np.zeros(n_hits + 100, dtype=rlib.HIT_DTYPE)
+    hits["read"][:n_hits] = np.repeat(np.arange(n), counts)
+    hits["pos"] = rng.integers(0, 1 << 32, n_hits + 100, dtype=np.uint64)
+    hits["score"] = rng.standard_normal(n_hits + 100)
+    h = bench.all_outputs(torch, rlib, torch.from_numpy(hits.view(np.int32)), torch.from_numpy(hoff), n_hits, n, "cpu")
+    assert all(v.dtype in (np.float32, np.float64) for v in h.values()) and sum(v.nbytes for v in h.values()) <= 64 << 20
+    assert np.array_equal(h["hit_count"], counts[h["read_index"].astype(np.int64)])
+    assert np.all(np.diff(h["hit_read"]) >= 0) and h["hit_read"].max() < n and h["hit_pos"].max() < 2 ** 32
+    bench.dump_outputs(str(tmp_path / "d"), a)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(k + ".npy" for k in a)
+    assert np.load(tmp_path / "d" / "position.npy").tobytes() == a["position"].tobytes()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_the_headline_and_dumps_the_same_outputs_twice(tmp_path):
+    """a plain run is the headline alone (no CPU baseline, no "extra"); --steps sets the timed steps; two runs with the same
+    arguments dump identical outputs, and the dumped records are the ones the line counts"""
+    n = 200_000
+    small = ["--genome-mbp", "20", "--reads", str(n), "--steps", "3", "--warmup", "1"]
+    runs = [_bench_json(small + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for j in runs:
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["cpu_baseline"] is None and "extra" not in j
+        assert abs(j["value"] * j["ms_per_step"] * 1e-3 - n) < 1e-6 * n
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and "state.npy" in names and "score.npy" in names
+    for f in names:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.shape == (n,) and x.tobytes() == y.tobytes(), f
+    st = np.load(tmp_path / "a" / "state.npy")
+    assert abs(float(((st == 1) | (st == 2)).mean()) - runs[0]["config"]["uniquely_aligned_frac_rank0"]) < 1e-12
+    j = _bench_json(small + ["--mode", "all", "--totalk", "2", "--dump-outputs", str(tmp_path / "all")])
+    cnt, hr = np.load(tmp_path / "all" / "hit_count.npy"), np.load(tmp_path / "all" / "hit_read.npy")
+    assert cnt.dtype == np.float64 and cnt.shape == (n,) and cnt.sum() == j["config"]["hits_per_step_rank0"] == hr.shape[0] > 0
+    assert np.array_equal(np.bincount(hr.astype(np.int64), minlength=n), cnt)
+
+
+@pytest.mark.gpu
+def test_bench_full_run_carries_the_cpu_baseline_and_the_side_measurements():
+    j = _bench_json(["--genome-mbp", "20", "--reads", "200000", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "1", "--extra-steps", "2"])
+    assert j["cpu_baseline"]["parity_on_sample"]
+    ex = j["extra"]
+    assert set(ex) == {"c2_byte_bases", "c2_fresh_records", "c2_shuffled_reads", "c2_host_inclusive", "c3_match_all", "c5_150bp_l64"}
+    assert not [k for k, v in ex.items() if "error" in v], ex
+    assert ex["c2_fresh_records"]["records_equal_initialised_run"] and ex["c2_host_inclusive"]["records_equal_resident_run"]
+    assert ex["c3_match_all"]["parity_on_sample"] and ex["c5_150bp_l64"]["verified_on_sample"]
