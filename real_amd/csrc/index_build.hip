@@ -86,30 +86,41 @@ int rh_count_wild(real_hip_ctx *ctx, uint64_t n)
 // ---------------------------------------------------------------------------
 // index layout from a sorted list
 // ---------------------------------------------------------------------------
-void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries)
+// prefix bits of bucket rows: about 11 entries per 128-byte row of 20; 32-bit signatures: at most 16 signature values per row
+static uint32_t rows_prefix_bits(uint32_t l, uint64_t n_entries)
 {
-    const uint32_t l = ctx->prm.seedl, want = ctx->prm.table_kind;
-    uint32_t pb = ctx->prm.prefix_bits;
-    const bool auto_pb = (pb == 0);
+    uint32_t pb = 1;
+    while (pb < 30 && (double)n_entries / (double)(1ull << pb) > 11.5) pb++;
+    if (l <= 32 && pb + 4 < l) pb = l - 4;
+    return pb;
+}
+
+// the decision itself, without the device: pure in its arguments (device_bytes = the device's total memory)
+RhTables rh_plan_tables(uint32_t l, uint32_t request, uint32_t prefix_bits, uint64_t n_entries, uint64_t device_bytes, bool no_rows)
+{
+    // the ABI request (real_hip_params.table_kind): 0 auto, 1 bucket starts, 2 directory, 3 bucket rows
+    const bool want_auto = request == 0, want_starts = request == 1, want_dir = request == 2, want_rows = request == 3;
+    const bool auto_pb = prefix_bits == 0;
     uint32_t lg = 0;
     while ((1ull << (lg + 1)) <= (n_entries ? n_entries : 1)) lg++;
-    const bool big = lg >= 27 && want != 1;
-    bool rows = want == 3;
-    if (want == 0 && auto_pb && big && !ctx->no_rows) {
+    const bool big = lg >= 27 && !want_starts;
+    const uint32_t rpb = rows_prefix_bits(l, n_entries);
+    bool rows = want_rows;
+    if (want_auto && auto_pb && big && !no_rows) {
         // bucket rows are the faster layout (one HBM line per lookup) when they fit: 128 B x 2^pb x 6 lists plus the
         // build's transients (the full entry array of one list, the window positions, the bucket starts and overflow scans)
-        uint32_t rpb = 1;
-        while (rpb < 30 && (double)n_entries / (double)(1ull << rpb) > 11.5) rpb++;
-        if (l <= 32 && rpb + 4 < l) rpb = l - 4;
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
         const double need = 6.0 * 128.0 * (double)(1ull << rpb) + 12.0 * (double)n_entries + 12.0 * (double)(1ull << rpb);
         // (only when the rows are reasonably full: a 200 Mbp genome would take the same 2^(l-4) rows as a 3 Gbp one)
-        rows = (l <= 32 ? rpb < l : rpb + 32 <= l) && (double)n_entries / (double)(1ull << rpb) >= 4.0 && need * 1.08 <= (double)total_b;
+        rows = (l <= 32 ? rpb < l : rpb + 32 <= l) && (double)n_entries / (double)(1ull << rpb) >= 4.0 && need * 1.08 <= (double)device_bytes;
     }
-    if (auto_pb) {
+    uint32_t pb = prefix_bits;
+    if (auto_pb && rows) { // (the room check above holds these bounds already; an explicit request may not)
+        pb = rpb;
+        if (l <= 32 && pb + 1 > l) pb = l > 1 ? l - 1 : 1;
+        else if (l > 32 && pb + 32 > l) pb = l - 32;
+    } else if (auto_pb) {
         if (l <= 32 && big) {
-            // large index, 32-bit signatures: prefix = all signature bits but three ("fine" tables: the bucket
+            // large index, 32-bit signatures: prefix = all signature bits but three (digest directories: the bucket
             // table also holds size and partner digest of the (at most eight) key groups of a bucket, so a
             // lookup lands on the reference's equal range without scanning, and on nothing at all when the
             // range is one chance entry); 16 B x 2^(l-3) per list
@@ -123,26 +134,27 @@ void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries)
             if (pb < 8) pb = 8;
         }
     }
-    if (rows && auto_pb) {
-        // bucket rows: about 11 entries per 128-byte row of 20; 32-bit signatures: at most 16 signature values per row
-        pb = 1;
-        while (pb < 30 && (double)n_entries / (double)(1ull << pb) > 11.5) pb++;
-        if (l <= 32) {
-            if (pb + 4 < l) pb = l - 4;
-            if (pb + 1 > l) pb = l > 1 ? l - 1 : 1;
-        } else if (pb + 32 > l) pb = l - 32;
-    }
     if (pb > l) pb = l; // a signature has seedl bits (two segments of seedl/4 bases)
     if (pb > 30) pb = 30;
     if (pb < 1) pb = 1;
-    ctx->pb = pb;
     uint32_t pshift, fshift, fbits, pbits;
     rh_index_geometry(l, pb, &pshift, &fshift, &fbits, &pbits);
-    if (want == 1) ctx->fine = 0;
-    else if (rows && ((l <= 32 && l >= pb && l - pb >= 1 && l - pb <= 4) || (l > 32 && pb + 32 <= l))) ctx->fine = 3;
-    else if (rh_is_fine(l, pb)) ctx->fine = 1;
-    else if (pbits == 0 && (want == 2 || (auto_pb && big))) ctx->fine = 2;
-    else ctx->fine = 0;
+    // rows: at most 16 key groups (signature values) per row
+    const bool row_groups = l <= 32 ? (l >= pb && l - pb >= 1 && l - pb <= 4) : pb + 32 <= l;
+    const RhLayout layout = want_starts ? RH_LAYOUT_STARTS
+                          : (rows && row_groups) ? RH_LAYOUT_ROWS
+                          : rh_digest_geometry(l, pb) ? RH_LAYOUT_DIGEST
+                          : (pbits == 0 && (want_dir || (auto_pb && big))) ? RH_LAYOUT_FINGERPRINT
+                          : RH_LAYOUT_STARTS;
+    return {pb, layout};
+}
+
+void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries)
+{
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const RhTables t = rh_plan_tables(ctx->prm.seedl, ctx->prm.table_kind, ctx->prm.prefix_bits, n_entries, total_b, ctx->no_rows);
+    ctx->pb = t.pb; ctx->layout = t.layout;
 }
 
 __device__ __forceinline__ uint64_t dev_text_bits(const uint64_t *__restrict__ T, uint64_t i, unsigned nb)
@@ -191,7 +203,7 @@ __global__ void entries_kernel(const K *__restrict__ sign, const uint32_t *__res
         for (uint64_t q = (uint64_t)p + 1; q <= nbuckets; ++q) bkt[q] = (uint32_t)n;
 }
 
-// fine bucket table: uint4 {start, 96 bits = 8 x {size:4, digest:8}} per bucket, field g = key group g
+// digest directory (RH_LAYOUT_DIGEST): uint4 {start, 96 bits = 8 x {size:4, digest:8}} per bucket, field g = key group g
 // (= signature value g of the bucket).  size 15 means "15 or more": the matcher then finds that group's
 // bounds by binary search inside the bucket.  digest = the leading (at most 8) partner-signature bits of
 // the group's first entry: for a group of one entry the matcher evaluates the seed popcount filter on
@@ -214,7 +226,7 @@ __global__ void fine_table_kernel(const uint32_t *__restrict__ bkt, const uint2 
 #pragma unroll
             for (int g = 0; g < 8; ++g) if (k == (uint32_t)g) f = fld[g];
             if ((f & 15u) == 0) f = (((x & pmask) >> (pbits - dbits)) << 4) | 1u;
-            else if ((f & 15u) < RH_FINE_SAT) f++;
+            else if ((f & 15u) < RH_DIGEST_SAT) f++;
 #pragma unroll
             for (int g = 0; g < 8; ++g) if (k == (uint32_t)g) fld[g] = f;
         }
@@ -253,13 +265,8 @@ __global__ void fp_table_kernel(const uint32_t *__restrict__ bkt, const uint2 *_
 }
 
 // ---------------------------------------------------------------------------
-// bucket rows (table kind 3): one 128-byte row per bucket holds the directory AND the entries, so that a
-// lookup is ONE line of HBM, fetched by eight lanes with one coalesced request (match_lists_rows).
-//   simple bucket (at most RH_ROW_CAP entries, every key group at most 15):
-//     u64  sixteen 4-bit counts, nibble g = entries of key group g (= signature value g of the bucket)
-//     then the entries in list order, 6 bytes each: u16 leading partner-signature bits, u32 position
-//   complex bucket: u64 all ones, u32 first entry in the overflow array, u32 entries, sixteen u8 group counts
-//     (255 = "255 or more": bounds by binary search); its entries live in the overflow array as {key, pos}
+// bucket rows (RH_LAYOUT_ROWS, format: real_hip_internal.h): one 128-byte row per bucket holds the directory AND the
+// entries, so that a lookup is ONE line of HBM, fetched by eight lanes with one coalesced request (match_lists_rows).
 // ---------------------------------------------------------------------------
 // (pbits == 0: wide signatures, the entries hold a 32-bit key; key group = its leading four bits)
 __device__ __forceinline__ void bucket_groups(const uint2 *__restrict__ ent, uint32_t start, uint32_t end, uint32_t pbits, uint32_t gmask,
@@ -307,27 +314,25 @@ __global__ void rows_fill_kernel(const uint32_t *__restrict__ bkt, const uint2 *
     uint32_t cnt[16];
     bucket_groups(ent, start, end, pbits, fbits >= 32 ? 15u : (1u << fbits) - 1, cnt);
     if (oc) { // complex
-        w[0] = w[1] = 0xffffffffu;
-        w[2] = os; w[3] = c;
+        rh_row_set_complex(w, os, c);
 #pragma unroll
-        for (int g = 0; g < 16; ++g) w[4 + (g >> 2)] |= (cnt[g] < 255 ? cnt[g] : 255u) << (8 * (g & 3));
+        for (int g = 0; g < 16; ++g) rh_row_set_count8(w, g, cnt[g]);
         for (uint32_t j = 0; j < c; ++j) ovf[os + j] = ent[start + j];
     } else {
 #pragma unroll
-        for (int g = 0; g < 16; ++g) w[g >> 3] |= cnt[g] << (4 * (g & 7));
+        for (int g = 0; g < 16; ++g) rh_row_set_count4(w, g, cnt[g]);
         const uint32_t p16 = pbits < 16 ? pbits : 16;
         const uint32_t pmask = pbits ? ((1u << pbits) - 1) : 0u;
         for (uint32_t j = 0; j < c; ++j) {
             const uint2 e = ent[start + j];
             const uint32_t key = pbits ? ((e.x & pmask) >> (pbits - p16)) : rh_fp16(e.x);
-            // 6 bytes at byte 8 + 6j: halfwords 4+3j (key), 5+3j (pos low), 6+3j (pos high)
             const uint32_t hw[3] = {key & 0xffffu, e.y & 0xffffu, e.y >> 16};
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
-                const uint32_t h = 4 + 3 * j + t;
+                const uint32_t h = rh_row_entry_hw(j) + t;
                 const uint32_t v = hw[t] << (16 * (h & 1));
 #pragma unroll
-                for (int i = 2; i < 32; ++i) if ((h >> 1) == (uint32_t)i) w[i] |= v;
+                for (int i = 2; i < 32; ++i) if ((h >> 1) == (uint32_t)i) w[i] |= v; // (w stays in registers)
             }
         }
     }
@@ -343,11 +348,7 @@ __global__ void rows_sizes_kernel(const uint4 *__restrict__ rows, uint64_t nbuck
     uint32_t c = 0;
     if (p < nbuckets) {
         const uint4 h = rows[p * 8];
-        if (h.x == 0xffffffffu && h.y == 0xffffffffu) c = h.w;
-        else {
-            const uint64_t hd = (uint64_t)h.x | ((uint64_t)h.y << 32);
-            for (int g = 0; g < 16; ++g) c += (uint32_t)(hd >> (4 * g)) & 15u;
-        }
+        c = rh_row_complex(h.x, h.y) ? h.w : rh_row_group4(h.x, h.y, 16).x;
     }
     size[p] = c;
 }
@@ -358,12 +359,10 @@ __global__ void rows_unpack_kernel(const uint4 *__restrict__ rows, const uint2 *
     if (p >= nbuckets) return;
     const uint32_t *w = reinterpret_cast<const uint32_t *>(rows + p * 8);
     const uint32_t o = off[p], c = off[p + 1] - o;
-    if (w[0] == 0xffffffffu && w[1] == 0xffffffffu) {
+    if (rh_row_complex(w[0], w[1])) {
         for (uint32_t j = 0; j < c; ++j) out[o + j] = ovf[w[2] + j];
     } else {
-        const uint16_t *hw = reinterpret_cast<const uint16_t *>(w);
-        for (uint32_t j = 0; j < c; ++j)
-            out[o + j] = make_uint2(hw[4 + 3 * j], (uint32_t)hw[5 + 3 * j] | ((uint32_t)hw[6 + 3 * j] << 16));
+        for (uint32_t j = 0; j < c; ++j) out[o + j] = rh_row_entry(w, j);
     }
 }
 
@@ -440,7 +439,7 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
         else { rocprim::double_buffer<uint64_t> k(nullptr, nullptr); e = sort_pairs<uint64_t>(nullptr, sort_tmp, k, v, n, l, ctx->stream); }
         if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "radix sort (size query)", e);
     }
-    const bool rows = ctx->fine == 3;
+    const bool rows = ctx->layout == RH_LAYOUT_ROWS;
     if (rows) {
         hipError_t e = rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, nb1, rocprim::plus<uint32_t>(), ctx->stream);
         if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "scan (size query)", e);
@@ -451,7 +450,7 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
     size_t x = need_sort ? pair + al(sort_tmp ? sort_tmp : 8) : 0;
     if (rows && !need_sort) x = al(nn * sizeof(uint2)); // (host-built lists: no pair A, the entries get room of their own)
     const size_t o_bkt = o_x + x;
-    const size_t o_ocnt = o_bkt + (ctx->fine ? al(nb1 * 4) : 0);       // (kind 0 keeps the bucket starts: an allocation of their own)
+    const size_t o_ocnt = o_bkt + (ctx->layout != RH_LAYOUT_STARTS ? al(nb1 * 4) : 0);       // (bucket starts keep them: an allocation of their own)
     const size_t o_ostart = o_ocnt + (rows ? al(nb1 * 4) : 0);
     const size_t o_scan = o_ostart + (rows ? al(nb1 * 4) : 0);
     const size_t total = o_scan + al(scan_tmp ? scan_tmp : 8);
@@ -461,7 +460,7 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
     S.keys_b = base + o_keys_b; S.vals_b = (uint32_t *)(base + o_vals_b);
     S.keys_a = base + o_x; S.vals_x = (uint32_t *)(base + o_x + nn * sig_bytes); S.sort_tmp = base + o_x + pair; S.sort_tmp_bytes = sort_tmp;
     S.ent = rows ? (uint2 *)(base + o_x) : nullptr; // (the device build moves it to the pair that is free after the sort)
-    S.bkt = ctx->fine ? (uint32_t *)(base + o_bkt) : nullptr;
+    S.bkt = ctx->layout != RH_LAYOUT_STARTS ? (uint32_t *)(base + o_bkt) : nullptr;
     S.ocnt = rows ? (uint32_t *)(base + o_ocnt) : nullptr;
     S.ostart = rows ? (uint32_t *)(base + o_ostart) : nullptr;
     S.scan_tmp = base + o_scan; S.scan_tmp_bytes = scan_tmp;
@@ -476,7 +475,7 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
     uint32_t pshift, fshift, fbits, pbits;
     rh_index_geometry(l, pb, &pshift, &fshift, &fbits, &pbits);
     const uint32_t nb = 1u << pb;
-    const bool rows = ctx->fine == 3;
+    const bool rows = ctx->layout == RH_LAYOUT_ROWS;
     int rc;
     // The tables of a previous block stay allocated when they have about the size this block needs (the next block of
     // a genome, the next file of a directory: same layout, and hipMalloc of 200 GB costs seconds); otherwise they go
@@ -487,7 +486,7 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
         return rh_reserve(ctx, b, need);
     };
     if (!n) {
-        const size_t esz = rows ? 128 : (ctx->fine ? 16 : 4);
+        const size_t esz = rows ? 128 : (ctx->layout != RH_LAYOUT_STARTS ? 16 : 4);
         if ((rc = fit(ctx->bkt[list], ((size_t)nb + 1) * esz))) return rc;
         if ((rc = fit(ctx->ent[list], sizeof(uint2)))) return rc;
         RH_HIP(ctx, hipMemsetAsync(ctx->bkt[list].p, 0, ((size_t)nb + 1) * esz, ctx->stream));
@@ -499,7 +498,7 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
         d_ent = (uint2 *)ctx->ent[list].p;
     }
     uint32_t *d_bkt = S.bkt;
-    if (!ctx->fine) {
+    if (ctx->layout == RH_LAYOUT_STARTS) {
         if ((rc = fit(ctx->bkt[list], ((size_t)nb + 1) * 4))) return rc;
         d_bkt = (uint32_t *)ctx->bkt[list].p;
     }
@@ -532,9 +531,9 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
         RH_HIP(ctx, hipGetLastError());
         return REAL_HIP_OK;
     }
-    if (ctx->fine) {
+    if (ctx->layout != RH_LAYOUT_STARTS) {
         if ((rc = fit(ctx->bkt[list], ((size_t)nb + 1) * sizeof(uint4)))) return rc;
-        if (ctx->fine == 1)
+        if (ctx->layout == RH_LAYOUT_DIGEST)
             hipLaunchKernelGGL(fine_table_kernel, dim3((unsigned)(((uint64_t)nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream,
                                (const uint32_t *)d_bkt, (const uint2 *)d_ent, (uint64_t)nb, pbits, fbits, (uint4 *)ctx->bkt[list].p);
         else
@@ -554,7 +553,7 @@ int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const si
 {
     const double t0 = rh_now_ms();
     BuildScratch S(ctx);
-    const bool rows = ctx->fine == 3; // bucket rows: the lists are sorted once more, by the mixed signature (sort_list)
+    const bool rows = ctx->layout == RH_LAYOUT_ROWS; // bucket rows: the lists are sorted once more, by the mixed signature (sort_list)
     int rc = plan_scratch(ctx, S, n, sig_bytes, rows);
     if (rc) return rc;
     for (int k = 0; k < 6; ++k) {
@@ -626,7 +625,7 @@ static int sort_list(real_hip_ctx *ctx, BuildScratch &S, int list, const uint32_
     const uint32_t l = ctx->prm.seedl;
     const void *d_sign = S.keys_b;
     const uint32_t *d_pos = S.vals_b;
-    const bool mix = ctx->fine == 3;
+    const bool mix = ctx->layout == RH_LAYOUT_ROWS;
     if (n) {
         rh_time_begin(ctx, ctx->stream, REAL_HIP_K_INDEX);
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
@@ -703,7 +702,7 @@ int rh_index_build_device(real_hip_ctx *ctx, uint64_t first_window, uint64_t max
         for (int k = 0; k < 6 && !rc; ++k)
             rc = (l <= 32) ? sort_list<uint32_t>(ctx, S, k, d_wpos, first_window, cnt) : sort_list<uint64_t>(ctx, S, k, d_wpos, first_window, cnt);
         if (!rc) RH_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (before the scratch goes)
-        if (rc == REAL_HIP_E_NOMEM && ctx->fine == 3 && ctx->prm.table_kind == 0 && !ctx->no_rows && attempt == 0) {
+        if (rc == REAL_HIP_E_NOMEM && ctx->layout == RH_LAYOUT_ROWS && ctx->prm.table_kind == 0 && !ctx->no_rows && attempt == 0) {
             // the rows did not fit after all (memory held by others): once more with directory tables
             (void)hipStreamSynchronize(ctx->stream);
             for (int j = 0; j < 6; ++j) { rh_release(ctx, ctx->ent[j]); rh_release(ctx, ctx->bkt[j]); }
@@ -947,7 +946,7 @@ int rh_index_export(real_hip_ctx *ctx, int list, void *h_sign, uint32_t *h_pos)
     if ((rc = rh_reserve(ctx, ctx->vals_a, n * 4))) return rc;
     ScopedBuf unpacked(ctx); // bucket rows: the entries in list order first
     const uint2 *d_ent = (const uint2 *)ctx->ent[list].p;
-    const bool rows = ctx->fine == 3;
+    const bool rows = ctx->layout == RH_LAYOUT_ROWS;
     size_t sort_tmp = 0;
     if (rows) {
         // ... and that order is the one of the mixed signatures (real_hip_internal.h: rh_mix32): signatures and positions are

@@ -6,7 +6,7 @@
 #define RH_DECL_W(N)                                                                    \
     void rh_launch_match_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all);         \
     void rh_launch_match2_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all);        \
-    uint32_t rh_stage_bytes_w##N(int tk);
+    uint32_t rh_stage_bytes_w##N(const DevIndex &ix);
 RH_DECL_W(1) RH_DECL_W(2) RH_DECL_W(3) RH_DECL_W(4) RH_DECL_W(5) RH_DECL_W(6) RH_DECL_W(7) RH_DECL_W(8) RH_DECL_W(9) RH_DECL_W(10)
 void rh_launch_match_wave(real_hip_ctx *ctx, const MatchArgs &a, bool all);
 
@@ -15,7 +15,7 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &args, bool all, int stat
     if (!args.b.n_reads) return REAL_HIP_OK;
     MatchArgs a = args;
     typedef void (*launch_fn)(real_hip_ctx *, const MatchArgs &, bool);
-    typedef uint32_t (*stage_fn)(int);
+    typedef uint32_t (*stage_fn)(const DevIndex &);
     static const launch_fn launch[RH_MAXW] = {rh_launch_match_w1, rh_launch_match_w2, rh_launch_match_w3, rh_launch_match_w4, rh_launch_match_w5,
                                               rh_launch_match_w6, rh_launch_match_w7, rh_launch_match_w8, rh_launch_match_w9, rh_launch_match_w10};
     static const launch_fn launch2[RH_MAXW] = {rh_launch_match2_w1, rh_launch_match2_w2, rh_launch_match2_w3, rh_launch_match2_w4, rh_launch_match2_w5,
@@ -26,7 +26,7 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &args, bool all, int stat
     int rc;
     { // reads a wave stages at a time: their bytes (+ alignment skew, pad, one dword of over-read) fit its LDS region
         const uint32_t maxlen = (a.b.off || a.b.upatl > 32u * a.b.W) ? 32u * a.b.W : a.b.upatl;
-        const uint32_t region = stage[a.b.W - 1](a.ix.fine == 3 ? 3 : (a.ix.fine ? 1 : 0));
+        const uint32_t region = stage[a.b.W - 1](a.ix);
         uint32_t gl = 64;
         while (gl > 1 && (uint64_t)gl * maxlen + 16 + 32 > region) gl >>= 1;
         a.b.gl = gl;

@@ -57,26 +57,22 @@ __device__ __forceinline__ WaveRange wave_lookup(const MatchArgs &a, uint64_t sh
     const uint32_t pbits = a.ix.pbits;
     R.partner = pbits ? (uint32_t)(sb >> (l - pbits)) : 0u;
     const uint32_t prefix = (uint32_t)(sa >> a.ix.pshift);
-    if (a.ix.fine != 3) {
+    if (a.ix.layout != RH_LAYOUT_ROWS) {
         // entry arrays in list order behind bucket starts (u32, or the .x of the 16-byte directory entries)
         uint32_t lo, hi;
-        if (a.ix.fine == 0) { lo = a.ix.bkt[la][prefix]; hi = a.ix.bkt[la][prefix + 1]; }
+        if (a.ix.layout == RH_LAYOUT_STARTS) { lo = a.ix.bkt[la][prefix]; hi = a.ix.bkt[la][prefix + 1]; }
         else {
             const uint4 *B = reinterpret_cast<const uint4 *>(a.ix.bkt[la]);
             lo = B[prefix].x; hi = B[prefix + 1].x;
         }
         const uint32_t f = (uint32_t)((sa >> a.ix.fshift) & ((a.ix.fbits >= 32) ? 0xffffffffull : ((1ull << a.ix.fbits) - 1)));
         // bounds of the key inside the bucket (entries of a bucket are sorted by key)
-        uint32_t x = lo, y = hi;
-        while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((R.E[mid].x >> pbits) < f) x = mid + 1; else y = mid; }
-        const uint32_t first = x;
-        y = hi;
-        while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((R.E[mid].x >> pbits) <= f) x = mid + 1; else y = mid; }
-        R.lo = first; R.cnt = x - first; R.key = f; R.mode = 0;
+        const uint2 kr = key_group_range(R.E, lo, hi, pbits, f);
+        R.lo = kr.x; R.cnt = kr.y; R.key = f; R.mode = 0;
         return R;
     }
     // bucket rows: addressed by the mixed signature (real_hip_internal.h: rh_mix32 / rh_mix64)
-    const bool wide = pbits == 0;
+    const bool wide = rh_wide_entries(a.ix);
     uint32_t g, bucket;
     if (!wide) {
         const uint32_t gbits = a.ix.fbits;
@@ -90,32 +86,17 @@ __device__ __forceinline__ WaveRange wave_lookup(const MatchArgs &a, uint64_t sh
         g = R.key >> 28;
     }
     const uint32_t *row = a.ix.bkt[la] + (uint64_t)bucket * 32;
-    const uint32_t h0 = row[0], h1 = row[1];
-    if ((h0 & h1) != 0xffffffffu) { // simple bucket: sixteen 4-bit counts, entries of 6 bytes
-        uint32_t base = 0, cnt = 0;
-        for (uint32_t q = 0; q < 16; ++q) {
-            const uint32_t c = ((q < 8 ? h0 : h1) >> (4 * (q & 7))) & 15u;
-            if (q < g) base += c;
-            if (q == g) cnt = c;
-        }
-        R.row = row; R.lo = base; R.cnt = cnt; R.mode = wide ? 2u : 1u;
+    if (!rh_row_complex(row[0], row[1])) { // simple bucket: sixteen 4-bit counts, entries of 6 bytes
+        const uint2 gr = rh_row_group4(row[0], row[1], g);
+        R.row = row; R.lo = gr.x; R.cnt = gr.y; R.mode = wide ? 2u : 1u;
     } else { // complex bucket: entries in the overflow array, sixteen 8-bit counts (255 = "255 or more")
         const uint32_t o0 = row[2], tot = row[3];
-        uint32_t base = 0, cnt = 0;
-        bool sat = false;
-        for (uint32_t q = 0; q <= g; ++q) {
-            const uint32_t c = (row[4 + (q >> 2)] >> (8 * (q & 3))) & 255u;
-            sat = sat || c == 255u;
-            if (q < g) base += c; else cnt = c;
-        }
-        uint32_t first = o0 + base;
+        bool sat;
+        const uint2 gr = rh_row_group8(row, g, &sat);
+        uint32_t first = o0 + gr.x, cnt = gr.y;
         if (sat) { // bounds of the key group by binary search
-            const uint32_t gs = wide ? 28u : pbits;
-            uint32_t x = o0, y = o0 + tot;
-            while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((R.E[mid].x >> gs) < g) x = mid + 1; else y = mid; }
-            first = x; y = o0 + tot;
-            while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((R.E[mid].x >> gs) <= g) x = mid + 1; else y = mid; }
-            cnt = x - first;
+            const uint2 kr = key_group_range(R.E, o0, o0 + tot, wide ? 28u : pbits, g);
+            first = kr.x; cnt = kr.y;
         }
         R.lo = first; R.cnt = cnt; R.mode = wide ? 4u : 3u;
     }
@@ -305,11 +286,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void m
             const uint32_t so = inv ? (patl - l) : 0u; // RestMatch::getMatchOffset, RestMatch.hpp:84-89
             uint32_t rpos = 0;
             if (cand) {
-                if (R.mode == 1 || R.mode == 2) { // 6 bytes at halfword 4 + 3 * (lo + i) of the row
-                    const uint32_t h = 4 + 3 * (R.lo + i);
-                    const uint32_t d0 = R.row[h >> 1], d1 = R.row[(h >> 1) + 1];
-                    const uint32_t key = (h & 1) ? (d0 >> 16) : (d0 & 0xffffu);
-                    rpos = (h & 1) ? d1 : ((d0 >> 16) | (d1 << 16));
+                if (R.mode == 1 || R.mode == 2) { // an entry of the row
+                    const uint2 re = rh_row_entry(R.row, R.lo + i);
+                    const uint32_t key = re.x;
+                    rpos = re.y;
                     const uint32_t x = key ^ (R.key >> (pbits - p16));
                     cand = R.mode == 2 ? (key == rh_fp16(R.key)) : (__popc(((x >> 1) | x) & 0x5555u) <= a.seedkmax);
                 } else {

@@ -395,7 +395,7 @@ extern "C" int real_hip_index_table_kind(const real_hip_ctx *ctx, uint32_t *kind
 {
     if (!ctx || !kind) return REAL_HIP_E_INVALID;
     if (!ctx->have_index) return REAL_HIP_E_STATE;
-    *kind = (uint32_t)ctx->fine;
+    *kind = (uint32_t)ctx->layout;
     return REAL_HIP_OK;
 }
 
@@ -405,7 +405,7 @@ extern "C" int real_hip_index_download(real_hip_ctx *ctx, int list, uint32_t *en
     if (!ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "no index", hipSuccess);
     if (list < 0 || list > 5) return rh_fail(ctx, REAL_HIP_E_INVALID, "list", hipSuccess);
     const uint64_t n = ctx->n_entries;
-    if (ctx->fine == 3) { // bucket rows: entries and bucket starts by an ordered traversal of the rows
+    if (ctx->layout == RH_LAYOUT_ROWS) { // bucket rows: entries and bucket starts by an ordered traversal of the rows
         ScopedBuf e(ctx), st(ctx);
         int rc;
         if ((rc = rh_reserve(ctx, e, (n ? n : 1) * sizeof(uint2)))) return rc;
@@ -421,7 +421,7 @@ extern "C" int real_hip_index_download(real_hip_ctx *ctx, int list, uint32_t *en
     if (n && entries) RH_HIP(ctx, hipMemcpy(entries, ctx->ent[list].p, n * sizeof(uint2), hipMemcpyDeviceToHost));
     if (bucket) {
         const size_t nbk = ((size_t)1 << ctx->pb) + 1;
-        if (ctx->fine) RH_HIP(ctx, hipMemcpy2D(bucket, 4, ctx->bkt[list].p, 16, 4, nbk, hipMemcpyDeviceToHost)); // the .x of every uint4 (kinds 1, 2)
+        if (ctx->layout != RH_LAYOUT_STARTS) RH_HIP(ctx, hipMemcpy2D(bucket, 4, ctx->bkt[list].p, 16, 4, nbk, hipMemcpyDeviceToHost)); // the .x of every uint4 (directories)
         else RH_HIP(ctx, hipMemcpy(bucket, ctx->bkt[list].p, nbk * 4, hipMemcpyDeviceToHost));
     }
     return REAL_HIP_OK;
@@ -548,7 +548,7 @@ static void fill_args(real_hip_ctx *ctx, const Staged &s, uint64_t n, MatchArgs 
     for (int k = 0; k < 6; ++k) { a.ix.ent[k] = (const uint2 *)ctx->ent[k].p; a.ix.bkt[k] = (const uint32_t *)ctx->bkt[k].p; }
     a.ix.n = ctx->n_entries; a.ix.pb = pb;
     rh_index_geometry(l, pb, &a.ix.pshift, &a.ix.fshift, &a.ix.fbits, &a.ix.pbits);
-    a.ix.fine = (uint32_t)ctx->fine;
+    a.ix.layout = ctx->layout;
     a.b.bases = s.bases; a.b.qual = ctx->prm.scores ? s.qual : nullptr; a.b.off = s.off;
     a.b.n_reads = n; a.b.upatl = s.upatl; a.b.W = s.W; a.b.maxpatl = s.maxpatl_declared ? REAL_HIP_MAX_PATL_LONG : s.maxpatl;
     a.b.packed = s.packed; a.b.nflags = s.nflags;

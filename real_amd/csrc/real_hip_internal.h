@@ -27,6 +27,10 @@ struct DevText {
     uint32_t fileid;
 };
 
+// The resident index layout, what the bucket tables bkt[] hold (the values real_hip_index_table_kind reports): 2^pb + 1 bucket
+// starts (u32); a digest or a fingerprint directory (uint4 per bucket, below); one 128-byte row per bucket (format below)
+enum RhLayout : uint32_t { RH_LAYOUT_STARTS = 0, RH_LAYOUT_DIGEST = 1, RH_LAYOUT_FINGERPRINT = 2, RH_LAYOUT_ROWS = 3 };
+
 // One entry of a sorted list: {fingerprint, window start}.  The fingerprint is
 // 32 bits of the signature just below the bucket prefix; entries of a bucket
 // are in the reference's list order (signature ascending, stable => position
@@ -34,30 +38,80 @@ struct DevText {
 // reference's equal range appear in the reference's order.
 struct DevIndex {
     const uint2    *ent[6];
-    const uint32_t *bkt[6]; // 2^pb + 1 bucket starts (u32), or in fine mode uint4 {start, 8 x {size:4, partner digest:8}}
+    const uint32_t *bkt[6]; // bucket tables of the layout
     uint64_t n;
     uint32_t pb;     // prefix bits
     uint32_t pshift; // sig_bits - pb: prefix = sign >> pshift
     uint32_t fshift; // entry.x = [fbits of (sign >> fshift)] [pbits of the partner signature's top bits]
     uint32_t fbits;  // signature bits kept in the entry (all sig_bits - pb of them when that is <= 30)
     uint32_t pbits;  // partner-signature bits kept in the entry (even; 0 when the signature needs all 32)
-    uint32_t fine;   // bucket table kind: 0 u32 starts; 1 "fine": size + partner digest of every key group of the bucket
-                     // (fbits <= 3); 2 fingerprints of the bucket's first entries (pbits == 0, wide signatures);
-                     // 3 bucket rows: bkt[] holds one 128-byte row per bucket (directory + entries), ent[] the overflow
+    RhLayout layout;
 };
+// wide signatures (pbits == 0): the entries hold a 32-bit key instead of key group + partner bits
+static inline __host__ __device__ bool rh_wide_entries(const DevIndex &ix) { return ix.pbits == 0; }
 
-// "fine" bucket tables: the prefix is all signature bits but one to three, so a bucket has at most eight key
-// groups (= signature values) and its 16-byte table entry describes each of them
-static inline bool rh_is_fine(uint32_t l, uint32_t pb) { return l >= pb && l - pb >= 1 && l - pb <= 3; }
-#define RH_FINE_SAT 15u /* group size field: 15 = "15 or more", bounds by binary search */
-// fingerprint tables: uint4 {start, count:8 | 8 x fingerprint:11}: the first eight entries of the bucket by an
+// digest directories: uint4 {start, 8 x {size:4, partner digest:8}}: the prefix is all signature bits but one to three, so a
+// bucket has at most eight key groups (= signature values) and its 16-byte table entry describes each of them
+static inline bool rh_digest_geometry(uint32_t l, uint32_t pb) { return l >= pb && l - pb >= 1 && l - pb <= 3; }
+#define RH_DIGEST_SAT 15u /* group size field: 15 = "15 or more", bounds by binary search */
+// fingerprint directories: uint4 {start, count:8 | 8 x fingerprint:11}: the first eight entries of the bucket by an
 // 11-bit hash of their 32-bit key; a lookup whose own fingerprint is not among them reads no entry at all
-#define RH_ROW_CAP 20u /* entries a bucket row holds (table kind 3) */
 #define RH_FP_SLOTS 8u
 static inline __host__ __device__ uint32_t rh_fp11(uint32_t key) { return (key * 0x9E3779B1u) >> 21; }
-// bucket rows of wide signatures (entries hold a 32-bit key): key group = the key's leading four bits, the row keeps a
-// 16-bit fingerprint of the other 28
+
+// the equal range {first, count} of key group `key` among the entries E[lo, hi) of a bucket (sorted by e.x >> shift)
+static inline __host__ __device__ uint2 key_group_range(const uint2 *E, uint32_t lo, uint32_t hi, uint32_t shift, uint32_t key)
+{
+    uint32_t x = lo, y = hi;
+    while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((E[mid].x >> shift) < key) x = mid + 1; else y = mid; }
+    const uint32_t first = x;
+    for (y = hi; x < y;) { const uint32_t mid = x + ((y - x) >> 1); if ((E[mid].x >> shift) <= key) x = mid + 1; else y = mid; }
+    return make_uint2(first, x - first);
+}
+
+// ---- bucket rows (RH_LAYOUT_ROWS): one row of 32 u32 words per bucket ----------------------------------------
+//   simple row (at most RH_ROW_CAP entries, every key group at most 15):
+//     words 0-1   sixteen 4-bit counts, nibble g = entries of key group g (= signature value g of the bucket)
+//     then the entries in list order, 6 bytes each from halfword 4 on: u16 key, u32 position (low half first)
+//   complex row: words 0-1 all ones, word 2 first entry in the overflow array, word 3 entries, words 4-7 sixteen
+//     8-bit group counts (RH_ROW_SAT = "255 or more": bounds by binary search); its entries live in the overflow
+//     array as {key, pos}
+// The key of a row entry is the leading 16 partner-signature bits (narrow), or rh_fp16 of the 32-bit key (wide: key
+// group = the key's leading four bits).
+#define RH_ROW_CAP 20u /* entries a simple row holds */
+#define RH_ROW_SAT 255u
 static inline __host__ __device__ uint32_t rh_fp16(uint32_t key) { return ((key & 0x0fffffffu) * 0x9E3779B1u) >> 16; }
+static inline __host__ __device__ bool rh_row_complex(uint32_t h0, uint32_t h1) { return (h0 & h1) == 0xffffffffu; }
+// simple row: {first entry, count} of key group g from the 4-bit counts (g = 16: {all entries, 0})
+static inline __host__ __device__ uint2 rh_row_group4(uint32_t h0, uint32_t h1, uint32_t g)
+{
+    uint32_t base = 0, cnt = 0;
+    for (uint32_t q = 0; q < 16; ++q) { const uint32_t c = ((q < 8 ? h0 : h1) >> (4 * (q & 7))) & 15u; if (q < g) base += c; if (q == g) cnt = c; }
+    return make_uint2(base, cnt);
+}
+// complex row: {first entry relative to the overflow start, count} of key group g from the 8-bit counts; *sat: a count of
+// key group g or one in front of it is saturated
+static inline __host__ __device__ uint2 rh_row_group8(const uint32_t *row, uint32_t g, bool *sat)
+{
+    uint32_t base = 0, cnt = 0;
+    bool s = false;
+    for (uint32_t q = 0; q <= g; ++q) { const uint32_t c = (row[4 + (q >> 2)] >> (8 * (q & 3))) & 255u; s = s || c == RH_ROW_SAT; if (q < g) base += c; else cnt = c; }
+    *sat = s;
+    return make_uint2(base, cnt);
+}
+// encoding a row into its 32 words w[] (zeroed): the header of a complex row, the count c of key group g
+static inline __host__ __device__ void rh_row_set_complex(uint32_t *w, uint32_t first, uint32_t total) { w[0] = w[1] = 0xffffffffu; w[2] = first; w[3] = total; }
+static inline __host__ __device__ void rh_row_set_count4(uint32_t *w, uint32_t g, uint32_t c) { w[g >> 3] |= c << (4 * (g & 7)); }
+static inline __host__ __device__ void rh_row_set_count8(uint32_t *w, uint32_t g, uint32_t c) { w[4 + (g >> 2)] |= (c < RH_ROW_SAT ? c : RH_ROW_SAT) << (8 * (g & 3)); }
+// simple row: halfword of entry j (its key; the position follows in the next two)
+static inline __host__ __device__ uint32_t rh_row_entry_hw(uint32_t j) { return 4 + 3 * j; }
+// simple row: {key, position} of entry j
+static inline __host__ __device__ uint2 rh_row_entry(const uint32_t *row, uint32_t j)
+{
+    const uint32_t h = rh_row_entry_hw(j);
+    const uint32_t d0 = row[h >> 1], d1 = row[(h >> 1) + 1];
+    return make_uint2((h & 1) ? (d0 >> 16) : (d0 & 0xffffu), (h & 1) ? d1 : ((d0 >> 16) | (d1 << 16)));
+}
 
 // Bucket rows are addressed through a bijection of the signature space: mixed = sign * odd constant mod 2^seedl.  The row
 // of a signature is the leading bits of the MIXED value, its key group the bits below.  A genome's signatures are far from
@@ -163,7 +217,7 @@ struct real_hip_ctx {
     DevBuf ent[6], bkt[6];
     uint64_t n_entries = 0;
     uint32_t pb = 0;
-    int fine = 0;      // bucket table kind, see DevIndex::fine
+    RhLayout layout = RH_LAYOUT_STARTS;
     bool no_rows = false; // bucket rows did not fit the device memory once: stay with directory tables
     bool have_index = false;
 
@@ -247,5 +301,8 @@ int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);
 int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const sign[6], const uint32_t *const pos[6], unsigned sig_bytes);
 int rh_index_build_device(real_hip_ctx *ctx, uint64_t first_window, uint64_t max_entries,
                           uint64_t *n_entries, int *have_next);
-void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries); // sets ctx->pb and ctx->fine
+// the bucket prefix width and layout of an index of n_entries per list (the ABI request: real_hip_params.table_kind)
+struct RhTables { uint32_t pb; RhLayout layout; };
+RhTables rh_plan_tables(uint32_t seedl, uint32_t request, uint32_t prefix_bits, uint64_t n_entries, uint64_t device_bytes, bool no_rows);
+void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries); // sets ctx->pb and ctx->layout
 int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts);

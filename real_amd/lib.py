@@ -26,6 +26,8 @@ REAL_HIP_MAX_PATL = 320
 REAL_HIP_MAX_PATL_LONG = 16384
 
 K_MATCH_UNIQUE, K_MATCH_ALL, K_ALL_SORT, K_INDEX, K_MATCH_REPEAT, K_PARSE = range(6)
+# resident index layouts, as real_hip_index_table_kind reports them (HipMatcher.table_kind)
+LAYOUT_STARTS, LAYOUT_DIGEST, LAYOUT_FINGERPRINT, LAYOUT_ROWS = range(4)
 
 # every symbol include/real_hip.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = [

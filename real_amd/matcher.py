@@ -129,7 +129,7 @@ class HipMatcher:
         p.seedl, p.seedkmax, p.totalkmax = opts.seedl, opts.seedkmax, opts.totalkmax
         p.scores = int(bool(opts.scores))
         p.prefix_bits = prefix_bits
-        p.table_kind = table_kind          # 0 auto, 1 bucket starts only, 2 directory entries (real_hip.h)
+        p.table_kind = table_kind          # request: 0 auto, 1 bucket starts only, 2 directory entries, 3 bucket rows (real_hip.h)
         p.device = device
         p.filter_mult = opts.filter_mult
         if LL is None:
@@ -224,7 +224,7 @@ class HipMatcher:
         self.n_entries, self.prefix_bits = int(n.value), int(pb.value)
         tk = C.c_uint32(0)
         self._check(self._L.real_hip_index_table_kind(self._h, C.byref(tk)))
-        self.table_kind = int(tk.value)
+        self.table_kind = int(tk.value)   # the layout built: lib.LAYOUT_STARTS .. lib.LAYOUT_ROWS
 
     def index_download(self, k: int, want_buckets: bool = True):
         """device layout of list k: entries (n x {fingerprint, pos}) and bucket starts."""

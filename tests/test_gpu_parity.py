@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from real_amd import host_index, synth
+from real_amd.lib import LAYOUT_DIGEST, LAYOUT_FINGERPRINT, LAYOUT_ROWS, LAYOUT_STARTS
 from real_amd.matcher import AllMatcher, RealOptions, UniqueMatcher, new_unique_info, unpack_info
 
 pytestmark = pytest.mark.gpu
@@ -146,6 +147,8 @@ def test_match_unique_random(ora, seedl, patl, k, scores, pb):
     m = UniqueMatcher(_opts(seedl, seedk, k, scores), prefix_bits=abs(pb) % 100, table_kind=3 if pb >= 100 else (2 if pb < 0 else 0))   # pb < 0: directory tables, pb >= 100: bucket rows
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == (LAYOUT_ROWS if pb >= 100 else LAYOUT_FINGERPRINT if pb < 0 else
+                            LAYOUT_DIGEST if pb and 1 <= seedl - pb <= 3 else LAYOUT_STARTS), m.table_kind
     info, score = m.match_unique(b.bases, b.qual, patl=patl)        # uniform-length batch form
     _compare_unique(info, score, oinfo, oscore, scores)
     c = m.counters()
@@ -191,6 +194,7 @@ def test_match_all_many_hits_per_read(ora, scores, rows):
     m = AllMatcher(_opts(8, 2, 4, scores), prefix_bits=5 if rows else 0, table_kind=3 if rows else 0)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == (LAYOUT_ROWS if rows else LAYOUT_STARTS), m.table_kind
     hits, hoff = m.match_all(b.bases, b.qual, b.offsets, cap=len(ohits) + 8)   # (no overflow retry: work counted once)
     assert np.array_equal(hoff, ooff)
     for x, y in zip(_hits_tuple(hits), _hits_tuple(ohits)):
@@ -215,6 +219,7 @@ def test_saturated_key_groups(ora, kind, pb):
     m = UniqueMatcher(_opts(8, 2, 3, 1), prefix_bits=pb, table_kind=kind)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == (LAYOUT_ROWS if kind == 3 else LAYOUT_DIGEST if pb else LAYOUT_STARTS), m.table_kind
     info, score = m.match_unique(b.bases, b.qual, b.offsets)
     _compare_unique(info, score, oinfo, oscore, 1)
     c = m.counters()
@@ -246,6 +251,7 @@ def test_index_blocks_compose(ora, kind, pb, device_build):
         else:
             sign, pos, n, nxt = host_index.build_lists(g.sym, 16, first, n_list)
             m.set_index_block(sign, pos)
+        assert m.table_kind == (LAYOUT_ROWS if kind == 3 else LAYOUT_DIGEST), m.table_kind   # (auto: 2^13 buckets of a 32 k block)
         first += n
         blocks += 1
         info, score = m.match_unique(b.bases, b.qual, b.offsets, info=info, score=score)
@@ -276,7 +282,7 @@ def test_index_layout_device_equals_host(ora):
             sg, ps = a.index_export(k)
             assert np.array_equal(sg.astype(np.uint64), oix.sign(k)) and np.array_equal(ps, oix.pos(k)), "exported list != reference list"
             osign, opos = oix.sign(k), oix.pos(k)
-            if a.table_kind == 3:
+            if a.table_kind == LAYOUT_ROWS:
                 # bucket rows are addressed by the mixed signature (real_hip_internal.h: rh_mix32 / rh_mix64: sign * odd constant
                 # mod 2^seedl, a bijection): the device list is the reference's list stably re-sorted by it -- equal
                 # signatures stay together and in ascending position, which is all the matcher's candidate order needs
@@ -371,6 +377,7 @@ def test_repeat_cliff_is_bit_exact_and_bounded_in_time(ora, seedl, kind, pb, sco
     m = UniqueMatcher(_opts(seedl, 2, 3, scores), prefix_bits=pb, table_kind=kind)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == {0: LAYOUT_STARTS, 2: LAYOUT_DIGEST, 3: LAYOUT_ROWS}[kind], m.table_kind
     m.match_unique(bases, qual, offsets)                    # warm-up (allocations)
     m.counters(reset=True)
     for k in (0, 4):
@@ -422,7 +429,7 @@ def test_reads_on_few_copy_repeats_stay_with_the_lane_matcher(ora, copies, kind)
     m = UniqueMatcher(_opts(seedl, 2, 3, 1), table_kind=kind, prefix_bits=pb)
     m.set_text_symbols(0, sym, frag)
     m.build_index_block()
-    assert m.table_kind == (3 if kind == 3 else (1 if kind == 2 else 0)), m.table_kind
+    assert m.table_kind == {0: LAYOUT_STARTS, 2: LAYOUT_DIGEST, 3: LAYOUT_ROWS}[kind], m.table_kind
     info, score = m.match_unique(bases, qual, patl=100)
     _compare_unique(info, score, oinfo, oscore, 1)
     c = m.counters()
@@ -439,29 +446,32 @@ def test_reads_on_few_copy_repeats_stay_with_the_lane_matcher(ora, copies, kind)
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 257, 1000])
 def test_batch_sizes_around_the_tile_of_64_reads(ora, n):
     """The waves of the resident grid take tiles of 64 reads from a counter: batches of less than a tile, of whole tiles
-    and with a partial last tile, packed bases and bytes."""
+    and with a partial last tile, packed bases and bytes; with bucket starts (32-base seeds: a request for rows at
+    2^13 buckets gets starts) and with bucket rows (16-base seeds)."""
     g = synth.random_genome(80_000, seed=400, n_frag=2, n_runs=2, repeats=6)
     b = synth.sample_reads(g, n, 100, 0.02, seed=401 + n)
-    p = ora.make_params(seedl=32, seedkmax=2, totalkmax=3, scores=1)
-    oinfo, oscore, octr = _oracle_unique(ora, None, g.sym, g.frag_start, 32, 0, p, b.bases, b.qual, b.offsets)
-    m = UniqueMatcher(_opts(32, 2, 3, 1), table_kind=3, prefix_bits=13)
-    m.set_text_symbols(0, g.sym, g.frag_start)
-    m.build_index_block()
-    info, score = m.match_unique(b.bases, b.qual, patl=100)
-    _compare_unique(info, score, oinfo, oscore, 1)
-    c = m.counters()
-    for kk in ("reads", "lookups", "candidates", "seedpass", "hits"):
-        assert c[kk] == octr[kk], (kk, c[kk], octr[kk])
-    if n % 4 == 0:                                           # the same batch with the bases 2-bit packed
-        q4 = b.bases.reshape(-1, 4)
-        pk = ((q4[:, 0] << 6) | (q4[:, 1] << 4) | (q4[:, 2] << 2) | q4[:, 3]).astype(np.uint8)
-        nfl = np.zeros((n + 7) // 8, dtype=np.uint8)
-        bad = np.nonzero((b.bases.reshape(n, 100) > 3).any(axis=1))[0]
-        np.bitwise_or.at(nfl, bad // 8, (1 << (bad % 8)).astype(np.uint8))
-        pk = ((np.minimum(q4[:, 0], 3) << 6) | (np.minimum(q4[:, 1], 3) << 4) | (np.minimum(q4[:, 2], 3) << 2) | np.minimum(q4[:, 3], 3)).astype(np.uint8)
-        info2, score2 = m.match_unique(pk, b.qual, patl=100, n_reads=n, packed=True, nflags=nfl)
-        _compare_unique(info2, score2, oinfo, oscore, 1)
-    m.close()
+    for seedl, layout in ((32, LAYOUT_STARTS), (16, LAYOUT_ROWS)):
+        p = ora.make_params(seedl=seedl, seedkmax=2, totalkmax=3, scores=1)
+        oinfo, oscore, octr = _oracle_unique(ora, None, g.sym, g.frag_start, seedl, 0, p, b.bases, b.qual, b.offsets)
+        m = UniqueMatcher(_opts(seedl, 2, 3, 1), table_kind=3, prefix_bits=13)
+        m.set_text_symbols(0, g.sym, g.frag_start)
+        m.build_index_block()
+        assert m.table_kind == layout, m.table_kind
+        info, score = m.match_unique(b.bases, b.qual, patl=100)
+        _compare_unique(info, score, oinfo, oscore, 1)
+        c = m.counters()
+        for kk in ("reads", "lookups", "candidates", "seedpass", "hits"):
+            assert c[kk] == octr[kk], (kk, c[kk], octr[kk])
+        if n % 4 == 0:                                           # the same batch with the bases 2-bit packed
+            q4 = b.bases.reshape(-1, 4)
+            pk = ((q4[:, 0] << 6) | (q4[:, 1] << 4) | (q4[:, 2] << 2) | q4[:, 3]).astype(np.uint8)
+            nfl = np.zeros((n + 7) // 8, dtype=np.uint8)
+            bad = np.nonzero((b.bases.reshape(n, 100) > 3).any(axis=1))[0]
+            np.bitwise_or.at(nfl, bad // 8, (1 << (bad % 8)).astype(np.uint8))
+            pk = ((np.minimum(q4[:, 0], 3) << 6) | (np.minimum(q4[:, 1], 3) << 4) | (np.minimum(q4[:, 2], 3) << 2) | np.minimum(q4[:, 3], 3)).astype(np.uint8)
+            info2, score2 = m.match_unique(pk, b.qual, patl=100, n_reads=n, packed=True, nflags=nfl)
+            _compare_unique(info2, score2, oinfo, oscore, 1)
+        m.close()
 
 
 @pytest.mark.parametrize("patl,shift", [(100, 0), (100, 4), (100, 7), (150, 0), (150, 5), (36, 3)])
@@ -470,25 +480,28 @@ def test_device_batch_at_any_address(ora, patl, shift):
     travel by LDS-DMA only when their first byte lies at a multiple of 16 (match_kernel.hip: quals_ahead), in one piece up to
     8 KiB per wave and in two above (150 bp reads); everything else is staged by the wave itself.  Same records either way."""
     import torch
-    seedl = 32 if patl < 150 else 64
     k = 3 if patl < 150 else 5
     g = synth.random_genome(150_000, seed=300 + patl, n_frag=2, n_runs=4, repeats=10)
     b = synth.sample_reads(g, 3000, patl, 0.02, seed=301 + shift)
-    p = ora.make_params(seedl=seedl, seedkmax=2, totalkmax=k, scores=1)
-    oinfo, oscore, _ = _oracle_unique(ora, None, g.sym, g.frag_start, seedl, 0, p, b.bases, b.qual, b.offsets)
-    m = UniqueMatcher(_opts(seedl, 2, k, 1), table_kind=3, prefix_bits=14)
-    m.set_text_symbols(0, g.sym, g.frag_start)
-    m.build_index_block()
-    n = b.n_reads
-    big_b = torch.zeros(n * patl + 64, dtype=torch.uint8, device="cuda")
-    big_q = torch.zeros(n * patl + 64, dtype=torch.uint8, device="cuda")
-    db, dq = big_b[shift:shift + n * patl], big_q[shift:shift + n * patl]
-    db.copy_(torch.from_numpy(b.bases)); dq.copy_(torch.from_numpy(b.qual))
-    info = torch.zeros(n, dtype=torch.int64, device="cuda")
-    score = torch.full((n,), float(np.float32(ora.NOSCORE_INIT)), dtype=torch.float32, device="cuda")
-    m.match_unique(db, dq, patl=patl, info=info, score=score, n_reads=n)
-    _compare_unique(info.cpu().numpy().view(np.uint64), score.cpu().numpy(), oinfo, oscore, 1)
-    m.close()
+    # a request for rows at 2^14 buckets: 32-base seeds get bucket starts, 64-base seeds wide rows; 16-base seeds at 2^13 rows
+    geometries = ((32, 14, LAYOUT_STARTS), (16, 13, LAYOUT_ROWS)) if patl < 150 else ((64, 14, LAYOUT_ROWS),)
+    for seedl, pb, layout in geometries:
+        p = ora.make_params(seedl=seedl, seedkmax=2, totalkmax=k, scores=1)
+        oinfo, oscore, _ = _oracle_unique(ora, None, g.sym, g.frag_start, seedl, 0, p, b.bases, b.qual, b.offsets)
+        m = UniqueMatcher(_opts(seedl, 2, k, 1), table_kind=3, prefix_bits=pb)
+        m.set_text_symbols(0, g.sym, g.frag_start)
+        m.build_index_block()
+        assert m.table_kind == layout, m.table_kind
+        n = b.n_reads
+        big_b = torch.zeros(n * patl + 64, dtype=torch.uint8, device="cuda")
+        big_q = torch.zeros(n * patl + 64, dtype=torch.uint8, device="cuda")
+        db, dq = big_b[shift:shift + n * patl], big_q[shift:shift + n * patl]
+        db.copy_(torch.from_numpy(b.bases)); dq.copy_(torch.from_numpy(b.qual))
+        info = torch.zeros(n, dtype=torch.int64, device="cuda")
+        score = torch.full((n,), float(np.float32(ora.NOSCORE_INIT)), dtype=torch.float32, device="cuda")
+        m.match_unique(db, dq, patl=patl, info=info, score=score, n_reads=n)
+        _compare_unique(info.cpu().numpy().view(np.uint64), score.cpu().numpy(), oinfo, oscore, 1)
+        m.close()
 
 
 @pytest.mark.parametrize("where", ["host", "device"])
@@ -503,6 +516,7 @@ def test_fresh_batch_ignores_what_the_record_arrays_hold(ora, where):
     m = UniqueMatcher(_opts(16, 2, 3, 1), prefix_bits=13, table_kind=3)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == LAYOUT_ROWS, m.table_kind
     n = offsets.shape[0] - 1
     info = np.full(n, 0x7123456789abcdef, dtype=np.uint64)   # garbage that would win every fold
     score = np.full(n, 1e30, dtype=np.float32)
@@ -531,6 +545,7 @@ def test_repeat_cliff_match_all(ora, seedl, kind, pb):
     m = AllMatcher(_opts(seedl, 2, 2, 1), prefix_bits=pb, table_kind=kind)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == (LAYOUT_ROWS if kind == 3 else LAYOUT_STARTS), m.table_kind
     cap = int(ohits.shape[0]) + 1024
     m.match_all(bases, qual, offsets, cap=cap)               # warm-up (allocations)
     m.counters(reset=True)
@@ -566,6 +581,7 @@ def test_near_copies_reach_the_fold_in_the_reference_order(ora, seedl, kind, pb)
     m = UniqueMatcher(_opts(seedl, 2, 3, 1), prefix_bits=pb, table_kind=kind)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    assert m.table_kind == {0: LAYOUT_STARTS, 2: LAYOUT_DIGEST, 3: LAYOUT_ROWS}[kind], m.table_kind
     # the read alone, and as every lane of two tiles (both strands: the reverse complement finds the same three windows)
     for reps in (1, 128):
         bases = np.concatenate([b.bases if i % 2 == 0 else synth.revcomp(b.bases) for i in range(reps)])
@@ -622,6 +638,11 @@ def test_diverged_copies_random(ora, seedl, patl, k, kind, pb):
     m = UniqueMatcher(_opts(seedl, 2, k, 1), prefix_bits=pb, table_kind=kind)
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
+    # (rows of 36-base seeds need at least 36 - 32 prefix bits: the request at 2^12 gets bucket starts; the automatic prefix
+    # on this genome is 18 bits, all but two of a 20-base signature's: a digest directory)
+    layout = {(32, 0): LAYOUT_STARTS, (32, 2): LAYOUT_DIGEST, (16, 3): LAYOUT_ROWS, (16, 2): LAYOUT_DIGEST, (16, 0): LAYOUT_STARTS,
+              (64, 0): LAYOUT_STARTS, (64, 2): LAYOUT_FINGERPRINT, (64, 3): LAYOUT_ROWS, (36, 3): LAYOUT_STARTS, (20, 0): LAYOUT_DIGEST}
+    assert m.table_kind == layout[(seedl, kind)], m.table_kind
     info, score = m.match_unique(b.bases, b.qual, patl=patl)
     _compare_unique(info, score, oinfo, oscore, 1)
     c = m.counters()
@@ -664,6 +685,7 @@ def test_two_genome_files_fold_through_the_file_id(ora, scores, kind, pb, seedl)
         oinfo, oscore, _ = ora.match_unique(og, ora.Index(og, seedl), p, b.bases, b.qual, b.offsets, info=oinfo, score=oscore)
         m.set_text_symbols(fid, g.sym, g.frag_start)
         m.build_index_block()
+        assert m.table_kind == {0: LAYOUT_STARTS, 2: LAYOUT_DIGEST, 3: LAYOUT_ROWS}[kind], m.table_kind
         m.match_unique(b.bases, b.qual, b.offsets, info=info, score=score)
     _compare_unique(info, score, oinfo, oscore, scores)
     st, fr, er, fi, po = unpack_info(info)
@@ -713,7 +735,7 @@ def test_second_pass_across_index_blocks_and_fresh_records(ora, scores):
     m.counters(reset=True)
     while nxt:
         cnt, nxt = m.build_index_block(first, n_list)
-        assert m.table_kind == 3
+        assert m.table_kind == LAYOUT_ROWS
         first += cnt
         m.match_unique(bases, qual, offsets, info=info, score=score, fresh=(blocks == 0))
         blocks += 1

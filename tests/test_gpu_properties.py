@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from real_amd import synth
+from real_amd.lib import LAYOUT_ROWS
 from real_amd.matcher import AllMatcher, RealOptions, UniqueMatcher, new_unique_info, unpack_info
 
 pytestmark = pytest.mark.gpu
@@ -163,7 +164,7 @@ def test_strand_symmetry_mid_size():
     m = UniqueMatcher(_opts(24, 3, 1), table_kind=3, prefix_bits=20)       # bucket rows: 24-base seeds, 2^20 rows of 16 signature values, 9.5 entries per row
     m.set_text_symbols(0, g.sym, g.frag_start)
     m.build_index_block()
-    assert m.table_kind == 3
+    assert m.table_kind == LAYOUT_ROWS
     info, score = m.match_unique(b.bases, b.qual, patl=100)
     c = m.counters()
     assert c["handed_over"] > 100, c                                       # the second pass and the wave kernel have work
