@@ -3,9 +3,8 @@
 // over the reads it handed over (match_wave.hip).
 #include "real_hip_internal.h"
 
-#define RH_DECL_W(N)                                                                    \
-    void rh_launch_match_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all);         \
-    void rh_launch_match2_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all);        \
+#define RH_DECL_W(N)                                                                        \
+    void rh_launch_match_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all, bool pass2); \
     uint32_t rh_stage_bytes_w##N(const DevIndex &ix);
 RH_DECL_W(1) RH_DECL_W(2) RH_DECL_W(3) RH_DECL_W(4) RH_DECL_W(5) RH_DECL_W(6) RH_DECL_W(7) RH_DECL_W(8) RH_DECL_W(9) RH_DECL_W(10)
 void rh_launch_match_wave(real_hip_ctx *ctx, const MatchArgs &a, bool all);
@@ -14,12 +13,10 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &args, bool all, int stat
 {
     if (!args.b.n_reads) return REAL_HIP_OK;
     MatchArgs a = args;
-    typedef void (*launch_fn)(real_hip_ctx *, const MatchArgs &, bool);
+    typedef void (*launch_fn)(real_hip_ctx *, const MatchArgs &, bool, bool);
     typedef uint32_t (*stage_fn)(const DevIndex &);
     static const launch_fn launch[RH_MAXW] = {rh_launch_match_w1, rh_launch_match_w2, rh_launch_match_w3, rh_launch_match_w4, rh_launch_match_w5,
                                               rh_launch_match_w6, rh_launch_match_w7, rh_launch_match_w8, rh_launch_match_w9, rh_launch_match_w10};
-    static const launch_fn launch2[RH_MAXW] = {rh_launch_match2_w1, rh_launch_match2_w2, rh_launch_match2_w3, rh_launch_match2_w4, rh_launch_match2_w5,
-                                               rh_launch_match2_w6, rh_launch_match2_w7, rh_launch_match2_w8, rh_launch_match2_w9, rh_launch_match2_w10};
     static const stage_fn stage[RH_MAXW] = {rh_stage_bytes_w1, rh_stage_bytes_w2, rh_stage_bytes_w3, rh_stage_bytes_w4, rh_stage_bytes_w5,
                                             rh_stage_bytes_w6, rh_stage_bytes_w7, rh_stage_bytes_w8, rh_stage_bytes_w9, rh_stage_bytes_w10};
     if (a.b.W < 1 || a.b.W > RH_MAXW) return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "read longer than REAL_HIP_MAX_PATL", hipSuccess);
@@ -46,11 +43,11 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &args, bool all, int stat
     a.ovf2_count = oc + 4;
     RH_HIP(ctx, hipMemsetAsync(ctx->ovf_count.p, 0, 64, ctx->stream));
     rh_time_begin(ctx, ctx->stream, all ? REAL_HIP_K_MATCH_ALL : REAL_HIP_K_MATCH_UNIQUE);
-    launch[a.b.W - 1](ctx, a, all);
+    launch[a.b.W - 1](ctx, a, all, false);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
     rh_time_begin(ctx, ctx->stream, REAL_HIP_K_MATCH_REPEAT);
-    launch2[a.b.W - 1](ctx, a, all);
+    launch[a.b.W - 1](ctx, a, all, true); // (bucket rows, parked hits: scores on or matchAll; nothing otherwise)
     rh_launch_match_wave(ctx, a, all);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());

@@ -48,12 +48,10 @@ __device__ __forceinline__ WaveRange wave_lookup(const MatchArgs &a, uint64_t sh
     const uint32_t bb = a.b_bits, l = a.l;
     const uint64_t mb = (bb >= 64) ? ~0ull : ((1ull << bb) - 1);
     const uint64_t m0 = shi >> bb, m1 = shi & mb, m2 = slo >> bb, m3 = slo & mb;
-    // s0..s5 = segments (0,1),(0,2),(0,3),(1,2),(1,3),(2,3), SignatureConstruction.hpp:62-67; partner = list 5-la
-    const uint32_t xa = (0x940u >> (2 * la)) & 3u, xc = (0xfb9u >> (2 * la)) & 3u;
-    const int lb = 5 - la;
-    const uint32_t xb = (0x940u >> (2 * lb)) & 3u, xd = (0xfb9u >> (2 * lb)) & 3u;
-    const uint64_t sa = (pick4(m0, m1, m2, m3, xa) << bb) | pick4(m0, m1, m2, m3, xc);
-    const uint64_t sb = (pick4(m0, m1, m2, m3, xb) << bb) | pick4(m0, m1, m2, m3, xd);
+    // signature s_a of list la, SignatureConstruction.hpp:62-67, and s_b of its partner list 5-la
+    const uint2 x = rh_list_segs(la), xp = rh_list_segs(5 - la);
+    const uint64_t sa = (pick4(m0, m1, m2, m3, x.x) << bb) | pick4(m0, m1, m2, m3, x.y);
+    const uint64_t sb = (pick4(m0, m1, m2, m3, xp.x) << bb) | pick4(m0, m1, m2, m3, xp.y);
     const uint32_t pbits = a.ix.pbits;
     R.partner = pbits ? (uint32_t)(sb >> (l - pbits)) : 0u;
     const uint32_t prefix = (uint32_t)(sa >> a.ix.pshift);
@@ -280,7 +278,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void m
         // position / fragment / N checks -> Hamming distance (no score yet).  R, inv, la may differ from lane to lane.
         auto candidate = [&](const WaveRange &R, uint32_t i, bool cand, uint32_t inv, uint32_t la, uint32_t &pos, uint32_t &total, uint32_t &frag,
                              uint32_t &first) -> bool {
-            const uint32_t xa = (0x940u >> (2 * la)) & 3u, xc = (0xfb9u >> (2 * la)) & 3u;
+            const uint2 x = rh_list_segs(la);
             const uint64_t hi_ = inv ? rhi : shi, lo_ = inv ? rlo : slo;
             const uint64_t *const cur = inv ? sR : sO;
             const uint32_t so = inv ? (patl - l) : 0u; // RestMatch::getMatchOffset, RestMatch.hpp:84-89
@@ -318,7 +316,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void m
             const uint32_t k0 = __popcll(dhi >> bb), k1 = __popcll(dhi & mb), k2 = __popcll(dlo >> bb), k3 = __popcll(dlo & mb);
             const bool z0 = !k0, z1 = !k1, z2 = !k2, z3 = !k3;
             // a member of list la's equal range iff both segments the list is keyed on are mismatch free
-            const bool za = xa == 0 ? z0 : xa == 1 ? z1 : z2, zc = xc == 1 ? z1 : xc == 2 ? z2 : z3;
+            const bool za = x.x == 0 ? z0 : x.x == 1 ? z1 : z2, zc = x.y == 1 ? z1 : x.y == 2 ? z2 : z3;
             bool ok = za && zc;
             if (ok && !pbits) cC++;
             const uint32_t seedk = k0 + k1 + k2 + k3; // = diffcountpair(s_b, list_b[p->ptr].sign), match.hpp:386

@@ -50,6 +50,11 @@ struct DevIndex {
 // wide signatures (pbits == 0): the entries hold a 32-bit key instead of key group + partner bits
 static inline __host__ __device__ bool rh_wide_entries(const DevIndex &ix) { return ix.pbits == 0; }
 
+// the two seed segments {a, c} list la is keyed on: s0..s5 = (0,1),(0,2),(0,3),(1,2),(1,3),(2,3), SignatureConstruction.hpp:62-67;
+// signature = segment a << segment bits | segment c.  The partner of list la is list 5 - la (its signature is the entry's s_b).
+// (bit tables: la is a run-time value in some callers, an array indexed by it would live in scratch memory)
+static inline __host__ __device__ uint2 rh_list_segs(uint32_t la) { return make_uint2((0x940u >> (2 * la)) & 3u, (0xfb9u >> (2 * la)) & 3u); }
+
 // digest directories: uint4 {start, 8 x {size:4, partner digest:8}}: the prefix is all signature bits but one to three, so a
 // bucket has at most eight key groups (= signature values) and its 16-byte table entry describes each of them
 static inline bool rh_digest_geometry(uint32_t l, uint32_t pb) { return l >= pb && l - pb >= 1 && l - pb <= 3; }
