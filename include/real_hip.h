@@ -77,7 +77,8 @@ typedef struct real_hip_params {
                                (real_hip_index_table_kind reports the one built); a host-layout detail like
                                prefix_bits, results do not depend on it                   */
     double   filter_mult;   /* RealOptions.cpp:455-463; epsilon=(float)(filter_mult*patl),
-                               RealOptions.hpp:74-77, matchUniqueImplementation.cpp:405 */
+                               RealOptions.hpp:74-77, matchUniqueImplementation.cpp:405;
+                               >= 0 (filter levels 0..4), negative or NaN is E_INVALID  */
     double   LL[1024];      /* Scoring::getRawLogScoreTable, index (ref<<8)|(read<<6)|q
                                (Scoring.hpp:70-73); ignored if !scores                */
 } real_hip_params;

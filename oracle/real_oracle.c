@@ -402,6 +402,7 @@ void ora_scoring_table(double similarity, double gcContent, double transitRate, 
 /* ComputeScore.hpp:50-190: raw = 1.0; raw += LL[ref_i, read_i, q_i] for
    i = 0..patl-1 in order; straight: read=mapped[i], q=quality[i]; inverted:
    read=transposed[i]=3-mapped[patl-1-i], q=quality[patl-1-i]; result (float)raw.
+   qual == NULL: reads without qualities, every q = 30 (Pattern.hpp:42-45).
    The reference walks the text word by word; symbol i is text[pos+i]. */
 float ora_compute_score(const ora_genome *g, const double *LL, int inverted,
                         const uint8_t *mapped, const uint8_t *qual, uint32_t pos, unsigned patl)
@@ -411,8 +412,9 @@ float ora_compute_score(const ora_genome *g, const double *LL, int inverted,
         uint64_t p = (uint64_t)pos + i;
         unsigned ref = (unsigned)((g->text[p >> 5] >> (62 - 2 * (p & 31))) & 3);
         unsigned pat, q;
-        if (inverted) { pat = 3u - mapped[patl - 1 - i]; q = (unsigned)(int)(signed char)qual[patl - 1 - i]; }
-        else          { pat = mapped[i];                 q = (unsigned)(int)(signed char)qual[i]; }
+        const unsigned j = inverted ? patl - 1 - i : i;
+        pat = inverted ? 3u - mapped[j] : mapped[j];
+        q = qual ? (unsigned)(int)(signed char)qual[j] : 30u; /* no qualities (FASTA): 30, Pattern.hpp:42-45 */
         raw += LL[(ref << 8) | (pat << 6) | q];
     }
     return (float)raw;

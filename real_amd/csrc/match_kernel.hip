@@ -232,6 +232,8 @@ __device__ __forceinline__ void deliver(const MatchArgs &a, LaneState<T> &s, uin
 // a later list, after other windows, has its later events at their own lists' turns -- not at its first one's).
 // Two consecutive update() calls for the same location are one: the second finds the record either at that location
 // (nothing differs), NonUnique with the same score comparison that just failed, or as untouched as the first left it.
+// That holds for eps = filter_mult * patl >= 0 only (eps < 0 would let the second call re-take a NonUnique record):
+// real_hip_create and real_hip_set_match_params reject a negative or NaN filter_mult.
 template <class T, class Row>
 __device__ __forceinline__ void flush_pending(const MatchArgs &a, LaneState<T> &s, const double *sLL, const Row &qrow)
 {
@@ -305,6 +307,7 @@ __device__ __forceinline__ void flush_pending(const MatchArgs &a, LaneState<T> &
     if (NP <= 4) {
         // the event sequence first (2 bits per event = its location; at most 4 x 6 events), then the calls: the fold's code
         // exists once and runs as often as the lane with the most events needs it
+        static_assert(NPEND <= 4 && NPEND * 6 * 2 <= 64, "the first pass' event word: a 2-bit location per event, NPEND x 6 events");
         uint64_t ev = 0;
         uint32_t nev = 0, last = SLOT_NONE;
 #pragma unroll 1

@@ -178,6 +178,7 @@ extern "C" int real_hip_create(real_hip_ctx **out, const real_hip_params *p)
     if (!out || !p || p->struct_size != sizeof(real_hip_params)) return REAL_HIP_E_INVALID;
     // RealOptions.cpp:434-453 clamps these; at the ABI they are errors
     if (p->seedl < 4 || p->seedl > 64 || (p->seedl % 4) || p->seedkmax > 2 || p->totalkmax > 15) return REAL_HIP_E_INVALID;
+    if (!(p->filter_mult >= 0.0)) return REAL_HIP_E_INVALID; // negative or NaN: the matcher's merge of repeated update() calls needs eps >= 0
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || p->device < 0 || p->device >= ndev) {
         (void)hipGetLastError();
@@ -247,6 +248,7 @@ extern "C" int real_hip_set_match_params(real_hip_ctx *ctx, uint32_t seedkmax, u
 {
     if (!ctx) return REAL_HIP_E_INVALID;
     if (seedkmax > 2 || totalkmax > 15) return rh_fail(ctx, REAL_HIP_E_INVALID, "seedkmax <= 2, totalkmax <= 15 (RealOptions.cpp:172-180, 449-453)", hipSuccess);
+    if (!(filter_mult >= 0.0)) return rh_fail(ctx, REAL_HIP_E_INVALID, "filter_mult must be >= 0 (flush_pending merges repeated update() calls: sound for eps >= 0 only)", hipSuccess);
     ctx->prm.seedkmax = seedkmax; ctx->prm.totalkmax = totalkmax; ctx->prm.scores = scores ? 1u : 0u; ctx->prm.filter_mult = filter_mult;
     return REAL_HIP_OK;
 }

@@ -82,6 +82,39 @@ def random_genome(n: int, seed: int, n_frag: int = 1, n_runs: int = 0, n_run_len
     return Genome(sym=sym, frag_start=starts, frag_names=names)
 
 
+def repeat_family_genome(n: int, seed: int, families: Sequence[int] = (3, 6, 30, 60), seg_len: int = 760,
+                         n_frag: int = 4, n_runs: int = 6, n_run_len: int = 7):
+    """Uniform ACGT genome with EXACT repeat families: for each entry c of ``families`` one random segment of ``seg_len``
+    bases is planted ``c`` times (random_genome perturbs its copies).  Copies, N runs and fragment cuts lie in disjoint
+    slots, so every copy is whole, N-free and inside one fragment: a read on a family of c copies has exactly c locations
+    per strand.  Returns (genome, [(segment start of each copy, ...) per family])."""
+    rng = np.random.default_rng(seed)
+    sym = rng.integers(0, 4, size=n, dtype=np.uint8)
+    slot = seg_len + 16
+    n_slots = n // slot
+    n_copies = int(sum(families))
+    assert n_slots >= n_copies + n_runs + n_frag, "genome too small for the repeat families"
+    order = rng.permutation(n_slots)
+    used = 0
+    copies = []
+    for c in families:
+        at = sorted(int(s) * slot + 8 for s in order[used:used + c])
+        used += c
+        seg = rng.integers(0, 4, size=seg_len, dtype=np.uint8)
+        for p in at:
+            sym[p:p + seg_len] = seg
+        copies.append(tuple(at))
+    for s in order[used:used + n_runs]:                      # N runs inside slots of their own
+        ln = int(rng.integers(1, n_run_len + 1))
+        p = int(s) * slot + int(rng.integers(0, slot - ln))
+        sym[p:p + ln] = 4
+    used += n_runs
+    cuts = sorted(int(s) * slot + slot // 2 for s in order[used:used + n_frag - 1])
+    starts = np.array([0] + cuts + [n], dtype=np.uint64)
+    names = [" families_%d_%d" % (n, i) for i in range(len(starts) - 1)]
+    return Genome(sym=sym, frag_start=starts, frag_names=names), copies
+
+
 _COMP = np.array([3, 2, 1, 0, 4], dtype=np.uint8)
 
 

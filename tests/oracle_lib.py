@@ -231,7 +231,7 @@ def match_unique(g: Genome, ix: Index, p: OraParams, bases, qual, offsets,
                  info: Optional[np.ndarray] = None, score: Optional[np.ndarray] = None,
                  want_events: bool = False):
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)   # None: no qualities (30 each)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = offsets.shape[0] - 1
     if info is None:
@@ -256,7 +256,7 @@ def match_unique(g: Genome, ix: Index, p: OraParams, bases, qual, offsets,
 
 def match_all(g: Genome, ix: Index, p: OraParams, bases, qual, offsets):
     bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)   # None: no qualities (30 each)
     offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
     n = offsets.shape[0] - 1
     cap = max(1024, 16 * n)

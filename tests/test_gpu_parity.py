@@ -325,6 +325,17 @@ def test_errors_are_loud():
     assert info.shape[0] == 0
     info, score = m.match_unique(np.full(40, 4, np.uint8), np.zeros(40, np.uint8), patl=20)
     assert np.all(info == 0)
+    # a negative or NaN filter_mult (eps < 0: flush_pending's merge of repeated update() calls is unsound) is refused, by
+    # the setter and at context creation
+    import ctypes as C
+    from real_amd import lib as rlib
+    for bad in (-1e-3, -1.0, float("nan")):
+        assert m._L.real_hip_set_match_params(m._h, 2, 3, 1, C.c_double(bad)) == rlib.REAL_HIP_E_INVALID, bad
+        p = rlib.RealHipParams()
+        p.struct_size, p.seedl, p.seedkmax, p.totalkmax, p.scores, p.filter_mult = C.sizeof(rlib.RealHipParams), 32, 2, 3, 1, bad
+        h = C.c_void_p()
+        assert m._L.real_hip_create(C.byref(h), C.byref(p)) == rlib.REAL_HIP_E_INVALID and not h.value, bad
+    assert m._L.real_hip_set_match_params(m._h, 2, 3, 1, C.c_double(0.0)) == 0      # (filter level 0: eps = 0 is fine)
     m.close()
 
 
