@@ -1,0 +1,175 @@
+#!/usr/bin/env python3
+"""Paired-end reads at C3-like size: what a caller had to do before real_hip_match_pairs existed (two real_hip_match_all
+calls with host outputs; the join on the host is not even counted) against real_hip_match_pairs, on the BASELINE genome
+generator and on a genome with 5 % of its positions in 16-copy repeat families.  Starts nothing by itself in CI.
+
+    python bench_support/pairs_bench.py --out profiles/pairs_bench.json                  # this checkout
+    python bench_support/pairs_bench.py --tree /path/to/parent/checkout --out ...        # the baseline on another build
+
+--tree: import real_amd and bench from that checkout (built) instead of this one; a checkout without PairMatcher gives
+the baseline figures only.  Results are merged into --out under the key --label.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def sample_pairs_device(torch, sym, n, patl, mean, sd, errprob, seed, dev, chunk=1 << 20):
+    """FR mates of n fragments, on the device: fragment length ~ N(mean, sd) clipped to [patl, mean + 4 sd], uniform start,
+    the forward mate is mate 1 or mate 2 by a coin flip; substitutions / qualities as bench.gen_reads"""
+    g = torch.Generator(device=dev); g.manual_seed(seed)
+    G = sym.shape[0]
+    L = torch.clamp(torch.round(torch.randn(n, generator=g, device=dev) * sd + mean), patl, mean + 4 * sd).to(torch.int64)
+    s = (torch.rand(n, generator=g, device=dev, dtype=torch.float64) * (G - L + 1).to(torch.float64)).to(torch.int64)
+    fwd1 = torch.rand(n, generator=g, device=dev) < 0.5
+    ar = torch.arange(patl, device=dev)
+    out = []
+    for is_fwd in (fwd1, ~fwd1):
+        bases = torch.empty(n * patl, dtype=torch.uint8, device=dev)
+        qual = torch.empty(n * patl, dtype=torch.uint8, device=dev)
+        for lo in range(0, n, chunk):
+            hi = min(n, lo + chunk)
+            f = is_fwd[lo:hi]
+            start = torch.where(f, s[lo:hi], s[lo:hi] + L[lo:hi] - patl)
+            rd = sym[start[:, None] + ar[None, :]]
+            rc = torch.where(rd < 4, 3 - rd, rd).flip(1)
+            rd = torch.where(f[:, None], rd, rc)
+            mut = (torch.rand(rd.shape, generator=g, device=dev) < errprob) & (rd < 4)
+            delta = torch.randint(1, 4, rd.shape, generator=g, device=dev, dtype=torch.uint8)
+            new = torch.where(mut, (rd + delta) & 3, rd)
+            bases[lo * patl:hi * patl] = new.reshape(-1)
+            qual[lo * patl:hi * patl] = torch.where(mut, 9, 35).to(torch.uint8).reshape(-1)
+        out.append((bases, qual))
+    torch.cuda.synchronize()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tree", default=HERE)
+    ap.add_argument("--label", default="this_commit")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "pairs_bench.json"))
+    ap.add_argument("--genome-mbp", type=float, default=3000.0)
+    ap.add_argument("--pairs", type=int, default=25_000_000)
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--genomes", default="iid,repeat")
+    args = ap.parse_args()
+    sys.path.insert(0, args.tree)
+    import numpy as np
+    import torch
+    import bench
+    from real_amd import lib as rlib
+    from real_amd import matcher as rm
+    have_pairs = hasattr(rm, "PairMatcher")
+    dev = torch.device("cuda", 0)
+    G, n, patl, lo_ins, hi_ins = int(args.genome_mbp * 1e6), args.pairs, 100, 100, 420
+    result = {"genome_mbp": args.genome_mbp, "pairs": n, "patl": patl, "insert": [lo_ins, hi_ins], "steps": args.steps,
+              "tree_has_match_pairs": have_pairs}
+    for kind in args.genomes.split(","):
+        sym = bench.gen_genome(torch, G, 3, dev)
+        if kind == "repeat":                       # 5 % of the positions in families of 16 exact copies of 1 kbp (bench_support/repeat_genome.py)
+            fam = int(G * 0.05 / (16 * 1000))
+            gg = torch.Generator(device="cpu"); gg.manual_seed(7)
+            ar = torch.arange(1000, device=dev)
+            src = torch.randint(0, G - 1000, (fam,), generator=gg).to(dev)
+            for c in range(15):
+                dst = torch.randint(0, G - 1000, (fam,), generator=gg).to(dev)
+                sym[(dst[:, None] + ar[None, :]).reshape(-1)] = sym[(src[:, None] + ar[None, :]).reshape(-1)]
+        (b1, q1), (b2, q2) = sample_pairs_device(torch, sym, n, patl, 300, 30, 0.02, 11, dev)
+        torch.cuda.synchronize(); torch.cuda.empty_cache()
+        Cls = rm.PairMatcher if have_pairs else rm.HipMatcher
+        m = Cls(rm.RealOptions(seedl=32, seedkmax=2, totalkmax=2, scores=True).normalise(), device=0)
+        m.set_text_symbols(0, sym, np.array([0, G], dtype=np.uint64))
+        m.build_index_block()
+        del sym
+        torch.cuda.empty_cache()
+        L = m._L
+
+        def batch(b, q):
+            rb = m._batch(b, q, None, patl, n)
+            rb.on_device = 2                       # read arrays on the device, outputs in host memory
+            return rb
+        for tk in (2, 3):
+            m.set_match_params(totalkmax=tk)
+            key = "%s_k%d" % (kind, tk)
+            r = {}
+            # -- baseline: two real_hip_match_all calls with host outputs (pinned buffers, sized by a first call)
+            hits, hoff, need = None, m.host_alloc(n + 1, np.uint64), [0, 0]
+            cap = int(n * 1.5)
+            for attempt in range(2):
+                hits = m.host_alloc(cap, rlib.HIT_DTYPE)
+                ok = True
+                for j, (b, q) in enumerate(((b1, q1), (b2, q2))):
+                    rb, nout = batch(b, q), C.c_uint64(0)
+                    rc = L.real_hip_match_all(m._h, C.byref(rb), hits.ctypes.data, cap, C.byref(nout), hoff.ctypes.data)
+                    need[j] = int(nout.value)
+                    if rc == rlib.REAL_HIP_E_OVERFLOW:
+                        ok = False
+                    else:
+                        m._check(rc)
+                if ok:
+                    break
+                cap = max(need) + 16
+            ts = []
+            for _ in range(args.steps):
+                t0 = time.perf_counter()
+                for b, q in ((b1, q1), (b2, q2)):
+                    rb, nout = batch(b, q), C.c_uint64(0)
+                    m._check(L.real_hip_match_all(m._h, C.byref(rb), hits.ctypes.data, cap, C.byref(nout), hoff.ctypes.data))
+                ts.append((time.perf_counter() - t0) * 1e3)
+            r["baseline_ms"], r["baseline_ms_all_steps"] = min(ts), ts
+            r["hits_per_mate"] = [need[0] / n, need[1] / n]
+            r["baseline_hit_bytes_downloaded"] = (need[0] + need[1]) * 16
+            if have_pairs:
+                pp = m._pair_params(lo_ins, hi_ins)
+                rec = m.host_alloc(n, rlib.PAIR_DTYPE)
+                rec_dev = torch.empty(n * 40, dtype=torch.uint8, device=dev)
+
+                def run(on_device, out_ptr):
+                    rb1, rb2 = batch(b1, q1), batch(b2, q2)
+                    rb1.on_device = rb2.on_device = on_device
+                    rb1.fresh = rb2.fresh = 1
+                    t0 = time.perf_counter()
+                    m._check(L.real_hip_match_pairs(m._h, C.byref(rb1), C.byref(rb2), C.byref(pp), out_ptr))
+                    return (time.perf_counter() - t0) * 1e3
+                run(2, rec.ctypes.data)                     # warm-up: the hit buffers grow here
+                for k in (rlib.K_MATCH_ALL, rlib.K_MATCH_REPEAT, rlib.K_ALL_SORT, rlib.K_PAIR, rlib.K_PAIR_WAVE):
+                    m.kernel_time(k, reset=True)
+                m.pair_stats(reset=True)
+                ts = [run(2, rec.ctypes.data) for _ in range(args.steps)]
+                r["match_pairs_ms"], r["match_pairs_ms_all_steps"] = min(ts), ts
+                S = float(args.steps)
+                r["split_ms_per_call"] = {"match_all_lane_kernels_both_mates": m.kernel_time(rlib.K_MATCH_ALL)[0] / S,
+                                          "match_all_second_pass_and_wave_both_mates": m.kernel_time(rlib.K_MATCH_REPEAT)[0] / S,
+                                          "sort_both_mates": m.kernel_time(rlib.K_ALL_SORT)[0] / S,
+                                          "pair_lane_kernel": m.kernel_time(rlib.K_PAIR)[0] / S,
+                                          "pair_wave_kernel": m.kernel_time(rlib.K_PAIR_WAVE)[0] / S}
+                st = m.pair_stats()
+                r["products_per_fragment"] = st["products"] / max(st["pairs"], 1)
+                r["handed_over_share"] = st["handed_over"] / max(st["pairs"], 1)
+                td = [run(1, rec_dev.data_ptr()) for _ in range(args.steps)]
+                r["match_pairs_device_records_ms"] = min(td)
+                r["split_ms_per_call"]["record_download_by_difference"] = min(ts) - min(td)
+                state = np.bincount(rec["state"], minlength=3)
+                r["states"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
+                r["record_bytes_downloaded"] = n * 40
+            result[key] = r
+            print(key, json.dumps(r), flush=True)
+        m.close()
+        del b1, q1, b2, q2
+        torch.cuda.empty_cache()
+    merged = {}
+    if os.path.exists(args.out):
+        merged = json.load(open(args.out))
+    merged[args.label] = result
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    json.dump(merged, open(args.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

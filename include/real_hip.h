@@ -228,6 +228,61 @@ typedef struct real_hip_hit {       /* MatchPosAndError, matchAllImplementation.
 int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b,
                        real_hip_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *hit_offsets);
 
+/* ---- paired-end reads: one placement per fragment.  The reference has no paired-end mode; the semantics are this
+ * project's own ("Paired-end reads") and are independent of the order of hits, lanes and genome files.
+ * Read i of batch 1 and read i of batch 2 are mates.  Candidates of a mate are its real_hip_match_all hits.  A hit f with
+ * inverted = 0 of one mate and a hit r with inverted = 1 of the other are CONCORDANT (orientation FR) iff same frag,
+ * f.pos <= r.pos, f.pos + len_f <= r.pos + len_r and min_insert <= r.pos + len_r - f.pos <= max_insert (outer distance
+ * in bases; either mate may be the forward one).  VALUE of a pair: (double)score1 + (double)score2 with scores on,
+ * -(double)(k1 + k2) with scores off.  LOCATION: (fileid, frag, pos1, pos2, inverted1).  The record keeps `best` (highest
+ * value; equal values: the smallest location in lexicographic order) and `second` (highest value at any OTHER location,
+ * -inf if none); merging two records is taking the top two of their union, so genome files fold in any order.  state:
+ * NoMatch without a concordant pair, NonUnique if second >= best - eps, else Unique, with
+ * eps = (double)(float)(filter_mult * (len1 + len2)) with scores on and 0 with scores off.                           */
+typedef struct real_hip_pair_params {
+    uint32_t struct_size;   /* = sizeof(real_hip_pair_params)                                         */
+    uint32_t min_insert;    /* bounds of the outer distance, inclusive; min > max is E_INVALID        */
+    uint32_t max_insert;
+    uint32_t orientation;   /* 0 = FR; anything else is REAL_HIP_E_UNSUPPORTED                        */
+} real_hip_pair_params;
+enum { REAL_HIP_PAIR_NOMATCH = 0, REAL_HIP_PAIR_UNIQUE = 1, REAL_HIP_PAIR_NONUNIQUE = 2 };
+typedef struct real_hip_pair {      /* 40 bytes, 8-byte aligned; in/out across genome files as uniqueinfo[] is   */
+    double   best;                  /* value of the best pair; -inf: none (the fields below are then 0)         */
+    double   second;                /* highest value at another location; -inf: none                            */
+    uint32_t pos1, pos2;            /* 0-based positions of mate 1 / mate 2 in the text of fileid               */
+    float    score1, score2;        /* the hits' scores (1.0f if !scores)                                        */
+    uint16_t frag;
+    uint8_t  fileid;
+    uint8_t  k1, k2;                /* mismatches of mate 1 / mate 2                                             */
+    uint8_t  inverted1;             /* strand of mate 1 (0 '+', 1 '-'); mate 2 has the other one                 */
+    uint8_t  state;                 /* REAL_HIP_PAIR_NOMATCH / _UNIQUE / _NONUNIQUE                               */
+    uint8_t  reserved;              /* 0                                                                         */
+} real_hip_pair;
+/* The join alone, on hit lists the caller holds: hits_m[off_m[i] .. off_m[i+1]) are the candidates of mate m of pair i
+ * (any order, e.g. the per-block lists of a genome file that needs several index blocks, concatenated per read),
+ * len_m[i] the mate's length in bases (uint32).  on_device: 0 all pointers host memory (copied), 1 all device
+ * pointers.  fresh != 0: pairs[] is output only (every record starts empty); 0: in/out, the fold of another genome
+ * file.  A hit must not appear twice in one list.  Uses the ctx's -q and -filter_level; needs neither text nor index.  */
+int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp,
+                       const real_hip_hit *hits1, const uint64_t *off1, const uint32_t *len1,
+                       const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                       uint64_t n_pairs, uint32_t fileid, int on_device, int fresh, real_hip_pair *pairs);
+/* matchAll of both mates against the resident text and index block with the hits kept on the device, then the join:
+ * only the pair records cross to the host (on_device 0 / 2; 1: pairs is a device pointer).  batch1 and batch2 must
+ * agree in n_reads and on_device; batch1->fresh says whether pairs[] is output only.  The hit buffers grow inside
+ * (a match is redone when they were too small).  Pairs across index blocks are not seen: a genome file that needs
+ * several blocks goes through real_hip_match_all + real_hip_pair_hits.                                            */
+int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                         const real_hip_pair_params *pp, real_hip_pair *pairs);
+/* work of the join, accumulated since the last reset                                                              */
+typedef struct real_hip_pair_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_pair_stats), 0                               */
+    uint64_t pairs;         /* fragments joined                                                       */
+    uint64_t products;      /* sum over the fragments of (hits of mate 1) x (hits of mate 2)          */
+    uint64_t handed_over;   /* fragments whose product exceeded a lane's budget: joined by a wave each */
+} real_hip_pair_stats;
+int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single
@@ -304,7 +359,9 @@ int real_hip_counters_get(real_hip_ctx *ctx, real_hip_counters *out, int reset);
 enum { REAL_HIP_K_MATCH_UNIQUE = 0, REAL_HIP_K_MATCH_ALL = 1, REAL_HIP_K_ALL_SORT = 2, REAL_HIP_K_INDEX = 3,
        REAL_HIP_K_MATCH_REPEAT = 4, /* second pass over the repeat-rich reads the matcher hands over (scores on) */
        REAL_HIP_K_PARSE = 5,        /* real_hip_parse_reads                                                      */
-       REAL_HIP_K_COUNT = 6 };
+       REAL_HIP_K_PAIR = 6,         /* paired-end join, lane per fragment                                        */
+       REAL_HIP_K_PAIR_WAVE = 7,    /* paired-end join, wave per fragment (the fragments the lanes handed over)  */
+       REAL_HIP_K_COUNT = 8 };
 int real_hip_kernel_time(real_hip_ctx *ctx, int which, double *total_ms, uint64_t *launches, int reset);
 int real_hip_timing_enable(real_hip_ctx *ctx, int on);
 

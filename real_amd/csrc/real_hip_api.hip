@@ -217,6 +217,8 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
                      &c->keys_b, &c->vals_a, &c->vals_b, &c->sort_tmp, &c->hit_off, &c->s_hits, &c->s_nflags};
     for (DevBuf *b : all) rh_release(*b);
     for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
+    DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats};
+    for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -703,19 +705,19 @@ extern "C" void real_hip_host_free(void *p)
     if (p) (void)hipHostFree(p);
 }
 
-extern "C" int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b, real_hip_hit *out, uint64_t cap,
-                                  uint64_t *n_out, uint64_t *hit_offsets)
+// matchAll of one batch; dev_out: out / hit_offsets are device memory whatever the batch's inputs are.  staged (nullable)
+// receives the device view of the batch's arrays (valid until the next batch is staged).
+static int match_all_run(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_out, real_hip_hit *out, uint64_t cap,
+                         uint64_t *n_out, uint64_t *hit_offsets, Staged *staged)
 {
-    RH_ENTER(ctx);
     Staged s;
-    real_hip_batch bv;
-    int rc = batch_view(ctx, b, bv);
-    if (rc) return rc;
-    b = &bv;
+    int rc;
+    const real_hip_batch *b = &bv;
     if ((rc = stage_batch(ctx, bv, s, StageBufs{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, ctx->stream, nullptr))) return rc;
     const uint64_t n = b->n_reads;
     if (n_out) *n_out = 0;
     if (cap > 0xffffffffull) cap = 0xffffffffull; // record indices are 32 bit inside the post-pass
+    if (staged) *staged = s;
     if ((rc = rh_reserve(ctx, ctx->raw_count, 8))) return rc;
     RH_HIP(ctx, hipMemsetAsync(ctx->raw_count.p, 0, 8, ctx->stream));
     if ((rc = rh_reserve(ctx, ctx->raw, (cap ? cap : 1) * sizeof(uint4)))) return rc;
@@ -735,7 +737,7 @@ extern "C" int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b, re
     if (n_raw > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffer too small", hipSuccess);
     real_hip_hit *d_out = out;
     uint64_t *d_off = hit_offsets;
-    if (b->on_device != 1) { // outputs in host memory
+    if (!dev_out) { // outputs in host memory
         if ((rc = rh_reserve(ctx, ctx->s_hits, (n_raw ? n_raw : 1) * sizeof(real_hip_hit)))) return rc;
         d_out = (real_hip_hit *)ctx->s_hits.p;
         if (hit_offsets) {
@@ -745,13 +747,169 @@ extern "C" int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b, re
     }
     if ((n_raw && !out) ) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit buffer", hipSuccess);
     if ((rc = rh_all_finish(ctx, n_raw, n, d_out, d_off))) return rc;
-    if (b->on_device != 1) { // outputs in host memory
+    if (!dev_out) { // outputs in host memory
         if (n_raw) RH_HIP(ctx, hipMemcpyAsync(out, d_out, n_raw * sizeof(real_hip_hit), hipMemcpyDeviceToHost, ctx->stream));
         if (hit_offsets) RH_HIP(ctx, hipMemcpyAsync(hit_offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rh_time_resolve(ctx);
     return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b, real_hip_hit *out, uint64_t cap,
+                                  uint64_t *n_out, uint64_t *hit_offsets)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = batch_view(ctx, b, bv);
+    if (rc) return rc;
+    return match_all_run(ctx, bv, bv.on_device == 1, out, cap, n_out, hit_offsets, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// paired-end reads: the join of the two mates' hit lists (pair_kernel.hip)
+// ---------------------------------------------------------------------------
+static int pair_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp)
+{
+    if (!pp || pp->struct_size != sizeof(real_hip_pair_params)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair params struct_size", hipSuccess);
+    if (pp->orientation != 0) return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "pair orientation other than FR (0)", hipSuccess);
+    if (pp->min_insert > pp->max_insert) return rh_fail(ctx, REAL_HIP_E_INVALID, "min_insert > max_insert", hipSuccess);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
+                                  const uint32_t *len1, const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                                  uint64_t n_pairs, uint32_t fileid, int on_device, int fresh, real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    if (fileid > 255) return rh_fail(ctx, REAL_HIP_E_INVALID, "fileid > 255", hipSuccess);
+    const uint64_t n = n_pairs;
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
+    if (!off1 || !off2 || !len1 || !len2 || !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths / pairs", hipSuccess);
+    const real_hip_hit *d_h[2] = {hits1, hits2};
+    const uint64_t *d_o[2] = {off1, off2};
+    const uint32_t *d_l[2] = {len1, len2};
+    uint64_t total[2] = {0, 0};
+    real_hip_pair *d_pairs = pairs;
+    for (int m = 0; m < 2; ++m) { // the offsets start at 0 and do not run backwards; off[n] is the number of hits
+        if (on_device) {
+            uint64_t ends[1] = {0}, first = 0;
+            RH_HIP(ctx, hipMemcpyAsync(&first, d_o[m], 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(ends, d_o[m] + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (first) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
+            total[m] = ends[0]; // (offsets in between are clamped to it by the kernels)
+        } else {
+            const uint64_t *o = d_o[m];
+            if (o[0]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
+            for (uint64_t i = 0; i < n; ++i)
+                if (o[i + 1] < o[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets not monotone", hipSuccess);
+            total[m] = o[n];
+        }
+        if (total[m] && !d_h[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
+    }
+    if (!on_device) {
+        for (int m = 0; m < 2; ++m) {
+            if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total[m] ? total[m] : 1) * sizeof(real_hip_hit)))) return rc;
+            if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
+            if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
+            if (total[m]) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, d_h[m], total[m] * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, d_o[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, d_l[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
+            d_h[m] = (const real_hip_hit *)ctx->pair_hits[m].p; d_o[m] = (const uint64_t *)ctx->pair_off[m].p; d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
+        }
+        ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
+        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
+        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
+        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = rh_launch_pair(ctx, *pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, fileid, fresh, d_pairs);
+    if (!rc && !on_device) {
+        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                    const real_hip_pair_params *pp, real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    real_hip_batch bv[2];
+    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
+    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
+    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    const uint64_t n = bv[0].n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pairs", hipSuccess);
+    const bool host_out = bv[0].on_device != 1;
+    uint64_t total[2] = {0, 0};
+    for (int m = 0; m < 2; ++m) {
+        if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
+    }
+    // the hit capacity is the library's problem: both buffers hold pair_cap hits; a match that needs more reports the size,
+    // the buffers grow and the matches are done again
+    if (ctx->pair_cap < n + n / 4 + 1024) ctx->pair_cap = 0;
+    for (int attempt = 0;; ++attempt) {
+        if (!ctx->pair_cap) {
+            uint64_t want = n + n / 4 + 1024;
+            if (total[0] > want) want = total[0];
+            if (total[1] > want) want = total[1];
+            for (int m = 0; m < 2; ++m)
+                if ((rc = rh_reserve(ctx, ctx->pair_hits[m], want * sizeof(real_hip_hit)))) return rc;
+            ctx->pair_cap = want;
+        }
+        bool overflow = false;
+        for (int m = 0; m < 2; ++m) {
+            Staged s;
+            rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s);
+            if (rc == REAL_HIP_E_OVERFLOW) { overflow = true; continue; } // (the other mate still reports its size)
+            if (rc) return rc;
+            // the read lengths, while this mate's offsets are staged
+            if ((rc = rh_pair_lens(ctx, s.off, s.upatl, n, (uint32_t *)ctx->pair_len[m].p))) return rc;
+        }
+        if (!overflow) break;
+        if (attempt >= 2) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffers of the pair join kept overflowing", hipSuccess);
+        if (total[0] > 0xffffffffull || total[1] > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "more than 2^32 hits of one mate in one batch", hipSuccess);
+        ctx->pair_cap = 0;
+    }
+    real_hip_pair *d_pairs = pairs;
+    const int fresh = bv[0].fresh != 0;
+    if (host_out) {
+        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
+        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
+        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = rh_launch_pair(ctx, *pp, (const real_hip_hit *)ctx->pair_hits[0].p, (const uint64_t *)ctx->pair_off[0].p, (const uint32_t *)ctx->pair_len[0].p, total[0],
+                        (const real_hip_hit *)ctx->pair_hits[1].p, (const uint64_t *)ctx->pair_off[1].p, (const uint32_t *)ctx->pair_len[1].p, total[1],
+                        n, ctx->fileid, fresh, d_pairs);
+    if (!rc && host_out) {
+        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_pair_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair stats struct_size", hipSuccess);
+    return rh_pair_stats(ctx, out, reset);
 }
 
 // ---------------------------------------------------------------------------

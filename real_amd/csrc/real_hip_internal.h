@@ -240,6 +240,12 @@ struct real_hip_ctx {
     // matchAll workspace
     DevBuf raw, raw_count, hit_cnt, big_list, all_cursor, keys_a, keys_b, vals_a, vals_b, sort_tmp, hit_off, s_hits;
 
+    // paired-end join (pair_kernel.hip): the two mates' hit lists, offsets and read lengths, staged records, the hand-over
+    // list of the wave kernel, striped statistics
+    DevBuf pair_hits[2], pair_off[2], pair_len[2], pair_rec, pair_list, pair_stats;
+    uint64_t pair_cap = 0;   // hits each of pair_hits[] holds (grown when a match overflowed it)
+    uint64_t pair_count = 0; // fragments joined since the last reset
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -300,6 +306,13 @@ int rh_max_patl(real_hip_ctx *ctx, const uint64_t *d_off, uint64_t n_reads, uint
 int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int fastq, int qoff, real_hip_parsed *out);
 int rh_all_finish(real_hip_ctx *ctx, uint64_t n_raw, uint64_t n_reads, real_hip_hit *d_out,
                   uint64_t *d_hit_offsets);
+
+// ---- paired-end join (pair_kernel.hip) ------------------------------------------
+int rh_pair_lens(real_hip_ctx *ctx, const uint64_t *d_off, uint32_t upatl, uint64_t n, uint32_t *d_len);
+int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
+                   uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
+                   uint32_t fileid, int fresh, real_hip_pair *d_pairs);
+int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

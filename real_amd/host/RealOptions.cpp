@@ -35,6 +35,9 @@ void RealOptions::printHelp() const
               << "-f <fraction of device memory to use for the index, default=0.75>\n"
               << "-q <compute scores, default=1>\n-Q <quality offset, default=autodetect>\n"
               << "-filter_level <0..4, default=2>\n-similarity -err -trans -gc -gcmut_bias <scoring parameters>\n"
+              << "-p2 <second pattern file: paired-end reads, read i of -p and of -p2 are mates (FR); one placement per fragment>\n"
+              << "-insert_min <smallest outer distance of a concordant pair, default=0>\n-insert_max <largest, default=1000>\n"
+              << "   (with -p2: needs -u 1 and -gpus 1; a genome file must fit one index block)\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -90,6 +93,9 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-prefix_bits") { prefix_bits = atoi(need("-prefix_bits").c_str()); i += 2; }
         else if (a == "-gpuparse") { gpuparse = atoi(need("-gpuparse").c_str()); i += 2; }
         else if (a == "-chunk") { chunk_bytes = strtoull(need("-chunk").c_str(), 0, 10); i += 2; }
+        else if (a == "-p2") { pattern2filename = need("-p2"); i += 2; }
+        else if (a == "-insert_min") { insert_min = (uint32_t)strtoul(need("-insert_min").c_str(), 0, 10); i += 2; }
+        else if (a == "-insert_max") { insert_max = (uint32_t)strtoul(need("-insert_max").c_str(), 0, 10); i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -150,6 +156,13 @@ RealOptions::RealOptions(int argc, char *argv[])
     filter_mult /= 70.0;
     std::cerr << "filter_mult=" << filter_mult << std::endl;
     if (gpus < 1) gpus = 1;
+    if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
+        if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0.");
+        if (gpus > 1) throw std::runtime_error("-p2 (paired-end reads) runs on one device: it cannot be combined with -gpus > 1.");
+        if (pattern2filename == "-" || !stdin_spool.empty()) throw std::runtime_error("-p2 (paired-end reads) needs two files: standard input cannot be one of them.");
+        if (insert_min > insert_max) throw std::runtime_error("-insert_min is larger than -insert_max.");
+        fastq2 = isFastQ(pattern2filename);
+    }
     if (chunk_bytes < 4096) chunk_bytes = 4096;
     if (chunk_bytes > (4ull << 30) - (1ull << 20)) chunk_bytes = (4ull << 30) - (1ull << 20); // real_hip_parse_reads: n_bytes < 4 GiB
 }

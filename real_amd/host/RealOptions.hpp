@@ -42,6 +42,11 @@ struct RealOptions {
     unsigned prefix_bits = 0;
     unsigned table_kind = 0;         // -table_kind: device bucket tables (real_hip.h), 0 = auto
     unsigned gpuparse = 1;           // -gpuparse: parse the read file on the device when it is in one-line-per-field form
+    // paired-end reads (no counterpart in the reference): -p holds mate 1, -p2 mate 2 of every fragment, in the same order
+    std::string pattern2filename;    // -p2
+    bool fastq2 = false;             // format of the -p2 file
+    uint32_t insert_min = 0;         // -insert_min / -insert_max: bounds of the outer distance of a concordant pair, inclusive
+    uint32_t insert_max = 1000;
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)
 
     RealOptions() {}

@@ -3,6 +3,7 @@
 //   host_selftest reads <reads> <fastq:0|1> <qoff> <outdir> -> bases.u8 qual.u8 off.u64 ids.txt (+ count, offset detect)
 //   host_selftest index <g.fa> <seedl> <first> <max> <threads> <outdir> -> l<k>_sign.bin l<k>_pos.u32 meta.txt
 //   host_selftest options <args...>               -> prints the parsed RealOptions
+//   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -114,6 +115,12 @@ int main(int argc, char **argv)
             std::cout << o.textfilename << " " << o.patternfilename << " " << o.outputfilename << " " << o.seedkmax << " " << o.totalkmax << " "
                       << o.seedl << " " << o.match_unique << " " << o.scores << " " << o.qualityOffset << " " << o.filter_level << " "
                       << o.filter_mult << " " << o.fastq << " " << o.gpus << " " << o.host_index << "\n";
+            return 0;
+        }
+        if (cmd == "pair_options") { // the paired-end flags: -p2 file ("." if none), its format, -insert_min, -insert_max, format of -p
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.pattern2filename.empty() ? "." : o.pattern2filename) << " " << o.fastq2 << " " << o.insert_min << " " << o.insert_max << " "
+                      << o.fastq << "\n";
             return 0;
         }
         return 2;

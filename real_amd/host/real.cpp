@@ -728,6 +728,100 @@ int matchAll(const RealOptions &o)
     return EXIT_SUCCESS;
 }
 
+// ---- paired-end reads: one placement per fragment ---------------------------------------------------------
+// No counterpart in the reference.  The two mate files are read in step by the host reader (read i of each are mates);
+// per genome file real_hip_match_pairs folds into the fragments' in/out records, as uniqueinfo[] folds for matchUnique.
+// A Unique fragment prints the 11-column line of mate 1 and then of mate 2; NoMatch / NonUnique print nothing.
+int matchPairs(const RealOptions &o)
+{
+    Timers T;
+    const double t_begin = now_s();
+    const int qoff1 = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
+    const int qoff2 = o.fastq2 ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.pattern2filename)) : 0;
+    if ((o.fastq && !qoff1) || (o.fastq2 && !qoff2)) throw std::runtime_error("Unable to automatically detect FastQ quality format.");
+    std::vector<std::string> files;
+    getFileList(o.textfilename, files);
+    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
+    if (files.size() > 64) throw std::runtime_error("more than 64 text files");
+    CtxVec ctx = makeContexts(o);
+    real_hip_ctx *h = ctx[0]->h;
+    real_hip_pair_params pp;
+    memset(&pp, 0, sizeof pp);
+    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    std::vector<real_hip_pair> pairs;
+    uint64_t numpat = 0;
+    Ranges RS;
+    ReadBlock b1, b2;
+    for (unsigned fi = 0; fi < files.size(); ++fi) {
+        std::cerr << "Processing file " << files[fi] << ((fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
+        Resident R;
+        double t0 = now_s();
+        R.G.load(files[fi]);
+        T.genome += now_s() - t0;
+        RS.names.push_back(R.G.frag_names); RS.starts.push_back(R.G.frag_start);
+        t0 = now_s();
+        setText(o, ctx, R, fi);
+        const uint64_t n_list = blockEntries(o, h, R.G.sym.size() ? R.G.sym.size() : 1);
+        bool have_next = false;
+        const uint64_t n = nextBlock(o, ctx, R, 0, n_list, have_next);
+        T.index += now_s() - t0;
+        if (have_next)
+            throw std::runtime_error("paired-end reads: " + files[fi] + " needs more than one index block (pairs across blocks would be lost); "
+                                     "raise -f / -block or split the file");
+        if (!n) continue;
+        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            t0 = now_s();
+            const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, false), n2 = r2.fillBlock(b2, o.batch_reads, false);
+            T.read += now_s() - t0;
+            if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
+            if (!n1) break;
+            if (seen + n1 > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n1, pairs.size() + pairs.size() / 2));
+            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
+            const double tm = now_s();
+            check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
+            T.match += now_s() - tm;
+            seen += n1;
+        }
+        if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
+        else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+    }
+    std::cerr << "All done." << std::endl;
+    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
+    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
+    std::vector<char> obuf((size_t)8 << 20);
+    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    uint64_t unique = 0, base = 0;
+    ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+    for (;;) {
+        const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
+        if (n1 != n2 || base + n1 > numpat) throw std::runtime_error("the read files changed between two passes");
+        if (!n1) break;
+        formatAndWrite(n1, out, T, [&](uint64_t i, std::string &s) {
+            const real_hip_pair &P = pairs[base + i];
+            if (P.state != REAL_HIP_PAIR_UNIQUE) return;
+            const std::string &fname = RS.names[P.fileid][P.frag];
+            const uint64_t fs = RS.starts[P.fileid][P.frag];
+            const uint64_t lo1 = b1.offsets[i], lo2 = b2.offsets[i];
+            appendLine(s, b1.ids[i].data(), b1.ids[i].size(), nullptr, &b1.bases[lo1], b1.offsets[i + 1] - lo1, o.scores, o.scores ? P.score1 : 0.f,
+                       P.inverted1 != 0, fname, (uint64_t)P.pos1 - fs + 1, P.k1);
+            appendLine(s, b2.ids[i].data(), b2.ids[i].size(), nullptr, &b2.bases[lo2], b2.offsets[i + 1] - lo2, o.scores, o.scores ? P.score2 : 0.f,
+                       P.inverted1 == 0, fname, (uint64_t)P.pos2 - fs + 1, P.k2);
+        });
+        base += n1;
+    }
+    if (base != numpat) throw std::runtime_error("the read files changed between two passes");
+    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
+    if (out != stdout) fclose(out);
+    for (uint64_t i = 0; i < numpat; ++i) unique += pairs[i].state == REAL_HIP_PAIR_UNIQUE;
+    std::cerr << "unique fragments: " << unique << std::endl;
+    T.reads = 2 * numpat; T.lines = 2 * unique; T.total = now_s() - t_begin;
+    T.print();
+    return EXIT_SUCCESS;
+}
+
 } // namespace
 
 int main(int argc, char *argv[])
@@ -735,6 +829,7 @@ int main(int argc, char *argv[])
     std::cerr << "This is real (MI355X read-matching path), ABI " << real_hip_abi_version() << "." << std::endl;
     try {
         RealOptions opts(argc, argv);
+        if (!opts.pattern2filename.empty()) return matchPairs(opts);
         return opts.match_unique ? matchUnique(opts) : matchAll(opts);
     } catch (const std::bad_alloc &) {
         std::cerr << "Insufficient memory." << std::endl;

@@ -26,6 +26,8 @@ REAL_HIP_MAX_PATL = 320
 REAL_HIP_MAX_PATL_LONG = 16384
 
 K_MATCH_UNIQUE, K_MATCH_ALL, K_ALL_SORT, K_INDEX, K_MATCH_REPEAT, K_PARSE = range(6)
+K_PAIR, K_PAIR_WAVE = 6, 7          # the paired-end join: lane per fragment, wave per handed-over fragment
+PAIR_NOMATCH, PAIR_UNIQUE, PAIR_NONUNIQUE = range(3)
 # resident index layouts, as real_hip_index_table_kind reports them (HipMatcher.table_kind)
 LAYOUT_STARTS, LAYOUT_DIGEST, LAYOUT_FINGERPRINT, LAYOUT_ROWS = range(4)
 
@@ -37,6 +39,7 @@ ABI_SYMBOLS = [
     "real_hip_index_table_kind", "real_hip_index_download", "real_hip_index_export", "real_hip_match_unique", "real_hip_match_all", "real_hip_match_unique_submit", "real_hip_wait",
     "real_hip_host_alloc", "real_hip_host_free",
     "real_hip_comm_id", "real_hip_comm_init", "real_hip_comm_destroy", "real_hip_gather_records", "real_hip_gather_hits",
+    "real_hip_pair_hits", "real_hip_match_pairs", "real_hip_pair_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -75,6 +78,21 @@ class RealHipCounters(C.Structure):
     def as_dict(self):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
+
+class RealHipPairParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("orientation", C.c_uint32)]
+
+
+class RealHipPairStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("products", C.c_uint64),
+                ("handed_over", C.c_uint64)]
+
+
+# real_hip_pair: the in/out record of one fragment
+PAIR_DTYPE = np.dtype([("best", "<f8"), ("second", "<f8"), ("pos1", "<u4"), ("pos2", "<u4"), ("score1", "<f4"), ("score2", "<f4"),
+                       ("frag", "<u2"), ("fileid", "u1"), ("k1", "u1"), ("k2", "u1"), ("inverted1", "u1"), ("state", "u1"),
+                       ("reserved", "u1")])
+assert PAIR_DTYPE.itemsize == 40
 
 HIT_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4"), ("score", "<f4"), ("frag", "<u2"),
                       ("k", "u1"), ("inverted", "u1")])
@@ -136,6 +154,9 @@ def load():
     L.real_hip_gather_records.argtypes = [vp, C.c_int, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
     L.real_hip_gather_hits.argtypes = [vp, C.c_int, vp, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
     L.real_hip_match_all.argtypes = [vp, C.POINTER(RealHipBatch), vp, u64, C.POINTER(u64), vp]
+    L.real_hip_pair_hits.argtypes = [vp, C.POINTER(RealHipPairParams), vp, vp, vp, vp, vp, vp, u64, u32, C.c_int, C.c_int, vp]
+    L.real_hip_match_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp]
+    L.real_hip_pair_stats_get.argtypes = [vp, C.POINTER(RealHipPairStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

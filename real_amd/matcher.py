@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _lib
-from .lib import (HIT_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
+from .lib import (HIT_DTYPE, PAIR_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
 
 NO_SCORE = np.float32(-np.finfo(np.float32).max)   # UniqueMatchInfo<true>() : score(-FLT_MAX), UniqueMatchInfo.hpp:191
 
@@ -47,6 +47,10 @@ class RealOptions:
     gc: float = 0.41
     gcmut_bias: float = 2.0
     gaps: bool = False
+    pattern2filename: str = ""      # -p2: paired-end reads, mate 2 of every fragment (this build; no counterpart in the reference)
+    insert_min: int = 0             # -insert_min / -insert_max: bounds of a concordant pair's outer distance
+    insert_max: int = 1000
+    gpus: int = 1
 
     def normalise(self) -> "RealOptions":
         """The clamps of RealOptions.cpp:172-180, 434-453."""
@@ -60,6 +64,13 @@ class RealOptions:
             raise ValueError("cannot handle seed length < 4")
         if self.seedkmax > 2:
             self.seedkmax = 2
+        if self.pattern2filename:       # the loud errors of `real -p2`
+            if not self.match_unique:
+                raise ValueError("-p2 (paired-end reads) cannot be combined with -u 0")
+            if self.gpus > 1:
+                raise ValueError("-p2 (paired-end reads) cannot be combined with -gpus > 1")
+            if self.insert_min > self.insert_max:
+                raise ValueError("-insert_min is larger than -insert_max")
         return self
 
     @property
@@ -84,7 +95,8 @@ class RealOptions:
                  "-R": ("rewritepatterns", lambda v: bool(int(v))), "-T": ("sort_threads", int),
                  "-g": ("gaps", lambda v: bool(int(v))), "-similarity": ("similarity", float), "-err": ("err", float),
                  "-trans": ("trans", float), "-gc": ("gc", float), "-gcmut_bias": ("gcmut_bias", float),
-                 "-filter_level": ("filter_level", int)}
+                 "-filter_level": ("filter_level", int), "-p2": ("pattern2filename", str), "-insert_min": ("insert_min", int),
+                 "-insert_max": ("insert_max", int), "-gpus": ("gpus", int)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -104,6 +116,14 @@ def new_unique_info(n: int, scores: bool = True) -> Tuple[np.ndarray, Optional[n
     info = np.zeros(n, dtype=np.uint64)
     score = np.full(n, NO_SCORE, dtype=np.float32) if scores else None
     return info, score
+
+
+def new_pair_info(n: int) -> np.ndarray:
+    """the records of n fragments before the first genome file: no pair, best = second = -inf (real_hip_pair)"""
+    rec = np.zeros(n, dtype=PAIR_DTYPE)
+    rec["best"] = -np.inf
+    rec["second"] = -np.inf
+    return rec
 
 
 def unpack_info(info: np.ndarray):
@@ -428,3 +448,73 @@ class UniqueMatcher(HipMatcher):
 class AllMatcher(HipMatcher):
     def match(self, bases, qual, offsets=None, patl: int = 0, **kw):
         return self.match_all(bases, qual, offsets, patl, **kw)
+
+
+class PairMatcher(AllMatcher):
+    """Paired-end reads: matchAll of both mates and the join of their hit lists on the device, one record per fragment
+    (real_hip_pair; semantics in include/real_hip.h and DESIGN.md).  The reference has no paired-end mode."""
+
+    @staticmethod
+    def _pair_params(min_insert: int, max_insert: int, orientation: int = 0) -> "_lib.RealHipPairParams":
+        pp = _lib.RealHipPairParams()
+        pp.struct_size = C.sizeof(_lib.RealHipPairParams)
+        pp.min_insert, pp.max_insert, pp.orientation = int(min_insert), int(max_insert), int(orientation)
+        return pp
+
+    new_pair_info = staticmethod(new_pair_info)
+
+    def _mate_batch(self, mate) -> RealHipBatch:
+        """mate: a synth.ReadBatch-like object (bases, qual, offsets) or a tuple (bases, qual, offsets)"""
+        bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
+        if isinstance(bases, np.ndarray):
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
+            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        self.sync_inputs(bases, qual, offsets)
+        b = self._batch(bases, qual, offsets, 0, None)
+        b._keep = (bases, qual, offsets)
+        return b
+
+    def match_pairs(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, orientation: int = 0):
+        """real_hip_match_pairs: mate i of mate1 and of mate2 belong together.  pairs: records to fold into (another genome
+        file's), None starts them.  Host batches give a numpy record array; device batches (torch tensors) need `pairs`
+        as a device tensor of 40-byte records."""
+        b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        fresh = pairs is None
+        if fresh:
+            pairs = new_pair_info(int(b1.n_reads))
+        b1.fresh = b2.fresh = int(fresh)
+        self.sync_inputs(pairs)
+        self._check(self._L.real_hip_match_pairs(self._h, C.byref(b1), C.byref(b2), C.byref(pp), _ptr(pairs)))
+        return pairs
+
+    def pair_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0, pairs=None,
+                  orientation: int = 0, fresh: Optional[bool] = None):
+        """real_hip_pair_hits: the join alone, on hit lists the caller holds (numpy arrays of lib.HIT_DTYPE / uint64 /
+        uint32, or device torch tensors of the same layout, all of one kind)."""
+        on_device = bool(getattr(off1, "is_cuda", False))
+        if not on_device:
+            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
+            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
+            len1, len2 = np.ascontiguousarray(len1, dtype=np.uint32), np.ascontiguousarray(len2, dtype=np.uint32)
+        n = int(off1.shape[0]) - 1
+        if int(off2.shape[0]) - 1 != n or int(len1.shape[0]) != n or int(len2.shape[0]) != n:
+            raise ValueError("the two mates' arrays describe different numbers of reads")
+        if fresh is None:
+            fresh = pairs is None
+        if pairs is None:
+            if on_device:
+                raise ValueError("device inputs need a device tensor for the records")
+            pairs = new_pair_info(n)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        self.sync_inputs(hits1, off1, len1, hits2, off2, len2, pairs)
+        self._check(self._L.real_hip_pair_hits(self._h, C.byref(pp), _ptr(hits1), _ptr(off1), _ptr(len1), _ptr(hits2), _ptr(off2), _ptr(len2),
+                                               n, int(fileid), int(on_device), int(bool(fresh)), _ptr(pairs)))
+        return pairs
+
+    def pair_stats(self, reset: bool = False) -> dict:
+        st = _lib.RealHipPairStats()
+        st.struct_size = C.sizeof(_lib.RealHipPairStats)
+        self._check(self._L.real_hip_pair_stats_get(self._h, C.byref(st), int(reset)))
+        return {"pairs": int(st.pairs), "products": int(st.products), "handed_over": int(st.handed_over)}

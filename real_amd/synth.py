@@ -289,3 +289,122 @@ def read_nflags(bases: np.ndarray, offsets: np.ndarray) -> np.ndarray:
     if idx.size:
         bad[np.searchsorted(offsets.astype(np.int64), idx, side="right") - 1] = True
     return np.packbits(bad, bitorder="little")
+
+
+def plant_pair_repeats(g: Genome, n_loci: int, span: int, gap: int, seed: int, avoid: Sequence = ()):
+    """Loci where pairing rescues a fragment: for each locus x the stretch [x, x+span) is copied to one far place and
+    [x+gap, x+gap+span) to another (``g.sym`` is changed in place).  A mate inside either stretch has two locations, a
+    fragment with one mate in each has one concordant placement.  Sources and destinations hold no N, no fragment cut and
+    nothing of ``avoid`` (a list of (start, end) ranges, e.g. the copies of repeat_family_genome).  Returns the x."""
+    rng = np.random.default_rng(seed)
+    n = g.n
+    busy = (g.sym > 3)
+    for c in g.frag_start[1:-1]:
+        busy[max(0, int(c) - 1):int(c) + 1] = True
+    for lo, hi in avoid:
+        busy[int(lo):int(hi)] = True
+    csum = np.concatenate([[0], np.cumsum(busy)])
+
+    def free(lo, hi):
+        return 0 <= lo and hi <= n and csum[hi] == csum[lo]
+
+    loci = []
+    tries = 0
+    while len(loci) < n_loci and tries < 200 * n_loci:
+        tries += 1
+        x, da, db = (int(v) for v in rng.integers(0, n - gap - span, size=3))
+        ranges = [(x, x + gap + span), (da, da + span), (db, db + span)]
+        if not all(free(lo, hi) for lo, hi in ranges):
+            continue
+        if any(a[0] < b[1] + gap + span and b[0] < a[1] + gap + span for i, a in enumerate(ranges) for b in ranges[i + 1:]):
+            continue        # (far apart: no second concordant placement)
+        g.sym[da:da + span] = g.sym[x:x + span]
+        g.sym[db:db + span] = g.sym[x + gap:x + gap + span]
+        for lo, hi in ranges:
+            busy[lo:hi] = True
+        csum = np.concatenate([[0], np.cumsum(busy)])
+        loci.append(x)
+    return loci
+
+
+def sample_pairs(g: Genome, n: int, patl1: int, patl2: int, insert_mean: float, insert_sd: float, errprob: float, seed: int,
+                 insert_min: Optional[int] = None, insert_max: Optional[int] = None, straddle_frac: float = 0.05,
+                 repeat_frac: float = 0.2, copies: Sequence = (), seg_len: int = 0, rescue_loci: Sequence = (),
+                 rescue_span: int = 0, rescue_gap: int = 0, rescue_frac: float = 0.05, q_ok: int = 35, q_mut: int = 9,
+                 with_ids: bool = True):
+    """Paired-end reads in FR orientation: a fragment [s, s+L) of the genome, L ~ N(insert_mean, insert_sd) rounded and
+    clipped to [insert_min, insert_max] (defaults: the longer mate .. mean + 4 sd); the forward mate is its first patl
+    bases, the other mate the reverse complement of its last ones; which of mate 1 / mate 2 is the forward one is a coin
+    flip.  Substitutions and qualities as sample_reads.  ``straddle_frac`` of the fragments contain a fragment cut of the
+    genome, ``repeat_frac`` have their forward mate wholly inside a copy of a repeat family (``copies``: what
+    repeat_family_genome returns, ``seg_len`` its segment length) with the fragment reaching out of it where it can, and
+    ``rescue_frac`` sit on a locus of plant_pair_repeats (one mate in each of the two stretches).  Returns two ReadBatches;
+    the ids are ``f<s>_<L>_<1|2>/<mate>`` (1|2: the forward mate), true_pos / true_inv hold each mate's own placement."""
+    rng = np.random.default_rng(seed)
+    N = g.n
+    lo_ins = max(patl1, patl2) if insert_min is None else int(insert_min)
+    hi_ins = int(round(insert_mean + 4 * insert_sd)) if insert_max is None else int(insert_max)
+    assert max(patl1, patl2) <= lo_ins <= hi_ins < N
+    L = np.clip(np.rint(rng.normal(insert_mean, insert_sd, size=n)), lo_ins, hi_ins).astype(np.int64)
+    s = (rng.random(n) * (N - L + 1)).astype(np.int64)
+    fwd1 = rng.integers(0, 2, size=n).astype(bool)                 # mate 1 is the forward mate
+    kind = rng.random(n)
+    pf = np.where(fwd1, patl1, patl2).astype(np.int64)             # length of the forward / of the reverse mate
+    pr = np.where(fwd1, patl2, patl1).astype(np.int64)
+    cuts = np.asarray(g.frag_start[1:-1], dtype=np.int64)
+    edge = 0.0
+    if cuts.size and straddle_frac > 0:
+        sel = np.nonzero(kind < straddle_frac)[0]
+        c = cuts[rng.integers(0, cuts.size, size=sel.size)]
+        s[sel] = np.clip(c - 1 - (rng.random(sel.size) * (L[sel] - 1)).astype(np.int64), 0, N - L[sel])
+        edge = straddle_frac
+    flat = np.array([p for fam in copies for p in fam], dtype=np.int64)
+    if flat.size and repeat_frac > 0 and seg_len >= max(patl1, patl2):
+        sel = np.nonzero((kind >= edge) & (kind < edge + repeat_frac))[0]
+        p = flat[rng.integers(0, flat.size, size=sel.size)]
+        room = np.maximum(L[sel] - pf[sel] - pr[sel], 0)            # the reverse mate can start this far behind the forward one's end
+        inside = rng.random(sel.size) < 0.5                         # half of them: the whole fragment inside the copy where it fits
+        off_out = seg_len - pf[sel] - (rng.random(sel.size) * (room + 1)).astype(np.int64)
+        off_in = (rng.random(sel.size) * np.maximum(seg_len - L[sel] + 1, 1)).astype(np.int64)
+        off = np.where(inside & (L[sel] <= seg_len), off_in, np.clip(off_out, 0, seg_len - pf[sel]))
+        s[sel] = np.clip(p + off, 0, N - L[sel])
+        edge += repeat_frac
+    if len(rescue_loci) and rescue_frac > 0 and rescue_span >= max(patl1, patl2):
+        sel = np.nonzero((kind >= edge) & (kind < edge + rescue_frac))[0]
+        x = np.asarray(rescue_loci, dtype=np.int64)[rng.integers(0, len(rescue_loci), size=sel.size)]
+        a = (rng.random(sel.size) * (rescue_span - pf[sel] + 1)).astype(np.int64)      # forward mate inside the first stretch
+        b = (rng.random(sel.size) * (rescue_span - pr[sel] + 1)).astype(np.int64)      # reverse mate inside the second
+        s[sel] = x + a
+        L[sel] = rescue_gap + b + pr[sel] - a
+    ok = (L >= np.maximum(pf, pr)) & (L >= lo_ins) & (L <= hi_ins) & (s >= 0) & (s + L <= N)
+    redo = np.nonzero(~ok)[0]                                      # (a rescue locus that cannot hold this insert: an ordinary fragment)
+    L[redo] = np.clip(np.rint(insert_mean), lo_ins, hi_ins).astype(np.int64)
+    s[redo] = (rng.random(redo.size) * (N - L[redo] + 1)).astype(np.int64)
+
+    def mate(patl, is_fwd):
+        start = np.where(is_fwd, s, s + L - patl)
+        rd = g.sym[start[:, None] + np.arange(patl, dtype=np.int64)[None, :]]
+        inv = ~is_fwd
+        rd[inv] = _COMP[rd[inv][:, ::-1]]
+        mut = rng.random(size=rd.shape) < errprob
+        delta = rng.integers(1, 4, size=rd.shape).astype(np.uint8)
+        orig = rd.copy()
+        rd = np.where(mut & (rd <= 3), (rd + delta) & 3, rd).astype(np.uint8)
+        qual = np.where(rd == orig, np.uint8(q_ok), np.uint8(q_mut)).astype(np.uint8)
+        return rd, qual, start, inv
+
+    out = []
+    for m, (patl, is_fwd) in enumerate(((patl1, fwd1), (patl2, ~fwd1))):
+        rd, qual, start, inv = mate(patl, is_fwd)
+        ids = None
+        if with_ids:
+            ids = ["f%d_%d_%d/%d" % (s[i], L[i], 1 if fwd1[i] else 2, m + 1) for i in range(n)]
+        out.append(ReadBatch(bases=rd.reshape(-1).copy(), qual=qual.reshape(-1).copy(),
+                             offsets=np.arange(n + 1, dtype=np.uint64) * np.uint64(patl), ids=ids,
+                             true_pos=start.astype(np.uint64), true_inv=inv))
+    return out[0], out[1]
+
+
+def ragged_pairs(pairs_a, pairs_b):
+    """two sample_pairs results (of different read lengths) as one ragged pair of batches"""
+    return concat_batches([pairs_a[0], pairs_b[0]]), concat_batches([pairs_a[1], pairs_b[1]])
