@@ -7,7 +7,9 @@ generator and on a genome with 5 % of its positions in 16-copy repeat families. 
     python bench_support/pairs_bench.py --tree /path/to/parent/checkout --out ...        # the baseline on another build
 
 --tree: import real_amd and bench from that checkout (built) instead of this one; a checkout without PairMatcher gives
-the baseline figures only.  Results are merged into --out under the key --label.
+the baseline figures only.  Results are merged into --out under the key --label.  A build with the mate search adds the
+search-on legs (real_hip_match_pairs_search: call time, the search kernel's own time, positions and placements per fragment,
+the states with the search off and on); the leg with reads at 4 % substitutions: --errprob 0.04 --ks 5 --genomes iid.
 """
 import argparse
 import ctypes as C
@@ -58,6 +60,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=25_000_000)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--genomes", default="iid,repeat")
+    ap.add_argument("--errprob", type=float, default=0.02)   # substitutions per base of the reads
+    ap.add_argument("--ks", default="2,3")                   # the -e values (totalkmax) measured
     args = ap.parse_args()
     sys.path.insert(0, args.tree)
     import numpy as np
@@ -68,7 +72,7 @@ def main():
     have_pairs = hasattr(rm, "PairMatcher")
     dev = torch.device("cuda", 0)
     G, n, patl, lo_ins, hi_ins = int(args.genome_mbp * 1e6), args.pairs, 100, 100, 420
-    result = {"genome_mbp": args.genome_mbp, "pairs": n, "patl": patl, "insert": [lo_ins, hi_ins], "steps": args.steps,
+    result = {"genome_mbp": args.genome_mbp, "pairs": n, "patl": patl, "insert": [lo_ins, hi_ins], "steps": args.steps, "errprob": args.errprob,
               "tree_has_match_pairs": have_pairs}
     for kind in args.genomes.split(","):
         sym = bench.gen_genome(torch, G, 3, dev)
@@ -80,7 +84,7 @@ def main():
             for c in range(15):
                 dst = torch.randint(0, G - 1000, (fam,), generator=gg).to(dev)
                 sym[(dst[:, None] + ar[None, :]).reshape(-1)] = sym[(src[:, None] + ar[None, :]).reshape(-1)]
-        (b1, q1), (b2, q2) = sample_pairs_device(torch, sym, n, patl, 300, 30, 0.02, 11, dev)
+        (b1, q1), (b2, q2) = sample_pairs_device(torch, sym, n, patl, 300, 30, args.errprob, 11, dev)
         torch.cuda.synchronize(); torch.cuda.empty_cache()
         Cls = rm.PairMatcher if have_pairs else rm.HipMatcher
         m = Cls(rm.RealOptions(seedl=32, seedkmax=2, totalkmax=2, scores=True).normalise(), device=0)
@@ -94,7 +98,7 @@ def main():
             rb = m._batch(b, q, None, patl, n)
             rb.on_device = 2                       # read arrays on the device, outputs in host memory
             return rb
-        for tk in (2, 3):
+        for tk in (int(v) for v in args.ks.split(",")):
             m.set_match_params(totalkmax=tk)
             key = "%s_k%d" % (kind, tk)
             r = {}
@@ -158,6 +162,25 @@ def main():
                 state = np.bincount(rec["state"], minlength=3)
                 r["states"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
                 r["record_bytes_downloaded"] = n * 40
+                if hasattr(m, "mate_search_stats"):         # the same call with the mate search behind the join
+                    sp = m._search_params(0)
+
+                    def run_search(on_device, out_ptr):
+                        rb1, rb2 = batch(b1, q1), batch(b2, q2)
+                        rb1.on_device = rb2.on_device = on_device
+                        rb1.fresh = rb2.fresh = 1
+                        t0 = time.perf_counter()
+                        m._check(L.real_hip_match_pairs_search(m._h, C.byref(rb1), C.byref(rb2), C.byref(pp), C.byref(sp), out_ptr))
+                        return (time.perf_counter() - t0) * 1e3
+                    run_search(2, rec.ctypes.data)
+                    m.mate_search_stats(reset=True)
+                    ts = [run_search(2, rec.ctypes.data) for _ in range(args.steps)]
+                    ms = m.mate_search_stats()
+                    r["match_pairs_search_ms"], r["match_pairs_search_ms_all_steps"] = min(ts), ts
+                    r["search_kernel_ms_per_call"] = ms["kernel_ms"] / max(ms["launches"], 1)
+                    r["search_per_fragment"] = {k: ms[k] / max(ms["fragments"], 1) for k in ("anchors", "positions", "placements")}
+                    state = np.bincount(rec["state"], minlength=3)
+                    r["states_search_on"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
             result[key] = r
             print(key, json.dumps(r), flush=True)
         m.close()

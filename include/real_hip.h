@@ -283,6 +283,55 @@ typedef struct real_hip_pair_stats {
 } real_hip_pair_stats;
 int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
 
+/* ---- mate search: place a mate the seeds missed (off unless these entry points are called).  real_hip_match_all finds a
+ * read only where its first seedl bases carry at most seedkmax mismatches; with pairs the other mate's hit says where
+ * the missing mate must lie, and every position there is compared over the whole read.
+ * A PLACEMENT of a read on a strand at text position p is what real_hip_match_all would report there if the seed filter
+ * did not exist: the read (reverse-complemented for inverted = 1) lies inside one fragment, the window holds no N and
+ * the Hamming distance to the text is k <= totalkmax; score as real_hip_match_all computes it (1.0f if !scores), frag
+ * the fragment of p.  An ANCHOR is a real_hip_match_all hit of either mate.  The WINDOW of an anchor a is the set of
+ * positions p at which a hit of the OTHER mate on the OPPOSITE strand would be concordant with a (the definition above,
+ * either mate forward) and lie wholly inside a's fragment; every position of the window is tested for a placement.
+ * The candidate set of a fragment in one genome file becomes: all concordant pairs of two hits (as before) PLUS all
+ * pairs (anchor, placement found in its window) -- every concordant pair of placements of which at least one mate was
+ * found by the seeds.  A location counts once (a placement that is also a hit adds nothing: score and k are functions
+ * of the location); value, location, best / second, eps, the states and the fold across files are unchanged, and the
+ * set does not depend on the order of hits, lanes or files.  A fragment with a mate the matcher skips (shorter than
+ * seedl, a symbol > 3) is not searched.  max_anchors (0 = no limit): a mate with more than max_anchors hits in this
+ * file contributes no anchors (its hits still join); the rule looks at the count only.
+ * Limits (REAL_HIP_E_UNSUPPORTED before anything is launched): a read longer than REAL_HIP_MAX_PATL, max_insert beyond
+ * REAL_HIP_MATE_SEARCH_MAX_INSERT (the text of one window sits in the wave's LDS).                                    */
+#define REAL_HIP_MATE_SEARCH_MAX_INSERT 4096u
+typedef struct real_hip_mate_search_params {
+    uint32_t struct_size;   /* = sizeof(real_hip_mate_search_params)                                  */
+    uint32_t max_anchors;   /* 0 = no limit                                                           */
+    uint32_t reserved[2];   /* 0                                                                      */
+} real_hip_mate_search_params;
+/* The search alone, on anchors the caller holds: folds the pairs (anchor, placement in its window) into the in/out
+ * records (fresh != 0: output only).  hits_m[off_m[i] .. off_m[i+1]) are the anchors of mate m of fragment i, batch1 /
+ * batch2 the mates' reads (same n_reads and on_device; on_device says where ALL pointers of the call live: 0 host
+ * memory (copied), 1 device).  Needs the text, not the index.  real_hip_pair_hits followed by this gives the full
+ * candidate set: the form for a genome file of several index blocks.                                             */
+int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_mate_search_params *sp,
+                         const real_hip_batch *batch1, const real_hip_batch *batch2,
+                         const real_hip_hit *hits1, const uint64_t *off1, const real_hip_hit *hits2, const uint64_t *off2,
+                         uint32_t fileid, int fresh, real_hip_pair *pairs);
+/* real_hip_match_pairs with the search behind the join: only the pair records cross to the host                   */
+int real_hip_match_pairs_search(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs);
+/* work of the search, accumulated since the last reset; kernel_ms: HIP events on the ctx's stream around the kernel */
+typedef struct real_hip_mate_search_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_mate_search_stats), 0                        */
+    uint64_t fragments;       /* fragments handed to the search                                       */
+    uint64_t anchors;         /* anchors whose window was searched                                    */
+    uint64_t anchors_skipped; /* hits that were no anchors because their mate had more than max_anchors */
+    uint64_t positions;       /* window positions tested                                              */
+    uint64_t placements;      /* placements found (per anchor: one seen from two anchors counts twice) */
+    uint64_t launches;
+    double   kernel_ms;
+} real_hip_mate_search_stats;
+int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

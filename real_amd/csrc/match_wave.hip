@@ -149,31 +149,6 @@ __device__ __forceinline__ uint32_t long_distance(const uint64_t *__restrict__ T
     return total;
 }
 
-// ComputeScore<...,true>::computeScore (ComputeScore.hpp:50-190) for a long read: the same sequential FP64 sum in base order
-__device__ __forceinline__ float long_score(const double *sLL, const uint64_t *__restrict__ T, const uint64_t *cur, uint32_t pos, uint32_t patl,
-                                            const uint8_t *qual, uint32_t inv)
-{
-    const uint64_t wi = pos >> 5;
-    const unsigned sh = 2u * (pos & 31);
-    const uint32_t nw = (patl + 31) >> 5;
-    double raw = 1.0;
-    uint64_t t0 = T[wi];
-    for (uint32_t j = 0; j < nw; ++j) {
-        const uint64_t t1 = T[wi + j + 1];
-        const uint64_t al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
-        const uint64_t rw = cur[j];
-        const uint32_t nb = min(32u, patl - 32u * j);
-        for (uint32_t u = 0; u < nb; ++u) {
-            const uint32_t i = 32u * j + u;
-            const uint32_t ref = (uint32_t)(al >> (62 - 2 * u)) & 3u, rb = (uint32_t)(rw >> (62 - 2 * u)) & 3u;
-            const uint32_t q = qual ? (uint32_t)qual[inv ? patl - 1 - i : i] : 30u; // no qualities => 30 (Pattern.hpp:42-45)
-            raw += sLL[((ref << 8) | (rb << 6) | q) & 1023];
-        }
-        t0 = t1;
-    }
-    return (float)raw;
-}
-
 // the score of the location at pos if the wave has computed it for this strand already (n = wave-uniform number of entries)
 __device__ __forceinline__ bool memo_score(const uint32_t *mpos, const float *msc, uint32_t n, uint32_t pos, float &sc)
 {

@@ -94,7 +94,10 @@ void rh_time_resolve(real_hip_ctx *c)
     for (auto &p : c->pending) {
         if (p.a && p.b && hipEventQuery(p.b) == hipSuccess) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
+            if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
+                if (p.which == RH_K_MATE_SEARCH) c->ms_kernel_ms += ms;
+                else { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
+            }
             c->ev_pool.push_back(p.a);
             c->ev_pool.push_back(p.b);
         } else {
@@ -217,7 +220,8 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
                      &c->keys_b, &c->vals_a, &c->vals_b, &c->sort_tmp, &c->hit_off, &c->s_hits, &c->s_nflags};
     for (DevBuf *b : all) rh_release(*b);
     for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
-    DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats};
+    DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats,
+                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats};
     for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
@@ -471,9 +475,11 @@ static int batch_view(real_hip_ctx *ctx, const real_hip_batch *b, real_hip_batch
 
 // Uploads (host batches; on `up`, which is ctx->stream for the synchronous calls and the copy stream for submitted ones).
 // After it the arrays of `s` are valid for kernels on ctx->stream.
-static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, const StageBufs &sb, hipStream_t up, hipEvent_t up_done)
+static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, const StageBufs &sb, hipStream_t up, hipEvent_t up_done,
+                       bool need_index = true)
 {
-    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    if (!ctx->have_text || (need_index && !ctx->have_index))
+        return rh_fail(ctx, REAL_HIP_E_STATE, need_index ? "text and index must be set" : "the text must be set", hipSuccess);
     if (b.n_reads > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one batch", hipSuccess);
     const uint64_t n = b.n_reads;
     if (!n) return REAL_HIP_OK;
@@ -706,14 +712,16 @@ extern "C" void real_hip_host_free(void *p)
 }
 
 // matchAll of one batch; dev_out: out / hit_offsets are device memory whatever the batch's inputs are.  staged (nullable)
-// receives the device view of the batch's arrays (valid until the next batch is staged).
+// receives the device view of the batch's arrays (valid until the next batch is staged into the same buffers: bufs, or the
+// ctx's own).
 static int match_all_run(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_out, real_hip_hit *out, uint64_t cap,
-                         uint64_t *n_out, uint64_t *hit_offsets, Staged *staged)
+                         uint64_t *n_out, uint64_t *hit_offsets, Staged *staged, const StageBufs *bufs = nullptr)
 {
     Staged s;
     int rc;
     const real_hip_batch *b = &bv;
-    if ((rc = stage_batch(ctx, bv, s, StageBufs{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, ctx->stream, nullptr))) return rc;
+    const StageBufs own{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags};
+    if ((rc = stage_batch(ctx, bv, s, bufs ? *bufs : own, ctx->stream, nullptr))) return rc;
     const uint64_t n = b->n_reads;
     if (n_out) *n_out = 0;
     if (cap > 0xffffffffull) cap = 0xffffffffull; // record indices are 32 bit inside the post-pass
@@ -777,6 +785,40 @@ static int pair_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp)
     return REAL_HIP_OK;
 }
 
+// the two mates' hit lists of n fragments as the caller holds them -> device views: the offsets start at 0 and do not run
+// backwards, off[n] is the number of hits; host lists are copied into the ctx's pair buffers
+static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *d_h[2], const uint64_t *d_o[2], uint64_t total[2], uint64_t n, bool on_device)
+{
+    int rc;
+    for (int m = 0; m < 2; ++m) {
+        if (on_device) {
+            uint64_t ends[1] = {0}, first = 0;
+            RH_HIP(ctx, hipMemcpyAsync(&first, d_o[m], 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(ends, d_o[m] + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            if (first) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
+            total[m] = ends[0]; // (offsets in between are clamped to it by the kernels)
+        } else {
+            const uint64_t *o = d_o[m];
+            if (o[0]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
+            for (uint64_t i = 0; i < n; ++i)
+                if (o[i + 1] < o[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets not monotone", hipSuccess);
+            total[m] = o[n];
+        }
+        if (total[m] && !d_h[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
+    }
+    if (on_device) return REAL_HIP_OK;
+    for (int m = 0; m < 2; ++m) {
+        if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total[m] ? total[m] : 1) * sizeof(real_hip_hit)))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
+        if (total[m]) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, d_h[m], total[m] * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
+        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, d_o[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        d_h[m] = (const real_hip_hit *)ctx->pair_hits[m].p; d_o[m] = (const uint64_t *)ctx->pair_off[m].p;
+    }
+    ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
+    return REAL_HIP_OK;
+}
+
 extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
                                   const uint32_t *len1, const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
                                   uint64_t n_pairs, uint32_t fileid, int on_device, int fresh, real_hip_pair *pairs)
@@ -794,34 +836,13 @@ extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params 
     const uint32_t *d_l[2] = {len1, len2};
     uint64_t total[2] = {0, 0};
     real_hip_pair *d_pairs = pairs;
-    for (int m = 0; m < 2; ++m) { // the offsets start at 0 and do not run backwards; off[n] is the number of hits
-        if (on_device) {
-            uint64_t ends[1] = {0}, first = 0;
-            RH_HIP(ctx, hipMemcpyAsync(&first, d_o[m], 8, hipMemcpyDeviceToHost, ctx->stream));
-            RH_HIP(ctx, hipMemcpyAsync(ends, d_o[m] + n, 8, hipMemcpyDeviceToHost, ctx->stream));
-            RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (first) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
-            total[m] = ends[0]; // (offsets in between are clamped to it by the kernels)
-        } else {
-            const uint64_t *o = d_o[m];
-            if (o[0]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
-            for (uint64_t i = 0; i < n; ++i)
-                if (o[i + 1] < o[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets not monotone", hipSuccess);
-            total[m] = o[n];
-        }
-        if (total[m] && !d_h[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
-    }
+    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0))) return rc;
     if (!on_device) {
         for (int m = 0; m < 2; ++m) {
-            if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total[m] ? total[m] : 1) * sizeof(real_hip_hit)))) return rc;
-            if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
             if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
-            if (total[m]) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, d_h[m], total[m] * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
-            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, d_o[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
             RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, d_l[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_h[m] = (const real_hip_hit *)ctx->pair_hits[m].p; d_o[m] = (const uint64_t *)ctx->pair_off[m].p; d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
+            d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
         }
-        ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
         if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
         d_pairs = (real_hip_pair *)ctx->pair_rec.p;
         if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
@@ -838,20 +859,108 @@ extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params 
     return REAL_HIP_OK;
 }
 
-extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
-                                    const real_hip_pair_params *pp, real_hip_pair *pairs)
+// ---- mate search (mate_search.hip): what both of its entry points check before anything is launched
+static int search_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_mate_search_params *sp)
+{
+    if (!sp || sp->struct_size != sizeof(real_hip_mate_search_params)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mate search params struct_size", hipSuccess);
+    if (pp->max_insert > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "mate search: max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
+    return REAL_HIP_OK;
+}
+// the two mates' batches: equal in n_reads and on_device, no read longer than REAL_HIP_MAX_PATL
+static int search_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2])
+{
+    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
+    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one batch", hipSuccess);
+    for (int m = 0; m < 2 && n; ++m) {
+        const real_hip_batch &b = bv[m];
+        uint64_t longest = b.patl;
+        if (b.offsets && !b.on_device) {
+            longest = 0;
+            for (uint64_t i = 0; i < n; ++i)
+                if (b.offsets[i + 1] >= b.offsets[i] && b.offsets[i + 1] - b.offsets[i] > longest) longest = b.offsets[i + 1] - b.offsets[i];
+        } else if (b.offsets) {
+            uint32_t mp = b.max_patl; // (the declared bound; a read beyond it is caught by the kernel: E_INVALID)
+            int rc;
+            if (!mp && (rc = rh_max_patl(ctx, b.offsets, n, &mp))) return rc;
+            longest = mp;
+        }
+        if (longest > REAL_HIP_MAX_PATL) return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "mate search: read longer than REAL_HIP_MAX_PATL", hipSuccess);
+    }
+    return REAL_HIP_OK;
+}
+static DevBatch dev_batch(real_hip_ctx *ctx, const Staged &s, uint64_t n)
+{
+    DevBatch b;
+    memset(&b, 0, sizeof b);
+    b.bases = s.bases; b.qual = ctx->prm.scores ? s.qual : nullptr; b.off = s.off;
+    b.n_reads = n; b.upatl = s.upatl; b.W = s.W; b.maxpatl = s.maxpatl; b.packed = s.packed; b.nflags = s.nflags;
+    return b;
+}
+
+extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_mate_search_params *sp,
+                                    const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_hit *hits1, const uint64_t *off1,
+                                    const real_hip_hit *hits2, const uint64_t *off2, uint32_t fileid, int fresh, real_hip_pair *pairs)
 {
     RH_ENTER(ctx);
     int rc = pair_params_check(ctx, pp);
+    if (rc || (rc = search_params_check(ctx, pp, sp))) return rc;
+    if (fileid > 255) return rh_fail(ctx, REAL_HIP_E_INVALID, "fileid > 255", hipSuccess);
+    real_hip_batch bv[2];
+    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
+    if (bv[0].on_device > 1) return rh_fail(ctx, REAL_HIP_E_INVALID, "real_hip_pair_search: on_device is 0 or 1", hipSuccess);
+    if (!ctx->have_text) return rh_fail(ctx, REAL_HIP_E_STATE, "the text must be set", hipSuccess);
+    if ((rc = search_batches_check(ctx, bv))) return rc;
+    const uint64_t n = bv[0].n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (!off1 || !off2 || !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / pairs", hipSuccess);
+    const bool on_device = bv[0].on_device == 1;
+    const real_hip_hit *d_h[2] = {hits1, hits2};
+    const uint64_t *d_o[2] = {off1, off2};
+    uint64_t total[2] = {0, 0};
+    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device))) return rc;
+    Staged st[2];
+    const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], bufs[m], ctx->stream, nullptr, false))) return rc;
+    real_hip_pair *d_pairs = pairs;
+    if (!on_device) {
+        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
+        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
+        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), d_h[0], d_o[0], total[0], d_h[1], d_o[1], total[1],
+                               n, fileid, fresh, d_pairs);
+    if (!rc && !on_device) {
+        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
+    rh_time_resolve(ctx);
     if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return rh_mate_search_finish(ctx);
+}
+
+// real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join
+static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_pair_params *pp,
+                           const real_hip_mate_search_params *sp, real_hip_pair *pairs)
+{
+    int rc;
     real_hip_batch bv[2];
     if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
     if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
     if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
     if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    if (sp && (rc = search_batches_check(ctx, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
     if (!n) return REAL_HIP_OK;
     if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pairs", hipSuccess);
+    // the search needs both mates' reads on the device at once: mate 2 is staged into buffers of its own then
+    Staged st[2];
+    const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
     const bool host_out = bv[0].on_device != 1;
     uint64_t total[2] = {0, 0};
     for (int m = 0; m < 2; ++m) {
@@ -872,8 +981,10 @@ extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *bat
         }
         bool overflow = false;
         for (int m = 0; m < 2; ++m) {
-            Staged s;
-            rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s);
+            Staged &s = st[m];
+            s = Staged();
+            rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s,
+                               sp ? &bufs[m] : nullptr);
             if (rc == REAL_HIP_E_OVERFLOW) { overflow = true; continue; } // (the other mate still reports its size)
             if (rc) return rc;
             // the read lengths, while this mate's offsets are staged
@@ -894,6 +1005,10 @@ extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *bat
     rc = rh_launch_pair(ctx, *pp, (const real_hip_hit *)ctx->pair_hits[0].p, (const uint64_t *)ctx->pair_off[0].p, (const uint32_t *)ctx->pair_len[0].p, total[0],
                         (const real_hip_hit *)ctx->pair_hits[1].p, (const uint64_t *)ctx->pair_off[1].p, (const uint32_t *)ctx->pair_len[1].p, total[1],
                         n, ctx->fileid, fresh, d_pairs);
+    if (!rc && sp) // the records of the join are the search's in/out records
+        rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), (const real_hip_hit *)ctx->pair_hits[0].p,
+                                   (const uint64_t *)ctx->pair_off[0].p, total[0], (const real_hip_hit *)ctx->pair_hits[1].p,
+                                   (const uint64_t *)ctx->pair_off[1].p, total[1], n, ctx->fileid, 0, d_pairs);
     if (!rc && host_out) {
         hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
@@ -902,7 +1017,32 @@ extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *bat
     rh_time_resolve(ctx);
     if (rc) return rc;
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return REAL_HIP_OK;
+    return sp ? rh_mate_search_finish(ctx) : REAL_HIP_OK;
+}
+
+extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                    const real_hip_pair_params *pp, real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    return match_pairs_run(ctx, batch1, batch2, pp, nullptr, pairs);
+}
+
+extern "C" int real_hip_match_pairs_search(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                           const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc || (rc = search_params_check(ctx, pp, sp))) return rc;
+    return match_pairs_run(ctx, batch1, batch2, pp, sp, pairs);
+}
+
+extern "C" int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_mate_search_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mate search stats struct_size", hipSuccess);
+    return rh_mate_search_stats(ctx, out, reset);
 }
 
 extern "C" int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset)

@@ -246,6 +246,13 @@ struct real_hip_ctx {
     uint64_t pair_cap = 0;   // hits each of pair_hits[] holds (grown when a match overflowed it)
     uint64_t pair_count = 0; // fragments joined since the last reset
 
+    // mate search (mate_search.hip): staging of mate 2's reads (both mates are resident while it runs), striped statistics
+    // followed by the kernel's error flags, the event times of its launches
+    DevBuf s2_bases, s2_qual, s2_off, s2_nflags, ms_stats;
+    uint64_t ms_fragments = 0, ms_launches = 0;
+    double   ms_kernel_ms = 0;
+    uint32_t ms_err = 0;     // the flags of the last launch, copied back behind it
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -313,6 +320,15 @@ int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real
                    uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
                    uint32_t fileid, int fresh, real_hip_pair *d_pairs);
 int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
+
+// ---- mate search (mate_search.hip) ----------------------------------------------
+#define RH_K_MATE_SEARCH (-1) /* rh_time_begin: the time goes to ctx->ms_kernel_ms (REAL_HIP_K_COUNT is part of the ABI) */
+// asynchronous on the ctx's stream; after the stream was synchronised rh_mate_search_finish reports what the kernel flagged
+int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_mate_search_params &sp, const DevBatch &b1,
+                          const DevBatch &b2, const real_hip_hit *d_h1, const uint64_t *d_o1, uint64_t total1, const real_hip_hit *d_h2,
+                          const uint64_t *d_o2, uint64_t total2, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
+int rh_mate_search_finish(real_hip_ctx *ctx);
+int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

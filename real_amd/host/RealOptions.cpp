@@ -1,10 +1,13 @@
 #include "RealOptions.hpp"
 
+#include "real_hip.h"
+
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
 #include <stdexcept>
+#include <string>
 #include <vector>
 #include <unistd.h>
 
@@ -38,6 +41,9 @@ void RealOptions::printHelp() const
               << "-p2 <second pattern file: paired-end reads, read i of -p and of -p2 are mates (FR); one placement per fragment>\n"
               << "-insert_min <smallest outer distance of a concordant pair, default=0>\n-insert_max <largest, default=1000>\n"
               << "   (with -p2: needs -u 1 and -gpus 1; a genome file must fit one index block)\n"
+              << "-mate_search <0|1: with -p2, search the window every hit of one mate allows for a placement of the other mate that\n"
+              << "   the seeds missed (more than -s mismatches in its first -l bases, at most -e in the whole read), default=0>\n"
+              << "-mate_search_anchors <a mate with more hits than this in a genome file starts no search, 0=no limit, default=0>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -96,6 +102,8 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-p2") { pattern2filename = need("-p2"); i += 2; }
         else if (a == "-insert_min") { insert_min = (uint32_t)strtoul(need("-insert_min").c_str(), 0, 10); i += 2; }
         else if (a == "-insert_max") { insert_max = (uint32_t)strtoul(need("-insert_max").c_str(), 0, 10); i += 2; }
+        else if (a == "-mate_search") { mate_search = atoi(need("-mate_search").c_str()) != 0; mate_search_given = true; i += 2; }
+        else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -161,7 +169,11 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (gpus > 1) throw std::runtime_error("-p2 (paired-end reads) runs on one device: it cannot be combined with -gpus > 1.");
         if (pattern2filename == "-" || !stdin_spool.empty()) throw std::runtime_error("-p2 (paired-end reads) needs two files: standard input cannot be one of them.");
         if (insert_min > insert_max) throw std::runtime_error("-insert_min is larger than -insert_max.");
+        if (mate_search && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+            throw std::runtime_error("-mate_search 1 takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
         fastq2 = isFastQ(pattern2filename);
+    } else if (mate_search_given) {
+        throw std::runtime_error("-mate_search / -mate_search_anchors are only meaningful with -p2 (paired-end reads).");
     }
     if (chunk_bytes < 4096) chunk_bytes = 4096;
     if (chunk_bytes > (4ull << 30) - (1ull << 20)) chunk_bytes = (4ull << 30) - (1ull << 20); // real_hip_parse_reads: n_bytes < 4 GiB

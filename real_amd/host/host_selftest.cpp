@@ -123,6 +123,11 @@ int main(int argc, char **argv)
                       << o.fastq << "\n";
             return 0;
         }
+        if (cmd == "mate_search_options") { // -mate_search, -mate_search_anchors
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << o.mate_search << " " << o.mate_search_anchors << "\n";
+            return 0;
+        }
         return 2;
     } catch (const std::exception &e) {
         std::cerr << e.what() << std::endl;

@@ -730,7 +730,8 @@ int matchAll(const RealOptions &o)
 
 // ---- paired-end reads: one placement per fragment ---------------------------------------------------------
 // No counterpart in the reference.  The two mate files are read in step by the host reader (read i of each are mates);
-// per genome file real_hip_match_pairs folds into the fragments' in/out records, as uniqueinfo[] folds for matchUnique.
+// per genome file real_hip_match_pairs (-mate_search 1: real_hip_match_pairs_search) folds into the fragments' in/out
+// records, as uniqueinfo[] folds for matchUnique.
 // A Unique fragment prints the 11-column line of mate 1 and then of mate 2; NoMatch / NonUnique print nothing.
 int matchPairs(const RealOptions &o)
 {
@@ -748,6 +749,9 @@ int matchPairs(const RealOptions &o)
     real_hip_pair_params pp;
     memset(&pp, 0, sizeof pp);
     pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    real_hip_mate_search_params sp; // -mate_search 1: the search behind the join
+    memset(&sp, 0, sizeof sp);
+    sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     uint64_t numpat = 0;
     Ranges RS;
@@ -781,7 +785,8 @@ int matchPairs(const RealOptions &o)
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
             const double tm = now_s();
-            check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
+            if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, pairs.data() + seen), "real_hip_match_pairs_search");
+            else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
             T.match += now_s() - tm;
             seen += n1;
         }

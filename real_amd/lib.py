@@ -24,6 +24,7 @@ REAL_HIP_E_STATE = -5
 REAL_HIP_E_UNSUPPORTED = -6
 REAL_HIP_MAX_PATL = 320
 REAL_HIP_MAX_PATL_LONG = 16384
+REAL_HIP_MATE_SEARCH_MAX_INSERT = 4096   # the widest insert bound the mate search takes
 
 K_MATCH_UNIQUE, K_MATCH_ALL, K_ALL_SORT, K_INDEX, K_MATCH_REPEAT, K_PARSE = range(6)
 K_PAIR, K_PAIR_WAVE = 6, 7          # the paired-end join: lane per fragment, wave per handed-over fragment
@@ -40,6 +41,7 @@ ABI_SYMBOLS = [
     "real_hip_host_alloc", "real_hip_host_free",
     "real_hip_comm_id", "real_hip_comm_init", "real_hip_comm_destroy", "real_hip_gather_records", "real_hip_gather_hits",
     "real_hip_pair_hits", "real_hip_match_pairs", "real_hip_pair_stats_get",
+    "real_hip_pair_search", "real_hip_match_pairs_search", "real_hip_mate_search_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -86,6 +88,16 @@ class RealHipPairParams(C.Structure):
 class RealHipPairStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("products", C.c_uint64),
                 ("handed_over", C.c_uint64)]
+
+
+class RealHipMateSearchParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_anchors", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class RealHipMateSearchStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fragments", C.c_uint64), ("anchors", C.c_uint64),
+                ("anchors_skipped", C.c_uint64), ("positions", C.c_uint64), ("placements", C.c_uint64), ("launches", C.c_uint64),
+                ("kernel_ms", C.c_double)]
 
 
 # real_hip_pair: the in/out record of one fragment
@@ -157,6 +169,11 @@ def load():
     L.real_hip_pair_hits.argtypes = [vp, C.POINTER(RealHipPairParams), vp, vp, vp, vp, vp, vp, u64, u32, C.c_int, C.c_int, vp]
     L.real_hip_match_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp]
     L.real_hip_pair_stats_get.argtypes = [vp, C.POINTER(RealHipPairStats), C.c_int]
+    L.real_hip_pair_search.argtypes = [vp, C.POINTER(RealHipPairParams), C.POINTER(RealHipMateSearchParams), C.POINTER(RealHipBatch),
+                                       C.POINTER(RealHipBatch), vp, vp, vp, vp, u32, C.c_int, vp]
+    L.real_hip_match_pairs_search.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
+                                              C.POINTER(RealHipMateSearchParams), vp]
+    L.real_hip_mate_search_stats_get.argtypes = [vp, C.POINTER(RealHipMateSearchStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

@@ -50,6 +50,8 @@ class RealOptions:
     pattern2filename: str = ""      # -p2: paired-end reads, mate 2 of every fragment (this build; no counterpart in the reference)
     insert_min: int = 0             # -insert_min / -insert_max: bounds of a concordant pair's outer distance
     insert_max: int = 1000
+    mate_search: bool = False       # -mate_search: search every hit's window for a placement of the other mate the seeds missed
+    mate_search_anchors: int = 0    # -mate_search_anchors: a mate with more hits than this contributes no anchors (0: no limit)
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -71,6 +73,12 @@ class RealOptions:
                 raise ValueError("-p2 (paired-end reads) cannot be combined with -gpus > 1")
             if self.insert_min > self.insert_max:
                 raise ValueError("-insert_min is larger than -insert_max")
+            if self.mate_search and self.insert_max > _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT:
+                raise ValueError("-mate_search 1 takes an -insert_max of at most %d" % _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        elif self.mate_search or self.mate_search_anchors:
+            raise ValueError("-mate_search / -mate_search_anchors need -p2 (paired-end reads)")
+        if self.mate_search_anchors < 0:
+            raise ValueError("-mate_search_anchors must not be negative")
         return self
 
     @property
@@ -96,7 +104,8 @@ class RealOptions:
                  "-g": ("gaps", lambda v: bool(int(v))), "-similarity": ("similarity", float), "-err": ("err", float),
                  "-trans": ("trans", float), "-gc": ("gc", float), "-gcmut_bias": ("gcmut_bias", float),
                  "-filter_level": ("filter_level", int), "-p2": ("pattern2filename", str), "-insert_min": ("insert_min", int),
-                 "-insert_max": ("insert_max", int), "-gpus": ("gpus", int)}
+                 "-insert_max": ("insert_max", int), "-gpus": ("gpus", int),
+                 "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -475,19 +484,66 @@ class PairMatcher(AllMatcher):
         b._keep = (bases, qual, offsets)
         return b
 
-    def match_pairs(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, orientation: int = 0):
+    @staticmethod
+    def _search_params(max_anchors: int = 0) -> "_lib.RealHipMateSearchParams":
+        sp = _lib.RealHipMateSearchParams()
+        sp.struct_size = C.sizeof(_lib.RealHipMateSearchParams)
+        sp.max_anchors = int(max_anchors)
+        return sp
+
+    def match_pairs(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, orientation: int = 0,
+                    mate_search: bool = False, max_anchors: int = 0, fresh: Optional[bool] = None):
         """real_hip_match_pairs: mate i of mate1 and of mate2 belong together.  pairs: records to fold into (another genome
         file's), None starts them.  Host batches give a numpy record array; device batches (torch tensors) need `pairs`
-        as a device tensor of 40-byte records."""
+        as a device tensor of 40-byte records (fresh=True: output only).  mate_search: real_hip_match_pairs_search -- every
+        hit's window is searched for a placement of the other mate the seeds missed (max_anchors: 0 = no limit)."""
         b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
         pp = self._pair_params(min_insert, max_insert, orientation)
-        fresh = pairs is None
-        if fresh:
+        if fresh is None:
+            fresh = pairs is None
+        if pairs is None:
             pairs = new_pair_info(int(b1.n_reads))
-        b1.fresh = b2.fresh = int(fresh)
+        b1.fresh = b2.fresh = int(bool(fresh))
         self.sync_inputs(pairs)
-        self._check(self._L.real_hip_match_pairs(self._h, C.byref(b1), C.byref(b2), C.byref(pp), _ptr(pairs)))
+        if mate_search:
+            sp = self._search_params(max_anchors)
+            self._check(self._L.real_hip_match_pairs_search(self._h, C.byref(b1), C.byref(b2), C.byref(pp), C.byref(sp), _ptr(pairs)))
+        else:
+            self._check(self._L.real_hip_match_pairs(self._h, C.byref(b1), C.byref(b2), C.byref(pp), _ptr(pairs)))
         return pairs
+
+    def pair_search(self, mate1, mate2, hits1, off1, hits2, off2, min_insert: int, max_insert: int, fileid: int = 0, pairs=None,
+                    max_anchors: int = 0, orientation: int = 0, fresh: Optional[bool] = None):
+        """real_hip_pair_search: the mate search alone on anchors the caller holds (numpy arrays of lib.HIT_DTYPE / uint64
+        with host batches, device torch tensors of the same layout with device batches); needs the text, not the index."""
+        b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
+        on_device = bool(b1.on_device)
+        if not on_device:
+            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
+            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
+        n = int(b1.n_reads)
+        if int(off1.shape[0]) - 1 != n or int(off2.shape[0]) - 1 != n:
+            raise ValueError("the anchors' offsets and the batches describe different numbers of fragments")
+        if fresh is None:
+            fresh = pairs is None
+        if pairs is None:
+            if on_device:
+                raise ValueError("device inputs need a device tensor for the records")
+            pairs = new_pair_info(n)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        sp = self._search_params(max_anchors)
+        self.sync_inputs(hits1, off1, hits2, off2, pairs)
+        self._check(self._L.real_hip_pair_search(self._h, C.byref(pp), C.byref(sp), C.byref(b1), C.byref(b2), _ptr(hits1), _ptr(off1),
+                                                 _ptr(hits2), _ptr(off2), int(fileid), int(bool(fresh)), _ptr(pairs)))
+        return pairs
+
+    def mate_search_stats(self, reset: bool = False) -> dict:
+        st = _lib.RealHipMateSearchStats()
+        st.struct_size = C.sizeof(_lib.RealHipMateSearchStats)
+        self._check(self._L.real_hip_mate_search_stats_get(self._h, C.byref(st), int(reset)))
+        return {"fragments": int(st.fragments), "anchors": int(st.anchors), "anchors_skipped": int(st.anchors_skipped),
+                "positions": int(st.positions), "placements": int(st.placements), "launches": int(st.launches),
+                "kernel_ms": float(st.kernel_ms)}
 
     def pair_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0, pairs=None,
                   orientation: int = 0, fresh: Optional[bool] = None):
