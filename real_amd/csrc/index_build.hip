@@ -109,7 +109,7 @@ RhTables rh_plan_tables(uint32_t l, uint32_t request, uint32_t prefix_bits, uint
     if (want_auto && auto_pb && big && !no_rows) {
         // bucket rows are the faster layout (one HBM line per lookup) when they fit: 128 B x 2^pb x 6 lists plus the
         // build's transients (the full entry array of one list, the window positions, the bucket starts and overflow scans)
-        const double need = 6.0 * 128.0 * (double)(1ull << rpb) + 12.0 * (double)n_entries + 12.0 * (double)(1ull << rpb);
+        const double need = 6.0 * 128.0 * (double)(1ull << rpb) + 12.0 * (double)n_entries + (l <= 32 ? 16.0 : 12.0) * (double)(1ull << rpb);
         // (only when the rows are reasonably full: a 200 Mbp genome would take the same 2^(l-4) rows as a 3 Gbp one)
         rows = (l <= 32 ? rpb < l : rpb + 32 <= l) && (double)n_entries / (double)(1ull << rpb) >= 4.0 && need * 1.08 <= (double)device_bytes;
     }
@@ -182,13 +182,13 @@ __device__ __forceinline__ uint64_t window_signature(const uint64_t *__restrict_
 template <typename K>
 __global__ void entries_kernel(const K *__restrict__ sign, const uint32_t *__restrict__ pos, uint64_t n, uint32_t l,
                                int list, const uint64_t *__restrict__ T, uint32_t pshift, uint32_t fshift, uint32_t fbits,
-                               uint32_t pbits, uint32_t nbuckets, uint2 *__restrict__ ent, uint32_t *__restrict__ bkt)
+                               uint32_t pbits, uint32_t gor, uint32_t nbuckets, uint2 *__restrict__ ent, uint32_t *__restrict__ bkt)
 {
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const uint64_t s = (uint64_t)sign[j];
     const uint32_t wp = pos[j];
-    uint64_t x = (s >> fshift) & ((fbits >= 32) ? 0xffffffffull : ((1ull << fbits) - 1));
+    uint64_t x = ((s >> fshift) & ((fbits >= 32) ? 0xffffffffull : ((1ull << fbits) - 1))) | gor; // (gor: the `which` bit of a pair table's second list)
     if (pbits) {
         const uint64_t partner = window_signature(T, wp, l, 5 - list);
         x = (x << pbits) | (partner >> (l - pbits));
@@ -340,19 +340,110 @@ __global__ void rows_fill_kernel(const uint32_t *__restrict__ bkt, const uint2 *
     for (int i = 0; i < 8; ++i) rows[p * 8 + i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
 }
 
-// ordered traversal of the rows: per-bucket sizes, then (after a scan) the entries in list order
-__global__ void rows_sizes_kernel(const uint4 *__restrict__ rows, uint64_t nbuckets, uint32_t *__restrict__ size)
+// Pair tables (real_hip_internal.h: paired bucket rows).  The first list of a pair (0, 1) is written as above into a table of
+// twice the rows; the second (5, 4: sorted by the mixed rc-form of its signature) is merged into the rows in place, from
+// the counts already there: a pair row is complex when the first list's part was, when both parts together exceed
+// RH_ROW_CAP or when a group of the second list exceeds 15.  Entries of the first list that sat in a simple row and move
+// to the overflow array get their full key back from the text (the row kept sixteen bits of it).
+__device__ __forceinline__ uint32_t row_entries(uint32_t h0, uint32_t h1, uint32_t w3) { return rh_row_complex(h0, h1) ? w3 : rh_row_group4(h0, h1, 16).x; }
+
+__global__ void pair_overflow_kernel(const uint32_t *__restrict__ bkt, const uint2 *__restrict__ ent, uint64_t nbuckets, uint32_t pbits,
+                                     uint32_t gbits, const uint4 *__restrict__ rows, uint32_t *__restrict__ ovf_cnt)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > nbuckets) return;
+    uint32_t out = 0;
+    if (p < nbuckets) {
+        const uint4 h = rows[p * 8];
+        const uint32_t ca = row_entries(h.x, h.y, h.w);
+        const uint32_t start = bkt[p], end = bkt[p + 1], c = end - start;
+        bool complex_ = rh_row_complex(h.x, h.y) || ca + c > RH_ROW_CAP;
+        if (!complex_ && c > 15) {
+            uint32_t cnt[16];
+            bucket_groups(ent, start, end, pbits, (1u << gbits) - 1, cnt);
+#pragma unroll
+            for (int g = 0; g < 16; ++g) complex_ = complex_ || cnt[g] > 15;
+        }
+        out = complex_ ? ca + c : 0u;
+    }
+    ovf_cnt[p] = out;
+}
+
+__global__ void pair_fill_kernel(const uint32_t *__restrict__ bkt, const uint2 *__restrict__ ent, uint64_t nbuckets, uint32_t pbits,
+                                 uint32_t gbits, const uint32_t *__restrict__ ovf_start, uint32_t *rows, const uint2 *__restrict__ first_ovf,
+                                 uint2 *__restrict__ ovf, const uint64_t *__restrict__ T, uint32_t l, int first_list)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= nbuckets) return;
+    const uint32_t start = bkt[p], end = bkt[p + 1], c = end - start;
+    const uint32_t os = ovf_start[p], oc = ovf_start[p + 1] - os;
+    if (!c && !oc) return;
+    uint32_t *w = rows + p * 32;
+    const uint32_t h0 = w[0], h1 = w[1];
+    const bool first_complex = rh_row_complex(h0, h1);
+    const uint32_t ca = row_entries(h0, h1, w[3]);
+    uint32_t cnt[16];
+    bucket_groups(ent, start, end, pbits, (1u << gbits) - 1, cnt);
+    if (oc) { // complex: both parts in the overflow array, the first list's in front
+        uint32_t hd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        rh_row_set_complex(hd, os, ca + c);
+        if (first_complex) {
+            const uint32_t fo = w[2];
+            for (int i = 4; i < 8; ++i) hd[i] = w[i];
+            for (uint32_t j = 0; j < ca; ++j) ovf[os + j] = first_ovf[fo + j];
+        } else {
+            uint32_t j = 0;
+            for (uint32_t g = 0; g < 16; ++g) {
+                const uint32_t cg = rh_row_group4(h0, h1, g).y;
+                rh_row_set_count8(hd, g, cg);
+                for (uint32_t i = 0; i < cg; ++i, ++j) {
+                    const uint32_t wp = rh_row_entry(w, j).y;
+                    const uint32_t partner = (uint32_t)(window_signature(T, wp, l, 5 - first_list) >> (l - pbits));
+                    ovf[os + j] = make_uint2((g << pbits) | partner, wp);
+                }
+            }
+        }
+        for (uint32_t g = 0; g < 16; ++g) if (cnt[g]) rh_row_set_count8(hd, g, cnt[g]);
+        for (uint32_t j = 0; j < c; ++j) ovf[os + ca + j] = ent[start + j];
+        for (int i = 0; i < 32; ++i) w[i] = i < 8 ? hd[i] : 0u;
+    } else { // simple: the second list's counts and entries behind the first's
+        uint32_t hd[2] = {h0, h1};
+        for (uint32_t g = 0; g < 16; ++g) rh_row_set_count4(hd, g, cnt[g]);
+        w[0] = hd[0]; w[1] = hd[1];
+        uint16_t *hw = reinterpret_cast<uint16_t *>(w);
+        const uint32_t p16 = pbits < 16 ? pbits : 16, pmask = (1u << pbits) - 1;
+        for (uint32_t j = 0; j < c; ++j) {
+            const uint2 e = ent[start + j];
+            const uint32_t h = rh_row_entry_hw(ca + j);
+            hw[h] = (uint16_t)((e.x & pmask) >> (pbits - p16)); hw[h + 1] = (uint16_t)(e.y & 0xffffu); hw[h + 2] = (uint16_t)(e.y >> 16);
+        }
+    }
+}
+
+// ordered traversal of the rows: per-bucket sizes, then (after a scan) the entries in list order.  [g0, g1): the key groups
+// of the row that belong to the list (a table of its own: 0, 16; a pair table: the list's half)
+__device__ __forceinline__ uint32_t ovf_groups_below(const uint2 *__restrict__ ovf, uint32_t o0, uint32_t tot, uint32_t pbits, uint32_t g)
+{
+    if (g == 0) return 0;
+    if (g >= 16) return tot;
+    uint32_t x = 0, y = tot;
+    while (x < y) { const uint32_t mid = x + ((y - x) >> 1); if ((ovf[o0 + mid].x >> pbits) < g) x = mid + 1; else y = mid; }
+    return x;
+}
+__global__ void rows_sizes_kernel(const uint4 *__restrict__ rows, const uint2 *__restrict__ ovf, uint64_t nbuckets, uint32_t pbits, uint32_t g0,
+                                  uint32_t g1, uint32_t *__restrict__ size)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p > nbuckets) return;
     uint32_t c = 0;
     if (p < nbuckets) {
         const uint4 h = rows[p * 8];
-        c = rh_row_complex(h.x, h.y) ? h.w : rh_row_group4(h.x, h.y, 16).x;
+        c = rh_row_complex(h.x, h.y) ? ovf_groups_below(ovf, h.z, h.w, pbits, g1) - ovf_groups_below(ovf, h.z, h.w, pbits, g0)
+                                     : rh_row_group4(h.x, h.y, g1).x - rh_row_group4(h.x, h.y, g0).x;
     }
     size[p] = c;
 }
-__global__ void rows_unpack_kernel(const uint4 *__restrict__ rows, const uint2 *__restrict__ ovf, uint64_t nbuckets,
+__global__ void rows_unpack_kernel(const uint4 *__restrict__ rows, const uint2 *__restrict__ ovf, uint64_t nbuckets, uint32_t pbits, uint32_t g0,
                                    const uint32_t *__restrict__ off, uint2 *__restrict__ out)
 {
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -360,31 +451,98 @@ __global__ void rows_unpack_kernel(const uint4 *__restrict__ rows, const uint2 *
     const uint32_t *w = reinterpret_cast<const uint32_t *>(rows + p * 8);
     const uint32_t o = off[p], c = off[p + 1] - o;
     if (rh_row_complex(w[0], w[1])) {
-        for (uint32_t j = 0; j < c; ++j) out[o + j] = ovf[w[2] + j];
+        const uint32_t base = w[2] + ovf_groups_below(ovf, w[2], w[3], pbits, g0);
+        for (uint32_t j = 0; j < c; ++j) out[o + j] = ovf[base + j];
     } else {
-        for (uint32_t j = 0; j < c; ++j) out[o + j] = rh_row_entry(w, j);
+        const uint32_t base = rh_row_group4(w[0], w[1], g0).x;
+        for (uint32_t j = 0; j < c; ++j) out[o + j] = rh_row_entry(w, base + j);
     }
 }
 
-// entries of list `list` in list order as {key, pos} (key = the row's 16 partner bits, or the overflow entry's key) and the
-// bucket starts; either output may be null.  Used by index_download / index_export.
-int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts)
+// the canonical order of a list placed by the rc-form of its signature (lists 5, 4 of the pair tables): by rh_mix32 of its OWN signature
+__global__ void own_keys_kernel(const uint2 *__restrict__ ent, const uint64_t *__restrict__ T, uint64_t n, uint32_t l, int list,
+                                uint32_t *__restrict__ keys)
 {
-    const uint64_t nb = 1ull << ctx->pb;
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) keys[j] = rh_mix32((uint32_t)window_signature(T, ent[j].y, l, list), l);
+}
+// the starts of the 2^pb prefixes of a pair table's list: every second row's
+__global__ void every_second_kernel(const uint32_t *__restrict__ in, uint64_t n, uint32_t *__restrict__ out)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < n) out[j] = in[2 * j];
+}
+__global__ void starts_kernel(const uint32_t *__restrict__ keys, uint64_t n, uint32_t pshift, uint64_t nbuckets, uint32_t *__restrict__ bkt)
+{
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    const uint32_t p = keys[j] >> pshift;
+    const int64_t pprev = j ? (int64_t)(keys[j - 1] >> pshift) : -1;
+    for (int64_t q = pprev + 1; q <= (int64_t)p; ++q) bkt[q] = (uint32_t)j;
+    if (j == n - 1)
+        for (uint64_t q = (uint64_t)p + 1; q <= nbuckets; ++q) bkt[q] = (uint32_t)n;
+}
+
+template <typename K>
+static hipError_t sort_pairs(void *tmp, size_t &tmp_bytes, rocprim::double_buffer<K> &keys, rocprim::double_buffer<uint32_t> &vals, uint64_t n,
+                             uint32_t bits, hipStream_t st);
+
+// entries of list `list` as {key, pos} (key = the row's 16 partner bits, or the overflow entry's key) and the 2^pb + 1 bucket
+// starts; either output may be null.  Used by index_download / index_export.  The order is the one of the rows, which for
+// lists 5 and 4 of a pair table is that of the rc-form of their signatures; `canonical` (both outputs wanted) sorts those
+// two back to the order of rh_mix32 of their own signature, the one every other list has: what index_download presents is
+// that canonical order, not the physical one.
+int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts, bool canonical)
+{
+    const uint32_t l = ctx->prm.seedl;
+    const bool paired = l <= 32 && rh_list_paired((uint32_t)list);
+    const int table = paired && list > 3 ? 5 - list : list;
+    const uint64_t nb = rh_table_rows((uint32_t)list, l, ctx->pb), n = ctx->n_entries;
+    uint32_t pshift, fshift, fbits, pbits;
+    rh_index_geometry(l, ctx->pb, &pshift, &fshift, &fbits, &pbits);
+    const uint32_t half = paired ? 1u << (fbits - 1) : 16u, g0 = paired && list > 3 ? half : 0u, g1 = paired && list < 2 ? half : 16u;
+    const bool resort = canonical && paired && list > 3 && n;
+    if (resort && !(d_entries && d_starts)) return rh_fail(ctx, REAL_HIP_E_INVALID, "rows unpack: canonical order needs both outputs", hipSuccess);
     int rc;
     ScopedBuf sizes(ctx), offs(ctx);
     if ((rc = rh_reserve(ctx, sizes, (nb + 1) * 4))) return rc;
     if ((rc = rh_reserve(ctx, offs, (nb + 1) * 4))) return rc;
-    hipLaunchKernelGGL(rows_sizes_kernel, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4 *)ctx->bkt[list].p,
-                       nb, (uint32_t *)sizes.p);
+    const uint4 *rows = (const uint4 *)ctx->bkt[table].p;
+    const uint2 *ovf = (const uint2 *)ctx->ent[table].p;
+    hipLaunchKernelGGL(rows_sizes_kernel, dim3((unsigned)((nb + 1 + 255) / 256)), dim3(256), 0, ctx->stream, rows, ovf, nb, pbits, g0, g1, (uint32_t *)sizes.p);
     size_t tmp = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, tmp, (uint32_t *)sizes.p, (uint32_t *)offs.p, 0u, (size_t)(nb + 1), rocprim::plus<uint32_t>(), ctx->stream);
     if (e == hipSuccess && !(rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8)))
         e = rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, (uint32_t *)sizes.p, (uint32_t *)offs.p, 0u, (size_t)(nb + 1), rocprim::plus<uint32_t>(), ctx->stream);
     if (e == hipSuccess && !rc && d_entries)
-        hipLaunchKernelGGL(rows_unpack_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4 *)ctx->bkt[list].p,
-                           (const uint2 *)ctx->ent[list].p, nb, (const uint32_t *)offs.p, d_entries);
-    if (e == hipSuccess && !rc && d_starts) e = hipMemcpyAsync(d_starts, offs.p, (nb + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream);
+        hipLaunchKernelGGL(rows_unpack_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, ctx->stream, rows, ovf, nb, pbits, g0,
+                           (const uint32_t *)offs.p, d_entries);
+    // the starts of the 2^pb prefixes: every row's of a table of its own, every second row's of a pair table
+    if (e == hipSuccess && !rc && d_starts && !resort)
+    {
+        const uint64_t ns = ((uint64_t)1 << ctx->pb) + 1;
+        if (paired) hipLaunchKernelGGL(every_second_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t *)offs.p, ns, d_starts);
+        else e = hipMemcpyAsync(d_starts, offs.p, (nb + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream);
+    }
+    // (the entries themselves are the values of the sort: two key arrays and one more entry array beside the caller's)
+    ScopedBuf k0(ctx), k1(ctx), other(ctx);
+    if (e == hipSuccess && !rc && resort) {
+        if (!rc) rc = rh_reserve(ctx, k0, n * 4);
+        if (!rc) rc = rh_reserve(ctx, k1, n * 4);
+        if (!rc) rc = rh_reserve(ctx, other, n * sizeof(uint2));
+        rocprim::double_buffer<uint32_t> keys((uint32_t *)k0.p, (uint32_t *)k1.p);
+        rocprim::double_buffer<uint2> vals(d_entries, (uint2 *)other.p);
+        size_t st = 0;
+        if (!rc) e = rocprim::radix_sort_pairs(nullptr, st, keys, vals, (size_t)n, 0u, l, ctx->stream);
+        if (!rc && e == hipSuccess) rc = rh_reserve(ctx, ctx->sort_tmp, st ? st : 8);
+        if (!rc && e == hipSuccess) {
+            const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+            hipLaunchKernelGGL(own_keys_kernel, grid, block, 0, ctx->stream, (const uint2 *)d_entries, (const uint64_t *)ctx->text.p, n, l, list, (uint32_t *)k0.p);
+            e = rocprim::radix_sort_pairs(ctx->sort_tmp.p, st, keys, vals, (size_t)n, 0u, l, ctx->stream); // (stable: equal signatures keep ascending position)
+            if (e == hipSuccess) hipLaunchKernelGGL(starts_kernel, grid, block, 0, ctx->stream, (const uint32_t *)keys.current(), n, pshift, (uint64_t)1 << ctx->pb, d_starts);
+            if (e == hipSuccess && vals.current() != d_entries) e = hipMemcpyAsync(d_entries, vals.current(), n * sizeof(uint2), hipMemcpyDeviceToDevice, ctx->stream);
+        }
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     else (void)hipStreamSynchronize(ctx->stream);
     if (rc) return rc;
@@ -401,7 +559,8 @@ int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_st
 //                  the sort ping-pongs between the pairs and needs no temporary of its own beyond histograms)
 //   entries        bucket rows only: the full entry array {key, pos} the rows are cut from lies over whichever pair
 //                  does NOT hold the sorted list
-//   tables         bucket starts; rows: overflow counts and their scan
+//   tables         bucket starts; rows: overflow counts, scanned in place (a pair table has twice the rows: two arrays of
+//                  2^(pb+1) + 1 where three of 2^pb + 1 were)
 // Persistent outputs (rows / overflow entries, or entries / bucket tables) are allocations of their own.
 // ---------------------------------------------------------------------------
 struct BuildScratch {
@@ -412,9 +571,10 @@ struct BuildScratch {
     size_t sort_tmp_bytes = 0;
     uint2 *ent = nullptr;
     uint32_t *bkt = nullptr, *ocnt = nullptr, *ostart = nullptr;
+    ScopedBuf first_ovf; // pair tables: the overflow entries of the first list until the second is merged in
     void *scan_tmp = nullptr;
     size_t scan_tmp_bytes = 0;
-    explicit BuildScratch(real_hip_ctx *c) : arena(c) {}
+    explicit BuildScratch(real_hip_ctx *c) : arena(c), first_ovf(c) {}
 };
 
 template <typename K>
@@ -429,7 +589,8 @@ static hipError_t sort_pairs(void *tmp, size_t &tmp_bytes, rocprim::double_buffe
 static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned sig_bytes, bool need_sort)
 {
     const uint32_t l = ctx->prm.seedl;
-    const size_t nn = n ? n : 1, nb1 = ((size_t)1 << ctx->pb) + 1;
+    const bool rows = ctx->layout == RH_LAYOUT_ROWS;
+    const size_t nn = n ? n : 1, nb1 = (rows ? (size_t)rh_table_rows(0, l, ctx->pb) : (size_t)1 << ctx->pb) + 1;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t sort_tmp = 0, scan_tmp = 0;
     if (need_sort && n) {
@@ -439,7 +600,6 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
         else { rocprim::double_buffer<uint64_t> k(nullptr, nullptr); e = sort_pairs<uint64_t>(nullptr, sort_tmp, k, v, n, l, ctx->stream); }
         if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "radix sort (size query)", e);
     }
-    const bool rows = ctx->layout == RH_LAYOUT_ROWS;
     if (rows) {
         hipError_t e = rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, nb1, rocprim::plus<uint32_t>(), ctx->stream);
         if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "scan (size query)", e);
@@ -451,7 +611,7 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
     if (rows && !need_sort) x = al(nn * sizeof(uint2)); // (host-built lists: no pair A, the entries get room of their own)
     const size_t o_bkt = o_x + x;
     const size_t o_ocnt = o_bkt + (ctx->layout != RH_LAYOUT_STARTS ? al(nb1 * 4) : 0);       // (bucket starts keep them: an allocation of their own)
-    const size_t o_ostart = o_ocnt + (rows ? al(nb1 * 4) : 0);
+    const size_t o_ostart = o_ocnt; // (scanned in place)
     const size_t o_scan = o_ostart + (rows ? al(nb1 * 4) : 0);
     const size_t total = o_scan + al(scan_tmp ? scan_tmp : 8);
     int rc = rh_reserve(ctx, S.arena, total);
@@ -474,8 +634,14 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
     const uint32_t l = ctx->prm.seedl, pb = ctx->pb;
     uint32_t pshift, fshift, fbits, pbits;
     rh_index_geometry(l, pb, &pshift, &fshift, &fbits, &pbits);
-    const uint32_t nb = 1u << pb;
     const bool rows = ctx->layout == RH_LAYOUT_ROWS;
+    // pair tables (narrow rows): list 0 / 1 fills a table of twice the rows, list 5 / 4 is merged into it
+    const bool paired = rows && l <= 32 && rh_list_paired((uint32_t)list), second = paired && list > 3;
+    const int table = second ? 5 - list : list;
+    const uint32_t nb = (uint32_t)(rows ? rh_table_rows((uint32_t)list, l, pb) : 1ull << pb);
+    const uint32_t gbits = fbits;
+    if (paired) { pshift -= 1; fbits -= 1; }
+    const uint32_t gor = second ? 1u << fbits : 0u;
     int rc;
     // The tables of a previous block stay allocated when they have about the size this block needs (the next block of
     // a genome, the next file of a directory: same layout, and hipMalloc of 200 GB costs seconds); otherwise they go
@@ -485,6 +651,7 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
         rh_release(ctx, b);
         return rh_reserve(ctx, b, need);
     };
+    if (!n && second) return REAL_HIP_OK; // (the first list left the rows empty)
     if (!n) {
         const size_t esz = rows ? 128 : (ctx->layout != RH_LAYOUT_STARTS ? 16 : 4);
         if ((rc = fit(ctx->bkt[list], ((size_t)nb + 1) * esz))) return rc;
@@ -507,28 +674,40 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
     rh_time_begin(ctx, ctx->stream, REAL_HIP_K_INDEX);
     if (sig_bytes == 4)
         hipLaunchKernelGGL(entries_kernel<uint32_t>, grid, block, 0, ctx->stream, (const uint32_t *)d_sign, d_pos, n, l, list, T,
-                           pshift, fshift, fbits, pbits, nb, d_ent, d_bkt);
+                           pshift, fshift, fbits, pbits, gor, nb, d_ent, d_bkt);
     else
         hipLaunchKernelGGL(entries_kernel<uint64_t>, grid, block, 0, ctx->stream, (const uint64_t *)d_sign, d_pos, n, l, list, T,
-                           pshift, fshift, fbits, pbits, nb, d_ent, d_bkt);
+                           pshift, fshift, fbits, pbits, gor, nb, d_ent, d_bkt);
     RH_HIP(ctx, hipGetLastError());
     if (rows) {
-        // rows: overflow sizes, scan, fill
+        // rows: overflow sizes, scan, fill (the key groups of a row count gbits bits, `which` included)
         const dim3 g1((unsigned)(((uint64_t)nb + 1 + 255) / 256)), b1(256);
-        hipLaunchKernelGGL(rows_overflow_kernel, g1, b1, 0, ctx->stream, (const uint32_t *)d_bkt, (const uint2 *)d_ent, (uint64_t)nb, pbits, fbits, S.ocnt);
+        if (second)
+            hipLaunchKernelGGL(pair_overflow_kernel, g1, b1, 0, ctx->stream, (const uint32_t *)d_bkt, (const uint2 *)d_ent, (uint64_t)nb, pbits, gbits,
+                               (const uint4 *)ctx->bkt[table].p, S.ocnt);
+        else
+            hipLaunchKernelGGL(rows_overflow_kernel, g1, b1, 0, ctx->stream, (const uint32_t *)d_bkt, (const uint2 *)d_ent, (uint64_t)nb, pbits, gbits, S.ocnt);
         size_t tmp = S.scan_tmp_bytes;
         RH_HIP(ctx, rocprim::exclusive_scan(S.scan_tmp, tmp, S.ocnt, S.ostart, 0u, (size_t)nb + 1, rocprim::plus<uint32_t>(), ctx->stream));
         rh_time_end(ctx, ctx->stream);
         uint32_t n_ovf = 0;
         RH_HIP(ctx, hipMemcpyAsync(&n_ovf, S.ostart + nb, 4, hipMemcpyDeviceToHost, ctx->stream));
         RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if ((rc = fit(ctx->bkt[list], (size_t)nb * 128))) return rc;
-        if ((rc = fit(ctx->ent[list], ((size_t)n_ovf + 1) * sizeof(uint2)))) return rc;
+        // (the first list of a pair: its overflow entries wait in the scratch for the second)
+        DevBuf &ovf = paired && !second ? (DevBuf &)S.first_ovf : ctx->ent[table];
+        if (!second && (rc = fit(ctx->bkt[table], (size_t)nb * 128))) return rc;
+        if ((rc = fit(ovf, ((size_t)n_ovf + 1) * sizeof(uint2)))) return rc;
         rh_time_begin(ctx, ctx->stream, REAL_HIP_K_INDEX);
-        hipLaunchKernelGGL(rows_fill_kernel, dim3((unsigned)(((uint64_t)nb + 255) / 256)), b1, 0, ctx->stream, (const uint32_t *)d_bkt,
-                           (const uint2 *)d_ent, (uint64_t)nb, pbits, fbits, (const uint32_t *)S.ostart, (uint4 *)ctx->bkt[list].p, (uint2 *)ctx->ent[list].p);
+        if (second)
+            hipLaunchKernelGGL(pair_fill_kernel, dim3((unsigned)(((uint64_t)nb + 255) / 256)), b1, 0, ctx->stream, (const uint32_t *)d_bkt, (const uint2 *)d_ent,
+                               (uint64_t)nb, pbits, gbits, (const uint32_t *)S.ostart, (uint32_t *)ctx->bkt[table].p, (const uint2 *)S.first_ovf.p,
+                               (uint2 *)ovf.p, T, l, table);
+        else
+            hipLaunchKernelGGL(rows_fill_kernel, dim3((unsigned)(((uint64_t)nb + 255) / 256)), b1, 0, ctx->stream, (const uint32_t *)d_bkt,
+                               (const uint2 *)d_ent, (uint64_t)nb, pbits, gbits, (const uint32_t *)S.ostart, (uint4 *)ctx->bkt[table].p, (uint2 *)ovf.p);
         rh_time_end(ctx, ctx->stream);
         RH_HIP(ctx, hipGetLastError());
+        if (second) { RH_HIP(ctx, hipStreamSynchronize(ctx->stream)); rh_release(ctx, S.first_ovf); }
         return REAL_HIP_OK;
     }
     if (ctx->layout != RH_LAYOUT_STARTS) {
@@ -547,6 +726,8 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
 
 template <typename K>
 static int sort_list(real_hip_ctx *ctx, BuildScratch &S, int list, const uint32_t *d_wpos, uint64_t first_window, uint64_t n, bool uploaded = false);
+// the lists in the order they are built: the second list of a pair table right behind the first
+static const int rh_build_order[6] = {0, 5, 1, 4, 2, 3};
 
 // host-built form (real_hip_set_index_block): the six sorted lists are uploaded one after the other through the scratch
 int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const sign[6], const uint32_t *const pos[6], unsigned sig_bytes)
@@ -556,7 +737,8 @@ int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const si
     const bool rows = ctx->layout == RH_LAYOUT_ROWS; // bucket rows: the lists are sorted once more, by the mixed signature (sort_list)
     int rc = plan_scratch(ctx, S, n, sig_bytes, rows);
     if (rc) return rc;
-    for (int k = 0; k < 6; ++k) {
+    for (int i = 0; i < 6; ++i) {
+        const int k = rh_build_order[i];
         if (n) {
             RH_HIP(ctx, hipMemcpyAsync(S.keys_b, sign[k], n * sig_bytes, hipMemcpyHostToDevice, ctx->stream));
             RH_HIP(ctx, hipMemcpyAsync(S.vals_b, pos[k], n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -598,8 +780,9 @@ __global__ void iota_kernel(uint32_t *out, uint64_t first, uint64_t n)
 }
 
 // list k signature of the window at wpos[j]; mix: the sort key of the bucket rows (rh_mix32 / rh_mix64)
+// (narrow rows: of the signature the list is placed by, rh_place_sig)
 template <typename K>
-__device__ __forceinline__ K mixed_key(K v, uint32_t l) { return sizeof(K) == 4 ? (K)rh_mix32((uint32_t)v, l) : (K)rh_mix64((uint64_t)v, l); }
+__device__ __forceinline__ K mixed_key(K v, uint32_t l, int list) { return sizeof(K) == 4 ? (K)rh_mix32(rh_place_sig((uint32_t)list, (uint32_t)v, l), l) : (K)rh_mix64((uint64_t)v, l); }
 template <typename K>
 __global__ void keys_kernel(const uint64_t *__restrict__ T, const uint32_t *__restrict__ wpos, uint64_t n, uint32_t l,
                             int list, bool mix, K *__restrict__ keys)
@@ -607,13 +790,13 @@ __global__ void keys_kernel(const uint64_t *__restrict__ T, const uint32_t *__re
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const K v = (K)window_signature(T, wpos[j], l, list);
-    keys[j] = mix ? mixed_key<K>(v, l) : v;
+    keys[j] = mix ? mixed_key<K>(v, l, list) : v;
 }
 template <typename K>
-__global__ void mix_keys_kernel(K *__restrict__ keys, uint64_t n, uint32_t l)
+__global__ void mix_keys_kernel(K *__restrict__ keys, uint64_t n, uint32_t l, int list)
 {
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) keys[j] = mixed_key<K>(keys[j], l);
+    if (j < n) keys[j] = mixed_key<K>(keys[j], l, list);
 }
 
 // d_wpos: the window starts of the block in ascending order, or null = every window from first_window on (no N in the text)
@@ -632,7 +815,7 @@ static int sort_list(real_hip_ctx *ctx, BuildScratch &S, int list, const uint32_
         rocprim::double_buffer<K> keys((K *)S.keys_a, (K *)S.keys_b);
         rocprim::double_buffer<uint32_t> vals(S.vals_x, S.vals_b);
         if (uploaded) {
-            hipLaunchKernelGGL(mix_keys_kernel<K>, grid, block, 0, ctx->stream, (K *)S.keys_b, n, l);
+            hipLaunchKernelGGL(mix_keys_kernel<K>, grid, block, 0, ctx->stream, (K *)S.keys_b, n, l, list);
             keys = rocprim::double_buffer<K>((K *)S.keys_b, (K *)S.keys_a);
             vals = rocprim::double_buffer<uint32_t>(S.vals_b, S.vals_x);
         } else {
@@ -699,8 +882,10 @@ int rh_index_build_device(real_hip_ctx *ctx, uint64_t first_window, uint64_t max
     for (int attempt = 0;; ++attempt) {
         BuildScratch S(ctx);
         rc = plan_scratch(ctx, S, cnt, l <= 32 ? 4 : 8, true);
-        for (int k = 0; k < 6 && !rc; ++k)
+        for (int i = 0; i < 6 && !rc; ++i) {
+            const int k = rh_build_order[i];
             rc = (l <= 32) ? sort_list<uint32_t>(ctx, S, k, d_wpos, first_window, cnt) : sort_list<uint64_t>(ctx, S, k, d_wpos, first_window, cnt);
+        }
         if (!rc) RH_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (before the scratch goes)
         if (rc == REAL_HIP_E_NOMEM && ctx->layout == RH_LAYOUT_ROWS && ctx->prm.table_kind == 0 && !ctx->no_rows && attempt == 0) {
             // the rows did not fit after all (memory held by others): once more with directory tables
@@ -960,7 +1145,7 @@ int rh_index_export(real_hip_ctx *ctx, int list, void *h_sign, uint32_t *h_pos)
         const size_t room = n * (sb + 4) > n * sizeof(uint2) ? n * (sb + 4) : n * sizeof(uint2);
         if ((rc = rh_reserve(ctx, unpacked, room))) return rc;
         if ((rc = rh_reserve(ctx, ctx->sort_tmp, sort_tmp ? sort_tmp : 8))) return rc;
-        if ((rc = rh_rows_unpack(ctx, list, (uint2 *)unpacked.p, nullptr))) return rc; // (uses ctx->sort_tmp for its scan: before the sort)
+        if ((rc = rh_rows_unpack(ctx, list, (uint2 *)unpacked.p, nullptr, false))) return rc; // (uses ctx->sort_tmp for its scan: before the sort)
         d_ent = (const uint2 *)unpacked.p;
     }
     dim3 grid((unsigned)((n + 255) / 256)), block(256);

@@ -116,8 +116,8 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v)
 __device__ __forceinline__ unsigned long long wave_append_slot(unsigned long long *counter)
 {
     unsigned long long mask = __ballot(1);
-    unsigned lane = threadIdx.x & 63;
-    unsigned rank = __popcll(mask & ((1ull << lane) - 1ull));
+    // (mbcnt: the set bits of the mask below this lane -- no lane mask for the compiler to keep in registers across a kernel's loops)
+    unsigned rank = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
     unsigned long long base = 0;
     if (rank == 0) base = atomicAdd(counter, (unsigned long long)__popcll(mask));
     unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)base);

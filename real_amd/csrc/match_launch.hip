@@ -33,6 +33,17 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &args, bool all, int stat
     if ((rc = rh_reserve(ctx, ctx->ovf_list, a.b.n_reads * 4))) return rc;
     if ((rc = rh_reserve(ctx, ctx->ovf2_list, a.b.n_reads * 4))) return rc;
     if ((rc = rh_reserve(ctx, ctx->ovf_count, 64))) return rc;
+    // the queue spill of the paired driver (narrow bucket rows with parked hits: scores on or matchAll; no other instance
+    // has one): RH_QSPILL_SLOTS x 64 lanes x {position, lists} per wave, four waves per workgroup, for as many workgroups
+    // as a device holds at a time -- at most eight per CU, which also caps that instance's resident grid
+    a.qspill = nullptr; a.qspill_blocks = 0;
+    if (a.ix.layout == RH_LAYOUT_ROWS && !rh_wide_entries(a.ix) && (all || ctx->prm.scores)) {
+        int n_cu = 0;
+        if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n_cu < 1) n_cu = 256;
+        a.qspill_blocks = 8u * (uint32_t)n_cu;
+        if ((rc = rh_reserve(ctx, ctx->qspill, (size_t)a.qspill_blocks * 4 * RH_QSPILL_SLOTS * 64 * sizeof(uint2)))) return rc;
+        a.qspill = (uint2 *)ctx->qspill.p;
+    }
     unsigned long long *oc = (unsigned long long *)ctx->ovf_count.p;
     a.ovf_list = (uint32_t *)ctx->ovf_list.p;
     a.ovf_count = oc;

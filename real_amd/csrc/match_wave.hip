@@ -73,9 +73,8 @@ __device__ __forceinline__ WaveRange wave_lookup(const MatchArgs &a, uint64_t sh
     const bool wide = rh_wide_entries(a.ix);
     uint32_t g, bucket;
     if (!wide) {
-        const uint32_t gbits = a.ix.fbits;
-        const uint32_t msa = rh_mix32((uint32_t)sa, l);
-        bucket = msa >> gbits; g = msa & ((1u << gbits) - 1);
+        const RhRowAddr ra = rh_row_addr((uint32_t)la, (uint32_t)sa, l, a.ix.fbits); // (bkt[la] / ent[la] of a pair are its table)
+        bucket = ra.row; g = ra.group;
         R.key = R.partner;
     } else {
         const uint64_t msa = rh_mix64(sa, l);

@@ -215,7 +215,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
     DevBuf *all[] = {&c->comm_counts, &c->comm_scratch, &c->text, &c->wild, &c->frag, &c->LL, &c->counters, &c->s_bases, &c->s_qual, &c->s_off, &c->s_info,
-                     &c->s_score, &c->maxpatl, &c->ovf_list, &c->ovf2_list, &c->ovf_count, &c->raw, &c->raw_count, &c->hit_cnt, &c->big_list, &c->all_cursor, &c->p_text, &c->p_nl, &c->p_scal, &c->p_spans, &c->p_off,
+                     &c->s_score, &c->maxpatl, &c->ovf_list, &c->ovf2_list, &c->ovf_count, &c->qspill, &c->raw, &c->raw_count, &c->hit_cnt, &c->big_list, &c->all_cursor, &c->p_text, &c->p_nl, &c->p_scal, &c->p_spans, &c->p_off,
                      &c->p_len1, &c->p_bases, &c->p_qual, &c->keys_a,
                      &c->keys_b, &c->vals_a, &c->vals_b, &c->sort_tmp, &c->hit_off, &c->s_hits, &c->s_nflags};
     for (DevBuf *b : all) rh_release(*b);
@@ -418,7 +418,7 @@ extern "C" int real_hip_index_download(real_hip_ctx *ctx, int list, uint32_t *en
         int rc;
         if ((rc = rh_reserve(ctx, e, (n ? n : 1) * sizeof(uint2)))) return rc;
         if ((rc = rh_reserve(ctx, st, (((size_t)1 << ctx->pb) + 1) * 4))) return rc;
-        rc = rh_rows_unpack(ctx, list, (uint2 *)e.p, (uint32_t *)st.p);
+        rc = rh_rows_unpack(ctx, list, (uint2 *)e.p, (uint32_t *)st.p, true); // (the canonical order, not the physical one)
         hipError_t he = hipSuccess;
         if (!rc && n && entries) he = hipMemcpy(entries, e.p, n * sizeof(uint2), hipMemcpyDeviceToHost);
         if (!rc && he == hipSuccess && bucket) he = hipMemcpy(bucket, st.p, (((size_t)1 << ctx->pb) + 1) * 4, hipMemcpyDeviceToHost);
@@ -555,7 +555,11 @@ static void fill_args(real_hip_ctx *ctx, const Staged &s, uint64_t n, MatchArgs 
     a.t.frag_start = (const uint64_t *)ctx->frag.p; a.t.n = ctx->n_bases; a.t.n_frag = ctx->n_frag;
     a.t.has_wild = ctx->n_wild ? 1 : 0; a.t.fileid = ctx->fileid;
     const uint32_t l = ctx->prm.seedl, pb = ctx->pb;
-    for (int k = 0; k < 6; ++k) { a.ix.ent[k] = (const uint2 *)ctx->ent[k].p; a.ix.bkt[k] = (const uint32_t *)ctx->bkt[k].p; }
+    for (int k = 0; k < 6; ++k) {
+        // (narrow bucket rows: lists 5 and 4 live in the pair tables of lists 0 and 1, rh_row_addr)
+        const int t = (ctx->layout == RH_LAYOUT_ROWS && l <= 32 && k > 3) ? 5 - k : k;
+        a.ix.ent[k] = (const uint2 *)ctx->ent[t].p; a.ix.bkt[k] = (const uint32_t *)ctx->bkt[t].p;
+    }
     a.ix.n = ctx->n_entries; a.ix.pb = pb;
     rh_index_geometry(l, pb, &a.ix.pshift, &a.ix.fshift, &a.ix.fbits, &a.ix.pbits);
     a.ix.layout = ctx->layout;

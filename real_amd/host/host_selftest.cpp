@@ -4,6 +4,7 @@
 //   host_selftest index <g.fa> <seedl> <first> <max> <threads> <outdir> -> l<k>_sign.bin l<k>_pos.u32 meta.txt
 //   host_selftest options <args...>               -> prints the parsed RealOptions
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
+//   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair tables (csrc/row_addr.h), prints ok
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,6 +16,8 @@
 #include "HostIndex.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
+#include "row_addr.h"
+#include <vector>
 
 template <typename T>
 static void dump(const std::string &fn, const T *p, size_t n)
@@ -108,6 +111,60 @@ int main(int argc, char **argv)
                 check((float)(c * 9.999995)); check((float)(c * 0.9999995)); check((float)(c * 1.2345675)); check((float)(c * 999999.5 / 1e5));
             }
             std::cout << bad << std::endl;
+            return bad ? 1 : 0;
+        }
+        if (cmd == "rowaddr" && argc == 3) {
+            // rh_sig_rcform / rh_place_sig / rh_row_addr as the library compiles them: the rc-form against a base-by-base
+            // reverse complement; (list, signature) -> (table, row, group) a bijection at every group width (all signatures
+            // up to seedl 12); the four paired lookups in the row and group the design says (all seeds up to seedl 12, two
+            // million drawn ones beyond: seedl 32 is the benchmark's geometry, its shifts by 0 and full masks included)
+            const uint32_t l = (uint32_t)atoi(argv[2]), q = l / 4; // q bases per segment
+            if (l < 4 || l > 32 || l % 4) return 2;
+            const uint64_t nsig = 1ull << l, smask = nsig - 1;
+            auto rc_naive = [](uint64_t v, uint32_t bases) { uint64_t o = 0; for (uint32_t i = 0; i < bases; ++i) o |= (3 - ((v >> (2 * i)) & 3)) << (2 * (bases - 1 - i)); return o; };
+            uint64_t rs = 0x9E3779B97F4A7C15ull;
+            auto next = [&]() { rs ^= rs << 13; rs ^= rs >> 7; rs ^= rs << 17; return rs; };
+            const bool all = l <= 12;
+            uint64_t bad = 0;
+            for (uint64_t i = 0, n = l <= 16 ? nsig : 2000000; i < n; ++i) {
+                const uint32_t sg = (uint32_t)((l <= 16 ? i : (i < 4 ? (i & 1 ? smask : 0) ^ (i & 2 ? 1 : 0) : next())) & smask);
+                const uint32_t r = rh_sig_rcform(sg, l);
+                if (r != (uint32_t)rc_naive(sg, l / 2) || rh_sig_rcform(r, l) != sg) bad++;
+            }
+            for (uint32_t gbits = 1; gbits <= 4 && gbits < l; ++gbits) {
+                const uint32_t pb = l - gbits;
+                if (all) {
+                    const uint64_t off[4] = {0, 2 * nsig, 4 * nsig, 5 * nsig};
+                    std::vector<uint8_t> seen(6 * nsig, 0);
+                    for (uint32_t la = 0; la < 6; ++la)
+                        for (uint64_t sg = 0; sg < nsig; ++sg) {
+                            const RhRowAddr a = rh_row_addr(la, (uint32_t)sg, l, gbits);
+                            if (a.table > 3 || a.table != (la > 3 ? 5 - la : la) || a.row >= rh_table_rows(la, l, pb) || a.group >= (1u << gbits)) { bad++; continue; }
+                            uint8_t &s = seen[off[a.table] + (((uint64_t)a.row << gbits) | a.group)];
+                            if (s) bad++;
+                            s = 1;
+                        }
+                    for (uint8_t s : seen) if (!s) bad++;
+                }
+                const uint64_t nseed = all ? 1ull << (2 * l) : 2000000;
+                const uint64_t gm = (1ull << (2 * q)) - 1;
+                for (uint64_t i = 0; i < nseed; ++i) {
+                    const uint64_t seed = all ? i : next();
+                    uint32_t m[4], r[4];
+                    for (int k = 0; k < 4; ++k) m[k] = (uint32_t)((seed >> (2 * q * (3 - k))) & gm);
+                    for (int k = 0; k < 4; ++k) r[k] = (uint32_t)rc_naive(m[3 - k], q);
+                    static const int A[6] = {0, 0, 0, 1, 1, 2}, C[6] = {1, 2, 3, 2, 3, 3}; // rh_list_segs
+                    auto sig = [&](const uint32_t *s, int la) { return (uint32_t)((((uint64_t)s[A[la]] << (2 * q)) | s[C[la]]) & smask); };
+                    for (int k = 0; k < 2; ++k)
+                        for (int st = 0; st < 2; ++st) { // this strand's list k and the other strand's list 5 - k: one row
+                            const uint32_t *own = st ? r : m, *oth = st ? m : r;
+                            const RhRowAddr a = rh_row_addr(k, sig(own, k), l, gbits), b = rh_row_addr(5 - k, sig(oth, 5 - k), l, gbits);
+                            const uint32_t half = 1u << (gbits - 1);
+                            if (a.table != b.table || a.row != b.row || (a.group & half) || b.group != (a.group | half)) bad++;
+                        }
+                }
+            }
+            std::cout << (bad ? "bad " : "ok ") << bad << std::endl;
             return bad ? 1 : 0;
         }
         if (cmd == "options") {
