@@ -9,6 +9,9 @@
 // ---------------------------------------------------------------------------
 // number of differing 2-bit symbols (PopCountTable.hpp:103-131 diffcountpair)
 __device__ __forceinline__ unsigned pairdiff(uint64_t x) { return __popcll(((x >> 1) | x) & M55); }
+// acc + the sum over the eight nibbles of x of (nibble of x) * (nibble of w): with w = a 1 in every nibble that counts, the
+// sum of those nibbles of x in one instruction (v_dot8_u32_u4)
+__device__ __forceinline__ uint32_t nibble_dot(uint32_t x, uint32_t w, uint32_t acc) { return __builtin_amdgcn_udot8(x, w, acc, false); }
 
 // nb (1..32) bases starting at base i, right aligned (AutoTextArray::getTextWord(i,l),
 // AutoTextArray.hpp:122-125 -> Rank::getBits64, ERank222B.hpp:55-85)
