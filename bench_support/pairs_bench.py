@@ -10,6 +10,9 @@ generator and on a genome with 5 % of its positions in 16-copy repeat families. 
 the baseline figures only.  Results are merged into --out under the key --label.  A build with the mate search adds the
 search-on legs (real_hip_match_pairs_search: call time, the search kernel's own time, positions and placements per fragment,
 the states with the search off and on); the leg with reads at 4 % substitutions: --errprob 0.04 --ks 5 --genomes iid.
+A build with real_hip_match_pairs_all adds the legs of the enumeration of every concordant pair (outputs in pinned host
+memory and left on the device, pairs per fragment, handed-over share, the kernels' own time); its comparison figure is
+baseline_ms, what a caller has to do without it to see the same pairs.  --skip-search leaves the mate-search legs out.
 """
 import argparse
 import ctypes as C
@@ -62,6 +65,7 @@ def main():
     ap.add_argument("--genomes", default="iid,repeat")
     ap.add_argument("--errprob", type=float, default=0.02)   # substitutions per base of the reads
     ap.add_argument("--ks", default="2,3")                   # the -e values (totalkmax) measured
+    ap.add_argument("--skip-search", action="store_true")    # leave the mate-search legs out
     args = ap.parse_args()
     sys.path.insert(0, args.tree)
     import numpy as np
@@ -162,7 +166,7 @@ def main():
                 state = np.bincount(rec["state"], minlength=3)
                 r["states"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
                 r["record_bytes_downloaded"] = n * 40
-                if hasattr(m, "mate_search_stats"):         # the same call with the mate search behind the join
+                if hasattr(m, "mate_search_stats") and not args.skip_search:         # the same call with the mate search behind the join
                     sp = m._search_params(0)
 
                     def run_search(on_device, out_ptr):
@@ -181,6 +185,40 @@ def main():
                     r["search_per_fragment"] = {k: ms[k] / max(ms["fragments"], 1) for k in ("anchors", "positions", "placements")}
                     state = np.bincount(rec["state"], minlength=3)
                     r["states_search_on"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
+                if hasattr(m, "match_pairs_all"):           # every concordant pair instead of one record per fragment
+                    poff = m.host_alloc(n + 1, np.uint64)
+                    poff_dev = torch.empty(n + 1, dtype=torch.int64, device=dev)
+                    pcap, need_p = int(n * 1.25), C.c_uint64(0)
+                    ph = m.host_alloc(pcap, rlib.PAIR_HIT_DTYPE)
+
+                    def run_all(on_device, out_ptr, off_ptr, may_overflow=False):
+                        rb1, rb2 = batch(b1, q1), batch(b2, q2)
+                        rb1.on_device = rb2.on_device = on_device
+                        t0 = time.perf_counter()
+                        rc = L.real_hip_match_pairs_all(m._h, C.byref(rb1), C.byref(rb2), C.byref(pp), out_ptr, pcap, C.byref(need_p), off_ptr)
+                        if not (may_overflow and rc == rlib.REAL_HIP_E_OVERFLOW):
+                            m._check(rc)
+                        return (time.perf_counter() - t0) * 1e3
+                    run_all(2, ph.ctypes.data, poff.ctypes.data, may_overflow=True)        # warm-up, and the size
+                    if need_p.value > pcap:
+                        pcap = int(need_p.value) + 16
+                        ph = m.host_alloc(pcap, rlib.PAIR_HIT_DTYPE)
+                    ph_dev = torch.empty(pcap * 32, dtype=torch.uint8, device=dev)
+                    run_all(2, ph.ctypes.data, poff.ctypes.data)
+                    m.pair_all_stats(reset=True)
+                    ts = [run_all(2, ph.ctypes.data, poff.ctypes.data) for _ in range(args.steps)]
+                    pa = m.pair_all_stats()
+                    r["match_pairs_all_ms"], r["match_pairs_all_ms_all_steps"] = min(ts), ts
+                    r["pairs_all_kernel_ms_per_call"] = pa["kernel_ms"] / float(args.steps)
+                    r["pairs_per_fragment"] = pa["pairs_out"] / max(pa["fragments"], 1)
+                    r["pairs_all_handed_over_share"] = pa["handed_over"] / max(pa["fragments"], 1)
+                    per = (poff[1:] - poff[:-1])
+                    r["fragments_with_two_or_more_pairs"] = int((per >= 2).sum())
+                    r["pair_hit_bytes_downloaded"] = int(need_p.value) * 32 + (n + 1) * 8
+                    td = [run_all(1, ph_dev.data_ptr(), poff_dev.data_ptr()) for _ in range(args.steps)]
+                    r["match_pairs_all_device_outputs_ms"] = min(td)
+                    r["pairs_all_download_by_difference_ms"] = min(ts) - min(td)
+                    del ph_dev, poff_dev
             result[key] = r
             print(key, json.dumps(r), flush=True)
         m.close()

@@ -332,6 +332,54 @@ typedef struct real_hip_mate_search_stats {
 } real_hip_mate_search_stats;
 int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
 
+/* ---- paired-end reads: every concordant pair of a fragment (what matchAll is to matchUnique).  The record of
+ * real_hip_match_pairs keeps the values of the top two pairs only; these calls list every concordant pair of two
+ * real_hip_match_all hits, with the definition of CONCORDANT above (FR only, either mate forward).  Pairs with a
+ * placement only the mate search finds are NOT listed: the enumeration covers pairs of two seed hits.
+ * ORDER: out[pair_offsets[i] .. pair_offsets[i+1]) holds the pairs of fragment i, row-major over the product of its two
+ * lists -- ascending index of the mate-1 hit in its list, then ascending index of the mate-2 hit.  The output order is a
+ * function of the input order alone (nothing is sorted, and nothing depends on lanes or waves); with lists in
+ * unifyMatches order (real_hip_match_all's) it is fixed.  A hit must not appear twice in a list.                       */
+typedef struct real_hip_pair_hit {   /* 32 bytes, one concordant pair */
+    uint32_t pair;        /* index of the fragment inside the batch                                                 */
+    uint32_t pos1, pos2;  /* 0-based positions of mate 1 / mate 2 in the text of fileid                             */
+    uint32_t outer;       /* outer distance r.pos + len_r - f.pos, the quantity the insert bounds test              */
+    float    score1, score2;   /* the hits' scores (1.0f if !scores)                                                */
+    uint16_t frag;
+    uint8_t  fileid, inverted1, k1, k2;   /* inverted1: strand of mate 1 (0 '+', 1 '-'), mate 2 has the other one   */
+    uint16_t reserved;    /* 0 */
+} real_hip_pair_hit;
+/* The enumeration alone, on hit lists the caller holds; the inputs and on_device are those of real_hip_pair_hits (0: all
+ * pointers host memory, 1: all device pointers, out and pair_offsets included; a device out must be 16-byte aligned).
+ * Needs neither text nor index.  cap = capacity of out in records; n_out is host memory and always receives the number
+ * of pairs; when that exceeds cap the call returns REAL_HIP_E_OVERFLOW and writes nothing to out (the count is known
+ * before anything is emitted).  pair_offsets has n_pairs + 1 entries (may be NULL).                                    */
+int real_hip_pair_all_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp,
+                           const real_hip_hit *hits1, const uint64_t *off1, const uint32_t *len1,
+                           const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                           uint64_t n_pairs, uint32_t fileid, int on_device,
+                           real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets);
+/* matchAll of both mates against the resident text and index block with the hits kept on the device (as
+ * real_hip_match_pairs does), then the enumeration: only the pair hits and offsets cross to the host (on_device 0 / 2;
+ * 1: out and pair_offsets are device pointers).  fileid is the resident text's.  One index block, as for
+ * real_hip_match_pairs: a genome file that needs several goes through real_hip_match_all + real_hip_pair_all_hits.    */
+int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                             const real_hip_pair_params *pp,
+                             real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets);
+/* work of the enumeration, accumulated since the last reset.  The count pass of a call that ended in
+ * REAL_HIP_E_OVERFLOW is work too: fragments, products and handed_over include it, pairs_out does not.
+ * kernel_ms: HIP events on the ctx's stream around the kernels (count + scan, emit)                                    */
+typedef struct real_hip_pair_all_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_pair_all_stats), 0                                */
+    uint64_t fragments;     /* fragments counted                                                          */
+    uint64_t products;      /* sum over the fragments of (hits of mate 1) x (hits of mate 2)              */
+    uint64_t pairs_out;     /* concordant pairs written                                                   */
+    uint64_t handed_over;   /* fragments whose product exceeded a lane's budget: a wave each              */
+    uint64_t launches;      /* kernels launched                                                           */
+    double   kernel_ms;
+} real_hip_pair_all_stats;
+int real_hip_pair_all_stats_get(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

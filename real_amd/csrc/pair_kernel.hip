@@ -14,9 +14,6 @@
 #include "real_hip_internal.h"
 #include "pair_state.h"
 
-#define RH_PAIR_LANE_BUDGET 32u   /* product cells a lane walks itself */
-#define RH_PAIR_STRIPES 256u      /* the statistics are striped over this many 128-byte lines (see RH_CSTRIPES) */
-
 struct PairArgs {
     const uint4 *h1, *h2;          // real_hip_hit records of mate 1 / mate 2
     const uint64_t *o1, *o2;       // n + 1 offsets into them
@@ -31,17 +28,12 @@ struct PairArgs {
     uint32_t fresh, fileid, scores, min_insert, max_insert;
 };
 
-// real_hip_hit as a uint4: x read, y pos, z score bits, w frag:16 | k:8 | inverted:8
+// one cell of the product: a concordant pair (pair_state.h) is folded into the state
 static __device__ __forceinline__ void pair_cell(PairState &st, const uint4 a, const uint4 b, uint32_t la, uint32_t lb, const PairArgs &A)
 {
-    const uint32_t inva = a.w >> 24, invb = b.w >> 24;
-    if ((a.w & 0xffffu) != (b.w & 0xffffu) || (inva != 0) == (invb != 0)) return;
-    const bool a_fwd = inva == 0;
-    const uint64_t fp = a_fwd ? a.y : b.y, rp = a_fwd ? b.y : a.y;
-    const uint64_t fe = fp + (a_fwd ? la : lb), re = rp + (a_fwd ? lb : la);
-    if (fp > rp || fe > re) return;
-    const uint64_t outer = re - fp;
-    if (outer < A.min_insert || outer > A.max_insert) return;
+    uint64_t outer;
+    if (!pair_concordant(a, b, la, lb, A.min_insert, A.max_insert, outer)) return;
+    const uint32_t inva = a.w >> 24;
     const uint32_t ka = (a.w >> 16) & 0xffu, kb = (b.w >> 16) & 0xffu;
     PairState c;
     c.best = A.scores ? (double)__uint_as_float(a.z) + (double)__uint_as_float(b.z) : -(double)(ka + kb);
@@ -55,12 +47,6 @@ static __device__ __forceinline__ void pair_cell(PairState &st, const uint4 a, c
 static __device__ __forceinline__ double pair_eps(const PairArgs &A, uint32_t la, uint32_t lb)
 {
     return A.scores ? (double)(float)(A.filter_mult * (double)((uint64_t)la + lb)) : 0.0;
-}
-static __device__ __forceinline__ void pair_range(const uint64_t *o, uint64_t i, uint64_t total, uint64_t &lo, uint64_t &hi)
-{
-    hi = o[i + 1]; lo = o[i];
-    if (hi > total) hi = total;
-    if (lo > hi) lo = hi;
 }
 
 __global__ void __launch_bounds__(256) pair_lane_kernel(const PairArgs A)

@@ -1,7 +1,35 @@
 // pair_state.h -- the fold state of the paired-end records (include/real_hip.h, "paired-end reads"): shared by the join
-// (pair_kernel.hip) and the mate search (mate_search.hip), which fold candidates of the same kind into the same records.
+// (pair_kernel.hip) and the mate search (mate_search.hip), which fold candidates of the same kind into the same records;
+// and what the join shares with the enumeration of all concordant pairs (pair_all.hip): the concordance test, the
+// clamped range of a fragment's hits and the lane budget.
 #pragma once
 #include "real_hip_internal.h"
+
+#define RH_PAIR_LANE_BUDGET 32u   /* product cells a lane walks itself */
+#define RH_PAIR_STRIPES 256u      /* the statistics are striped over this many 128-byte lines (see RH_CSTRIPES) */
+
+// real_hip_hit as a uint4: x read, y pos, z score bits, w frag:16 | k:8 | inverted:8.
+// Hit a of mate 1 and hit b of mate 2 (read lengths la, lb) are concordant: same fragment, opposite strands, the forward
+// hit neither starts nor ends behind the reverse one, outer distance within the bounds.  outer: r.pos + len_r - f.pos
+static __device__ __forceinline__ bool pair_concordant(const uint4 a, const uint4 b, uint32_t la, uint32_t lb, uint32_t min_insert,
+                                                       uint32_t max_insert, uint64_t &outer)
+{
+    const uint32_t inva = a.w >> 24, invb = b.w >> 24;
+    if ((a.w & 0xffffu) != (b.w & 0xffffu) || (inva != 0) == (invb != 0)) return false;
+    const bool a_fwd = inva == 0;
+    const uint64_t fp = a_fwd ? a.y : b.y, rp = a_fwd ? b.y : a.y;
+    const uint64_t fe = fp + (a_fwd ? la : lb), re = rp + (a_fwd ? lb : la);
+    if (fp > rp || fe > re) return false;
+    outer = re - fp;
+    return outer >= min_insert && outer <= max_insert;
+}
+// hits [lo, hi) of fragment i: the offsets clamped to `total`, an upper bound of the hits inside the buffer
+static __device__ __forceinline__ void pair_range(const uint64_t *o, uint64_t i, uint64_t total, uint64_t &lo, uint64_t &hi)
+{
+    hi = o[i + 1]; lo = o[i];
+    if (hi > total) hi = total;
+    if (lo > hi) lo = hi;
+}
 
 // top two of a set of (value, location): the best with its payload, and the highest value at another location
 struct PairState {

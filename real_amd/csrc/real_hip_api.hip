@@ -96,6 +96,7 @@ void rh_time_resolve(real_hip_ctx *c)
             float ms = 0.f;
             if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
                 if (p.which == RH_K_MATE_SEARCH) c->ms_kernel_ms += ms;
+                else if (p.which == RH_K_PAIR_ALL) c->pa_kernel_ms += ms;
                 else { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
             }
             c->ev_pool.push_back(p.a);
@@ -221,7 +222,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     for (DevBuf *b : all) rh_release(*b);
     for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
     DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats,
-                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats};
+                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats, &c->pa_cnt, &c->pa_off, &c->pa_out, &c->pa_stats};
     for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
@@ -948,25 +949,16 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
     return rh_mate_search_finish(ctx);
 }
 
-// real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join
-static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_pair_params *pp,
-                           const real_hip_mate_search_params *sp, real_hip_pair *pairs)
+// matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
+// hold mate m's unified hit lists, their n + 1 offsets and the read lengths; total[m] is an upper bound of the hits inside
+// the buffer (the matcher's count before duplicates go).  both_resident: mate 2 is staged into buffers of its own, so that
+// both mates' reads stay on the device (st[] are their views).
+static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_resident, Staged st[2], uint64_t total[2])
 {
     int rc;
-    real_hip_batch bv[2];
-    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
-    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
-    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
-    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
-    if (sp && (rc = search_batches_check(ctx, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
-    if (!n) return REAL_HIP_OK;
-    if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pairs", hipSuccess);
-    // the search needs both mates' reads on the device at once: mate 2 is staged into buffers of its own then
-    Staged st[2];
     const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
-    const bool host_out = bv[0].on_device != 1;
-    uint64_t total[2] = {0, 0};
+    total[0] = total[1] = 0;
     for (int m = 0; m < 2; ++m) {
         if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
         if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
@@ -988,7 +980,7 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
             Staged &s = st[m];
             s = Staged();
             rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s,
-                               sp ? &bufs[m] : nullptr);
+                               both_resident ? &bufs[m] : nullptr);
             if (rc == REAL_HIP_E_OVERFLOW) { overflow = true; continue; } // (the other mate still reports its size)
             if (rc) return rc;
             // the read lengths, while this mate's offsets are staged
@@ -999,6 +991,27 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
         if (total[0] > 0xffffffffull || total[1] > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "more than 2^32 hits of one mate in one batch", hipSuccess);
         ctx->pair_cap = 0;
     }
+    return REAL_HIP_OK;
+}
+
+// real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join
+static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_pair_params *pp,
+                           const real_hip_mate_search_params *sp, real_hip_pair *pairs)
+{
+    int rc;
+    real_hip_batch bv[2];
+    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
+    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
+    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    if (sp && (rc = search_batches_check(ctx, bv))) return rc;
+    const uint64_t n = bv[0].n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pairs", hipSuccess);
+    Staged st[2];
+    uint64_t total[2] = {0, 0};
+    if ((rc = match_mates(ctx, bv, sp != nullptr, st, total))) return rc;
+    const bool host_out = bv[0].on_device != 1;
     real_hip_pair *d_pairs = pairs;
     const int fresh = bv[0].fresh != 0;
     if (host_out) {
@@ -1054,6 +1067,122 @@ extern "C" int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *o
     RH_ENTER(ctx);
     if (out && out->struct_size != sizeof(real_hip_pair_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair stats struct_size", hipSuccess);
     return rh_pair_stats(ctx, out, reset);
+}
+
+// ---- every concordant pair of a fragment (pair_all.hip) -----------------------------------------------------------
+// count, then -- the total being known -- the overflow decision, then the records; dev_out: out / pair_offsets are device memory
+static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *const d_h[2], const uint64_t *const d_o[2],
+                        const uint32_t *const d_l[2], const uint64_t total[2], uint64_t n, uint32_t fileid, bool dev_out,
+                        real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets)
+{
+    int rc;
+    uint64_t *d_off = pair_offsets;
+    if (!dev_out || !pair_offsets) {
+        if ((rc = rh_reserve(ctx, ctx->pa_off, (n + 1) * 8))) return rc;
+        d_off = (uint64_t *)ctx->pa_off.p;
+    }
+    uint64_t found = 0;
+    rc = rh_pair_all_count(ctx, pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, d_off, &found);
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    *n_out = found;
+    if (found > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "pair hit buffer too small", hipSuccess);
+    real_hip_pair_hit *d_out = out;
+    if (!dev_out) {
+        if ((rc = rh_reserve(ctx, ctx->pa_out, (found ? found : 1) * sizeof(real_hip_pair_hit)))) return rc;
+        d_out = (real_hip_pair_hit *)ctx->pa_out.p;
+    }
+    rc = rh_pair_all_emit(ctx, pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, fileid, d_off, d_out, dev_out ? cap : found, found);
+    if (!rc && !dev_out) {
+        hipError_t e = hipSuccess;
+        if (found) e = hipMemcpyAsync(out, d_out, found * sizeof(real_hip_pair_hit), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess && pair_offsets) e = hipMemcpyAsync(pair_offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair hits", e);
+    }
+    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return REAL_HIP_OK;
+}
+// what both entry points check of their outputs; n == 0 is answered here (*done)
+static int pair_all_outputs_check(real_hip_ctx *ctx, uint64_t n, bool dev_out, real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out,
+                                  uint64_t *pair_offsets, bool *done)
+{
+    *done = false;
+    if (!n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "null n_out", hipSuccess);
+    *n_out = 0;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
+    if (cap && !out) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pair hit buffer", hipSuccess);
+    if (dev_out && ((uintptr_t)out & 15u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the pair hit buffer must be 16-byte aligned", hipSuccess);
+    if (n) return REAL_HIP_OK;
+    *done = true;
+    if (pair_offsets) {
+        if (!dev_out) pair_offsets[0] = 0;
+        else {
+            RH_HIP(ctx, hipMemsetAsync(pair_offsets, 0, 8, ctx->stream));
+            RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+    }
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_pair_all_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
+                                      const uint32_t *len1, const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                                      uint64_t n_pairs, uint32_t fileid, int on_device, real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out,
+                                      uint64_t *pair_offsets)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    if (fileid > 255) return rh_fail(ctx, REAL_HIP_E_INVALID, "fileid > 255", hipSuccess);
+    const uint64_t n = n_pairs;
+    bool done;
+    if ((rc = pair_all_outputs_check(ctx, n, on_device != 0, out, cap, n_out, pair_offsets, &done)) || done) return rc;
+    if (!off1 || !off2 || !len1 || !len2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths", hipSuccess);
+    const real_hip_hit *d_h[2] = {hits1, hits2};
+    const uint64_t *d_o[2] = {off1, off2};
+    const uint32_t *d_l[2] = {len1, len2};
+    uint64_t total[2] = {0, 0};
+    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0))) return rc;
+    if (!on_device)
+        for (int m = 0; m < 2; ++m) {
+            if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
+            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, d_l[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
+            d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
+        }
+    return pair_all_run(ctx, *pp, d_h, d_o, d_l, total, n, fileid, on_device != 0, out, cap, n_out, pair_offsets);
+}
+
+extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                        const real_hip_pair_params *pp, real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    real_hip_batch bv[2];
+    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
+    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
+    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    const uint64_t n = bv[0].n_reads;
+    const bool dev_out = bv[0].on_device == 1;
+    bool done;
+    if ((rc = pair_all_outputs_check(ctx, n, dev_out, out, cap, n_out, pair_offsets, &done)) || done) return rc;
+    Staged st[2];
+    uint64_t total[2] = {0, 0};
+    if ((rc = match_mates(ctx, bv, false, st, total))) return rc;
+    const real_hip_hit *d_h[2] = {(const real_hip_hit *)ctx->pair_hits[0].p, (const real_hip_hit *)ctx->pair_hits[1].p};
+    const uint64_t *d_o[2] = {(const uint64_t *)ctx->pair_off[0].p, (const uint64_t *)ctx->pair_off[1].p};
+    const uint32_t *d_l[2] = {(const uint32_t *)ctx->pair_len[0].p, (const uint32_t *)ctx->pair_len[1].p};
+    return pair_all_run(ctx, *pp, d_h, d_o, d_l, total, n, ctx->fileid, dev_out, out, cap, n_out, pair_offsets);
+}
+
+extern "C" int real_hip_pair_all_stats_get(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_pair_all_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair all stats struct_size", hipSuccess);
+    return rh_pair_all_stats(ctx, out, reset);
 }
 
 // ---------------------------------------------------------------------------

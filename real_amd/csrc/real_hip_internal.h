@@ -253,6 +253,12 @@ struct real_hip_ctx {
     double   ms_kernel_ms = 0;
     uint32_t ms_err = 0;     // the flags of the last launch, copied back behind it
 
+    // every concordant pair of a fragment (pair_all.hip): counts per fragment, their scan and the staged records when the
+    // caller's outputs are host memory, striped statistics, the event times of its launches
+    DevBuf pa_cnt, pa_off, pa_out, pa_stats;
+    uint64_t pa_fragments = 0, pa_pairs_out = 0, pa_launches = 0;
+    double   pa_kernel_ms = 0;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -329,6 +335,17 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
                           const uint64_t *d_o2, uint64_t total2, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
 int rh_mate_search_finish(real_hip_ctx *ctx);
 int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
+
+// ---- every concordant pair of a fragment (pair_all.hip) ---------------------------
+#define RH_K_PAIR_ALL (-2) /* rh_time_begin: the time goes to ctx->pa_kernel_ms */
+// count + scan into d_off (n + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
+int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
+                      uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
+                      uint64_t *d_off, uint64_t *total);
+int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
+                     uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
+                     uint32_t fileid, const uint64_t *d_off, real_hip_pair_hit *d_out, uint64_t cap, uint64_t total);
+int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

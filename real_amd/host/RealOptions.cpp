@@ -44,6 +44,8 @@ void RealOptions::printHelp() const
               << "-mate_search <0|1: with -p2, search the window every hit of one mate allows for a placement of the other mate that\n"
               << "   the seeds missed (more than -s mismatches in its first -l bases, at most -e in the whole read), default=0>\n"
               << "-mate_search_anchors <a mate with more hits than this in a genome file starts no search, 0=no limit, default=0>\n"
+              << "-pairs_all <0|1: with -p2, print EVERY concordant pair of a fragment (two lines each, per genome file, in the order of\n"
+              << "   the two mates' hit lists) instead of the unique one; pairs of two seed hits: not with -mate_search 1, default=0>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -103,6 +105,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-insert_min") { insert_min = (uint32_t)strtoul(need("-insert_min").c_str(), 0, 10); i += 2; }
         else if (a == "-insert_max") { insert_max = (uint32_t)strtoul(need("-insert_max").c_str(), 0, 10); i += 2; }
         else if (a == "-mate_search") { mate_search = atoi(need("-mate_search").c_str()) != 0; mate_search_given = true; i += 2; }
+        else if (a == "-pairs_all") { pairs_all = atoi(need("-pairs_all").c_str()) != 0; pairs_all_given = true; i += 2; }
         else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
@@ -165,15 +168,19 @@ RealOptions::RealOptions(int argc, char *argv[])
     std::cerr << "filter_mult=" << filter_mult << std::endl;
     if (gpus < 1) gpus = 1;
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
-        if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0.");
+        if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");
         if (gpus > 1) throw std::runtime_error("-p2 (paired-end reads) runs on one device: it cannot be combined with -gpus > 1.");
         if (pattern2filename == "-" || !stdin_spool.empty()) throw std::runtime_error("-p2 (paired-end reads) needs two files: standard input cannot be one of them.");
         if (insert_min > insert_max) throw std::runtime_error("-insert_min is larger than -insert_max.");
         if (mate_search && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
             throw std::runtime_error("-mate_search 1 takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
+        if (pairs_all && mate_search)
+            throw std::runtime_error("-pairs_all 1 lists the concordant pairs of two seed hits: it cannot be combined with -mate_search 1.");
         fastq2 = isFastQ(pattern2filename);
     } else if (mate_search_given) {
         throw std::runtime_error("-mate_search / -mate_search_anchors are only meaningful with -p2 (paired-end reads).");
+    } else if (pairs_all_given) {
+        throw std::runtime_error("-pairs_all is only meaningful with -p2 (paired-end reads).");
     }
     if (chunk_bytes < 4096) chunk_bytes = 4096;
     if (chunk_bytes > (4ull << 30) - (1ull << 20)) chunk_bytes = (4ull << 30) - (1ull << 20); // real_hip_parse_reads: n_bytes < 4 GiB

@@ -4,6 +4,7 @@
 //   host_selftest index <g.fa> <seedl> <first> <max> <threads> <outdir> -> l<k>_sign.bin l<k>_pos.u32 meta.txt
 //   host_selftest options <args...>               -> prints the parsed RealOptions
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
+//   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair tables (csrc/row_addr.h), prints ok
 #include <cstdio>
 #include <cstdlib>
@@ -183,6 +184,11 @@ int main(int argc, char **argv)
         if (cmd == "mate_search_options") { // -mate_search, -mate_search_anchors
             RealOptions o(argc - 1, argv + 1);
             std::cout << o.mate_search << " " << o.mate_search_anchors << "\n";
+            return 0;
+        }
+        if (cmd == "pairs_all_options") { // -pairs_all
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << o.pairs_all << "\n";
             return 0;
         }
         return 2;

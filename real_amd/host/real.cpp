@@ -827,6 +827,97 @@ int matchPairs(const RealOptions &o)
     return EXIT_SUCCESS;
 }
 
+// ---- paired-end reads: every concordant pair of a fragment (-pairs_all 1) -----------------------------------------
+// Per genome file, as matchAll emits per block: real_hip_match_pairs_all gives every concordant pair of two seed hits of
+// every fragment; for every fragment in read order and every pair in the ABI's order (row-major over the two mates' hit
+// lists) the 11-column line of mate 1 and then of mate 2 is printed.  There is no fold across genome files.
+int matchPairsAll(const RealOptions &o)
+{
+    Timers T;
+    const double t_begin = now_s();
+    const int qoff1 = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
+    const int qoff2 = o.fastq2 ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.pattern2filename)) : 0;
+    if ((o.fastq && !qoff1) || (o.fastq2 && !qoff2)) throw std::runtime_error("Unable to automatically detect FastQ quality format.");
+    std::vector<std::string> files;
+    getFileList(o.textfilename, files);
+    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
+    if (files.size() > 64) throw std::runtime_error("more than 64 text files");
+    CtxVec ctx = makeContexts(o);
+    real_hip_ctx *h = ctx[0]->h;
+    real_hip_pair_params pp;
+    memset(&pp, 0, sizeof pp);
+    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
+    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
+    std::vector<char> obuf((size_t)8 << 20);
+    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    std::vector<real_hip_pair_hit> hits;
+    std::vector<uint64_t> poff;
+    uint64_t numpat = 0, n_pairs = 0;
+    ReadBlock b1, b2;
+    for (unsigned fi = 0; fi < files.size(); ++fi) {
+        std::cerr << "Processing file " << files[fi] << ((fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
+        Resident R;
+        double t0 = now_s();
+        R.G.load(files[fi]);
+        T.genome += now_s() - t0;
+        t0 = now_s();
+        setText(o, ctx, R, fi);
+        const uint64_t n_list = blockEntries(o, h, R.G.sym.size() ? R.G.sym.size() : 1);
+        bool have_next = false;
+        const uint64_t n = nextBlock(o, ctx, R, 0, n_list, have_next);
+        T.index += now_s() - t0;
+        if (have_next)
+            throw std::runtime_error("paired-end reads: " + files[fi] + " needs more than one index block (pairs across blocks would be lost); "
+                                     "raise -f / -block or split the file");
+        if (!n) continue;
+        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            t0 = now_s();
+            const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
+            T.read += now_s() - t0;
+            if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
+            if (!n1) break;
+            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            poff.assign(n1 + 1, 0);
+            if (hits.size() < n1 + n1 / 4 + 1024) hits.resize(n1 + n1 / 4 + 1024); // (about one pair per fragment is the rule: room for a quarter more)
+            const double tm = now_s();
+            uint64_t np = 0;
+            int rc = real_hip_match_pairs_all(h, &rb1, &rb2, &pp, hits.data(), hits.size(), &np, poff.data());
+            if (rc == REAL_HIP_E_OVERFLOW) { // retry with the size the library reports
+                hits.resize(np + 16);
+                rc = real_hip_match_pairs_all(h, &rb1, &rb2, &pp, hits.data(), hits.size(), &np, poff.data());
+            }
+            check(h, rc, "real_hip_match_pairs_all");
+            T.match += now_s() - tm;
+            n_pairs += np;
+            formatAndWrite(n1, out, T, [&](uint64_t i, std::string &s) {
+                const uint64_t lo1 = b1.offsets[i], lo2 = b2.offsets[i];
+                for (uint64_t k = poff[i]; k < poff[i + 1]; ++k) {
+                    const real_hip_pair_hit &P = hits[k];
+                    const std::string &fname = R.G.frag_names[P.frag];
+                    const uint64_t fs = R.G.frag_start[P.frag];
+                    appendLine(s, b1.ids[i].data(), b1.ids[i].size(), nullptr, &b1.bases[lo1], b1.offsets[i + 1] - lo1, o.scores, o.scores ? P.score1 : 0.f,
+                               P.inverted1 != 0, fname, (uint64_t)P.pos1 - fs + 1, P.k1);
+                    appendLine(s, b2.ids[i].data(), b2.ids[i].size(), nullptr, &b2.bases[lo2], b2.offsets[i + 1] - lo2, o.scores, o.scores ? P.score2 : 0.f,
+                               P.inverted1 == 0, fname, (uint64_t)P.pos2 - fs + 1, P.k2);
+                }
+            });
+            seen += n1;
+        }
+        if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
+        else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+    }
+    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
+    if (out != stdout) fclose(out);
+    std::cerr << "All done." << std::endl;
+    std::cerr << "concordant pairs: " << n_pairs << std::endl;
+    T.reads = 2 * numpat; T.lines = 2 * n_pairs; T.total = now_s() - t_begin;
+    T.print();
+    return EXIT_SUCCESS;
+}
+
 } // namespace
 
 int main(int argc, char *argv[])
@@ -834,7 +925,7 @@ int main(int argc, char *argv[])
     std::cerr << "This is real (MI355X read-matching path), ABI " << real_hip_abi_version() << "." << std::endl;
     try {
         RealOptions opts(argc, argv);
-        if (!opts.pattern2filename.empty()) return matchPairs(opts);
+        if (!opts.pattern2filename.empty()) return opts.pairs_all ? matchPairsAll(opts) : matchPairs(opts);
         return opts.match_unique ? matchUnique(opts) : matchAll(opts);
     } catch (const std::bad_alloc &) {
         std::cerr << "Insufficient memory." << std::endl;

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "real_hip_comm_id", "real_hip_comm_init", "real_hip_comm_destroy", "real_hip_gather_records", "real_hip_gather_hits",
     "real_hip_pair_hits", "real_hip_match_pairs", "real_hip_pair_stats_get",
     "real_hip_pair_search", "real_hip_match_pairs_search", "real_hip_mate_search_stats_get",
+    "real_hip_pair_all_hits", "real_hip_match_pairs_all", "real_hip_pair_all_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -99,6 +100,22 @@ class RealHipMateSearchStats(C.Structure):
                 ("anchors_skipped", C.c_uint64), ("positions", C.c_uint64), ("placements", C.c_uint64), ("launches", C.c_uint64),
                 ("kernel_ms", C.c_double)]
 
+
+class RealHipPairAllStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fragments", C.c_uint64), ("products", C.c_uint64),
+                ("pairs_out", C.c_uint64), ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+class RealHipPairHit(C.Structure):
+    """real_hip_pair_hit: one concordant pair (PAIR_HIT_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("pair", C.c_uint32), ("pos1", C.c_uint32), ("pos2", C.c_uint32), ("outer", C.c_uint32),
+                ("score1", C.c_float), ("score2", C.c_float), ("frag", C.c_uint16), ("fileid", C.c_uint8),
+                ("inverted1", C.c_uint8), ("k1", C.c_uint8), ("k2", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+PAIR_HIT_DTYPE = np.dtype([("pair", "<u4"), ("pos1", "<u4"), ("pos2", "<u4"), ("outer", "<u4"), ("score1", "<f4"), ("score2", "<f4"),
+                           ("frag", "<u2"), ("fileid", "u1"), ("inverted1", "u1"), ("k1", "u1"), ("k2", "u1"), ("reserved", "<u2")])
+assert PAIR_HIT_DTYPE.itemsize == 32 and C.sizeof(RealHipPairHit) == 32
 
 # real_hip_pair: the in/out record of one fragment
 PAIR_DTYPE = np.dtype([("best", "<f8"), ("second", "<f8"), ("pos1", "<u4"), ("pos2", "<u4"), ("score1", "<f4"), ("score2", "<f4"),
@@ -174,6 +191,10 @@ def load():
     L.real_hip_match_pairs_search.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
                                               C.POINTER(RealHipMateSearchParams), vp]
     L.real_hip_mate_search_stats_get.argtypes = [vp, C.POINTER(RealHipMateSearchStats), C.c_int]
+    L.real_hip_pair_all_hits.argtypes = [vp, C.POINTER(RealHipPairParams), vp, vp, vp, vp, vp, vp, u64, u32, C.c_int, vp, u64, C.POINTER(u64), vp]
+    L.real_hip_match_pairs_all.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp, u64,
+                                           C.POINTER(u64), vp]
+    L.real_hip_pair_all_stats_get.argtypes = [vp, C.POINTER(RealHipPairAllStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

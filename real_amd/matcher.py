@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _lib
-from .lib import (HIT_DTYPE, PAIR_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
+from .lib import (HIT_DTYPE, PAIR_DTYPE, PAIR_HIT_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
 
 NO_SCORE = np.float32(-np.finfo(np.float32).max)   # UniqueMatchInfo<true>() : score(-FLT_MAX), UniqueMatchInfo.hpp:191
 
@@ -52,6 +52,8 @@ class RealOptions:
     insert_max: int = 1000
     mate_search: bool = False       # -mate_search: search every hit's window for a placement of the other mate the seeds missed
     mate_search_anchors: int = 0    # -mate_search_anchors: a mate with more hits than this contributes no anchors (0: no limit)
+    pairs_all: bool = False         # -pairs_all: with -p2, print every concordant pair of a fragment instead of the unique one
+    pairs_all_given: bool = False   # (the flag was on the command line: an error without -p2)
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -68,15 +70,19 @@ class RealOptions:
             self.seedkmax = 2
         if self.pattern2filename:       # the loud errors of `real -p2`
             if not self.match_unique:
-                raise ValueError("-p2 (paired-end reads) cannot be combined with -u 0")
+                raise ValueError("-p2 (paired-end reads) cannot be combined with -u 0 (every concordant pair: -pairs_all 1)")
             if self.gpus > 1:
                 raise ValueError("-p2 (paired-end reads) cannot be combined with -gpus > 1")
             if self.insert_min > self.insert_max:
                 raise ValueError("-insert_min is larger than -insert_max")
             if self.mate_search and self.insert_max > _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT:
                 raise ValueError("-mate_search 1 takes an -insert_max of at most %d" % _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT)
+            if self.pairs_all and self.mate_search:
+                raise ValueError("-pairs_all 1 lists pairs of two seed hits: it cannot be combined with -mate_search 1")
         elif self.mate_search or self.mate_search_anchors:
             raise ValueError("-mate_search / -mate_search_anchors need -p2 (paired-end reads)")
+        elif self.pairs_all or self.pairs_all_given:
+            raise ValueError("-pairs_all needs -p2 (paired-end reads)")
         if self.mate_search_anchors < 0:
             raise ValueError("-mate_search_anchors must not be negative")
         return self
@@ -105,7 +111,8 @@ class RealOptions:
                  "-trans": ("trans", float), "-gc": ("gc", float), "-gcmut_bias": ("gcmut_bias", float),
                  "-filter_level": ("filter_level", int), "-p2": ("pattern2filename", str), "-insert_min": ("insert_min", int),
                  "-insert_max": ("insert_max", int), "-gpus": ("gpus", int),
-                 "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int)}
+                 "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int),
+                 "-pairs_all": ("pairs_all", lambda v: bool(int(v)))}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -114,6 +121,8 @@ class RealOptions:
                     raise ValueError("Parameter for argument %s is missing." % a)
                 name, conv = table[a]
                 setattr(o, name, conv(argv[i + 1]))
+                if a == "-pairs_all":
+                    o.pairs_all_given = True
                 i += 2
             else:
                 i += 1
@@ -574,3 +583,70 @@ class PairMatcher(AllMatcher):
         st.struct_size = C.sizeof(_lib.RealHipPairStats)
         self._check(self._L.real_hip_pair_stats_get(self._h, C.byref(st), int(reset)))
         return {"pairs": int(st.pairs), "products": int(st.products), "handed_over": int(st.handed_over)}
+
+    # -- every concordant pair of a fragment (real_hip_pair_hit records) --
+    def _pair_all_call(self, call, n: int, on_device: bool, cap: int, out, pair_offsets):
+        """one enumeration call with the overflow retry of match_all: host outputs are allocated here and grow to the size
+        the library reports; device outputs are the caller's (a too small `out` raises)"""
+        nout = C.c_uint64(0)
+        if on_device:
+            if out is None or pair_offsets is None:
+                raise ValueError("device inputs need device tensors for the pair hits and the offsets")
+            self.sync_inputs(out, pair_offsets)
+            rc = call(_ptr(out), int(cap or out.numel() * out.element_size() // 32), C.byref(nout), _ptr(pair_offsets))
+            if rc == _lib.REAL_HIP_E_OVERFLOW:      # the caller's tensor: he sizes it again (needed: records)
+                err = RealHipError(rc, "pair hit buffer too small: %d records needed" % nout.value)
+                err.needed = int(nout.value)
+                raise err
+            self._check(rc)
+            return int(nout.value), pair_offsets
+        cap = cap or max(1024, 2 * n)
+        while True:
+            out = np.zeros(cap, dtype=PAIR_HIT_DTYPE)
+            poff = np.zeros(n + 1, dtype=np.uint64)
+            rc = call(out.ctypes.data, cap, C.byref(nout), poff.ctypes.data)
+            if rc == _lib.REAL_HIP_E_OVERFLOW:      # retry with the size the library reports
+                cap = int(nout.value)
+                continue
+            self._check(rc)
+            return out[:int(nout.value)], poff
+
+    def pair_all_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0,
+                      orientation: int = 0, cap: int = 0, out=None, pair_offsets=None):
+        """real_hip_pair_all_hits: every concordant pair of every fragment, row-major over the product of the two lists the
+        caller holds.  Host arrays -> (pair hits as lib.PAIR_HIT_DTYPE, offsets); device tensors need `out` (32-byte
+        records) and `pair_offsets` (n + 1 int64) as device tensors -> (number of pairs, pair_offsets)."""
+        on_device = bool(getattr(off1, "is_cuda", False))
+        if not on_device:
+            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
+            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
+            len1, len2 = np.ascontiguousarray(len1, dtype=np.uint32), np.ascontiguousarray(len2, dtype=np.uint32)
+        n = int(off1.shape[0]) - 1
+        if int(off2.shape[0]) - 1 != n or int(len1.shape[0]) != n or int(len2.shape[0]) != n:
+            raise ValueError("the two mates' arrays describe different numbers of reads")
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        self.sync_inputs(hits1, off1, len1, hits2, off2, len2)
+
+        def call(o, c, no, po):
+            return self._L.real_hip_pair_all_hits(self._h, C.byref(pp), _ptr(hits1), _ptr(off1), _ptr(len1), _ptr(hits2), _ptr(off2),
+                                                  _ptr(len2), n, int(fileid), int(on_device), o, c, no, po)
+        return self._pair_all_call(call, n, on_device, cap, out, pair_offsets)
+
+    def match_pairs_all(self, mate1, mate2, min_insert: int, max_insert: int, orientation: int = 0, cap: int = 0, out=None,
+                        pair_offsets=None):
+        """real_hip_match_pairs_all: matchAll of both mates with the hits kept on the device, then every concordant pair.
+        Host batches -> (pair hits, offsets) as numpy arrays; device batches need `out` and `pair_offsets` as device
+        tensors -> (number of pairs, pair_offsets)."""
+        b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+
+        def call(o, c, no, po):
+            return self._L.real_hip_match_pairs_all(self._h, C.byref(b1), C.byref(b2), C.byref(pp), o, c, no, po)
+        return self._pair_all_call(call, int(b1.n_reads), bool(b1.on_device), cap, out, pair_offsets)
+
+    def pair_all_stats(self, reset: bool = False) -> dict:
+        st = _lib.RealHipPairAllStats()
+        st.struct_size = C.sizeof(_lib.RealHipPairAllStats)
+        self._check(self._L.real_hip_pair_all_stats_get(self._h, C.byref(st), int(reset)))
+        return {"fragments": int(st.fragments), "products": int(st.products), "pairs_out": int(st.pairs_out),
+                "handed_over": int(st.handed_over), "launches": int(st.launches), "kernel_ms": float(st.kernel_ms)}
