@@ -459,7 +459,8 @@ __global__ void rows_unpack_kernel(const uint4 *__restrict__ rows, const uint2 *
     }
 }
 
-// the canonical order of a list placed by the rc-form of its signature (lists 5, 4 of the pair tables): by rh_mix32 of its OWN signature
+// the order index_download presents of a list that is not placed by its own signature (lists 5, 4 of the pair tables, lists 2, 3
+// of the canonical tables): by rh_mix32 of its OWN signature
 __global__ void own_keys_kernel(const uint2 *__restrict__ ent, const uint64_t *__restrict__ T, uint64_t n, uint32_t l, int list,
                                 uint32_t *__restrict__ keys)
 {
@@ -489,19 +490,19 @@ static hipError_t sort_pairs(void *tmp, size_t &tmp_bytes, rocprim::double_buffe
 
 // entries of list `list` as {key, pos} (key = the row's 16 partner bits, or the overflow entry's key) and the 2^pb + 1 bucket
 // starts; either output may be null.  Used by index_download / index_export.  The order is the one of the rows, which for
-// lists 5 and 4 of a pair table is that of the rc-form of their signatures; `canonical` (both outputs wanted) sorts those
-// two back to the order of rh_mix32 of their own signature, the one every other list has: what index_download presents is
-// that canonical order, not the physical one.
+// lists 5 and 4 of a pair table is that of the rc-form of their signatures and for lists 2 and 3 that of their canonical
+// index (row_addr.h); `canonical` (both outputs wanted) sorts those four back to the order of rh_mix32 of their own signature,
+// the one lists 0 and 1 have: what index_download presents is that order, not the physical one.
 int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts, bool canonical)
 {
     const uint32_t l = ctx->prm.seedl;
-    const bool paired = l <= 32 && rh_list_paired((uint32_t)list);
-    const int table = paired && list > 3 ? 5 - list : list;
-    const uint64_t nb = rh_table_rows((uint32_t)list, l, ctx->pb), n = ctx->n_entries;
+    const bool narrow = l <= 32, paired = narrow && rh_table_kind((uint32_t)list) == RH_TABLE_PAIR;
+    const int table = narrow ? (int)rh_table_of((uint32_t)list) : list;
+    const uint64_t nb = narrow ? rh_table_rows((uint32_t)list, ctx->pb) : 1ull << ctx->pb, n = ctx->n_entries;
     uint32_t pshift, fshift, fbits, pbits;
     rh_index_geometry(l, ctx->pb, &pshift, &fshift, &fbits, &pbits);
     const uint32_t half = paired ? 1u << (fbits - 1) : 16u, g0 = paired && list > 3 ? half : 0u, g1 = paired && list < 2 ? half : 16u;
-    const bool resort = canonical && paired && list > 3 && n;
+    const bool resort = canonical && narrow && list > 1 && n;
     if (resort && !(d_entries && d_starts)) return rh_fail(ctx, REAL_HIP_E_INVALID, "rows unpack: canonical order needs both outputs", hipSuccess);
     int rc;
     ScopedBuf sizes(ctx), offs(ctx);
@@ -590,7 +591,7 @@ static int plan_scratch(real_hip_ctx *ctx, BuildScratch &S, uint64_t n, unsigned
 {
     const uint32_t l = ctx->prm.seedl;
     const bool rows = ctx->layout == RH_LAYOUT_ROWS;
-    const size_t nn = n ? n : 1, nb1 = (rows ? (size_t)rh_table_rows(0, l, ctx->pb) : (size_t)1 << ctx->pb) + 1;
+    const size_t nn = n ? n : 1, nb1 = (rows && l <= 32 ? (size_t)rh_table_rows(0, ctx->pb) : (size_t)1 << ctx->pb) + 1;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     size_t sort_tmp = 0, scan_tmp = 0;
     if (need_sort && n) {
@@ -635,10 +636,11 @@ static int index_from_sorted(real_hip_ctx *ctx, BuildScratch &S, int list, const
     uint32_t pshift, fshift, fbits, pbits;
     rh_index_geometry(l, pb, &pshift, &fshift, &fbits, &pbits);
     const bool rows = ctx->layout == RH_LAYOUT_ROWS;
-    // pair tables (narrow rows): list 0 / 1 fills a table of twice the rows, list 5 / 4 is merged into it
-    const bool paired = rows && l <= 32 && rh_list_paired((uint32_t)list), second = paired && list > 3;
+    // pair tables (narrow rows): list 0 / 1 fills a table of twice the rows, list 5 / 4 is merged into it.  A canonical table
+    // (lists 2, 3) is cut like a table of its own: its list comes sorted by row, then group (rh_place_key), `which` included
+    const bool paired = rows && l <= 32 && rh_table_kind((uint32_t)list) == RH_TABLE_PAIR, second = paired && list > 3;
     const int table = second ? 5 - list : list;
-    const uint32_t nb = (uint32_t)(rows ? rh_table_rows((uint32_t)list, l, pb) : 1ull << pb);
+    const uint32_t nb = (uint32_t)(rows && l <= 32 ? rh_table_rows((uint32_t)list, pb) : 1ull << pb);
     const uint32_t gbits = fbits;
     if (paired) { pshift -= 1; fbits -= 1; }
     const uint32_t gor = second ? 1u << fbits : 0u;
@@ -779,24 +781,24 @@ __global__ void iota_kernel(uint32_t *out, uint64_t first, uint64_t n)
     if (i < n) out[i] = (uint32_t)(first + i);
 }
 
-// list k signature of the window at wpos[j]; mix: the sort key of the bucket rows (rh_mix32 / rh_mix64)
-// (narrow rows: of the signature the list is placed by, rh_place_sig)
+// list k signature of the window at wpos[j]; mix: the sort key of the bucket rows (narrow rows: rh_place_key, the key that
+// orders the list's entries by row, then group; wide rows: rh_mix64)
 template <typename K>
-__device__ __forceinline__ K mixed_key(K v, uint32_t l, int list) { return sizeof(K) == 4 ? (K)rh_mix32(rh_place_sig((uint32_t)list, (uint32_t)v, l), l) : (K)rh_mix64((uint64_t)v, l); }
+__device__ __forceinline__ K mixed_key(K v, uint32_t l, int list, uint32_t gbits) { return sizeof(K) == 4 ? (K)rh_place_key((uint32_t)list, (uint32_t)v, l, gbits) : (K)rh_mix64((uint64_t)v, l); }
 template <typename K>
 __global__ void keys_kernel(const uint64_t *__restrict__ T, const uint32_t *__restrict__ wpos, uint64_t n, uint32_t l,
-                            int list, bool mix, K *__restrict__ keys)
+                            int list, bool mix, uint32_t gbits, K *__restrict__ keys)
 {
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const K v = (K)window_signature(T, wpos[j], l, list);
-    keys[j] = mix ? mixed_key<K>(v, l, list) : v;
+    keys[j] = mix ? mixed_key<K>(v, l, list, gbits) : v;
 }
 template <typename K>
-__global__ void mix_keys_kernel(K *__restrict__ keys, uint64_t n, uint32_t l, int list)
+__global__ void mix_keys_kernel(K *__restrict__ keys, uint64_t n, uint32_t l, int list, uint32_t gbits)
 {
     uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < n) keys[j] = mixed_key<K>(keys[j], l, list);
+    if (j < n) keys[j] = mixed_key<K>(keys[j], l, list, gbits);
 }
 
 // d_wpos: the window starts of the block in ascending order, or null = every window from first_window on (no N in the text)
@@ -809,13 +811,15 @@ static int sort_list(real_hip_ctx *ctx, BuildScratch &S, int list, const uint32_
     const void *d_sign = S.keys_b;
     const uint32_t *d_pos = S.vals_b;
     const bool mix = ctx->layout == RH_LAYOUT_ROWS;
+    uint32_t pshift, fshift, gbits, pbits;
+    rh_index_geometry(l, ctx->pb, &pshift, &fshift, &gbits, &pbits);
     if (n) {
         rh_time_begin(ctx, ctx->stream, REAL_HIP_K_INDEX);
         const dim3 grid((unsigned)((n + 255) / 256)), block(256);
         rocprim::double_buffer<K> keys((K *)S.keys_a, (K *)S.keys_b);
         rocprim::double_buffer<uint32_t> vals(S.vals_x, S.vals_b);
         if (uploaded) {
-            hipLaunchKernelGGL(mix_keys_kernel<K>, grid, block, 0, ctx->stream, (K *)S.keys_b, n, l, list);
+            hipLaunchKernelGGL(mix_keys_kernel<K>, grid, block, 0, ctx->stream, (K *)S.keys_b, n, l, list, gbits);
             keys = rocprim::double_buffer<K>((K *)S.keys_b, (K *)S.keys_a);
             vals = rocprim::double_buffer<uint32_t>(S.vals_b, S.vals_x);
         } else {
@@ -823,7 +827,7 @@ static int sort_list(real_hip_ctx *ctx, BuildScratch &S, int list, const uint32_
             if (d_wpos) RH_HIP(ctx, hipMemcpyAsync(S.vals_x, d_wpos, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
             else hipLaunchKernelGGL(iota_kernel, grid, block, 0, ctx->stream, S.vals_x, first_window, n);
             hipLaunchKernelGGL(keys_kernel<K>, grid, block, 0, ctx->stream, (const uint64_t *)ctx->text.p, (const uint32_t *)S.vals_x, n, l, list, mix,
-                               (K *)S.keys_a);
+                               gbits, (K *)S.keys_a);
         }
         size_t tmp = S.sort_tmp_bytes;
         RH_HIP(ctx, sort_pairs<K>(S.sort_tmp, tmp, keys, vals, n, l, ctx->stream));

@@ -30,8 +30,9 @@
 // The update() events of a read reach the fold in the canonical order (strand, list, position), which
 // matters because the fold is order dependent when scores are on.  Every index access is a
 // dependent random read of a 128-byte line of an HBM-resident table: the kernel is bound by the HBM lines it
-// moves (13.6 per read with bucket rows on the C2 workload), not by arithmetic (no MFMA:
-// XOR/popcount and a short FP64 add chain).
+// moves (13.6 per read with one bucket row per lookup on the C2 workload, 7.5 with the six rows of the paired driver, where
+// the decode of the rows weighs as much: DESIGN.md section 4), not by arithmetic (no MFMA: XOR/popcount and a short FP64
+// add chain).
 #include "match_common.h"
 
 // RH_ABLATE (experimental builds only, make variant): bit 0 no scoring, bit 1 no verification of queued candidates,
@@ -99,7 +100,7 @@ struct LaneInst {
     static constexpr bool WIDE = TK == TK_ROWS_WIDE;    // (a compile-time property: as a run-time flag it cost the 32-bit path registers)
     static constexpr bool DIR = TK == TK_DIRECTORY;
     static constexpr bool HAS_PASS2 = ROWS && DEFER;    // a second pass stands behind the first
-    // the paired driver (match_rows_paired): narrow rows, no early-out between the lists (parked hits), first pass -- eight row
+    // the paired driver (match_rows_paired): narrow rows, no early-out between the lists (parked hits), first pass -- six row
     // lines per read.  The second pass keeps the strand loop and its MQR2 slots per strand: it sees a few hundred reads.
     static constexpr bool PAIRED = ROWS && !WIDE && DEFER && !PASS2;
     static constexpr int NP = PASS2 ? NPEND2 : NPEND;   // parked locations
@@ -871,7 +872,7 @@ __device__ __forceinline__ void match_lists_rows(const MatchArgs &a, LaneState<T
     // the rows are addressed by the MIXED signature (real_hip_internal.h: rh_mix32 / rh_mix64): row = its leading bits,
     // key group = the bits below; the partner key of an entry is plain
     auto msig_wide = [&](int la) { return rh_mix64(sig_wide(la), a.l); };
-    // (narrow: row and key group by rh_row_addr -- lists 0 / 5 and 1 / 4 share a pair table)
+    // (narrow: row and key group by rh_row_addr -- lists 0 / 5 and 1 / 4 share a pair table, lists 2 and 3 have canonical tables)
     auto bucket_of = [&](int la) { return wide ? (uint32_t)(msig_wide(la) >> a.ix.pshift) : rh_row_addr((uint32_t)la, sig_of(la), a.l, gbits).row; };
     uint32_t qn = 0, q_last = 0, q_lastla = 0; // queue fill; position and list bits of the entry pushed last
     uint4 va0, va1, va2, va3, va4, va5, va6, va7; // (eight scalars, not an array: the array went through scratch memory)
@@ -1114,21 +1115,28 @@ __device__ __forceinline__ void match_lists_rows(const MatchArgs &a, LaneState<T
 }
 
 // ---------------------------------------------------------------------------
-// bucket rows, paired driver (LaneInst::PAIRED): BOTH strands of a read from eight rows
+// bucket rows, paired driver (LaneInst::PAIRED): BOTH strands of a read from six rows
 // ---------------------------------------------------------------------------
 // With parked hits there is no early-out between the lists: all twelve (strand, list) lookups of a read are always made, and
-// the pair tables (real_hip_internal.h: paired bucket rows) answer two of them with one row.  Round li = 2 t + ks fetches
-// the row of table t (P05, P14, list 2, list 3) found with strand ks' signature of list t; the owner lane decodes the key
-// group of (ks, t) and -- pair tables -- the group of (1 - ks, 5 - t), which differs in the `which` bit alone.  When the
-// seed is its own reverse complement the two rounds of a table fetch the same row; each round still answers its own two
-// (strand, list), so every lookup is answered exactly once.  Survivors of both strands share one queue, tagged with their
+// every table (row_addr.h) answers two of them with one row.  Rounds 0 .. 3, li = 2 t + ks, fetch the row of pair table t
+// (P05, P14) found with strand ks' signature of list t; the owner lane decodes the key group of (ks, t) and the group of
+// (1 - ks, 5 - t).  Rounds 4 and 5 fetch the row of the canonical table of list 2, list 3, found with the forward signature:
+// the reverse strand's signature of the same list is its rc-form and lies in the same row, so the round answers (forward, t)
+// and (reverse, t).  In every round the two groups differ in the `which` bit alone and are decoded as "the group without the
+// bit, then the group with it"; which strand (and, pair tables, which list) a group belongs to is the round's in a pair table
+// and the LANE's in a canonical one -- the `which` of its forward signature -- so strand tag and partner key are chosen per
+// lane and group.  When the seed is its own reverse complement the two rounds of a pair table fetch the same row; each round
+// still answers its own two (strand, list).  When a list-2 (list-3) signature is its own rc-form both strands ask for the
+// SAME group: it is taken as first and as second group, filtered once against each strand's partner key.  Every lookup is
+// answered exactly once.  Survivors of both strands share one queue, tagged with their
 // strand (bit 6 beside the six list bits); verification needs the oriented read, so the forward entries are drained, the
 // read is reverse-complemented in registers, then the reverse entries are drained.  Every strand keeps its T::QSLOTS
 // slots: the first T::QSLOTS entries of a lane lie in LDS as before, the rest -- repeat-rich loci on both strands only --
 // in the wave's spill area in global memory (a.qspill).  The forward candidates are verified before the reverse ones, as in
-// the strand loop; within a strand the queue is filled in round order, lists 0, 5, 1, 4, 2, 3, not list by list.  That is
-// sound only because nothing downstream depends on it: parking, flush_pending and the fold rebuild the reference's
-// (strand, list, position) order from the parked list sets alone, and rh_all_finish orders matchAll hits itself.
+// the strand loop; within a strand the queue is filled in round order -- the forward strand's lists 0, 5, 1, 4, the reverse
+// strand's 5, 0, 4, 1, then lists 2 and 3 of both -- not list by list.  That is sound only because nothing downstream depends
+// on it: process_loaded verifies a window once per strand whatever list brings it, parking, flush_pending and the fold rebuild
+// the reference's (strand, list, position) order from the parked list sets alone, and rh_all_finish orders matchAll hits itself.
 template <class T>
 __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<T> &s, const double *sLL, uint8_t *stg, bool act, uint32_t rhi,
                                                   uint32_t rlo) // (the reverse strand's seed halves: seedl <= 32 bits each)
@@ -1154,8 +1162,21 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
         const uint32_t sa_ = ((x.x < 2 ? hi : lo) >> ((x.x & 1) ? 0u : bb)) & mb, sc_ = ((x.y < 2 ? hi : lo) >> ((x.y & 1) ? 0u : bb)) & mb;
         return (sa_ << bb) | sc_;
     };
-    // round li: the row of table li >> 1 by strand li & 1 (lists 0 .. 3 are placed by their own signature)
-    auto row_of = [&](uint32_t li) { return rh_row_addr(li >> 1, sig_of(li & 1u, li >> 1), a.l, gbits).row; };
+    // round li: its table; its row, the two key groups (without / with the `which` bit) and the strand the first of them belongs to
+    auto tbl_of = [](uint32_t li) { return li < 4 ? li >> 1 : li - 2; };
+    struct Round { uint32_t row, g0, g1, s0; };
+    auto round_of = [&](uint32_t li) -> Round {
+        const uint32_t tbl = tbl_of(li), wbit = 1u << (gbits - 1); // (every narrow table has the `which` bit: gbits >= 1)
+        if (li < 4) { // pair table: by strand li & 1 (lists 0, 1 are placed by their own signature, `which` 0)
+            const RhRowAddr ra = rh_row_addr_pair(tbl, sig_of(li & 1u, tbl), a.l, gbits);
+            return {ra.row, ra.group, ra.group | wbit, li & 1u};
+        }
+        // canonical table: a = the forward signature's high half, b = rc(its low half) = the reverse signature's high half
+        const RhCanon c = rh_canon(sig_of(0u, tbl) >> bb, sig_of(1u, tbl) >> bb, bb);
+        const RhRowAddr ra = rh_row_addr_canon(tbl, c, a.l, gbits);
+        const uint32_t lo = c.self ? ra.group : ra.group & ~wbit;
+        return {ra.row, lo, c.self ? lo : lo | wbit, c.which}; // (the forward strand has the group with bit c.which)
+    };
     uint32_t qn = 0, qnf = 0, q_last = 0, q_lastla = 0; // queue fill, forward entries among them; the entry pushed last
     auto q_getp = [&](uint32_t k) { return k < QS ? q_pos[k * 64] : spill(k).x; };
     auto q_getl = [&](uint32_t k) { return k < QS ? (uint32_t)q_la[k * 64] : spill(k).y; };
@@ -1163,11 +1184,11 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
     uint32_t *bkx = reinterpret_cast<uint32_t *>(stg + T::BKX);
 #define ISSUE_ROWS_P(LI)                                                                                                    \
     do {                                                                                                                    \
-        bkx[(lane & 7) * 8 + (lane >> 3)] = act ? row_of(LI) : 0u;                                                          \
+        bkx[(lane & 7) * 8 + (lane >> 3)] = act ? round_of(LI).row : 0u;                                                    \
         __builtin_amdgcn_wave_barrier();                                                                                    \
         const uint4 b0_ = *reinterpret_cast<const uint4 *>(bkx + (lane >> 3) * 8);                                          \
         const uint4 b1_ = *reinterpret_cast<const uint4 *>(bkx + (lane >> 3) * 8 + 4);                                      \
-        const uint4 *__restrict__ R_ = reinterpret_cast<const uint4 *>(a.ix.bkt[(LI) >> 1]) + (lane & 7);                   \
+        const uint4 *__restrict__ R_ = reinterpret_cast<const uint4 *>(a.ix.bkt[tbl_of(LI)]) + (lane & 7);                  \
         va0 = R_[(uint64_t)b0_.x * 8]; va1 = R_[(uint64_t)b0_.y * 8]; va2 = R_[(uint64_t)b0_.z * 8];                        \
         va3 = R_[(uint64_t)b0_.w * 8]; va4 = R_[(uint64_t)b1_.x * 8]; va5 = R_[(uint64_t)b1_.y * 8];                        \
         va6 = R_[(uint64_t)b1_.z * 8]; va7 = R_[(uint64_t)b1_.w * 8];                                                       \
@@ -1182,8 +1203,9 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
         }
     ISSUE_ROWS_P(0u);
 #pragma unroll 1
-    for (uint32_t li = 0; li < 8; ++li) {
-        const uint32_t tbl = li >> 1, ks = li & 1u;
+    for (uint32_t li = 0; li < 6; ++li) {
+        const uint32_t tbl = tbl_of(li);
+        const bool pairt = li < 4;
 #if RH_PHASE_TIMING
         const unsigned ph0 = PH_NOW();
 #endif
@@ -1203,35 +1225,33 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
         const uint8_t *rowb = rowbuf + lane * 128;
         const uint32_t sw = lane & 7;
         auto row = [&](uint32_t d) { return *reinterpret_cast<const uint32_t *>(rowb + ((((d >> 2) ^ sw) << 4) | ((d & 3) << 2))); };
-        // One decode pass per row.  A pair row (tables 0, 1) answers two lookups: (ks, tbl) from key group g0 and (1 - ks, 5 - tbl)
-        // from g1, which differs in the `which` bit alone.  The header is read and judged once, both groups' {first entry, count}
+        // One decode pass per row.  A row answers two lookups: (s0, tbl) from key group g0 and (1 - s0, la1) from g1, which differs
+        // in the `which` bit alone (or, a signature that is its own rc-form, is g0 again); la1 = 5 - tbl in a pair table, tbl
+        // in a canonical one.  The header is read and judged once, both groups' {first entry, count}
         // come from the same two words, their entries are filtered as ONE sequence -- the first group's, then the second's,
         // each against the partner key of its own lookup -- and the survivors are taken in that order.  What the records and
         // the counters depend on stays per (strand, list): the hand-over rules, the counters, the strand's queue limit, the tag.
-        const RhRowAddr ra = rh_row_addr(tbl, sig_of(ks, tbl), a.l, gbits);
-        const bool pairt = tbl < 2;
-        const uint32_t g0 = ra.group, g1 = pairt ? g0 | (1u << (gbits - 1)) : g0; // (a pair table has the `which` bit: gbits >= 1)
+        const Round rd = round_of(li);
+        const uint32_t g0 = rd.g0, g1 = rd.g1, s0 = rd.s0, la1 = pairt ? 5 - tbl : tbl;
         // what an entry's partner key is compared with, per lookup
-        const uint32_t r0 = sig_of(ks, 5 - tbl) >> (a.l - pbits);
-        const uint32_t r1 = pairt ? sig_of(ks ^ 1u, tbl) >> (a.l - pbits) : 0u;
+        const uint32_t r0 = sig_of(s0, 5 - tbl) >> (a.l - pbits);
+        const uint32_t r1 = sig_of(s0 ^ 1u, 5 - la1) >> (a.l - pbits);
         const bool mine = act && !(s.p_n == PEND_OVF) && !(RH_ABLATE & 8);
         const uint32_t h0 = row(0), h1 = row(1);
         const bool cplx = mine && rh_row_complex(h0, h1);
         // simple row: sixteen 4-bit counts.  The entries in front of a group are a dot product of the nibbles with ones below
         // the group (rh_row_group4 in one instruction per word); the second group's sum is the first's, extended by the
-        // nibbles g0 .. g1 - 1.
+        // nibbles g0 .. g1 - 1 (none when g1 == g0: the same entries once more).
         uint32_t c0 = 0, c1 = 0, eb0 = 0, eb1 = 0;
         if (mine && !cplx) {
             const uint64_t hh = ((uint64_t)h1 << 32) | h0, ones = 0x1111111111111111ull;
             const uint64_t below0 = ones & ~(~0ull << (4 * g0));
             eb0 = nibble_dot(h0, (uint32_t)below0, nibble_dot(h1, (uint32_t)(below0 >> 32), 0u));
             c0 = (uint32_t)(hh >> (4 * g0)) & 15u;
-            if (pairt) {
-                const uint64_t ext = (ones & ~(~0ull << (4 * g1))) ^ below0;
-                eb1 = nibble_dot(h0, (uint32_t)ext, nibble_dot(h1, (uint32_t)(ext >> 32), eb0));
-                c1 = (uint32_t)(hh >> (4 * g1)) & 15u;
-            }
-            s.addL(pairt ? 2u : 1u);
+            const uint64_t ext = (ones & ~(~0ull << (4 * g1))) ^ below0;
+            eb1 = nibble_dot(h0, (uint32_t)ext, nibble_dot(h1, (uint32_t)(ext >> 32), eb0));
+            c1 = (uint32_t)(hh >> (4 * g1)) & 15u;
+            s.addL(2u);
             s.addC(c0 + c1);
             s.addP(c0 + c1);
             if (RH_ABLATE & 4) c0 = c1 = 0;
@@ -1261,10 +1281,10 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
         // cost registers): header, first two overflow entries requested, and -- behind the simple rows of the wave -- the walk.
         // A lane is of one kind for the whole round, so the order of its own entries is what it was.  The second pass over the
         // halves is made only by a wave that has such a lane.
-        const uint32_t nhalf = (pairt && __any(cplx)) ? 2u : 1u;
+        const uint32_t nhalf = __any(cplx) ? 2u : 1u;
 #pragma unroll 1
         for (uint32_t half = 0; half < nhalf; ++half) { // (a real loop: the code below exists once)
-            const uint32_t strand = ks ^ half, la = half ? 5 - tbl : tbl;
+            const uint32_t strand = s0 ^ half, la = half ? la1 : tbl;
             const uint32_t g = half ? g1 : g0, r = half ? r1 : r0;
             const bool e_ovf = cplx && !(s.p_n == PEND_OVF); // (handed over in the first half: the second is not looked at)
             uint32_t e_j = 0, e_base = 0;
@@ -1298,10 +1318,10 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
             if (e_ovf && e_cnt) pre = load2(reinterpret_cast<const uint64_t *>(a.ix.ent[tbl] + e_base));
             if (half == 0) {
                 // the next round's rows are in flight while this one is decoded (the registers are free: the rows lie in LDS)
-                if (li + 1 < 8) ISSUE_ROWS_P(li + 1);
+                if (li + 1 < 6) ISSUE_ROWS_P(li + 1);
                 // simple rows: entry j of the concatenation is entry eb0 + j of the row, or eb1 + (j - c0); four keys per step,
                 // bit j of passm = entry j survives the partner filter (a simple row holds at most RH_ROW_CAP = 20 entries)
-                static_assert(RH_ROW_CAP < 32, "one mask word for both groups of a simple row");
+                static_assert(RH_ROW_CAP < 32 && 2 * 15 < 32, "one mask word for both groups of a simple row (one group taken twice: 2 x 15 entries)");
                 const uint32_t ct = c0 + c1, d1 = eb1 - c0;
                 const uint32_t rk0 = r0 >> (pbits - p16), rk1 = r1 >> (pbits - p16); // (the row keeps the leading 16 partner bits)
                 uint32_t passm = 0;
@@ -1331,7 +1351,7 @@ __device__ __forceinline__ void match_rows_paired(const MatchArgs &a, LaneState<
                     const bool sec = jj >= c0;
                     const uint32_t h = step ? rh_row_entry_hw(jj + (sec ? d1 : eb0)) : 4u;
                     const uint32_t d0 = row(h >> 1), d1w = row((h >> 1) + 1);
-                    take(step, (h & 1) ? d1w : ((d0 >> 16) | (d1w << 16)), ks ^ (sec ? 1u : 0u), sec ? 5 - tbl : tbl);
+                    take(step, (h & 1) ? d1w : ((d0 >> 16) | (d1w << 16)), s0 ^ (sec ? 1u : 0u), sec ? la1 : tbl);
                 }
             }
             auto take_ovf = [&](bool ok, uint2 e) { take(ok && passes((e.x & pmask) ^ r), e.y, strand, la); };

@@ -557,7 +557,7 @@ static void fill_args(real_hip_ctx *ctx, const Staged &s, uint64_t n, MatchArgs 
     a.t.has_wild = ctx->n_wild ? 1 : 0; a.t.fileid = ctx->fileid;
     const uint32_t l = ctx->prm.seedl, pb = ctx->pb;
     for (int k = 0; k < 6; ++k) {
-        // (narrow bucket rows: lists 5 and 4 live in the pair tables of lists 0 and 1, rh_row_addr)
+        // (narrow bucket rows: lists 5 and 4 live in the pair tables of lists 0 and 1, lists 2 and 3 in canonical tables of their own, rh_row_addr)
         const int t = (ctx->layout == RH_LAYOUT_ROWS && l <= 32 && k > 3) ? 5 - k : k;
         a.ix.ent[k] = (const uint2 *)ctx->ent[t].p; a.ix.bkt[k] = (const uint32_t *)ctx->bkt[t].p;
     }

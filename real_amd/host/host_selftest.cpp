@@ -5,7 +5,7 @@
 //   host_selftest options <args...>               -> prints the parsed RealOptions
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
-//   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair tables (csrc/row_addr.h), prints ok
+//   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -115,9 +115,9 @@ int main(int argc, char **argv)
             return bad ? 1 : 0;
         }
         if (cmd == "rowaddr" && argc == 3) {
-            // rh_sig_rcform / rh_place_sig / rh_row_addr as the library compiles them: the rc-form against a base-by-base
+            // rh_sig_rcform / rh_canon / rh_row_addr as the library compiles them: the rc-form against a base-by-base
             // reverse complement; (list, signature) -> (table, row, group) a bijection at every group width (all signatures
-            // up to seedl 12); the four paired lookups in the row and group the design says (all seeds up to seedl 12, two
+            // up to seedl 12); the four paired lookups and the two canonical ones in the row and group the design says (all seeds up to seedl 12, two
             // million drawn ones beyond: seedl 32 is the benchmark's geometry, its shifts by 0 and full masks included)
             const uint32_t l = (uint32_t)atoi(argv[2]), q = l / 4; // q bases per segment
             if (l < 4 || l > 32 || l % 4) return 2;
@@ -140,12 +140,23 @@ int main(int argc, char **argv)
                     for (uint32_t la = 0; la < 6; ++la)
                         for (uint64_t sg = 0; sg < nsig; ++sg) {
                             const RhRowAddr a = rh_row_addr(la, (uint32_t)sg, l, gbits);
-                            if (a.table > 3 || a.table != (la > 3 ? 5 - la : la) || a.row >= rh_table_rows(la, l, pb) || a.group >= (1u << gbits)) { bad++; continue; }
+                            if (a.table > 3 || a.table != (la > 3 ? 5 - la : la) || a.row >= rh_table_rows(la, pb) || a.group >= (1u << gbits)) { bad++; continue; }
                             uint8_t &s = seen[off[a.table] + (((uint64_t)a.row << gbits) | a.group)];
                             if (s) bad++;
                             s = 1;
                         }
                     for (uint8_t s : seen) if (!s) bad++;
+                    // canonical tables: a signature and its rc-form in one row, their groups apart in the `which` bit alone; a
+                    // signature that is its own rc-form has the one group; the sort key of the build is row, then group
+                    for (uint32_t la = 2; la < 4; ++la)
+                        for (uint64_t sg = 0; sg < nsig; ++sg) {
+                            const uint32_t rf = rh_sig_rcform((uint32_t)sg, l), half = 1u << (gbits - 1);
+                            const RhRowAddr a = rh_row_addr(la, (uint32_t)sg, l, gbits), b = rh_row_addr(la, rf, l, gbits);
+                            const RhCanon c = rh_sig_canon((uint32_t)sg, l), cr = rh_sig_canon(rf, l);
+                            if (a.table != la || b.table != la || a.row != b.row || (a.group ^ b.group) != (rf == sg ? 0u : half)) bad++;
+                            if (c.index != cr.index || c.self != (rf == sg) || c.index >> (l - 1) || (rf != sg && c.which == cr.which)) bad++;
+                            if (rh_place_key(la, (uint32_t)sg, l, gbits) != ((a.row << gbits) | a.group)) bad++;
+                        }
                 }
                 const uint64_t nseed = all ? 1ull << (2 * l) : 2000000;
                 const uint64_t gm = (1ull << (2 * q)) - 1;
@@ -163,6 +174,16 @@ int main(int argc, char **argv)
                             const uint32_t half = 1u << (gbits - 1);
                             if (a.table != b.table || a.row != b.row || (a.group & half) || b.group != (a.group | half)) bad++;
                         }
+                    for (int k = 2; k < 4; ++k) { // both strands' list k: one row of its canonical table, the groups apart in `which` alone
+                        const uint32_t sf = sig(m, k), sr = sig(r, k), half = 1u << (gbits - 1), h2 = l / 2;
+                        const RhRowAddr a = rh_row_addr(k, sf, l, gbits), b = rh_row_addr(k, sr, l, gbits);
+                        if (sr != rh_sig_rcform(sf, l) || a.table != (uint32_t)k || b.table != (uint32_t)k || a.row != b.row || a.row >= rh_table_rows(k, pb) ||
+                            (a.group ^ b.group) != (sf == sr ? 0u : half)) bad++;
+                        // (the matcher has rc(low half) as the other strand's high half: no bit reversal)
+                        const RhCanon c = rh_canon(sf >> h2, sr >> h2, h2), d = rh_sig_canon(sf, l);
+                        if (c.index != d.index || c.which != d.which || c.self != d.self || c.self != (sf == sr)) bad++;
+                        if (rh_place_key(k, sf, l, gbits) != ((a.row << gbits) | a.group)) bad++;
+                    }
                 }
             }
             std::cout << (bad ? "bad " : "ok ") << bad << std::endl;
