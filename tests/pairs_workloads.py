@@ -11,10 +11,19 @@ RESCUE_SPAN, RESCUE_GAP, SEG_LEN = 160, 200, 760
 MIN_INS, MAX_INS = 150, 420
 
 
-def pair_workload(kind: str, ragged: bool, patl=(100, 80), n: int = 1500, errprob: float = 0.01, seed: int = 11, size: int = 400_000):
+def pair_workload(kind: str, ragged: bool, patl=(100, 80), n: int = 1500, errprob: float = 0.01, seed: int = 11, size: int = 400_000, *,
+                  min_ins: int = MIN_INS, max_ins: int = MAX_INS, insert_mean: float = 300, insert_sd: float = 30, ragged_patl=(60, 120),
+                  rescue_span: int = RESCUE_SPAN, rescue_gap: int = RESCUE_GAP, random_qual: bool = False):
     """(genome, mate batch 1, mate batch 2): an i.i.d. genome with perturbed repeats or repeat_family_genome (3/6/30/60
-    copies), both with loci where pairing rescues a fragment; a few reads carry an N (skipped by the matcher)."""
+    copies), both with loci where pairing rescues a fragment; a few reads carry an N (skipped by the matcher).
+
+    The insert bounds, the insert mean / sd, the length pair(s) of the ragged part and the geometry of the rescue loci
+    (a mate must fit into rescue_span) are arguments; the defaults give the inputs every earlier caller has always had
+    (test_workload_defaults_cpu.py holds their hashes).  random_qual: per-base qualities uniform in 0..63 instead of
+    35 / 9, for every read (nothing here is planted on a read, so no read needs a fixed quality)."""
     from real_amd import synth
+    from mate_search_workloads import ragged_parts, random_qualities
+    RESCUE_SPAN, RESCUE_GAP = rescue_span, rescue_gap
     if kind == "families":
         g, copies = synth.repeat_family_genome(size, seed, seg_len=SEG_LEN)
         avoid = [(p, p + SEG_LEN) for fam in copies for p in fam]
@@ -29,17 +38,19 @@ def pair_workload(kind: str, ragged: bool, patl=(100, 80), n: int = 1500, errpro
             copies.append(tuple(at))
         avoid = [(p, p + SEG_LEN) for fam in copies for p in fam]
     loci = synth.plant_pair_repeats(g, 8, RESCUE_SPAN, RESCUE_GAP, seed + 2, avoid=avoid)
-    kw = dict(insert_min=MIN_INS, insert_max=MAX_INS, copies=copies, seg_len=SEG_LEN, rescue_loci=loci, rescue_span=RESCUE_SPAN,
+    kw = dict(insert_min=min_ins, insert_max=max_ins, copies=copies, seg_len=SEG_LEN, rescue_loci=loci, rescue_span=RESCUE_SPAN,
               rescue_gap=RESCUE_GAP, rescue_frac=0.08)
-    p1 = synth.sample_pairs(g, n, patl[0], patl[1], 300, 30, errprob, seed + 3, **kw)
+    p1 = synth.sample_pairs(g, n, patl[0], patl[1], insert_mean, insert_sd, errprob, seed + 3, **dict(kw, insert_min=max(min_ins, *patl)))
     if ragged:
-        p2 = synth.sample_pairs(g, n // 2, 60, 120, 300, 30, errprob, seed + 4, **kw)
+        p2 = ragged_parts(synth, g, n // 2, ragged_patl, insert_mean, insert_sd, errprob, seed + 4, kw)
         b1, b2 = synth.ragged_pairs(p1, p2)
     else:
         b1, b2 = p1
     for b, every in ((b1, 97), (b2, 131)):                         # reads the matcher skips: a symbol > 3
         for i in range(5, b.n_reads, every):
             b.bases[int(b.offsets[i]) + 7] = 4
+    if random_qual:
+        random_qualities((b1, b2), (), seed + 6)
     return g, b1, b2
 
 

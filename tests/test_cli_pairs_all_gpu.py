@@ -148,3 +148,26 @@ def test_real_cli_pairs_all_loud_errors(tmp_path):
                        (["-p", p1, "-p2", p2, "-pairs_all", "1", "-block", "20000"], b"more than one index block")):
         r = _run(base + args)
         assert r.returncode != 0 and word in r.stderr, (args[1:], r.stderr.decode()[-500:])
+
+
+def test_real_cli_pairs_all_150bp_seed_64(ora, tmp_path):
+    """2 x 150 bases, 64-base seeds, five mismatches, inserts 200..700, random qualities"""
+    import mate_search_workloads as mw
+    row = mw.PROTOCOL_ROWS[0]
+    assert (row.patl, row.seedl, row.tk, row.min_ins, row.max_ins) == ((150, 150), 64, 5, 200, 700)
+    g, b1, b2 = mw.protocol_pair_workload(row, "families")
+    fa = str(tmp_path / "genome.fa")
+    synth.genome_to_fasta(g, fa)
+    p1, p2 = _write(tmp_path, b1, b2)
+    out = str(tmp_path / "out.tsv")
+    r = _run([REAL, "-l", "64", "-e", "5", "-t", fa, "-p", p1, "-p2", p2, "-o", out, "-insert_min", "200", "-insert_max", "700", "-s", "2", "-q", "1",
+              "-Q", "33", "-pairs_all", "1"])
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    (_, h1, o1, h2, o2), _ = pw.oracle_pairs(ora, g, b1, b2, 64, 5, 1, 2)
+    recs, off = pac.enumerate_pairs(h1, o1, pw.lens_of(b1), h2, o2, pw.lens_of(b2), 200, 700, 0)
+    want = expected_all_lines(recs, g, b1, b2, 1)
+    got = open(out).read().split("\n")[:-1]
+    per = (off[1:] - off[:-1]).astype(np.int64)
+    assert len(want) > 1200 and (per >= 2).sum() >= 20 and len(got) == len(want)
+    assert got == want
+    assert ("concordant pairs: %d" % recs.shape[0]) in r.stderr.decode()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import mate_search_checker as mc
+import mate_search_hand as mh
 import mate_search_workloads as mw
 import pairs_checker as pc
 from real_amd import lib as rlib
@@ -165,95 +166,16 @@ def test_two_genome_files_fold_in_both_orders(ora, scores):
 
 
 # ---- hand-made anchors through real_hip_pair_search ---------------------------------------------------------------------
-MIN_H, MAX_H, L1, L2 = 150, 420, 100, 80
-
-
-def _hand_genome():
-    g = synth.random_genome(20_000, seed=77, n_frag=1)
-    g.sym[g.sym > 3] = 0
-    g.frag_start = np.array([0, 10_000, 20_000], dtype=np.uint64)
-    g.frag_names = [" hand_0", " hand_1"]
-    g.sym[3200] = 4                                                  # one N
-    return g
-
-
-def _hand_fragments(g, S, tk):
-    """[(what, read 1, read 2, anchors of mate 1, anchors of mate 2, expected state of the search alone)]; the anchors are
-    the mates' true placements, scored by the checker"""
-    rng = np.random.default_rng(5)
-    F = []
-
-    def text(p, ln):
-        t = g.sym[p:p + ln].copy()
-        t[t > 3] = 0
-        return t
-
-    def subs(rd, k, lo=0):
-        rd = rd.copy()
-        rd[lo + rng.choice(len(rd) - lo, size=k, replace=False)] ^= 2
-        return rd
-
-    def anchor(rd, inv, p):
-        k, sc, frag = S.placement(rd, np.full(len(rd), 30, np.uint8), inv, p)
-        return (p, frag, inv, k, float(sc))
-
-    def add(what, p1, p2, fwd1, anchors, state, k1=0, k2=0):
-        """mate 1 at p1 and mate 2 at p2 (true text positions), mate 1 forward or reverse; anchors: which mates are anchors"""
-        r1, r2 = subs(text(p1, L1), k1), subs(text(p2, L2), k2)
-        r1, r2 = (r1, mc.COMP[r2[::-1]]) if fwd1 else (mc.COMP[r1[::-1]], r2)
-        a1 = [anchor(r1, int(not fwd1), p1)] if 0 in anchors else []
-        a2 = [anchor(r2, int(fwd1), p2)] if 1 in anchors else []
-        F.append((what, r1, r2, a1, a2, state))
-
-    U, NO = pc.UNIQUE, pc.NOMATCH
-    # mate 1 forward at 1000 is the anchor; outer distance = p2 + L2 - 1000
-    add("outer distance at the upper bound", 1000, 1000 + MAX_H - L2, True, (0,), U)
-    add("one beyond the upper bound", 1000, 1001 + MAX_H - L2, True, (0,), NO)
-    add("outer distance at the lower bound", 1000, 1000 + MIN_H - L2, True, (0,), U)
-    add("one below the lower bound", 1000, 999 + MIN_H - L2, True, (0,), NO)
-    add("the placement touches the fragment's last base", 9700, 10_000 - L2, True, (0,), U)
-    add("an N inside the placement", 3000, 3150, True, (0,), NO)
-    add("k == totalkmax", 5000, 5200, True, (0,), U, k2=tk)
-    add("k == totalkmax + 1", 5000, 5200, True, (0,), NO, k2=tk + 1)
-    # the anchor on either strand and of either mate
-    add("anchor: mate 2, reverse", 6000, 6200, True, (1,), U, k1=2)
-    add("anchor: mate 1, reverse", 7220, 7000, False, (0,), U, k2=1)
-    add("anchor: mate 2, forward", 7220, 7000, False, (1,), U, k1=3)
-    add("both mates anchor: one location", 8000, 8250, True, (0, 1), U)
-    add("reverse anchor, outer distance at the upper bound", 12_000 + MAX_H - L1, 12_000, False, (0,), U)
-    add("reverse anchor, one beyond", 12_001 + MAX_H - L1, 12_000, False, (0,), NO)
-    add("reverse anchor at the fragment's first base", 10_200, 10_000, False, (0,), U)
-    add("no anchors", 15_000, 15_200, True, (), NO)
-    # one past the fragment's last base: mate 2 would straddle the cut at 10000 (its read is the text across it)
-    r1, r2 = text(9700, L1), mc.COMP[text(10_001 - L2, L2)[::-1]]
-    F.append(("one past the fragment's last base", r1, r2, [anchor(r1, 0, 9700)], [], NO))
-    return F
-
-
-def _hand_batches(F):
-    def batch(k):
-        rd = [f[k] for f in F]
-        off = np.cumsum([0] + [len(r) for r in rd]).astype(np.uint64)
-        bases = np.concatenate(rd).astype(np.uint8)
-        return synth.ReadBatch(bases=bases, qual=np.full(bases.shape[0], 30, np.uint8), offsets=off, ids=None)
-    hit = np.dtype([("pos", "<u4"), ("frag", "<u4"), ("inverted", "u1"), ("k", "u1"), ("score", "<f4")])
-
-    def lists(k):
-        rows = [a for f in F for a in f[k]]
-        h = np.zeros(len(rows), dtype=hit)
-        for j, (p, frag, inv, kk, sc) in enumerate(rows):
-            h[j] = (p, frag, inv, kk, sc)
-        return h, np.cumsum([0] + [len(f[k]) for f in F]).astype(np.uint64)
-    return batch(1), batch(2), lists(3), lists(4)
+MIN_H, MAX_H, L1, L2 = mh.MIN_H, mh.MAX_H, mh.L1, mh.L2
 
 
 @pytest.mark.parametrize("scores", [1, 0])
 def test_pair_search_on_hand_made_anchors(ora, scores):
     tk, seedl, fl = 3, 32, 2
-    g = _hand_genome()
+    g = mh.classic_genome()
     S = mc.Searcher(ora, g, seedl, tk, scores, MIN_H, MAX_H)
-    F = _hand_fragments(g, S, tk)
-    b1, b2, (h1, o1), (h2, o2) = _hand_batches(F)
+    F = mh.classic_cases(g, S, tk)
+    b1, b2, (h1, o1), (h2, o2) = mh.batches(F)
     fm = ora.filter_mult(fl, tk)
     want, ctr = mc.search_only(ora, {0: g}, [(0, h1, o1, h2, o2)], b1, b2, MIN_H, MAX_H, scores, fm, seedl, tk)
     assert [int(s) for s in want["state"]] == [f[5] for f in F], [(f[0], int(s)) for f, s in zip(F, want["state"]) if int(s) != f[5]]

@@ -55,6 +55,46 @@ def test_workloads_hold_every_state_change(ora, kind, ragged, patl, seedl, total
     assert same.sum() > 100, "most fragments the seeds place stay as they are"
 
 
+@pytest.mark.parametrize("scores", [1, 0])
+@pytest.mark.parametrize("kind", ["iid", "families"])
+@pytest.mark.parametrize("row", mw.PROTOCOL_ROWS, ids=[r.name for r in mw.PROTOCOL_ROWS])
+def test_protocol_workloads_hold_every_state_change(ora, row, kind, scores):
+    """the coverage conditions of test_gpu_pairs_protocols.py at every protocol shape, met by the checker alone"""
+    g, b1, b2, planted = mw.protocol_search_workload(row, kind)
+    f = mw.oracle_lists(ora, g, b1, b2, row.seedl, row.tk, scores, 2)
+    args = (b1, b2, row.min_ins, row.max_ins, scores, ora.filter_mult(2, row.tk), row.seedl, row.tk)
+    off, _ = mc.check_pairs_search(ora, {0: g}, [f], *args, search=False)
+    on, _ = mc.check_pairs_search(ora, {0: g}, [f], *args)
+    tr = mw.assert_coverage(off, on, f, "%s %s" % (row.name, kind))
+    for cat, key in zip("ABCD", ("nomatch_unique", "nomatch_nonunique", "unique_nonunique", "unique_better")):
+        assert set(planted[cat]) <= set(tr[key].tolist()), (cat, planted[cat], tr[key])
+    lens = np.concatenate([mw.lens_of(b1), mw.lens_of(b2)])
+    assert 550 <= b1.n_reads <= 650 and 300_000 <= g.n <= 400_000 and lens.max() == max(max(row.patl), max(max(p) for p in row.ragged_patl or [(0, 0)]))
+    if kind == "families":
+        n = b1.n_reads
+        assert max(int(f[2][-1]), int(f[4][-1])) > n + n // 4 + 1024
+    if row.ragged_patl:
+        for b in (b1, b2):
+            assert {(int(v) + 31) // 32 for v in mw.lens_of(b)} >= set(range(2, 11)), "every width in one batch"
+        assert lens.min() == 36
+
+
+def test_checker_against_the_whole_genome_formulation_at_150_bases(ora):
+    """2 x 150 bases, 64-base seeds, five mismatches, inserts 200..700, random qualities: the checker against the second,
+    differently written formulation on a small genome"""
+    seedl, tk, scores, fl, mn, mx = 64, 5, 1, 2, 200, 700
+    g, b1, b2, _ = mw.search_workload("iid", False, (150, 150), seedl, tk, n=40, size=200_000, min_ins=mn, max_ins=mx, frag_l=400, insert_mean=400,
+                                      insert_sd=50, random_qual=True)
+    f = mw.oracle_lists(ora, g, b1, b2, seedl, tk, scores, fl)
+    fm = ora.filter_mult(fl, tk)
+    args = (b1, b2, mn, mx, scores, fm, seedl, tk)
+    on, ctr = mc.check_pairs_search(ora, {0: g}, [f], *args)
+    pc.assert_records_equal(on, mc.whole_genome_pairs(ora, g, 0, f, *args), "checker vs whole genome")
+    off, _ = mc.check_pairs_search(ora, {0: g}, [f], *args, search=False)
+    mw.assert_coverage(off, on, f, "small genome, 150 bases")
+    assert ctr["anchors"] > 0 and ctr["positions"] > ctr["anchors"] and ctr["placements"] > 0
+
+
 def test_window_of_is_the_concordance_test():
     """every position: inside the window <=> concordant with the anchor and inside its fragment"""
     fs, fe = 1000, 3000
