@@ -13,6 +13,11 @@ the states with the search off and on); the leg with reads at 4 % substitutions:
 A build with real_hip_match_pairs_all adds the legs of the enumeration of every concordant pair (outputs in pinned host
 memory and left on the device, pairs per fragment, handed-over share, the kernels' own time); its comparison figure is
 baseline_ms, what a caller has to do without it to see the same pairs.  --skip-search leaves the mate-search legs out.
+--singles adds the legs of real_hip_match_pairs_singles (the pairs plus each mate's own placement record): the call with
+pinned host outputs and with outputs left on the device, the fold's kernel time beside the join's of the same run, the
+reads handed to the wave kernel, bytes downloaded, and the split of the extra time over match_pairs_ms into kernels and
+download; --skip-baseline / --skip-pairs-all leave the other legs out.  The parent's match_pairs_ms for the comparison:
+the same command with --tree on a parent checkout, in the same session, alternating.
 """
 import argparse
 import ctypes as C
@@ -66,6 +71,9 @@ def main():
     ap.add_argument("--errprob", type=float, default=0.02)   # substitutions per base of the reads
     ap.add_argument("--ks", default="2,3")                   # the -e values (totalkmax) measured
     ap.add_argument("--skip-search", action="store_true")    # leave the mate-search legs out
+    ap.add_argument("--skip-baseline", action="store_true")  # leave the two-match_all baseline out
+    ap.add_argument("--skip-pairs-all", action="store_true") # leave the legs of the enumeration out
+    ap.add_argument("--singles", action="store_true")        # add the legs of real_hip_match_pairs_singles
     args = ap.parse_args()
     sys.path.insert(0, args.tree)
     import numpy as np
@@ -109,7 +117,7 @@ def main():
             # -- baseline: two real_hip_match_all calls with host outputs (pinned buffers, sized by a first call)
             hits, hoff, need = None, m.host_alloc(n + 1, np.uint64), [0, 0]
             cap = int(n * 1.5)
-            for attempt in range(2):
+            for attempt in range(0 if args.skip_baseline else 2):
                 hits = m.host_alloc(cap, rlib.HIT_DTYPE)
                 ok = True
                 for j, (b, q) in enumerate(((b1, q1), (b2, q2))):
@@ -124,15 +132,17 @@ def main():
                     break
                 cap = max(need) + 16
             ts = []
-            for _ in range(args.steps):
+            for _ in range(0 if args.skip_baseline else args.steps):
                 t0 = time.perf_counter()
                 for b, q in ((b1, q1), (b2, q2)):
                     rb, nout = batch(b, q), C.c_uint64(0)
                     m._check(L.real_hip_match_all(m._h, C.byref(rb), hits.ctypes.data, cap, C.byref(nout), hoff.ctypes.data))
                 ts.append((time.perf_counter() - t0) * 1e3)
-            r["baseline_ms"], r["baseline_ms_all_steps"] = min(ts), ts
-            r["hits_per_mate"] = [need[0] / n, need[1] / n]
-            r["baseline_hit_bytes_downloaded"] = (need[0] + need[1]) * 16
+            if not args.skip_baseline:
+                r["baseline_ms"], r["baseline_ms_all_steps"] = min(ts), ts
+                r["hits_per_mate"] = [need[0] / n, need[1] / n]
+                r["baseline_hit_bytes_downloaded"] = (need[0] + need[1]) * 16
+            del hits
             if have_pairs:
                 pp = m._pair_params(lo_ins, hi_ins)
                 rec = m.host_alloc(n, rlib.PAIR_DTYPE)
@@ -185,7 +195,45 @@ def main():
                     r["search_per_fragment"] = {k: ms[k] / max(ms["fragments"], 1) for k in ("anchors", "positions", "placements")}
                     state = np.bincount(rec["state"], minlength=3)
                     r["states_search_on"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
-                if hasattr(m, "match_pairs_all"):           # every concordant pair instead of one record per fragment
+                if args.singles and hasattr(m, "match_pairs_singles"):   # the pairs plus each mate's own placement record
+                    sg_host = [m.host_alloc(n, rlib.SINGLE_DTYPE) for _ in range(2)]
+                    sg_dev = [torch.empty(n * 16, dtype=torch.uint8, device=dev) for _ in range(2)]
+
+                    def run_singles(on_device, out_ptr, s1_ptr, s2_ptr):
+                        rb1, rb2 = batch(b1, q1), batch(b2, q2)
+                        rb1.on_device = rb2.on_device = on_device
+                        rb1.fresh = rb2.fresh = 1
+                        t0 = time.perf_counter()
+                        m._check(L.real_hip_match_pairs_singles(m._h, C.byref(rb1), C.byref(rb2), C.byref(pp), None, out_ptr, s1_ptr, s2_ptr))
+                        return (time.perf_counter() - t0) * 1e3
+                    plain = rec.copy()
+                    run_singles(2, rec.ctypes.data, sg_host[0].ctypes.data, sg_host[1].ctypes.data)
+                    r["singles_pairs_equal_match_pairs"] = bool(rec.tobytes() == plain.tobytes())
+                    for k in (rlib.K_PAIR, rlib.K_PAIR_WAVE):
+                        m.kernel_time(k, reset=True)
+                    m.single_stats(reset=True)
+                    ts = [run_singles(2, rec.ctypes.data, sg_host[0].ctypes.data, sg_host[1].ctypes.data) for _ in range(args.steps)]
+                    sg = m.single_stats()
+                    r["match_pairs_singles_ms"], r["match_pairs_singles_ms_all_steps"] = min(ts), ts
+                    r["singles_fold_kernel_ms_per_call"] = sg["kernel_ms"] / S
+                    r["singles_join_kernels_ms_per_call_same_run"] = (m.kernel_time(rlib.K_PAIR)[0] + m.kernel_time(rlib.K_PAIR_WAVE)[0]) / S
+                    r["singles_handed_over_per_call"] = sg["handed_over"] / S
+                    r["singles_hits_per_read"] = sg["hits"] / max(sg["reads"], 1)
+                    td = [run_singles(1, rec_dev.data_ptr(), sg_dev[0].data_ptr(), sg_dev[1].data_ptr()) for _ in range(args.steps)]
+                    r["match_pairs_singles_device_outputs_ms"], r["match_pairs_singles_device_outputs_ms_all_steps"] = min(td), td
+                    r["singles_bytes_downloaded"] = n * (40 + 32)
+                    extra = min(ts) - r["match_pairs_ms"]
+                    on_dev = min(td) - r["match_pairs_device_records_ms"]
+                    r["singles_extra_ms"] = {"over_match_pairs_ms": extra, "of_it_with_outputs_on_the_device": on_dev,
+                                             "of_it_download_of_32_bytes_per_fragment_by_difference": extra - on_dev}
+                    nm = rec["state"] == 0
+                    t1, t2 = (sg_host[0]["tag"] >> 5) & 3, (sg_host[1]["tag"] >> 5) & 3
+                    r["singles_of_nomatch_fragments"] = {"fragments": int(nm.sum()), "both_unique": int((nm & (t1 == 1) & (t2 == 1)).sum()),
+                                                         "one_unique": int((nm & ((t1 == 1) != (t2 == 1))).sum()),
+                                                         "a_nonunique_mate": int((nm & ((t1 == 2) | (t2 == 2))).sum()),
+                                                         "neither_placed": int((nm & (t1 == 0) & (t2 == 0)).sum())}
+                    del sg_dev
+                if hasattr(m, "match_pairs_all") and not args.skip_pairs_all:           # every concordant pair instead of one record per fragment
                     poff = m.host_alloc(n + 1, np.uint64)
                     poff_dev = torch.empty(n + 1, dtype=torch.int64, device=dev)
                     pcap, need_p = int(n * 1.25), C.c_uint64(0)

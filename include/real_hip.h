@@ -380,6 +380,60 @@ typedef struct real_hip_pair_all_stats {
 } real_hip_pair_all_stats;
 int real_hip_pair_all_stats_get(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
 
+/* ---- single placements of a mate: where each mate of a fragment lies on its own, for the fragments without a concordant
+ * pair (one mate placed and the other not, or both placed but not concordantly).  The semantics are this project's own, in
+ * the words of the paired-end block above, and are independent of the order of hits, lanes, waves, index blocks and genome
+ * files.  Candidates of a read are its real_hip_match_all hits in one genome file.  VALUE of a hit: (double)score with
+ * scores on, -(double)k with scores off (k = 0 gives -0.0).  LOCATION: (fileid, frag, pos, inverted).  The record keeps
+ * `best` (highest value; equal values: the smallest location in lexicographic order) and `second` (highest value at any
+ * OTHER location, -inf if none; of +0.0 and -0.0 the latter); merging two records is taking the top two of their union,
+ * a location counts once, so genome files and index blocks fold in any order.  state: NoMatch without a hit, NonUnique if
+ * second >= best - eps (in FP64), else Unique, with eps = (double)(float)(filter_mult * len) with scores on and 0 with
+ * scores off; the values are REAL_HIP_PAIR_NOMATCH / _UNIQUE / _NONUNIQUE.
+ * This is deliberately NOT the record of real_hip_match_unique: that one reproduces the reference's fold over update()
+ * calls, whose outcome depends on the order of the calls (matchUniqueImplementation.cpp:97-160); this one is a function of
+ * the set of hits alone, as the pair record is.                                                                       */
+typedef struct real_hip_single {    /* 16 bytes, 16-byte aligned on the device (one vector store); in/out across genome files */
+    float    score;                 /* the best hit's score (1.0f if !scores)                                              */
+    float    second;                /* (float) of the second value (exact: the values are floats or small integers); -inf: none;
+                                       -(float)k with scores off (-0.0f for k = 0)                                       */
+    uint32_t pos;                   /* 0-based position in the text of fileid                                              */
+    uint16_t frag;
+    uint8_t  fileid;
+    uint8_t  tag;                   /* k in bits 0-3 (k <= 15, as everywhere in this ABI), inverted in bit 4, state in bits 5-6 */
+} real_hip_single;
+#define REAL_HIP_SINGLE_K(tag)        ((tag) & 15u)
+#define REAL_HIP_SINGLE_INVERTED(tag) (((tag) >> 4) & 1u)
+#define REAL_HIP_SINGLE_STATE(tag)    (((tag) >> 5) & 3u)
+/* A record is empty iff its state is NoMatch: on input its other fields are ignored, on output they are score 0, second
+ * -inf, everything else 0.
+ * The fold alone, on one mate's lists as the caller holds them: hits[off[i] .. off[i+1]) are the candidates of read i (any
+ * order, e.g. the per-block lists of a genome file that needs several index blocks), len[i] its length in bases (uint32).
+ * Staging and checks are those of real_hip_pair_hits: on_device 0 all pointers host memory (copied), 1 all device pointers
+ * (singles 16-byte aligned); the offsets start at 0 and do not run backwards; fileid <= 255; fresh != 0: singles[] is
+ * output only, 0: in/out.  A hit may appear twice (a location counts once).  Uses the ctx's -q and -filter_level; needs
+ * neither text nor index.                                                                                             */
+int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits, const uint64_t *off, const uint32_t *len,
+                         uint64_t n_reads, uint32_t fileid, int on_device, int fresh, real_hip_single *singles);
+/* real_hip_match_pairs (sp == NULL) or real_hip_match_pairs_search (sp != NULL), and in the same call each mate's
+ * device-resident hit list folded into singles1[] / singles2[]: no hit crosses to the host.  batch1->fresh governs all three
+ * arrays, on_device where all three live (0 / 2 host memory, 1 device pointers).  pairs[] is bit for bit what the existing
+ * calls give.  The singles are folds of SEED hits only: a placement that only the mate search finds is not a candidate
+ * of its mate's record.                                                                                               */
+int real_hip_match_pairs_singles(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                 const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs,
+                                 real_hip_single *singles1, real_hip_single *singles2);
+/* work of the fold, accumulated since the last reset; kernel_ms: HIP events on the ctx's stream around the kernels     */
+typedef struct real_hip_single_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_single_stats), 0                                       */
+    uint64_t reads;         /* reads folded                                                                    */
+    uint64_t hits;          /* hits walked                                                                     */
+    uint64_t handed_over;   /* reads whose list exceeded a lane's budget: folded by a wave each                */
+    uint64_t launches;      /* kernels launched                                                                */
+    double   kernel_ms;
+} real_hip_single_stats;
+int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -97,6 +97,7 @@ void rh_time_resolve(real_hip_ctx *c)
             if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
                 if (p.which == RH_K_MATE_SEARCH) c->ms_kernel_ms += ms;
                 else if (p.which == RH_K_PAIR_ALL) c->pa_kernel_ms += ms;
+                else if (p.which == RH_K_SINGLE) c->sg_kernel_ms += ms;
                 else { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
             }
             c->ev_pool.push_back(p.a);
@@ -222,7 +223,8 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     for (DevBuf *b : all) rh_release(*b);
     for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
     DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats,
-                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats, &c->pa_cnt, &c->pa_off, &c->pa_out, &c->pa_stats};
+                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats, &c->pa_cnt, &c->pa_off, &c->pa_out, &c->pa_stats,
+                    &c->sg_rec[0], &c->sg_rec[1], &c->sg_list, &c->sg_stats};
     for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
@@ -790,12 +792,13 @@ static int pair_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp)
     return REAL_HIP_OK;
 }
 
-// the two mates' hit lists of n fragments as the caller holds them -> device views: the offsets start at 0 and do not run
-// backwards, off[n] is the number of hits; host lists are copied into the ctx's pair buffers
-static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *d_h[2], const uint64_t *d_o[2], uint64_t total[2], uint64_t n, bool on_device)
+// the two mates' hit lists of n fragments (lists = 1: one read's lists alone) as the caller holds them -> device views: the
+// offsets start at 0 and do not run backwards, off[n] is the number of hits; host lists are copied into the ctx's pair buffers
+static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *d_h[2], const uint64_t *d_o[2], uint64_t total[2], uint64_t n, bool on_device,
+                           int lists = 2)
 {
     int rc;
-    for (int m = 0; m < 2; ++m) {
+    for (int m = 0; m < lists; ++m) {
         if (on_device) {
             uint64_t ends[1] = {0}, first = 0;
             RH_HIP(ctx, hipMemcpyAsync(&first, d_o[m], 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -813,7 +816,7 @@ static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *d_h[2], const 
         if (total[m] && !d_h[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
     }
     if (on_device) return REAL_HIP_OK;
-    for (int m = 0; m < 2; ++m) {
+    for (int m = 0; m < lists; ++m) {
         if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total[m] ? total[m] : 1) * sizeof(real_hip_hit)))) return rc;
         if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
         if (total[m]) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, d_h[m], total[m] * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
@@ -949,6 +952,71 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
     return rh_mate_search_finish(ctx);
 }
 
+// ---- single placements of a mate (single_fold.hip): the in/out records of `lists` lists, staged when they are host memory
+static int stage_singles(real_hip_ctx *ctx, int lists, real_hip_single *const singles[2], uint64_t n, bool host_out, int fresh,
+                         real_hip_single *d_singles[2])
+{
+    int rc;
+    for (int m = 0; m < lists; ++m) {
+        d_singles[m] = singles[m];
+        if (!host_out) {
+            if ((uintptr_t)singles[m] & 15u) return rh_fail(ctx, REAL_HIP_E_INVALID, "the single records must be 16-byte aligned", hipSuccess);
+            continue;
+        }
+        if ((rc = rh_reserve(ctx, ctx->sg_rec[m], n * sizeof(real_hip_single)))) return rc;
+        d_singles[m] = (real_hip_single *)ctx->sg_rec[m].p;
+        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_singles[m], singles[m], n * sizeof(real_hip_single), hipMemcpyHostToDevice, ctx->stream));
+    }
+    return REAL_HIP_OK;
+}
+static int download_singles(real_hip_ctx *ctx, int lists, real_hip_single *const singles[2], uint64_t n, real_hip_single *const d_singles[2])
+{
+    for (int m = 0; m < lists; ++m) {
+        hipError_t e = hipMemcpyAsync(singles[m], d_singles[m], n * sizeof(real_hip_single), hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the single records", e);
+    }
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
+                                    uint32_t fileid, int on_device, int fresh, real_hip_single *singles)
+{
+    RH_ENTER(ctx);
+    int rc;
+    if (fileid > 255) return rh_fail(ctx, REAL_HIP_E_INVALID, "fileid > 255", hipSuccess);
+    const uint64_t n = n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
+    if (!off || !len || !singles) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths / singles", hipSuccess);
+    const real_hip_hit *d_h[2] = {hits, nullptr};
+    const uint64_t *d_o[2] = {off, nullptr};
+    const uint32_t *d_l[2] = {len, nullptr};
+    uint64_t total[2] = {0, 0};
+    real_hip_single *const sv[2] = {singles, nullptr};
+    real_hip_single *d_singles[2] = {nullptr, nullptr};
+    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0, 1))) return rc;
+    if (!on_device) {
+        if ((rc = rh_reserve(ctx, ctx->pair_len[0], n * 4))) return rc;
+        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[0].p, len, n * 4, hipMemcpyHostToDevice, ctx->stream));
+        d_l[0] = (const uint32_t *)ctx->pair_len[0].p;
+    }
+    rc = stage_singles(ctx, 1, sv, n, !on_device, fresh, d_singles);
+    if (!rc) rc = rh_launch_single(ctx, 1, d_h, d_o, d_l, total, n, fileid, fresh, d_singles);
+    if (!rc && !on_device) rc = download_singles(ctx, 1, sv, n, d_singles);
+    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_single_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "single stats struct_size", hipSuccess);
+    return rh_single_stats(ctx, out, reset);
+}
+
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
 // hold mate m's unified hit lists, their n + 1 offsets and the read lengths; total[m] is an upper bound of the hits inside
 // the buffer (the matcher's count before duplicates go).  both_resident: mate 2 is staged into buffers of its own, so that
@@ -994,9 +1062,10 @@ static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_
     return REAL_HIP_OK;
 }
 
-// real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join
+// real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join; with singles
+// (real_hip_match_pairs_singles: both arrays or none) each mate's hit list is folded into its records while it is resident
 static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_pair_params *pp,
-                           const real_hip_mate_search_params *sp, real_hip_pair *pairs)
+                           const real_hip_mate_search_params *sp, real_hip_pair *pairs, real_hip_single *const singles[2] = nullptr)
 {
     int rc;
     real_hip_batch bv[2];
@@ -1022,6 +1091,14 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
     rc = rh_launch_pair(ctx, *pp, (const real_hip_hit *)ctx->pair_hits[0].p, (const uint64_t *)ctx->pair_off[0].p, (const uint32_t *)ctx->pair_len[0].p, total[0],
                         (const real_hip_hit *)ctx->pair_hits[1].p, (const uint64_t *)ctx->pair_off[1].p, (const uint32_t *)ctx->pair_len[1].p, total[1],
                         n, ctx->fileid, fresh, d_pairs);
+    real_hip_single *d_singles[2] = {nullptr, nullptr};
+    if (!rc && singles) { // seed hits only: the search below adds nothing to the lists
+        const real_hip_hit *d_h[2] = {(const real_hip_hit *)ctx->pair_hits[0].p, (const real_hip_hit *)ctx->pair_hits[1].p};
+        const uint64_t *d_o[2] = {(const uint64_t *)ctx->pair_off[0].p, (const uint64_t *)ctx->pair_off[1].p};
+        const uint32_t *d_l[2] = {(const uint32_t *)ctx->pair_len[0].p, (const uint32_t *)ctx->pair_len[1].p};
+        rc = stage_singles(ctx, 2, singles, n, host_out, fresh, d_singles);
+        if (!rc) rc = rh_launch_single(ctx, 2, d_h, d_o, d_l, total, n, ctx->fileid, fresh, d_singles);
+    }
     if (!rc && sp) // the records of the join are the search's in/out records
         rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), (const real_hip_hit *)ctx->pair_hits[0].p,
                                    (const uint64_t *)ctx->pair_off[0].p, total[0], (const real_hip_hit *)ctx->pair_hits[1].p,
@@ -1030,6 +1107,7 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
         hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
     }
+    if (!rc && host_out && singles) rc = download_singles(ctx, 2, singles, n, d_singles);
     hipError_t e = hipStreamSynchronize(ctx->stream);
     rh_time_resolve(ctx);
     if (rc) return rc;
@@ -1053,6 +1131,18 @@ extern "C" int real_hip_match_pairs_search(real_hip_ctx *ctx, const real_hip_bat
     int rc = pair_params_check(ctx, pp);
     if (rc || (rc = search_params_check(ctx, pp, sp))) return rc;
     return match_pairs_run(ctx, batch1, batch2, pp, sp, pairs);
+}
+
+extern "C" int real_hip_match_pairs_singles(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                            const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs,
+                                            real_hip_single *singles1, real_hip_single *singles2)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc || (sp && (rc = search_params_check(ctx, pp, sp)))) return rc;
+    if (!singles1 || !singles2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null singles", hipSuccess);
+    real_hip_single *const singles[2] = {singles1, singles2};
+    return match_pairs_run(ctx, batch1, batch2, pp, sp, pairs, singles);
 }
 
 extern "C" int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)

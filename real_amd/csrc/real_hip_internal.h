@@ -259,6 +259,12 @@ struct real_hip_ctx {
     uint64_t pa_fragments = 0, pa_pairs_out = 0, pa_launches = 0;
     double   pa_kernel_ms = 0;
 
+    // single placements of a mate (single_fold.hip): the staged records of the two lists when the caller's are host memory,
+    // the hand-over list of the wave kernel, striped statistics, the event times of its launches
+    DevBuf sg_rec[2], sg_list, sg_stats;
+    uint64_t sg_reads = 0, sg_launches = 0;
+    double   sg_kernel_ms = 0;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -346,6 +352,12 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const re
                      uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
                      uint32_t fileid, const uint64_t *d_off, real_hip_pair_hit *d_out, uint64_t cap, uint64_t total);
 int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
+
+// ---- single placements of a mate (single_fold.hip) ---------------------------------
+#define RH_K_SINGLE (-3) /* rh_time_begin: the time goes to ctx->sg_kernel_ms */
+int rh_launch_single(real_hip_ctx *ctx, int lists, const real_hip_hit *const d_h[2], const uint64_t *const d_o[2], const uint32_t *const d_len[2],
+                     const uint64_t total[2], uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
+int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

@@ -46,6 +46,9 @@ void RealOptions::printHelp() const
               << "-mate_search_anchors <a mate with more hits than this in a genome file starts no search, 0=no limit, default=0>\n"
               << "-pairs_all <0|1: with -p2, print EVERY concordant pair of a fragment (two lines each, per genome file, in the order of\n"
               << "   the two mates' hit lists) instead of the unique one; pairs of two seed hits: not with -mate_search 1, default=0>\n"
+              << "-unpaired <file: with -p2, receives the mates of the fragments WITHOUT a concordant pair (after the last genome file, and\n"
+              << "   after the search with -mate_search 1) that are placed uniquely on their own: mate 1's line, then mate 2's, as the\n"
+              << "   single-end mode prints that hit; -o is unchanged; not with -pairs_all 1>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -107,6 +110,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-mate_search") { mate_search = atoi(need("-mate_search").c_str()) != 0; mate_search_given = true; i += 2; }
         else if (a == "-pairs_all") { pairs_all = atoi(need("-pairs_all").c_str()) != 0; pairs_all_given = true; i += 2; }
         else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
+        else if (a == "-unpaired") { unpairedfilename = need("-unpaired"); unpaired_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -176,9 +180,15 @@ RealOptions::RealOptions(int argc, char *argv[])
             throw std::runtime_error("-mate_search 1 takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
         if (pairs_all && mate_search)
             throw std::runtime_error("-pairs_all 1 lists the concordant pairs of two seed hits: it cannot be combined with -mate_search 1.");
+        if (unpaired_given && pairs_all)
+            throw std::runtime_error("-unpaired lists the mates of the fragments without a pair: it cannot be combined with -pairs_all 1.");
+        if (unpaired_given && (unpairedfilename.empty() || unpairedfilename == outputfilename))
+            throw std::runtime_error("-unpaired must name a file of its own: it names the same file as -o.");
         fastq2 = isFastQ(pattern2filename);
     } else if (mate_search_given) {
         throw std::runtime_error("-mate_search / -mate_search_anchors are only meaningful with -p2 (paired-end reads).");
+    } else if (unpaired_given) {
+        throw std::runtime_error("-unpaired is only meaningful with -p2 (paired-end reads).");
     } else if (pairs_all_given) {
         throw std::runtime_error("-pairs_all is only meaningful with -p2 (paired-end reads).");
     }

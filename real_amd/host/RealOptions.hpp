@@ -51,6 +51,8 @@ struct RealOptions {
     uint32_t mate_search_anchors = 0; // -mate_search_anchors: real_hip_mate_search_params.max_anchors
     bool pairs_all = false;           // -pairs_all: every concordant pair of a fragment (real_hip_match_pairs_all) instead of the unique one
     bool pairs_all_given = false;     // (the flag was on the command line: an error without -p2)
+    std::string unpairedfilename;     // -unpaired: the file that receives the Unique mates of the fragments without a pair (real_hip_match_pairs_singles)
+    bool unpaired_given = false;      // (the flag was on the command line: an error without -p2)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)
 

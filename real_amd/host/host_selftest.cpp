@@ -5,6 +5,7 @@
 //   host_selftest options <args...>               -> prints the parsed RealOptions
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
+//   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 #include <cstdio>
 #include <cstdlib>
@@ -205,6 +206,11 @@ int main(int argc, char **argv)
         if (cmd == "mate_search_options") { // -mate_search, -mate_search_anchors
             RealOptions o(argc - 1, argv + 1);
             std::cout << o.mate_search << " " << o.mate_search_anchors << "\n";
+            return 0;
+        }
+        if (cmd == "unpaired_options") { // -unpaired
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.unpairedfilename.empty() ? "." : o.unpairedfilename) << "\n";
             return 0;
         }
         if (cmd == "pairs_all_options") { // -pairs_all

@@ -733,6 +733,9 @@ int matchAll(const RealOptions &o)
 // per genome file real_hip_match_pairs (-mate_search 1: real_hip_match_pairs_search) folds into the fragments' in/out
 // records, as uniqueinfo[] folds for matchUnique.
 // A Unique fragment prints the 11-column line of mate 1 and then of mate 2; NoMatch / NonUnique print nothing.
+// -unpaired <file>: real_hip_match_pairs_singles folds each mate's own hits beside the pairs; a fragment whose final pair
+// state is NoMatch writes to <file> the line of mate 1 if it is Unique on its own, then mate 2's likewise, as the
+// single-end mode would print that hit.  The main output does not change.
 int matchPairs(const RealOptions &o)
 {
     Timers T;
@@ -753,6 +756,8 @@ int matchPairs(const RealOptions &o)
     memset(&sp, 0, sizeof sp);
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
+    const bool unpaired = !o.unpairedfilename.empty();
+    std::vector<real_hip_single> singles1, singles2; // -unpaired: kept across the genome files as pairs is
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
@@ -782,10 +787,14 @@ int matchPairs(const RealOptions &o)
             if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
             if (!n1) break;
             if (seen + n1 > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n1, pairs.size() + pairs.size() / 2));
+            if (unpaired && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
             const double tm = now_s();
-            if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, pairs.data() + seen), "real_hip_match_pairs_search");
+            if (unpaired)
+                check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, pairs.data() + seen, singles1.data() + seen,
+                                                      singles2.data() + seen), "real_hip_match_pairs_singles");
+            else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, pairs.data() + seen), "real_hip_match_pairs_search");
             else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
             T.match += now_s() - tm;
             seen += n1;
@@ -799,11 +808,33 @@ int matchPairs(const RealOptions &o)
     std::vector<char> obuf((size_t)8 << 20);
     setvbuf(out, obuf.data(), _IOFBF, obuf.size());
     uint64_t unique = 0, base = 0;
+    FILE *uout = nullptr;
+    std::vector<char> ubuf;
+    if (unpaired) {
+        uout = fopen(o.unpairedfilename.c_str(), "wb");
+        if (!uout) throw std::runtime_error("cannot open the -unpaired file " + o.unpairedfilename);
+        ubuf.resize((size_t)8 << 20);
+        setvbuf(uout, ubuf.data(), _IOFBF, ubuf.size());
+    }
+    // the line of a mate that is placed uniquely on its own, as the single-end mode prints that hit
+    auto singleLine = [&](std::string &s, const ReadBlock &b, uint64_t i, const real_hip_single &S) {
+        if (REAL_HIP_SINGLE_STATE(S.tag) != REAL_HIP_PAIR_UNIQUE) return;
+        const uint64_t lo = b.offsets[i];
+        appendLine(s, b.ids[i].data(), b.ids[i].size(), nullptr, &b.bases[lo], b.offsets[i + 1] - lo, o.scores, o.scores ? S.score : 0.f,
+                   REAL_HIP_SINGLE_INVERTED(S.tag) != 0, RS.names[S.fileid][S.frag], (uint64_t)S.pos - RS.starts[S.fileid][S.frag] + 1,
+                   REAL_HIP_SINGLE_K(S.tag));
+    };
     ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
     for (;;) {
         const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
         if (n1 != n2 || base + n1 > numpat) throw std::runtime_error("the read files changed between two passes");
         if (!n1) break;
+        if (unpaired)
+            formatAndWrite(n1, uout, T, [&](uint64_t i, std::string &s) {
+                if (pairs[base + i].state != REAL_HIP_PAIR_NOMATCH) return;
+                singleLine(s, b1, i, singles1[base + i]);
+                singleLine(s, b2, i, singles2[base + i]);
+            });
         formatAndWrite(n1, out, T, [&](uint64_t i, std::string &s) {
             const real_hip_pair &P = pairs[base + i];
             if (P.state != REAL_HIP_PAIR_UNIQUE) return;
@@ -822,6 +853,15 @@ int matchPairs(const RealOptions &o)
     if (out != stdout) fclose(out);
     for (uint64_t i = 0; i < numpat; ++i) unique += pairs[i].state == REAL_HIP_PAIR_UNIQUE;
     std::cerr << "unique fragments: " << unique << std::endl;
+    if (unpaired) {
+        if (fflush(uout) != 0) throw std::runtime_error("write to the -unpaired file failed");
+        fclose(uout);
+        uint64_t mates = 0;
+        for (uint64_t i = 0; i < numpat; ++i)
+            if (pairs[i].state == REAL_HIP_PAIR_NOMATCH)
+                mates += (REAL_HIP_SINGLE_STATE(singles1[i].tag) == REAL_HIP_PAIR_UNIQUE) + (REAL_HIP_SINGLE_STATE(singles2[i].tag) == REAL_HIP_PAIR_UNIQUE);
+        std::cerr << "unpaired mates: " << mates << std::endl;
+    }
     T.reads = 2 * numpat; T.lines = 2 * unique; T.total = now_s() - t_begin;
     T.print();
     return EXIT_SUCCESS;

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "real_hip_pair_hits", "real_hip_match_pairs", "real_hip_pair_stats_get",
     "real_hip_pair_search", "real_hip_match_pairs_search", "real_hip_mate_search_stats_get",
     "real_hip_pair_all_hits", "real_hip_match_pairs_all", "real_hip_pair_all_stats_get",
+    "real_hip_single_hits", "real_hip_match_pairs_singles", "real_hip_single_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -106,6 +107,11 @@ class RealHipPairAllStats(C.Structure):
                 ("pairs_out", C.c_uint64), ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
+class RealHipSingleStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("reads", C.c_uint64), ("hits", C.c_uint64),
+                ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
 class RealHipPairHit(C.Structure):
     """real_hip_pair_hit: one concordant pair (PAIR_HIT_DTYPE is the same record as a numpy dtype)"""
     _fields_ = [("pair", C.c_uint32), ("pos1", C.c_uint32), ("pos2", C.c_uint32), ("outer", C.c_uint32),
@@ -122,6 +128,23 @@ PAIR_DTYPE = np.dtype([("best", "<f8"), ("second", "<f8"), ("pos1", "<u4"), ("po
                        ("frag", "<u2"), ("fileid", "u1"), ("k1", "u1"), ("k2", "u1"), ("inverted1", "u1"), ("state", "u1"),
                        ("reserved", "u1")])
 assert PAIR_DTYPE.itemsize == 40
+
+# real_hip_single: the in/out record of one mate on its own; tag = k (bits 0-3) | inverted << 4 | state << 5
+SINGLE_DTYPE = np.dtype([("score", "<f4"), ("second", "<f4"), ("pos", "<u4"), ("frag", "<u2"), ("fileid", "u1"), ("tag", "u1")])
+assert SINGLE_DTYPE.itemsize == 16
+
+
+def single_k(tag):
+    return np.asarray(tag) & 15
+
+
+def single_inverted(tag):
+    return (np.asarray(tag) >> 4) & 1
+
+
+def single_state(tag):
+    return (np.asarray(tag) >> 5) & 3
+
 
 HIT_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4"), ("score", "<f4"), ("frag", "<u2"),
                       ("k", "u1"), ("inverted", "u1")])
@@ -195,6 +218,10 @@ def load():
     L.real_hip_match_pairs_all.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp, u64,
                                            C.POINTER(u64), vp]
     L.real_hip_pair_all_stats_get.argtypes = [vp, C.POINTER(RealHipPairAllStats), C.c_int]
+    L.real_hip_single_hits.argtypes = [vp, vp, vp, vp, u64, u32, C.c_int, C.c_int, vp]
+    L.real_hip_match_pairs_singles.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
+                                               C.POINTER(RealHipMateSearchParams), vp, vp, vp]
+    L.real_hip_single_stats_get.argtypes = [vp, C.POINTER(RealHipSingleStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import lib as _lib
-from .lib import (HIT_DTYPE, PAIR_DTYPE, PAIR_HIT_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
+from .lib import (HIT_DTYPE, PAIR_DTYPE, PAIR_HIT_DTYPE, SINGLE_DTYPE, RealHipBatch, RealHipCounters, RealHipError, RealHipParams, _ptr)
 
 NO_SCORE = np.float32(-np.finfo(np.float32).max)   # UniqueMatchInfo<true>() : score(-FLT_MAX), UniqueMatchInfo.hpp:191
 
@@ -54,6 +54,7 @@ class RealOptions:
     mate_search_anchors: int = 0    # -mate_search_anchors: a mate with more hits than this contributes no anchors (0: no limit)
     pairs_all: bool = False         # -pairs_all: with -p2, print every concordant pair of a fragment instead of the unique one
     pairs_all_given: bool = False   # (the flag was on the command line: an error without -p2)
+    unpairedfilename: str = ""      # -unpaired: with -p2, the file that receives the Unique mates of the fragments without a pair
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -79,6 +80,12 @@ class RealOptions:
                 raise ValueError("-mate_search 1 takes an -insert_max of at most %d" % _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT)
             if self.pairs_all and self.mate_search:
                 raise ValueError("-pairs_all 1 lists pairs of two seed hits: it cannot be combined with -mate_search 1")
+            if self.unpairedfilename and self.pairs_all:
+                raise ValueError("-unpaired lists the mates of the fragments without a pair: it cannot be combined with -pairs_all 1")
+            if self.unpairedfilename and self.unpairedfilename == self.outputfilename:
+                raise ValueError("-unpaired names the same file as -o")
+        elif self.unpairedfilename:
+            raise ValueError("-unpaired needs -p2 (paired-end reads)")
         elif self.mate_search or self.mate_search_anchors:
             raise ValueError("-mate_search / -mate_search_anchors need -p2 (paired-end reads)")
         elif self.pairs_all or self.pairs_all_given:
@@ -112,7 +119,7 @@ class RealOptions:
                  "-filter_level": ("filter_level", int), "-p2": ("pattern2filename", str), "-insert_min": ("insert_min", int),
                  "-insert_max": ("insert_max", int), "-gpus": ("gpus", int),
                  "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int),
-                 "-pairs_all": ("pairs_all", lambda v: bool(int(v)))}
+                 "-pairs_all": ("pairs_all", lambda v: bool(int(v))), "-unpaired": ("unpairedfilename", str)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -140,6 +147,13 @@ def new_pair_info(n: int) -> np.ndarray:
     """the records of n fragments before the first genome file: no pair, best = second = -inf (real_hip_pair)"""
     rec = np.zeros(n, dtype=PAIR_DTYPE)
     rec["best"] = -np.inf
+    rec["second"] = -np.inf
+    return rec
+
+
+def new_single_info(n: int) -> np.ndarray:
+    """the records of n reads before the first genome file: empty (state NoMatch, score 0, second -inf; real_hip_single)"""
+    rec = np.zeros(n, dtype=SINGLE_DTYPE)
     rec["second"] = -np.inf
     return rec
 
@@ -577,6 +591,61 @@ class PairMatcher(AllMatcher):
         self._check(self._L.real_hip_pair_hits(self._h, C.byref(pp), _ptr(hits1), _ptr(off1), _ptr(len1), _ptr(hits2), _ptr(off2), _ptr(len2),
                                                n, int(fileid), int(on_device), int(bool(fresh)), _ptr(pairs)))
         return pairs
+
+    # -- single placements of a mate (real_hip_single records) --
+    new_single_info = staticmethod(new_single_info)
+
+    def single_hits(self, hits, off, lens, fileid: int = 0, singles=None, fresh: Optional[bool] = None):
+        """real_hip_single_hits: the fold alone, on one mate's lists as the caller holds them (numpy arrays of lib.HIT_DTYPE /
+        uint64 / uint32, or device torch tensors of the same layout, all of one kind; device inputs need `singles` as a device
+        tensor of 16-byte records)."""
+        on_device = bool(getattr(off, "is_cuda", False))
+        if not on_device:
+            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            lens = np.ascontiguousarray(lens, dtype=np.uint32)
+        n = int(off.shape[0]) - 1
+        if int(lens.shape[0]) != n:
+            raise ValueError("the offsets and the lengths describe different numbers of reads")
+        if fresh is None:
+            fresh = singles is None
+        if singles is None:
+            if on_device:
+                raise ValueError("device inputs need a device tensor for the records")
+            singles = new_single_info(n)
+        self.sync_inputs(hits, off, lens, singles)
+        self._check(self._L.real_hip_single_hits(self._h, _ptr(hits), _ptr(off), _ptr(lens), n, int(fileid), int(on_device),
+                                                 int(bool(fresh)), _ptr(singles)))
+        return singles
+
+    def match_pairs_singles(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, singles1=None, singles2=None,
+                            orientation: int = 0, mate_search: bool = False, max_anchors: int = 0, fresh: Optional[bool] = None):
+        """real_hip_match_pairs_singles: match_pairs (mate_search: with the search behind the join) and, in the same call,
+        each mate's hit list folded into its own records -> (pairs, singles1, singles2).  The three arrays are started
+        together (None) or folded into together; device batches need all three as device tensors (fresh=True: output only)."""
+        b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        given = [x is not None for x in (pairs, singles1, singles2)]
+        if any(given) and not all(given):
+            raise ValueError("pairs, singles1 and singles2 are started together or folded into together")
+        if fresh is None:
+            fresh = pairs is None
+        if pairs is None:
+            n = int(b1.n_reads)
+            pairs, singles1, singles2 = new_pair_info(n), new_single_info(n), new_single_info(n)
+        b1.fresh = b2.fresh = int(bool(fresh))
+        self.sync_inputs(pairs, singles1, singles2)
+        sp = self._search_params(max_anchors) if mate_search else None
+        self._check(self._L.real_hip_match_pairs_singles(self._h, C.byref(b1), C.byref(b2), C.byref(pp), C.byref(sp) if sp is not None else None,
+                                                         _ptr(pairs), _ptr(singles1), _ptr(singles2)))
+        return pairs, singles1, singles2
+
+    def single_stats(self, reset: bool = False) -> dict:
+        st = _lib.RealHipSingleStats()
+        st.struct_size = C.sizeof(_lib.RealHipSingleStats)
+        self._check(self._L.real_hip_single_stats_get(self._h, C.byref(st), int(reset)))
+        return {"reads": int(st.reads), "hits": int(st.hits), "handed_over": int(st.handed_over), "launches": int(st.launches),
+                "kernel_ms": float(st.kernel_ms)}
 
     def pair_stats(self, reset: bool = False) -> dict:
         st = _lib.RealHipPairStats()
