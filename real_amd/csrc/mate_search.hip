@@ -19,14 +19,11 @@
 
 #define RH_MS_STRIPES 256u /* the statistics are striped over this many 128-byte lines (see RH_CSTRIPES) */
 #define RH_MS_TW (REAL_HIP_MATE_SEARCH_MAX_INSERT / 32u + 2u) /* text words of a window: max_insert bases from anywhere inside a word, one more for the funnel shift */
-#define RH_MS_BLOCKS 2048u /* a fixed grid: the waves take fragments in turn and the score table is loaded once per block */
 
 struct MateSearchArgs {
     DevText t;
     DevBatch b[2];                 // the mates' reads
-    const uint4 *h[2];             // real_hip_hit records: the anchors of mate 1 / mate 2
-    const uint64_t *o[2];          // n + 1 offsets into them
-    uint64_t total[2];             // the offsets are clamped to these (rh_launch_pair)
+    MateLists L;                   // the hit lists of mate 1 / mate 2: the anchors (len[] is not read: the lengths come from the batches)
     uint64_t n;                    // fragments
     real_hip_pair *pairs;
     const double *LL;
@@ -62,13 +59,6 @@ static __device__ __forceinline__ uint64_t ms_word(const DevBatch &b, uint64_t o
     return w;
 }
 
-static __device__ __forceinline__ void ms_range(const uint64_t *o, uint64_t i, uint64_t total, uint64_t &lo, uint64_t &hi)
-{
-    hi = o[i + 1]; lo = o[i];
-    if (hi > total) hi = total;
-    if (lo > hi) lo = hi;
-}
-
 template <bool SCORES>
 __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A)
 {
@@ -96,7 +86,7 @@ __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
             const DevBatch &b = A.b[m];
-            ms_range(A.o[m], i, A.total[m], hlo[m], hhi[m]);
+            A.L.range(m, i, hlo[m], hhi[m]);
             o0[m] = b.off ? b.off[i] : i * (uint64_t)b.upatl;
             const uint64_t span = b.off ? (b.off[i + 1] >= o0[m] ? b.off[i + 1] - o0[m] : 0) : (uint64_t)b.upatl;
             if (span > (uint64_t)REAL_HIP_MAX_PATL) { // (the host has refused the batches it could measure)
@@ -148,7 +138,7 @@ __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A
             const uint32_t nwb = ((uint32_t)lb + 31) >> 5;
             const uint64_t lastmask = ~0ull << (64 - 2 * ((uint32_t)lb - 32 * (nwb - 1)));
             for (uint64_t x = hlo[m]; x < hlo[m] + cnt; ++x) {
-                const uint4 a = A.h[m][x]; // (the same record in every lane)
+                const uint4 a = A.L.h[m][x]; // (the same record in every lane)
                 const uint32_t aw = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.w), az = (uint32_t)__builtin_amdgcn_readfirstlane((int)a.z);
                 const int64_t pa = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)a.y);
                 const uint32_t frag = aw & 0xffffu, ka = (aw >> 16) & 0xffu;
@@ -207,31 +197,18 @@ __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A
                         const uint32_t pos1 = m == 0 ? (uint32_t)pa : (uint32_t)p, pos2 = m == 0 ? (uint32_t)p : (uint32_t)pa;
                         const uint32_t inv1 = m == 0 ? (inva ? 1u : 0u) : invb;
                         PairState c;
-                        c.best = A.scores ? (double)__uint_as_float(s1) + (double)__uint_as_float(s2) : -(double)(k1 + k2);
-                        c.second = pair_neg_inf();
-                        c.lhi = ((uint64_t)A.fileid << 48) | ((uint64_t)frag << 32) | pos1;
-                        c.llo = ((uint64_t)pos2 << 1) | inv1;
-                        c.s1 = s1; c.s2 = s2; c.k = k1 | (k2 << 8);
+                        ps_candidate(c, A.scores, A.fileid, frag, pos1, pos2, inv1, s1, s2, k1, k2);
                         ps_merge(st, c);
                     }
                 }
             }
         }
-        if (elig) {
-            for (int d = 32; d; d >>= 1) { // butterfly: every lane ends with the wave's state
-                PairState o;
-                o.best = __shfl_xor(st.best, d); o.second = __shfl_xor(st.second, d);
-                o.lhi = __shfl_xor((unsigned long long)st.lhi, d); o.llo = __shfl_xor((unsigned long long)st.llo, d);
-                o.s1 = __shfl_xor(st.s1, d); o.s2 = __shfl_xor(st.s2, d); o.k = __shfl_xor(st.k, d);
-                ps_merge(st, o);
-            }
-        }
+        if (elig) ps_butterfly(st);
         // the record: in/out records the search adds nothing to stay as they are
         if (lane == 0 && (A.fresh || st.best != pair_neg_inf())) {
             if (!A.fresh) { PairState in; ps_from_record(in, A.pairs[i]); ps_merge(st, in); }
-            const double eps = A.scores ? (double)(float)(A.filter_mult * (double)((uint64_t)len[0] + len[1])) : 0.0; // (an empty record needs none)
             real_hip_pair r;
-            ps_to_record(st, eps, r);
+            ps_to_record(st, ps_eps(A.scores, A.filter_mult, len[0], len[1]), r); // (an empty record needs no eps)
             A.pairs[i] = r;
         }
     }
@@ -246,23 +223,19 @@ __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A
 
 // the search over n fragments on device arrays; asynchronous on the ctx's stream
 int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_mate_search_params &sp, const DevBatch &b1,
-                          const DevBatch &b2, const real_hip_hit *d_h1, const uint64_t *d_o1, uint64_t total1, const real_hip_hit *d_h2,
-                          const uint64_t *d_o2, uint64_t total2, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs)
+                          const DevBatch &b2, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs)
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
     const size_t stat_bytes = (size_t)RH_MS_STRIPES * 16 * 8;
-    if (!ctx->ms_stats.p) {
-        if ((rc = rh_reserve(ctx, ctx->ms_stats, stat_bytes + 8))) return rc;
-        RH_HIP(ctx, hipMemsetAsync(ctx->ms_stats.p, 0, stat_bytes + 8, ctx->stream));
-    }
+    if ((rc = rh_stats_reserve(ctx, ctx->ms_stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
     MateSearchArgs A;
     memset(&A, 0, sizeof A);
     A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p; A.t.frag_start = (const uint64_t *)ctx->frag.p;
     A.t.n = ctx->n_bases; A.t.n_frag = ctx->n_frag; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = fileid;
     A.b[0] = b1; A.b[1] = b2;
-    A.h[0] = (const uint4 *)d_h1; A.h[1] = (const uint4 *)d_h2; A.o[0] = d_o1; A.o[1] = d_o2; A.total[0] = total1; A.total[1] = total2;
+    A.L = L; // (its len[] may be null: the kernel takes the read lengths from the batches)
     A.n = n; A.pairs = d_pairs; A.LL = (const double *)ctx->LL.p;
     A.stats = (unsigned long long *)ctx->ms_stats.p;
     A.err_flags = (uint32_t *)((char *)ctx->ms_stats.p + stat_bytes);
@@ -271,10 +244,9 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
     A.min_insert = pp.min_insert; A.max_insert = pp.max_insert; A.seedl = ctx->prm.seedl; A.totalkmax = ctx->prm.totalkmax;
     A.max_anchors = sp.max_anchors;
     RH_HIP(ctx, hipMemsetAsync(A.err_flags, 0, 4, ctx->stream));
-    const uint64_t blocks = (n + 3) / 4 < RH_MS_BLOCKS ? (n + 3) / 4 : RH_MS_BLOCKS;
     rh_time_begin(ctx, ctx->stream, RH_K_MATE_SEARCH);
-    if (A.scores) hipLaunchKernelGGL(mate_search_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, A);
-    else hipLaunchKernelGGL(mate_search_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, A);
+    if (A.scores) hipLaunchKernelGGL(mate_search_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+    else hipLaunchKernelGGL(mate_search_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
     RH_HIP(ctx, hipMemcpyAsync(&ctx->ms_err, A.err_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -294,15 +266,9 @@ int rh_mate_search_finish(real_hip_ctx *ctx)
 
 int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)
 {
-    uint64_t h[4] = {0, 0, 0, 0};
-    if (ctx->ms_stats.p) {
-        std::vector<uint64_t> all((size_t)RH_MS_STRIPES * 16);
-        RH_HIP(ctx, hipMemcpyAsync(all.data(), ctx->ms_stats.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (reset) RH_HIP(ctx, hipMemsetAsync(ctx->ms_stats.p, 0, all.size() * 8, ctx->stream));
-        RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t st = 0; st < RH_MS_STRIPES; ++st)
-            for (int k = 0; k < 4; ++k) h[k] += all[st * 16 + k];
-    }
+    uint64_t h[4];
+    int rc;
+    if ((rc = rh_stats_read(ctx, ctx->ms_stats, RH_MS_STRIPES, 4, reset, h))) return rc;
     rh_time_resolve(ctx);
     if (out) {
         out->reserved = 0;

@@ -15,10 +15,8 @@
 #include <rocprim/device/device_scan.hpp>
 
 struct PairAllArgs {
-    const uint4 *h1, *h2;          // real_hip_hit records of mate 1 / mate 2
-    const uint64_t *o1, *o2;       // n + 1 offsets into them
-    const uint32_t *len1, *len2;   // read lengths
-    uint64_t n, total1, total2;    // fragments; upper bounds of the hits inside h1 / h2 (the offsets are clamped to them)
+    MateLists L;                   // the hit lists of mate 1 / mate 2
+    uint64_t n;                    // fragments
     uint64_t *cnt;                 // n + 1: concordant pairs per fragment (count kernels; cnt[n] = 0)
     const uint64_t *off;           // n + 1: their exclusive scan (emit kernels)
     uint4 *out;                    // real_hip_pair_hit records, two uint4 each
@@ -51,17 +49,17 @@ __global__ void __launch_bounds__(256) pair_all_lane_kernel(const PairAllArgs A)
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < A.n;
     uint64_t lo1 = 0, hi1 = 0, lo2 = 0, hi2 = 0;
-    if (live) { pair_range(A.o1, i, A.total1, lo1, hi1); pair_range(A.o2, i, A.total2, lo2, hi2); }
+    if (live) { A.L.range(0, i, lo1, hi1); A.L.range(1, i, lo2, hi2); }
     unsigned long long cells = pair_all_cells(hi1 - lo1, hi2 - lo2);
     const bool big = cells > RH_PAIR_LANE_BUDGET;
     if (live && !big) {
         uint64_t found = 0, slot = EMIT ? A.off[i] : 0;
         if (cells) {
-            const uint32_t la = A.len1[i], lb = A.len2[i];
+            const uint32_t la = A.L.len[0][i], lb = A.L.len[1][i];
             for (uint64_t x = lo1; x < hi1; ++x) {
-                const uint4 a = A.h1[x];
+                const uint4 a = A.L.h[0][x];
                 for (uint64_t y = lo2; y < hi2; ++y) {
-                    const uint4 b = A.h2[y];
+                    const uint4 b = A.L.h[1][y];
                     uint64_t outer;
                     if (!pair_concordant(a, b, la, lb, A.min_insert, A.max_insert, outer)) continue;
                     if (EMIT) pair_all_store(A, slot++, (uint32_t)i, a, b, outer);
@@ -73,22 +71,7 @@ __global__ void __launch_bounds__(256) pair_all_lane_kernel(const PairAllArgs A)
     }
     if (EMIT) return;
     if (i == A.n) A.cnt[i] = 0; // (the grid covers n + 1 lanes)
-    // hand-over list (one atomic per wave) and statistics (one stripe per block)
-    const unsigned long long mask = __ballot(live && big);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (mask) {
-        unsigned long long base = 0;
-        const int leader = __ffsll((long long)mask) - 1;
-        if ((int)lane == leader) base = atomicAdd(A.list_count, (unsigned long long)__popcll(mask));
-        base = __shfl(base, leader);
-        if (live && big) A.list[base + __popcll(mask & ((1ull << lane) - 1ull))] = (uint32_t)i;
-    }
-    for (int d = 32; d; d >>= 1) cells += __shfl_xor(cells, d);
-    if (lane == 0) {
-        unsigned long long *s = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-        if (cells) atomicAdd(s, cells);
-        if (mask) atomicAdd(s + 1, (unsigned long long)__popcll(mask));
-    }
+    pair_hand_over(live && big, (uint32_t)i, cells, blockIdx.x, A.list, A.list_count, A.stats);
 }
 
 // one wave per handed-over fragment, 64 consecutive cells of the flattened product per turn
@@ -101,11 +84,11 @@ __global__ void __launch_bounds__(256) pair_all_wave_kernel(const PairAllArgs A)
     for (uint64_t w = wave; w < count; w += n_waves) {
         const uint32_t i = A.list[w];
         uint64_t lo1, hi1, lo2, hi2;
-        pair_range(A.o1, i, A.total1, lo1, hi1);
-        pair_range(A.o2, i, A.total2, lo2, hi2);
+        A.L.range(0, i, lo1, hi1);
+        A.L.range(1, i, lo2, hi2);
         const uint64_t n1 = hi1 - lo1, n2 = hi2 - lo2;
         const unsigned long long cells = pair_all_cells(n1, n2);
-        const uint32_t la = A.len1[i], lb = A.len2[i];
+        const uint32_t la = A.L.len[0][i], lb = A.L.len[1][i];
         // cell lane of the first turn, and the step of 64 cells as (rows, columns): y + ystep < 2 * n2
         uint64_t x, y, xstep, ystep;
         if (n2 > 64) { x = 0; y = lane; xstep = 0; ystep = 64; }
@@ -116,7 +99,7 @@ __global__ void __launch_bounds__(256) pair_all_wave_kernel(const PairAllArgs A)
             uint4 a = make_uint4(0, 0, 0, 0), b = a;
             uint64_t outer = 0;
             if (x < n1) { // (c0 + lane < cells)
-                a = A.h1[lo1 + x]; b = A.h2[lo2 + y];
+                a = A.L.h[0][lo1 + x]; b = A.L.h[1][lo2 + y];
                 ok = pair_concordant(a, b, la, lb, A.min_insert, A.max_insert, outer);
             }
             const unsigned long long mask = __ballot(ok);
@@ -132,42 +115,32 @@ __global__ void __launch_bounds__(256) pair_all_wave_kernel(const PairAllArgs A)
 // Phase 1 of the enumeration of n fragments on device arrays: counts, their scan into d_off (n + 1 entries, device) and the
 // total, read back (the stream is synchronised).  Phase 2, rh_pair_all_emit, writes the records; the caller decides in
 // between whether they fit.
-static PairAllArgs pair_all_args(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                                 uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                                 uint32_t fileid, const uint64_t *d_off)
+static PairAllArgs pair_all_args(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, const uint64_t *d_off)
 {
     PairAllArgs A;
-    A.h1 = (const uint4 *)d_h1; A.h2 = (const uint4 *)d_h2; A.o1 = d_o1; A.o2 = d_o2; A.len1 = d_len1; A.len2 = d_len2;
-    A.n = n; A.total1 = total1; A.total2 = total2;
+    A.L = L; A.n = n;
     A.cnt = (uint64_t *)ctx->pa_cnt.p; A.off = d_off; A.out = nullptr; A.cap = 0;
     A.list_count = (unsigned long long *)ctx->pair_list.p; A.list = (uint32_t *)ctx->pair_list.p + 2;
     A.stats = (unsigned long long *)ctx->pa_stats.p;
     A.fileid = fileid; A.min_insert = pp.min_insert; A.max_insert = pp.max_insert;
     return A;
 }
-// a fixed grid of waves takes the handed-over fragments in turn (their number stays on the device)
-static unsigned pair_all_wave_blocks(uint64_t n) { return (unsigned)((n + 3) / 4 < 2048 ? (n + 3) / 4 : 2048); }
 
-int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                      uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                      uint64_t *d_off, uint64_t *total)
+int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint64_t *d_off, uint64_t *total)
 {
     *total = 0;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
-    if (!ctx->pa_stats.p) {
-        if ((rc = rh_reserve(ctx, ctx->pa_stats, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
-        RH_HIP(ctx, hipMemsetAsync(ctx->pa_stats.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
-    }
+    if ((rc = rh_stats_reserve(ctx, ctx->pa_stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, ctx->pair_list, n * 4 + 8))) return rc;
     if ((rc = rh_reserve(ctx, ctx->pa_cnt, (n + 1) * 8))) return rc;
-    const PairAllArgs A = pair_all_args(ctx, pp, d_h1, d_o1, d_len1, total1, d_h2, d_o2, d_len2, total2, n, 0, d_off);
+    const PairAllArgs A = pair_all_args(ctx, pp, L, n, 0, d_off);
     RH_HIP(ctx, hipMemsetAsync(ctx->pair_list.p, 0, 8, ctx->stream));
     rh_time_begin(ctx, ctx->stream, RH_K_PAIR_ALL);
     hipLaunchKernelGGL(pair_all_lane_kernel<false>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, A);
     RH_HIP(ctx, hipGetLastError());
     if (n) {
-        hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(pair_all_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+        hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
         RH_HIP(ctx, hipGetLastError());
         ctx->pa_launches += 1;
     }
@@ -185,17 +158,16 @@ int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const r
 
 // the records of the fragments counted last, behind d_off into d_out (cap records, 16-byte aligned); asynchronous on the
 // ctx's stream.  The lists must be what rh_pair_all_count saw.
-int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                     uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                     uint32_t fileid, const uint64_t *d_off, real_hip_pair_hit *d_out, uint64_t cap, uint64_t total)
+int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, const uint64_t *d_off,
+                     real_hip_pair_hit *d_out, uint64_t cap, uint64_t total)
 {
     if (!n || !total) return REAL_HIP_OK;
-    PairAllArgs A = pair_all_args(ctx, pp, d_h1, d_o1, d_len1, total1, d_h2, d_o2, d_len2, total2, n, fileid, d_off);
+    PairAllArgs A = pair_all_args(ctx, pp, L, n, fileid, d_off);
     A.out = (uint4 *)d_out; A.cap = cap;
     rh_time_begin(ctx, ctx->stream, RH_K_PAIR_ALL);
     hipLaunchKernelGGL(pair_all_lane_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
     RH_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(pair_all_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+    hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
     ctx->pa_launches += 2;
@@ -205,14 +177,9 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const re
 
 int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset)
 {
-    uint64_t h[2] = {0, 0};
-    if (ctx->pa_stats.p) {
-        std::vector<uint64_t> all((size_t)RH_PAIR_STRIPES * 16);
-        RH_HIP(ctx, hipMemcpyAsync(all.data(), ctx->pa_stats.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (reset) RH_HIP(ctx, hipMemsetAsync(ctx->pa_stats.p, 0, all.size() * 8, ctx->stream));
-        RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t st = 0; st < RH_PAIR_STRIPES; ++st) { h[0] += all[st * 16]; h[1] += all[st * 16 + 1]; }
-    }
+    uint64_t h[2];
+    int rc;
+    if ((rc = rh_stats_read(ctx, ctx->pa_stats, RH_PAIR_STRIPES, 2, reset, h))) return rc;
     rh_time_resolve(ctx);
     if (out) {
         out->reserved = 0;

@@ -1,7 +1,8 @@
-// pair_state.h -- the fold state of the paired-end records (include/real_hip.h, "paired-end reads"): shared by the join
-// (pair_kernel.hip) and the mate search (mate_search.hip), which fold candidates of the same kind into the same records;
-// and what the join shares with the enumeration of all concordant pairs (pair_all.hip): the concordance test, the
-// clamped range of a fragment's hits and the lane budget.
+// pair_state.h -- what the paired-end stages share (include/real_hip.h, "paired-end reads"): the view of the two mates' hit
+// lists with the clamped range of a fragment's hits, the concordance test, the lane budget and the hand-over of what is
+// beyond it to a wave kernel (the join pair_kernel.hip, the enumeration pair_all.hip, the single placements single_fold.hip);
+// and the fold state of the pair records with the candidate made of two placements (the join and the mate search
+// mate_search.hip, which fold candidates of the same kind into the same records).
 #pragma once
 #include "real_hip_internal.h"
 
@@ -23,12 +24,46 @@ static __device__ __forceinline__ bool pair_concordant(const uint4 a, const uint
     outer = re - fp;
     return outer >= min_insert && outer <= max_insert;
 }
-// hits [lo, hi) of fragment i: the offsets clamped to `total`, an upper bound of the hits inside the buffer
-static __device__ __forceinline__ void pair_range(const uint64_t *o, uint64_t i, uint64_t total, uint64_t &lo, uint64_t &hi)
+
+// The hit lists of the two mates (of the two lists of a fold): real_hip_hit records, n + 1 offsets into them, the read
+// lengths, and per list an upper bound `total` of the hits inside its buffer (real_hip_match_pairs passes the matcher's
+// count before duplicates go): the offsets are clamped to it, o[n] is the real end.
+struct MateLists {
+    const uint4 *h[2];
+    const uint64_t *o[2];
+    const uint32_t *len[2];
+    uint64_t total[2];
+    // hits [lo, hi) of fragment i in list m
+    __device__ __forceinline__ void range(uint32_t m, uint64_t i, uint64_t &lo, uint64_t &hi) const
+    {
+        hi = o[m][i + 1]; lo = o[m][i];
+        if (hi > total[m]) hi = total[m];
+        if (lo > hi) lo = hi;
+    }
+};
+
+// The end of a lane kernel: the lanes with more work than a lane's budget (`handed`) append their entry to the hand-over
+// list (one atomic per wave, the slots in lane order), and the wave adds its work and the number handed over to words 0
+// and 1 of a statistics stripe (one stripe per block).  Every lane of the wave calls it.
+template <typename E>
+static __device__ __forceinline__ void pair_hand_over(bool handed, E entry, unsigned long long work, uint32_t stripe, E *list,
+                                                      unsigned long long *list_count, unsigned long long *stats)
 {
-    hi = o[i + 1]; lo = o[i];
-    if (hi > total) hi = total;
-    if (lo > hi) lo = hi;
+    const unsigned long long mask = __ballot(handed);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (mask) {
+        unsigned long long base = 0;
+        const int leader = __ffsll((long long)mask) - 1;
+        if ((int)lane == leader) base = atomicAdd(list_count, (unsigned long long)__popcll(mask));
+        base = __shfl(base, leader);
+        if (handed) list[base + __popcll(mask & ((1ull << lane) - 1ull))] = entry;
+    }
+    for (int d = 32; d; d >>= 1) work += __shfl_xor(work, d);
+    if (lane == 0) {
+        unsigned long long *s = stats + (size_t)(stripe % RH_PAIR_STRIPES) * 16;
+        if (work) atomicAdd(s, work);
+        if (mask) atomicAdd(s + 1, (unsigned long long)__popcll(mask));
+    }
 }
 
 // top two of a set of (value, location): the best with its payload, and the highest value at another location
@@ -85,4 +120,30 @@ static __device__ __forceinline__ void ps_to_record(const PairState &s, double e
     r.inverted1 = none ? 0 : (uint8_t)(s.llo & 1u);
     r.state = none ? REAL_HIP_PAIR_NOMATCH : (s.second >= s.best - eps ? REAL_HIP_PAIR_NONUNIQUE : REAL_HIP_PAIR_UNIQUE);
     r.reserved = 0;
+}
+// the candidate made of a placement of mate 1 (pos1, score bits s1, k1 mismatches, inv1: reverse strand) and one of mate 2
+static __device__ __forceinline__ void ps_candidate(PairState &c, uint32_t scores, uint32_t fileid, uint32_t frag, uint32_t pos1, uint32_t pos2,
+                                                    uint32_t inv1, uint32_t s1, uint32_t s2, uint32_t k1, uint32_t k2)
+{
+    c.best = scores ? (double)__uint_as_float(s1) + (double)__uint_as_float(s2) : -(double)(k1 + k2);
+    c.second = pair_neg_inf();
+    c.lhi = ((uint64_t)fileid << 48) | ((uint64_t)frag << 32) | pos1;
+    c.llo = ((uint64_t)pos2 << 1) | inv1;
+    c.s1 = s1; c.s2 = s2; c.k = k1 | (k2 << 8);
+}
+// butterfly: every lane ends with the wave's state
+static __device__ __forceinline__ void ps_butterfly(PairState &st)
+{
+    for (int d = 32; d; d >>= 1) {
+        PairState o;
+        o.best = __shfl_xor(st.best, d); o.second = __shfl_xor(st.second, d);
+        o.lhi = __shfl_xor((unsigned long long)st.lhi, d); o.llo = __shfl_xor((unsigned long long)st.llo, d);
+        o.s1 = __shfl_xor(st.s1, d); o.s2 = __shfl_xor(st.s2, d); o.k = __shfl_xor(st.k, d);
+        ps_merge(st, o);
+    }
+}
+// the eps of a pair record (ps_to_record) of mates la and lb bases long
+static __device__ __forceinline__ double ps_eps(uint32_t scores, double filter_mult, uint32_t la, uint32_t lb)
+{
+    return scores ? (double)(float)(filter_mult * (double)((uint64_t)la + lb)) : 0.0;
 }

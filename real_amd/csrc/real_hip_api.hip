@@ -1,6 +1,7 @@
 // real_hip_api.hip -- the C ABI of include/real_hip.h: context, uploads, staging,
 // launches.  No CPU fallback: every entry point either runs the HIP path or fails.
 #include "real_hip_internal.h"
+#include "pair_state.h"
 
 #include <chrono>
 #include <cmath>
@@ -792,38 +793,84 @@ static int pair_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp)
     return REAL_HIP_OK;
 }
 
-// the two mates' hit lists of n fragments (lists = 1: one read's lists alone) as the caller holds them -> device views: the
-// offsets start at 0 and do not run backwards, off[n] is the number of hits; host lists are copied into the ctx's pair buffers
-static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *d_h[2], const uint64_t *d_o[2], uint64_t total[2], uint64_t n, bool on_device,
-                           int lists = 2)
+// the two mates' hit lists of n fragments (lists = 1: one read's lists alone) as the caller holds them -> the device view L:
+// the offsets start at 0 and do not run backwards, off[n] is the number of hits; host lists are copied into the ctx's pair
+// buffers, the read lengths with them (len: null for the mate search, which takes them from the batches)
+static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *const hits[2], const uint64_t *const off[2], const uint32_t *const len[2], uint64_t n,
+                           bool on_device, MateLists &L, int lists = 2)
 {
     int rc;
+    memset(&L, 0, sizeof L);
     for (int m = 0; m < lists; ++m) {
         if (on_device) {
             uint64_t ends[1] = {0}, first = 0;
-            RH_HIP(ctx, hipMemcpyAsync(&first, d_o[m], 8, hipMemcpyDeviceToHost, ctx->stream));
-            RH_HIP(ctx, hipMemcpyAsync(ends, d_o[m] + n, 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(&first, off[m], 8, hipMemcpyDeviceToHost, ctx->stream));
+            RH_HIP(ctx, hipMemcpyAsync(ends, off[m] + n, 8, hipMemcpyDeviceToHost, ctx->stream));
             RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
             if (first) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
-            total[m] = ends[0]; // (offsets in between are clamped to it by the kernels)
+            L.total[m] = ends[0]; // (offsets in between are clamped to it by the kernels)
         } else {
-            const uint64_t *o = d_o[m];
+            const uint64_t *o = off[m];
             if (o[0]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets must start at 0", hipSuccess);
             for (uint64_t i = 0; i < n; ++i)
                 if (o[i + 1] < o[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "hit offsets not monotone", hipSuccess);
-            total[m] = o[n];
+            L.total[m] = o[n];
         }
-        if (total[m] && !d_h[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
+        if (L.total[m] && !hits[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
+        L.h[m] = (const uint4 *)hits[m]; L.o[m] = off[m]; L.len[m] = len ? len[m] : nullptr;
     }
     if (on_device) return REAL_HIP_OK;
     for (int m = 0; m < lists; ++m) {
-        if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total[m] ? total[m] : 1) * sizeof(real_hip_hit)))) return rc;
+        const uint64_t total = L.total[m];
+        if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total ? total : 1) * sizeof(real_hip_hit)))) return rc;
         if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
-        if (total[m]) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, d_h[m], total[m] * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
-        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, d_o[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_h[m] = (const real_hip_hit *)ctx->pair_hits[m].p; d_o[m] = (const uint64_t *)ctx->pair_off[m].p;
+        if (total) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, hits[m], total * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
+        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, off[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        L.h[m] = (const uint4 *)ctx->pair_hits[m].p; L.o[m] = (const uint64_t *)ctx->pair_off[m].p;
+        if (!len) continue;
+        if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
+        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, len[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
+        L.len[m] = (const uint32_t *)ctx->pair_len[m].p;
     }
     ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
+    return REAL_HIP_OK;
+}
+// the lists match_mates leaves resident in the ctx's pair buffers
+static MateLists resident_lists(real_hip_ctx *ctx, const uint64_t total[2])
+{
+    MateLists L;
+    for (int m = 0; m < 2; ++m) {
+        L.h[m] = (const uint4 *)ctx->pair_hits[m].p; L.o[m] = (const uint64_t *)ctx->pair_off[m].p;
+        L.len[m] = (const uint32_t *)ctx->pair_len[m].p; L.total[m] = total[m];
+    }
+    return L;
+}
+
+// the in/out real_hip_pair records, staged in pair_rec when they are host memory
+static int stage_pairs(real_hip_ctx *ctx, real_hip_pair *pairs, uint64_t n, bool host_out, int fresh, real_hip_pair **d_pairs)
+{
+    *d_pairs = pairs;
+    if (!host_out) return REAL_HIP_OK;
+    int rc;
+    if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
+    *d_pairs = (real_hip_pair *)ctx->pair_rec.p;
+    if (!fresh) RH_HIP(ctx, hipMemcpyAsync(*d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
+    return REAL_HIP_OK;
+}
+static int download_pairs(real_hip_ctx *ctx, real_hip_pair *pairs, uint64_t n, const real_hip_pair *d_pairs)
+{
+    hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
+    return REAL_HIP_OK;
+}
+// the tail of a synchronous call: the stream is synchronised also behind an error (nothing of the caller's memory stays in
+// flight), and the call's own error is reported before the synchronisation's
+static int rh_sync_tail(real_hip_ctx *ctx, int rc)
+{
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
     return REAL_HIP_OK;
 }
 
@@ -839,32 +886,16 @@ extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params 
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     if (!off1 || !off2 || !len1 || !len2 || !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths / pairs", hipSuccess);
-    const real_hip_hit *d_h[2] = {hits1, hits2};
-    const uint64_t *d_o[2] = {off1, off2};
-    const uint32_t *d_l[2] = {len1, len2};
-    uint64_t total[2] = {0, 0};
-    real_hip_pair *d_pairs = pairs;
-    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0))) return rc;
-    if (!on_device) {
-        for (int m = 0; m < 2; ++m) {
-            if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, d_l[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
-        }
-        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
-        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
-        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = rh_launch_pair(ctx, *pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, fileid, fresh, d_pairs);
-    if (!rc && !on_device) {
-        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return REAL_HIP_OK;
+    const real_hip_hit *const hits[2] = {hits1, hits2};
+    const uint64_t *const off[2] = {off1, off2};
+    const uint32_t *const len[2] = {len1, len2};
+    MateLists L;
+    real_hip_pair *d_pairs;
+    if ((rc = stage_hit_lists(ctx, hits, off, len, n, on_device != 0, L))) return rc;
+    if ((rc = stage_pairs(ctx, pairs, n, !on_device, fresh, &d_pairs))) return rc;
+    rc = rh_launch_pair(ctx, *pp, L, n, fileid, fresh, d_pairs);
+    if (!rc && !on_device) rc = download_pairs(ctx, pairs, n, d_pairs);
+    return rh_sync_tail(ctx, rc);
 }
 
 // ---- mate search (mate_search.hip): what both of its entry points check before anything is launched
@@ -875,11 +906,19 @@ static int search_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp
         return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "mate search: max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
     return REAL_HIP_OK;
 }
-// the two mates' batches: equal in n_reads and on_device, no read longer than REAL_HIP_MAX_PATL
-static int search_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2])
+// the two mates' batches: equal in n_reads and on_device; need_index: they are to be matched, text and index are set
+static int mate_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2], bool need_index)
 {
     if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
     if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    if (need_index && (!ctx->have_text || !ctx->have_index)) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    return REAL_HIP_OK;
+}
+// what the mate search asks of them beyond that: no read longer than REAL_HIP_MAX_PATL
+static int search_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2])
+{
+    int rc = mate_batches_check(ctx, bv, false);
+    if (rc) return rc;
     const uint64_t n = bv[0].n_reads;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one batch", hipSuccess);
     for (int m = 0; m < 2 && n; ++m) {
@@ -891,7 +930,6 @@ static int search_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2])
                 if (b.offsets[i + 1] >= b.offsets[i] && b.offsets[i + 1] - b.offsets[i] > longest) longest = b.offsets[i + 1] - b.offsets[i];
         } else if (b.offsets) {
             uint32_t mp = b.max_patl; // (the declared bound; a read beyond it is caught by the kernel: E_INVALID)
-            int rc;
             if (!mp && (rc = rh_max_patl(ctx, b.offsets, n, &mp))) return rc;
             longest = mp;
         }
@@ -925,31 +963,20 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
     if (!n) return REAL_HIP_OK;
     if (!off1 || !off2 || !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / pairs", hipSuccess);
     const bool on_device = bv[0].on_device == 1;
-    const real_hip_hit *d_h[2] = {hits1, hits2};
-    const uint64_t *d_o[2] = {off1, off2};
-    uint64_t total[2] = {0, 0};
-    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device))) return rc;
+    const real_hip_hit *const hits[2] = {hits1, hits2};
+    const uint64_t *const off[2] = {off1, off2};
+    MateLists L;
+    if ((rc = stage_hit_lists(ctx, hits, off, nullptr, n, on_device, L))) return rc;
     Staged st[2];
     const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
     for (int m = 0; m < 2; ++m)
         if ((rc = stage_batch(ctx, bv[m], st[m], bufs[m], ctx->stream, nullptr, false))) return rc;
-    real_hip_pair *d_pairs = pairs;
-    if (!on_device) {
-        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
-        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
-        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), d_h[0], d_o[0], total[0], d_h[1], d_o[1], total[1],
-                               n, fileid, fresh, d_pairs);
-    if (!rc && !on_device) {
-        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
-    }
-    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return rh_mate_search_finish(ctx);
+    real_hip_pair *d_pairs;
+    if ((rc = stage_pairs(ctx, pairs, n, !on_device, fresh, &d_pairs))) return rc;
+    rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, fileid, fresh, d_pairs);
+    if (!rc && !on_device) rc = download_pairs(ctx, pairs, n, d_pairs);
+    rc = rh_sync_tail(ctx, rc);
+    return rc ? rc : rh_mate_search_finish(ctx);
 }
 
 // ---- single placements of a mate (single_fold.hip): the in/out records of `lists` lists, staged when they are host memory
@@ -988,26 +1015,17 @@ extern "C" int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits,
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
     if (!off || !len || !singles) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths / singles", hipSuccess);
-    const real_hip_hit *d_h[2] = {hits, nullptr};
-    const uint64_t *d_o[2] = {off, nullptr};
-    const uint32_t *d_l[2] = {len, nullptr};
-    uint64_t total[2] = {0, 0};
+    const real_hip_hit *const hv[2] = {hits, nullptr};
+    const uint64_t *const ov[2] = {off, nullptr};
+    const uint32_t *const lv[2] = {len, nullptr};
+    MateLists L;
     real_hip_single *const sv[2] = {singles, nullptr};
     real_hip_single *d_singles[2] = {nullptr, nullptr};
-    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0, 1))) return rc;
-    if (!on_device) {
-        if ((rc = rh_reserve(ctx, ctx->pair_len[0], n * 4))) return rc;
-        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[0].p, len, n * 4, hipMemcpyHostToDevice, ctx->stream));
-        d_l[0] = (const uint32_t *)ctx->pair_len[0].p;
-    }
+    if ((rc = stage_hit_lists(ctx, hv, ov, lv, n, on_device != 0, L, 1))) return rc;
     rc = stage_singles(ctx, 1, sv, n, !on_device, fresh, d_singles);
-    if (!rc) rc = rh_launch_single(ctx, 1, d_h, d_o, d_l, total, n, fileid, fresh, d_singles);
+    if (!rc) rc = rh_launch_single(ctx, 1, L, n, fileid, fresh, d_singles);
     if (!rc && !on_device) rc = download_singles(ctx, 1, sv, n, d_singles);
-    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return REAL_HIP_OK;
+    return rh_sync_tail(ctx, rc);
 }
 
 extern "C" int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stats *out, int reset)
@@ -1070,9 +1088,7 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
     int rc;
     real_hip_batch bv[2];
     if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
-    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
-    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
-    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    if ((rc = mate_batches_check(ctx, bv, true))) return rc;
     if (sp && (rc = search_batches_check(ctx, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
     if (!n) return REAL_HIP_OK;
@@ -1080,39 +1096,23 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
     Staged st[2];
     uint64_t total[2] = {0, 0};
     if ((rc = match_mates(ctx, bv, sp != nullptr, st, total))) return rc;
+    const MateLists L = resident_lists(ctx, total);
     const bool host_out = bv[0].on_device != 1;
-    real_hip_pair *d_pairs = pairs;
     const int fresh = bv[0].fresh != 0;
-    if (host_out) {
-        if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
-        d_pairs = (real_hip_pair *)ctx->pair_rec.p;
-        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
-    }
-    rc = rh_launch_pair(ctx, *pp, (const real_hip_hit *)ctx->pair_hits[0].p, (const uint64_t *)ctx->pair_off[0].p, (const uint32_t *)ctx->pair_len[0].p, total[0],
-                        (const real_hip_hit *)ctx->pair_hits[1].p, (const uint64_t *)ctx->pair_off[1].p, (const uint32_t *)ctx->pair_len[1].p, total[1],
-                        n, ctx->fileid, fresh, d_pairs);
+    real_hip_pair *d_pairs;
+    if ((rc = stage_pairs(ctx, pairs, n, host_out, fresh, &d_pairs))) return rc;
+    rc = rh_launch_pair(ctx, *pp, L, n, ctx->fileid, fresh, d_pairs);
     real_hip_single *d_singles[2] = {nullptr, nullptr};
     if (!rc && singles) { // seed hits only: the search below adds nothing to the lists
-        const real_hip_hit *d_h[2] = {(const real_hip_hit *)ctx->pair_hits[0].p, (const real_hip_hit *)ctx->pair_hits[1].p};
-        const uint64_t *d_o[2] = {(const uint64_t *)ctx->pair_off[0].p, (const uint64_t *)ctx->pair_off[1].p};
-        const uint32_t *d_l[2] = {(const uint32_t *)ctx->pair_len[0].p, (const uint32_t *)ctx->pair_len[1].p};
         rc = stage_singles(ctx, 2, singles, n, host_out, fresh, d_singles);
-        if (!rc) rc = rh_launch_single(ctx, 2, d_h, d_o, d_l, total, n, ctx->fileid, fresh, d_singles);
+        if (!rc) rc = rh_launch_single(ctx, 2, L, n, ctx->fileid, fresh, d_singles);
     }
     if (!rc && sp) // the records of the join are the search's in/out records
-        rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), (const real_hip_hit *)ctx->pair_hits[0].p,
-                                   (const uint64_t *)ctx->pair_off[0].p, total[0], (const real_hip_hit *)ctx->pair_hits[1].p,
-                                   (const uint64_t *)ctx->pair_off[1].p, total[1], n, ctx->fileid, 0, d_pairs);
-    if (!rc && host_out) {
-        hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
-    }
+        rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, ctx->fileid, 0, d_pairs);
+    if (!rc && host_out) rc = download_pairs(ctx, pairs, n, d_pairs);
     if (!rc && host_out && singles) rc = download_singles(ctx, 2, singles, n, d_singles);
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return sp ? rh_mate_search_finish(ctx) : REAL_HIP_OK;
+    rc = rh_sync_tail(ctx, rc);
+    return rc || !sp ? rc : rh_mate_search_finish(ctx);
 }
 
 extern "C" int real_hip_match_pairs(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
@@ -1161,8 +1161,7 @@ extern "C" int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *o
 
 // ---- every concordant pair of a fragment (pair_all.hip) -----------------------------------------------------------
 // count, then -- the total being known -- the overflow decision, then the records; dev_out: out / pair_offsets are device memory
-static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *const d_h[2], const uint64_t *const d_o[2],
-                        const uint32_t *const d_l[2], const uint64_t total[2], uint64_t n, uint32_t fileid, bool dev_out,
+static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, bool dev_out,
                         real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets)
 {
     int rc;
@@ -1172,7 +1171,7 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
         d_off = (uint64_t *)ctx->pa_off.p;
     }
     uint64_t found = 0;
-    rc = rh_pair_all_count(ctx, pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, d_off, &found);
+    rc = rh_pair_all_count(ctx, pp, L, n, d_off, &found);
     rh_time_resolve(ctx);
     if (rc) return rc;
     *n_out = found;
@@ -1182,18 +1181,14 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
         if ((rc = rh_reserve(ctx, ctx->pa_out, (found ? found : 1) * sizeof(real_hip_pair_hit)))) return rc;
         d_out = (real_hip_pair_hit *)ctx->pa_out.p;
     }
-    rc = rh_pair_all_emit(ctx, pp, d_h[0], d_o[0], d_l[0], total[0], d_h[1], d_o[1], d_l[1], total[1], n, fileid, d_off, d_out, dev_out ? cap : found, found);
+    rc = rh_pair_all_emit(ctx, pp, L, n, fileid, d_off, d_out, dev_out ? cap : found, found);
     if (!rc && !dev_out) {
         hipError_t e = hipSuccess;
         if (found) e = hipMemcpyAsync(out, d_out, found * sizeof(real_hip_pair_hit), hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess && pair_offsets) e = hipMemcpyAsync(pair_offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
         if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair hits", e);
     }
-    hipError_t e = hipStreamSynchronize(ctx->stream); // (also behind an error: nothing of the caller's memory stays in flight)
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return REAL_HIP_OK;
+    return rh_sync_tail(ctx, rc);
 }
 // what both entry points check of their outputs; n == 0 is answered here (*done)
 static int pair_all_outputs_check(real_hip_ctx *ctx, uint64_t n, bool dev_out, real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out,
@@ -1230,18 +1225,12 @@ extern "C" int real_hip_pair_all_hits(real_hip_ctx *ctx, const real_hip_pair_par
     bool done;
     if ((rc = pair_all_outputs_check(ctx, n, on_device != 0, out, cap, n_out, pair_offsets, &done)) || done) return rc;
     if (!off1 || !off2 || !len1 || !len2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths", hipSuccess);
-    const real_hip_hit *d_h[2] = {hits1, hits2};
-    const uint64_t *d_o[2] = {off1, off2};
-    const uint32_t *d_l[2] = {len1, len2};
-    uint64_t total[2] = {0, 0};
-    if ((rc = stage_hit_lists(ctx, d_h, d_o, total, n, on_device != 0))) return rc;
-    if (!on_device)
-        for (int m = 0; m < 2; ++m) {
-            if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, d_l[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_l[m] = (const uint32_t *)ctx->pair_len[m].p;
-        }
-    return pair_all_run(ctx, *pp, d_h, d_o, d_l, total, n, fileid, on_device != 0, out, cap, n_out, pair_offsets);
+    const real_hip_hit *const hits[2] = {hits1, hits2};
+    const uint64_t *const off[2] = {off1, off2};
+    const uint32_t *const len[2] = {len1, len2};
+    MateLists L;
+    if ((rc = stage_hit_lists(ctx, hits, off, len, n, on_device != 0, L))) return rc;
+    return pair_all_run(ctx, *pp, L, n, fileid, on_device != 0, out, cap, n_out, pair_offsets);
 }
 
 extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
@@ -1252,9 +1241,7 @@ extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch 
     if (rc) return rc;
     real_hip_batch bv[2];
     if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
-    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
-    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
-    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    if ((rc = mate_batches_check(ctx, bv, true))) return rc;
     const uint64_t n = bv[0].n_reads;
     const bool dev_out = bv[0].on_device == 1;
     bool done;
@@ -1262,10 +1249,7 @@ extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch 
     Staged st[2];
     uint64_t total[2] = {0, 0};
     if ((rc = match_mates(ctx, bv, false, st, total))) return rc;
-    const real_hip_hit *d_h[2] = {(const real_hip_hit *)ctx->pair_hits[0].p, (const real_hip_hit *)ctx->pair_hits[1].p};
-    const uint64_t *d_o[2] = {(const uint64_t *)ctx->pair_off[0].p, (const uint64_t *)ctx->pair_off[1].p};
-    const uint32_t *d_l[2] = {(const uint32_t *)ctx->pair_len[0].p, (const uint32_t *)ctx->pair_len[1].p};
-    return pair_all_run(ctx, *pp, d_h, d_o, d_l, total, n, ctx->fileid, dev_out, out, cap, n_out, pair_offsets);
+    return pair_all_run(ctx, *pp, resident_lists(ctx, total), n, ctx->fileid, dev_out, out, cap, n_out, pair_offsets);
 }
 
 extern "C" int real_hip_pair_all_stats_get(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset)
@@ -1306,16 +1290,35 @@ extern "C" int real_hip_download(real_hip_ctx *ctx, const void *device_ptr, void
 // ---------------------------------------------------------------------------
 // counters / timing
 // ---------------------------------------------------------------------------
+int rh_stats_reserve(real_hip_ctx *ctx, DevBuf &buf, size_t stripes, size_t extra_bytes)
+{
+    if (buf.p) return REAL_HIP_OK;
+    const size_t bytes = stripes * 16 * 8 + extra_bytes;
+    int rc = rh_reserve(ctx, buf, bytes);
+    if (rc) return rc;
+    RH_HIP(ctx, hipMemsetAsync(buf.p, 0, bytes, ctx->stream));
+    return REAL_HIP_OK;
+}
+
+int rh_stats_read(real_hip_ctx *ctx, const DevBuf &buf, size_t stripes, int n_words, int reset, uint64_t out[])
+{
+    for (int k = 0; k < n_words; ++k) out[k] = 0;
+    if (!buf.p) return REAL_HIP_OK;
+    std::vector<uint64_t> all(stripes * 16);
+    RH_HIP(ctx, hipMemcpyAsync(all.data(), buf.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (reset) RH_HIP(ctx, hipMemsetAsync(buf.p, 0, all.size() * 8, ctx->stream));
+    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t st = 0; st < stripes; ++st)
+        for (int k = 0; k < n_words; ++k) out[k] += all[st * 16 + k];
+    return REAL_HIP_OK;
+}
+
 extern "C" int real_hip_counters_get(real_hip_ctx *ctx, real_hip_counters *out, int reset)
 {
     RH_ENTER(ctx);
-    std::vector<uint64_t> all((size_t)RH_CSTRIPES * 16);
-    RH_HIP(ctx, hipMemcpyAsync(all.data(), ctx->counters.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    if (reset) RH_HIP(ctx, hipMemsetAsync(ctx->counters.p, 0, all.size() * 8, ctx->stream));
-    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    uint64_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (size_t st = 0; st < RH_CSTRIPES; ++st)
-        for (int k = 0; k < 8; ++k) h[k] += all[st * 16 + k];
+    uint64_t h[8];
+    int rc;
+    if ((rc = rh_stats_read(ctx, ctx->counters, RH_CSTRIPES, 8, reset, h))) return rc; // (not the scratch stripe behind them)
     if (out) {
         out->reads = h[0]; out->lookups = h[1]; out->probes = h[2]; out->candidates = h[3];
         out->seedpass = h[4]; out->hits = h[5]; out->verified = h[6]; out->handed_over = h[7];

@@ -326,37 +326,41 @@ int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int 
 int rh_all_finish(real_hip_ctx *ctx, uint64_t n_raw, uint64_t n_reads, real_hip_hit *d_out,
                   uint64_t *d_hit_offsets);
 
+// ---- what the paired-end stages share ---------------------------------------------
+struct MateLists; // the two mates' hit lists on the device (pair_state.h)
+// a fixed grid of waves (four per block) takes `work` items in turn: the number of handed-over fragments stays on the
+// device, and what a block loads once (the mate search's score table) is loaded at most this often
+static inline unsigned rh_wave_blocks(uint64_t work) { return (unsigned)((work + 3) / 4 < 2048 ? (work + 3) / 4 : 2048); }
+// striped statistics: `stripes` 128-byte lines of 16 words, summed on the host (see RH_CSTRIPES), with extra_bytes behind
+// them.  rh_stats_reserve allocates and zeroes the buffer on first use; rh_stats_read sums words 0 .. n_words - 1 over the
+// stripes into out[] (zeros while there is no buffer), clears the stripes if `reset`, and synchronises the stream
+int rh_stats_reserve(real_hip_ctx *ctx, DevBuf &buf, size_t stripes, size_t extra_bytes);
+int rh_stats_read(real_hip_ctx *ctx, const DevBuf &buf, size_t stripes, int n_words, int reset, uint64_t out[]);
+
 // ---- paired-end join (pair_kernel.hip) ------------------------------------------
 int rh_pair_lens(real_hip_ctx *ctx, const uint64_t *d_off, uint32_t upatl, uint64_t n, uint32_t *d_len);
-int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                   uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                   uint32_t fileid, int fresh, real_hip_pair *d_pairs);
+int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
 int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
 
 // ---- mate search (mate_search.hip) ----------------------------------------------
 #define RH_K_MATE_SEARCH (-1) /* rh_time_begin: the time goes to ctx->ms_kernel_ms (REAL_HIP_K_COUNT is part of the ABI) */
 // asynchronous on the ctx's stream; after the stream was synchronised rh_mate_search_finish reports what the kernel flagged
 int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_mate_search_params &sp, const DevBatch &b1,
-                          const DevBatch &b2, const real_hip_hit *d_h1, const uint64_t *d_o1, uint64_t total1, const real_hip_hit *d_h2,
-                          const uint64_t *d_o2, uint64_t total2, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
+                          const DevBatch &b2, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
 int rh_mate_search_finish(real_hip_ctx *ctx);
 int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
 
 // ---- every concordant pair of a fragment (pair_all.hip) ---------------------------
 #define RH_K_PAIR_ALL (-2) /* rh_time_begin: the time goes to ctx->pa_kernel_ms */
 // count + scan into d_off (n + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
-int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                      uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                      uint64_t *d_off, uint64_t *total);
-int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_hit *d_h1, const uint64_t *d_o1, const uint32_t *d_len1,
-                     uint64_t total1, const real_hip_hit *d_h2, const uint64_t *d_o2, const uint32_t *d_len2, uint64_t total2, uint64_t n,
-                     uint32_t fileid, const uint64_t *d_off, real_hip_pair_hit *d_out, uint64_t cap, uint64_t total);
+int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint64_t *d_off, uint64_t *total);
+int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, const uint64_t *d_off,
+                     real_hip_pair_hit *d_out, uint64_t cap, uint64_t total);
 int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
 
 // ---- single placements of a mate (single_fold.hip) ---------------------------------
 #define RH_K_SINGLE (-3) /* rh_time_begin: the time goes to ctx->sg_kernel_ms */
-int rh_launch_single(real_hip_ctx *ctx, int lists, const real_hip_hit *const d_h[2], const uint64_t *const d_o[2], const uint32_t *const d_len[2],
-                     const uint64_t total[2], uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
+int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
 int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------

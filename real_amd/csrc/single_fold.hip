@@ -12,11 +12,9 @@
 #include "single_state.h"
 
 struct SingleArgs {
-    const uint4 *h0, *h1;          // real_hip_hit records of list 0 / list 1
-    const uint64_t *o0, *o1;       // n + 1 offsets into them
-    const uint32_t *len0, *len1;   // read lengths
-    uint4 *out0, *out1;            // real_hip_single records, in/out
-    uint64_t n, total0, total1;    // reads per list; an upper bound of the hits inside h0 / h1 (the offsets are clamped to it, pair_range)
+    MateLists L;                   // the hit lists of list 0 / list 1 (pair_state.h)
+    uint4 *out[2];                 // real_hip_single records, in/out
+    uint64_t n;                    // reads per list
     unsigned long long *list;      // reads handed to the wave kernel: list << 32 | read
     unsigned long long *list_count;
     unsigned long long *stats;     // RH_PAIR_STRIPES x 16 words: [0] hits walked, [1] handed over
@@ -31,15 +29,15 @@ static __device__ __forceinline__ double single_eps(const SingleArgs &A, uint32_
 
 __global__ void __launch_bounds__(256) single_lane_kernel(const SingleArgs A)
 {
-    const uint32_t m = blockIdx.y; // (uniform: the selects below are scalar)
-    const uint4 *h = m ? A.h1 : A.h0;
-    const uint64_t *o = m ? A.o1 : A.o0;
-    uint4 *out = m ? A.out1 : A.out0;
-    const uint64_t total = m ? A.total1 : A.total0;
+    // (uniform.  The list is picked by selects between the two constant slots, which sit in scalar registers: A.L.h[m] is a
+    // load from the argument segment in every wave, and the fold's kernels measured about 1 % slower with it)
+    const uint32_t m = blockIdx.y;
+    const uint4 *h = m ? A.L.h[1] : A.L.h[0];
+    uint4 *out = m ? A.out[1] : A.out[0];
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < A.n;
     uint64_t lo = 0, hi = 0;
-    if (live) pair_range(o, i, total, lo, hi);
+    if (live) { if (m) A.L.range(1, i, lo, hi); else A.L.range(0, i, lo, hi); }
     unsigned long long cnt = hi - lo;
     const bool big = cnt > RH_SINGLE_LANE_BUDGET;
     if (live && !big) {
@@ -51,24 +49,9 @@ __global__ void __launch_bounds__(256) single_lane_kernel(const SingleArgs A)
             ss_from_hit(c, h[x], A.fileid, A.scores);
             ss_merge(st, c);
         }
-        out[i] = ss_to_record(st, single_eps(A, (m ? A.len1 : A.len0)[i]));
+        out[i] = ss_to_record(st, single_eps(A, (m ? A.L.len[1] : A.L.len[0])[i]));
     }
-    // hand-over list (one atomic per wave) and statistics (one stripe per block)
-    const unsigned long long mask = __ballot(live && big);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (mask) {
-        unsigned long long base = 0;
-        const int leader = __ffsll((long long)mask) - 1;
-        if ((int)lane == leader) base = atomicAdd(A.list_count, (unsigned long long)__popcll(mask));
-        base = __shfl(base, leader);
-        if (live && big) A.list[base + __popcll(mask & ((1ull << lane) - 1ull))] = ((unsigned long long)m << 32) | i;
-    }
-    for (int d = 32; d; d >>= 1) cnt += __shfl_xor(cnt, d);
-    if (lane == 0) {
-        unsigned long long *s = A.stats + (size_t)((blockIdx.x + blockIdx.y) % RH_PAIR_STRIPES) * 16;
-        if (cnt) atomicAdd(s, cnt);
-        if (mask) atomicAdd(s + 1, (unsigned long long)__popcll(mask));
-    }
+    pair_hand_over(live && big, ((unsigned long long)m << 32) | i, cnt, blockIdx.x + blockIdx.y, A.list, A.list_count, A.stats);
 }
 
 __global__ void __launch_bounds__(256) single_wave_kernel(const SingleArgs A)
@@ -80,10 +63,10 @@ __global__ void __launch_bounds__(256) single_wave_kernel(const SingleArgs A)
         const unsigned long long e = A.list[w];
         const uint32_t m = (uint32_t)(e >> 32);
         const uint64_t i = e & 0xffffffffull;
-        const uint4 *h = m ? A.h1 : A.h0;
-        uint4 *out = m ? A.out1 : A.out0;
+        const uint4 *h = m ? A.L.h[1] : A.L.h[0];
+        uint4 *out = m ? A.out[1] : A.out[0];
         uint64_t lo, hi;
-        pair_range(m ? A.o1 : A.o0, i, m ? A.total1 : A.total0, lo, hi);
+        if (m) A.L.range(1, i, lo, hi); else A.L.range(0, i, lo, hi);
         SingleState st;
         ss_clear(st);
         for (uint64_t x = lo + lane; x < hi; x += 64) {
@@ -100,28 +83,25 @@ __global__ void __launch_bounds__(256) single_wave_kernel(const SingleArgs A)
         }
         if (lane == 0) {
             if (!A.fresh) { SingleState in; ss_from_record(in, out[i], A.scores); ss_merge(st, in); }
-            out[i] = ss_to_record(st, single_eps(A, (m ? A.len1 : A.len0)[i]));
+            out[i] = ss_to_record(st, single_eps(A, (m ? A.L.len[1] : A.L.len[0])[i]));
         }
     }
 }
 
 // the fold of n reads of each of `lists` (1 or 2) lists on device arrays; asynchronous on the ctx's stream
-int rh_launch_single(real_hip_ctx *ctx, int lists, const real_hip_hit *const d_h[2], const uint64_t *const d_o[2], const uint32_t *const d_len[2],
-                     const uint64_t total[2], uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2])
+int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2])
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
     int rc;
-    if (!ctx->sg_stats.p) {
-        if ((rc = rh_reserve(ctx, ctx->sg_stats, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
-        RH_HIP(ctx, hipMemsetAsync(ctx->sg_stats.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
-    }
+    if ((rc = rh_stats_reserve(ctx, ctx->sg_stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, ctx->sg_list, (size_t)lists * n * 8 + 8))) return rc;
     const int l1 = lists > 1 ? 1 : 0; // (one list: both slots describe it, slot 1 is never selected)
     SingleArgs A;
-    A.h0 = (const uint4 *)d_h[0]; A.h1 = (const uint4 *)d_h[l1]; A.o0 = d_o[0]; A.o1 = d_o[l1]; A.len0 = d_len[0]; A.len1 = d_len[l1];
-    A.out0 = (uint4 *)d_out[0]; A.out1 = (uint4 *)d_out[l1];
-    A.n = n; A.total0 = total[0]; A.total1 = total[l1];
+    A.L = L;
+    A.L.h[1] = L.h[l1]; A.L.o[1] = L.o[l1]; A.L.len[1] = L.len[l1]; A.L.total[1] = L.total[l1];
+    A.out[0] = (uint4 *)d_out[0]; A.out[1] = (uint4 *)d_out[l1];
+    A.n = n;
     A.list_count = (unsigned long long *)ctx->sg_list.p; A.list = (unsigned long long *)ctx->sg_list.p + 1;
     A.stats = (unsigned long long *)ctx->sg_stats.p;
     A.filter_mult = ctx->prm.filter_mult;
@@ -132,8 +112,7 @@ int rh_launch_single(real_hip_ctx *ctx, int lists, const real_hip_hit *const d_h
     RH_HIP(ctx, hipGetLastError());
     // a fixed grid of waves takes the handed-over reads in turn (their number stays on the device)
     const uint64_t work = (uint64_t)lists * n;
-    const uint64_t blocks = (work + 3) / 4 < 2048 ? (work + 3) / 4 : 2048;
-    hipLaunchKernelGGL(single_wave_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, A);
+    hipLaunchKernelGGL(single_wave_kernel, dim3(rh_wave_blocks(work)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
     ctx->sg_reads += work;
@@ -143,14 +122,9 @@ int rh_launch_single(real_hip_ctx *ctx, int lists, const real_hip_hit *const d_h
 
 int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset)
 {
-    uint64_t h[2] = {0, 0};
-    if (ctx->sg_stats.p) {
-        std::vector<uint64_t> all((size_t)RH_PAIR_STRIPES * 16);
-        RH_HIP(ctx, hipMemcpyAsync(all.data(), ctx->sg_stats.p, all.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (reset) RH_HIP(ctx, hipMemsetAsync(ctx->sg_stats.p, 0, all.size() * 8, ctx->stream));
-        RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        for (size_t st = 0; st < RH_PAIR_STRIPES; ++st) { h[0] += all[st * 16]; h[1] += all[st * 16 + 1]; }
-    }
+    uint64_t h[2];
+    int rc;
+    if ((rc = rh_stats_read(ctx, ctx->sg_stats, RH_PAIR_STRIPES, 2, reset, h))) return rc;
     rh_time_resolve(ctx);
     if (out) {
         out->reserved = 0;
