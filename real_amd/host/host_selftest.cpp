@@ -7,6 +7,7 @@
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
+//   host_selftest lines <reads.fq> <outdir>       -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,6 +17,7 @@
 #include "FastFormat.hpp"
 #include "GenomeText.hpp"
 #include "HostIndex.hpp"
+#include "Lines.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "row_addr.h"
@@ -189,6 +191,46 @@ int main(int argc, char **argv)
             }
             std::cout << (bad ? "bad " : "ok ") << bad << std::endl;
             return bad ? 1 : 0;
+        }
+        if (cmd == "lines" && argc == 4) {
+            // Every read of a one-line-per-field FASTQ file formatted twice (Lines.hpp): from the host reader's blocks, and
+            // from the file as one text chunk whose spans a newline scan finds here.  The placement of read r is a fixed
+            // function of r (tests/test_host_cpp.py states it again): both strands, scores on and off, positions up to
+            // 2^35 - 1, errors 0..15, a fragment name with a leading space.
+            const std::string d = argv[3];
+            const std::string names[3] = {" chr one", "two", " 3"};
+            auto line = [&](const ReadSource &src, uint64_t first, uint64_t i, std::string &s) {
+                const uint64_t r = first + i;
+                uint64_t pos1 = (r * 0x9E3779B97F4A7C15ull) >> 29;
+                if (r == 0) pos1 = (1ull << 35) - 1;
+                if (r == 1) pos1 = 1;
+                appendLine(s, src[i], r % 3 != 2, Placement{(float)((int64_t)(r * 7919 % 100003) - 50000) / 16.0f, (r & 1) != 0, names[r % 3], pos1, (unsigned)(r % 16)});
+            };
+            Timers T;
+            FILE *fb = fopen((d + "/block.tsv").c_str(), "wb"), *fc = fopen((d + "/chunk.tsv").c_str(), "wb");
+            if (!fb || !fc) return 1;
+            ReadReader rr(argv[2], true, ReadReader::getOffset(argv[2]));
+            ReadBlock b;
+            const ReadSource blocks(b);
+            while (rr.fillBlock(b, 7, true)) // tiny blocks: most of the thread ranges are empty
+                formatAndWrite(blocks.size(), fb, T, [&](uint64_t i, std::string &s) { line(blocks, b.first_id, i, s); });
+            std::ifstream in(argv[2], std::ios::binary);
+            std::string text((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            Chunk c;
+            c.text = &text[0]; c.cap = c.size = text.size();
+            Spans sp;
+            sp.off.push_back(0);
+            for (size_t at = 0, ln = 0; at < text.size(); ++ln) { // line 4k: '@' id, line 4k + 1: the sequence; a '\r' belongs to neither
+                size_t nl = text.find('\n', at);
+                if (nl == std::string::npos) nl = text.size();
+                const size_t len = nl - at - (nl > at && text[nl - 1] == '\r' ? 1 : 0);
+                if (ln % 4 == 0) { sp.id_start.push_back((uint32_t)at + 1); sp.id_len.push_back((uint32_t)len - 1); }
+                if (ln % 4 == 1) sp.off.push_back(sp.off.back() + len);
+                at = nl + 1;
+            }
+            const ReadSource chunk(c, sp);
+            formatAndWrite(chunk.size(), fc, T, [&](uint64_t i, std::string &s) { line(chunk, 0, i, s); });
+            return (fclose(fb) == 0) & (fclose(fc) == 0) ? 0 : 1;
         }
         if (cmd == "options") {
             RealOptions o(argc - 1, argv + 1);

@@ -14,14 +14,15 @@
 // its cores and writes them with large sequential writes.  A file (or a later part of one) that is not in
 // one-line-per-field form is read by the host reader from that record on.
 //
+// Here: what the four drivers share (genomePass, streamReads, OutFile, fillMates) and the drivers.  Each formats through
+// one lambda -- read i of a ReadSource and a Placement, whatever parsed the read (Lines.hpp: all about the lines).
+//
 // Deliberate differences from reference quirks (SURVEY 8a "quirks"): matchAll handles FASTQ input
 // (quirk 1) and writes every line (quirk 2); the exit status is non-zero on errors (quirk 6).
 #include <fcntl.h>
-#include <omp.h>
 #include <unistd.h>
 
 #include <cfloat>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,27 +34,14 @@
 #include <thread>
 #include <vector>
 
-#include "FastFormat.hpp"
 #include "GenomeText.hpp"
 #include "HostIndex.hpp"
+#include "Lines.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "real_hip.h"
 
 namespace {
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-// where the wall time went; printed as one "timing:" line on stderr at the end (bench_support/cli_midsize.py reads it)
-struct Timers {
-    double genome = 0, index = 0, read = 0, parse = 0, match = 0, format = 0, write = 0, total = 0;
-    uint64_t reads = 0, lines = 0, out_bytes = 0;
-    void print() const
-    {
-        fprintf(stderr, "timing: genome_load_s=%.3f index_s=%.3f read_file_s=%.3f parse_s=%.3f match_s=%.3f format_s=%.3f write_s=%.3f total_s=%.3f reads=%llu lines=%llu out_bytes=%llu\n",
-                genome, index, read, parse, match, format, write, total, (unsigned long long)reads, (unsigned long long)lines, (unsigned long long)out_bytes);
-    }
-};
 
 struct Ctx {
     real_hip_ctx *h = nullptr;
@@ -120,110 +108,52 @@ uint64_t blockEntries(const RealOptions &o, real_hip_ctx *h, uint64_t windows)
 
 struct Ranges { std::vector<std::vector<std::string>> names; std::vector<std::vector<uint64_t>> starts; };
 
-// ---- output lines (printMatchUnlocked, matchUniqueImplementation.cpp:252-321) --------------------------
-// id \t sequence as matched \t score|"" \t 1 \t a \t patl \t +|- \t fragment name \t 1-based position \t "" \t errors \n
-// Written straight into the thread's buffer: table lookups for the sequence, hand-rolled decimal numbers, and the score by
-// fastformat::fmt_g6 -- the digits of printf's %g, which is what operator<<(float) prints, from integer arithmetic.
-struct SeqTables {
-    char fwd[256], rc[256], map_fwd[5], map_rc[5];
-    SeqTables()
+// the quality offset of a FASTQ read file: -Q, or detected from the file (0 for FASTA)
+int qualityOffset(const RealOptions &o, bool fastq, const std::string &filename)
+{
+    if (!fastq) return 0;
+    const int qoff = o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(filename);
+    if (!qoff) throw std::runtime_error("Unable to automatically detect FastQ quality format."); // :1112
+    return qoff;
+}
+
+// the genome files of -t; too_many: the error for more than 64 of them where the records hold a file id of 6 bits
+std::vector<std::string> genomeFiles(const RealOptions &o, const char *too_many)
+{
+    std::vector<std::string> files;
+    getFileList(o.textfilename, files);
+    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
+    if (too_many && files.size() > 64) throw std::runtime_error(too_many);
+    return files;
+}
+
+// An output file behind a buffer of 8 MiB ("-": standard output; the -unpaired file is always a file).  close() is the
+// regular end.  The destructor is the way out through an exception: what the buffer holds is written while the buffer
+// still exists, so lines formatted before an error reach the file.  (Standard output keeps pointing at the buffer, empty
+// from then on: nothing is written to it behind the drivers.)
+class OutFile {
+public:
+    explicit OutFile(const std::string &filename, bool unpaired = false) : unpaired_(unpaired), buf_((size_t)8 << 20)
     {
-        for (int c = 0; c < 256; ++c) { fwd[c] = 'N'; rc[c] = 'N'; }   // anything but ACGT (lowercase too) maps to 4 and prints as N
-        fwd['A'] = 'A'; fwd['C'] = 'C'; fwd['G'] = 'G'; fwd['T'] = 'T';
-        rc['A'] = 'T'; rc['C'] = 'G'; rc['G'] = 'C'; rc['T'] = 'A';
-        memcpy(map_fwd, "ACGTN", 5); memcpy(map_rc, "TGCAN", 5);       // remapChar, acgtnMap.hpp:24-35; transposed: 3 - c
+        f_ = (!unpaired && filename == "-") ? stdout : fopen(filename.c_str(), "wb");
+        if (!f_) throw std::runtime_error((unpaired ? "cannot open the -unpaired file " : "cannot open output file ") + filename);
+        setvbuf(f_, buf_.data(), _IOFBF, buf_.size());
     }
+    ~OutFile() { if (f_ == stdout) fflush(f_); else if (f_) fclose(f_); }
+    OutFile(const OutFile &) = delete;
+    OutFile &operator=(const OutFile &) = delete;
+    FILE *file() const { return f_; }
+    void close()
+    {
+        if (fflush(f_) != 0) throw std::runtime_error(unpaired_ ? "write to the -unpaired file failed" : "write to the output file failed");
+        if (f_ != stdout) fclose(f_);
+        f_ = nullptr;
+    }
+private:
+    bool unpaired_;
+    std::vector<char> buf_;
+    FILE *f_;
 };
-const SeqTables kSeq;
-
-inline char *putUint(char *p, uint64_t v)
-{
-    char tmp[24];
-    int n = 0;
-    do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-    while (n) *p++ = tmp[--n];
-    return p;
-}
-// room for one line behind the current end of out; returns the write position
-inline char *lineRoom(std::string &out, size_t bytes)
-{
-    const size_t at = out.size();
-    if (out.capacity() < at + bytes) out.reserve(std::max(out.capacity() * 2, at + bytes));
-    out.resize(at + bytes);
-    return &out[at];
-}
-inline char *putTail(char *p, bool scores, float score, uint64_t patl, bool inverted, const std::string &fragname, uint64_t pos1, unsigned errors)
-{
-    *p++ = '\t';
-    if (scores) p += fastformat::fmt_g6(score, p); // operator<<(float): %g, six significant digits
-    memcpy(p, "\t1\ta\t", 5); p += 5;
-    p = putUint(p, patl);
-    *p++ = '\t'; *p++ = inverted ? '-' : '+'; *p++ = '\t';
-    memcpy(p, fragname.data(), fragname.size()); p += fragname.size();
-    *p++ = '\t';
-    p = putUint(p, pos1);
-    *p++ = '\t'; *p++ = '\t';
-    p = putUint(p, errors);
-    *p++ = '\n';
-    return p;
-}
-// one line; the sequence column from the characters of the read file (seq_text) or from mapped symbols (seq_mapped)
-inline void appendLine(std::string &out, const char *id, size_t idlen, const char *seq_text, const uint8_t *seq_mapped, uint64_t patl, bool scores,
-                       float score, bool inverted, const std::string &fragname, uint64_t pos1, unsigned errors)
-{
-    const size_t at = out.size();
-    char *p = lineRoom(out, idlen + patl + fragname.size() + 112), *p0 = p;
-    memcpy(p, id, idlen); p += idlen;
-    *p++ = '\t';
-    if (seq_text) {
-        if (!inverted) for (uint64_t i = 0; i < patl; ++i) p[i] = kSeq.fwd[(unsigned char)seq_text[i]];
-        else for (uint64_t i = 0; i < patl; ++i) p[i] = kSeq.rc[(unsigned char)seq_text[patl - 1 - i]];
-    } else {
-        if (!inverted) for (uint64_t i = 0; i < patl; ++i) p[i] = kSeq.map_fwd[seq_mapped[i] < 4 ? seq_mapped[i] : 4];
-        else for (uint64_t i = 0; i < patl; ++i) { const uint8_t c = seq_mapped[patl - 1 - i]; p[i] = kSeq.map_rc[c < 4 ? c : 4]; }
-    }
-    p += patl;
-    p = putTail(p, scores, score, patl, inverted, fragname, pos1, errors);
-    out.resize(at + (size_t)(p - p0));
-}
-
-struct Record { unsigned st, frag, errors, file; uint64_t pos; };
-inline Record unpack(uint64_t rec)
-{
-    Record r;
-    r.st = (unsigned)(rec >> 61); r.frag = (rec >> 45) & 0xffff; r.errors = (rec >> 41) & 15; r.file = (rec >> 35) & 63; r.pos = rec & ((1ull << 35) - 1);
-    return r;
-}
-
-// The lines of reads [0, n) of one block, formatted by all host threads (each a contiguous range of reads into its
-// own buffer) and written in read order with one large write per buffer.  line(i, out) appends read i's line(s).
-struct alignas(128) LineBuf { std::string s; }; // (a cache line pair of its own: the threads update their string's length line by line)
-
-template <class LineFn>
-void formatAndWrite(uint64_t n, FILE *out, Timers &T, LineFn line)
-{
-    const int nt = std::max(1, omp_get_max_threads());
-    static std::vector<LineBuf> buf; // (kept across calls: the pages of a buffer are touched once, not once per block)
-    if ((int)buf.size() < nt) buf = std::vector<LineBuf>((size_t)nt);
-    const double t0 = now_s();
-#pragma omp parallel num_threads(nt)
-    {
-        const int t = omp_get_thread_num();
-        const uint64_t lo = n * (uint64_t)t / nt, hi = n * (uint64_t)(t + 1) / nt;
-        std::string b;
-        b.swap(buf[(size_t)t].s); // (worked on as a local: its length and pointer live in registers / this thread's stack)
-        b.clear();
-        for (uint64_t i = lo; i < hi; ++i) line(i, b);
-        b.swap(buf[(size_t)t].s);
-    }
-    const double t1 = now_s();
-    for (int t = 0; t < nt; ++t) {
-        const std::string &b = buf[(size_t)t].s;
-        if (!b.empty() && fwrite(b.data(), 1, b.size(), out) != b.size()) throw std::runtime_error("write to the output file failed");
-        T.out_bytes += b.size();
-    }
-    T.format += t1 - t0; T.write += now_s() - t1;
-}
 
 // text + one index block on every device
 struct Resident {
@@ -269,17 +199,45 @@ uint64_t nextBlock(const RealOptions &o, CtxVec &ctx, Resident &R, uint64_t firs
     return n;
 }
 
+// ---- one genome file -----------------------------------------------------------------------------------
+// Genome file fi announced (kSayLast: with the note on the last one), loaded, its text put on every device and its index
+// blocks made resident one after the other: onBlock(R) runs with each of them.  kOneBlock: paired-end reads, whose pairs
+// across two blocks would be lost -- a file that needs a second block is refused.  RS, where given, collects the
+// fragments of all files for the output behind the last one.
+enum { kSayLast = 1, kOneBlock = 2 };
+template <class OnBlock>
+void genomePass(const RealOptions &o, CtxVec &ctx, const std::vector<std::string> &files, unsigned fi, int how, Timers &T, Ranges *RS, OnBlock onBlock)
+{
+    std::cerr << "Processing file " << files[fi] << (((how & kSayLast) && fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
+    Resident R;
+    double t0 = now_s();
+    R.G.load(files[fi]);
+    T.genome += now_s() - t0;
+    if (RS) { RS->names.push_back(R.G.frag_names); RS->starts.push_back(R.G.frag_start); }
+    t0 = now_s();
+    setText(o, ctx, R, fi);
+    T.index += now_s() - t0;
+    const uint64_t n_list = blockEntries(o, ctx[0]->h, R.G.sym.size() ? R.G.sym.size() : 1);
+    uint64_t first = 0;
+    bool have_next = true;
+    while (have_next) {
+        t0 = now_s();
+        const uint64_t n = nextBlock(o, ctx, R, first, n_list, have_next);
+        T.index += now_s() - t0;
+        if ((how & kOneBlock) && have_next)
+            throw std::runtime_error("paired-end reads: " + files[fi] + " needs more than one index block (pairs across blocks would be lost); "
+                                     "raise -f / -block or split the file");
+        if (!n) break;
+        first += n;
+        onBlock(R);
+    }
+}
+
 // ---- the read file as text chunks ----------------------------------------------------------------------
 // Chunks of whole records for real_hip_parse_reads: a chunk ends behind a newline whose index is a multiple of the
 // lines per record (4 FASTQ, 2 FASTA) -- only text in one-line-per-field form parses, and only for such text the cuts
 // are record boundaries.  Buffers are pinned (real_hip_host_alloc): they cross PCIe by DMA.  The next chunk is read by
 // a prefetch thread while the devices work on the current ones.
-struct Chunk {
-    char *text = nullptr;
-    size_t cap = 0, size = 0;
-    uint64_t file_offset = 0; // of text[0]
-};
-
 class RawChunker {
 public:
     RawChunker(const std::string &fn, bool fastq, size_t chunk_bytes, size_t n_buffers) : lpr_(fastq ? 4 : 2)
@@ -420,16 +378,39 @@ real_hip_batch makeBatch(const real_hip_parsed &p)
     return rb;
 }
 
-// One pass over the read file.  Rounds of up to one chunk per context: parsed on the devices, then onChunks(first_id,
-// chunks, parsed) sees them (in file order).  From the first chunk a device parser refuses (text not in one-line-per-
-// field form) the host reader takes over at that record: onBlocks(blocks) sees rounds of host-parsed blocks.  A file
-// that is refused from its first chunk on -- or -gpuparse 0 -- is read by the host reader alone.
+// One round's share of one context: its reads as a batch for the matcher and, in a pass that wants the ids, as the
+// source of the formatter.
+struct ReadItem {
+    uint64_t first_id;
+    real_hip_batch batch;
+    ReadSource src;
+};
+
+// what the device parser found in a chunk, for the formatter
+void downloadSpans(real_hip_ctx *h, const real_hip_parsed &p, Spans &sp, Timers &T)
+{
+    const uint64_t n = p.n_reads;
+    sp.id_start.resize(n); sp.id_len.resize(n); sp.off.resize(n + 1);
+    if (!n) return;
+    const double t0 = now_s();
+    check(h, real_hip_download(h, p.id_start, sp.id_start.data(), n * 4), "real_hip_download");
+    check(h, real_hip_download(h, p.id_len, sp.id_len.data(), n * 4), "real_hip_download");
+    check(h, real_hip_download(h, p.offsets, sp.off.data(), (n + 1) * 8), "real_hip_download");
+    T.parse += now_s() - t0;
+}
+
+// One pass over the read file.  Rounds of up to one chunk per context: parsed on the devices, then onRound(items) sees
+// them (in file order, item g on context g).  From the first chunk a device parser refuses (text not in one-line-per-
+// field form) the host reader takes over at that record: onRound sees rounds of host-parsed blocks.  A file that is
+// refused from its first chunk on -- or -gpuparse 0 -- is read by the host reader alone.
 // Returns the number of reads seen.
-template <class OnChunks, class OnBlocks>
-uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids, Timers &T, OnChunks onChunks, OnBlocks onBlocks)
+template <class OnRound>
+uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids, Timers &T, OnRound onRound)
 {
     uint64_t next_id = 0, takeover_at = 0;
     bool host = !o.gpuparse;
+    std::vector<ReadItem> items;
+    std::vector<Spans> spans(ctx.size());
     if (!host) {
         RawChunker rc(o.patternfilename, o.fastq, o.chunk_bytes, 2 * ctx.size());
         while (!host) {
@@ -455,9 +436,13 @@ uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids,
             if (good < ch.size()) { host = true; takeover_at = ch[good].file_offset; }
             ch.resize(good); pr.resize(good);
             if (good) {
-                std::vector<uint64_t> first(good);
-                for (size_t g = 0; g < good; ++g) { first[g] = next_id; next_id += pr[g].n_reads; }
-                onChunks(first, ch, pr);
+                items.clear();
+                for (size_t g = 0; g < good; ++g) {
+                    if (want_ids) downloadSpans(ctx[g]->h, pr[g], spans[g], T);
+                    items.push_back(ReadItem{next_id, makeBatch(pr[g]), ReadSource(ch[g], spans[g])});
+                    next_id += pr[g].n_reads;
+                }
+                onRound(items);
             }
             for (auto &c : ch) rc.release(c);
         }
@@ -473,25 +458,35 @@ uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids,
                 if (!rr.fillBlock(blk[used], o.batch_reads, want_ids)) break;
             T.parse += now_s() - t0;
             if (!used) break;
-            onBlocks(blk, used);
+            items.clear();
+            for (size_t g = 0; g < used; ++g) items.push_back(ReadItem{blk[g].first_id, makeBatch(blk[g]), ReadSource(blk[g])});
+            onRound(items);
             for (size_t g = 0; g < used; ++g) next_id += blk[g].size();
         }
     }
     return next_id;
 }
 
-void progress(uint64_t handled, uint64_t numpat)
+// list(h, in..., hits, room, &n, offsets) lists into hits and answers REAL_HIP_E_OVERFLOW with the number it has to list:
+// retried once with room for them.  Returns the number listed.
+template <class Hit, class List, class... In>
+uint64_t listGrowing(real_hip_ctx *h, const char *what, std::vector<Hit> &hits, uint64_t *offsets, List list, In... in)
 {
-    std::cerr << "\r                                                              \r" << (double)handled / (numpat ? numpat : 1) << std::flush;
+    uint64_t n = 0;
+    int rc = list(h, in..., hits.data(), hits.size(), &n, offsets);
+    if (rc == REAL_HIP_E_OVERFLOW) { // retry with the size the library reports
+        hits.resize(n + 16);
+        rc = list(h, in..., hits.data(), hits.size(), &n, offsets);
+    }
+    check(h, rc, what);
+    return n;
 }
 
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
 int matchUnique(const RealOptions &o)
 {
     Timers T;
-    const double t_begin = now_s();
-    int qoff = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
-    if (o.fastq && !qoff) throw std::runtime_error("Unable to automatically detect FastQ quality format."); // :1112
+    const int qoff = qualityOffset(o, o.fastq, o.patternfilename);
     // uniqueinfo(numpat), :1094-1097.  The reference counts the reads in a pass of its own; here the arrays grow with the
     // first pass over the file (records start as NoMatch / -FLT_MAX, UniqueMatchInfo.hpp:191).
     std::vector<uint64_t> info;
@@ -505,120 +500,52 @@ int matchUnique(const RealOptions &o)
             if (o.scores) score.resize(to, -FLT_MAX);
         }
     };
-    std::vector<std::string> files;
-    getFileList(o.textfilename, files);
-    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
-    if (files.size() > 64) throw std::runtime_error("more than 64 text files (6 bits of file id, UniqueMatchInfo.hpp:31)");
+    const std::vector<std::string> files = genomeFiles(o, "more than 64 text files (6 bits of file id, UniqueMatchInfo.hpp:31)");
     CtxVec ctx = makeContexts(o);
     Ranges RS;
-    for (unsigned fi = 0; fi < files.size(); ++fi) {
-        std::cerr << "Processing file " << files[fi] << ((fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
-        Resident R;
-        double t0 = now_s();
-        R.G.load(files[fi]);
-        T.genome += now_s() - t0;
-        RS.names.push_back(R.G.frag_names); RS.starts.push_back(R.G.frag_start);
-        t0 = now_s();
-        setText(o, ctx, R, fi);
-        T.index += now_s() - t0;
-        const uint64_t nwin_upper = R.G.sym.size();
-        const uint64_t n_list = blockEntries(o, ctx[0]->h, nwin_upper ? nwin_upper : 1);
-        uint64_t first = 0;
-        bool have_next = true;
-        while (have_next) {
-            t0 = now_s();
-            const uint64_t n = nextBlock(o, ctx, R, first, n_list, have_next);
-            T.index += now_s() - t0;
-            if (!n) break;
-            first += n;
-            const uint64_t seen = streamReads(o, ctx, qoff, false, T,
-                [&](const std::vector<uint64_t> &first_id, const std::vector<Chunk> &ch, const std::vector<real_hip_parsed> &pr) {
-                    grow(first_id.back() + pr.back().n_reads);
-                    const double tm = now_s();
-                    onEach(ch.size(), [&](size_t g) {
-                        real_hip_batch rb = makeBatch(pr[g]);
-                        rb.fresh = !counted; // first pass over the reads: the records start on the device
-                        if (rb.n_reads)
-                            check(ctx[g]->h, real_hip_match_unique(ctx[g]->h, &rb, info.data() + first_id[g], o.scores ? score.data() + first_id[g] : nullptr),
-                                  "real_hip_match_unique");
-                    });
-                    T.match += now_s() - tm;
-                    if (counted) progress(first_id.back() + pr.back().n_reads, numpat);
-                },
-                [&](std::vector<ReadBlock> &blk, size_t used) {
-                    grow(blk[used - 1].first_id + blk[used - 1].size());
-                    const double tm = now_s();
-                    onEach(used, [&](size_t g) {
-                        real_hip_batch rb = makeBatch(blk[g]);
-                        rb.fresh = !counted;
-                        if (rb.n_reads)
-                            check(ctx[g]->h, real_hip_match_unique(ctx[g]->h, &rb, info.data() + blk[g].first_id, o.scores ? score.data() + blk[g].first_id : nullptr),
-                                  "real_hip_match_unique");
-                    });
-                    T.match += now_s() - tm;
-                    if (counted) progress(blk[used - 1].first_id + blk[used - 1].size(), numpat);
-                });
-            if (!counted) { numpat = seen; counted = true; std::cerr << "number of reads " << numpat << std::endl; } // :1096
-            else if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
-            std::cerr << std::endl;
-        }
-    }
+    for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, kSayLast, T, &RS, [&](Resident &) {
+        const uint64_t seen = streamReads(o, ctx, qoff, false, T, [&](const std::vector<ReadItem> &items) {
+            const uint64_t end = items.back().first_id + items.back().batch.n_reads;
+            grow(end);
+            const double tm = now_s();
+            onEach(items.size(), [&](size_t g) {
+                real_hip_batch rb = items[g].batch;
+                rb.fresh = !counted; // first pass over the reads: the records start on the device
+                if (rb.n_reads)
+                    check(ctx[g]->h, real_hip_match_unique(ctx[g]->h, &rb, info.data() + items[g].first_id, o.scores ? score.data() + items[g].first_id : nullptr),
+                          "real_hip_match_unique");
+            });
+            T.match += now_s() - tm;
+            if (counted) std::cerr << "\r                                                              \r" << (double)end / (numpat ? numpat : 1) << std::flush;
+        });
+        if (!counted) { numpat = seen; counted = true; std::cerr << "number of reads " << numpat << std::endl; } // :1096
+        else if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+        std::cerr << std::endl;
+    });
     std::cerr << "All done." << std::endl;
     // output, in read order (PatternIdReader re-stream, :1438-1486)
-    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
-    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
-    std::vector<char> obuf((size_t)8 << 20);
-    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    OutFile out(o.outputfilename);
     uint64_t unique = 0;
-    std::vector<uint32_t> id_start, id_len;
-    std::vector<uint64_t> off;
-    streamReads(o, ctx, qoff, true, T,
-        [&](const std::vector<uint64_t> &first_id, const std::vector<Chunk> &ch, const std::vector<real_hip_parsed> &pr) {
-            for (size_t g = 0; g < ch.size(); ++g) { // (in file order; the spans of one chunk at a time)
-                const uint64_t n = pr[g].n_reads;
-                if (!n) continue;
-                id_start.resize(n); id_len.resize(n); off.resize(n + 1);
-                const double td = now_s();
-                check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].id_start, id_start.data(), n * 4), "real_hip_download");
-                check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].id_len, id_len.data(), n * 4), "real_hip_download");
-                check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].offsets, off.data(), (n + 1) * 8), "real_hip_download");
-                T.parse += now_s() - td;
-                const char *text = ch[g].text;
-                const uint64_t base = first_id[g];
-                formatAndWrite(n, out, T, [&](uint64_t i, std::string &b) {
-                    const Record r = unpack(info[base + i]);
-                    if (r.st != 1 && r.st != 2) return; // NoMatch / NonUnique / Gapped print nothing
-                    // the id is everything behind the marker up to the newline (a '\r' in front of it included, as the
-                    // reference's reader keeps it); the sequence is the next line
-                    uint64_t il = id_len[i];
-                    if (text[id_start[i] + il] == '\r') il++;
-                    const uint64_t patl = off[i + 1] - off[i];
-                    appendLine(b, text + id_start[i], il, text + id_start[i] + il + 1, nullptr, patl, o.scores, o.scores ? score[base + i] : 0.f, r.st == 2,
-                               RS.names[r.file][r.frag], r.pos - RS.starts[r.file][r.frag] + 1, r.errors);
-                });
-            }
-        },
-        [&](std::vector<ReadBlock> &blk, size_t used) {
-            for (size_t g = 0; g < used; ++g) {
-                const ReadBlock &b = blk[g];
-                formatAndWrite(b.size(), out, T, [&](uint64_t i, std::string &s) {
-                    const Record r = unpack(info[b.first_id + i]);
-                    if (r.st != 1 && r.st != 2) return;
-                    const uint64_t lo = b.offsets[i], patl = b.offsets[i + 1] - lo;
-                    appendLine(s, b.ids[i].data(), b.ids[i].size(), nullptr, &b.bases[lo], patl, o.scores, o.scores ? score[b.first_id + i] : 0.f, r.st == 2,
-                               RS.names[r.file][r.frag], r.pos - RS.starts[r.file][r.frag] + 1, r.errors);
-                });
-            }
-        });
-    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
-    if (out != stdout) fclose(out);
+    streamReads(o, ctx, qoff, true, T, [&](const std::vector<ReadItem> &items) {
+        for (const ReadItem &it : items) { // (in file order)
+            const ReadSource src = it.src;
+            if (!src.size()) continue;
+            const uint64_t base = it.first_id;
+            formatAndWrite(src.size(), out.file(), T, [&](uint64_t i, std::string &s) {
+                const Record r = unpack(info[base + i]);
+                if (r.st != 1 && r.st != 2) return; // NoMatch / NonUnique / Gapped print nothing
+                appendLine(s, src[i], o.scores, Placement{o.scores ? score[base + i] : 0.f, r.st == 2, RS.names[r.file][r.frag],
+                                                          r.pos - RS.starts[r.file][r.frag] + 1, r.errors});
+            });
+        }
+    });
+    out.close();
     // (counted here, once, and not line by line inside the formatter: sixteen threads bumping neighbouring counters
     // cost more than formatting the lines)
 #pragma omp parallel for reduction(+ : unique) schedule(static)
     for (uint64_t i = 0; i < numpat; ++i) { const unsigned st = (unsigned)(info[i] >> 61); unique += (st == 1 || st == 2); }
     std::cerr << "unique: " << unique << std::endl; // :1488
-    T.reads = numpat; T.lines = unique; T.total = now_s() - t_begin;
-    T.print();
+    T.finish(numpat, unique);
     return EXIT_SUCCESS;
 }
 
@@ -628,109 +555,72 @@ int matchUnique(const RealOptions &o)
 int matchAll(const RealOptions &o)
 {
     Timers T;
-    const double t_begin = now_s();
-    int qoff = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
-    if (o.fastq && !qoff) throw std::runtime_error("Unable to automatically detect FastQ quality format.");
-    std::vector<std::string> files;
-    getFileList(o.textfilename, files);
-    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
+    const int qoff = qualityOffset(o, o.fastq, o.patternfilename);
+    const std::vector<std::string> files = genomeFiles(o, nullptr);
     CtxVec ctx = makeContexts(o);
-    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
-    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
-    std::vector<char> obuf((size_t)8 << 20);
-    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    OutFile out(o.outputfilename);
     uint64_t n_reads = 0, n_lines = 0;
-    for (unsigned fi = 0; fi < files.size(); ++fi) {
-        std::cerr << "Processing file " << files[fi] << std::endl;
-        Resident R;
-        double t0 = now_s();
-        R.G.load(files[fi]);
-        T.genome += now_s() - t0;
-        t0 = now_s();
-        setText(o, ctx, R, fi);
-        T.index += now_s() - t0;
-        const uint64_t n_list = blockEntries(o, ctx[0]->h, R.G.sym.size() ? R.G.sym.size() : 1);
-        uint64_t first = 0;
-        bool have_next = true;
-        while (have_next) {
-            t0 = now_s();
-            const uint64_t n = nextBlock(o, ctx, R, first, n_list, have_next);
-            T.index += now_s() - t0;
-            if (!n) break;
-            first += n;
-            std::vector<std::vector<real_hip_hit>> hits(ctx.size(), std::vector<real_hip_hit>(1u << 20));
-            std::vector<std::vector<uint64_t>> hoff(ctx.size());
-            auto matchOne = [&](size_t g, real_hip_batch rb) {
+    for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, 0, T, nullptr, [&](Resident &R) {
+        std::vector<std::vector<real_hip_hit>> hits(ctx.size(), std::vector<real_hip_hit>(1u << 20));
+        std::vector<std::vector<uint64_t>> hoff(ctx.size());
+        n_reads = streamReads(o, ctx, qoff, true, T, [&](const std::vector<ReadItem> &items) {
+            const double tm = now_s();
+            onEach(items.size(), [&](size_t g) {
+                const real_hip_batch &rb = items[g].batch;
                 hoff[g].assign(rb.n_reads + 1, 0);
-                if (!rb.n_reads) return;
-                uint64_t nh = 0;
-                int rc = real_hip_match_all(ctx[g]->h, &rb, hits[g].data(), hits[g].size(), &nh, hoff[g].data());
-                if (rc == REAL_HIP_E_OVERFLOW) { // retry with the size the library reports
-                    hits[g].resize(nh + 16);
-                    rc = real_hip_match_all(ctx[g]->h, &rb, hits[g].data(), hits[g].size(), &nh, hoff[g].data());
-                }
-                check(ctx[g]->h, rc, "real_hip_match_all");
-            };
-            std::vector<uint32_t> id_start, id_len;
-            std::vector<uint64_t> off;
-            n_reads = streamReads(o, ctx, qoff, true, T,
-                [&](const std::vector<uint64_t> &, const std::vector<Chunk> &ch, const std::vector<real_hip_parsed> &pr) {
-                    const double tm = now_s();
-                    onEach(ch.size(), [&](size_t g) { matchOne(g, makeBatch(pr[g])); });
-                    T.match += now_s() - tm;
-                    for (size_t g = 0; g < ch.size(); ++g) { // (in file order)
-                        const uint64_t n = pr[g].n_reads;
-                        if (!n) continue;
-                        id_start.resize(n); id_len.resize(n); off.resize(n + 1);
-                        const double td = now_s();
-                        check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].id_start, id_start.data(), n * 4), "real_hip_download");
-                        check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].id_len, id_len.data(), n * 4), "real_hip_download");
-                        check(ctx[g]->h, real_hip_download(ctx[g]->h, pr[g].offsets, off.data(), (n + 1) * 8), "real_hip_download");
-                        T.parse += now_s() - td;
-                        const char *text = ch[g].text;
-                        n_lines += hoff[g][n];
-                        formatAndWrite(n, out, T, [&](uint64_t i, std::string &s) {
-                            uint64_t il = id_len[i];
-                            if (text[id_start[i] + il] == '\r') il++;
-                            const uint64_t patl = off[i + 1] - off[i];
-                            for (uint64_t k = hoff[g][i]; k < hoff[g][i + 1]; ++k) {
-                                const real_hip_hit &M = hits[g][k];
-                                appendLine(s, text + id_start[i], il, text + id_start[i] + il + 1, nullptr, patl, o.scores, M.score, M.inverted != 0,
-                                           R.G.frag_names[M.frag], (uint64_t)M.pos - R.G.frag_start[M.frag] + 1, M.k);
-                            }
-                        });
-                    }
-                },
-                [&](std::vector<ReadBlock> &blk, size_t used) {
-                    const double tm = now_s();
-                    onEach(used, [&](size_t g) { matchOne(g, makeBatch(blk[g])); });
-                    T.match += now_s() - tm;
-                    for (size_t g = 0; g < used; ++g) {
-                        const ReadBlock &b = blk[g];
-                        n_lines += hoff[g][b.size()];
-                        formatAndWrite(b.size(), out, T, [&](uint64_t i, std::string &s) {
-                            const uint64_t lo = b.offsets[i], patl = b.offsets[i + 1] - lo;
-                            for (uint64_t k = hoff[g][i]; k < hoff[g][i + 1]; ++k) {
-                                const real_hip_hit &M = hits[g][k];
-                                appendLine(s, b.ids[i].data(), b.ids[i].size(), nullptr, &b.bases[lo], patl, o.scores, M.score, M.inverted != 0,
-                                           R.G.frag_names[M.frag], (uint64_t)M.pos - R.G.frag_start[M.frag] + 1, M.k);
-                            }
-                        });
+                if (rb.n_reads) listGrowing(ctx[g]->h, "real_hip_match_all", hits[g], hoff[g].data(), real_hip_match_all, &rb);
+            });
+            T.match += now_s() - tm;
+            for (size_t g = 0; g < items.size(); ++g) { // (in file order)
+                const ReadSource src = items[g].src;
+                const uint64_t n = src.size();
+                if (!n) continue;
+                n_lines += hoff[g][n];
+                formatAndWrite(n, out.file(), T, [&](uint64_t i, std::string &s) {
+                    const ReadView r = src[i];
+                    for (uint64_t k = hoff[g][i]; k < hoff[g][i + 1]; ++k) {
+                        const real_hip_hit &M = hits[g][k];
+                        appendLine(s, r, o.scores, Placement{M.score, M.inverted != 0, R.G.frag_names[M.frag], (uint64_t)M.pos - R.G.frag_start[M.frag] + 1, M.k});
                     }
                 });
-        }
-    }
-    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
-    if (out != stdout) fclose(out);
+            }
+        });
+    });
+    out.close();
     std::cerr << "All done." << std::endl;
-    T.reads = n_reads; T.lines = n_lines; T.total = now_s() - t_begin;
-    T.print();
+    T.finish(n_reads, n_lines);
     return EXIT_SUCCESS;
 }
 
+// ---- paired-end reads: what the two drivers share (no counterpart in the reference) --------------------------
+real_hip_pair_params pairParams(const RealOptions &o)
+{
+    real_hip_pair_params pp;
+    memset(&pp, 0, sizeof pp);
+    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    return pp;
+}
+
+// The next block of each of the two mate files, read in step by the host reader: read i of each are mates.  Returns the
+// number of fragments, 0 at the end of both.
+uint64_t fillMates(const RealOptions &o, ReadReader &r1, ReadReader &r2, ReadBlock &b1, ReadBlock &b2, bool want_ids)
+{
+    const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, want_ids), n2 = r2.fillBlock(b2, o.batch_reads, want_ids);
+    if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
+    return n1;
+}
+
+// The two lines of a pair (a real_hip_pair or a real_hip_pair_hit): mate 1, then mate 2 on the other strand; fs is the
+// start of the fragment `fragname` in its file's text.
+template <class Pair>
+inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, bool scores, const Pair &P, const std::string &fragname, uint64_t fs)
+{
+    appendLine(s, m1, scores, Placement{P.score1, P.inverted1 != 0, fragname, (uint64_t)P.pos1 - fs + 1, P.k1});
+    appendLine(s, m2, scores, Placement{P.score2, P.inverted1 == 0, fragname, (uint64_t)P.pos2 - fs + 1, P.k2});
+}
+
 // ---- paired-end reads: one placement per fragment ---------------------------------------------------------
-// No counterpart in the reference.  The two mate files are read in step by the host reader (read i of each are mates);
-// per genome file real_hip_match_pairs (-mate_search 1: real_hip_match_pairs_search) folds into the fragments' in/out
+// Per genome file real_hip_match_pairs (-mate_search 1: real_hip_match_pairs_search) folds into the fragments' in/out
 // records, as uniqueinfo[] folds for matchUnique.
 // A Unique fragment prints the 11-column line of mate 1 and then of mate 2; NoMatch / NonUnique print nothing.
 // -unpaired <file>: real_hip_match_pairs_singles folds each mate's own hits beside the pairs; a fragment whose final pair
@@ -739,19 +629,11 @@ int matchAll(const RealOptions &o)
 int matchPairs(const RealOptions &o)
 {
     Timers T;
-    const double t_begin = now_s();
-    const int qoff1 = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
-    const int qoff2 = o.fastq2 ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.pattern2filename)) : 0;
-    if ((o.fastq && !qoff1) || (o.fastq2 && !qoff2)) throw std::runtime_error("Unable to automatically detect FastQ quality format.");
-    std::vector<std::string> files;
-    getFileList(o.textfilename, files);
-    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
-    if (files.size() > 64) throw std::runtime_error("more than 64 text files");
+    const int qoff1 = qualityOffset(o, o.fastq, o.patternfilename), qoff2 = qualityOffset(o, o.fastq2, o.pattern2filename);
+    const std::vector<std::string> files = genomeFiles(o, "more than 64 text files");
     CtxVec ctx = makeContexts(o);
     real_hip_ctx *h = ctx[0]->h;
-    real_hip_pair_params pp;
-    memset(&pp, 0, sizeof pp);
-    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    const real_hip_pair_params pp = pairParams(o);
     real_hip_mate_search_params sp; // -mate_search 1: the search behind the join
     memset(&sp, 0, sizeof sp);
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
@@ -761,32 +643,15 @@ int matchPairs(const RealOptions &o)
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
-    for (unsigned fi = 0; fi < files.size(); ++fi) {
-        std::cerr << "Processing file " << files[fi] << ((fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
-        Resident R;
-        double t0 = now_s();
-        R.G.load(files[fi]);
-        T.genome += now_s() - t0;
-        RS.names.push_back(R.G.frag_names); RS.starts.push_back(R.G.frag_start);
-        t0 = now_s();
-        setText(o, ctx, R, fi);
-        const uint64_t n_list = blockEntries(o, h, R.G.sym.size() ? R.G.sym.size() : 1);
-        bool have_next = false;
-        const uint64_t n = nextBlock(o, ctx, R, 0, n_list, have_next);
-        T.index += now_s() - t0;
-        if (have_next)
-            throw std::runtime_error("paired-end reads: " + files[fi] + " needs more than one index block (pairs across blocks would be lost); "
-                                     "raise -f / -block or split the file");
-        if (!n) continue;
+    for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, kSayLast | kOneBlock, T, &RS, [&](Resident &) {
         ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
-            t0 = now_s();
-            const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, false), n2 = r2.fillBlock(b2, o.batch_reads, false);
+            const double t0 = now_s();
+            const uint64_t n = fillMates(o, r1, r2, b1, b2, false);
             T.read += now_s() - t0;
-            if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
-            if (!n1) break;
-            if (seen + n1 > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n1, pairs.size() + pairs.size() / 2));
+            if (!n) break;
+            if (seen + n > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n, pairs.size() + pairs.size() / 2));
             if (unpaired && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
@@ -797,73 +662,53 @@ int matchPairs(const RealOptions &o)
             else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, pairs.data() + seen), "real_hip_match_pairs_search");
             else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
             T.match += now_s() - tm;
-            seen += n1;
+            seen += n;
         }
         if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
         else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-    }
+    });
     std::cerr << "All done." << std::endl;
-    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
-    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
-    std::vector<char> obuf((size_t)8 << 20);
-    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    OutFile out(o.outputfilename);
+    std::unique_ptr<OutFile> uout(unpaired ? new OutFile(o.unpairedfilename, true) : nullptr);
     uint64_t unique = 0, base = 0;
-    FILE *uout = nullptr;
-    std::vector<char> ubuf;
-    if (unpaired) {
-        uout = fopen(o.unpairedfilename.c_str(), "wb");
-        if (!uout) throw std::runtime_error("cannot open the -unpaired file " + o.unpairedfilename);
-        ubuf.resize((size_t)8 << 20);
-        setvbuf(uout, ubuf.data(), _IOFBF, ubuf.size());
-    }
     // the line of a mate that is placed uniquely on its own, as the single-end mode prints that hit
-    auto singleLine = [&](std::string &s, const ReadBlock &b, uint64_t i, const real_hip_single &S) {
+    auto singleLine = [&](std::string &s, const ReadView &r, const real_hip_single &S) {
         if (REAL_HIP_SINGLE_STATE(S.tag) != REAL_HIP_PAIR_UNIQUE) return;
-        const uint64_t lo = b.offsets[i];
-        appendLine(s, b.ids[i].data(), b.ids[i].size(), nullptr, &b.bases[lo], b.offsets[i + 1] - lo, o.scores, o.scores ? S.score : 0.f,
-                   REAL_HIP_SINGLE_INVERTED(S.tag) != 0, RS.names[S.fileid][S.frag], (uint64_t)S.pos - RS.starts[S.fileid][S.frag] + 1,
-                   REAL_HIP_SINGLE_K(S.tag));
+        appendLine(s, r, o.scores, Placement{S.score, REAL_HIP_SINGLE_INVERTED(S.tag) != 0, RS.names[S.fileid][S.frag],
+                                             (uint64_t)S.pos - RS.starts[S.fileid][S.frag] + 1, REAL_HIP_SINGLE_K(S.tag)});
     };
     ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+    const ReadSource m1(b1), m2(b2);
     for (;;) {
-        const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
-        if (n1 != n2 || base + n1 > numpat) throw std::runtime_error("the read files changed between two passes");
-        if (!n1) break;
+        const uint64_t n = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
+        if (n != n2 || base + n > numpat) throw std::runtime_error("the read files changed between two passes");
+        if (!n) break;
         if (unpaired)
-            formatAndWrite(n1, uout, T, [&](uint64_t i, std::string &s) {
+            formatAndWrite(n, uout->file(), T, [&](uint64_t i, std::string &s) {
                 if (pairs[base + i].state != REAL_HIP_PAIR_NOMATCH) return;
-                singleLine(s, b1, i, singles1[base + i]);
-                singleLine(s, b2, i, singles2[base + i]);
+                singleLine(s, m1[i], singles1[base + i]);
+                singleLine(s, m2[i], singles2[base + i]);
             });
-        formatAndWrite(n1, out, T, [&](uint64_t i, std::string &s) {
+        formatAndWrite(n, out.file(), T, [&](uint64_t i, std::string &s) {
             const real_hip_pair &P = pairs[base + i];
             if (P.state != REAL_HIP_PAIR_UNIQUE) return;
-            const std::string &fname = RS.names[P.fileid][P.frag];
-            const uint64_t fs = RS.starts[P.fileid][P.frag];
-            const uint64_t lo1 = b1.offsets[i], lo2 = b2.offsets[i];
-            appendLine(s, b1.ids[i].data(), b1.ids[i].size(), nullptr, &b1.bases[lo1], b1.offsets[i + 1] - lo1, o.scores, o.scores ? P.score1 : 0.f,
-                       P.inverted1 != 0, fname, (uint64_t)P.pos1 - fs + 1, P.k1);
-            appendLine(s, b2.ids[i].data(), b2.ids[i].size(), nullptr, &b2.bases[lo2], b2.offsets[i + 1] - lo2, o.scores, o.scores ? P.score2 : 0.f,
-                       P.inverted1 == 0, fname, (uint64_t)P.pos2 - fs + 1, P.k2);
+            appendPair(s, m1[i], m2[i], o.scores, P, RS.names[P.fileid][P.frag], RS.starts[P.fileid][P.frag]);
         });
-        base += n1;
+        base += n;
     }
     if (base != numpat) throw std::runtime_error("the read files changed between two passes");
-    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
-    if (out != stdout) fclose(out);
+    out.close();
     for (uint64_t i = 0; i < numpat; ++i) unique += pairs[i].state == REAL_HIP_PAIR_UNIQUE;
     std::cerr << "unique fragments: " << unique << std::endl;
     if (unpaired) {
-        if (fflush(uout) != 0) throw std::runtime_error("write to the -unpaired file failed");
-        fclose(uout);
+        uout->close();
         uint64_t mates = 0;
         for (uint64_t i = 0; i < numpat; ++i)
             if (pairs[i].state == REAL_HIP_PAIR_NOMATCH)
                 mates += (REAL_HIP_SINGLE_STATE(singles1[i].tag) == REAL_HIP_PAIR_UNIQUE) + (REAL_HIP_SINGLE_STATE(singles2[i].tag) == REAL_HIP_PAIR_UNIQUE);
         std::cerr << "unpaired mates: " << mates << std::endl;
     }
-    T.reads = 2 * numpat; T.lines = 2 * unique; T.total = now_s() - t_begin;
-    T.print();
+    T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;
 }
 
@@ -874,87 +719,47 @@ int matchPairs(const RealOptions &o)
 int matchPairsAll(const RealOptions &o)
 {
     Timers T;
-    const double t_begin = now_s();
-    const int qoff1 = o.fastq ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.patternfilename)) : 0;
-    const int qoff2 = o.fastq2 ? (o.qualityOffset ? (int)o.qualityOffset : ReadReader::getOffset(o.pattern2filename)) : 0;
-    if ((o.fastq && !qoff1) || (o.fastq2 && !qoff2)) throw std::runtime_error("Unable to automatically detect FastQ quality format.");
-    std::vector<std::string> files;
-    getFileList(o.textfilename, files);
-    if (files.empty()) throw std::runtime_error("no .fa text file found at " + o.textfilename);
-    if (files.size() > 64) throw std::runtime_error("more than 64 text files");
+    const int qoff1 = qualityOffset(o, o.fastq, o.patternfilename), qoff2 = qualityOffset(o, o.fastq2, o.pattern2filename);
+    const std::vector<std::string> files = genomeFiles(o, "more than 64 text files");
     CtxVec ctx = makeContexts(o);
     real_hip_ctx *h = ctx[0]->h;
-    real_hip_pair_params pp;
-    memset(&pp, 0, sizeof pp);
-    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
-    FILE *out = (o.outputfilename == "-") ? stdout : fopen(o.outputfilename.c_str(), "wb");
-    if (!out) throw std::runtime_error("cannot open output file " + o.outputfilename);
-    std::vector<char> obuf((size_t)8 << 20);
-    setvbuf(out, obuf.data(), _IOFBF, obuf.size());
+    const real_hip_pair_params pp = pairParams(o);
+    OutFile out(o.outputfilename);
     std::vector<real_hip_pair_hit> hits;
     std::vector<uint64_t> poff;
     uint64_t numpat = 0, n_pairs = 0;
     ReadBlock b1, b2;
-    for (unsigned fi = 0; fi < files.size(); ++fi) {
-        std::cerr << "Processing file " << files[fi] << ((fi + 1 == files.size()) ? " (last processed file)" : "") << std::endl;
-        Resident R;
-        double t0 = now_s();
-        R.G.load(files[fi]);
-        T.genome += now_s() - t0;
-        t0 = now_s();
-        setText(o, ctx, R, fi);
-        const uint64_t n_list = blockEntries(o, h, R.G.sym.size() ? R.G.sym.size() : 1);
-        bool have_next = false;
-        const uint64_t n = nextBlock(o, ctx, R, 0, n_list, have_next);
-        T.index += now_s() - t0;
-        if (have_next)
-            throw std::runtime_error("paired-end reads: " + files[fi] + " needs more than one index block (pairs across blocks would be lost); "
-                                     "raise -f / -block or split the file");
-        if (!n) continue;
+    const ReadSource m1(b1), m2(b2);
+    for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, kSayLast | kOneBlock, T, nullptr, [&](Resident &R) {
         ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
-            t0 = now_s();
-            const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
+            const double t0 = now_s();
+            const uint64_t n = fillMates(o, r1, r2, b1, b2, true);
             T.read += now_s() - t0;
-            if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
-            if (!n1) break;
-            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
-            poff.assign(n1 + 1, 0);
-            if (hits.size() < n1 + n1 / 4 + 1024) hits.resize(n1 + n1 / 4 + 1024); // (about one pair per fragment is the rule: room for a quarter more)
+            if (!n) break;
+            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            poff.assign(n + 1, 0);
+            if (hits.size() < n + n / 4 + 1024) hits.resize(n + n / 4 + 1024); // (about one pair per fragment is the rule: room for a quarter more)
             const double tm = now_s();
-            uint64_t np = 0;
-            int rc = real_hip_match_pairs_all(h, &rb1, &rb2, &pp, hits.data(), hits.size(), &np, poff.data());
-            if (rc == REAL_HIP_E_OVERFLOW) { // retry with the size the library reports
-                hits.resize(np + 16);
-                rc = real_hip_match_pairs_all(h, &rb1, &rb2, &pp, hits.data(), hits.size(), &np, poff.data());
-            }
-            check(h, rc, "real_hip_match_pairs_all");
+            n_pairs += listGrowing(h, "real_hip_match_pairs_all", hits, poff.data(), real_hip_match_pairs_all, &rb1, &rb2, &pp);
             T.match += now_s() - tm;
-            n_pairs += np;
-            formatAndWrite(n1, out, T, [&](uint64_t i, std::string &s) {
-                const uint64_t lo1 = b1.offsets[i], lo2 = b2.offsets[i];
+            formatAndWrite(n, out.file(), T, [&](uint64_t i, std::string &s) {
+                const ReadView v1 = m1[i], v2 = m2[i];
                 for (uint64_t k = poff[i]; k < poff[i + 1]; ++k) {
                     const real_hip_pair_hit &P = hits[k];
-                    const std::string &fname = R.G.frag_names[P.frag];
-                    const uint64_t fs = R.G.frag_start[P.frag];
-                    appendLine(s, b1.ids[i].data(), b1.ids[i].size(), nullptr, &b1.bases[lo1], b1.offsets[i + 1] - lo1, o.scores, o.scores ? P.score1 : 0.f,
-                               P.inverted1 != 0, fname, (uint64_t)P.pos1 - fs + 1, P.k1);
-                    appendLine(s, b2.ids[i].data(), b2.ids[i].size(), nullptr, &b2.bases[lo2], b2.offsets[i + 1] - lo2, o.scores, o.scores ? P.score2 : 0.f,
-                               P.inverted1 == 0, fname, (uint64_t)P.pos2 - fs + 1, P.k2);
+                    appendPair(s, v1, v2, o.scores, P, R.G.frag_names[P.frag], R.G.frag_start[P.frag]);
                 }
             });
-            seen += n1;
+            seen += n;
         }
         if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
         else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-    }
-    if (fflush(out) != 0) throw std::runtime_error("write to the output file failed");
-    if (out != stdout) fclose(out);
+    });
+    out.close();
     std::cerr << "All done." << std::endl;
     std::cerr << "concordant pairs: " << n_pairs << std::endl;
-    T.reads = 2 * numpat; T.lines = 2 * n_pairs; T.total = now_s() - t_begin;
-    T.print();
+    T.finish(2 * numpat, 2 * n_pairs);
     return EXIT_SUCCESS;
 }
 

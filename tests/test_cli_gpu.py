@@ -94,15 +94,27 @@ def test_real_cli_match_unique(ora, tmp_path, scores, extra, n_list, fastq):
     assert ("unique: %d" % len(want)) in r.stderr.decode()
 
 
-@pytest.mark.parametrize("extra", [[], ["-gpus", "2", "-gpus_share_device", "1", "-batch", "150"]])
-def test_real_cli_match_all(ora, tmp_path, extra):
+def match_all_case(ora, tmp_path, extra, wrap_record=None):
+    """`real -u 0` on the matchAll inputs against the oracle's hit list; wrap_record: sequence and quality of that record
+    are cut in two lines each, so that the device parser refuses its chunk and the host reader takes over there"""
     g = synth.random_genome(60_000, seed=51, n_frag=2, repeats=25, repeat_len=200)
     b = synth.sample_reads(g, 800, 100, 0.01, seed=52)
     fa, rd = write_inputs(tmp_path, g, b, True)
+    if wrap_record is not None:
+        lines = open(rd).read().split("\n")
+        assert len(lines) == 4 * 800 + 1
+        s, q = lines[4 * wrap_record + 1], lines[4 * wrap_record + 3]
+        lines[4 * wrap_record + 1] = s[:41] + "\n" + s[41:]
+        lines[4 * wrap_record + 3] = q[:17] + "\n" + q[17:]
+        open(rd, "w").write("\n".join(lines))
     out = str(tmp_path / "all.tsv")
     r = subprocess.run([REAL, "-t", fa, "-p", rd, "-o", out, "-u", "0", "-e", "2", "-s", "2", "-l", "32", "-q", "1"] + extra,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
+    err = r.stderr.decode()
+    assert ("host reader takes over" in err) == (wrap_record is not None), err[-1500:]
+    if wrap_record is not None:                                    # in the middle of the file: not from its first chunk on
+        assert 30000 < int(err.split("one-line-per-field form at byte ")[1].split(":")[0]) < os.path.getsize(rd) - 30000
     og = ora.Genome(g.sym, g.frag_start)
     ix = ora.Index(og, 32)
     p = ora.make_params(seedl=32, seedkmax=2, totalkmax=2, scores=1)
@@ -116,6 +128,22 @@ def test_real_cli_match_all(ora, tmp_path, extra):
                                str(int(h["pos"]) - int(g.frag_start[int(h["frag"])]) + 1), "", str(int(h["k"]))]))
     got = open(out).read().split("\n")[:-1]
     assert got == want
+
+
+@pytest.mark.parametrize("extra", [
+    [],
+    ["-gpus", "2", "-gpus_share_device", "1", "-batch", "150"],
+    ["-gpuparse", "0", "-batch", "150"],                           # read file parsed by the host reader: several blocks
+    ["-gpus", "2", "-gpus_share_device", "1", "-gpuparse", "0", "-batch", "150"],   # two contexts fed by the host reader
+])
+def test_real_cli_match_all(ora, tmp_path, extra):
+    match_all_case(ora, tmp_path, extra)
+
+
+def test_real_cli_match_all_host_reader_takes_over_in_mid_file(ora, tmp_path):
+    """record 400 of 800 wrapped and small chunks: the chunks in front of it come from the device parser, the rest of
+    the file from the host reader; the lines are those of the regular file"""
+    match_all_case(ora, tmp_path, ["-chunk", "30000"], wrap_record=400)
 
 
 def test_real_cli_errors_are_loud(tmp_path):

@@ -187,7 +187,7 @@ def test_device_parser_equals_the_reference_readers_or_refuses(case):
     ids0, idl = m.download(p.id_start, n, np.uint32), m.download(p.id_len, n, np.uint32)
     got = b""
     for s, l in zip(ids0.tolist(), idl.tolist()):
-        if text[s + l:s + l + 1] == b"\r":               # (the rule of the output formatter, real_amd/host/real.cpp)
+        if text[s + l:s + l + 1] == b"\r":               # (the rule of the output formatter, real_amd/host/Lines.hpp)
             l += 1
         got += text[s:s + l] + b"\0"
     assert got == z[case + "/ids"].tobytes()

@@ -136,3 +136,41 @@ def test_fast_score_formatter_equals_printf(selftest):
     operator<<(float) prints -- on random bit patterns, score-like values, integers and both sides of every power of ten"""
     r = subprocess.run([selftest, "fmtcheck", "400000"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and r.stdout.strip() == "0", r.stderr[-2000:]
+
+
+@pytest.mark.parametrize("threads,crlf", [(1, False), (7, False), (7, True)])
+def test_output_lines_from_blocks_and_from_text(selftest, tmp_path, threads, crlf):
+    """the 11-column lines (real_amd/host/Lines.hpp) of every read of a file, formatted from the host reader's blocks and
+    from the file as one text chunk: both equal the lines built here with the formula of expected_unique
+    (tests/test_cli_gpu.py).  Placement of read r, as `host_selftest lines` states it: '-' for odd r, no score for
+    r % 3 == 2, positions up to 2^35 - 1, errors r % 16, one name with a leading space.  Anything but ACGT prints as N;
+    7 threads on blocks of 7 reads and a read of one base: empty thread ranges; CRLF: the '\\r' belongs to the id."""
+    g = synth.random_genome(20000, seed=4)
+    b = synth.concat_batches([synth.sample_reads(g, 20, 36, 0.05, seed=5, n_read_prob=0.05),
+                              synth.sample_reads(g, 1, 1, 0.0, seed=7),
+                              synth.sample_reads(g, 19, 100, 0.05, seed=6, n_read_prob=0.01)])
+    assert (b.bases == 4).any()
+    fq = tmp_path / "r.fq"
+    names = [" chr one", "two", " 3"]
+    nl = "\r\n" if crlf else "\n"
+    want = []
+    with open(fq, "w", newline="") as f:
+        for r in range(b.n_reads):
+            lo, hi = int(b.offsets[r]), int(b.offsets[r + 1])
+            bases = b.bases[lo:hi].copy()
+            text = ["ACGTN"[c] for c in bases]
+            for k in range(r % 5, hi - lo, 11):                   # lowercase letters: not ACGT, so N
+                text[k] = text[k].lower()
+                bases[k] = 4
+            f.write("@" + b.ids[r] + nl + "".join(text) + nl + "+" + nl + "I" * (hi - lo) + nl)
+            inv = r % 2 == 1
+            pos1 = ((r * 0x9E3779B97F4A7C15) & (2 ** 64 - 1)) >> 29
+            pos1 = {0: 2 ** 35 - 1, 1: 1}.get(r, pos1)
+            score = "%g" % float(np.float32((r * 7919 % 100003 - 50000) / 16.0))
+            seq = "".join("ACGTN"[c] for c in (synth.revcomp(bases) if inv else bases))
+            want.append("\t".join([b.ids[r] + ("\r" if crlf else ""), seq, score if r % 3 != 2 else "", "1", "a", str(hi - lo), "-" if inv else "+",
+                                   names[r % 3], str(pos1), "", str(r % 16)]))
+    subprocess.check_call([selftest, "lines", str(fq), str(tmp_path)], env=dict(os.environ, OMP_NUM_THREADS=str(threads)))
+    assert len(want) == 40 and max(len(w) for w in want) > 150
+    for name in ("block.tsv", "chunk.tsv"):
+        assert open(tmp_path / name, newline="").read().split("\n")[:-1] == want, name
