@@ -16,7 +16,11 @@ baseline_ms, what a caller has to do without it to see the same pairs.  --skip-s
 --singles adds the legs of real_hip_match_pairs_singles (the pairs plus each mate's own placement record): the call with
 pinned host outputs and with outputs left on the device, the fold's kernel time beside the join's of the same run, the
 reads handed to the wave kernel, bytes downloaded, and the split of the extra time over match_pairs_ms into kernels and
-download; --skip-baseline / --skip-pairs-all leave the other legs out.  The parent's match_pairs_ms for the comparison:
+download; --skip-baseline / --skip-pairs-all leave the other legs out.  --insert-hist adds the legs of
+real_hip_pair_insert_hist on the records real_hip_match_pairs left on the device: the kernel's own time for the workload's
+outer distances and for all records forced into one bin (n_bins 422 / 1002 / 16384), beside the time of a device-to-device copy of the same records array taken in the same run:
+    python bench_support/pairs_bench.py --genomes iid --ks 3 --skip-baseline --skip-search --skip-pairs-all --insert-hist \
+        --out profiles/insert_hist_bench.json  The parent's match_pairs_ms for the comparison:
 the same command with --tree on a parent checkout, in the same session, alternating.
 """
 import argparse
@@ -74,6 +78,7 @@ def main():
     ap.add_argument("--skip-baseline", action="store_true")  # leave the two-match_all baseline out
     ap.add_argument("--skip-pairs-all", action="store_true") # leave the legs of the enumeration out
     ap.add_argument("--singles", action="store_true")        # add the legs of real_hip_match_pairs_singles
+    ap.add_argument("--insert-hist", action="store_true")    # add the legs of real_hip_pair_insert_hist on the records left on the device
     args = ap.parse_args()
     sys.path.insert(0, args.tree)
     import numpy as np
@@ -195,6 +200,48 @@ def main():
                     r["search_per_fragment"] = {k: ms[k] / max(ms["fragments"], 1) for k in ("anchors", "positions", "placements")}
                     state = np.bincount(rec["state"], minlength=3)
                     r["states_search_on"] = {"nomatch": int(state[0]), "unique": int(state[1]), "nonunique": int(state[2])}
+                if args.insert_hist and hasattr(m, "insert_hist"):       # the histogram of the outer distances of the records left on the device
+                    lens = torch.full((n,), patl, dtype=torch.int32, device=dev)
+                    one = rec_dev.clone()
+                    w = one.view(torch.int32).view(n, 10)                 # words 4, 5: pos1, pos2; word 9: k2 | inverted1 << 8 | state << 16
+                    w[:, 4] = torch.arange(n, dtype=torch.int32, device=dev)
+                    w[:, 5] = w[:, 4] + (300 - patl)
+                    w[:, 9] = rlib.PAIR_UNIQUE << 16
+                    copy_to = torch.empty_like(rec_dev)
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    reps = 10
+
+                    def copy_ms(src):
+                        e0.record(); copy_to.copy_(src); e1.record(); e1.synchronize()
+                        return e0.elapsed_time(e1)
+                    ih = {"reps": reps, "record_bytes": n * 40}
+                    for n_bins in (hi_ins + 2, 1002, 16384):
+                        hist = torch.zeros(n_bins, dtype=torch.int64, device=dev)
+                        leg = {}
+                        for name, src in (("workload", rec_dev), ("one_bin", one)):
+                            m.insert_hist(src, lens, lens, n_bins, hist=hist, fresh=True)       # warm-up
+                            copy_ms(src)
+                            tk_, tc_ = [], []
+                            for _ in range(reps):                       # kernel and copy alternate
+                                m.insert_stats(reset=True)
+                                m.insert_hist(src, lens, lens, n_bins, hist=hist, fresh=True)
+                                tk_.append(m.insert_stats()["kernel_ms"])
+                                tc_.append(copy_ms(src))
+                            st = m.insert_stats()
+                            leg[name] = {"kernel_ms": min(tk_), "kernel_ms_median": sorted(tk_)[reps // 2], "copy_d2d_ms": min(tc_),
+                                         "copy_d2d_ms_median": sorted(tc_)[reps // 2], "kernel_over_copy": min(tk_) / min(tc_),
+                                         "counted": st["counted"], "overflow": st["overflow"], "invalid": st["invalid"],
+                                         "non_zero_bins": int((hist != 0).sum())}
+                            if name == "workload":                      # the same histogram from torch
+                                sv = src.view(torch.int32).view(n, 10)
+                                uq = ((sv[:, 9] >> 16) & 255) == rlib.PAIR_UNIQUE
+                                p1, p2 = sv[:, 4].to(torch.int64) & 0xffffffff, sv[:, 5].to(torch.int64) & 0xffffffff
+                                outer = (torch.where(((sv[:, 9] >> 8) & 255) == 0, p2 - p1, p1 - p2) + patl)[uq]
+                                leg[name]["equals_torch_bincount"] = bool(torch.equal(torch.bincount(outer.clamp(max=n_bins - 1), minlength=n_bins), hist))
+                        leg["one_bin_over_workload"] = leg["one_bin"]["kernel_ms"] / leg["workload"]["kernel_ms"]
+                        ih["n_bins_%d" % n_bins] = leg
+                    r["insert_hist"] = ih
+                    del one, copy_to, lens, w
                 if args.singles and hasattr(m, "match_pairs_singles"):   # the pairs plus each mate's own placement record
                     sg_host = [m.host_alloc(n, rlib.SINGLE_DTYPE) for _ in range(2)]
                     sg_dev = [torch.empty(n * 16, dtype=torch.uint8, device=dev) for _ in range(2)]

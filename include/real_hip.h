@@ -434,6 +434,46 @@ typedef struct real_hip_single_stats {
 } real_hip_single_stats;
 int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
 
+/* ---- insert sizes: the histogram of the Unique fragments' outer distances, computed where the pair records live, and the
+ * insert bounds it suggests.  The OUTER DISTANCE of a record is r.pos + len_r - f.pos in 64-bit arithmetic, the quantity the
+ * insert bounds of CONCORDANT test; the forward mate f is mate 1 iff inverted1 == 0, r is the other one.  Only records with
+ * state == REAL_HIP_PAIR_UNIQUE count.  hist[d] counts the records with outer == d for d < n_bins - 1, hist[n_bins - 1]
+ * those with outer >= n_bins - 1 (the overflow bin).  A Unique record that is no valid placement -- the forward mate starts
+ * behind the reverse one, or the reverse mate ends before the forward one starts -- goes nowhere in hist and is counted as
+ * `invalid` in the stats: sum(hist) is the number of valid Unique records.  The counts are integers and a function of the
+ * set of records alone (nothing depends on lanes, blocks or the order of the records).
+ * fresh != 0: hist is output only; 0: the counts are added to what hist holds (the next batch, the next call).  on_device
+ * 0: all pointers host memory (copied), 1: all device pointers, hist included.  n_bins in 2 .. REAL_HIP_INSERT_HIST_MAX_BINS,
+ * else REAL_HIP_E_INVALID; n_pairs == 0 is valid (a fresh hist is cleared).  Needs neither text nor index.             */
+#define REAL_HIP_INSERT_HIST_MAX_BINS 16384u   /* one block's private histogram sits in LDS: 64 KiB of the CU's 160 */
+#define REAL_HIP_INSERT_MIN_COUNT 32u          /* the fewest valid Unique records `real` takes insert bounds from   */
+int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair *pairs, const uint32_t *len1, const uint32_t *len2,
+                              uint64_t n_pairs, int on_device, int fresh, uint32_t n_bins, uint64_t *hist);
+/* Insert bounds from a histogram by the quartile rule BWA-MEM uses for its mapping bounds; host only, integers only.
+ * n = sum(hist); q_j (j = 1, 2, 3) is the smallest d with hist[0] + .. + hist[d] >= (j * n + 3) / 4 (integer division);
+ * iqr = q3 - q1; low = q1 - min(q1, iqr_mult * iqr); high = min(UINT32_MAX, q3 + iqr_mult * iqr), formed in 64 bits.
+ * `real` calls it with iqr_mult = 3.  n < min_count (or n == 0): REAL_HIP_E_STATE; q3 in the overflow bin (the histogram is too
+ * narrow to say): REAL_HIP_E_OVERFLOW; null pointers, a wrong struct_size or n_bins < 2: REAL_HIP_E_INVALID.            */
+typedef struct real_hip_insert_estimate {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_insert_estimate), 0                          */
+    uint64_t n;                     /* sum(hist)                                                      */
+    uint32_t q1, median, q3;        /* the quartiles of the outer distance                            */
+    uint32_t low, high;             /* the suggested bounds, inclusive                                */
+    uint32_t pad;                   /* 0                                                              */
+} real_hip_insert_estimate;
+int real_hip_insert_bounds(const uint64_t *hist, uint32_t n_bins, uint64_t min_count, uint32_t iqr_mult, real_hip_insert_estimate *out);
+/* work of the histogram, accumulated since the last reset; kernel_ms: HIP events on the ctx's stream around the kernel  */
+typedef struct real_hip_insert_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_insert_stats), 0                             */
+    uint64_t records;       /* records handed in                                                      */
+    uint64_t counted;       /* valid Unique records: what was added to hist, the overflow bin included */
+    uint64_t overflow;      /* of those, the ones that went to the overflow bin                       */
+    uint64_t invalid;       /* Unique records that are no valid placement                             */
+    uint64_t launches;      /* kernels launched                                                       */
+    double   kernel_ms;
+} real_hip_insert_stats;
+int real_hip_insert_stats_get(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

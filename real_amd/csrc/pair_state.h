@@ -12,6 +12,8 @@
 // real_hip_hit as a uint4: x read, y pos, z score bits, w frag:16 | k:8 | inverted:8.
 // Hit a of mate 1 and hit b of mate 2 (read lengths la, lb) are concordant: same fragment, opposite strands, the forward
 // hit neither starts nor ends behind the reverse one, outer distance within the bounds.  outer: r.pos + len_r - f.pos
+// the outer distance of a forward placement at fp and a reverse one of len_r bases at rp (64-bit: positions reach 2^32)
+static __device__ __forceinline__ uint64_t pair_outer(uint64_t fp, uint64_t rp, uint32_t len_r) { return rp + len_r - fp; }
 static __device__ __forceinline__ bool pair_concordant(const uint4 a, const uint4 b, uint32_t la, uint32_t lb, uint32_t min_insert,
                                                        uint32_t max_insert, uint64_t &outer)
 {
@@ -21,7 +23,7 @@ static __device__ __forceinline__ bool pair_concordant(const uint4 a, const uint
     const uint64_t fp = a_fwd ? a.y : b.y, rp = a_fwd ? b.y : a.y;
     const uint64_t fe = fp + (a_fwd ? la : lb), re = rp + (a_fwd ? lb : la);
     if (fp > rp || fe > re) return false;
-    outer = re - fp;
+    outer = pair_outer(fp, rp, a_fwd ? lb : la);
     return outer >= min_insert && outer <= max_insert;
 }
 

@@ -99,6 +99,7 @@ void rh_time_resolve(real_hip_ctx *c)
                 if (p.which == RH_K_MATE_SEARCH) c->ms_kernel_ms += ms;
                 else if (p.which == RH_K_PAIR_ALL) c->pa_kernel_ms += ms;
                 else if (p.which == RH_K_SINGLE) c->sg_kernel_ms += ms;
+                else if (p.which == RH_K_INSERT_HIST) c->ih_kernel_ms += ms;
                 else { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
             }
             c->ev_pool.push_back(p.a);
@@ -225,7 +226,8 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
     DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats,
                     &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats, &c->pa_cnt, &c->pa_off, &c->pa_out, &c->pa_stats,
-                    &c->sg_rec[0], &c->sg_rec[1], &c->sg_list, &c->sg_stats};
+                    &c->sg_rec[0], &c->sg_rec[1], &c->sg_list, &c->sg_stats,
+                    &c->ih_rec, &c->ih_len[0], &c->ih_len[1], &c->ih_hist, &c->ih_stats};
     for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
@@ -1033,6 +1035,79 @@ extern "C" int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stat
     RH_ENTER(ctx);
     if (out && out->struct_size != sizeof(real_hip_single_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "single stats struct_size", hipSuccess);
     return rh_single_stats(ctx, out, reset);
+}
+
+// ---- insert sizes (insert_hist.hip): staging as real_hip_pair_hits does it
+extern "C" int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair *pairs, const uint32_t *len1, const uint32_t *len2,
+                                         uint64_t n_pairs, int on_device, int fresh, uint32_t n_bins, uint64_t *hist)
+{
+    RH_ENTER(ctx);
+    if (n_bins < 2 || n_bins > REAL_HIP_INSERT_HIST_MAX_BINS)
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "n_bins must be in 2 .. REAL_HIP_INSERT_HIST_MAX_BINS", hipSuccess);
+    const uint64_t n = n_pairs;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
+    if (!hist || (n && (!pairs || !len1 || !len2))) return rh_fail(ctx, REAL_HIP_E_INVALID, "null pairs / lengths / hist", hipSuccess);
+    if (on_device && ((uintptr_t)pairs & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the pair records must be 8-byte aligned", hipSuccess);
+    int rc;
+    const real_hip_pair *d_pairs = pairs;
+    const uint32_t *d_len[2] = {len1, len2};
+    uint64_t *d_hist = hist;
+    const size_t hist_bytes = (size_t)n_bins * 8;
+    if (!on_device) {
+        if ((rc = rh_reserve(ctx, ctx->ih_hist, hist_bytes))) return rc;
+        d_hist = (uint64_t *)ctx->ih_hist.p;
+        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (n) {
+            if ((rc = rh_reserve(ctx, ctx->ih_rec, n * sizeof(real_hip_pair)))) return rc;
+            RH_HIP(ctx, hipMemcpyAsync(ctx->ih_rec.p, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
+            d_pairs = (const real_hip_pair *)ctx->ih_rec.p;
+            for (int m = 0; m < 2; ++m) {
+                if ((rc = rh_reserve(ctx, ctx->ih_len[m], n * 4))) return rc;
+                RH_HIP(ctx, hipMemcpyAsync(ctx->ih_len[m].p, m ? len2 : len1, n * 4, hipMemcpyHostToDevice, ctx->stream));
+                d_len[m] = (const uint32_t *)ctx->ih_len[m].p;
+            }
+        }
+    }
+    if (fresh) RH_HIP(ctx, hipMemsetAsync(d_hist, 0, hist_bytes, ctx->stream));
+    rc = rh_launch_insert_hist(ctx, d_pairs, d_len[0], d_len[1], n, n_bins, d_hist);
+    if (!rc && !on_device) {
+        hipError_t e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, ctx->stream);
+        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the histogram", e);
+    }
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_insert_stats_get(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_insert_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "insert stats struct_size", hipSuccess);
+    return rh_insert_stats(ctx, out, reset);
+}
+
+// the quartile rule on a histogram: host only, integers only (include/real_hip.h)
+extern "C" int real_hip_insert_bounds(const uint64_t *hist, uint32_t n_bins, uint64_t min_count, uint32_t iqr_mult, real_hip_insert_estimate *out)
+{
+    if (!hist || !out || out->struct_size != sizeof(real_hip_insert_estimate) || n_bins < 2) return REAL_HIP_E_INVALID;
+    uint64_t n = 0;
+    for (uint32_t d = 0; d < n_bins; ++d) n += hist[d];
+    out->reserved = 0; out->pad = 0;
+    out->n = n;
+    out->q1 = out->median = out->q3 = out->low = out->high = 0;
+    if (n < min_count || !n) return REAL_HIP_E_STATE;
+    uint32_t q[3] = {0, 0, 0};
+    uint64_t cum = 0;
+    uint32_t j = 0;
+    for (uint32_t d = 0; d < n_bins && j < 3; ++d) {
+        cum += hist[d];
+        while (j < 3 && cum >= ((uint64_t)(j + 1) * n + 3) / 4) q[j++] = d;
+    }
+    out->q1 = q[0]; out->median = q[1]; out->q3 = q[2];
+    if (q[2] == n_bins - 1) return REAL_HIP_E_OVERFLOW;
+    const uint64_t reach = (uint64_t)iqr_mult * (q[2] - q[0]);
+    out->low = q[0] - (uint32_t)(reach < q[0] ? reach : q[0]);
+    const uint64_t high = q[2] + reach;
+    out->high = high > 0xffffffffull ? 0xffffffffu : (uint32_t)high;
+    return REAL_HIP_OK;
 }
 
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]

@@ -265,6 +265,12 @@ struct real_hip_ctx {
     uint64_t sg_reads = 0, sg_launches = 0;
     double   sg_kernel_ms = 0;
 
+    // insert-size histogram (insert_hist.hip): the staged records, lengths and histogram when the caller's are host memory,
+    // striped statistics, the event times of its launches
+    DevBuf ih_rec, ih_len[2], ih_hist, ih_stats;
+    uint64_t ih_records = 0, ih_launches = 0;
+    double   ih_kernel_ms = 0;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -362,6 +368,13 @@ int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset
 #define RH_K_SINGLE (-3) /* rh_time_begin: the time goes to ctx->sg_kernel_ms */
 int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
 int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
+
+// ---- insert-size histogram (insert_hist.hip) ----------------------------------------
+#define RH_K_INSERT_HIST (-4) /* rh_time_begin: the time goes to ctx->ih_kernel_ms */
+// d_hist += the histogram of n records, all arrays on the device; asynchronous on the ctx's stream
+int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const uint32_t *d_len1, const uint32_t *d_len2, uint64_t n,
+                          uint32_t n_bins, uint64_t *d_hist);
+int rh_insert_stats(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

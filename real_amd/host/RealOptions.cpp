@@ -49,6 +49,14 @@ void RealOptions::printHelp() const
               << "-unpaired <file: with -p2, receives the mates of the fragments WITHOUT a concordant pair (after the last genome file, and\n"
               << "   after the search with -mate_search 1) that are placed uniquely on their own: mate 1's line, then mate 2's, as the\n"
               << "   single-end mode prints that hit; -o is unchanged; not with -pairs_all 1>\n"
+              << "-insert_hist <file: with -p2, receives the histogram of the outer distances of the Unique fragments (after the last\n"
+              << "   genome file) as lines outer<TAB>count, the last bin (-insert_max + 1) holding what lies beyond; the quartiles go to\n"
+              << "   standard error; -o is unchanged; not with -pairs_all 1>\n"
+              << "-insert_auto <N: with -p2, estimate the insert bounds from the first N fragments before the run: the quartiles q1, q3 of\n"
+              << "   their Unique outer distances give [q1 - 3 (q3 - q1), q3 + 3 (q3 - q1)], cut to -insert_min .. -insert_max; the estimate\n"
+              << "   judges uniqueness in the FIRST genome file only and under the window -insert_min .. -insert_max; not with\n"
+              << "   -pairs_all 1, default=0 (off)>\n"
+              << "   (-insert_hist and -insert_auto take an -insert_max of at most " << (REAL_HIP_INSERT_HIST_MAX_BINS - 2) << ")\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -111,6 +119,8 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pairs_all") { pairs_all = atoi(need("-pairs_all").c_str()) != 0; pairs_all_given = true; i += 2; }
         else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
         else if (a == "-unpaired") { unpairedfilename = need("-unpaired"); unpaired_given = true; i += 2; }
+        else if (a == "-insert_hist") { inserthistfilename = need("-insert_hist"); insert_flags_given = true; i += 2; }
+        else if (a == "-insert_auto") { insert_auto = strtoull(need("-insert_auto").c_str(), 0, 10); insert_flags_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -184,7 +194,18 @@ RealOptions::RealOptions(int argc, char *argv[])
             throw std::runtime_error("-unpaired lists the mates of the fragments without a pair: it cannot be combined with -pairs_all 1.");
         if (unpaired_given && (unpairedfilename.empty() || unpairedfilename == outputfilename))
             throw std::runtime_error("-unpaired must name a file of its own: it names the same file as -o.");
+        if (insert_flags_given) {
+            const bool hist = !inserthistfilename.empty();
+            if (pairs_all) throw std::runtime_error("-insert_hist / -insert_auto look at the unique placement of a fragment: they cannot be combined with -pairs_all 1.");
+            if ((hist || insert_auto) && insert_max > REAL_HIP_INSERT_HIST_MAX_BINS - 2)
+                throw std::runtime_error("-insert_hist / -insert_auto take an -insert_max of at most " + std::to_string(REAL_HIP_INSERT_HIST_MAX_BINS - 2) + ".");
+            if (hist && inserthistfilename == outputfilename) throw std::runtime_error("-insert_hist must name a file of its own: it names the same file as -o.");
+            if (hist && unpaired_given && inserthistfilename == unpairedfilename)
+                throw std::runtime_error("-insert_hist must name a file of its own: it names the same file as -unpaired.");
+        }
         fastq2 = isFastQ(pattern2filename);
+    } else if (insert_flags_given) {
+        throw std::runtime_error("-insert_hist / -insert_auto are only meaningful with -p2 (paired-end reads).");
     } else if (mate_search_given) {
         throw std::runtime_error("-mate_search / -mate_search_anchors are only meaningful with -p2 (paired-end reads).");
     } else if (unpaired_given) {

@@ -54,6 +54,9 @@ struct RealOptions {
     std::string unpairedfilename;     // -unpaired: the file that receives the Unique mates of the fragments without a pair (real_hip_match_pairs_singles)
     bool unpaired_given = false;      // (the flag was on the command line: an error without -p2)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
+    std::string inserthistfilename;   // -insert_hist: the file that receives the histogram of the Unique fragments' outer distances (real_hip_pair_insert_hist)
+    uint64_t insert_auto = 0;         // -insert_auto: fragments the insert bounds are estimated from before the run (real_hip_insert_bounds), 0 = off
+    bool insert_flags_given = false;  // (either flag was on the command line: an error without -p2)
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)
 
     RealOptions() {}

@@ -6,6 +6,7 @@
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
+//   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 //   host_selftest lines <reads.fq> <outdir>       -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
 #include <cstdio>
@@ -253,6 +254,11 @@ int main(int argc, char **argv)
         if (cmd == "unpaired_options") { // -unpaired
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.unpairedfilename.empty() ? "." : o.unpairedfilename) << "\n";
+            return 0;
+        }
+        if (cmd == "insert_options") { // -insert_hist, -insert_auto
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.inserthistfilename.empty() ? "." : o.inserthistfilename) << " " << o.insert_auto << " " << o.insert_min << " " << o.insert_max << "\n";
             return 0;
         }
         if (cmd == "pairs_all_options") { // -pairs_all

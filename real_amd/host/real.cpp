@@ -603,11 +603,19 @@ real_hip_pair_params pairParams(const RealOptions &o)
 
 // The next block of each of the two mate files, read in step by the host reader: read i of each are mates.  Returns the
 // number of fragments, 0 at the end of both.
-uint64_t fillMates(const RealOptions &o, ReadReader &r1, ReadReader &r2, ReadBlock &b1, ReadBlock &b2, bool want_ids)
+uint64_t fillMates(const RealOptions &o, ReadReader &r1, ReadReader &r2, ReadBlock &b1, ReadBlock &b2, bool want_ids, uint64_t max_reads = 0)
 {
-    const uint64_t n1 = r1.fillBlock(b1, o.batch_reads, want_ids), n2 = r2.fillBlock(b2, o.batch_reads, want_ids);
+    if (!max_reads) max_reads = o.batch_reads;
+    const uint64_t n1 = r1.fillBlock(b1, max_reads, want_ids), n2 = r2.fillBlock(b2, max_reads, want_ids);
     if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
     return n1;
+}
+
+// the lengths of a block's reads, from its offsets
+void readLengths(const ReadBlock &b, std::vector<uint32_t> &len)
+{
+    len.resize(b.size());
+    for (uint64_t i = 0; i < b.size(); ++i) len[i] = (uint32_t)(b.offsets[i + 1] - b.offsets[i]);
 }
 
 // The two lines of a pair (a real_hip_pair or a real_hip_pair_hit): mate 1, then mate 2 on the other strand; fs is the
@@ -626,6 +634,9 @@ inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, b
 // -unpaired <file>: real_hip_match_pairs_singles folds each mate's own hits beside the pairs; a fragment whose final pair
 // state is NoMatch writes to <file> the line of mate 1 if it is Unique on its own, then mate 2's likewise, as the
 // single-end mode would print that hit.  The main output does not change.
+// -insert_hist <file>: the histogram of the final Unique records' outer distances (real_hip_pair_insert_hist in the output
+// pass) as lines outer<TAB>count, its quartiles on standard error.  -insert_auto N: the bounds of the run come from the
+// first N fragments against the first genome file (real_hip_insert_bounds), cut to -insert_min .. -insert_max.
 int matchPairs(const RealOptions &o)
 {
     Timers T;
@@ -633,7 +644,7 @@ int matchPairs(const RealOptions &o)
     const std::vector<std::string> files = genomeFiles(o, "more than 64 text files");
     CtxVec ctx = makeContexts(o);
     real_hip_ctx *h = ctx[0]->h;
-    const real_hip_pair_params pp = pairParams(o);
+    real_hip_pair_params pp = pairParams(o); // (-insert_auto narrows the bounds before the first batch of the run)
     real_hip_mate_search_params sp; // -mate_search 1: the search behind the join
     memset(&sp, 0, sizeof sp);
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
@@ -643,7 +654,58 @@ int matchPairs(const RealOptions &o)
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
+    // the call of a batch, for the run and for the probe of -insert_auto
+    auto matchBatch = [&](const real_hip_batch &rb1, const real_hip_batch &rb2, real_hip_pair *P, real_hip_single *S1, real_hip_single *S2) {
+        if (unpaired) check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2), "real_hip_match_pairs_singles");
+        else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, P), "real_hip_match_pairs_search");
+        else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, P), "real_hip_match_pairs");
+    };
+    // the histogram of the records P of the fragments in b1 / b2 (added to hist unless fresh)
+    std::vector<uint32_t> len1, len2;
+    auto insertHist = [&](const real_hip_pair *P, uint64_t n, bool fresh, std::vector<uint64_t> &hist) {
+        readLengths(b1, len1); readLengths(b2, len2);
+        check(h, real_hip_pair_insert_hist(h, P, len1.data(), len2.data(), n, 0, fresh, (uint32_t)hist.size(), hist.data()), "real_hip_pair_insert_hist");
+    };
+    // -insert_auto N: the first N fragments against the first genome file under the window -insert_min .. -insert_max; the
+    // quartiles of their Unique outer distances give the bounds of the run
+    auto estimateBounds = [&]() {
+        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+        std::vector<real_hip_pair> probe;
+        std::vector<real_hip_single> ps1, ps2;
+        std::vector<uint64_t> hist((size_t)o.insert_max + 2, 0);
+        uint64_t seen = 0;
+        while (seen < o.insert_auto) {
+            const uint64_t n = fillMates(o, r1, r2, b1, b2, false, std::min<uint64_t>(o.batch_reads, o.insert_auto - seen));
+            if (!n) break;
+            probe.resize(n);
+            if (unpaired) { ps1.resize(n); ps2.resize(n); }
+            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            rb1.fresh = rb2.fresh = 1;
+            matchBatch(rb1, rb2, probe.data(), ps1.data(), ps2.data());
+            insertHist(probe.data(), n, seen == 0, hist);
+            seen += n;
+        }
+        real_hip_insert_estimate est;
+        memset(&est, 0, sizeof est);
+        est.struct_size = sizeof est;
+        const int rc = real_hip_insert_bounds(hist.data(), (uint32_t)hist.size(), REAL_HIP_INSERT_MIN_COUNT, 3, &est);
+        if (rc == REAL_HIP_E_STATE)
+            throw std::runtime_error("-insert_auto: only " + std::to_string(est.n) + " of the first " + std::to_string(seen) + " fragments are placed uniquely (" +
+                                     std::to_string(REAL_HIP_INSERT_MIN_COUNT) + " are needed): give the bounds explicitly with -insert_min / -insert_max.");
+        if (rc == REAL_HIP_E_OVERFLOW)
+            throw std::runtime_error("-insert_auto: the third quartile of the outer distances lies beyond -insert_max: give the bounds explicitly with -insert_min / -insert_max.");
+        if (rc) throw std::runtime_error("real_hip_insert_bounds failed");
+        pp.min_insert = std::max(o.insert_min, est.low);
+        pp.max_insert = std::min(o.insert_max, est.high);
+        std::cerr << "insert size estimate: fragments=" << seen << " unique=" << est.n << " q1=" << est.q1 << " median=" << est.median << " q3=" << est.q3
+                  << " bounds=[" << pp.min_insert << ", " << pp.max_insert << "]" << std::endl;
+    };
     for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, kSayLast | kOneBlock, T, &RS, [&](Resident &) {
+        if (fi == 0 && o.insert_auto) {
+            const double tm = now_s();
+            estimateBounds();
+            T.match += now_s() - tm;
+        }
         ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
@@ -656,11 +718,7 @@ int matchPairs(const RealOptions &o)
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
             const double tm = now_s();
-            if (unpaired)
-                check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, pairs.data() + seen, singles1.data() + seen,
-                                                      singles2.data() + seen), "real_hip_match_pairs_singles");
-            else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, pairs.data() + seen), "real_hip_match_pairs_search");
-            else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, pairs.data() + seen), "real_hip_match_pairs");
+            matchBatch(rb1, rb2, pairs.data() + seen, unpaired ? singles1.data() + seen : nullptr, unpaired ? singles2.data() + seen : nullptr);
             T.match += now_s() - tm;
             seen += n;
         }
@@ -671,6 +729,11 @@ int matchPairs(const RealOptions &o)
     OutFile out(o.outputfilename);
     std::unique_ptr<OutFile> uout(unpaired ? new OutFile(o.unpairedfilename, true) : nullptr);
     uint64_t unique = 0, base = 0;
+    // -insert_hist <file>: the outer distances of the final Unique records, batch by batch (the last bin: what lies beyond the bounds)
+    const bool insert_hist = !o.inserthistfilename.empty();
+    std::vector<uint64_t> hist(insert_hist ? (size_t)pp.max_insert + 2 : 0, 0);
+    FILE *hist_file = insert_hist ? fopen(o.inserthistfilename.c_str(), "wb") : nullptr; // (opened before the pass: a path that cannot be written fails here)
+    if (insert_hist && !hist_file) throw std::runtime_error("cannot open the -insert_hist file " + o.inserthistfilename);
     // the line of a mate that is placed uniquely on its own, as the single-end mode prints that hit
     auto singleLine = [&](std::string &s, const ReadView &r, const real_hip_single &S) {
         if (REAL_HIP_SINGLE_STATE(S.tag) != REAL_HIP_PAIR_UNIQUE) return;
@@ -683,6 +746,7 @@ int matchPairs(const RealOptions &o)
         const uint64_t n = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
         if (n != n2 || base + n > numpat) throw std::runtime_error("the read files changed between two passes");
         if (!n) break;
+        if (insert_hist) insertHist(pairs.data() + base, n, base == 0, hist);
         if (unpaired)
             formatAndWrite(n, uout->file(), T, [&](uint64_t i, std::string &s) {
                 if (pairs[base + i].state != REAL_HIP_PAIR_NOMATCH) return;
@@ -707,6 +771,21 @@ int matchPairs(const RealOptions &o)
             if (pairs[i].state == REAL_HIP_PAIR_NOMATCH)
                 mates += (REAL_HIP_SINGLE_STATE(singles1[i].tag) == REAL_HIP_PAIR_UNIQUE) + (REAL_HIP_SINGLE_STATE(singles2[i].tag) == REAL_HIP_PAIR_UNIQUE);
         std::cerr << "unpaired mates: " << mates << std::endl;
+    }
+    if (insert_hist) {
+        bool ok = true;
+        for (size_t d = 0; d < hist.size(); ++d)
+            if (hist[d]) ok = fprintf(hist_file, "%zu\t%llu\n", d, (unsigned long long)hist[d]) > 0 && ok;
+        if ((fclose(hist_file) != 0) || !ok) throw std::runtime_error("write to the -insert_hist file failed");
+        real_hip_insert_estimate est;
+        memset(&est, 0, sizeof est);
+        est.struct_size = sizeof est;
+        const int rc = real_hip_insert_bounds(hist.data(), (uint32_t)hist.size(), REAL_HIP_INSERT_MIN_COUNT, 3, &est);
+        if (rc == REAL_HIP_E_STATE)
+            std::cerr << "insert size: fewer than " << REAL_HIP_INSERT_MIN_COUNT << " unique fragments (n=" << est.n << "), no quartiles" << std::endl;
+        else if (rc == REAL_HIP_OK || rc == REAL_HIP_E_OVERFLOW)
+            std::cerr << "insert size: n=" << est.n << " q1=" << est.q1 << " median=" << est.median << " q3=" << est.q3 << std::endl;
+        else throw std::runtime_error("real_hip_insert_bounds failed");
     }
     T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;

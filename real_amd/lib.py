@@ -25,6 +25,8 @@ REAL_HIP_E_UNSUPPORTED = -6
 REAL_HIP_MAX_PATL = 320
 REAL_HIP_MAX_PATL_LONG = 16384
 REAL_HIP_MATE_SEARCH_MAX_INSERT = 4096   # the widest insert bound the mate search takes
+REAL_HIP_INSERT_HIST_MAX_BINS = 16384    # the most bins of an insert-size histogram
+REAL_HIP_INSERT_MIN_COUNT = 32           # the fewest valid Unique records `real` takes insert bounds from
 
 K_MATCH_UNIQUE, K_MATCH_ALL, K_ALL_SORT, K_INDEX, K_MATCH_REPEAT, K_PARSE = range(6)
 K_PAIR, K_PAIR_WAVE = 6, 7          # the paired-end join: lane per fragment, wave per handed-over fragment
@@ -44,6 +46,7 @@ ABI_SYMBOLS = [
     "real_hip_pair_search", "real_hip_match_pairs_search", "real_hip_mate_search_stats_get",
     "real_hip_pair_all_hits", "real_hip_match_pairs_all", "real_hip_pair_all_stats_get",
     "real_hip_single_hits", "real_hip_match_pairs_singles", "real_hip_single_stats_get",
+    "real_hip_pair_insert_hist", "real_hip_insert_bounds", "real_hip_insert_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -110,6 +113,16 @@ class RealHipPairAllStats(C.Structure):
 class RealHipSingleStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("reads", C.c_uint64), ("hits", C.c_uint64),
                 ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+class RealHipInsertEstimate(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("n", C.c_uint64), ("q1", C.c_uint32), ("median", C.c_uint32),
+                ("q3", C.c_uint32), ("low", C.c_uint32), ("high", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class RealHipInsertStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("counted", C.c_uint64),
+                ("overflow", C.c_uint64), ("invalid", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class RealHipPairHit(C.Structure):
@@ -222,6 +235,9 @@ def load():
     L.real_hip_match_pairs_singles.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
                                                C.POINTER(RealHipMateSearchParams), vp, vp, vp]
     L.real_hip_single_stats_get.argtypes = [vp, C.POINTER(RealHipSingleStats), C.c_int]
+    L.real_hip_pair_insert_hist.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, u32, vp]
+    L.real_hip_insert_bounds.argtypes = [vp, u32, u64, u32, C.POINTER(RealHipInsertEstimate)]
+    L.real_hip_insert_stats_get.argtypes = [vp, C.POINTER(RealHipInsertStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

@@ -55,6 +55,8 @@ class RealOptions:
     pairs_all: bool = False         # -pairs_all: with -p2, print every concordant pair of a fragment instead of the unique one
     pairs_all_given: bool = False   # (the flag was on the command line: an error without -p2)
     unpairedfilename: str = ""      # -unpaired: with -p2, the file that receives the Unique mates of the fragments without a pair
+    inserthistfilename: str = ""    # -insert_hist: with -p2, the file that receives the histogram of the Unique fragments' outer distances
+    insert_auto: int = 0            # -insert_auto: with -p2, fragments the insert bounds are estimated from before the run (0: off)
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -84,6 +86,15 @@ class RealOptions:
                 raise ValueError("-unpaired lists the mates of the fragments without a pair: it cannot be combined with -pairs_all 1")
             if self.unpairedfilename and self.unpairedfilename == self.outputfilename:
                 raise ValueError("-unpaired names the same file as -o")
+            if self.inserthistfilename or self.insert_auto:
+                if self.pairs_all:
+                    raise ValueError("-insert_hist / -insert_auto cannot be combined with -pairs_all 1")
+                if self.insert_max > _lib.REAL_HIP_INSERT_HIST_MAX_BINS - 2:
+                    raise ValueError("-insert_hist / -insert_auto take an -insert_max of at most %d" % (_lib.REAL_HIP_INSERT_HIST_MAX_BINS - 2))
+                if self.inserthistfilename and self.inserthistfilename in (self.outputfilename, self.unpairedfilename):
+                    raise ValueError("-insert_hist names the same file as -o or -unpaired")
+        elif self.inserthistfilename or self.insert_auto:
+            raise ValueError("-insert_hist / -insert_auto need -p2 (paired-end reads)")
         elif self.unpairedfilename:
             raise ValueError("-unpaired needs -p2 (paired-end reads)")
         elif self.mate_search or self.mate_search_anchors:
@@ -119,7 +130,8 @@ class RealOptions:
                  "-filter_level": ("filter_level", int), "-p2": ("pattern2filename", str), "-insert_min": ("insert_min", int),
                  "-insert_max": ("insert_max", int), "-gpus": ("gpus", int),
                  "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int),
-                 "-pairs_all": ("pairs_all", lambda v: bool(int(v))), "-unpaired": ("unpairedfilename", str)}
+                 "-pairs_all": ("pairs_all", lambda v: bool(int(v))), "-unpaired": ("unpairedfilename", str),
+                 "-insert_hist": ("inserthistfilename", str), "-insert_auto": ("insert_auto", int)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -646,6 +658,60 @@ class PairMatcher(AllMatcher):
         self._check(self._L.real_hip_single_stats_get(self._h, C.byref(st), int(reset)))
         return {"reads": int(st.reads), "hits": int(st.hits), "handed_over": int(st.handed_over), "launches": int(st.launches),
                 "kernel_ms": float(st.kernel_ms)}
+
+    # -- insert sizes: the histogram of the Unique fragments' outer distances, and the bounds it suggests --
+    def insert_hist(self, pairs, len1, len2, n_bins: int, hist=None, fresh: Optional[bool] = None):
+        """real_hip_pair_insert_hist: hist[d] = Unique records of `pairs` with outer distance d, the last bin what lies beyond
+        (numpy arrays of lib.PAIR_DTYPE / uint32 give a numpy uint64 histogram; device torch tensors of the same layout, all
+        of one kind, need `hist` as a device tensor of n_bins 64-bit counts).  hist given: the counts are added to it unless
+        fresh=True."""
+        on_device = bool(getattr(len1, "is_cuda", False))
+        if not on_device:
+            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
+            len1, len2 = np.ascontiguousarray(len1, dtype=np.uint32), np.ascontiguousarray(len2, dtype=np.uint32)
+            n = int(pairs.shape[0])
+        else:
+            n = int(pairs.numel() * pairs.element_size() // 40)
+        if int(len1.shape[0]) != n or int(len2.shape[0]) != n:
+            raise ValueError("the records and the lengths describe different numbers of fragments")
+        if fresh is None:
+            fresh = hist is None
+        if hist is None:
+            if on_device:
+                raise ValueError("device inputs need a device tensor for the histogram")
+            hist = np.zeros(int(n_bins), dtype=np.uint64)
+        elif not on_device and (not isinstance(hist, np.ndarray) or hist.dtype != np.uint64 or not hist.flags.c_contiguous):
+            raise ValueError("hist must be a contiguous numpy uint64 array")
+        if int(hist.shape[0]) != int(n_bins):
+            raise ValueError("hist must hold n_bins counts")
+        self.sync_inputs(pairs, len1, len2, hist)
+        self._check(self._L.real_hip_pair_insert_hist(self._h, _ptr(pairs), _ptr(len1), _ptr(len2), n, int(on_device), int(bool(fresh)),
+                                                      int(n_bins), _ptr(hist)))
+        return hist
+
+    @staticmethod
+    def insert_bounds(hist, min_count: int = _lib.REAL_HIP_INSERT_MIN_COUNT, iqr_mult: int = 3) -> dict:
+        """real_hip_insert_bounds: the quartiles of a histogram and the bounds q1 - iqr_mult * iqr .. q3 + iqr_mult * iqr.
+        Raises RealHipError with status REAL_HIP_E_STATE (fewer than min_count records) or REAL_HIP_E_OVERFLOW (q3 in the
+        overflow bin)."""
+        if hasattr(hist, "cpu"):
+            hist = hist.cpu().numpy().view(np.uint64)
+        hist = np.ascontiguousarray(hist, dtype=np.uint64)
+        est = _lib.RealHipInsertEstimate()
+        est.struct_size = C.sizeof(_lib.RealHipInsertEstimate)
+        L = _lib.load()
+        rc = L.real_hip_insert_bounds(hist.ctypes.data, int(hist.shape[0]), int(min_count), int(iqr_mult), C.byref(est))
+        if rc != _lib.REAL_HIP_OK:
+            raise RealHipError(rc, {_lib.REAL_HIP_E_STATE: "too few records for insert bounds (n = %d)" % est.n,
+                                    _lib.REAL_HIP_E_OVERFLOW: "the third quartile lies in the overflow bin"}.get(rc, "invalid argument"))
+        return {"n": int(est.n), "q1": int(est.q1), "median": int(est.median), "q3": int(est.q3), "low": int(est.low), "high": int(est.high)}
+
+    def insert_stats(self, reset: bool = False) -> dict:
+        st = _lib.RealHipInsertStats()
+        st.struct_size = C.sizeof(_lib.RealHipInsertStats)
+        self._check(self._L.real_hip_insert_stats_get(self._h, C.byref(st), int(reset)))
+        return {"records": int(st.records), "counted": int(st.counted), "overflow": int(st.overflow), "invalid": int(st.invalid),
+                "launches": int(st.launches), "kernel_ms": float(st.kernel_ms)}
 
     def pair_stats(self, reset: bool = False) -> dict:
         st = _lib.RealHipPairStats()
