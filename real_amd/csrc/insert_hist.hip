@@ -93,35 +93,34 @@ int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     if (n_bins < 2 || n_bins > REAL_HIP_INSERT_HIST_MAX_BINS) return rh_fail(ctx, REAL_HIP_E_INVALID, "n_bins out of range", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->ih_stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->insert.stats, RH_PAIR_STRIPES, 0))) return rc;
     InsertArgs A;
     A.rec = (const uint2 *)d_pairs; A.len[0] = d_len1; A.len[1] = d_len2;
-    A.n = n; A.hist = (unsigned long long *)d_hist; A.stats = (unsigned long long *)ctx->ih_stats.p;
+    A.n = n; A.hist = (unsigned long long *)d_hist; A.stats = (unsigned long long *)ctx->insert.stats.p;
     A.n_bins = n_bins;
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n_cu < 1) n_cu = 256;
     const uint64_t resident = (uint64_t)n_cu * 2, need = (n + RH_IH_BLOCK - 1) / RH_IH_BLOCK;
     const unsigned blocks = (unsigned)(need < resident ? need : resident);
-    rh_time_begin(ctx, ctx->stream, RH_K_INSERT_HIST);
+    rh_time_begin(ctx, ctx->stream, ctx->insert);
     hipLaunchKernelGGL(insert_hist_kernel, dim3(blocks), dim3(RH_IH_BLOCK), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->ih_records += n;
-    ctx->ih_launches += 1;
+    ctx->insert.items += n;
+    ctx->insert.launches += 1;
     return REAL_HIP_OK;
 }
 
 int rh_insert_stats(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset)
 {
     uint64_t h[3];
+    RhStageCount was;
     int rc;
-    if ((rc = rh_stats_read(ctx, ctx->ih_stats, RH_PAIR_STRIPES, 3, reset, h))) return rc;
-    rh_time_resolve(ctx);
+    if ((rc = rh_stage_read(ctx, ctx->insert, RH_PAIR_STRIPES, 3, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
-        out->records = ctx->ih_records; out->counted = h[0]; out->overflow = h[1]; out->invalid = h[2];
-        out->launches = ctx->ih_launches; out->kernel_ms = ctx->ih_kernel_ms;
+        out->records = was.items; out->counted = h[0]; out->overflow = h[1]; out->invalid = h[2];
+        out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
-    if (reset) { ctx->ih_records = 0; ctx->ih_launches = 0; ctx->ih_kernel_ms = 0; }
     return REAL_HIP_OK;
 }

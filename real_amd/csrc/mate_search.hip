@@ -229,7 +229,7 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
     const size_t stat_bytes = (size_t)RH_MS_STRIPES * 16 * 8;
-    if ((rc = rh_stats_reserve(ctx, ctx->ms_stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
+    if ((rc = rh_stats_reserve(ctx, ctx->search.stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
     MateSearchArgs A;
     memset(&A, 0, sizeof A);
     A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p; A.t.frag_start = (const uint64_t *)ctx->frag.p;
@@ -237,21 +237,21 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
     A.b[0] = b1; A.b[1] = b2;
     A.L = L; // (its len[] may be null: the kernel takes the read lengths from the batches)
     A.n = n; A.pairs = d_pairs; A.LL = (const double *)ctx->LL.p;
-    A.stats = (unsigned long long *)ctx->ms_stats.p;
-    A.err_flags = (uint32_t *)((char *)ctx->ms_stats.p + stat_bytes);
+    A.stats = (unsigned long long *)ctx->search.stats.p;
+    A.err_flags = (uint32_t *)((char *)ctx->search.stats.p + stat_bytes);
     A.filter_mult = ctx->prm.filter_mult;
     A.fresh = fresh ? 1u : 0u; A.fileid = fileid; A.scores = ctx->prm.scores ? 1u : 0u;
     A.min_insert = pp.min_insert; A.max_insert = pp.max_insert; A.seedl = ctx->prm.seedl; A.totalkmax = ctx->prm.totalkmax;
     A.max_anchors = sp.max_anchors;
     RH_HIP(ctx, hipMemsetAsync(A.err_flags, 0, 4, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, RH_K_MATE_SEARCH);
+    rh_time_begin(ctx, ctx->stream, ctx->search);
     if (A.scores) hipLaunchKernelGGL(mate_search_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     else hipLaunchKernelGGL(mate_search_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
     RH_HIP(ctx, hipMemcpyAsync(&ctx->ms_err, A.err_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->ms_fragments += n;
-    ctx->ms_launches += 1;
+    ctx->search.items += n;
+    ctx->search.launches += 1;
     return REAL_HIP_OK;
 }
 
@@ -267,14 +267,13 @@ int rh_mate_search_finish(real_hip_ctx *ctx)
 int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)
 {
     uint64_t h[4];
+    RhStageCount was;
     int rc;
-    if ((rc = rh_stats_read(ctx, ctx->ms_stats, RH_MS_STRIPES, 4, reset, h))) return rc;
-    rh_time_resolve(ctx);
+    if ((rc = rh_stage_read(ctx, ctx->search, RH_MS_STRIPES, 4, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
-        out->fragments = ctx->ms_fragments; out->anchors = h[0]; out->anchors_skipped = h[1]; out->positions = h[2]; out->placements = h[3];
-        out->launches = ctx->ms_launches; out->kernel_ms = ctx->ms_kernel_ms;
+        out->fragments = was.items; out->anchors = h[0]; out->anchors_skipped = h[1]; out->positions = h[2]; out->placements = h[3];
+        out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
-    if (reset) { ctx->ms_fragments = 0; ctx->ms_launches = 0; ctx->ms_kernel_ms = 0; }
     return REAL_HIP_OK;
 }

@@ -121,7 +121,7 @@ static PairAllArgs pair_all_args(real_hip_ctx *ctx, const real_hip_pair_params &
     A.L = L; A.n = n;
     A.cnt = (uint64_t *)ctx->pa_cnt.p; A.off = d_off; A.out = nullptr; A.cap = 0;
     A.list_count = (unsigned long long *)ctx->pair_list.p; A.list = (uint32_t *)ctx->pair_list.p + 2;
-    A.stats = (unsigned long long *)ctx->pa_stats.p;
+    A.stats = (unsigned long long *)ctx->pair_all.stats.p;
     A.fileid = fileid; A.min_insert = pp.min_insert; A.max_insert = pp.max_insert;
     return A;
 }
@@ -131,20 +131,20 @@ int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const M
     *total = 0;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->pa_stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->pair_all.stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, ctx->pair_list, n * 4 + 8))) return rc;
     if ((rc = rh_reserve(ctx, ctx->pa_cnt, (n + 1) * 8))) return rc;
     const PairAllArgs A = pair_all_args(ctx, pp, L, n, 0, d_off);
     RH_HIP(ctx, hipMemsetAsync(ctx->pair_list.p, 0, 8, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, RH_K_PAIR_ALL);
+    rh_time_begin(ctx, ctx->stream, ctx->pair_all);
     hipLaunchKernelGGL(pair_all_lane_kernel<false>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, A);
     RH_HIP(ctx, hipGetLastError());
     if (n) {
         hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
         RH_HIP(ctx, hipGetLastError());
-        ctx->pa_launches += 1;
+        ctx->pair_all.launches += 1;
     }
-    ctx->pa_launches += 1;
+    ctx->pair_all.launches += 1;
     size_t tmp = 0;
     RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, A.cnt, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream));
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
@@ -152,7 +152,7 @@ int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const M
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pa_fragments += n;
+    ctx->pair_all.items += n;
     return REAL_HIP_OK;
 }
 
@@ -164,13 +164,13 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Ma
     if (!n || !total) return REAL_HIP_OK;
     PairAllArgs A = pair_all_args(ctx, pp, L, n, fileid, d_off);
     A.out = (uint4 *)d_out; A.cap = cap;
-    rh_time_begin(ctx, ctx->stream, RH_K_PAIR_ALL);
+    rh_time_begin(ctx, ctx->stream, ctx->pair_all);
     hipLaunchKernelGGL(pair_all_lane_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
     RH_HIP(ctx, hipGetLastError());
     hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->pa_launches += 2;
+    ctx->pair_all.launches += 2;
     ctx->pa_pairs_out += total;
     return REAL_HIP_OK;
 }
@@ -178,14 +178,14 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Ma
 int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset)
 {
     uint64_t h[2];
+    RhStageCount was;
     int rc;
-    if ((rc = rh_stats_read(ctx, ctx->pa_stats, RH_PAIR_STRIPES, 2, reset, h))) return rc;
-    rh_time_resolve(ctx);
+    if ((rc = rh_stage_read(ctx, ctx->pair_all, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
-        out->fragments = ctx->pa_fragments; out->products = h[0]; out->pairs_out = ctx->pa_pairs_out; out->handed_over = h[1];
-        out->launches = ctx->pa_launches; out->kernel_ms = ctx->pa_kernel_ms;
+        out->fragments = was.items; out->products = h[0]; out->pairs_out = ctx->pa_pairs_out; out->handed_over = h[1];
+        out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
-    if (reset) { ctx->pa_fragments = 0; ctx->pa_pairs_out = 0; ctx->pa_launches = 0; ctx->pa_kernel_ms = 0; }
+    if (reset) ctx->pa_pairs_out = 0;
     return REAL_HIP_OK;
 }

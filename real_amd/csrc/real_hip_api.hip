@@ -53,6 +53,23 @@ void rh_release(real_hip_ctx *ctx, DevBuf &b)
 }
 void rh_release(DevBuf &b) { rh_release(nullptr, b); }
 
+int RhStaging::view(DevBuf &buf, const void *src, size_t bytes, size_t room, bool upload, void **dev) const
+{
+    *dev = const_cast<void *>(src);
+    if (!host) return REAL_HIP_OK;
+    int rc = rh_reserve(ctx, buf, room > bytes ? room : bytes);
+    if (rc) return rc;
+    *dev = buf.p;
+    if (upload && bytes) RH_HIP(ctx, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, up));
+    return REAL_HIP_OK;
+}
+int RhStaging::back_bytes(void *dst, const void *dev, size_t bytes, const char *what) const
+{
+    if (!host || !bytes) return REAL_HIP_OK;
+    hipError_t e = hipMemcpyAsync(dst, dev, bytes, hipMemcpyDeviceToHost, down);
+    return e == hipSuccess ? REAL_HIP_OK : rh_fail(ctx, REAL_HIP_E_DEVICE, what, e);
+}
+
 RhTimer::RhTimer(real_hip_ctx *ctx, int w) : c(ctx), which(w)
 {
     if (c->timing) (void)hipEventRecord(c->ev0, c->stream);
@@ -75,13 +92,15 @@ static hipEvent_t rh_event(real_hip_ctx *c)
     (void)hipEventCreate(&e);
     return e;
 }
-void rh_time_begin(real_hip_ctx *c, hipStream_t st, int which)
+static void time_begin(real_hip_ctx *c, hipStream_t st, double *ms, uint64_t *n)
 {
     if (!c->timing) return;
-    real_hip_ctx::Pending p; p.a = rh_event(c); p.b = nullptr; p.which = which;
+    real_hip_ctx::Pending p; p.a = rh_event(c); p.b = nullptr; p.ms = ms; p.n = n;
     (void)hipEventRecord(p.a, st);
     c->pending.push_back(p);
 }
+void rh_time_begin(real_hip_ctx *c, hipStream_t st, int which) { time_begin(c, st, &c->k_ms[which], &c->k_n[which]); }
+void rh_time_begin(real_hip_ctx *c, hipStream_t st, RhStage &stage) { time_begin(c, st, &stage.kernel_ms, nullptr); }
 void rh_time_end(real_hip_ctx *c, hipStream_t st)
 {
     if (!c->timing || c->pending.empty()) return;
@@ -95,13 +114,7 @@ void rh_time_resolve(real_hip_ctx *c)
     for (auto &p : c->pending) {
         if (p.a && p.b && hipEventQuery(p.b) == hipSuccess) {
             float ms = 0.f;
-            if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) {
-                if (p.which == RH_K_MATE_SEARCH) c->ms_kernel_ms += ms;
-                else if (p.which == RH_K_PAIR_ALL) c->pa_kernel_ms += ms;
-                else if (p.which == RH_K_SINGLE) c->sg_kernel_ms += ms;
-                else if (p.which == RH_K_INSERT_HIST) c->ih_kernel_ms += ms;
-                else { c->k_ms[p.which] += ms; c->k_n[p.which] += 1; }
-            }
+            if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { *p.ms += ms; if (p.n) *p.n += 1; }
             c->ev_pool.push_back(p.a);
             c->ev_pool.push_back(p.b);
         } else {
@@ -110,6 +123,16 @@ void rh_time_resolve(real_hip_ctx *c)
     }
     (void)hipGetLastError(); // (hipErrorNotReady of the queries)
     c->pending.resize(keep);
+}
+// the tail of a synchronous call: the stream is synchronised also behind an error (nothing of the caller's memory stays in
+// flight), and the call's own error is reported before the synchronisation's
+static int rh_sync_tail(real_hip_ctx *ctx, int rc)
+{
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    rh_time_resolve(ctx);
+    if (rc) return rc;
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
+    return REAL_HIP_OK;
 }
 
 extern "C" const char *real_hip_strerror(int s)
@@ -218,23 +241,10 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
-    DevBuf *all[] = {&c->comm_counts, &c->comm_scratch, &c->text, &c->wild, &c->frag, &c->LL, &c->counters, &c->s_bases, &c->s_qual, &c->s_off, &c->s_info,
-                     &c->s_score, &c->maxpatl, &c->ovf_list, &c->ovf2_list, &c->ovf_count, &c->qspill, &c->raw, &c->raw_count, &c->hit_cnt, &c->big_list, &c->all_cursor, &c->p_text, &c->p_nl, &c->p_scal, &c->p_spans, &c->p_off,
-                     &c->p_len1, &c->p_bases, &c->p_qual, &c->keys_a,
-                     &c->keys_b, &c->vals_a, &c->vals_b, &c->sort_tmp, &c->hit_off, &c->s_hits, &c->s_nflags};
-    for (DevBuf *b : all) rh_release(*b);
-    for (int k = 0; k < 6; ++k) { rh_release(c->ent[k]); rh_release(c->bkt[k]); }
-    DevBuf *pr[] = {&c->pair_hits[0], &c->pair_hits[1], &c->pair_off[0], &c->pair_off[1], &c->pair_len[0], &c->pair_len[1], &c->pair_rec, &c->pair_list, &c->pair_stats,
-                    &c->s2_bases, &c->s2_qual, &c->s2_off, &c->s2_nflags, &c->ms_stats, &c->pa_cnt, &c->pa_off, &c->pa_out, &c->pa_stats,
-                    &c->sg_rec[0], &c->sg_rec[1], &c->sg_list, &c->sg_stats,
-                    &c->ih_rec, &c->ih_len[0], &c->ih_len[1], &c->ih_hist, &c->ih_stats};
-    for (DevBuf *b : pr) rh_release(*b);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
         RhSlot &S = c->slot[i];
-        DevBuf *sb[] = {&S.bases, &S.qual, &S.off, &S.nflags, &S.info, &S.score};
-        for (DevBuf *b : sb) rh_release(*b);
         if (S.up) (void)hipEventDestroy(S.up);
         if (S.matched) (void)hipEventDestroy(S.matched);
         if (S.done) (void)hipEventDestroy(S.done);
@@ -249,7 +259,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c; // (every DevBuf the ctx holds goes with it)
 }
 
 #define RH_ENTER(ctx)                                   \
@@ -463,10 +473,6 @@ struct Staged {
     uint32_t packed = 0;             // the matcher reads the 2-bit packed bases itself
     const uint8_t *nflags = nullptr;
 };
-// device buffers a host batch is copied into: the ctx's own (synchronous calls) or those of a slot (submit / wait)
-struct StageBufs {
-    DevBuf *bases, *qual, *off, *nflags;
-};
 
 // the batch struct of ABI version 1 ended behind max_patl
 #define RH_BATCH_V1_SIZE 48u
@@ -481,7 +487,7 @@ static int batch_view(real_hip_ctx *ctx, const real_hip_batch *b, real_hip_batch
 
 // Uploads (host batches; on `up`, which is ctx->stream for the synchronous calls and the copy stream for submitted ones).
 // After it the arrays of `s` are valid for kernels on ctx->stream.
-static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, const StageBufs &sb, hipStream_t up, hipEvent_t up_done,
+static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, BatchBufs &sb, hipStream_t up, hipEvent_t up_done,
                        bool need_index = true)
 {
     if (!ctx->have_text || (need_index && !ctx->have_index))
@@ -493,22 +499,21 @@ static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, co
     if (b.nflags && !b.packed) return rh_fail(ctx, REAL_HIP_E_INVALID, "nflags belong to packed batches (unpacked ones carry symbol 4)", hipSuccess);
     int rc;
     uint64_t total = 0;
+    const RhStaging io{ctx, !b.on_device, up, up};
     if (b.offsets) {
-        if (b.on_device) {
-            s.off = b.offsets;
-            s.maxpatl = b.max_patl;
-            s.maxpatl_declared = b.max_patl != 0;
-            if (!s.maxpatl && (rc = rh_max_patl(ctx, s.off, n, &s.maxpatl))) return rc;
-        } else {
+        if (!b.on_device) {
             for (uint64_t i = 0; i < n; ++i) {
                 if (b.offsets[i + 1] < b.offsets[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "offsets not monotone", hipSuccess);
                 uint64_t len = b.offsets[i + 1] - b.offsets[i];
                 if (len > s.maxpatl) s.maxpatl = (uint32_t)(len > 0xffffffffull ? 0xffffffffull : len);
             }
             total = b.offsets[n];
-            if ((rc = rh_reserve(ctx, *sb.off, (n + 1) * 8))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(sb.off->p, b.offsets, (n + 1) * 8, hipMemcpyHostToDevice, up));
-            s.off = (const uint64_t *)sb.off->p;
+        }
+        if ((rc = io.in(sb.off, b.offsets, n + 1, s.off))) return rc;
+        if (b.on_device) {
+            s.maxpatl = b.max_patl;
+            s.maxpatl_declared = b.max_patl != 0;
+            if (!s.maxpatl && (rc = rh_max_patl(ctx, s.off, n, &s.maxpatl))) return rc;
         }
     } else {
         s.upatl = b.patl; s.maxpatl = b.patl;
@@ -519,35 +524,17 @@ static int stage_batch(real_hip_ctx *ctx, const real_hip_batch &b, Staged &s, co
     // an explicit, loud error and not a skip.
     if (s.maxpatl > REAL_HIP_MAX_PATL_LONG) return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "read longer than REAL_HIP_MAX_PATL_LONG", hipSuccess);
     const uint64_t base_bytes = b.packed ? (total + 3) / 4 : total;
-    const uint8_t *d_bases = b.bases, *d_flags = b.nflags;
-    if (b.on_device) {
-        s.qual = b.qual;
-    } else {
-        if ((rc = rh_reserve(ctx, *sb.bases, (base_bytes ? base_bytes : 1) + 16))) return rc;
-        RH_HIP(ctx, hipMemcpyAsync(sb.bases->p, b.bases, base_bytes, hipMemcpyHostToDevice, up));
-        d_bases = (const uint8_t *)sb.bases->p;
-        if (b.qual) {
-            if ((rc = rh_reserve(ctx, *sb.qual, total ? total : 1))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(sb.qual->p, b.qual, total, hipMemcpyHostToDevice, up));
-            s.qual = (const uint8_t *)sb.qual->p;
-        }
-        if (b.nflags) {
-            if ((rc = rh_reserve(ctx, *sb.nflags, (n + 7) / 8))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(sb.nflags->p, b.nflags, (n + 7) / 8, hipMemcpyHostToDevice, up));
-            d_flags = (const uint8_t *)sb.nflags->p;
-        }
-    }
+    const uint8_t *d_flags = b.nflags;
+    if ((rc = io.in(sb.bases, b.bases, base_bytes, s.bases, (base_bytes ? base_bytes : 1) + 16))) return rc;
+    if (b.qual && (rc = io.in(sb.qual, b.qual, total, s.qual, total ? total : 1))) return rc;
+    if (b.nflags && (rc = io.in(sb.nflags, b.nflags, (n + 7) / 8, d_flags))) return rc;
     if (up != ctx->stream) { // the kernels wait for the upload, the host does not
         RH_HIP(ctx, hipEventRecord(up_done, up));
         RH_HIP(ctx, hipStreamWaitEvent(ctx->stream, up_done, 0));
     }
-    if (b.packed) {
-        // the matcher packs its words straight from the packed bytes (25 instead of 100 bytes of HBM per 100 bp read);
-        // a read may start anywhere inside a byte
-        s.bases = d_bases; s.packed = 1; s.nflags = d_flags;
-    } else {
-        s.bases = d_bases;
-    }
+    // packed: the matcher packs its words straight from the packed bytes (25 instead of 100 bytes of HBM per 100 bp read);
+    // a read may start anywhere inside a byte
+    if (b.packed) { s.packed = 1; s.nflags = d_flags; }
     s.W = (s.maxpatl + 31) / 32;
     if (s.W < 1) s.W = 1;
     if (s.W > RH_MAXW) s.W = RH_MAXW; // (longer reads: handed over to the wave-per-read kernel)
@@ -586,34 +573,27 @@ extern "C" int real_hip_match_unique(real_hip_ctx *ctx, const real_hip_batch *b,
     int rc = batch_view(ctx, b, bv);
     if (rc) return rc;
     b = &bv;
-    if ((rc = stage_batch(ctx, bv, s, StageBufs{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, ctx->stream, nullptr))) return rc;
     const uint64_t n = b->n_reads;
+    // from the first copy out of the caller's memory on, every path ends in rh_sync_tail
+    if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr))) return rh_sync_tail(ctx, rc);
     if (!n) return REAL_HIP_OK;
     const bool sc = ctx->prm.scores != 0;
-    if (!info || (sc && !score)) return rh_fail(ctx, REAL_HIP_E_INVALID, "null info/score", hipSuccess);
+    const RhStaging io{ctx, b->on_device != 1, ctx->stream, ctx->stream}; // (host: the outputs are host memory)
     uint64_t *d_info = info;
     float *d_score = score;
-    if (b->on_device != 1) { // outputs in host memory
-        if ((rc = rh_reserve(ctx, ctx->s_info, n * 8))) return rc;
-        if (!b->fresh) RH_HIP(ctx, hipMemcpyAsync(ctx->s_info.p, info, n * 8, hipMemcpyHostToDevice, ctx->stream));
-        d_info = (uint64_t *)ctx->s_info.p;
-        if (sc) {
-            if ((rc = rh_reserve(ctx, ctx->s_score, n * 4))) return rc;
-            if (!b->fresh) RH_HIP(ctx, hipMemcpyAsync(ctx->s_score.p, score, n * 4, hipMemcpyHostToDevice, ctx->stream));
-            d_score = (float *)ctx->s_score.p;
-        }
+    if (!info || (sc && !score)) rc = rh_fail(ctx, REAL_HIP_E_INVALID, "null info/score", hipSuccess);
+    if (!rc) rc = io.inout(ctx->s_info, info, n, b->fresh != 0, d_info);
+    if (!rc && sc) rc = io.inout(ctx->s_score, score, n, b->fresh != 0, d_score);
+    if (!rc) {
+        MatchArgs a;
+        fill_args(ctx, s, n, a);
+        a.info = d_info; a.score = d_score; a.b.fresh = b->fresh ? 1u : 0u;
+        rc = rh_launch_match(ctx, a, false, 2);
     }
-    MatchArgs a;
-    fill_args(ctx, s, n, a);
-    a.info = d_info; a.score = d_score; a.b.fresh = b->fresh ? 1u : 0u;
-    if ((rc = rh_launch_match(ctx, a, false, 2))) return rc;
-    if (b->on_device != 1) { // outputs in host memory
-        RH_HIP(ctx, hipMemcpyAsync(info, d_info, n * 8, hipMemcpyDeviceToHost, ctx->stream));
-        if (sc) RH_HIP(ctx, hipMemcpyAsync(score, d_score, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rh_time_resolve(ctx);
-    return rh_match_finish(ctx, 2);
+    if (!rc) rc = io.back(info, d_info, n, "download of the records");
+    if (!rc && sc) rc = io.back(score, d_score, n, "download of the scores");
+    rc = rh_sync_tail(ctx, rc);
+    return rc ? rc : rh_match_finish(ctx, 2);
 }
 
 // ---------------------------------------------------------------------------
@@ -649,22 +629,21 @@ static int submit_unique(real_hip_ctx *ctx, RhSlot &S, int slot, const real_hip_
     int rc;
     // records: uploaded (they are in/out: folds compose across genome blocks), or initialised on the device (fresh:
     // uniqueinfo(numpat), matchUniqueImplementation.cpp:1094-1097 -- NoMatch, score -FLT_MAX)
-    if ((rc = rh_reserve(ctx, S.info, n * 8))) return rc;
-    if (sc && (rc = rh_reserve(ctx, S.score, n * 4))) return rc;
-    if (!fresh) { // (fresh: the kernel starts every record itself)
-        RH_HIP(ctx, hipMemcpyAsync(S.info.p, info, n * 8, hipMemcpyHostToDevice, ctx->copy_stream));
-        if (sc) RH_HIP(ctx, hipMemcpyAsync(S.score.p, score, n * 4, hipMemcpyHostToDevice, ctx->copy_stream));
-    }
+    const RhStaging io{ctx, true, ctx->copy_stream, ctx->down_stream};
+    uint64_t *d_info = nullptr;
+    float *d_score = nullptr;
+    if ((rc = io.inout(S.info, info, n, fresh != 0, d_info))) return rc; // (fresh: the kernel starts every record itself)
+    if (sc && (rc = io.inout(S.score, score, n, fresh != 0, d_score))) return rc;
     Staged s;
-    if ((rc = stage_batch(ctx, bv, s, StageBufs{&S.bases, &S.qual, &S.off, &S.nflags}, ctx->copy_stream, S.up))) return rc;
+    if ((rc = stage_batch(ctx, bv, s, S.in, ctx->copy_stream, S.up))) return rc;
     MatchArgs a;
     fill_args(ctx, s, n, a);
-    a.info = (uint64_t *)S.info.p; a.score = (float *)S.score.p; a.b.fresh = (fresh || bv.fresh) ? 1u : 0u;
+    a.info = d_info; a.score = d_score; a.b.fresh = (fresh || bv.fresh) ? 1u : 0u;
     if ((rc = rh_launch_match(ctx, a, false, slot))) return rc;
     RH_HIP(ctx, hipEventRecord(S.matched, ctx->stream));
     RH_HIP(ctx, hipStreamWaitEvent(ctx->down_stream, S.matched, 0));
-    RH_HIP(ctx, hipMemcpyAsync(info, S.info.p, n * 8, hipMemcpyDeviceToHost, ctx->down_stream));
-    if (sc) RH_HIP(ctx, hipMemcpyAsync(score, S.score.p, n * 4, hipMemcpyDeviceToHost, ctx->down_stream));
+    if ((rc = io.back(info, d_info, n, "download of the records"))) return rc;
+    if (sc && (rc = io.back(score, d_score, n, "download of the scores"))) return rc;
     RH_HIP(ctx, hipEventRecord(S.done, ctx->down_stream));
     return REAL_HIP_OK;
 }
@@ -722,17 +701,15 @@ extern "C" void real_hip_host_free(void *p)
 }
 
 // matchAll of one batch; dev_out: out / hit_offsets are device memory whatever the batch's inputs are.  staged (nullable)
-// receives the device view of the batch's arrays (valid until the next batch is staged into the same buffers: bufs, or the
-// ctx's own).
-static int match_all_run(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_out, real_hip_hit *out, uint64_t cap,
-                         uint64_t *n_out, uint64_t *hit_offsets, Staged *staged, const StageBufs *bufs = nullptr)
+// receives the device view of the batch's arrays (valid until the next batch is staged into the same buffers: bufs).
+// match_all_run wraps the steps: once they may have queued copies of the caller's memory, every path ends in rh_sync_tail.
+static int match_all_steps(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_out, real_hip_hit *out, uint64_t cap,
+                           uint64_t *n_out, uint64_t *hit_offsets, Staged *staged, BatchBufs &bufs)
 {
     Staged s;
     int rc;
-    const real_hip_batch *b = &bv;
-    const StageBufs own{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags};
-    if ((rc = stage_batch(ctx, bv, s, bufs ? *bufs : own, ctx->stream, nullptr))) return rc;
-    const uint64_t n = b->n_reads;
+    if ((rc = stage_batch(ctx, bv, s, bufs, ctx->stream, nullptr))) return rc;
+    const uint64_t n = bv.n_reads;
     if (n_out) *n_out = 0;
     if (cap > 0xffffffffull) cap = 0xffffffffull; // record indices are 32 bit inside the post-pass
     if (staged) *staged = s;
@@ -753,25 +730,20 @@ static int match_all_run(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_o
     }
     if (n_out) *n_out = n_raw;
     if (n_raw > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffer too small", hipSuccess);
+    const RhStaging io{ctx, !dev_out, ctx->stream, ctx->stream};
     real_hip_hit *d_out = out;
     uint64_t *d_off = hit_offsets;
-    if (!dev_out) { // outputs in host memory
-        if ((rc = rh_reserve(ctx, ctx->s_hits, (n_raw ? n_raw : 1) * sizeof(real_hip_hit)))) return rc;
-        d_out = (real_hip_hit *)ctx->s_hits.p;
-        if (hit_offsets) {
-            if ((rc = rh_reserve(ctx, ctx->hit_off, (n + 1) * 8))) return rc;
-            d_off = (uint64_t *)ctx->hit_off.p;
-        }
-    }
-    if ((n_raw && !out) ) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit buffer", hipSuccess);
+    if ((rc = io.inout(ctx->s_hits, out, n_raw, true, d_out, sizeof(real_hip_hit)))) return rc; // (outputs: nothing is uploaded)
+    if (hit_offsets && (rc = io.inout(ctx->hit_off, hit_offsets, n + 1, true, d_off))) return rc;
+    if (n_raw && !out) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit buffer", hipSuccess);
     if ((rc = rh_all_finish(ctx, n_raw, n, d_out, d_off))) return rc;
-    if (!dev_out) { // outputs in host memory
-        if (n_raw) RH_HIP(ctx, hipMemcpyAsync(out, d_out, n_raw * sizeof(real_hip_hit), hipMemcpyDeviceToHost, ctx->stream));
-        if (hit_offsets) RH_HIP(ctx, hipMemcpyAsync(hit_offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
-    }
-    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    rh_time_resolve(ctx);
-    return REAL_HIP_OK;
+    if ((rc = io.back(out, d_out, n_raw, "download of the hits"))) return rc;
+    return hit_offsets ? io.back(hit_offsets, d_off, n + 1, "download of the hit offsets") : REAL_HIP_OK;
+}
+static int match_all_run(real_hip_ctx *ctx, const real_hip_batch &bv, bool dev_out, real_hip_hit *out, uint64_t cap,
+                         uint64_t *n_out, uint64_t *hit_offsets, Staged *staged, BatchBufs *bufs = nullptr)
+{
+    return rh_sync_tail(ctx, match_all_steps(ctx, bv, dev_out, out, cap, n_out, hit_offsets, staged, bufs ? *bufs : ctx->stage[0]));
 }
 
 extern "C" int real_hip_match_all(real_hip_ctx *ctx, const real_hip_batch *b, real_hip_hit *out, uint64_t cap,
@@ -819,22 +791,14 @@ static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *const hits[2],
             L.total[m] = o[n];
         }
         if (L.total[m] && !hits[m]) return rh_fail(ctx, REAL_HIP_E_INVALID, "null hit list", hipSuccess);
-        L.h[m] = (const uint4 *)hits[m]; L.o[m] = off[m]; L.len[m] = len ? len[m] : nullptr;
     }
-    if (on_device) return REAL_HIP_OK;
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     for (int m = 0; m < lists; ++m) {
-        const uint64_t total = L.total[m];
-        if ((rc = rh_reserve(ctx, ctx->pair_hits[m], (total ? total : 1) * sizeof(real_hip_hit)))) return rc;
-        if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
-        if (total) RH_HIP(ctx, hipMemcpyAsync(ctx->pair_hits[m].p, hits[m], total * sizeof(real_hip_hit), hipMemcpyHostToDevice, ctx->stream));
-        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_off[m].p, off[m], (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-        L.h[m] = (const uint4 *)ctx->pair_hits[m].p; L.o[m] = (const uint64_t *)ctx->pair_off[m].p;
-        if (!len) continue;
-        if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
-        RH_HIP(ctx, hipMemcpyAsync(ctx->pair_len[m].p, len[m], n * 4, hipMemcpyHostToDevice, ctx->stream));
-        L.len[m] = (const uint32_t *)ctx->pair_len[m].p;
+        if ((rc = io.in(ctx->pair_hits[m], (const uint4 *)hits[m], L.total[m], L.h[m], sizeof(real_hip_hit)))) return rc;
+        if ((rc = io.in(ctx->pair_off[m], off[m], n + 1, L.o[m]))) return rc;
+        if (len && (rc = io.in(ctx->pair_len[m], len[m], n, L.len[m]))) return rc;
     }
-    ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
+    if (!on_device) ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
     return REAL_HIP_OK;
 }
 // the lists match_mates leaves resident in the ctx's pair buffers
@@ -846,34 +810,6 @@ static MateLists resident_lists(real_hip_ctx *ctx, const uint64_t total[2])
         L.len[m] = (const uint32_t *)ctx->pair_len[m].p; L.total[m] = total[m];
     }
     return L;
-}
-
-// the in/out real_hip_pair records, staged in pair_rec when they are host memory
-static int stage_pairs(real_hip_ctx *ctx, real_hip_pair *pairs, uint64_t n, bool host_out, int fresh, real_hip_pair **d_pairs)
-{
-    *d_pairs = pairs;
-    if (!host_out) return REAL_HIP_OK;
-    int rc;
-    if ((rc = rh_reserve(ctx, ctx->pair_rec, n * sizeof(real_hip_pair)))) return rc;
-    *d_pairs = (real_hip_pair *)ctx->pair_rec.p;
-    if (!fresh) RH_HIP(ctx, hipMemcpyAsync(*d_pairs, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
-    return REAL_HIP_OK;
-}
-static int download_pairs(real_hip_ctx *ctx, real_hip_pair *pairs, uint64_t n, const real_hip_pair *d_pairs)
-{
-    hipError_t e = hipMemcpyAsync(pairs, d_pairs, n * sizeof(real_hip_pair), hipMemcpyDeviceToHost, ctx->stream);
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair records", e);
-    return REAL_HIP_OK;
-}
-// the tail of a synchronous call: the stream is synchronised also behind an error (nothing of the caller's memory stays in
-// flight), and the call's own error is reported before the synchronisation's
-static int rh_sync_tail(real_hip_ctx *ctx, int rc)
-{
-    hipError_t e = hipStreamSynchronize(ctx->stream);
-    rh_time_resolve(ctx);
-    if (rc) return rc;
-    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "hipStreamSynchronize", e);
-    return REAL_HIP_OK;
 }
 
 extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
@@ -892,11 +828,12 @@ extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params 
     const uint64_t *const off[2] = {off1, off2};
     const uint32_t *const len[2] = {len1, len2};
     MateLists L;
-    real_hip_pair *d_pairs;
+    real_hip_pair *d_pairs = pairs;
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     if ((rc = stage_hit_lists(ctx, hits, off, len, n, on_device != 0, L))) return rc;
-    if ((rc = stage_pairs(ctx, pairs, n, !on_device, fresh, &d_pairs))) return rc;
+    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_pair(ctx, *pp, L, n, fileid, fresh, d_pairs);
-    if (!rc && !on_device) rc = download_pairs(ctx, pairs, n, d_pairs);
+    if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
     return rh_sync_tail(ctx, rc);
 }
 
@@ -970,41 +907,32 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
     MateLists L;
     if ((rc = stage_hit_lists(ctx, hits, off, nullptr, n, on_device, L))) return rc;
     Staged st[2];
-    const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
     for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], bufs[m], ctx->stream, nullptr, false))) return rc;
-    real_hip_pair *d_pairs;
-    if ((rc = stage_pairs(ctx, pairs, n, !on_device, fresh, &d_pairs))) return rc;
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rc;
+    real_hip_pair *d_pairs = pairs;
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, fileid, fresh, d_pairs);
-    if (!rc && !on_device) rc = download_pairs(ctx, pairs, n, d_pairs);
+    if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
     rc = rh_sync_tail(ctx, rc);
     return rc ? rc : rh_mate_search_finish(ctx);
 }
 
-// ---- single placements of a mate (single_fold.hip): the in/out records of `lists` lists, staged when they are host memory
-static int stage_singles(real_hip_ctx *ctx, int lists, real_hip_single *const singles[2], uint64_t n, bool host_out, int fresh,
-                         real_hip_single *d_singles[2])
+// ---- single placements of a mate (single_fold.hip): the in/out records of `lists` lists (device records: 16-byte aligned)
+static int stage_singles(const RhStaging &io, int lists, real_hip_single *const singles[2], uint64_t n, int fresh, real_hip_single *d_singles[2])
 {
-    int rc;
-    for (int m = 0; m < lists; ++m) {
-        d_singles[m] = singles[m];
-        if (!host_out) {
-            if ((uintptr_t)singles[m] & 15u) return rh_fail(ctx, REAL_HIP_E_INVALID, "the single records must be 16-byte aligned", hipSuccess);
-            continue;
-        }
-        if ((rc = rh_reserve(ctx, ctx->sg_rec[m], n * sizeof(real_hip_single)))) return rc;
-        d_singles[m] = (real_hip_single *)ctx->sg_rec[m].p;
-        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_singles[m], singles[m], n * sizeof(real_hip_single), hipMemcpyHostToDevice, ctx->stream));
+    int rc = REAL_HIP_OK;
+    for (int m = 0; m < lists && !rc; ++m) {
+        if (!io.host && ((uintptr_t)singles[m] & 15u)) return rh_fail(io.ctx, REAL_HIP_E_INVALID, "the single records must be 16-byte aligned", hipSuccess);
+        rc = io.inout(io.ctx->sg_rec[m], singles[m], n, fresh != 0, d_singles[m]);
     }
-    return REAL_HIP_OK;
+    return rc;
 }
-static int download_singles(real_hip_ctx *ctx, int lists, real_hip_single *const singles[2], uint64_t n, real_hip_single *const d_singles[2])
+static int download_singles(const RhStaging &io, int lists, real_hip_single *const singles[2], uint64_t n, real_hip_single *const d_singles[2])
 {
-    for (int m = 0; m < lists; ++m) {
-        hipError_t e = hipMemcpyAsync(singles[m], d_singles[m], n * sizeof(real_hip_single), hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the single records", e);
-    }
-    return REAL_HIP_OK;
+    int rc = REAL_HIP_OK;
+    for (int m = 0; m < lists && !rc; ++m) rc = io.back(singles[m], d_singles[m], n, "download of the single records");
+    return rc;
 }
 
 extern "C" int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits, const uint64_t *off, const uint32_t *len, uint64_t n_reads,
@@ -1023,10 +951,11 @@ extern "C" int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits,
     MateLists L;
     real_hip_single *const sv[2] = {singles, nullptr};
     real_hip_single *d_singles[2] = {nullptr, nullptr};
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     if ((rc = stage_hit_lists(ctx, hv, ov, lv, n, on_device != 0, L, 1))) return rc;
-    rc = stage_singles(ctx, 1, sv, n, !on_device, fresh, d_singles);
+    rc = stage_singles(io, 1, sv, n, fresh, d_singles);
     if (!rc) rc = rh_launch_single(ctx, 1, L, n, fileid, fresh, d_singles);
-    if (!rc && !on_device) rc = download_singles(ctx, 1, sv, n, d_singles);
+    if (!rc) rc = download_singles(io, 1, sv, n, d_singles);
     return rh_sync_tail(ctx, rc);
 }
 
@@ -1052,28 +981,16 @@ extern "C" int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair 
     const real_hip_pair *d_pairs = pairs;
     const uint32_t *d_len[2] = {len1, len2};
     uint64_t *d_hist = hist;
-    const size_t hist_bytes = (size_t)n_bins * 8;
-    if (!on_device) {
-        if ((rc = rh_reserve(ctx, ctx->ih_hist, hist_bytes))) return rc;
-        d_hist = (uint64_t *)ctx->ih_hist.p;
-        if (!fresh) RH_HIP(ctx, hipMemcpyAsync(d_hist, hist, hist_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (n) {
-            if ((rc = rh_reserve(ctx, ctx->ih_rec, n * sizeof(real_hip_pair)))) return rc;
-            RH_HIP(ctx, hipMemcpyAsync(ctx->ih_rec.p, pairs, n * sizeof(real_hip_pair), hipMemcpyHostToDevice, ctx->stream));
-            d_pairs = (const real_hip_pair *)ctx->ih_rec.p;
-            for (int m = 0; m < 2; ++m) {
-                if ((rc = rh_reserve(ctx, ctx->ih_len[m], n * 4))) return rc;
-                RH_HIP(ctx, hipMemcpyAsync(ctx->ih_len[m].p, m ? len2 : len1, n * 4, hipMemcpyHostToDevice, ctx->stream));
-                d_len[m] = (const uint32_t *)ctx->ih_len[m].p;
-            }
-        }
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    if ((rc = io.inout(ctx->ih_hist, hist, n_bins, fresh != 0, d_hist))) return rc;
+    if (n) {
+        if ((rc = io.in(ctx->ih_rec, pairs, n, d_pairs))) return rc;
+        for (int m = 0; m < 2; ++m)
+            if ((rc = io.in(ctx->ih_len[m], m ? len2 : len1, n, d_len[m]))) return rc;
     }
-    if (fresh) RH_HIP(ctx, hipMemsetAsync(d_hist, 0, hist_bytes, ctx->stream));
+    if (fresh) RH_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)n_bins * 8, ctx->stream));
     rc = rh_launch_insert_hist(ctx, d_pairs, d_len[0], d_len[1], n, n_bins, d_hist);
-    if (!rc && !on_device) {
-        hipError_t e = hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the histogram", e);
-    }
+    if (!rc) rc = io.back(hist, d_hist, n_bins, "download of the histogram");
     return rh_sync_tail(ctx, rc);
 }
 
@@ -1118,7 +1035,6 @@ static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_
 {
     int rc;
     const uint64_t n = bv[0].n_reads;
-    const StageBufs bufs[2] = {{&ctx->s_bases, &ctx->s_qual, &ctx->s_off, &ctx->s_nflags}, {&ctx->s2_bases, &ctx->s2_qual, &ctx->s2_off, &ctx->s2_nflags}};
     total[0] = total[1] = 0;
     for (int m = 0; m < 2; ++m) {
         if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
@@ -1141,7 +1057,7 @@ static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_
             Staged &s = st[m];
             s = Staged();
             rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s,
-                               both_resident ? &bufs[m] : nullptr);
+                               both_resident ? &ctx->stage[m] : nullptr);
             if (rc == REAL_HIP_E_OVERFLOW) { overflow = true; continue; } // (the other mate still reports its size)
             if (rc) return rc;
             // the read lengths, while this mate's offsets are staged
@@ -1174,18 +1090,19 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
     const MateLists L = resident_lists(ctx, total);
     const bool host_out = bv[0].on_device != 1;
     const int fresh = bv[0].fresh != 0;
-    real_hip_pair *d_pairs;
-    if ((rc = stage_pairs(ctx, pairs, n, host_out, fresh, &d_pairs))) return rc;
+    real_hip_pair *d_pairs = pairs;
+    const RhStaging io{ctx, host_out, ctx->stream, ctx->stream};
+    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_pair(ctx, *pp, L, n, ctx->fileid, fresh, d_pairs);
     real_hip_single *d_singles[2] = {nullptr, nullptr};
     if (!rc && singles) { // seed hits only: the search below adds nothing to the lists
-        rc = stage_singles(ctx, 2, singles, n, host_out, fresh, d_singles);
+        rc = stage_singles(io, 2, singles, n, fresh, d_singles);
         if (!rc) rc = rh_launch_single(ctx, 2, L, n, ctx->fileid, fresh, d_singles);
     }
     if (!rc && sp) // the records of the join are the search's in/out records
         rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, ctx->fileid, 0, d_pairs);
-    if (!rc && host_out) rc = download_pairs(ctx, pairs, n, d_pairs);
-    if (!rc && host_out && singles) rc = download_singles(ctx, 2, singles, n, d_singles);
+    if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
+    if (!rc && singles) rc = download_singles(io, 2, singles, n, d_singles);
     rc = rh_sync_tail(ctx, rc);
     return rc || !sp ? rc : rh_mate_search_finish(ctx);
 }
@@ -1240,11 +1157,10 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
                         real_hip_pair_hit *out, uint64_t cap, uint64_t *n_out, uint64_t *pair_offsets)
 {
     int rc;
+    // (outputs: nothing is uploaded; without pair_offsets the scan still needs a device array)
+    const RhStaging io{ctx, !dev_out, ctx->stream, ctx->stream}, off_io{ctx, !dev_out || !pair_offsets, ctx->stream, ctx->stream};
     uint64_t *d_off = pair_offsets;
-    if (!dev_out || !pair_offsets) {
-        if ((rc = rh_reserve(ctx, ctx->pa_off, (n + 1) * 8))) return rc;
-        d_off = (uint64_t *)ctx->pa_off.p;
-    }
+    if ((rc = off_io.inout(ctx->pa_off, pair_offsets, n + 1, true, d_off))) return rc;
     uint64_t found = 0;
     rc = rh_pair_all_count(ctx, pp, L, n, d_off, &found);
     rh_time_resolve(ctx);
@@ -1252,17 +1168,10 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
     *n_out = found;
     if (found > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "pair hit buffer too small", hipSuccess);
     real_hip_pair_hit *d_out = out;
-    if (!dev_out) {
-        if ((rc = rh_reserve(ctx, ctx->pa_out, (found ? found : 1) * sizeof(real_hip_pair_hit)))) return rc;
-        d_out = (real_hip_pair_hit *)ctx->pa_out.p;
-    }
+    if ((rc = io.inout(ctx->pa_out, out, found, true, d_out, sizeof(real_hip_pair_hit)))) return rc;
     rc = rh_pair_all_emit(ctx, pp, L, n, fileid, d_off, d_out, dev_out ? cap : found, found);
-    if (!rc && !dev_out) {
-        hipError_t e = hipSuccess;
-        if (found) e = hipMemcpyAsync(out, d_out, found * sizeof(real_hip_pair_hit), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess && pair_offsets) e = hipMemcpyAsync(pair_offsets, d_off, (n + 1) * 8, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) rc = rh_fail(ctx, REAL_HIP_E_DEVICE, "download of the pair hits", e);
-    }
+    if (!rc) rc = io.back(out, d_out, found, "download of the pair hits");
+    if (!rc && pair_offsets) rc = io.back(pair_offsets, d_off, n + 1, "download of the pair hits");
     return rh_sync_tail(ctx, rc);
 }
 // what both entry points check of their outputs; n == 0 is answered here (*done)
@@ -1343,12 +1252,9 @@ extern "C" int real_hip_parse_reads(real_hip_ctx *ctx, const char *text, uint64_
     RH_ENTER(ctx);
     if (!out || (n_bytes && !text)) return rh_fail(ctx, REAL_HIP_E_INVALID, "null text / out", hipSuccess);
     const char *d_text = text;
-    if (!text_on_device && n_bytes) {
-        int rc = rh_reserve(ctx, ctx->p_text, n_bytes);
-        if (rc) return rc;
-        RH_HIP(ctx, hipMemcpyAsync(ctx->p_text.p, text, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d_text = (const char *)ctx->p_text.p;
-    }
+    const RhStaging io{ctx, !text_on_device, ctx->stream, ctx->stream};
+    int rc;
+    if (n_bytes && (rc = io.in(ctx->p_text, text, n_bytes, d_text))) return rc;
     RhTimer tm(ctx, REAL_HIP_K_PARSE);
     return rh_parse_reads(ctx, d_text, n_bytes, fastq, quality_offset, out);
 }
@@ -1385,6 +1291,16 @@ int rh_stats_read(real_hip_ctx *ctx, const DevBuf &buf, size_t stripes, int n_wo
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t st = 0; st < stripes; ++st)
         for (int k = 0; k < n_words; ++k) out[k] += all[st * 16 + k];
+    return REAL_HIP_OK;
+}
+
+int rh_stage_read(real_hip_ctx *ctx, RhStage &stage, size_t stripes, int n_words, int reset, uint64_t h[], RhStageCount &was)
+{
+    int rc = rh_stats_read(ctx, stage.stats, stripes, n_words, reset, h);
+    if (rc) return rc;
+    rh_time_resolve(ctx);
+    was = stage;
+    if (reset) static_cast<RhStageCount &>(stage) = RhStageCount();
     return REAL_HIP_OK;
 }
 

@@ -191,18 +191,43 @@ struct MatchArgs {
 };
 
 // ---- host context ------------------------------------------------------------
+struct DevBuf;
+struct real_hip_ctx;
+void rh_release(DevBuf &b);
+// a device allocation and its owner: it goes with whatever holds it (the ctx, a slot, a function's scope)
 struct DevBuf {
     void  *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { rh_release(*this); }
+};
+
+// device copies of a host batch's four arrays: the ctx's own two sets (synchronous calls; the second holds mate 2 while
+// both mates are resident) or those of a slot (submit / wait)
+struct BatchBufs {
+    DevBuf bases, qual, off, nflags;
 };
 
 // one slot of the submit / wait pipeline: device copies of a host batch and its records
 struct RhSlot {
-    DevBuf bases, qual, off, nflags, info, score;
+    BatchBufs in;
+    DevBuf info, score;
     hipEvent_t up = nullptr, matched = nullptr, done = nullptr;
     uint64_t n = 0;
     int status = 0;
     bool busy = false, empty = false;
+};
+
+// what the ctx keeps of one paired stage: the items it was given, its launches and their event times since the last reset,
+// and the striped statistics its kernels add to (rh_stats_reserve)
+struct RhStageCount {
+    uint64_t items = 0, launches = 0;
+    double   kernel_ms = 0;
+};
+struct RhStage : RhStageCount {
+    DevBuf stats;
 };
 
 struct real_hip_ctx {
@@ -230,7 +255,8 @@ struct real_hip_ctx {
     DevBuf LL, counters;
 
     // batch staging (host batches), hand-over list of the repeat kernel
-    DevBuf s_bases, s_qual, s_off, s_info, s_score, s_nflags;
+    BatchBufs stage[2];
+    DevBuf s_info, s_score;
     RhSlot slot[REAL_HIP_SLOTS];                    // submit / wait
     hipStream_t copy_stream = nullptr, down_stream = nullptr;
     DevBuf maxpatl, ovf_list, ovf2_list, ovf_count, qspill;
@@ -241,35 +267,29 @@ struct real_hip_ctx {
     DevBuf raw, raw_count, hit_cnt, big_list, all_cursor, keys_a, keys_b, vals_a, vals_b, sort_tmp, hit_off, s_hits;
 
     // paired-end join (pair_kernel.hip): the two mates' hit lists, offsets and read lengths, staged records, the hand-over
-    // list of the wave kernel, striped statistics
-    DevBuf pair_hits[2], pair_off[2], pair_len[2], pair_rec, pair_list, pair_stats;
+    // list of the wave kernel; its two kernels are timed under their public ids, join.launches / kernel_ms stay 0
+    DevBuf pair_hits[2], pair_off[2], pair_len[2], pair_rec, pair_list;
     uint64_t pair_cap = 0;   // hits each of pair_hits[] holds (grown when a match overflowed it)
-    uint64_t pair_count = 0; // fragments joined since the last reset
+    RhStage join;
 
-    // mate search (mate_search.hip): staging of mate 2's reads (both mates are resident while it runs), striped statistics
-    // followed by the kernel's error flags, the event times of its launches
-    DevBuf s2_bases, s2_qual, s2_off, s2_nflags, ms_stats;
-    uint64_t ms_fragments = 0, ms_launches = 0;
-    double   ms_kernel_ms = 0;
+    // mate search (mate_search.hip): the kernel's error flags lie behind its statistics
+    RhStage search;
     uint32_t ms_err = 0;     // the flags of the last launch, copied back behind it
 
     // every concordant pair of a fragment (pair_all.hip): counts per fragment, their scan and the staged records when the
-    // caller's outputs are host memory, striped statistics, the event times of its launches
-    DevBuf pa_cnt, pa_off, pa_out, pa_stats;
-    uint64_t pa_fragments = 0, pa_pairs_out = 0, pa_launches = 0;
-    double   pa_kernel_ms = 0;
+    // caller's outputs are host memory
+    DevBuf pa_cnt, pa_off, pa_out;
+    RhStage pair_all;
+    uint64_t pa_pairs_out = 0;
 
     // single placements of a mate (single_fold.hip): the staged records of the two lists when the caller's are host memory,
-    // the hand-over list of the wave kernel, striped statistics, the event times of its launches
-    DevBuf sg_rec[2], sg_list, sg_stats;
-    uint64_t sg_reads = 0, sg_launches = 0;
-    double   sg_kernel_ms = 0;
+    // the hand-over list of the wave kernel
+    DevBuf sg_rec[2], sg_list;
+    RhStage single;
 
-    // insert-size histogram (insert_hist.hip): the staged records, lengths and histogram when the caller's are host memory,
-    // striped statistics, the event times of its launches
-    DevBuf ih_rec, ih_len[2], ih_hist, ih_stats;
-    uint64_t ih_records = 0, ih_launches = 0;
-    double   ih_kernel_ms = 0;
+    // insert-size histogram (insert_hist.hip): the staged records, lengths and histogram when the caller's are host memory
+    DevBuf ih_rec, ih_len[2], ih_hist;
+    RhStage insert;
 
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
@@ -286,7 +306,7 @@ struct real_hip_ctx {
     uint64_t k_n[REAL_HIP_K_COUNT] = {};
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // asynchronous timing of pipelined launches: event pairs resolved at the next synchronisation point
-    struct Pending { hipEvent_t a, b; int which; };
+    struct Pending { hipEvent_t a, b; double *ms; uint64_t *n; }; // where the time goes: a k_ms / k_n slot, or a stage's kernel_ms (n null)
     std::vector<Pending> pending;
     std::vector<hipEvent_t> ev_pool;
 };
@@ -299,16 +319,44 @@ int rh_fail(real_hip_ctx *ctx, int status, const char *what, hipError_t e);
         if (_e != hipSuccess) return rh_fail((ctx), REAL_HIP_E_DEVICE, #call, _e); \
     } while (0)
 int rh_reserve(real_hip_ctx *ctx, DevBuf &b, size_t bytes);
-void rh_release(DevBuf &b);
 void rh_release(real_hip_ctx *ctx, DevBuf &b); // (timed: real_hip_index_build_stats)
 double rh_now_ms();
-// a function-local device buffer: released on every exit path
+// a function-local device buffer whose release is charged to the ctx's build statistics
 struct ScopedBuf : DevBuf {
     real_hip_ctx *c;
     explicit ScopedBuf(real_hip_ctx *ctx) : c(ctx) {}
     ~ScopedBuf() { rh_release(c, *this); }
-    ScopedBuf(const ScopedBuf &) = delete;
-    ScopedBuf &operator=(const ScopedBuf &) = delete;
+};
+
+// The one rule for an array that crosses the ABI.  host: the caller's arrays are host memory, each is copied into a DevBuf
+// of the ctx on `up` and the kernels read the copy; otherwise the caller's pointer is the device view.
+//   in     the device view of `count` elements (room: bytes to reserve where that is more than the elements take)
+//   inout  the same, the upload skipped when `fresh` (the kernel starts every record itself)
+//   back   the download on `down`; its error is returned, so that the caller's rh_sync_tail still runs
+struct RhStaging {
+    real_hip_ctx *ctx;
+    bool host;
+    hipStream_t up, down;
+    int view(DevBuf &buf, const void *src, size_t bytes, size_t room, bool upload, void **dev) const;
+    int back_bytes(void *dst, const void *dev, size_t bytes, const char *what) const;
+    template <typename T> int in(DevBuf &buf, const T *src, size_t count, const T *&dev, size_t room = 0) const
+    {
+        void *d = nullptr;
+        const int rc = view(buf, src, count * sizeof(T), room, true, &d);
+        dev = static_cast<const T *>(d);
+        return rc;
+    }
+    template <typename T> int inout(DevBuf &buf, T *src, size_t count, bool fresh, T *&dev, size_t room = 0) const
+    {
+        void *d = nullptr;
+        const int rc = view(buf, src, count * sizeof(T), room, !fresh, &d);
+        dev = static_cast<T *>(d);
+        return rc;
+    }
+    template <typename T> int back(T *dst, const T *dev, size_t count, const char *what) const
+    {
+        return back_bytes(dst, dev, count * sizeof(T), what);
+    }
 };
 
 struct RhTimer { // HIP events on the ctx stream around a group of launches
@@ -324,7 +372,8 @@ int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &a, bool all, int state_s
 int rh_match_finish(real_hip_ctx *ctx, int state_slot); // after the launch has completed: errors the kernels flagged
 
 // asynchronous kernel timing (no host synchronisation at the launch site)
-void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, int which);
+void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, int which);   // a public kernel id: k_ms / k_n
+void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, RhStage &stage); // a paired stage: its kernel_ms
 void rh_time_end(real_hip_ctx *ctx, hipStream_t st);
 void rh_time_resolve(real_hip_ctx *ctx); // call after the streams were synchronised
 int rh_max_patl(real_hip_ctx *ctx, const uint64_t *d_off, uint64_t n_reads, uint32_t *out);
@@ -342,6 +391,9 @@ static inline unsigned rh_wave_blocks(uint64_t work) { return (unsigned)((work +
 // stripes into out[] (zeros while there is no buffer), clears the stripes if `reset`, and synchronises the stream
 int rh_stats_reserve(real_hip_ctx *ctx, DevBuf &buf, size_t stripes, size_t extra_bytes);
 int rh_stats_read(real_hip_ctx *ctx, const DevBuf &buf, size_t stripes, int n_words, int reset, uint64_t out[]);
+// what the stages' stats functions share: the striped words into h[], the pending event times resolved, `was` = the counts
+// as they stand, which then start again if `reset`
+int rh_stage_read(real_hip_ctx *ctx, RhStage &stage, size_t stripes, int n_words, int reset, uint64_t h[], RhStageCount &was);
 
 // ---- paired-end join (pair_kernel.hip) ------------------------------------------
 int rh_pair_lens(real_hip_ctx *ctx, const uint64_t *d_off, uint32_t upatl, uint64_t n, uint32_t *d_len);
@@ -349,7 +401,6 @@ int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Mate
 int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
 
 // ---- mate search (mate_search.hip) ----------------------------------------------
-#define RH_K_MATE_SEARCH (-1) /* rh_time_begin: the time goes to ctx->ms_kernel_ms (REAL_HIP_K_COUNT is part of the ABI) */
 // asynchronous on the ctx's stream; after the stream was synchronised rh_mate_search_finish reports what the kernel flagged
 int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_mate_search_params &sp, const DevBatch &b1,
                           const DevBatch &b2, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
@@ -357,7 +408,6 @@ int rh_mate_search_finish(real_hip_ctx *ctx);
 int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
 
 // ---- every concordant pair of a fragment (pair_all.hip) ---------------------------
-#define RH_K_PAIR_ALL (-2) /* rh_time_begin: the time goes to ctx->pa_kernel_ms */
 // count + scan into d_off (n + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
 int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint64_t *d_off, uint64_t *total);
 int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, const uint64_t *d_off,
@@ -365,12 +415,10 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Ma
 int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
 
 // ---- single placements of a mate (single_fold.hip) ---------------------------------
-#define RH_K_SINGLE (-3) /* rh_time_begin: the time goes to ctx->sg_kernel_ms */
 int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
 int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
 
 // ---- insert-size histogram (insert_hist.hip) ----------------------------------------
-#define RH_K_INSERT_HIST (-4) /* rh_time_begin: the time goes to ctx->ih_kernel_ms */
 // d_hist += the histogram of n records, all arrays on the device; asynchronous on the ctx's stream
 int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const uint32_t *d_len1, const uint32_t *d_len2, uint64_t n,
                           uint32_t n_bins, uint64_t *d_hist);

@@ -274,12 +274,17 @@ class HipMatcher:
         self._refresh_index_info()
         return int(n.value), bool(nxt.value)
 
+    def _stats(self, struct, entry, fields: Sequence[str], reset: bool) -> dict:
+        """one read of a statistics struct of the ABI: the named fields, times (*_ms) as float, counts as int"""
+        st = struct()
+        st.struct_size = C.sizeof(struct)
+        self._check(entry(self._h, C.byref(st), int(reset)))
+        return {k: (float if k.endswith("_ms") else int)(getattr(st, k)) for k in fields}
+
     def index_build_stats(self, reset: bool = False) -> dict:
         """where the wall time of this context's index builds went (real_hip_index_build_stats)"""
-        st = _lib.RealHipBuildStats()
-        st.struct_size = C.sizeof(_lib.RealHipBuildStats)
-        self._check(self._L.real_hip_index_build_stats(self._h, C.byref(st), int(reset)))
-        return {k: (float(getattr(st, k)) if k.endswith("_ms") else int(getattr(st, k))) for k, _ in st._fields_ if k not in ("struct_size", "reserved")}
+        return self._stats(_lib.RealHipBuildStats, self._L.real_hip_index_build_stats,
+                           ("wall_ms", "kernel_ms", "alloc_ms", "free_ms", "alloc_bytes", "alloc_calls", "free_calls"), reset)
 
     def _refresh_index_info(self):
         n = C.c_uint64(0)
@@ -573,12 +578,8 @@ class PairMatcher(AllMatcher):
         return pairs
 
     def mate_search_stats(self, reset: bool = False) -> dict:
-        st = _lib.RealHipMateSearchStats()
-        st.struct_size = C.sizeof(_lib.RealHipMateSearchStats)
-        self._check(self._L.real_hip_mate_search_stats_get(self._h, C.byref(st), int(reset)))
-        return {"fragments": int(st.fragments), "anchors": int(st.anchors), "anchors_skipped": int(st.anchors_skipped),
-                "positions": int(st.positions), "placements": int(st.placements), "launches": int(st.launches),
-                "kernel_ms": float(st.kernel_ms)}
+        return self._stats(_lib.RealHipMateSearchStats, self._L.real_hip_mate_search_stats_get,
+                           ("fragments", "anchors", "anchors_skipped", "positions", "placements", "launches", "kernel_ms"), reset)
 
     def pair_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0, pairs=None,
                   orientation: int = 0, fresh: Optional[bool] = None):
@@ -653,11 +654,8 @@ class PairMatcher(AllMatcher):
         return pairs, singles1, singles2
 
     def single_stats(self, reset: bool = False) -> dict:
-        st = _lib.RealHipSingleStats()
-        st.struct_size = C.sizeof(_lib.RealHipSingleStats)
-        self._check(self._L.real_hip_single_stats_get(self._h, C.byref(st), int(reset)))
-        return {"reads": int(st.reads), "hits": int(st.hits), "handed_over": int(st.handed_over), "launches": int(st.launches),
-                "kernel_ms": float(st.kernel_ms)}
+        return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get,
+                           ("reads", "hits", "handed_over", "launches", "kernel_ms"), reset)
 
     # -- insert sizes: the histogram of the Unique fragments' outer distances, and the bounds it suggests --
     def insert_hist(self, pairs, len1, len2, n_bins: int, hist=None, fresh: Optional[bool] = None):
@@ -707,17 +705,11 @@ class PairMatcher(AllMatcher):
         return {"n": int(est.n), "q1": int(est.q1), "median": int(est.median), "q3": int(est.q3), "low": int(est.low), "high": int(est.high)}
 
     def insert_stats(self, reset: bool = False) -> dict:
-        st = _lib.RealHipInsertStats()
-        st.struct_size = C.sizeof(_lib.RealHipInsertStats)
-        self._check(self._L.real_hip_insert_stats_get(self._h, C.byref(st), int(reset)))
-        return {"records": int(st.records), "counted": int(st.counted), "overflow": int(st.overflow), "invalid": int(st.invalid),
-                "launches": int(st.launches), "kernel_ms": float(st.kernel_ms)}
+        return self._stats(_lib.RealHipInsertStats, self._L.real_hip_insert_stats_get,
+                           ("records", "counted", "overflow", "invalid", "launches", "kernel_ms"), reset)
 
     def pair_stats(self, reset: bool = False) -> dict:
-        st = _lib.RealHipPairStats()
-        st.struct_size = C.sizeof(_lib.RealHipPairStats)
-        self._check(self._L.real_hip_pair_stats_get(self._h, C.byref(st), int(reset)))
-        return {"pairs": int(st.pairs), "products": int(st.products), "handed_over": int(st.handed_over)}
+        return self._stats(_lib.RealHipPairStats, self._L.real_hip_pair_stats_get, ("pairs", "products", "handed_over"), reset)
 
     # -- every concordant pair of a fragment (real_hip_pair_hit records) --
     def _pair_all_call(self, call, n: int, on_device: bool, cap: int, out, pair_offsets):
@@ -780,8 +772,5 @@ class PairMatcher(AllMatcher):
         return self._pair_all_call(call, int(b1.n_reads), bool(b1.on_device), cap, out, pair_offsets)
 
     def pair_all_stats(self, reset: bool = False) -> dict:
-        st = _lib.RealHipPairAllStats()
-        st.struct_size = C.sizeof(_lib.RealHipPairAllStats)
-        self._check(self._L.real_hip_pair_all_stats_get(self._h, C.byref(st), int(reset)))
-        return {"fragments": int(st.fragments), "products": int(st.products), "pairs_out": int(st.pairs_out),
-                "handed_over": int(st.handed_over), "launches": int(st.launches), "kernel_ms": float(st.kernel_ms)}
+        return self._stats(_lib.RealHipPairAllStats, self._L.real_hip_pair_all_stats_get,
+                           ("fragments", "products", "pairs_out", "handed_over", "launches", "kernel_ms"), reset)
