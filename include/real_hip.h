@@ -474,6 +474,78 @@ typedef struct real_hip_insert_stats {
 } real_hip_insert_stats;
 int real_hip_insert_stats_get(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset);
 
+/* ---- pileup: what the final placements add up to over one genome file -- the depth of every text position and, where a
+ * placed read shows another base than the text, how often each base was seen.  The reference has no such output; the
+ * semantics are this project's own.  The pileup covers the RESIDENT text: n bases, file id f.  A PLACEMENT
+ * is a read of length L at 0-based text position p on a strand, with p + L <= n; its ORIENTED base at text position p + i is
+ * read[i] with quality qual[i] on the forward strand and 3 - read[L-1-i] with quality qual[L-1-i] on the reverse strand (a
+ * batch without qualities counts as quality 30).  Single-end: every info record of state 1 or 2 (Unique forward / reverse,
+ * UniqueMatchInfo.hpp:29-39) is a placement of its read at the record's pos, on the reverse strand iff the state is 2.
+ * Paired-end: every real_hip_pair of state REAL_HIP_PAIR_UNIQUE gives two placements, mate 1 at pos1 on strand inverted1
+ * and mate 2 at pos2 on the other strand.  Records of another state are skipped; then records of another file id than f are
+ * skipped and counted as other_file; then a placement with p + L > n is skipped and counted as invalid (per read: a pair
+ * record counts once for each mate).
+ *   depth[x]   = the number of placements with p <= x < p + L (no quality filter);
+ *   alt[x][b]  = the number of placements covering x whose oriented base at x is b != ref[x] (the 2-bit text, N stored as
+ *                0), whose quality there is >= min_qual, and where the text's N bit at x is clear;
+ *   a SITE is a position with alt[x][0] + .. + alt[x][3] > 0; the site list is in ascending position.
+ * All results are integer sums: nothing depends on the order of reads, batches, lanes or calls, and two add calls give
+ * exactly what one call on the concatenated batch gives.
+ * Device memory: the accumulators are a dense table of 4 x u32 per text position and the depth's difference array of
+ * n + 1 u32 (scanned in place by finish): 20 bytes per base, 60 GB for a text of 3 Gbp.  begin fails with
+ * REAL_HIP_E_NOMEM and a message when that does not fit.
+ * Protocol: begin (needs the text, not the index; allocates and zeroes; a second begin starts again), any number of add /
+ * add_pairs, finish (synchronises; once per begin), depth / sites any number of times, end (releases the accumulators).
+ * add without begin, after finish, or after the text was replaced by one of another n_bases or file id (finish likewise:
+ * it takes the sites' reference bases from the text), and finish / depth / sites out of turn are REAL_HIP_E_INVALID with
+ * a message, nothing launched; a finish that fails for another reason ends the pileup as end does; so are more than 2^32 reads in one
+ * call and a depth window that reaches beyond n.
+ * info / pairs live where the records of real_hip_match_unique / real_hip_match_pairs live for the batch's on_device:
+ * host memory for 0 and 2, device memory for 1 -- a caller passes the arrays it matched with.  Reads of any length up
+ * to REAL_HIP_MAX_PATL_LONG.                                                                                       */
+typedef struct real_hip_pileup_params {
+    uint32_t struct_size;   /* = sizeof(real_hip_pileup_params)                                       */
+    uint32_t min_qual;      /* a mismatch of lower quality is not counted in alt (0: qualities are not read); <= 63 */
+} real_hip_pileup_params;
+typedef struct real_hip_pileup_site {   /* 32 bytes */
+    uint32_t pos;           /* 0-based position in the text                                           */
+    uint32_t depth;
+    uint32_t alt[4];        /* alt[ref] is 0                                                          */
+    uint32_t ref;           /* the text's base 0..3                                                   */
+    uint32_t reserved;      /* 0                                                                      */
+} real_hip_pileup_site;
+int real_hip_pileup_begin(real_hip_ctx *ctx, const real_hip_pileup_params *p);
+int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info);
+/* batch1 and batch2 must agree in n_reads and on_device                                              */
+int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs);
+int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites);
+/* depth[first .. first + count) into depth (host memory, or device memory if on_device); after finish */
+int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device);
+/* the site list into out (cap records; host memory, or device memory if on_device); *n_out (host memory) always receives
+ * the number of sites; when that exceeds cap the call returns REAL_HIP_E_OVERFLOW and writes nothing to out; after finish */
+int real_hip_pileup_sites(real_hip_ctx *ctx, real_hip_pileup_site *out, uint64_t cap, uint64_t *n_out, int on_device);
+int real_hip_pileup_end(real_hip_ctx *ctx);
+/* work of the pileup.  reads .. n_dropped, launches and kernel_ms are accumulated since the last reset; covered, sites
+ * and max_depth are those of the last finish (0 from begin until then).  A mismatch is tested for quality first, then
+ * for the N bit: low_qual counts the mismatches min_qual dropped, n_dropped those of sufficient quality on an N.      */
+typedef struct real_hip_pileup_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_pileup_stats), 0                             */
+    uint64_t reads;         /* reads handed in (a pair counts two)                                    */
+    uint64_t placed;        /* placements piled up                                                    */
+    uint64_t other_file;    /* placed reads of another file id                                        */
+    uint64_t invalid;       /* placements that end behind the text                                    */
+    uint64_t bases;         /* sum of L over the placements = sum of depth[]                          */
+    uint64_t mismatches;    /* increments of alt                                                      */
+    uint64_t low_qual;      /* mismatches that min_qual dropped                                       */
+    uint64_t n_dropped;     /* mismatches on an N of the text                                         */
+    uint64_t covered;       /* positions with depth > 0                                               */
+    uint64_t sites;
+    uint64_t max_depth;
+    uint64_t launches;      /* kernels launched (the scans of finish count one each)                  */
+    double   kernel_ms;     /* HIP events on the ctx's stream around the kernels of add and finish    */
+} real_hip_pileup_stats;
+int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

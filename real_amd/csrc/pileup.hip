@@ -1,0 +1,336 @@
+// pileup.hip -- the pileup of the final placements over the resident text: per-position depth, and at every position where a
+// placed read shows another base than the text, how often each base was seen (include/real_hip.h, "pileup").
+//
+// pileup_add_kernel: one lane per read, and the lane WALKS ITS READ WORD BY WORD -- 32 bases at a time, whatever the length
+// (up to REAL_HIP_MAX_PATL_LONG): no register array of the read, no second kernel for long reads.  Per word the lane packs
+// the 32 read bases that lie over the next 32 text positions with match_common.h's pack_read / pack_read_packed (W = 1; a
+// packed read may start inside a byte) -- on the reverse strand those are the read's LAST unvisited bases, turned round with
+// revcomp_words -- loads the 2-bit text funnel-shifted to the placement and takes XOR: one flag per base.  Every flagged
+// base checks its quality (one byte, loaded only when min_qual > 0), then the text's N bit, then does one atomicAdd into the
+// alt table (4 x u32 per text position).  The depth is a difference array of n + 1 u32: +1 at p, -1 at p + L in wrap-around
+// arithmetic -- two atomics per read, not one per base.
+//
+// finish: rocPRIM's inclusive scan turns the difference array into depth[] in place; then count, scan, emit over the
+// positions (the pattern of pair_all.hip): a block of 256 positions counts its sites (alt sum > 0), the block counts are
+// scanned, and the emit pass writes the 32-byte site records in ascending position.  The count pass also sums `covered`
+// and takes `max_depth`.
+//
+// Everything is an integer sum: nothing depends on the order of reads, lanes, blocks or calls.  No LDS in the add kernel,
+// no scratch memory; plain C++ and vector stores.
+#include "real_hip_internal.h"
+#include "match_common.h"
+#include "pair_state.h"
+
+#include <rocprim/device/device_scan.hpp>
+
+#include <cstring>
+
+#define RH_PU_BLOCK 256u
+
+// a read's bytes in place, a dword per request: the aligned dword that holds the first byte asked for and, where the request
+// straddles it and the row goes on, the next one.  Never a dword without a byte of the row in it (an aligned dword does not
+// cross a page, so nothing outside the caller's allocation's pages is touched); bytes behind the row's end come back as
+// whatever lies there, and pack_read / pack_read_packed mask them off.
+struct DwordRow {
+    const uint8_t *row;
+    __device__ __forceinline__ uint32_t dword(int byteoff, uint32_t nbytes) const
+    {
+        if (byteoff < 0 || (uint32_t)byteoff >= nbytes) return 0;
+        const uintptr_t a = (uintptr_t)(row + byteoff);
+        const uint32_t mis = (uint32_t)(a & 3u);
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(a - mis);
+        const uint32_t lo = p[0];
+        uint32_t hi = 0;
+        if (mis && (uint32_t)byteoff + (4u - mis) < nbytes) hi = p[1];
+        return __builtin_amdgcn_alignbyte(hi, lo, mis);
+    }
+};
+
+struct PileupArgs {
+    DevText  t;
+    DevBatch b;                    // the reads of this launch (mate `mate` of a pair launch)
+    const uint64_t *info;          // single-end records, or
+    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (insert_hist.hip)
+    uint32_t mate;                 // pair launches: 0 = mate 1, 1 = mate 2
+    uint32_t min_qual;
+    uint32_t *diff;                // n + 1: the depth's difference array
+    uint32_t *alt;                 // 4 per text position
+    unsigned long long *stats;     // RH_PAIR_STRIPES x 16 words: [0] placed, [1] other_file, [2] invalid, [3] bases, [4] mismatches,
+                                   // [5] low_qual, [6] n_dropped
+};
+
+template <bool PAIRS>
+__global__ void __launch_bounds__(RH_PU_BLOCK) pileup_add_kernel(const PileupArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * RH_PU_BLOCK + threadIdx.x;
+    uint32_t placed = 0, other = 0, invalid = 0, bases = 0, mism = 0, lowq = 0, ndrop = 0;
+    if (i < A.b.n_reads) {
+        // the record: is it a placement in this file, where, on which strand
+        bool place, inv;
+        uint32_t file, p;
+        if (PAIRS) {
+            const uint2 pos = A.pairs[i * 5 + 2], tail = A.pairs[i * 5 + 4];
+            place = ((tail.y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE;
+            inv = (((tail.y >> 8) & 0xffu) != 0) != (A.mate != 0); // mate 2 has the other strand
+            file = (tail.x >> 16) & 0xffu;
+            p = A.mate ? pos.y : pos.x;
+        } else {
+            const uint64_t r = A.info[i];
+            const uint32_t st = (uint32_t)(r >> ST_SHIFT);
+            place = st == ST_STRAIGHT || st == ST_REVERSE;
+            inv = st == ST_REVERSE;
+            file = (uint32_t)(r >> FI_SHIFT) & 63u;
+            const uint64_t p64 = r & POS_MASK;
+            p = (uint32_t)p64;
+            if (place && file == A.t.fileid && p64 > 0xffffffffull) { place = false; ++invalid; } // (35 bits of position, 32 of text)
+        }
+        if (place && file != A.t.fileid) { place = false; ++other; }
+        uint64_t start = 0;
+        uint32_t L = 0;
+        if (place) {
+            if (A.b.off) { start = A.b.off[i]; const uint64_t e = A.b.off[i + 1]; L = e >= start && e - start <= REAL_HIP_MAX_PATL_LONG ? (uint32_t)(e - start) : 0xffffffffu; }
+            else { start = i * (uint64_t)A.b.upatl; L = A.b.upatl; }
+            if ((uint64_t)p + L > A.t.n) { place = false; ++invalid; }
+        }
+        if (place) {
+            placed = 1; bases = L;
+            atomicAdd(A.diff + p, 1u);
+            atomicAdd(A.diff + (uint64_t)p + L, 0xffffffffu);
+            const uint64_t wi = p >> 5;
+            const uint32_t sh = 2u * (p & 31u);
+            const uint32_t nw = (L + 31u) >> 5;
+            uint64_t t0 = nw ? A.t.text[wi] : 0;
+            for (uint32_t j = 0; j < nw; ++j) {
+                const uint32_t nb = min(32u, L - 32u * j);
+                // the nb read bases over text positions p + 32j ..: read[32j ..] forward, read[L - 32j - nb ..] turned round
+                const uint64_t s = start + (inv ? L - 32u * j - nb : 32u * j);
+                uint64_t w, o;
+                if (A.b.packed) pack_read_packed<1>(DwordRow{A.b.bases + (s >> 2)}, nb, (uint32_t)(s & 3u), &w);
+                else (void)pack_read<1>(DwordRow{A.b.bases + s}, nb, &w);
+                if (inv) revcomp_words<1>(&w, &o, nb); else o = w;
+                const uint64_t t1 = A.t.text[wi + j + 1]; // (the text is padded behind its end)
+                const uint64_t al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
+                t0 = t1;
+                const uint64_t x = al ^ o;
+                uint64_t flags = ((x >> 1) | x) & M55;
+                if (nb < 32) flags &= ~0ull << (64 - 2 * nb);
+                while (flags) {
+                    const uint32_t u = (uint32_t)__clzll((long long)flags) >> 1; // base u of the word: its flag is bit 62 - 2u
+                    flags &= ~(1ull << (62 - 2 * u));
+                    const uint32_t k = 32u * j + u;                              // base k of the oriented read
+                    const uint64_t tp = (uint64_t)p + k;
+                    if (A.min_qual) {
+                        const uint32_t q = A.b.qual ? A.b.qual[start + (inv ? L - 1 - k : k)] : 30u;
+                        if (q < A.min_qual) { ++lowq; continue; }
+                    }
+                    if (A.t.has_wild && ((A.t.wild[tp >> 6] >> (63 - (tp & 63))) & 1ull)) { ++ndrop; continue; }
+                    atomicAdd(A.alt + 4 * tp + ((uint32_t)(o >> (62 - 2 * u)) & 3u), 1u);
+                    ++mism;
+                }
+            }
+        }
+    }
+    // the statistics: one sum per wave, added to a striped line
+    uint32_t s[7] = {placed, other, invalid, bases, mism, lowq, ndrop}; // (a wave's sums stay below 2^32: 64 reads of at most 2^14 bases)
+#pragma unroll
+    for (int k = 0; k < 7; ++k)
+        for (int d = 32; d; d >>= 1) s[k] += (uint32_t)__shfl_xor((int)s[k], d);
+    if ((threadIdx.x & 63u) == 0) {
+        unsigned long long *line = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
+#pragma unroll
+        for (int k = 0; k < 7; ++k)
+            if (s[k]) atomicAdd(line + k, (unsigned long long)s[k]);
+    }
+}
+
+// ---- finish: the sites ------------------------------------------------------------------------------------------
+struct PileupFinArgs {
+    const uint64_t *text;
+    const uint32_t *depth;         // n: the scanned difference array
+    const uint4 *alt;              // n
+    uint64_t n;
+    uint64_t *blk;                 // count pass: sites per block (blocks + 1, the last one 0)
+    const uint64_t *blk_off;       // emit pass: their exclusive scan
+    uint4 *out;                    // real_hip_pileup_site records, two uint4 each
+    uint64_t cap;
+    unsigned long long *fin;       // RH_PAIR_STRIPES x 16 words: [0] covered (sum), [1] max_depth (max)
+};
+
+// one lane per position; EMIT = false counts the block's sites, EMIT = true writes them behind the block's offset
+template <bool EMIT>
+__global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupFinArgs A)
+{
+    __shared__ uint32_t wave_cnt[RH_PU_BLOCK / 64];
+    __shared__ uint32_t wave_cov[RH_PU_BLOCK / 64];
+    __shared__ uint32_t wave_max[RH_PU_BLOCK / 64];
+    const uint64_t x = (uint64_t)blockIdx.x * RH_PU_BLOCK + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint4 a = make_uint4(0, 0, 0, 0);
+    uint32_t d = 0;
+    if (x < A.n) { a = A.alt[x]; d = A.depth[x]; }
+    const bool site = (a.x | a.y | a.z | a.w) != 0;
+    const unsigned long long mask = __ballot(site);
+    if (!EMIT) {
+        const unsigned long long cov = __ballot(d != 0);
+        uint32_t m = d;
+        for (int k = 32; k; k >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, k));
+        if (lane == 0) { wave_cnt[wave] = (uint32_t)__popcll(mask); wave_cov[wave] = (uint32_t)__popcll(cov); wave_max[wave] = m; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t c = 0, v = 0, mx = 0;
+            for (uint32_t k = 0; k < RH_PU_BLOCK / 64; ++k) { c += wave_cnt[k]; v += wave_cov[k]; mx = max(mx, wave_max[k]); }
+            A.blk[blockIdx.x] = c;
+            if (blockIdx.x + 1 == gridDim.x) A.blk[gridDim.x] = 0;
+            unsigned long long *line = A.fin + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
+            if (v) atomicAdd(line, (unsigned long long)v);
+            if (mx) atomicMax(line + 1, (unsigned long long)mx);
+        }
+        return;
+    }
+    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    if (!site) return;
+    uint64_t slot = A.blk_off[blockIdx.x];
+    for (uint32_t k = 0; k < wave; ++k) slot += wave_cnt[k];
+    slot += __popcll(mask & ((1ull << lane) - 1ull));
+    if (slot >= A.cap) return; // (cannot happen: the table is what the count saw)
+    const uint32_t ref = (uint32_t)(A.text[x >> 5] >> (62 - 2 * (x & 31))) & 3u;
+    A.out[2 * slot] = make_uint4((uint32_t)x, d, a.x, a.y);
+    A.out[2 * slot + 1] = make_uint4(a.z, a.w, ref, 0u);
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------
+static void pileup_release(real_hip_ctx *ctx)
+{
+    rh_release(ctx, ctx->pu_diff); rh_release(ctx, ctx->pu_alt); rh_release(ctx, ctx->pu_blk); rh_release(ctx, ctx->pu_sites);
+    ctx->pu_state = 0; ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
+}
+
+int rh_pileup_begin(real_hip_ctx *ctx, uint32_t min_qual)
+{
+    static_assert(sizeof(real_hip_pileup_site) == 32, "a site is two 16-byte stores");
+    const uint64_t n = ctx->n_bases;
+    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    pileup_release(ctx);
+    int rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->pileup.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->pu_fin, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->pu_diff, (size_t)(n + 1) * 4)) || (rc = rh_reserve(ctx, ctx->pu_alt, (size_t)(n ? n : 1) * 16))) {
+        pileup_release(ctx);
+        return rh_fail(ctx, REAL_HIP_E_NOMEM, "pileup: the accumulators (20 bytes per base of the text) do not fit the device memory", hipSuccess);
+    }
+    RH_HIP(ctx, hipMemsetAsync(ctx->pu_diff.p, 0, (size_t)(n + 1) * 4, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->pu_alt.p, 0, (size_t)(n ? n : 1) * 16, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->pu_fin.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
+    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->pu_n = n; ctx->pu_fileid = ctx->fileid; ctx->pu_min_qual = min_qual;
+    ctx->pu_state = 1;
+    return REAL_HIP_OK;
+}
+
+void rh_pileup_end(real_hip_ctx *ctx)
+{
+    (void)hipStreamSynchronize(ctx->stream);
+    pileup_release(ctx);
+}
+
+// the placements of one batch (d_info) or of mate `mate` of a batch of pairs (d_pairs); all arrays on the device;
+// asynchronous on the ctx's stream
+int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate)
+{
+    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
+                      offsetof(real_hip_pair, fileid) == 34 && offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
+                  "pileup_add_kernel reads words 2 and 4 of the record");
+    const uint64_t n = b.n_reads;
+    if (!n) return REAL_HIP_OK;
+    PileupArgs A;
+    memset(&A, 0, sizeof A);
+    A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p;
+    A.t.n = ctx->n_bases; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = ctx->fileid;
+    A.b = b;
+    if (!ctx->pu_min_qual) A.b.qual = nullptr; // (not loaded)
+    A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pu_min_qual;
+    A.diff = (uint32_t *)ctx->pu_diff.p; A.alt = (uint32_t *)ctx->pu_alt.p;
+    A.stats = (unsigned long long *)ctx->pileup.stats.p;
+    const unsigned blocks = (unsigned)((n + RH_PU_BLOCK - 1) / RH_PU_BLOCK);
+    rh_time_begin(ctx, ctx->stream, ctx->pileup);
+    if (d_pairs) hipLaunchKernelGGL(pileup_add_kernel<true>, dim3(blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, A);
+    else hipLaunchKernelGGL(pileup_add_kernel<false>, dim3(blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, A);
+    rh_time_end(ctx, ctx->stream);
+    RH_HIP(ctx, hipGetLastError());
+    ctx->pileup.items += n;
+    ctx->pileup.launches += 1;
+    return REAL_HIP_OK;
+}
+
+int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
+{
+    const uint64_t n = ctx->pu_n;
+    const uint64_t blocks = (n + RH_PU_BLOCK - 1) / RH_PU_BLOCK;
+    uint32_t *depth = (uint32_t *)ctx->pu_diff.p;
+    int rc;
+    ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
+    if (!n) { ctx->pu_state = 2; if (n_sites) *n_sites = 0; return REAL_HIP_OK; }
+    if ((rc = rh_reserve(ctx, ctx->pu_blk, (size_t)(blocks + 1) * 16))) return rc;
+    size_t tmp = 0, tmp2 = 0;
+    RH_HIP(ctx, rocprim::inclusive_scan(nullptr, tmp, depth, depth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
+    uint64_t *blk = (uint64_t *)ctx->pu_blk.p, *blk_off = blk + blocks + 1;
+    RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp2, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream));
+    if (tmp2 > tmp) tmp = tmp2;
+    if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
+    PileupFinArgs F;
+    F.text = (const uint64_t *)ctx->text.p; F.depth = depth; F.alt = (const uint4 *)ctx->pu_alt.p; F.n = n;
+    F.blk = blk; F.blk_off = blk_off; F.out = nullptr; F.cap = 0; F.fin = (unsigned long long *)ctx->pu_fin.p;
+    rh_time_begin(ctx, ctx->stream, ctx->pileup); // (no return inside the bracket: a failing step is reported behind rh_time_end)
+    size_t t = tmp;
+    hipError_t e = rocprim::inclusive_scan(ctx->sort_tmp.p, t, depth, depth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(pileup_sites_kernel<false>, dim3((unsigned)blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, F);
+        e = hipGetLastError();
+    }
+    t = tmp;
+    if (e == hipSuccess) e = rocprim::exclusive_scan(ctx->sort_tmp.p, t, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream);
+    rh_time_end(ctx, ctx->stream);
+    if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "pileup: scan of the depth / count of the sites", e);
+    ctx->pileup.launches += 3;
+    uint64_t total = 0;
+    std::vector<uint64_t> fin((size_t)RH_PAIR_STRIPES * 16);
+    RH_HIP(ctx, hipMemcpyAsync(&total, blk_off + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
+    RH_HIP(ctx, hipMemcpyAsync(fin.data(), ctx->pu_fin.p, fin.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t s = 0; s < RH_PAIR_STRIPES; ++s) {
+        ctx->pu_covered += fin[s * 16];
+        if (fin[s * 16 + 1] > ctx->pu_max_depth) ctx->pu_max_depth = fin[s * 16 + 1];
+    }
+    if (total) {
+        if ((rc = rh_reserve(ctx, ctx->pu_sites, (size_t)total * sizeof(real_hip_pileup_site)))) return rc;
+        F.out = (uint4 *)ctx->pu_sites.p; F.cap = total;
+        rh_time_begin(ctx, ctx->stream, ctx->pileup);
+        hipLaunchKernelGGL(pileup_sites_kernel<true>, dim3((unsigned)blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, F);
+        rh_time_end(ctx, ctx->stream);
+        RH_HIP(ctx, hipGetLastError());
+        ctx->pileup.launches += 1;
+        RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    rh_time_resolve(ctx);
+    ctx->pu_n_sites = total;
+    ctx->pu_state = 2; // (only now: a finish that failed leaves nothing to read, real_hip_pileup_finish releases the accumulators)
+    if (n_sites) *n_sites = total;
+    return REAL_HIP_OK;
+}
+
+int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset)
+{
+    uint64_t h[7];
+    RhStageCount was;
+    int rc;
+    if ((rc = rh_stage_read(ctx, ctx->pileup, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
+    if (out) {
+        out->reserved = 0;
+        out->reads = was.items; out->placed = h[0]; out->other_file = h[1]; out->invalid = h[2]; out->bases = h[3];
+        out->mismatches = h[4]; out->low_qual = h[5]; out->n_dropped = h[6];
+        out->covered = ctx->pu_covered; out->sites = ctx->pu_n_sites; out->max_depth = ctx->pu_max_depth;
+        out->launches = was.launches; out->kernel_ms = was.kernel_ms;
+    }
+    return REAL_HIP_OK;
+}

@@ -1027,6 +1027,136 @@ extern "C" int real_hip_insert_bounds(const uint64_t *hist, uint32_t n_bins, uin
     return REAL_HIP_OK;
 }
 
+// ---- pileup (pileup.hip): the reads are staged as a match stages them, the records as the match's outputs
+// the resident text is still the one begin saw (add reads it, finish takes the sites' reference bases from it)
+static int pileup_text_check(real_hip_ctx *ctx)
+{
+    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the text was replaced since begin", hipSuccess);
+    return REAL_HIP_OK;
+}
+static int pileup_add_check(real_hip_ctx *ctx)
+{
+    if (ctx->pu_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add without begin", hipSuccess);
+    if (ctx->pu_state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add after finish", hipSuccess);
+    return pileup_text_check(ctx);
+}
+
+extern "C" int real_hip_pileup_begin(real_hip_ctx *ctx, const real_hip_pileup_params *p)
+{
+    RH_ENTER(ctx);
+    if (!p || p->struct_size != sizeof(real_hip_pileup_params)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup params struct_size", hipSuccess);
+    if (p->min_qual > 63) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: min_qual beyond 63", hipSuccess);
+    if (!ctx->have_text) return rh_fail(ctx, REAL_HIP_E_STATE, "the text must be set", hipSuccess);
+    return rh_pileup_begin(ctx, p->min_qual);
+}
+
+extern "C" int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = batch_view(ctx, b, bv);
+    if (rc || (rc = pileup_add_check(ctx))) return rc;
+    const uint64_t n = bv.n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: more than 2^32 reads in one call", hipSuccess);
+    if (!n) return REAL_HIP_OK;
+    if (!info) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null info", hipSuccess);
+    Staged s;
+    if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
+    const uint64_t *d_info = info;
+    rc = io.in(ctx->pu_rec, info, n, d_info);
+    if (!rc) {
+        DevBatch db = dev_batch(ctx, s, n);
+        db.qual = s.qual; // (the pileup's use of the qualities does not hang on -q)
+        rc = rh_launch_pileup_add(ctx, db, d_info, nullptr, 0);
+    }
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv[2];
+    int rc;
+    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1])) || (rc = pileup_add_check(ctx))) return rc;
+    if (bv[0].n_reads != bv[1].n_reads || bv[0].on_device != bv[1].on_device)
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the mates' batches must agree in n_reads and on_device", hipSuccess);
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: more than 2^32 reads in one call", hipSuccess);
+    if (!n) return REAL_HIP_OK;
+    if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null pairs", hipSuccess);
+    if (bv[0].on_device == 1 && ((uintptr_t)pairs & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the pair records must be 8-byte aligned", hipSuccess);
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    const RhStaging io{ctx, bv[0].on_device != 1, ctx->stream, ctx->stream};
+    const real_hip_pair *d_pairs = pairs;
+    rc = io.in(ctx->pu_rec, pairs, n, d_pairs);
+    for (uint32_t m = 0; m < 2 && !rc; ++m) {
+        DevBatch db = dev_batch(ctx, st[m], n);
+        db.qual = st[m].qual;
+        rc = rh_launch_pileup_add(ctx, db, nullptr, d_pairs, m);
+    }
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
+{
+    RH_ENTER(ctx);
+    if (ctx->pu_state != 1) return rh_fail(ctx, REAL_HIP_E_INVALID, ctx->pu_state ? "pileup: finish twice" : "pileup: finish without begin", hipSuccess);
+    int rc = pileup_text_check(ctx);
+    if (rc) return rc;
+    rc = rh_sync_tail(ctx, rh_pileup_finish(ctx, n_sites));
+    if (rc) { // nothing half-finished stays readable: the pileup is over, as after end (the message of rc is kept)
+        const std::string msg = ctx->last_error;
+        rh_pileup_end(ctx);
+        ctx->last_error = msg;
+    }
+    return rc;
+}
+
+extern "C" int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device)
+{
+    RH_ENTER(ctx);
+    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
+    if (first > ctx->pu_n || count > ctx->pu_n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
+    if (!count) return REAL_HIP_OK;
+    if (!depth) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null depth", hipSuccess);
+    RH_HIP(ctx, hipMemcpyAsync(depth, (const uint32_t *)ctx->pu_diff.p + first, (size_t)count * 4,
+                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return rh_sync_tail(ctx, REAL_HIP_OK);
+}
+
+extern "C" int real_hip_pileup_sites(real_hip_ctx *ctx, real_hip_pileup_site *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    RH_ENTER(ctx);
+    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: sites before finish", hipSuccess);
+    if (!n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null n_out", hipSuccess);
+    const uint64_t total = ctx->pu_n_sites;
+    *n_out = total;
+    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "pileup: the site list needs more room", hipSuccess);
+    if (!total) return REAL_HIP_OK;
+    if (!out) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null out", hipSuccess);
+    RH_HIP(ctx, hipMemcpyAsync(out, ctx->pu_sites.p, (size_t)total * sizeof(real_hip_pileup_site),
+                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return rh_sync_tail(ctx, REAL_HIP_OK);
+}
+
+extern "C" int real_hip_pileup_end(real_hip_ctx *ctx)
+{
+    RH_ENTER(ctx);
+    rh_pileup_end(ctx);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_pileup_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup stats struct_size", hipSuccess);
+    return rh_pileup_stats(ctx, out, reset);
+}
+
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
 // hold mate m's unified hit lists, their n + 1 offsets and the read lengths; total[m] is an upper bound of the hits inside
 // the buffer (the matcher's count before duplicates go).  both_resident: mate 2 is staged into buffers of its own, so that

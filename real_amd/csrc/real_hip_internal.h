@@ -291,6 +291,15 @@ struct real_hip_ctx {
     DevBuf ih_rec, ih_len[2], ih_hist;
     RhStage insert;
 
+    // pileup (pileup.hip): the depth's difference array (n + 1 u32, scanned in place by finish), the alt table (4 u32 per
+    // position), the per-block site counts and their scan, the site list, covered / max_depth of finish (striped), the
+    // staged records when the caller's are host memory
+    DevBuf pu_diff, pu_alt, pu_blk, pu_sites, pu_fin, pu_rec;
+    RhStage pileup;
+    int      pu_state = 0;   // 0 none, 1 begun (adds), 2 finished (depth / sites)
+    uint64_t pu_n = 0, pu_n_sites = 0, pu_covered = 0, pu_max_depth = 0; // the text begin saw; the last finish
+    uint32_t pu_fileid = 0, pu_min_qual = 0;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -423,6 +432,14 @@ int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
 int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const uint32_t *d_len1, const uint32_t *d_len2, uint64_t n,
                           uint32_t n_bins, uint64_t *d_hist);
 int rh_insert_stats(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset);
+
+// ---- pileup (pileup.hip) ---------------------------------------------------------------
+int rh_pileup_begin(real_hip_ctx *ctx, uint32_t min_qual);
+// the placements of a batch (d_info) or of mate `mate` of a batch of pairs (d_pairs), all arrays on the device; asynchronous
+int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate);
+int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites); // synchronises
+void rh_pileup_end(real_hip_ctx *ctx);
+int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

@@ -57,6 +57,15 @@ void RealOptions::printHelp() const
               << "   judges uniqueness in the FIRST genome file only and under the window -insert_min .. -insert_max; not with\n"
               << "   -pairs_all 1, default=0 (off)>\n"
               << "   (-insert_hist and -insert_auto take an -insert_max of at most " << (REAL_HIP_INSERT_HIST_MAX_BINS - 2) << ")\n"
+              << "-pileup <file: after the output pass, pile the FINAL unique placements (single-end: the printed lines; with -p2: both\n"
+              << "   mates of the Unique fragments) up over every genome file on one fresh context on -device, and write one line per\n"
+              << "   position where a placed read shows another base than the genome: fragment name, 1-based position in the fragment,\n"
+              << "   reference base, depth, and how often A, C, G, T were seen there as a mismatch (the reference base's column is 0);\n"
+              << "   a summary line per genome file goes to standard error; -o is unchanged; needs -u 1, not with -pairs_all 1;\n"
+              << "   the placements of -unpaired are NOT part of the pileup; 20 bytes of device memory per genome base>\n"
+              << "-pileup_depth <file: the depth as runs: fragment name, 0-based start, end, depth, for the maximal runs of equal\n"
+              << "   non-zero depth inside a fragment; same conditions as -pileup>\n"
+              << "-pileup_minq <Q: with -pileup, a mismatch of quality below Q is not counted, 0..63, default=0>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -121,6 +130,9 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-unpaired") { unpairedfilename = need("-unpaired"); unpaired_given = true; i += 2; }
         else if (a == "-insert_hist") { inserthistfilename = need("-insert_hist"); insert_flags_given = true; i += 2; }
         else if (a == "-insert_auto") { insert_auto = strtoull(need("-insert_auto").c_str(), 0, 10); insert_flags_given = true; i += 2; }
+        else if (a == "-pileup") { pileupfilename = need("-pileup"); pileup_given = true; i += 2; }
+        else if (a == "-pileup_depth") { pileupdepthfilename = need("-pileup_depth"); pileup_depth_given = true; i += 2; }
+        else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -181,6 +193,24 @@ RealOptions::RealOptions(int argc, char *argv[])
     filter_mult /= 70.0;
     std::cerr << "filter_mult=" << filter_mult << std::endl;
     if (gpus < 1) gpus = 1;
+    if (pileup_given || pileup_depth_given) { // the pileup: loud errors before anything runs
+        const char *flag = pileup_given ? "-pileup" : "-pileup_depth";
+        if (!match_unique) throw std::runtime_error(std::string(flag) + " piles up the unique placements: it cannot be combined with -u 0.");
+        if (pairs_all) throw std::runtime_error(std::string(flag) + " piles up the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
+        for (const std::string *f : {&pileupfilename, &pileupdepthfilename}) {
+            const bool given = f == &pileupfilename ? pileup_given : pileup_depth_given;
+            if (!given) continue;
+            if (f->empty()) throw std::runtime_error("-pileup / -pileup_depth need a file name: an empty one was given.");
+            if (*f == "-") throw std::runtime_error("-pileup / -pileup_depth write to a file: standard output (-) cannot be it.");
+            if (*f == outputfilename) throw std::runtime_error("-pileup / -pileup_depth must name a file of its own: it names the same file as -o.");
+            if (unpaired_given && *f == unpairedfilename) throw std::runtime_error("-pileup / -pileup_depth must name a file of its own: it names the same file as -unpaired.");
+            if (!inserthistfilename.empty() && *f == inserthistfilename) throw std::runtime_error("-pileup / -pileup_depth must name a file of its own: it names the same file as -insert_hist.");
+        }
+        if (pileup_given && pileup_depth_given && pileupfilename == pileupdepthfilename)
+            throw std::runtime_error("-pileup and -pileup_depth must name two files.");
+    }
+    if (pileup_minq_given && !pileup_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
+    if (pileup_minq > 63) throw std::runtime_error("-pileup_minq takes a quality of at most 63.");
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
         if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");
         if (gpus > 1) throw std::runtime_error("-p2 (paired-end reads) runs on one device: it cannot be combined with -gpus > 1.");

@@ -55,6 +55,10 @@ struct RealOptions {
     bool unpaired_given = false;      // (the flag was on the command line: an error without -p2)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
     std::string inserthistfilename;   // -insert_hist: the file that receives the histogram of the Unique fragments' outer distances (real_hip_pair_insert_hist)
+    std::string pileupfilename;       // -pileup: the file that receives the sites of the pileup of the final placements (real_hip_pileup_*)
+    std::string pileupdepthfilename;  // -pileup_depth: the file that receives the depth as runs
+    unsigned long pileup_minq = 0;    // -pileup_minq: a mismatch of lower quality is not counted
+    bool pileup_given = false, pileup_depth_given = false, pileup_minq_given = false;
     uint64_t insert_auto = 0;         // -insert_auto: fragments the insert bounds are estimated from before the run (real_hip_insert_bounds), 0 = off
     bool insert_flags_given = false;  // (either flag was on the command line: an error without -p2)
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)

@@ -58,8 +58,10 @@ void check(real_hip_ctx *h, int rc, const char *what)
     throw std::runtime_error(msg);
 }
 
-CtxVec makeContexts(const RealOptions &o)
+// the contexts of the run: one per device of -gpus, or `gpus` of them (the pileup pass: one, on -device)
+CtxVec makeContexts(const RealOptions &o, int gpus = 0)
 {
+    if (!gpus) gpus = o.gpus;
     real_hip_params p;
     memset(&p, 0, sizeof p);
     p.struct_size = sizeof p;
@@ -67,7 +69,7 @@ CtxVec makeContexts(const RealOptions &o)
     p.prefix_bits = o.prefix_bits; p.table_kind = o.table_kind; p.filter_mult = o.filter_mult;
     real_hip_scoring_table(o.similarity, o.gc, o.trans, o.err, o.gcmut_bias, p.LL); // Scoring(opts...) :1115
     CtxVec v;
-    for (int g = 0; g < o.gpus; ++g) {
+    for (int g = 0; g < gpus; ++g) {
         p.device = o.gpus_share_device ? o.device : o.device + g;
         std::unique_ptr<Ctx> c(new Ctx);
         check(nullptr, real_hip_create(&c->h, &p), "real_hip_create (is an MI355X visible? there is no CPU fallback)");
@@ -133,10 +135,11 @@ std::vector<std::string> genomeFiles(const RealOptions &o, const char *too_many)
 // from then on: nothing is written to it behind the drivers.)
 class OutFile {
 public:
-    explicit OutFile(const std::string &filename, bool unpaired = false) : unpaired_(unpaired), buf_((size_t)8 << 20)
+    // flag: the file of another flag than -o (never standard output), named in the errors
+    explicit OutFile(const std::string &filename, bool unpaired = false, const char *flag = nullptr) : flag_(unpaired ? "-unpaired" : flag), buf_((size_t)8 << 20)
     {
-        f_ = (!unpaired && filename == "-") ? stdout : fopen(filename.c_str(), "wb");
-        if (!f_) throw std::runtime_error((unpaired ? "cannot open the -unpaired file " : "cannot open output file ") + filename);
+        f_ = (!flag_ && filename == "-") ? stdout : fopen(filename.c_str(), "wb");
+        if (!f_) throw std::runtime_error((flag_ ? std::string("cannot open the ") + flag_ + " file " : std::string("cannot open output file ")) + filename);
         setvbuf(f_, buf_.data(), _IOFBF, buf_.size());
     }
     ~OutFile() { if (f_ == stdout) fflush(f_); else if (f_) fclose(f_); }
@@ -145,12 +148,12 @@ public:
     FILE *file() const { return f_; }
     void close()
     {
-        if (fflush(f_) != 0) throw std::runtime_error(unpaired_ ? "write to the -unpaired file failed" : "write to the output file failed");
+        if (fflush(f_) != 0) throw std::runtime_error(flag_ ? std::string("write to the ") + flag_ + " file failed" : std::string("write to the output file failed"));
         if (f_ != stdout) fclose(f_);
         f_ = nullptr;
     }
 private:
-    bool unpaired_;
+    const char *flag_;
     std::vector<char> buf_;
     FILE *f_;
 };
@@ -482,6 +485,90 @@ uint64_t listGrowing(real_hip_ctx *h, const char *what, std::vector<Hit> &hits, 
     return n;
 }
 
+// ---- -pileup / -pileup_depth: the final placements piled up over every genome file -----------------------------
+// Runs behind the output pass, when the matching contexts are gone: one fresh context on -device takes the genome files in
+// order -- the text alone, no index -- and for each of them real_hip_pileup_begin, the reads once more through
+// addAll(ctx), which hands every batch with its final records to real_hip_pileup_add / _add_pairs, and
+// real_hip_pileup_finish.  The sites and the depth runs of all files go to the two files, a summary line per file to
+// standard error.
+const uint64_t kDepthWindow = (uint64_t)64 << 20; // positions of depth[] fetched at a time
+
+void writeSites(real_hip_ctx *h, uint64_t n_sites, const GenomeText &G, FILE *f)
+{
+    std::vector<real_hip_pileup_site> sites(n_sites);
+    uint64_t n = 0;
+    check(h, real_hip_pileup_sites(h, sites.data(), sites.size(), &n, 0), "real_hip_pileup_sites");
+    size_t fr = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        const real_hip_pileup_site &S = sites[k];
+        while (fr + 1 < G.frag_names.size() && G.frag_start[fr + 1] <= S.pos) ++fr; // (ascending positions)
+        fprintf(f, "%s\t%llu\t%c\t%u\t%u\t%u\t%u\t%u\n", G.frag_names[fr].c_str(), (unsigned long long)(S.pos - G.frag_start[fr] + 1), "ACGT"[S.ref & 3u],
+                S.depth, S.alt[0], S.alt[1], S.alt[2], S.alt[3]);
+    }
+}
+
+// maximal runs of equal non-zero depth that do not cross a fragment boundary, from windows of depth[]
+void writeDepthRuns(real_hip_ctx *h, const GenomeText &G, FILE *f)
+{
+    const uint64_t n = G.sym.size();
+    std::vector<uint32_t> win((size_t)std::min<uint64_t>(n, kDepthWindow));
+    size_t fr = 0;
+    uint64_t run_start = 0;
+    uint32_t run_depth = 0;
+    auto flush = [&](uint64_t end) {
+        if (run_depth) fprintf(f, "%s\t%llu\t%llu\t%u\n", G.frag_names[fr].c_str(), (unsigned long long)(run_start - G.frag_start[fr]),
+                               (unsigned long long)(end - G.frag_start[fr]), run_depth);
+    };
+    for (uint64_t first = 0; first < n; first += kDepthWindow) {
+        const uint64_t count = std::min<uint64_t>(kDepthWindow, n - first);
+        check(h, real_hip_pileup_depth(h, first, count, win.data(), 0), "real_hip_pileup_depth");
+        for (uint64_t k = 0; k < count; ++k) {
+            const uint64_t x = first + k;
+            if (fr + 1 < G.frag_names.size() && x == G.frag_start[fr + 1]) { flush(x); ++fr; run_start = x; run_depth = 0; }
+            if (win[k] != run_depth) { flush(x); run_start = x; run_depth = win[k]; }
+        }
+    }
+    flush(n);
+}
+
+template <class AddAll>
+void pileupPass(const RealOptions &o, const std::vector<std::string> &files, AddAll addAll)
+{
+    if (!o.pileup_given && !o.pileup_depth_given) return;
+    std::unique_ptr<OutFile> sites_out(o.pileup_given ? new OutFile(o.pileupfilename, false, "-pileup") : nullptr);
+    std::unique_ptr<OutFile> depth_out(o.pileup_depth_given ? new OutFile(o.pileupdepthfilename, false, "-pileup_depth") : nullptr);
+    CtxVec ctx = makeContexts(o, 1);
+    real_hip_ctx *h = ctx[0]->h;
+    real_hip_pileup_params pp;
+    pp.struct_size = sizeof pp; pp.min_qual = (uint32_t)o.pileup_minq;
+    for (unsigned fi = 0; fi < files.size(); ++fi) {
+        GenomeText G;
+        G.load(files[fi]);
+        check(h, real_hip_set_text_symbols(h, fi, G.sym.data(), G.sym.size(), 0, G.frag_start.data(), (uint32_t)G.frag_names.size()), "real_hip_set_text_symbols");
+        check(h, real_hip_pileup_begin(h, &pp), "real_hip_pileup_begin");
+        addAll(ctx);
+        uint64_t n_sites = 0;
+        check(h, real_hip_pileup_finish(h, &n_sites), "real_hip_pileup_finish");
+        if (sites_out) writeSites(h, n_sites, G, sites_out->file());
+        if (depth_out) writeDepthRuns(h, G, depth_out->file());
+        real_hip_pileup_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        check(h, real_hip_pileup_stats_get(h, &st, 1), "real_hip_pileup_stats_get");
+        fprintf(stderr, "pileup: file=%s placements=%llu bases=%llu covered=%llu mean_depth=%.3f max_depth=%llu sites=%llu mismatches=%llu low_qual=%llu\n",
+                files[fi].c_str(), (unsigned long long)st.placed, (unsigned long long)st.bases, (unsigned long long)st.covered,
+                st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
+                (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
+        check(h, real_hip_pileup_end(h), "real_hip_pileup_end");
+    }
+    for (OutFile *f : {sites_out.get(), depth_out.get()}) {
+        if (!f) continue;
+        const bool bad = ferror(f->file()) != 0; // (a line that could not be written)
+        f->close();
+        if (bad) throw std::runtime_error("write to the -pileup / -pileup_depth file failed");
+    }
+}
+
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
 int matchUnique(const RealOptions &o)
 {
@@ -545,6 +632,14 @@ int matchUnique(const RealOptions &o)
 #pragma omp parallel for reduction(+ : unique) schedule(static)
     for (uint64_t i = 0; i < numpat; ++i) { const unsigned st = (unsigned)(info[i] >> 61); unique += (st == 1 || st == 2); }
     std::cerr << "unique: " << unique << std::endl; // :1488
+    if (o.pileup_given || o.pileup_depth_given) ctx.clear(); // (the matching contexts go before the pileup's own one comes)
+    pileupPass(o, files, [&](CtxVec &pc) {
+        const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
+            for (const ReadItem &it : items)
+                if (it.batch.n_reads) check(pc[0]->h, real_hip_pileup_add(pc[0]->h, &it.batch, info.data() + it.first_id), "real_hip_pileup_add");
+        });
+        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+    });
     T.finish(numpat, unique);
     return EXIT_SUCCESS;
 }
@@ -787,6 +882,20 @@ int matchPairs(const RealOptions &o)
             std::cerr << "insert size: n=" << est.n << " q1=" << est.q1 << " median=" << est.median << " q3=" << est.q3 << std::endl;
         else throw std::runtime_error("real_hip_insert_bounds failed");
     }
+    if (o.pileup_given || o.pileup_depth_given) ctx.clear(); // (the matching context goes before the pileup's own one comes)
+    pileupPass(o, files, [&](CtxVec &pc) {
+        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
+            if (!n) break;
+            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
+            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            check(pc[0]->h, real_hip_pileup_add_pairs(pc[0]->h, &rb1, &rb2, pairs.data() + seen), "real_hip_pileup_add_pairs");
+            seen += n;
+        }
+        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+    });
     T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;
 }

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "real_hip_pair_all_hits", "real_hip_match_pairs_all", "real_hip_pair_all_stats_get",
     "real_hip_single_hits", "real_hip_match_pairs_singles", "real_hip_single_stats_get",
     "real_hip_pair_insert_hist", "real_hip_insert_bounds", "real_hip_insert_stats_get",
+    "real_hip_pileup_begin", "real_hip_pileup_add", "real_hip_pileup_add_pairs", "real_hip_pileup_finish", "real_hip_pileup_depth",
+    "real_hip_pileup_sites", "real_hip_pileup_end", "real_hip_pileup_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -123,6 +125,28 @@ class RealHipInsertEstimate(C.Structure):
 class RealHipInsertStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("counted", C.c_uint64),
                 ("overflow", C.c_uint64), ("invalid", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+
+class RealHipPileupParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_qual", C.c_uint32)]
+
+
+class RealHipPileupSite(C.Structure):
+    """real_hip_pileup_site: one position where a placed read shows another base than the text (PILEUP_SITE_DTYPE is the same
+    record as a numpy dtype)"""
+    _fields_ = [("pos", C.c_uint32), ("depth", C.c_uint32), ("alt", C.c_uint32 * 4), ("ref", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PILEUP_SITE_DTYPE = np.dtype([("pos", "<u4"), ("depth", "<u4"), ("alt", "<u4", (4,)), ("ref", "<u4"), ("reserved", "<u4")])
+assert PILEUP_SITE_DTYPE.itemsize == 32 and C.sizeof(RealHipPileupSite) == 32
+
+PILEUP_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mismatches", "low_qual", "n_dropped", "covered", "sites",
+                       "max_depth", "launches", "kernel_ms")
+
+
+class RealHipPileupStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in PILEUP_STATS_FIELDS]
 
 
 class RealHipPairHit(C.Structure):
@@ -238,6 +262,14 @@ def load():
     L.real_hip_pair_insert_hist.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, u32, vp]
     L.real_hip_insert_bounds.argtypes = [vp, u32, u64, u32, C.POINTER(RealHipInsertEstimate)]
     L.real_hip_insert_stats_get.argtypes = [vp, C.POINTER(RealHipInsertStats), C.c_int]
+    L.real_hip_pileup_begin.argtypes = [vp, C.POINTER(RealHipPileupParams)]
+    L.real_hip_pileup_add.argtypes = [vp, C.POINTER(RealHipBatch), vp]
+    L.real_hip_pileup_add_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp]
+    L.real_hip_pileup_finish.argtypes = [vp, C.POINTER(u64)]
+    L.real_hip_pileup_depth.argtypes = [vp, u64, u64, vp, C.c_int]
+    L.real_hip_pileup_sites.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
+    L.real_hip_pileup_end.argtypes = [vp]
+    L.real_hip_pileup_stats_get.argtypes = [vp, C.POINTER(RealHipPileupStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

@@ -471,6 +471,88 @@ class HipMatcher:
             self._check(self._L.real_hip_download(self._h, C.c_void_p(int(dev_ptr)), out.ctypes.data, out.nbytes))
         return out
 
+    # -- pileup: depth and mismatch base counts per position of the resident text (include/real_hip.h, "pileup") --
+    def pileup_begin(self, min_qual: int = 0):
+        """real_hip_pileup_begin: accumulators for the resident text, zeroed; a second begin starts again"""
+        p = _lib.RealHipPileupParams()
+        p.struct_size = C.sizeof(_lib.RealHipPileupParams)
+        p.min_qual = int(min_qual)
+        self._check(self._L.real_hip_pileup_begin(self._h, C.byref(p)))
+
+    def _pileup_batch(self, bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, records_on_host) -> RealHipBatch:
+        if isinstance(bases, np.ndarray):
+            bases = np.ascontiguousarray(bases, dtype=np.uint8)
+            qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
+            offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
+        if packed and offsets is None and n_reads is None:
+            raise ValueError("a packed batch of uniform length needs n_reads")
+        b = self._batch(bases, qual, offsets, patl, n_reads, max_patl)
+        if b.on_device and records_on_host:
+            b.on_device = 2
+        b.packed = int(bool(packed))
+        b.nflags = _ptr(nflags)
+        b._keep = (bases, qual, offsets, nflags)
+        self.sync_inputs(bases, qual, offsets, nflags)
+        return b
+
+    def pileup_add(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
+                   packed: bool = False, nflags=None):
+        """real_hip_pileup_add: the placements of the records `info` (what match_unique returned for this batch).  Host
+        numpy arrays, device torch tensors, or device reads with numpy records (on_device = 2)."""
+        host_info = isinstance(info, np.ndarray)
+        if host_info:
+            info = np.ascontiguousarray(info, dtype=np.uint64)
+        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
+        if int(info.shape[0]) != int(b.n_reads):
+            raise ValueError("one record per read")
+        self.sync_inputs(info)
+        self._check(self._L.real_hip_pileup_add(self._h, C.byref(b), _ptr(info)))
+
+    def pileup_add_pairs(self, mate1, mate2, pairs):
+        """real_hip_pileup_add_pairs: both mates of every Unique record of `pairs` (what match_pairs returned); mates as
+        (bases, qual, offsets) tuples or ReadBatch-like objects, all host arrays or all device tensors"""
+        host_pairs = isinstance(pairs, np.ndarray)
+        if host_pairs:
+            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
+        bs = []
+        for mate in (mate1, mate2):
+            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
+            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
+        self.sync_inputs(pairs)
+        self._check(self._L.real_hip_pileup_add_pairs(self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs)))
+
+    def pileup_finish(self) -> int:
+        """real_hip_pileup_finish: scans the depth and compacts the sites; returns the number of sites"""
+        n = C.c_uint64(0)
+        self._check(self._L.real_hip_pileup_finish(self._h, C.byref(n)))
+        return int(n.value)
+
+    def pileup_depth(self, first: int, count: int, out=None) -> np.ndarray:
+        """depth[first .. first + count) as numpy uint32 (out: a device torch tensor of count 32-bit words instead)"""
+        on_device = bool(getattr(out, "is_cuda", False))
+        if out is None:
+            out = np.zeros(int(count), dtype=np.uint32)
+        self.sync_inputs(out)
+        self._check(self._L.real_hip_pileup_depth(self._h, int(first), int(count), _ptr(out), int(on_device)))
+        return out
+
+    def pileup_sites(self, cap: int = 1024) -> np.ndarray:
+        """the site list as lib.PILEUP_SITE_DTYPE, ascending position; the buffer grows once to the size the library reports"""
+        n = C.c_uint64(0)
+        out = np.zeros(int(cap), dtype=_lib.PILEUP_SITE_DTYPE)
+        rc = self._L.real_hip_pileup_sites(self._h, out.ctypes.data, int(cap), C.byref(n), 0)
+        if rc == _lib.REAL_HIP_E_OVERFLOW:
+            out = np.zeros(int(n.value), dtype=_lib.PILEUP_SITE_DTYPE)
+            rc = self._L.real_hip_pileup_sites(self._h, out.ctypes.data, int(n.value), C.byref(n), 0)
+        self._check(rc)
+        return out[:int(n.value)]
+
+    def pileup_end(self):
+        self._check(self._L.real_hip_pileup_end(self._h))
+
+    def pileup_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipPileupStats, self._L.real_hip_pileup_stats_get, _lib.PILEUP_STATS_FIELDS, reset)
+
     # -- instrumentation --
     def counters(self, reset: bool = False) -> dict:
         c = RealHipCounters()
