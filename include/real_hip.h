@@ -546,6 +546,60 @@ typedef struct real_hip_pileup_stats {
 } real_hip_pileup_stats;
 int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
 
+/* ---- mismatch lists: where each finally placed read differs from the resident text -- what NM / MD of a SAM line are
+ * written from.  The reference has no such output; the semantics are this project's own.  PLACEMENT, ORIENTED
+ * base, the resident text (n bases, file id f) are the pileup's, word for word.
+ * Single-end (real_hip_mismatches): read i is list i.  An info record of state 1 or 2 is a placement of its read at the
+ * record's pos, on the reverse strand iff the state is 2; the mismatch count it carries is its errors field.
+ * Paired-end (real_hip_mismatches_pairs): mate 1 of fragment i is list 2i, mate 2 list 2i + 1.  The FINAL placement of a
+ * mate: if the pair record's state is REAL_HIP_PAIR_UNIQUE, mate 1 lies at pos1 on strand inverted1 with k1 mismatches, mate
+ * 2 at pos2 on the other strand with k2; otherwise, if singles are given AND the pair record's state is REAL_HIP_PAIR_NOMATCH
+ * AND the mate's single record is Unique, the mate lies at the single's pos on the single's strand with REAL_HIP_SINGLE_K
+ * mismatches (the rule `real -unpaired` prints by); a NonUnique pair record places nothing, whatever the singles say.
+ * A record of another state gets an empty list; then a record of another file id than f gets an empty list and is counted as
+ * other_file; then a placement with p + L > n gets an empty list and is counted as invalid.
+ * The list of a placement holds every offset i in 0 .. L-1 where the text's N bit at p + i is set (ref = 4, whatever the
+ * read shows) and, elsewhere, every offset where the oriented base differs from the 2-bit text; ascending offset.  A placed
+ * read holds symbols 0..3 only (the matcher places no other read): the lists of a read with another symbol are undefined.
+ * out[mm_offsets[j] .. mm_offsets[j+1]) is list j; mm_offsets has one entry more than there are lists and starts at 0.
+ * The output is a function of records, reads and text alone: nothing depends on lanes, blocks or calls, and two calls on
+ * the halves of a batch give the lists of one call on the whole, up to rebasing the offsets.
+ * info / pairs / singles live where the match left them for the batch's on_device: host memory for 0 and 2, device memory
+ * for 1 (pairs 8-byte, singles 16-byte aligned).  out and mm_offsets are host memory for 0 and 2 and device memory for 1
+ * (out 4-byte aligned); n_out is host memory and always receives the total.  When the total exceeds cap the call returns
+ * REAL_HIP_E_OVERFLOW and writes nothing to out (mm_offsets is still written): the count is known before anything is
+ * emitted, the protocol of real_hip_pair_all_hits.  n_reads == 0 is valid: mm_offsets[0] = 0.  The calls need the text,
+ * not the index: REAL_HIP_E_STATE without it.  REAL_HIP_E_INVALID with a message, nothing launched: a NULL mm_offsets or
+ * n_out, a NULL out with cap > 0, NULL records with n_reads > 0, one singles pointer without the other, batches that
+ * disagree in n_reads or on_device, more than 2^32 reads.  Reads of any length up to REAL_HIP_MAX_PATL_LONG.            */
+typedef struct real_hip_mismatch {   /* 4 bytes */
+    uint16_t off;    /* 0-based offset from the placement's text position p: text position p + off; < L <= 16384 */
+    uint8_t  ref;    /* the text's base 0..3, or 4 where the text's N bit is set                                  */
+    uint8_t  base;   /* the read's ORIENTED base there, 0..3                                                      */
+} real_hip_mismatch;
+int real_hip_mismatches(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info,
+                        real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, uint64_t *mm_offsets /* n_reads + 1 */);
+int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs,
+                              const real_hip_single *singles1, const real_hip_single *singles2 /* both or neither NULL */,
+                              real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, uint64_t *mm_offsets /* 2 * n_reads + 1 */);
+/* work of the lists, accumulated since the last reset.  disagree counts the placements whose list length differs from the
+ * mismatch count their record carries: the cross-check between the matcher's verification and this kernel, 0 for records
+ * that come from this library's matchers (they place no read over an N).                                                 */
+typedef struct real_hip_mismatch_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_mismatch_stats), 0                           */
+    uint64_t reads;         /* lists asked for (a pair counts two)                                    */
+    uint64_t placed;        /* placements walked                                                      */
+    uint64_t other_file;    /* placed reads of another file id                                        */
+    uint64_t invalid;       /* placements that end behind the text                                    */
+    uint64_t bases;         /* sum of L over the placements                                           */
+    uint64_t mismatches;    /* entries written, or counted by a call that overflowed                  */
+    uint64_t on_n;          /* of those, the entries with ref = 4                                     */
+    uint64_t disagree;      /* placements whose list length is not the record's mismatch count        */
+    uint64_t launches;      /* kernels launched (the scan counts one)                                 */
+    double   kernel_ms;     /* HIP events on the ctx's stream around count, scan and emit             */
+} real_hip_mismatch_stats;
+int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -2,7 +2,8 @@
 // placed read shows another base than the text, how often each base was seen (include/real_hip.h, "pileup").
 //
 // pileup_add_kernel: one lane per read, and the lane WALKS ITS READ WORD BY WORD -- 32 bases at a time, whatever the length
-// (up to REAL_HIP_MAX_PATL_LONG): no register array of the read, no second kernel for long reads.  Per word the lane packs
+// (up to REAL_HIP_MAX_PATL_LONG): no register array of the read, no second kernel for long reads (the walk itself is
+// read_walk.h, shared with mismatch_list.hip).  Per word the lane packs
 // the 32 read bases that lie over the next 32 text positions with match_common.h's pack_read / pack_read_packed (W = 1; a
 // packed read may start inside a byte) -- on the reverse strand those are the read's LAST unvisited bases, turned round with
 // revcomp_words -- loads the 2-bit text funnel-shifted to the placement and takes XOR: one flag per base.  Every flagged
@@ -18,7 +19,7 @@
 // Everything is an integer sum: nothing depends on the order of reads, lanes, blocks or calls.  No LDS in the add kernel,
 // no scratch memory; plain C++ and vector stores.
 #include "real_hip_internal.h"
-#include "match_common.h"
+#include "read_walk.h"
 #include "pair_state.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -26,25 +27,6 @@
 #include <cstring>
 
 #define RH_PU_BLOCK 256u
-
-// a read's bytes in place, a dword per request: the aligned dword that holds the first byte asked for and, where the request
-// straddles it and the row goes on, the next one.  Never a dword without a byte of the row in it (an aligned dword does not
-// cross a page, so nothing outside the caller's allocation's pages is touched); bytes behind the row's end come back as
-// whatever lies there, and pack_read / pack_read_packed mask them off.
-struct DwordRow {
-    const uint8_t *row;
-    __device__ __forceinline__ uint32_t dword(int byteoff, uint32_t nbytes) const
-    {
-        if (byteoff < 0 || (uint32_t)byteoff >= nbytes) return 0;
-        const uintptr_t a = (uintptr_t)(row + byteoff);
-        const uint32_t mis = (uint32_t)(a & 3u);
-        const uint32_t *p = reinterpret_cast<const uint32_t *>(a - mis);
-        const uint32_t lo = p[0];
-        uint32_t hi = 0;
-        if (mis && (uint32_t)byteoff + (4u - mis) < nbytes) hi = p[1];
-        return __builtin_amdgcn_alignbyte(hi, lo, mis);
-    }
-};
 
 struct PileupArgs {
     DevText  t;
@@ -88,32 +70,20 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_add_kernel(const PileupArg
         uint64_t start = 0;
         uint32_t L = 0;
         if (place) {
-            if (A.b.off) { start = A.b.off[i]; const uint64_t e = A.b.off[i + 1]; L = e >= start && e - start <= REAL_HIP_MAX_PATL_LONG ? (uint32_t)(e - start) : 0xffffffffu; }
-            else { start = i * (uint64_t)A.b.upatl; L = A.b.upatl; }
+            L = read_extent(A.b, i, start);
             if ((uint64_t)p + L > A.t.n) { place = false; ++invalid; }
         }
         if (place) {
             placed = 1; bases = L;
             atomicAdd(A.diff + p, 1u);
             atomicAdd(A.diff + (uint64_t)p + L, 0xffffffffu);
-            const uint64_t wi = p >> 5;
-            const uint32_t sh = 2u * (p & 31u);
             const uint32_t nw = (L + 31u) >> 5;
-            uint64_t t0 = nw ? A.t.text[wi] : 0;
+            ReadWalk walk;
+            walk.begin(A.t.text, p, L);
             for (uint32_t j = 0; j < nw; ++j) {
-                const uint32_t nb = min(32u, L - 32u * j);
-                // the nb read bases over text positions p + 32j ..: read[32j ..] forward, read[L - 32j - nb ..] turned round
-                const uint64_t s = start + (inv ? L - 32u * j - nb : 32u * j);
-                uint64_t w, o;
-                if (A.b.packed) pack_read_packed<1>(DwordRow{A.b.bases + (s >> 2)}, nb, (uint32_t)(s & 3u), &w);
-                else (void)pack_read<1>(DwordRow{A.b.bases + s}, nb, &w);
-                if (inv) revcomp_words<1>(&w, &o, nb); else o = w;
-                const uint64_t t1 = A.t.text[wi + j + 1]; // (the text is padded behind its end)
-                const uint64_t al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
-                t0 = t1;
-                const uint64_t x = al ^ o;
-                uint64_t flags = ((x >> 1) | x) & M55;
-                if (nb < 32) flags &= ~0ull << (64 - 2 * nb);
+                uint32_t nb;
+                uint64_t al, o;
+                uint64_t flags = walk.step(A.b, start, L, inv, j, nb, al, o); // one flag per base that differs from the text
                 while (flags) {
                     const uint32_t u = (uint32_t)__clzll((long long)flags) >> 1; // base u of the word: its flag is bit 62 - 2u
                     flags &= ~(1ull << (62 - 2 * u));

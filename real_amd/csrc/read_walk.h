@@ -1,0 +1,67 @@
+// read_walk.h -- a lane walks one placed read word by word against the 2-bit text: what pileup.hip (counts per text position)
+// and mismatch_list.hip (the list of one read) share.  32 bases per step, whatever the length (up to
+// REAL_HIP_MAX_PATL_LONG): no register array of the read.  No LDS, no scratch memory.
+#pragma once
+#include "match_common.h"
+
+// a read's bytes in place, a dword per request: the aligned dword that holds the first byte asked for and, where the request
+// straddles it and the row goes on, the next one.  Never a dword without a byte of the row in it (an aligned dword does not
+// cross a page, so nothing outside the caller's allocation's pages is touched); bytes behind the row's end come back as
+// whatever lies there, and pack_read / pack_read_packed mask them off.
+struct DwordRow {
+    const uint8_t *row;
+    __device__ __forceinline__ uint32_t dword(int byteoff, uint32_t nbytes) const
+    {
+        if (byteoff < 0 || (uint32_t)byteoff >= nbytes) return 0;
+        const uintptr_t a = (uintptr_t)(row + byteoff);
+        const uint32_t mis = (uint32_t)(a & 3u);
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(a - mis);
+        const uint32_t lo = p[0];
+        uint32_t hi = 0;
+        if (mis && (uint32_t)byteoff + (4u - mis) < nbytes) hi = p[1];
+        return __builtin_amdgcn_alignbyte(hi, lo, mis);
+    }
+};
+
+// The walk of a read of L bases that starts at base `start` of the batch and lies at text position p (p + L <= n), reverse
+// strand iff inv.  step(j) is word j = the text positions p + 32j .. p + 32j + nb - 1, j ascending from 0:
+//   al     the text there, funnel-shifted to the placement (base u of the word at bits 63 - 2u, 62 - 2u)
+//   o      the ORIENTED read there: read[32j ..] forward, read[L - 32j - nb ..] turned round with revcomp_words
+//   return one flag per base that differs, base u at bit 62 - 2u; nothing behind the read's end
+struct ReadWalk {
+    const uint64_t *text;
+    uint64_t wi, t0;
+    uint32_t sh;
+    __device__ __forceinline__ void begin(const uint64_t *T, uint32_t p, uint32_t L)
+    {
+        text = T; wi = p >> 5; sh = 2u * (p & 31u);
+        t0 = L ? T[wi] : 0;
+    }
+    __device__ __forceinline__ uint64_t step(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb, uint64_t &al,
+                                             uint64_t &o)
+    {
+        nb = min(32u, L - 32u * j);
+        const uint64_t s = start + (inv ? L - 32u * j - nb : 32u * j);
+        uint64_t w;
+        if (b.packed) pack_read_packed<1>(DwordRow{b.bases + (s >> 2)}, nb, (uint32_t)(s & 3u), &w);
+        else (void)pack_read<1>(DwordRow{b.bases + s}, nb, &w);
+        if (inv) revcomp_words<1>(&w, &o, nb); else o = w;
+        const uint64_t t1 = text[wi + j + 1]; // (the text is padded behind its end)
+        al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
+        t0 = t1;
+        const uint64_t x = al ^ o;
+        uint64_t flags = ((x >> 1) | x) & M55;
+        if (nb < 32) flags &= ~0ull << (64 - 2 * nb);
+        return flags;
+    }
+};
+
+// where a read starts in its batch and how long it is; 0xffffffff for a read of a ragged batch whose offsets run backwards or
+// span more than REAL_HIP_MAX_PATL_LONG (no placement of it fits any text)
+static __device__ __forceinline__ uint32_t read_extent(const DevBatch &b, uint64_t i, uint64_t &start)
+{
+    if (!b.off) { start = i * (uint64_t)b.upatl; return b.upatl; }
+    start = b.off[i];
+    const uint64_t e = b.off[i + 1];
+    return e >= start && e - start <= REAL_HIP_MAX_PATL_LONG ? (uint32_t)(e - start) : 0xffffffffu;
+}

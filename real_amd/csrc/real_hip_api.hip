@@ -1157,6 +1157,90 @@ extern "C" int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stat
     return rh_pileup_stats(ctx, out, reset);
 }
 
+// ---- mismatch lists (mismatch_list.hip): the reads are staged as the pileup stages them, the records as the match's outputs;
+// count, then -- the total being known -- the overflow decision, then the lists (pair_all_run's protocol)
+static int mismatch_outputs_check(real_hip_ctx *ctx, const real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, const uint64_t *mm_offsets, bool dev_out)
+{
+    if (!mm_offsets || !n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null mm_offsets / n_out", hipSuccess);
+    *n_out = 0;
+    if (cap && !out) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null out", hipSuccess);
+    if (dev_out && ((uintptr_t)out & 3u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: out must be 4-byte aligned", hipSuccess);
+    return REAL_HIP_OK;
+}
+static int mismatch_run(real_hip_ctx *ctx, const RhStaging &io, const RhMismatchLaunch l[], int n_launch, real_hip_mismatch *out, uint64_t cap,
+                        uint64_t *n_out, uint64_t *mm_offsets)
+{
+    const uint64_t lists = l[0].b.n_reads * (uint64_t)n_launch;
+    uint64_t *d_off = mm_offsets;
+    int rc;
+    if ((rc = io.inout(ctx->mm_off, mm_offsets, lists + 1, true, d_off))) return rc; // (outputs: nothing is uploaded)
+    uint64_t total = 0;
+    if ((rc = rh_mismatch_count(ctx, l, n_launch, d_off, &total))) return rc;
+    *n_out = total;
+    if ((rc = io.back(mm_offsets, d_off, lists + 1, "download of the mismatch offsets"))) return rc;
+    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "mismatch lists: the buffer needs more room", hipSuccess);
+    real_hip_mismatch *d_out = out;
+    if ((rc = io.inout(ctx->mm_out, out, total, true, d_out, sizeof(real_hip_mismatch)))) return rc;
+    if ((rc = rh_mismatch_emit(ctx, l, n_launch, d_off, d_out, total))) return rc;
+    return io.back(out, d_out, total, "download of the mismatch lists");
+}
+
+extern "C" int real_hip_mismatches(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info, real_hip_mismatch *out, uint64_t cap,
+                                   uint64_t *n_out, uint64_t *mm_offsets)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = batch_view(ctx, b, bv);
+    if (rc || (rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, bv.on_device == 1))) return rc;
+    const uint64_t n = bv.n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: more than 2^32 reads in one call", hipSuccess);
+    if (n && !info) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null info", hipSuccess);
+    Staged s;
+    if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
+    RhMismatchLaunch l{dev_batch(ctx, s, n), info, nullptr, nullptr};
+    if (n) rc = io.in(ctx->mm_rec, info, n, l.info);
+    if (!rc) rc = mismatch_run(ctx, io, &l, 1, out, cap, n_out, mm_offsets);
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs,
+                                         const real_hip_single *singles1, const real_hip_single *singles2, real_hip_mismatch *out, uint64_t cap,
+                                         uint64_t *n_out, uint64_t *mm_offsets)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv[2];
+    int rc;
+    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1]))) return rc;
+    const bool dev = bv[0].on_device == 1;
+    if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev))) return rc;
+    if (bv[0].n_reads != bv[1].n_reads || bv[0].on_device != bv[1].on_device)
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: the mates' batches must agree in n_reads and on_device", hipSuccess);
+    if ((singles1 != nullptr) != (singles2 != nullptr)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: one singles array without the other", hipSuccess);
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: more than 2^32 reads in one call", hipSuccess);
+    if (n && !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null pairs", hipSuccess);
+    if (dev && (((uintptr_t)pairs & 7u) || ((uintptr_t)singles1 & 15u) || ((uintptr_t)singles2 & 15u)))
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: the pair records must be 8-byte, the single records 16-byte aligned", hipSuccess);
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    RhMismatchLaunch l[2] = {{dev_batch(ctx, st[0], n), nullptr, pairs, singles1}, {dev_batch(ctx, st[1], n), nullptr, pairs, singles2}};
+    if (n) rc = io.in(ctx->mm_rec, pairs, n, l[0].pairs);
+    l[1].pairs = l[0].pairs;
+    for (int m = 0; m < 2 && !rc && n && singles1; ++m) rc = io.in(ctx->mm_sg[m], m ? singles2 : singles1, n, l[m].singles);
+    if (!rc) rc = mismatch_run(ctx, io, l, 2, out, cap, n_out, mm_offsets);
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_mismatch_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch stats struct_size", hipSuccess);
+    return rh_mismatch_stats(ctx, out, reset);
+}
+
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
 // hold mate m's unified hit lists, their n + 1 offsets and the read lengths; total[m] is an upper bound of the hits inside
 // the buffer (the matcher's count before duplicates go).  both_resident: mate 2 is staged into buffers of its own, so that

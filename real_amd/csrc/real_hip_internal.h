@@ -300,6 +300,11 @@ struct real_hip_ctx {
     uint64_t pu_n = 0, pu_n_sites = 0, pu_covered = 0, pu_max_depth = 0; // the text begin saw; the last finish
     uint32_t pu_fileid = 0, pu_min_qual = 0;
 
+    // mismatch lists (mismatch_list.hip): the counts per list, and when the caller's arrays are host memory the staged
+    // records (info or pairs, the two mates' singles), the offsets and the lists
+    DevBuf mm_cnt, mm_off, mm_out, mm_rec, mm_sg[2];
+    RhStage mismatch;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -440,6 +445,21 @@ int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d
 int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites); // synchronises
 void rh_pileup_end(real_hip_ctx *ctx);
 int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
+
+// ---- mismatch lists (mismatch_list.hip) -------------------------------------------------
+// one launch: the reads and the records that place them, all arrays on the device: info (single-end), or pairs and -- nullable --
+// this mate's singles
+struct RhMismatchLaunch {
+    DevBatch b;
+    const uint64_t *info;
+    const real_hip_pair *pairs;
+    const real_hip_single *singles;
+};
+// l[0] (single-end: n lists) or l[0], l[1] = mate 1, mate 2 (pairs: 2n lists, mate m of fragment i is list 2i + m).  count +
+// scan into d_off (lists + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
+int rh_mismatch_count(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, uint64_t *d_off, uint64_t *total);
+int rh_mismatch_emit(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, const uint64_t *d_off, real_hip_mismatch *d_out, uint64_t total);
+int rh_mismatch_stats(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

@@ -47,19 +47,31 @@ struct Spans {
     std::vector<uint64_t> off; // n+1
 };
 
-// the sequence either as the characters of the read file (text) or as mapped symbols (mapped): the other one is null
+// the sequence either as the characters of the read file (text) or as mapped symbols (mapped): the other one is null.
+// qual: the quality of base i is (uint8_t)(qual[i] - qsub) -- the characters of the read file less the quality offset, or
+// the host reader's values less 0; null for FASTA, and for a source that was not asked for the qualities (withQuality)
 struct ReadView {
     const char *id;
     size_t idlen;
     const char *text;
     const uint8_t *mapped;
     uint64_t patl;
+    const uint8_t *qual;
+    uint8_t qsub;
 };
 
 class ReadSource {
 public:
-    ReadSource(const Chunk &c, const Spans &s) : text_(c.text), id_start_(s.id_start.data()), id_len_(s.id_len.data()), off_(s.off.data()), n_(s.id_start.size()) {}
+    ReadSource(const Chunk &c, const Spans &s)
+        : text_(c.text), text_end_(c.text + c.size), id_start_(s.id_start.data()), id_len_(s.id_len.data()), off_(s.off.data()), n_(s.id_start.size()) {}
     explicit ReadSource(const ReadBlock &b) : blk_(&b) {} // (follows the block: what the reader fills in next is seen)
+    // the same reads with their qualities in the views (the SAM lines): of a FASTQ file read with quality offset qoff
+    ReadSource withQuality(bool fastq, int qoff) const
+    {
+        ReadSource r = *this;
+        r.qoff_ = fastq ? qoff : -1;
+        return r;
+    }
     uint64_t size() const { return blk_ ? blk_->size() : n_; }
     ReadView operator[](uint64_t i) const
     {
@@ -69,6 +81,7 @@ public:
             v.id = blk_->ids[i].data(); v.idlen = blk_->ids[i].size();
             v.text = nullptr; v.mapped = &blk_->bases[lo];
             v.patl = blk_->offsets[i + 1] - lo;
+            v.qual = qoff_ >= 0 ? &blk_->qual[lo] : nullptr; v.qsub = 0;
         } else {
             // the id is everything behind the marker up to the newline (a '\r' in front of it included, as the
             // reference's reader keeps it); the sequence is the next line
@@ -76,15 +89,22 @@ public:
             if (v.id[v.idlen] == '\r') v.idlen++;
             v.text = v.id + v.idlen + 1; v.mapped = nullptr;
             v.patl = off_[i + 1] - off_[i];
+            v.qual = nullptr; v.qsub = 0;
+            if (qoff_ >= 0) { // one line per field: behind the sequence line comes the '+' line, then the qualities
+                const char *q = (const char *)memchr(v.text + v.patl, '\n', (size_t)(text_end_ - (v.text + v.patl)));
+                if (q) q = (const char *)memchr(q + 1, '\n', (size_t)(text_end_ - (q + 1)));
+                if (q && q + 1 + v.patl <= text_end_) { v.qual = (const uint8_t *)(q + 1); v.qsub = (uint8_t)qoff_; }
+            }
         }
         return v;
     }
 private:
-    const char *text_ = nullptr; // a chunk and its n_ spans (as they are when the source is made), or
+    const char *text_ = nullptr, *text_end_ = nullptr; // a chunk and its n_ spans (as they are when the source is made), or
     const uint32_t *id_start_ = nullptr, *id_len_ = nullptr;
     const uint64_t *off_ = nullptr;
     uint64_t n_ = 0;
     const ReadBlock *blk_ = nullptr; // a block
+    int qoff_ = -1;                  // >= 0: the views carry the qualities
 };
 
 // where a read lies: pos1 is the 1-based position in the fragment; the score is printed only where scores are on

@@ -66,6 +66,14 @@ void RealOptions::printHelp() const
               << "-pileup_depth <file: the depth as runs: fragment name, 0-based start, end, depth, for the maximal runs of equal\n"
               << "   non-zero depth inside a fragment; same conditions as -pileup>\n"
               << "-pileup_minq <Q: with -pileup, a mismatch of quality below Q is not counted, 0..63, default=0>\n"
+              << "-sam <file: after the output pass, write EVERY read as a SAM line (header: one @SQ per fragment of every genome file): a\n"
+              << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255, CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
+              << "   its mismatch list, computed on one fresh context on -device (ZS:f: the score, with -q 1); an unplaced read with FLAG 4.\n"
+              << "   With -p2 the final placement of a mate is its Unique pair's, else -- for a fragment without any concordant pair -- its\n"
+              << "   own unique one (the rule of -unpaired), and the lines carry the pair flags, RNEXT / PNEXT and TLEN (the outer distance,\n"
+              << "   Unique pairs only).  Order: per genome file the reads placed in it, in read order, an unplaced mate beside its placed\n"
+              << "   mate; reads and fragments with nothing placed in the pass of the last file; two mates placed in different files\n"
+              << "   appear each in its own file's pass (@HD SO:unknown).  -o is unchanged; needs -u 1, not with -pairs_all 1>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -133,6 +141,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pileup") { pileupfilename = need("-pileup"); pileup_given = true; i += 2; }
         else if (a == "-pileup_depth") { pileupdepthfilename = need("-pileup_depth"); pileup_depth_given = true; i += 2; }
         else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
+        else if (a == "-sam") { samfilename = need("-sam"); sam_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -208,6 +217,17 @@ RealOptions::RealOptions(int argc, char *argv[])
         }
         if (pileup_given && pileup_depth_given && pileupfilename == pileupdepthfilename)
             throw std::runtime_error("-pileup and -pileup_depth must name two files.");
+    }
+    if (sam_given) { // SAM output: loud errors before anything runs
+        if (!match_unique) throw std::runtime_error("-sam writes the unique placement of a read: it cannot be combined with -u 0.");
+        if (pairs_all) throw std::runtime_error("-sam writes the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
+        if (samfilename.empty()) throw std::runtime_error("-sam needs a file name: an empty one was given.");
+        if (samfilename == "-") throw std::runtime_error("-sam writes to a file: standard output (-) cannot be it.");
+        if (samfilename == outputfilename) throw std::runtime_error("-sam must name a file of its own: it names the same file as -o.");
+        if (unpaired_given && samfilename == unpairedfilename) throw std::runtime_error("-sam must name a file of its own: it names the same file as -unpaired.");
+        if (!inserthistfilename.empty() && samfilename == inserthistfilename) throw std::runtime_error("-sam must name a file of its own: it names the same file as -insert_hist.");
+        if ((pileup_given && samfilename == pileupfilename) || (pileup_depth_given && samfilename == pileupdepthfilename))
+            throw std::runtime_error("-sam must name a file of its own: it names the same file as -pileup / -pileup_depth.");
     }
     if (pileup_minq_given && !pileup_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
     if (pileup_minq > 63) throw std::runtime_error("-pileup_minq takes a quality of at most 63.");

@@ -59,6 +59,8 @@ struct RealOptions {
     std::string pileupdepthfilename;  // -pileup_depth: the file that receives the depth as runs
     unsigned long pileup_minq = 0;    // -pileup_minq: a mismatch of lower quality is not counted
     bool pileup_given = false, pileup_depth_given = false, pileup_minq_given = false;
+    std::string samfilename;          // -sam: the file that receives the final placements as SAM with NM / MD (real_hip_mismatches*)
+    bool sam_given = false;
     uint64_t insert_auto = 0;         // -insert_auto: fragments the insert bounds are estimated from before the run (real_hip_insert_bounds), 0 = off
     bool insert_flags_given = false;  // (either flag was on the command line: an error without -p2)
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)

@@ -9,6 +9,10 @@
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 //   host_selftest lines <reads.fq> <outdir>       -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
+//   host_selftest sam <dir> <fastq:0|1> <qoff> <scores:0|1> <paired:0|1> -> <dir>/block.sam chunk.sam: the -sam file of the reads <dir>/r1 (and r2)
+//       from the records in <dir> (names.txt: a line "file<TAB>start<TAB>name" per fragment and one "file<TAB>n<TAB>" behind a file's
+//       last; info.u64 score.f32, or pairs.bin s1.bin s2.bin; per genome file mm<fi>.bin moff<fi>.u64), formatted by Sam.hpp from
+//       the host reader's blocks and (single-end) from the text
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +25,7 @@
 #include "Lines.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
+#include "Sam.hpp"
 #include "row_addr.h"
 #include <vector>
 
@@ -31,11 +36,87 @@ static void dump(const std::string &fn, const T *p, size_t n)
     o.write(reinterpret_cast<const char *>(p), n * sizeof(T));
 }
 
+template <typename T>
+static std::vector<T> slurp(const std::string &fn)
+{
+    std::ifstream f(fn.c_str(), std::ios::binary);
+    std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+    std::vector<T> v(raw.size() / sizeof(T));
+    if (!v.empty()) memcpy(v.data(), raw.data(), v.size() * sizeof(T));
+    return v;
+}
+
+// the -sam file from records and lists on disk, through the functions `real` formats with
+static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, bool paired)
+{
+    std::vector<std::vector<std::string>> names;
+    std::vector<std::vector<uint64_t>> starts;
+    std::ifstream nf((d + "/names.txt").c_str());
+    for (std::string line; std::getline(nf, line);) {
+        const size_t a = line.find('\t'), b = line.find('\t', a + 1);
+        const size_t f = (size_t)atoi(line.substr(0, a).c_str());
+        if (names.size() <= f) { names.resize(f + 1); starts.resize(f + 1); }
+        starts[f].push_back(strtoull(line.substr(a + 1, b - a - 1).c_str(), 0, 10));
+        if (b + 1 < line.size()) names[f].push_back(line.substr(b + 1)); // (the line behind a file's last fragment has no name: its start is n)
+    }
+    const SamRefs refs(names, starts);
+    const std::vector<uint64_t> info = slurp<uint64_t>(d + "/info.u64");
+    const std::vector<float> score = slurp<float>(d + "/score.f32");
+    const std::vector<real_hip_pair> pairs = slurp<real_hip_pair>(d + "/pairs.bin");
+    const std::vector<real_hip_single> s1 = slurp<real_hip_single>(d + "/s1.bin"), s2 = slurp<real_hip_single>(d + "/s2.bin");
+    // the reads, whole: as one block of the host reader and (single-end) as one chunk of text with its spans
+    ReadBlock b1, b2;
+    ReadReader r1(d + "/r1", fastq, qoff);
+    const uint64_t n = r1.fillBlock(b1, ~0ull, true);
+    if (paired) { ReadReader r2(d + "/r2", fastq, qoff); if (r2.fillBlock(b2, ~0ull, true) != n) return 3; }
+    std::vector<char> text;
+    Spans sp;
+    if (!paired) {
+        std::ifstream f((d + "/r1").c_str(), std::ios::binary);
+        text.assign((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        sp.off.push_back(0);
+        for (size_t p = 0; p < text.size();) { // one line per field
+            const char *idl = (const char *)memchr(&text[p], '\n', text.size() - p);
+            const size_t seq = (size_t)(idl - text.data()) + 1;
+            const size_t seq_end = (size_t)((const char *)memchr(&text[seq], '\n', text.size() - seq) - text.data());
+            sp.id_start.push_back((uint32_t)(p + 1)); sp.id_len.push_back((uint32_t)(seq - 1 - (p + 1)));
+            sp.off.push_back(sp.off.back() + (seq_end - seq));
+            p = seq_end + 1;
+            if (fastq) for (int k = 0; k < 2; ++k) p = (size_t)((const char *)memchr(&text[p], '\n', text.size() - p) - text.data()) + 1;
+        }
+        if (sp.id_start.size() != n) return 4;
+    }
+    Chunk ch;
+    ch.text = text.data(); ch.size = ch.cap = text.size();
+    for (int form = 0; form < (paired ? 1 : 2); ++form) {
+        std::string out = refs.header();
+        const ReadSource v1 = (form ? ReadSource(ch, sp) : ReadSource(b1)).withQuality(fastq, qoff), v2 = ReadSource(b2).withQuality(fastq, qoff);
+        for (unsigned fi = 0; fi < names.size(); ++fi) {
+            const std::vector<real_hip_mismatch> mm = slurp<real_hip_mismatch>(d + "/mm" + std::to_string(fi) + ".bin");
+            const std::vector<uint64_t> moff = slurp<uint64_t>(d + "/moff" + std::to_string(fi) + ".u64");
+            const bool last = fi + 1 == names.size();
+            for (uint64_t i = 0; i < n; ++i) {
+                if (!paired) {
+                    appendSamRead(out, v1[i], refs, samPlace(unpack(info[i]), scores ? score[i] : 0.f), fi, last, mm.data() + moff[i], moff[i + 1] - moff[i], scores);
+                } else {
+                    const ReadView r[2] = {v1[i], v2[i]};
+                    const SamPlace at[2] = {samPlace(pairs[i], s1[i], 0), samPlace(pairs[i], s2[i], 1)};
+                    appendSamFragment(out, r, refs, at, fi, last, mm.data(), moff.data(), i, scores);
+                }
+            }
+        }
+        std::ofstream o((d + (form ? "/chunk.sam" : "/block.sam")).c_str(), std::ios::binary);
+        o.write(out.data(), (std::streamsize)out.size());
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     try {
         if (argc < 2) return 2;
         std::string cmd = argv[1];
+        if (cmd == "sam" && argc == 7) return samSelftest(argv[2], atoi(argv[3]) != 0, atoi(argv[4]), atoi(argv[5]) != 0, atoi(argv[6]) != 0);
         if (cmd == "genome" && argc == 4) {
             GenomeText G; G.load(argv[2]);
             std::string d = argv[3];

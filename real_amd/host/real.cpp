@@ -39,6 +39,7 @@
 #include "Lines.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
+#include "Sam.hpp"
 #include "real_hip.h"
 
 namespace {
@@ -531,20 +532,38 @@ void writeDepthRuns(real_hip_ctx *h, const GenomeText &G, FILE *f)
     flush(n);
 }
 
+// What the passes behind the output pass share (-pileup, -sam): one fresh context on -device takes the genome files in order,
+// the text alone, and perFile(ctx, fi, G) runs with each of them resident.
+template <class PerFile>
+void textPass(const RealOptions &o, const std::vector<std::string> &files, Timers &T, PerFile perFile)
+{
+    double t0 = now_s();
+    CtxVec ctx = makeContexts(o, 1);
+    real_hip_ctx *h = ctx[0]->h;
+    T.index += now_s() - t0; // (the context and the texts: what the matching contexts' index time holds too)
+    for (unsigned fi = 0; fi < files.size(); ++fi) {
+        GenomeText G;
+        t0 = now_s();
+        G.load(files[fi]);
+        T.genome += now_s() - t0;
+        t0 = now_s();
+        check(h, real_hip_set_text_symbols(h, fi, G.sym.data(), G.sym.size(), 0, G.frag_start.data(), (uint32_t)G.frag_names.size()), "real_hip_set_text_symbols");
+        T.index += now_s() - t0;
+        perFile(ctx, fi, G);
+    }
+}
+inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.sam_given; }
+
 template <class AddAll>
-void pileupPass(const RealOptions &o, const std::vector<std::string> &files, AddAll addAll)
+void pileupPass(const RealOptions &o, const std::vector<std::string> &files, Timers &T, AddAll addAll)
 {
     if (!o.pileup_given && !o.pileup_depth_given) return;
     std::unique_ptr<OutFile> sites_out(o.pileup_given ? new OutFile(o.pileupfilename, false, "-pileup") : nullptr);
     std::unique_ptr<OutFile> depth_out(o.pileup_depth_given ? new OutFile(o.pileupdepthfilename, false, "-pileup_depth") : nullptr);
-    CtxVec ctx = makeContexts(o, 1);
-    real_hip_ctx *h = ctx[0]->h;
     real_hip_pileup_params pp;
     pp.struct_size = sizeof pp; pp.min_qual = (uint32_t)o.pileup_minq;
-    for (unsigned fi = 0; fi < files.size(); ++fi) {
-        GenomeText G;
-        G.load(files[fi]);
-        check(h, real_hip_set_text_symbols(h, fi, G.sym.data(), G.sym.size(), 0, G.frag_start.data(), (uint32_t)G.frag_names.size()), "real_hip_set_text_symbols");
+    textPass(o, files, T, [&](CtxVec &ctx, unsigned fi, const GenomeText &G) {
+        real_hip_ctx *h = ctx[0]->h;
         check(h, real_hip_pileup_begin(h, &pp), "real_hip_pileup_begin");
         addAll(ctx);
         uint64_t n_sites = 0;
@@ -560,13 +579,62 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, Add
                 st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
                 (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
         check(h, real_hip_pileup_end(h), "real_hip_pileup_end");
-    }
+    });
     for (OutFile *f : {sites_out.get(), depth_out.get()}) {
         if (!f) continue;
         const bool bad = ferror(f->file()) != 0; // (a line that could not be written)
         f->close();
         if (bad) throw std::runtime_error("write to the -pileup / -pileup_depth file failed");
     }
+}
+
+// ---- -sam: every read as a SAM line, NM / MD from the mismatch lists of the final placements ----------------------------
+// Runs where pileupPass runs, through the same textPass.  The header names the fragments of all genome files (RS).  Per file
+// writeAll(ctx, fi, last, refs, lists, out) streams the reads once more, takes each batch's lists from real_hip_mismatches /
+// _pairs with the final records (SamLists::fill), and writes the lines of the reads placed in this file -- and, in the pass
+// of the last file, of those placed nowhere (Sam.hpp: all about the lines).  A summary line per file goes to standard error.
+struct SamLists {
+    std::vector<real_hip_mismatch> mm = std::vector<real_hip_mismatch>(1024); // (grows by the count the library reports)
+    std::vector<uint64_t> off;
+    uint64_t placed = 0, mismatches = 0, on_n = 0, disagree = 0; // of the calls that listed, summed over a genome file
+    // list(h, in..., mm, room, &n, off): the lists of one batch of n_lists reads.  A call that overflows has counted and written
+    // nothing: its statistics are dropped and the call is repeated with room for what it reported (and an eighth more).
+    template <class List, class... In>
+    void fill(real_hip_ctx *h, const char *what, uint64_t n_lists, List list, In... in)
+    {
+        off.assign(n_lists + 1, 0);
+        uint64_t n = 0;
+        real_hip_mismatch_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        int rc = list(h, in..., mm.data(), mm.size(), &n, off.data());
+        if (rc == REAL_HIP_E_OVERFLOW) {
+            check(h, real_hip_mismatch_stats_get(h, &st, 1), "real_hip_mismatch_stats_get");
+            mm.resize(n + n / 8 + 16);
+            rc = list(h, in..., mm.data(), mm.size(), &n, off.data());
+        }
+        check(h, rc, what);
+        check(h, real_hip_mismatch_stats_get(h, &st, 1), "real_hip_mismatch_stats_get");
+        placed += st.placed; mismatches += st.mismatches; on_n += st.on_n; disagree += st.disagree;
+    }
+};
+
+template <class WriteAll>
+void samPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, WriteAll writeAll)
+{
+    if (!o.sam_given) return;
+    const SamRefs refs(RS.names, RS.starts);
+    OutFile out(o.samfilename, false, "-sam");
+    const std::string head = refs.header();
+    if (fwrite(head.data(), 1, head.size(), out.file()) != head.size()) throw std::runtime_error("write to the -sam file failed");
+    SamLists L;
+    textPass(o, files, T, [&](CtxVec &ctx, unsigned fi, const GenomeText &) {
+        L.placed = L.mismatches = L.on_n = L.disagree = 0;
+        writeAll(ctx, fi, fi + 1 == files.size(), refs, L, out.file());
+        fprintf(stderr, "sam: file=%s placements=%llu mismatches=%llu on_n=%llu disagree=%llu\n", files[fi].c_str(), (unsigned long long)L.placed,
+                (unsigned long long)L.mismatches, (unsigned long long)L.on_n, (unsigned long long)L.disagree);
+    });
+    out.close();
 }
 
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
@@ -632,11 +700,29 @@ int matchUnique(const RealOptions &o)
 #pragma omp parallel for reduction(+ : unique) schedule(static)
     for (uint64_t i = 0; i < numpat; ++i) { const unsigned st = (unsigned)(info[i] >> 61); unique += (st == 1 || st == 2); }
     std::cerr << "unique: " << unique << std::endl; // :1488
-    if (o.pileup_given || o.pileup_depth_given) ctx.clear(); // (the matching contexts go before the pileup's own one comes)
-    pileupPass(o, files, [&](CtxVec &pc) {
+    if (passesBehindOutput(o)) ctx.clear(); // (the matching contexts go before the pass's own one comes)
+    pileupPass(o, files, T, [&](CtxVec &pc) {
         const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items)
                 if (it.batch.n_reads) check(pc[0]->h, real_hip_pileup_add(pc[0]->h, &it.batch, info.data() + it.first_id), "real_hip_pileup_add");
+        });
+        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+    });
+    samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
+        const uint64_t seen = streamReads(o, sc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
+            for (const ReadItem &it : items) {
+                const uint64_t n = it.batch.n_reads, base = it.first_id;
+                if (!n) continue;
+                if (base + n > numpat) throw std::runtime_error("the read file changed between two passes");
+                const double tm = now_s();
+                L.fill(sc[0]->h, "real_hip_mismatches", n, real_hip_mismatches, &it.batch, (const uint64_t *)info.data() + base);
+                T.match += now_s() - tm;
+                const ReadSource src = it.src.withQuality(o.fastq, qoff);
+                formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
+                    appendSamRead(s, src[i], refs, samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f), fi, last, L.mm.data() + L.off[i],
+                                  L.off[i + 1] - L.off[i], o.scores);
+                });
+            }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
@@ -745,13 +831,14 @@ int matchPairs(const RealOptions &o)
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
-    std::vector<real_hip_single> singles1, singles2; // -unpaired: kept across the genome files as pairs is
+    const bool singles = unpaired || o.sam_given; // (-sam places the mates of a fragment without a pair as -unpaired prints them)
+    std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
     // the call of a batch, for the run and for the probe of -insert_auto
     auto matchBatch = [&](const real_hip_batch &rb1, const real_hip_batch &rb2, real_hip_pair *P, real_hip_single *S1, real_hip_single *S2) {
-        if (unpaired) check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2), "real_hip_match_pairs_singles");
+        if (singles) check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2), "real_hip_match_pairs_singles");
         else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, P), "real_hip_match_pairs_search");
         else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, P), "real_hip_match_pairs");
     };
@@ -773,7 +860,7 @@ int matchPairs(const RealOptions &o)
             const uint64_t n = fillMates(o, r1, r2, b1, b2, false, std::min<uint64_t>(o.batch_reads, o.insert_auto - seen));
             if (!n) break;
             probe.resize(n);
-            if (unpaired) { ps1.resize(n); ps2.resize(n); }
+            if (singles) { ps1.resize(n); ps2.resize(n); }
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = 1;
             matchBatch(rb1, rb2, probe.data(), ps1.data(), ps2.data());
@@ -809,11 +896,11 @@ int matchPairs(const RealOptions &o)
             T.read += now_s() - t0;
             if (!n) break;
             if (seen + n > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n, pairs.size() + pairs.size() / 2));
-            if (unpaired && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
+            if (singles && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
             const double tm = now_s();
-            matchBatch(rb1, rb2, pairs.data() + seen, unpaired ? singles1.data() + seen : nullptr, unpaired ? singles2.data() + seen : nullptr);
+            matchBatch(rb1, rb2, pairs.data() + seen, singles ? singles1.data() + seen : nullptr, singles ? singles2.data() + seen : nullptr);
             T.match += now_s() - tm;
             seen += n;
         }
@@ -882,8 +969,8 @@ int matchPairs(const RealOptions &o)
             std::cerr << "insert size: n=" << est.n << " q1=" << est.q1 << " median=" << est.median << " q3=" << est.q3 << std::endl;
         else throw std::runtime_error("real_hip_insert_bounds failed");
     }
-    if (o.pileup_given || o.pileup_depth_given) ctx.clear(); // (the matching context goes before the pileup's own one comes)
-    pileupPass(o, files, [&](CtxVec &pc) {
+    if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
+    pileupPass(o, files, T, [&](CtxVec &pc) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
@@ -892,6 +979,28 @@ int matchPairs(const RealOptions &o)
             if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
             const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             check(pc[0]->h, real_hip_pileup_add_pairs(pc[0]->h, &rb1, &rb2, pairs.data() + seen), "real_hip_pileup_add_pairs");
+            seen += n;
+        }
+        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+    });
+    samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
+        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
+        const ReadSource v1 = m1.withQuality(o.fastq, qoff1), v2 = m2.withQuality(o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            const uint64_t n = fillMates(o, q1, q2, b1, b2, true);
+            if (!n) break;
+            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
+            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            const double tm = now_s();
+            L.fill(sc[0]->h, "real_hip_mismatches_pairs", 2 * n, real_hip_mismatches_pairs, &rb1, &rb2, (const real_hip_pair *)pairs.data() + seen,
+                   (const real_hip_single *)singles1.data() + seen, (const real_hip_single *)singles2.data() + seen);
+            T.match += now_s() - tm;
+            formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
+                const ReadView r[2] = {v1[i], v2[i]};
+                const SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
+                appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
+            });
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "real_hip_pair_insert_hist", "real_hip_insert_bounds", "real_hip_insert_stats_get",
     "real_hip_pileup_begin", "real_hip_pileup_add", "real_hip_pileup_add_pairs", "real_hip_pileup_finish", "real_hip_pileup_depth",
     "real_hip_pileup_sites", "real_hip_pileup_end", "real_hip_pileup_stats_get",
+    "real_hip_mismatches", "real_hip_mismatches_pairs", "real_hip_mismatch_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -147,6 +148,22 @@ PILEUP_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mis
 class RealHipPileupStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
                [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in PILEUP_STATS_FIELDS]
+
+
+class RealHipMismatch(C.Structure):
+    """real_hip_mismatch: one base of a placed read that differs from the text (MISMATCH_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("off", C.c_uint16), ("ref", C.c_uint8), ("base", C.c_uint8)]
+
+
+MISMATCH_DTYPE = np.dtype([("off", "<u2"), ("ref", "u1"), ("base", "u1")])
+assert MISMATCH_DTYPE.itemsize == 4 and C.sizeof(RealHipMismatch) == 4
+
+MISMATCH_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mismatches", "on_n", "disagree", "launches", "kernel_ms")
+
+
+class RealHipMismatchStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in MISMATCH_STATS_FIELDS]
 
 
 class RealHipPairHit(C.Structure):
@@ -270,6 +287,9 @@ def load():
     L.real_hip_pileup_sites.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
     L.real_hip_pileup_end.argtypes = [vp]
     L.real_hip_pileup_stats_get.argtypes = [vp, C.POINTER(RealHipPileupStats), C.c_int]
+    L.real_hip_mismatches.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp, u64, C.POINTER(u64), vp]
+    L.real_hip_mismatches_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp, vp, vp, vp, u64, C.POINTER(u64), vp]
+    L.real_hip_mismatch_stats_get.argtypes = [vp, C.POINTER(RealHipMismatchStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

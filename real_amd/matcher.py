@@ -553,6 +553,73 @@ class HipMatcher:
     def pileup_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipPileupStats, self._L.real_hip_pileup_stats_get, _lib.PILEUP_STATS_FIELDS, reset)
 
+    # -- mismatch lists: where each placed read differs from the resident text (include/real_hip.h, "mismatch lists") --
+    def _mismatch_call(self, call, lists: int, on_device: bool, cap: int):
+        """one list call with its outputs: host numpy arrays, or device tensors when the records are; the buffer grows once to
+        the size the library reports -> (lists as lib.MISMATCH_DTYPE, offsets)"""
+        n = C.c_uint64(0)
+        cap = int(cap)
+
+        def room(c):
+            if not on_device:
+                return np.zeros(c, dtype=_lib.MISMATCH_DTYPE)
+            import torch
+            return torch.zeros(max(c, 1), dtype=torch.int32, device="cuda")
+        if on_device:
+            import torch
+            off = torch.zeros(lists + 1, dtype=torch.int64, device="cuda")
+        else:
+            off = np.zeros(lists + 1, dtype=np.uint64)
+        out = room(cap)
+        self.sync_inputs(out, off)
+        rc = call(_ptr(out), cap, C.byref(n), _ptr(off))
+        if rc == _lib.REAL_HIP_E_OVERFLOW:
+            cap = int(n.value)
+            out = room(cap)
+            self.sync_inputs(out)
+            rc = call(_ptr(out), cap, C.byref(n), _ptr(off))
+        self._check(rc)
+        return out[:int(n.value)], off
+
+    def mismatches(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
+                   packed: bool = False, nflags=None, cap: int = 0):
+        """real_hip_mismatches: the mismatch list of every placement among the records `info` (what match_unique returned for
+        this batch) -> (lists, offsets): lists[offsets[i] : offsets[i + 1]] is read i's.  Host numpy arrays, device torch
+        tensors (the outputs then are device tensors: int32 words of lib.MISMATCH_DTYPE, int64 offsets), or device reads with
+        numpy records (on_device = 2)."""
+        host_info = isinstance(info, np.ndarray)
+        if host_info:
+            info = np.ascontiguousarray(info, dtype=np.uint64)
+        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
+        n = int(b.n_reads)
+        if int(info.shape[0]) != n:
+            raise ValueError("one record per read")
+        self.sync_inputs(info)
+        return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches(self._h, C.byref(b), _ptr(info), o, c, no, po),
+                                   n, not host_info, cap or max(1024, 4 * n))
+
+    def mismatches_pairs(self, mate1, mate2, pairs, singles1=None, singles2=None, cap: int = 0):
+        """real_hip_mismatches_pairs: the lists of both mates' final placements (mate 1 of fragment i is list 2i, mate 2 list
+        2i + 1) from the pair records and, where given, the mates' single records; mates as (bases, qual, offsets) tuples or
+        ReadBatch-like objects, all host arrays or all device tensors"""
+        host_pairs = isinstance(pairs, np.ndarray)
+        if host_pairs:
+            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
+            singles1 = None if singles1 is None else np.ascontiguousarray(singles1, dtype=_lib.SINGLE_DTYPE)
+            singles2 = None if singles2 is None else np.ascontiguousarray(singles2, dtype=_lib.SINGLE_DTYPE)
+        bs = []
+        for mate in (mate1, mate2):
+            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
+            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
+        n = int(bs[0].n_reads)
+        self.sync_inputs(pairs, singles1, singles2)
+        return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches_pairs(
+            self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs), _ptr(singles1), _ptr(singles2), o, c, no, po),
+            2 * n, not host_pairs, cap or max(1024, 8 * n))
+
+    def mismatch_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipMismatchStats, self._L.real_hip_mismatch_stats_get, _lib.MISMATCH_STATS_FIELDS, reset)
+
     # -- instrumentation --
     def counters(self, reset: bool = False) -> dict:
         c = RealHipCounters()
