@@ -600,6 +600,52 @@ typedef struct real_hip_mismatch_stats {
 } real_hip_mismatch_stats;
 int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset);
 
+/* ---- duplicates: which placed reads (fragments) are copies of one another -- PCR / optical duplicates as samtools markdup
+ * and Picard MarkDuplicates mark them.  The reference has no such step; the semantics are this project's own.
+ * Every result is a function of the input arrays alone: nothing depends on lanes, blocks, the sort's internals or the order
+ * of calls.
+ * READ SUMMARY (real_hip_read_summary): len is the read's length, qsum the sum of the read's qualities that are >= min_qual
+ * (a batch without qualities counts 30 per base: 30 * len if min_qual <= 30, else 0).  Every read of the batch gets one, also
+ * the reads the matcher skips.  min_qual <= 63, else REAL_HIP_E_INVALID.  The call needs neither text nor index and does not
+ * read the bases (packed or not: the qualities stay bytes).  Reads up to REAL_HIP_MAX_PATL_LONG: qsum <= 16384 * 63 < 2^20.
+ * out lives where the batch's outputs live: host memory for on_device 0 and 2, device memory for 1.
+ * SINGLE-END (real_hip_mark_duplicates): a read is PLACED iff its info record has state 1 or 2.  Its END5 is pos for state
+ * 1 and pos + len - 1 for state 2 (len from its summary), in 64 bits.  Its KEY is (fileid, state, END5): the fragment is
+ * implied by the text position.  A GROUP is the set of placed reads of one KEY; its REPRESENTATIVE the read with the largest
+ * qsum, among equals the one of the smallest index.  dup[i] = 1 iff read i is placed and is not its group's representative,
+ * else 0.  No validity test is made (the marking needs no text).
+ * PAIRED-END (real_hip_mark_duplicates_pairs): a fragment is PLACED iff its real_hip_pair has state REAL_HIP_PAIR_UNIQUE.  The
+ * forward mate f is mate 1 iff inverted1 == 0, r is the other one; START = f.pos, END = r.pos + len_r - 1 in 64 bits; KEY =
+ * (fileid, inverted1, START, END); the quality of a fragment is qsum1 + qsum2; representative and dup[] as above, one byte
+ * per fragment.  Single records of unpaired mates take no part.
+ * Both: a qsum beyond 2^20 - 1 counts as 2^20 - 1; END5 is taken modulo 2^36 and END modulo 2^33 (summaries of
+ * real_hip_read_summary and records of this library's matchers stay inside).  on_device 0: all pointers host memory
+ * (copied), 1: all device pointers, dup included (pairs 8-byte, summaries 8-byte aligned).  n == 0 is valid.  NULL arrays
+ * with n > 0 or more than 2^32 records: REAL_HIP_E_INVALID with a message, nothing launched; buffers that do not fit (24 bytes
+ * per record single-end, 40 paired-end, beside the sort's own): REAL_HIP_E_NOMEM.                                          */
+typedef struct real_hip_read_sum {
+    uint32_t len;    /* bases                                        */
+    uint32_t qsum;   /* sum of the qualities >= min_qual             */
+} real_hip_read_sum;
+int real_hip_read_summary(real_hip_ctx *ctx, const real_hip_batch *b, uint32_t min_qual, real_hip_read_sum *out);
+int real_hip_mark_duplicates(real_hip_ctx *ctx, const uint64_t *info, const real_hip_read_sum *sum,
+                             uint64_t n_reads, int on_device, uint8_t *dup);
+int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
+                                   const real_hip_read_sum *sum2, uint64_t n_pairs, int on_device, uint8_t *dup);
+/* work of the marking, accumulated since the last reset.  placed, groups and duplicates count the marking calls; launches and
+ * kernel_ms (HIP events on the ctx's stream around the kernels) also those of real_hip_read_summary; a sort counts as one
+ * launch                                                                                                                */
+typedef struct real_hip_dup_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_dup_stats), 0                                */
+    uint64_t reads;         /* records handed in to the marking calls                                 */
+    uint64_t placed;        /* placed reads or fragments                                              */
+    uint64_t groups;
+    uint64_t duplicates;    /* placed - groups                                                        */
+    uint64_t launches;
+    double   kernel_ms;
+} real_hip_dup_stats;
+int real_hip_dup_stats_get(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -1241,6 +1241,95 @@ extern "C" int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_
     return rh_mismatch_stats(ctx, out, reset);
 }
 
+// ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no
+// text); the marking stages records and summaries as real_hip_pair_insert_hist stages its arrays
+extern "C" int real_hip_read_summary(real_hip_ctx *ctx, const real_hip_batch *b, uint32_t min_qual, real_hip_read_sum *out)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = batch_view(ctx, b, bv);
+    if (rc) return rc;
+    if (min_qual > 63) return rh_fail(ctx, REAL_HIP_E_INVALID, "read summary: min_qual beyond 63", hipSuccess);
+    const uint64_t n = bv.n_reads;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "read summary: more than 2^32 reads in one batch", hipSuccess);
+    if (!n) return REAL_HIP_OK;
+    if (!out) return rh_fail(ctx, REAL_HIP_E_INVALID, "read summary: null out", hipSuccess);
+    if (bv.on_device == 1 && ((uintptr_t)out & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "read summary: out must be 8-byte aligned", hipSuccess);
+    DevBatch db;
+    memset(&db, 0, sizeof db);
+    db.n_reads = n; db.upatl = bv.patl;
+    uint64_t total = n * (uint64_t)bv.patl, longest = bv.patl;
+    const RhStaging in{ctx, !bv.on_device, ctx->stream, ctx->stream};
+    if (bv.offsets) {
+        if (!bv.on_device) {
+            longest = 0;
+            for (uint64_t i = 0; i < n; ++i) {
+                if (bv.offsets[i + 1] < bv.offsets[i]) return rh_fail(ctx, REAL_HIP_E_INVALID, "offsets not monotone", hipSuccess);
+                if (bv.offsets[i + 1] - bv.offsets[i] > longest) longest = bv.offsets[i + 1] - bv.offsets[i];
+            }
+            total = bv.offsets[n];
+        }
+        if ((rc = in.in(ctx->stage[0].off, bv.offsets, n + 1, db.off))) return rh_sync_tail(ctx, rc);
+        if (bv.on_device) {
+            uint32_t m = bv.max_patl;
+            if (!m && (rc = rh_max_patl(ctx, db.off, n, &m))) return rh_sync_tail(ctx, rc);
+            longest = m;
+        }
+    }
+    if (longest > REAL_HIP_MAX_PATL_LONG) return rh_sync_tail(ctx, rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "read longer than REAL_HIP_MAX_PATL_LONG", hipSuccess));
+    if (bv.qual && (rc = in.in(ctx->stage[0].qual, bv.qual, total, db.qual, total ? total : 1))) return rh_sync_tail(ctx, rc);
+    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream}; // (host: the output is host memory)
+    real_hip_read_sum *d_out = out;
+    rc = io.inout(ctx->dup_out, out, n, true, d_out);
+    if (!rc) rc = rh_launch_read_summary(ctx, db, min_qual, d_out);
+    if (!rc) rc = io.back(out, d_out, n, "download of the read summaries");
+    return rh_sync_tail(ctx, rc);
+}
+
+static int mark_duplicates_run(real_hip_ctx *ctx, const uint64_t *info, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
+                               const real_hip_read_sum *sum2, uint64_t n, int on_device, uint8_t *dup)
+{
+    if (n > (1ull << 32)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: more than 2^32 records in one call", hipSuccess);
+    if (!n) return REAL_HIP_OK;
+    if ((!info && !pairs) || !sum1 || (pairs && !sum2) || !dup) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null records / summaries / dup", hipSuccess);
+    if (on_device && (((uintptr_t)info | (uintptr_t)pairs | (uintptr_t)sum1 | (uintptr_t)sum2) & 7u))
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: records and summaries must be 8-byte aligned", hipSuccess);
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    const uint64_t *d_info = info;
+    const real_hip_pair *d_pairs = pairs;
+    const real_hip_read_sum *d_sum[2] = {sum1, sum2};
+    uint8_t *d_dup = dup;
+    int rc = info ? io.in(ctx->dup_rec, info, n, d_info) : io.in(ctx->dup_rec, pairs, n, d_pairs);
+    for (int m = 0; m < (pairs ? 2 : 1) && !rc; ++m) rc = io.in(ctx->dup_sum[m], m ? sum2 : sum1, n, d_sum[m]);
+    if (!rc) rc = io.inout(ctx->dup_out, dup, n, true, d_dup);
+    if (!rc) rc = rh_launch_mark_duplicates(ctx, d_info, d_pairs, d_sum[0], d_sum[1], n, d_dup);
+    if (!rc) rc = io.back(dup, d_dup, n, "download of the duplicate marks");
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_mark_duplicates(real_hip_ctx *ctx, const uint64_t *info, const real_hip_read_sum *sum, uint64_t n_reads, int on_device,
+                                        uint8_t *dup)
+{
+    RH_ENTER(ctx);
+    if (n_reads && !info) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null info", hipSuccess);
+    return mark_duplicates_run(ctx, info, nullptr, sum, nullptr, n_reads, on_device, dup);
+}
+
+extern "C" int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
+                                              const real_hip_read_sum *sum2, uint64_t n_pairs, int on_device, uint8_t *dup)
+{
+    RH_ENTER(ctx);
+    if (n_pairs && !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null pairs", hipSuccess);
+    return mark_duplicates_run(ctx, nullptr, pairs, sum1, sum2, n_pairs, on_device, dup);
+}
+
+extern "C" int real_hip_dup_stats_get(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_dup_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicate stats struct_size", hipSuccess);
+    return rh_dup_stats(ctx, out, reset);
+}
+
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
 // hold mate m's unified hit lists, their n + 1 offsets and the read lengths; total[m] is an upper bound of the hits inside
 // the buffer (the matcher's count before duplicates go).  both_resident: mate 2 is staged into buffers of its own, so that

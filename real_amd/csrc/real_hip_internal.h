@@ -305,6 +305,11 @@ struct real_hip_ctx {
     DevBuf mm_cnt, mm_off, mm_out, mm_rec, mm_sg[2];
     RhStage mismatch;
 
+    // duplicate marking (duplicates.hip): the two buffers of the sort's keys and values, the paired key's two words in record
+    // order, and when the caller's arrays are host memory the staged records, summaries and marks
+    DevBuf dup_key[2], dup_val[2], dup_lo, dup_hi, dup_rec, dup_sum[2], dup_out;
+    RhStage dup;
+
     // where the wall time of an index build goes (real_hip_index_build_stats)
     double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
     uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
@@ -460,6 +465,14 @@ struct RhMismatchLaunch {
 int rh_mismatch_count(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, uint64_t *d_off, uint64_t *total);
 int rh_mismatch_emit(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, const uint64_t *d_off, real_hip_mismatch *d_out, uint64_t total);
 int rh_mismatch_stats(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset);
+
+// ---- duplicate marking (duplicates.hip) ---------------------------------------------------
+// {len, qsum} of every read of b (qual, off, upatl, n_reads; the bases are not read), all arrays on the device; asynchronous
+int rh_launch_read_summary(real_hip_ctx *ctx, const DevBatch &b, uint32_t min_qual, real_hip_read_sum *d_out);
+// dup[] of n records, all arrays on the device: d_info and d_sum1 (single-end) or d_pairs, d_sum1 and d_sum2; asynchronous
+int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_pair *d_pairs, const real_hip_read_sum *d_sum1,
+                              const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup);
+int rh_dup_stats(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset);
 
 // ---- text + index (index_build.hip) ------------------------------------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);

@@ -74,6 +74,12 @@ void RealOptions::printHelp() const
               << "   Unique pairs only).  Order: per genome file the reads placed in it, in read order, an unplaced mate beside its placed\n"
               << "   mate; reads and fragments with nothing placed in the pass of the last file; two mates placed in different files\n"
               << "   appear each in its own file's pass (@HD SO:unknown).  -o is unchanged; needs -u 1, not with -pairs_all 1>\n"
+              << "-dedup <0|1: mark duplicates: the placed reads with one 5' end (file, strand, position of the first sequenced base), with\n"
+              << "   -p2 the Unique fragments with one pair of 5' ends, are copies of one another; the copy with the largest sum of base\n"
+              << "   qualities stays (ties: the first in the read file), the others are marked on the first device after the matching: their\n"
+              << "   -sam lines carry FLAG 1024 (both mates of a fragment), -pileup / -pileup_depth leave them out; -o and -unpaired are\n"
+              << "   unchanged; a summary line goes to standard error; needs -u 1, not with -pairs_all 1, default=0>\n"
+              << "-dedup_minq <n: with -dedup 1, a base quality below n does not count in the sum, 0..63, default=15>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -142,6 +148,8 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pileup_depth") { pileupdepthfilename = need("-pileup_depth"); pileup_depth_given = true; i += 2; }
         else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
         else if (a == "-sam") { samfilename = need("-sam"); sam_given = true; i += 2; }
+        else if (a == "-dedup") { dedup = atoi(need("-dedup").c_str()) != 0; dedup_given = true; i += 2; }
+        else if (a == "-dedup_minq") { dedup_minq = strtol(need("-dedup_minq").c_str(), 0, 10); dedup_minq_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -229,6 +237,12 @@ RealOptions::RealOptions(int argc, char *argv[])
         if ((pileup_given && samfilename == pileupfilename) || (pileup_depth_given && samfilename == pileupdepthfilename))
             throw std::runtime_error("-sam must name a file of its own: it names the same file as -pileup / -pileup_depth.");
     }
+    if (dedup) { // duplicate marking: loud errors before anything runs
+        if (!match_unique) throw std::runtime_error("-dedup marks copies of the unique placement of a read: it cannot be combined with -u 0.");
+        if (pairs_all) throw std::runtime_error("-dedup marks copies of the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
+    }
+    if (dedup_minq_given && !dedup) throw std::runtime_error("-dedup_minq needs -dedup 1.");
+    if (dedup_minq < 0 || dedup_minq > 63) throw std::runtime_error("-dedup_minq must be in 0..63.");
     if (pileup_minq_given && !pileup_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
     if (pileup_minq > 63) throw std::runtime_error("-pileup_minq takes a quality of at most 63.");
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences

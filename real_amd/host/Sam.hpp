@@ -45,6 +45,7 @@ struct SamRefs {
 // where a read finally lies, from the record that places it
 struct SamPlace {
     bool placed = false, inverted = false, paired = false; // paired: the placement is a Unique pair record's
+    bool duplicate = false; // -dedup marked the read (the fragment): FLAG 1024
     unsigned file = 0, frag = 0;
     uint64_t pos = 0; // 0-based in the file's text
     float score = 0.f;
@@ -99,6 +100,7 @@ inline void appendSam(std::string &out, const ReadView &r, const SamRefs &R, con
     if (mate && ql >= 2 && r.id[ql - 2] == '/' && (r.id[ql - 1] == '1' || r.id[ql - 1] == '2')) ql -= 2;
     out.append(r.id, ql);
     unsigned flag = self.placed ? (self.inverted ? 16u : 0u) : 4u;
+    if (self.duplicate) flag |= 1024u;
     if (mate) flag |= 1u | which | (self.paired ? 2u : 0u) | (mate->placed ? (mate->inverted ? 32u : 0u) : 8u);
     out.push_back('\t'); samPutInt(out, flag); out.push_back('\t');
     // RNAME POS MAPQ CIGAR: an unplaced mate of a placed one sits where its mate does

@@ -637,6 +637,30 @@ void samPass(const RealOptions &o, const std::vector<std::string> &files, const 
     out.close();
 }
 
+// ---- -dedup: the copies of a placed read / fragment marked (real_hip_mark_duplicates*) -------------------------
+// The summaries are taken with the first pass over the reads and kept beside the records; behind "All done." one call marks
+// all records on the first context (duplicates in different batches, host blocks and parser chunks meet), and the summary line
+// goes to standard error.  The pileup then gets, per batch, a scratch copy of the records with the duplicates set to NoMatch.
+void reportDuplicates(real_hip_ctx *h, const RealOptions &o)
+{
+    real_hip_dup_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    check(h, real_hip_dup_stats_get(h, &st, 1), "real_hip_dup_stats_get");
+    fprintf(stderr, "duplicates: placed=%llu groups=%llu duplicates=%llu rate=%.4f min_qual=%ld\n", (unsigned long long)st.placed, (unsigned long long)st.groups,
+            (unsigned long long)st.duplicates, st.placed ? (double)st.duplicates / (double)st.placed : 0.0, o.dedup_minq);
+}
+// records[first .. first + n) with the duplicates masked, in `scratch`; the records themselves where nothing is marked
+template <class Rec, class Mask>
+const Rec *withoutDuplicates(const std::vector<Rec> &records, const std::vector<uint8_t> &dup, uint64_t first, uint64_t n, std::vector<Rec> &scratch, Mask mask)
+{
+    if (dup.empty()) return records.data() + first;
+    scratch.assign(records.begin() + (ptrdiff_t)first, records.begin() + (ptrdiff_t)(first + n));
+    for (uint64_t i = 0; i < n; ++i)
+        if (dup[first + i]) mask(scratch[i]);
+    return scratch.data();
+}
+
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
 int matchUnique(const RealOptions &o)
 {
@@ -646,12 +670,15 @@ int matchUnique(const RealOptions &o)
     // first pass over the file (records start as NoMatch / -FLT_MAX, UniqueMatchInfo.hpp:191).
     std::vector<uint64_t> info;
     std::vector<float> score;
+    std::vector<real_hip_read_sum> sums; // -dedup: kept for the run beside info
+    std::vector<uint8_t> dup;            // -dedup: one mark per read, from behind "All done." on
     uint64_t numpat = 0;
     bool counted = false;
     auto grow = [&](uint64_t n) {
         if (n > info.size()) {
             const uint64_t to = std::max<uint64_t>(n, info.size() + info.size() / 2);
             info.resize(to, 0);
+            if (o.dedup) sums.resize(to);
             if (o.scores) score.resize(to, -FLT_MAX);
         }
     };
@@ -669,6 +696,8 @@ int matchUnique(const RealOptions &o)
                 if (rb.n_reads)
                     check(ctx[g]->h, real_hip_match_unique(ctx[g]->h, &rb, info.data() + items[g].first_id, o.scores ? score.data() + items[g].first_id : nullptr),
                           "real_hip_match_unique");
+                if (o.dedup && !counted && rb.n_reads) // (the first pass over the reads: no pass of its own)
+                    check(ctx[g]->h, real_hip_read_summary(ctx[g]->h, &rb, (uint32_t)o.dedup_minq, sums.data() + items[g].first_id), "real_hip_read_summary");
             });
             T.match += now_s() - tm;
             if (counted) std::cerr << "\r                                                              \r" << (double)end / (numpat ? numpat : 1) << std::flush;
@@ -678,6 +707,13 @@ int matchUnique(const RealOptions &o)
         std::cerr << std::endl;
     });
     std::cerr << "All done." << std::endl;
+    if (o.dedup) {
+        dup.assign(numpat, 0);
+        const double tm = now_s();
+        check(ctx[0]->h, real_hip_mark_duplicates(ctx[0]->h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
+        T.match += now_s() - tm;
+        reportDuplicates(ctx[0]->h, o);
+    }
     // output, in read order (PatternIdReader re-stream, :1438-1486)
     OutFile out(o.outputfilename);
     uint64_t unique = 0;
@@ -701,10 +737,15 @@ int matchUnique(const RealOptions &o)
     for (uint64_t i = 0; i < numpat; ++i) { const unsigned st = (unsigned)(info[i] >> 61); unique += (st == 1 || st == 2); }
     std::cerr << "unique: " << unique << std::endl; // :1488
     if (passesBehindOutput(o)) ctx.clear(); // (the matching contexts go before the pass's own one comes)
+    std::vector<uint64_t> kept; // -dedup: a batch's records without the duplicates
     pileupPass(o, files, T, [&](CtxVec &pc) {
         const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
-            for (const ReadItem &it : items)
-                if (it.batch.n_reads) check(pc[0]->h, real_hip_pileup_add(pc[0]->h, &it.batch, info.data() + it.first_id), "real_hip_pileup_add");
+            for (const ReadItem &it : items) {
+                if (!it.batch.n_reads) continue;
+                if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
+                check(pc[0]->h, real_hip_pileup_add(pc[0]->h, &it.batch, withoutDuplicates(info, dup, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
+                      "real_hip_pileup_add");
+            }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
@@ -719,8 +760,9 @@ int matchUnique(const RealOptions &o)
                 T.match += now_s() - tm;
                 const ReadSource src = it.src.withQuality(o.fastq, qoff);
                 formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
-                    appendSamRead(s, src[i], refs, samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f), fi, last, L.mm.data() + L.off[i],
-                                  L.off[i + 1] - L.off[i], o.scores);
+                    SamPlace at = samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f);
+                    at.duplicate = o.dedup && dup[base + i];
+                    appendSamRead(s, src[i], refs, at, fi, last, L.mm.data() + L.off[i], L.off[i + 1] - L.off[i], o.scores);
                 });
             }
         });
@@ -833,6 +875,8 @@ int matchPairs(const RealOptions &o)
     const bool unpaired = !o.unpairedfilename.empty();
     const bool singles = unpaired || o.sam_given; // (-sam places the mates of a fragment without a pair as -unpaired prints them)
     std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
+    std::vector<real_hip_read_sum> sums1, sums2;     // -dedup: the mates' summaries, kept for the run beside pairs
+    std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
@@ -897,10 +941,15 @@ int matchPairs(const RealOptions &o)
             if (!n) break;
             if (seen + n > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n, pairs.size() + pairs.size() / 2));
             if (singles && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
+            if (o.dedup && pairs.size() > sums1.size()) { sums1.resize(pairs.size()); sums2.resize(pairs.size()); }
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
             const double tm = now_s();
             matchBatch(rb1, rb2, pairs.data() + seen, singles ? singles1.data() + seen : nullptr, singles ? singles2.data() + seen : nullptr);
+            if (o.dedup && fi == 0) { // (the first pass over the reads: no pass of its own)
+                check(h, real_hip_read_summary(h, &rb1, (uint32_t)o.dedup_minq, sums1.data() + seen), "real_hip_read_summary");
+                check(h, real_hip_read_summary(h, &rb2, (uint32_t)o.dedup_minq, sums2.data() + seen), "real_hip_read_summary");
+            }
             T.match += now_s() - tm;
             seen += n;
         }
@@ -908,6 +957,13 @@ int matchPairs(const RealOptions &o)
         else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
     });
     std::cerr << "All done." << std::endl;
+    if (o.dedup) {
+        dup.assign(numpat, 0);
+        const double tm = now_s();
+        check(h, real_hip_mark_duplicates_pairs(h, pairs.data(), sums1.data(), sums2.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_pairs");
+        T.match += now_s() - tm;
+        reportDuplicates(h, o);
+    }
     OutFile out(o.outputfilename);
     std::unique_ptr<OutFile> uout(unpaired ? new OutFile(o.unpairedfilename, true) : nullptr);
     uint64_t unique = 0, base = 0;
@@ -970,6 +1026,7 @@ int matchPairs(const RealOptions &o)
         else throw std::runtime_error("real_hip_insert_bounds failed");
     }
     if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
+    std::vector<real_hip_pair> kept; // -dedup: a batch's records without the duplicates
     pileupPass(o, files, T, [&](CtxVec &pc) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
@@ -978,7 +1035,8 @@ int matchPairs(const RealOptions &o)
             if (!n) break;
             if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
             const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
-            check(pc[0]->h, real_hip_pileup_add_pairs(pc[0]->h, &rb1, &rb2, pairs.data() + seen), "real_hip_pileup_add_pairs");
+            check(pc[0]->h, real_hip_pileup_add_pairs(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, dup, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
+                  "real_hip_pileup_add_pairs");
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
@@ -998,7 +1056,8 @@ int matchPairs(const RealOptions &o)
             T.match += now_s() - tm;
             formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
                 const ReadView r[2] = {v1[i], v2[i]};
-                const SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
+                SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
+                at[0].duplicate = at[1].duplicate = o.dedup && dup[seen + i]; // (a duplicate fragment is Unique: both mates have lines)
                 appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
             });
             seen += n;

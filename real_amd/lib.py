@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "real_hip_pileup_begin", "real_hip_pileup_add", "real_hip_pileup_add_pairs", "real_hip_pileup_finish", "real_hip_pileup_depth",
     "real_hip_pileup_sites", "real_hip_pileup_end", "real_hip_pileup_stats_get",
     "real_hip_mismatches", "real_hip_mismatches_pairs", "real_hip_mismatch_stats_get",
+    "real_hip_read_summary", "real_hip_mark_duplicates", "real_hip_mark_duplicates_pairs", "real_hip_dup_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -164,6 +165,22 @@ MISMATCH_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "m
 class RealHipMismatchStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
                [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in MISMATCH_STATS_FIELDS]
+
+
+class RealHipReadSum(C.Structure):
+    """real_hip_read_sum: a read's length and the sum of its qualities >= min_qual (READ_SUM_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("len", C.c_uint32), ("qsum", C.c_uint32)]
+
+
+READ_SUM_DTYPE = np.dtype([("len", "<u4"), ("qsum", "<u4")])
+assert READ_SUM_DTYPE.itemsize == 8 and C.sizeof(RealHipReadSum) == 8
+
+DUP_STATS_FIELDS = ("reads", "placed", "groups", "duplicates", "launches", "kernel_ms")
+
+
+class RealHipDupStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in DUP_STATS_FIELDS]
 
 
 class RealHipPairHit(C.Structure):
@@ -290,6 +307,10 @@ def load():
     L.real_hip_mismatches.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp, u64, C.POINTER(u64), vp]
     L.real_hip_mismatches_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp, vp, vp, vp, u64, C.POINTER(u64), vp]
     L.real_hip_mismatch_stats_get.argtypes = [vp, C.POINTER(RealHipMismatchStats), C.c_int]
+    L.real_hip_read_summary.argtypes = [vp, C.POINTER(RealHipBatch), u32, vp]
+    L.real_hip_mark_duplicates.argtypes = [vp, vp, vp, u64, C.c_int, vp]
+    L.real_hip_mark_duplicates_pairs.argtypes = [vp, vp, vp, vp, u64, C.c_int, vp]
+    L.real_hip_dup_stats_get.argtypes = [vp, C.POINTER(RealHipDupStats), C.c_int]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
     L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
     L.real_hip_timing_enable.argtypes = [vp, C.c_int]

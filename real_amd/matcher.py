@@ -620,6 +620,57 @@ class HipMatcher:
     def mismatch_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipMismatchStats, self._L.real_hip_mismatch_stats_get, _lib.MISMATCH_STATS_FIELDS, reset)
 
+    # -- duplicate marking: read summaries, then the marks of the placed reads / fragments (include/real_hip.h, "duplicates") --
+    def read_summary(self, bases, qual, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
+                     packed: bool = False, nflags=None, min_qual: int = 15, out=None):
+        """real_hip_read_summary: {len, qsum} of every read as lib.READ_SUM_DTYPE.  Host numpy arrays give a numpy array;
+        device torch tensors give a device tensor of n x 2 int32 words (len, qsum), or -- out: a numpy array -- host records
+        from device reads (on_device = 2)."""
+        on_device = bool(getattr(bases, "is_cuda", False))
+        host_out = not on_device or isinstance(out, np.ndarray)
+        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_out)
+        n = int(b.n_reads)
+        if out is None:
+            if host_out:
+                out = np.zeros(n, dtype=_lib.READ_SUM_DTYPE)
+            else:
+                import torch
+                out = torch.zeros((n, 2), dtype=torch.int32, device=bases.device)
+        self.sync_inputs(out)
+        self._check(self._L.real_hip_read_summary(self._h, C.byref(b), int(min_qual), _ptr(out)))
+        return out
+
+    def _mark_call(self, entry, records, sums, dtype):
+        """one marking call: numpy records and summaries give numpy marks (on_device 0), device tensors a device uint8 tensor"""
+        host = isinstance(records, np.ndarray)
+        if host:
+            records = np.ascontiguousarray(records, dtype=dtype)
+            sums = [np.ascontiguousarray(s, dtype=_lib.READ_SUM_DTYPE) for s in sums]
+            n = int(records.shape[0])
+            dup = np.zeros(n, dtype=np.uint8)
+        else:
+            import torch
+            n = int(records.shape[0])
+            dup = torch.zeros(n, dtype=torch.uint8, device=records.device)
+        if any(int(s.shape[0]) != n for s in sums):
+            raise ValueError("one summary per record")
+        self.sync_inputs(records, *sums, dup)
+        self._check(entry(self._h, _ptr(records), *[_ptr(s) for s in sums], n, int(not host), _ptr(dup)))
+        return dup
+
+    def mark_duplicates(self, info, sums):
+        """real_hip_mark_duplicates: dup[i] = 1 iff read i is placed and not its group's representative.  info: the records
+        of match_unique (numpy uint64, or a device tensor of n 64-bit words), sums: what read_summary returned for them"""
+        return self._mark_call(self._L.real_hip_mark_duplicates, info, [sums], np.uint64)
+
+    def mark_duplicates_pairs(self, pairs, sums1, sums2):
+        """real_hip_mark_duplicates_pairs: one byte per fragment; pairs as lib.PAIR_DTYPE (or a device tensor holding the
+        records, first dimension n), sums1 / sums2 the two mates' summaries"""
+        return self._mark_call(self._L.real_hip_mark_duplicates_pairs, pairs, [sums1, sums2], _lib.PAIR_DTYPE)
+
+    def dup_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipDupStats, self._L.real_hip_dup_stats_get, _lib.DUP_STATS_FIELDS, reset)
+
     # -- instrumentation --
     def counters(self, reset: bool = False) -> dict:
         c = RealHipCounters()
