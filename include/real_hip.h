@@ -546,6 +546,84 @@ typedef struct real_hip_pileup_stats {
 } real_hip_pileup_stats;
 int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
 
+/* ---- variant calls: which sites of a finished pileup are single-base variants, and with which genotype.  The reference has
+ * no caller; the semantics are this project's own.  PLACEMENT, ORIENTED base, the resident text, the state,
+ * file-id and validity skips, and "a batch without qualities counts 30" are the pileup's, word for word.  The calls sit on
+ * a FINISHED pileup: its sites (ascending position; slot s = index in the site list) and its min_qual.
+ * EVIDENCE, per site s at text position x: for every placement covering x take its oriented base b there with quality q; if
+ * q >= min_qual, cnt[s][b] += 1 and qsum[s][b] += q (b == ref included), otherwise low_qual += 1.  All counters are u32:
+ * more than 2^26 placements on one position are out of scope (qsum and QUAL would wrap).  The text's N bit is clear at
+ * every site by construction, so for b != ref cnt[s][b] == site.alt[b] when the same records were added to both.
+ * GENOTYPE, per site, in integers in phred units: E[b] = qsum[b] + REAL_HIP_CALL_ERR * cnt[b] (an error towards one given
+ * base, e/3).  Genotypes (a, b), a <= b, over the bases 0..3:
+ *   PL(a,a) = sum over d != a of E[d]
+ *   PL(a,b) = REAL_HIP_CALL_HET * (cnt[a] + cnt[b]) + sum over d not in {a, b} of E[d]
+ * plus a prior on every genotype but (ref, ref): REAL_HIP_CALL_PRIOR_HET for a heterozygote holding ref,
+ * REAL_HIP_CALL_PRIOR_HOM for a homozygote of another base, REAL_HIP_CALL_PRIOR_HET2 for a heterozygote of two other bases.
+ * The ten genotypes are ordered (ref, ref) first, then the other nine by ascending (a, b); the best is the first of minimal
+ * PL.  QUAL = PL(ref,ref) - PL(best) (as u32; beyond 2^32 - 1 it counts as that), GQ = min(99, smallest other PL -
+ * PL(best)), DP = cnt[0] + .. + cnt[3].  A CALL is a site with best != (ref, ref), QUAL >= min_call_qual and DP >=
+ * min_depth; the call list is in ascending position.  Everything is an integer sum or a function of one: nothing depends
+ * on the order of reads, lanes, batches or calls.
+ * Device memory beside what the pileup holds until its end: one bit per text position, a u32 per 64 positions and 32 bytes
+ * per site (n/8 + n/16 + 32 * sites bytes); begin fails with REAL_HIP_E_NOMEM and a message when that does not fit.
+ * Protocol: call_begin (needs a finished pileup of the resident text; a second begin starts again), any number of call_add /
+ * call_add_pairs, call_finish (synchronises; may be called again with other thresholds, it only re-reads the evidence),
+ * call_evidence / call_variants any number of times after a finish, call_end.  real_hip_pileup_end and a new
+ * real_hip_pileup_begin end the calls as well.  Calls out of turn, a text replaced by one of another n_bases or file id and
+ * more than 2^32 reads in one call are REAL_HIP_E_INVALID with a message, nothing launched.  A pileup with zero sites is
+ * valid: zero calls.  Records and batches live where the pileup's live for the batch's on_device.                      */
+#define REAL_HIP_CALL_HET        3u  /* phred cost of a read of either allele under a heterozygote: -10 log10(1/2)      */
+#define REAL_HIP_CALL_ERR        5u  /* added to a base's quality: an error towards one given base of three (e/3)       */
+#define REAL_HIP_CALL_PRIOR_HET  30u /* heterozygote holding the reference base                                         */
+#define REAL_HIP_CALL_PRIOR_HOM  33u /* homozygote of another base                                                      */
+#define REAL_HIP_CALL_PRIOR_HET2 60u /* heterozygote of two other bases                                                 */
+typedef struct real_hip_call_params {
+    uint32_t struct_size;   /* = sizeof(real_hip_call_params)                                         */
+    uint32_t min_call_qual; /* a call needs QUAL >= this                                              */
+    uint32_t min_depth;     /* and DP >= this                                                         */
+} real_hip_call_params;
+typedef struct real_hip_call_evidence_rec {   /* 32 bytes; record s belongs to site s of the pileup */
+    uint32_t cnt[4];        /* bases of quality >= min_qual seen at the site, the reference base too  */
+    uint32_t qsum[4];       /* the sums of their qualities                                            */
+} real_hip_call_evidence_rec;
+typedef struct real_hip_call {   /* 32 bytes */
+    uint32_t pos;           /* 0-based position in the text                                           */
+    uint32_t depth;         /* the site's depth (no quality filter)                                   */
+    uint32_t cnt[4];        /* the evidence's counts: DP is their sum                                 */
+    uint32_t qual;          /* QUAL                                                                   */
+    uint8_t  ref, a1, a2;   /* the text's base; the genotype (a1 <= a2)                               */
+    uint8_t  gq;            /* GQ                                                                     */
+} real_hip_call;
+int real_hip_call_begin(real_hip_ctx *ctx);
+int real_hip_call_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info);
+/* batch1 and batch2 must agree in n_reads and on_device                                              */
+int real_hip_call_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs);
+int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_params *p, uint64_t *n_calls);
+/* the evidence table (one record per site of the pileup) / the call list into out (cap records; host memory, or device
+ * memory if on_device); *n_out (host memory) always receives the number of records; when that exceeds cap the call returns
+ * REAL_HIP_E_OVERFLOW and writes nothing to out; after finish                                                          */
+int real_hip_call_evidence(real_hip_ctx *ctx, real_hip_call_evidence_rec *out, uint64_t cap, uint64_t *n_out, int on_device);
+int real_hip_call_variants(real_hip_ctx *ctx, real_hip_call *out, uint64_t cap, uint64_t *n_out, int on_device);
+int real_hip_call_end(real_hip_ctx *ctx);
+/* work of the calls.  reads .. low_qual, launches and kernel_ms are accumulated since the last reset; calls, het and hom
+ * are those of the last finish (0 from begin until then)                                                               */
+typedef struct real_hip_call_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_call_stats), 0                               */
+    uint64_t reads;         /* reads handed in (a pair counts two)                                    */
+    uint64_t placed;        /* placements walked                                                      */
+    uint64_t other_file;    /* placed reads of another file id                                        */
+    uint64_t invalid;       /* placements that end behind the text                                    */
+    uint64_t site_bases;    /* increments of cnt                                                      */
+    uint64_t low_qual;      /* bases over a site that min_qual dropped                                */
+    uint64_t calls;
+    uint64_t het;           /* calls with a1 != a2                                                    */
+    uint64_t hom;
+    uint64_t launches;      /* kernels launched (the scan of finish counts one)                       */
+    double   kernel_ms;     /* HIP events on the ctx's stream around the kernels of begin, add, finish */
+} real_hip_call_stats;
+int real_hip_call_stats_get(real_hip_ctx *ctx, real_hip_call_stats *out, int reset);
+
 /* ---- mismatch lists: where each finally placed read differs from the resident text -- what NM / MD of a SAM line are
  * written from.  The reference has no such output; the semantics are this project's own.  PLACEMENT, ORIENTED
  * base, the resident text (n bases, file id f) are the pileup's, word for word.

@@ -47,33 +47,13 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_add_kernel(const PileupArg
     const uint64_t i = (uint64_t)blockIdx.x * RH_PU_BLOCK + threadIdx.x;
     uint32_t placed = 0, other = 0, invalid = 0, bases = 0, mism = 0, lowq = 0, ndrop = 0;
     if (i < A.b.n_reads) {
-        // the record: is it a placement in this file, where, on which strand
-        bool place, inv;
-        uint32_t file, p;
-        if (PAIRS) {
-            const uint2 pos = A.pairs[i * 5 + 2], tail = A.pairs[i * 5 + 4];
-            place = ((tail.y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE;
-            inv = (((tail.y >> 8) & 0xffu) != 0) != (A.mate != 0); // mate 2 has the other strand
-            file = (tail.x >> 16) & 0xffu;
-            p = A.mate ? pos.y : pos.x;
-        } else {
-            const uint64_t r = A.info[i];
-            const uint32_t st = (uint32_t)(r >> ST_SHIFT);
-            place = st == ST_STRAIGHT || st == ST_REVERSE;
-            inv = st == ST_REVERSE;
-            file = (uint32_t)(r >> FI_SHIFT) & 63u;
-            const uint64_t p64 = r & POS_MASK;
-            p = (uint32_t)p64;
-            if (place && file == A.t.fileid && p64 > 0xffffffffull) { place = false; ++invalid; } // (35 bits of position, 32 of text)
-        }
-        if (place && file != A.t.fileid) { place = false; ++other; }
-        uint64_t start = 0;
-        uint32_t L = 0;
-        if (place) {
-            L = read_extent(A.b, i, start);
-            if ((uint64_t)p + L > A.t.n) { place = false; ++invalid; }
-        }
-        if (place) {
+        // the record: is it a placement in this file, where, on which strand (read_walk.h)
+        const PlacedRead r = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, A.mate, i);
+        other = r.other; invalid = r.bad;
+        const bool inv = r.inv;
+        const uint32_t p = r.p, L = r.L;
+        const uint64_t start = r.start;
+        if (r.place) {
             placed = 1; bases = L;
             atomicAdd(A.diff + p, 1u);
             atomicAdd(A.diff + (uint64_t)p + L, 0xffffffffu);
@@ -172,6 +152,7 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupF
 // ---- host side --------------------------------------------------------------------------------------------------
 static void pileup_release(real_hip_ctx *ctx)
 {
+    rh_call_release(ctx); // (the calls stand on this pileup's sites: they go with it)
     rh_release(ctx, ctx->pu_diff); rh_release(ctx, ctx->pu_alt); rh_release(ctx, ctx->pu_blk); rh_release(ctx, ctx->pu_sites);
     ctx->pu_state = 0; ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
 }

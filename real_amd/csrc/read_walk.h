@@ -37,15 +37,21 @@ struct ReadWalk {
         text = T; wi = p >> 5; sh = 2u * (p & 31u);
         t0 = L ? T[wi] : 0;
     }
-    __device__ __forceinline__ uint64_t step(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb, uint64_t &al,
-                                             uint64_t &o)
+    // word j of the oriented read alone (step's `o` and `nb`): what a caller takes that needs no text (snp_call.hip)
+    static __device__ __forceinline__ uint64_t oriented(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb)
     {
         nb = min(32u, L - 32u * j);
         const uint64_t s = start + (inv ? L - 32u * j - nb : 32u * j);
-        uint64_t w;
+        uint64_t w, o;
         if (b.packed) pack_read_packed<1>(DwordRow{b.bases + (s >> 2)}, nb, (uint32_t)(s & 3u), &w);
         else (void)pack_read<1>(DwordRow{b.bases + s}, nb, &w);
         if (inv) revcomp_words<1>(&w, &o, nb); else o = w;
+        return o;
+    }
+    __device__ __forceinline__ uint64_t step(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb, uint64_t &al,
+                                             uint64_t &o)
+    {
+        o = oriented(b, start, L, inv, j, nb);
         const uint64_t t1 = text[wi + j + 1]; // (the text is padded behind its end)
         al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
         t0 = t1;
@@ -64,4 +70,46 @@ static __device__ __forceinline__ uint32_t read_extent(const DevBatch &b, uint64
     start = b.off[i];
     const uint64_t e = b.off[i + 1];
     return e >= start && e - start <= REAL_HIP_MAX_PATL_LONG ? (uint32_t)(e - start) : 0xffffffffu;
+}
+
+// Record i of a launch as a placement on the text t: single-end records `info`, or mate `mate` (0 = mate 1, 1 = mate 2) of the
+// real_hip_pair records `pairs`, read as five 8-byte words (insert_hist.hip).  A record of another state places nothing; then
+// one of another file id is flagged `other`; then one that ends behind the text (or holds more than 32 bits of position)
+// `bad`.  What pileup.hip and snp_call.hip share: the same records are skipped and counted in both.
+struct PlacedRead {
+    bool place, inv;   // a placement; on the reverse strand
+    bool other, bad;   // no placement: a record of another file; one that ends behind the text
+    uint32_t p, L;     // text position, length
+    uint64_t start;    // first base in the batch
+};
+template <bool PAIRS>
+static __device__ __forceinline__ PlacedRead placed_read(const DevText &t, const DevBatch &b, const uint64_t *info, const uint2 *pairs, uint32_t mate,
+                                                         uint64_t i)
+{
+    PlacedRead r;
+    uint32_t file;
+    r.other = r.bad = false;
+    if (PAIRS) {
+        const uint2 pos = pairs[i * 5 + 2], tail = pairs[i * 5 + 4];
+        r.place = ((tail.y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE;
+        r.inv = (((tail.y >> 8) & 0xffu) != 0) != (mate != 0); // mate 2 has the other strand
+        file = (tail.x >> 16) & 0xffu;
+        r.p = mate ? pos.y : pos.x;
+    } else {
+        const uint64_t rec = info[i];
+        const uint32_t st = (uint32_t)(rec >> ST_SHIFT);
+        r.place = st == ST_STRAIGHT || st == ST_REVERSE;
+        r.inv = st == ST_REVERSE;
+        file = (uint32_t)(rec >> FI_SHIFT) & 63u;
+        const uint64_t p64 = rec & POS_MASK;
+        r.p = (uint32_t)p64;
+        if (r.place && file == t.fileid && p64 > 0xffffffffull) { r.place = false; r.bad = true; } // (35 bits of position, 32 of text)
+    }
+    if (r.place && file != t.fileid) { r.place = false; r.other = true; }
+    r.start = 0; r.L = 0;
+    if (r.place) {
+        r.L = read_extent(b, i, r.start);
+        if ((uint64_t)r.p + r.L > t.n) { r.place = false; r.bad = true; }
+    }
+    return r;
 }

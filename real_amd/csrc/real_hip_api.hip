@@ -1051,54 +1051,78 @@ extern "C" int real_hip_pileup_begin(real_hip_ctx *ctx, const real_hip_pileup_pa
     return rh_pileup_begin(ctx, p->min_qual);
 }
 
-extern "C" int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
+// what real_hip_pileup_add* and real_hip_call_add* share: both hand the placements of a batch to a kernel of their own
+struct PlacementSink {
+    const char *name;                    // the prefix of its messages
+    int (*check)(real_hip_ctx *);        // may an add come now
+    DevBuf real_hip_ctx::*rec;           // the staged records when the caller's are host memory
+    int (*launch)(real_hip_ctx *, const DevBatch &, const uint64_t *, const real_hip_pair *, uint32_t);
+};
+static int sink_invalid(real_hip_ctx *ctx, const PlacementSink &k, const char *what)
 {
-    RH_ENTER(ctx);
+    return rh_fail(ctx, REAL_HIP_E_INVALID, (std::string(k.name) + ": " + what).c_str(), hipSuccess);
+}
+
+static int placements_add(real_hip_ctx *ctx, const PlacementSink &k, const real_hip_batch *b, const uint64_t *info)
+{
     real_hip_batch bv;
     int rc = batch_view(ctx, b, bv);
-    if (rc || (rc = pileup_add_check(ctx))) return rc;
+    if (rc || (rc = k.check(ctx))) return rc;
     const uint64_t n = bv.n_reads;
-    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: more than 2^32 reads in one call", hipSuccess);
+    if (n > 0xffffffffull) return sink_invalid(ctx, k, "more than 2^32 reads in one call");
     if (!n) return REAL_HIP_OK;
-    if (!info) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null info", hipSuccess);
+    if (!info) return sink_invalid(ctx, k, "null info");
     Staged s;
     if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
     const uint64_t *d_info = info;
-    rc = io.in(ctx->pu_rec, info, n, d_info);
+    rc = io.in(ctx->*k.rec, info, n, d_info);
     if (!rc) {
         DevBatch db = dev_batch(ctx, s, n);
         db.qual = s.qual; // (the pileup's use of the qualities does not hang on -q)
-        rc = rh_launch_pileup_add(ctx, db, d_info, nullptr, 0);
+        rc = k.launch(ctx, db, d_info, nullptr, 0);
     }
     return rh_sync_tail(ctx, rc);
 }
 
-extern "C" int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
+static int placements_add_pairs(real_hip_ctx *ctx, const PlacementSink &k, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
 {
-    RH_ENTER(ctx);
     real_hip_batch bv[2];
     int rc;
-    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1])) || (rc = pileup_add_check(ctx))) return rc;
+    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1])) || (rc = k.check(ctx))) return rc;
     if (bv[0].n_reads != bv[1].n_reads || bv[0].on_device != bv[1].on_device)
-        return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the mates' batches must agree in n_reads and on_device", hipSuccess);
+        return sink_invalid(ctx, k, "the mates' batches must agree in n_reads and on_device");
     const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: more than 2^32 reads in one call", hipSuccess);
+    if (n > 0xffffffffull) return sink_invalid(ctx, k, "more than 2^32 reads in one call");
     if (!n) return REAL_HIP_OK;
-    if (!pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null pairs", hipSuccess);
+    if (!pairs) return sink_invalid(ctx, k, "null pairs");
     if (bv[0].on_device == 1 && ((uintptr_t)pairs & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the pair records must be 8-byte aligned", hipSuccess);
     Staged st[2];
     for (int m = 0; m < 2; ++m)
         if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, bv[0].on_device != 1, ctx->stream, ctx->stream};
     const real_hip_pair *d_pairs = pairs;
-    rc = io.in(ctx->pu_rec, pairs, n, d_pairs);
+    rc = io.in(ctx->*k.rec, pairs, n, d_pairs);
     for (uint32_t m = 0; m < 2 && !rc; ++m) {
         DevBatch db = dev_batch(ctx, st[m], n);
         db.qual = st[m].qual;
-        rc = rh_launch_pileup_add(ctx, db, nullptr, d_pairs, m);
+        rc = k.launch(ctx, db, nullptr, d_pairs, m);
     }
     return rh_sync_tail(ctx, rc);
+}
+
+static const PlacementSink kPileupSink = {"pileup", pileup_add_check, &real_hip_ctx::pu_rec, rh_launch_pileup_add};
+
+extern "C" int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
+{
+    RH_ENTER(ctx);
+    return placements_add(ctx, kPileupSink, b, info);
+}
+
+extern "C" int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    return placements_add_pairs(ctx, kPileupSink, b1, b2, pairs);
 }
 
 extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
@@ -1155,6 +1179,98 @@ extern "C" int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stat
     RH_ENTER(ctx);
     if (out && out->struct_size != sizeof(real_hip_pileup_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup stats struct_size", hipSuccess);
     return rh_pileup_stats(ctx, out, reset);
+}
+
+// ---- variant calls (snp_call.hip): on top of the finished pileup; the reads and records are staged as the pileup stages them
+static int call_pileup_check(real_hip_ctx *ctx, const char *unfinished)
+{
+    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, unfinished, hipSuccess);
+    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: the text was replaced since the pileup's begin", hipSuccess);
+    return REAL_HIP_OK;
+}
+static int call_add_check(real_hip_ctx *ctx)
+{
+    if (ctx->cl_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add without begin", hipSuccess);
+    if (ctx->cl_state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add after finish", hipSuccess);
+    return call_pileup_check(ctx, "calls: add without a finished pileup");
+}
+static const PlacementSink kCallSink = {"calls", call_add_check, &real_hip_ctx::cl_rec, rh_launch_call_add};
+
+extern "C" int real_hip_call_begin(real_hip_ctx *ctx)
+{
+    RH_ENTER(ctx);
+    int rc = call_pileup_check(ctx, "calls: begin needs a finished pileup");
+    if (rc) return rc;
+    return rh_sync_tail(ctx, rh_call_begin(ctx));
+}
+
+extern "C" int real_hip_call_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
+{
+    RH_ENTER(ctx);
+    return placements_add(ctx, kCallSink, b, info);
+}
+
+extern "C" int real_hip_call_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
+{
+    RH_ENTER(ctx);
+    return placements_add_pairs(ctx, kCallSink, b1, b2, pairs);
+}
+
+extern "C" int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_params *p, uint64_t *n_calls)
+{
+    RH_ENTER(ctx);
+    if (!p || p->struct_size != sizeof(real_hip_call_params)) return rh_fail(ctx, REAL_HIP_E_INVALID, "call params struct_size", hipSuccess);
+    if (ctx->cl_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: finish without begin", hipSuccess);
+    int rc = call_pileup_check(ctx, "calls: finish without a finished pileup");
+    if (rc) return rc;
+    rc = rh_sync_tail(ctx, rh_call_finish(ctx, p->min_call_qual, p->min_depth, n_calls));
+    if (rc) { // nothing half-finished stays readable (the message of rc is kept)
+        const std::string msg = ctx->last_error;
+        rh_call_release(ctx);
+        ctx->last_error = msg;
+    }
+    return rc;
+}
+
+// the capacity protocol of real_hip_pileup_sites over `total` records of `size` bytes at `src`
+static int call_list(real_hip_ctx *ctx, const char *what, const void *src, uint64_t total, size_t size, void *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    if (ctx->cl_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, (std::string("calls: ") + what + " before finish").c_str(), hipSuccess);
+    if (!n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: null n_out", hipSuccess);
+    *n_out = total;
+    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, (std::string("calls: the ") + what + " list needs more room").c_str(), hipSuccess);
+    if (!total) return REAL_HIP_OK;
+    if (!out) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: null out", hipSuccess);
+    RH_HIP(ctx, hipMemcpyAsync(out, src, (size_t)total * size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return rh_sync_tail(ctx, REAL_HIP_OK);
+}
+
+extern "C" int real_hip_call_evidence(real_hip_ctx *ctx, real_hip_call_evidence_rec *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    RH_ENTER(ctx);
+    return call_list(ctx, "evidence", ctx->cl_ev.p, ctx->pu_n_sites, sizeof(real_hip_call_evidence_rec), out, cap, n_out, on_device);
+}
+
+extern "C" int real_hip_call_variants(real_hip_ctx *ctx, real_hip_call *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    RH_ENTER(ctx);
+    return call_list(ctx, "variants", ctx->cl_calls.p, ctx->cl_n_calls, sizeof(real_hip_call), out, cap, n_out, on_device);
+}
+
+extern "C" int real_hip_call_end(real_hip_ctx *ctx)
+{
+    RH_ENTER(ctx);
+    (void)hipStreamSynchronize(ctx->stream);
+    rh_call_release(ctx);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_call_stats_get(real_hip_ctx *ctx, real_hip_call_stats *out, int reset)
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(real_hip_call_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "call stats struct_size", hipSuccess);
+    return rh_call_stats(ctx, out, reset);
 }
 
 // ---- mismatch lists (mismatch_list.hip): the reads are staged as the pileup stages them, the records as the match's outputs;

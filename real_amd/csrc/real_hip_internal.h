@@ -300,6 +300,14 @@ struct real_hip_ctx {
     uint64_t pu_n = 0, pu_n_sites = 0, pu_covered = 0, pu_max_depth = 0; // the text begin saw; the last finish
     uint32_t pu_fileid = 0, pu_min_qual = 0;
 
+    // variant calls (snp_call.hip), on top of the finished pileup: the site bitmap (a bit per text position) and its rank array
+    // (sites before each 64-bit word), the evidence table (32 bytes per site), the per-block call counts and their scan, the
+    // call list, het / hom of finish (striped), the staged records when the caller's are host memory
+    DevBuf cl_bits, cl_rank, cl_ev, cl_blk, cl_calls, cl_fin, cl_rec;
+    RhStage call;
+    int      cl_state = 0;   // 0 none, 1 begun (adds), 2 finished (evidence / variants; finish again)
+    uint64_t cl_n_calls = 0, cl_het = 0, cl_hom = 0; // the last finish
+
     // mismatch lists (mismatch_list.hip): the counts per list, and when the caller's arrays are host memory the staged
     // records (info or pairs, the two mates' singles), the offsets and the lists
     DevBuf mm_cnt, mm_off, mm_out, mm_rec, mm_sg[2];
@@ -450,6 +458,14 @@ int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d
 int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites); // synchronises
 void rh_pileup_end(real_hip_ctx *ctx);
 int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
+
+// ---- variant calls (snp_call.hip) ------------------------------------------------------------
+int rh_call_begin(real_hip_ctx *ctx); // bitmap, rank array and zeroed evidence from the pileup's site list; synchronises
+// the evidence of a batch (d_info) or of mate `mate` of a batch of pairs (d_pairs), all arrays on the device; asynchronous
+int rh_launch_call_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate);
+int rh_call_finish(real_hip_ctx *ctx, uint32_t min_call_qual, uint32_t min_depth, uint64_t *n_calls); // synchronises
+void rh_call_release(real_hip_ctx *ctx); // (no synchronisation: the caller's)
+int rh_call_stats(real_hip_ctx *ctx, real_hip_call_stats *out, int reset);
 
 // ---- mismatch lists (mismatch_list.hip) -------------------------------------------------
 // one launch: the reads and the records that place them, all arrays on the device: info (single-end), or pairs and -- nullable --

@@ -66,6 +66,11 @@ void RealOptions::printHelp() const
               << "-pileup_depth <file: the depth as runs: fragment name, 0-based start, end, depth, for the maximal runs of equal\n"
               << "   non-zero depth inside a fragment; same conditions as -pileup>\n"
               << "-pileup_minq <Q: with -pileup, a mismatch of quality below Q is not counted, 0..63, default=0>\n"
+              << "-vcf <file: after the pileup of a genome file (it runs also without -pileup; -pileup_minq then applies to it), call SNPs at\n"
+              << "   its sites: the reads once more, bases of quality >= -pileup_minq counted per site, ten genotype likelihoods in integers,\n"
+              << "   VCF 4.2 with GT:GQ:DP:AD; same conditions as -pileup; -dedup 1 leaves the duplicates out; no indels, one sample>\n"
+              << "-vcf_minqual <Q: with -vcf, a call needs QUAL >= Q, default=20>\n"
+              << "-vcf_mindepth <D: with -vcf, a call needs D bases of sufficient quality, default=4>\n"
               << "-sam <file: after the output pass, write EVERY read as a SAM line (header: one @SQ per fragment of every genome file): a\n"
               << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255, CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
               << "   its mismatch list, computed on one fresh context on -device (ZS:f: the score, with -q 1); an unplaced read with FLAG 4.\n"
@@ -147,6 +152,9 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pileup") { pileupfilename = need("-pileup"); pileup_given = true; i += 2; }
         else if (a == "-pileup_depth") { pileupdepthfilename = need("-pileup_depth"); pileup_depth_given = true; i += 2; }
         else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
+        else if (a == "-vcf") { vcffilename = need("-vcf"); vcf_given = true; i += 2; }
+        else if (a == "-vcf_minqual") { vcf_minqual = strtoul(need("-vcf_minqual").c_str(), 0, 10); vcf_minqual_given = true; i += 2; }
+        else if (a == "-vcf_mindepth") { vcf_mindepth = strtoul(need("-vcf_mindepth").c_str(), 0, 10); vcf_mindepth_given = true; i += 2; }
         else if (a == "-sam") { samfilename = need("-sam"); sam_given = true; i += 2; }
         else if (a == "-dedup") { dedup = atoi(need("-dedup").c_str()) != 0; dedup_given = true; i += 2; }
         else if (a == "-dedup_minq") { dedup_minq = strtol(need("-dedup_minq").c_str(), 0, 10); dedup_minq_given = true; i += 2; }
@@ -237,13 +245,28 @@ RealOptions::RealOptions(int argc, char *argv[])
         if ((pileup_given && samfilename == pileupfilename) || (pileup_depth_given && samfilename == pileupdepthfilename))
             throw std::runtime_error("-sam must name a file of its own: it names the same file as -pileup / -pileup_depth.");
     }
+    if (vcf_given) { // SNP calls: loud errors before anything runs
+        if (!match_unique) throw std::runtime_error("-vcf calls variants from the unique placements: it cannot be combined with -u 0.");
+        if (pairs_all) throw std::runtime_error("-vcf calls variants from the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
+        if (vcffilename.empty()) throw std::runtime_error("-vcf needs a file name: an empty one was given.");
+        if (vcffilename == "-") throw std::runtime_error("-vcf writes to a file: standard output (-) cannot be it.");
+        if (vcffilename == outputfilename) throw std::runtime_error("-vcf must name a file of its own: it names the same file as -o.");
+        if (unpaired_given && vcffilename == unpairedfilename) throw std::runtime_error("-vcf must name a file of its own: it names the same file as -unpaired.");
+        if (!inserthistfilename.empty() && vcffilename == inserthistfilename) throw std::runtime_error("-vcf must name a file of its own: it names the same file as -insert_hist.");
+        if ((pileup_given && vcffilename == pileupfilename) || (pileup_depth_given && vcffilename == pileupdepthfilename))
+            throw std::runtime_error("-vcf must name a file of its own: it names the same file as -pileup / -pileup_depth.");
+        if (sam_given && vcffilename == samfilename) throw std::runtime_error("-vcf must name a file of its own: it names the same file as -sam.");
+        if (vcf_minqual > 0xfffffffful || vcf_mindepth > 0xfffffffful) throw std::runtime_error("-vcf_minqual / -vcf_mindepth take a number below 2^32.");
+    }
+    if (vcf_minqual_given && !vcf_given) throw std::runtime_error("-vcf_minqual is only meaningful with -vcf.");
+    if (vcf_mindepth_given && !vcf_given) throw std::runtime_error("-vcf_mindepth is only meaningful with -vcf.");
     if (dedup) { // duplicate marking: loud errors before anything runs
         if (!match_unique) throw std::runtime_error("-dedup marks copies of the unique placement of a read: it cannot be combined with -u 0.");
         if (pairs_all) throw std::runtime_error("-dedup marks copies of the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
     }
     if (dedup_minq_given && !dedup) throw std::runtime_error("-dedup_minq needs -dedup 1.");
     if (dedup_minq < 0 || dedup_minq > 63) throw std::runtime_error("-dedup_minq must be in 0..63.");
-    if (pileup_minq_given && !pileup_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
+    if (pileup_minq_given && !pileup_given && !vcf_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
     if (pileup_minq > 63) throw std::runtime_error("-pileup_minq takes a quality of at most 63.");
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
         if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");

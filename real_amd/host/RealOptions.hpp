@@ -61,6 +61,10 @@ struct RealOptions {
     bool pileup_given = false, pileup_depth_given = false, pileup_minq_given = false;
     std::string samfilename;          // -sam: the file that receives the final placements as SAM with NM / MD (real_hip_mismatches*)
     bool sam_given = false;
+    std::string vcffilename;          // -vcf: the file that receives the SNP calls of the pileup's sites as VCF (real_hip_call_*)
+    unsigned long vcf_minqual = 20;   // -vcf_minqual: a call needs QUAL of at least this
+    unsigned long vcf_mindepth = 4;   // -vcf_mindepth: and this many bases of sufficient quality
+    bool vcf_given = false, vcf_minqual_given = false, vcf_mindepth_given = false;
     bool dedup = false;               // -dedup: mark the copies of a placed read / fragment (real_hip_mark_duplicates*): FLAG 1024 in -sam, left out of -pileup
     long dedup_minq = 15;             // -dedup_minq: a base quality below it does not count in the sum that chooses the copy that stays
     bool dedup_given = false, dedup_minq_given = false;

@@ -40,6 +40,7 @@
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "Sam.hpp"
+#include "Vcf.hpp"
 #include "real_hip.h"
 
 namespace {
@@ -552,20 +553,60 @@ void textPass(const RealOptions &o, const std::vector<std::string> &files, Timer
         perFile(ctx, fi, G);
     }
 }
-inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.sam_given; }
+inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.vcf_given || o.sam_given; }
 
+// -vcf: the calls of the finished pileup of one genome file (real_hip_call_*) -- the reads once more through
+// addAll(ctx, true), which hands every batch with its final records to real_hip_call_add / _add_pairs -- as VCF lines, and a
+// summary line to standard error
 template <class AddAll>
-void pileupPass(const RealOptions &o, const std::vector<std::string> &files, Timers &T, AddAll addAll)
+void writeCalls(const RealOptions &o, CtxVec &ctx, const std::string &file, const std::vector<std::string> &names, const GenomeText &G, FILE *f, AddAll addAll)
 {
-    if (!o.pileup_given && !o.pileup_depth_given) return;
+    real_hip_ctx *h = ctx[0]->h;
+    check(h, real_hip_call_begin(h), "real_hip_call_begin");
+    addAll(ctx, true);
+    real_hip_call_params cp;
+    cp.struct_size = sizeof cp; cp.min_call_qual = (uint32_t)o.vcf_minqual; cp.min_depth = (uint32_t)o.vcf_mindepth;
+    uint64_t n_calls = 0, n = 0;
+    check(h, real_hip_call_finish(h, &cp, &n_calls), "real_hip_call_finish");
+    std::vector<real_hip_call> calls(n_calls);
+    check(h, real_hip_call_variants(h, calls.data(), calls.size(), &n, 0), "real_hip_call_variants");
+    size_t fr = 0;
+    for (uint64_t k = 0; k < n; ++k) {
+        while (fr + 1 < names.size() && G.frag_start[fr + 1] <= calls[k].pos) ++fr; // (ascending positions)
+        writeVcfLine(f, names[fr], calls[k].pos - G.frag_start[fr] + 1, calls[k]);
+    }
+    real_hip_pileup_stats ps;
+    memset(&ps, 0, sizeof ps);
+    ps.struct_size = sizeof ps;
+    check(h, real_hip_pileup_stats_get(h, &ps, 0), "real_hip_pileup_stats_get");
+    real_hip_call_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    check(h, real_hip_call_stats_get(h, &st, 1), "real_hip_call_stats_get");
+    fprintf(stderr, "calls: file=%s sites=%llu calls=%llu het=%llu hom=%llu site_bases=%llu low_qual=%llu\n", file.c_str(), (unsigned long long)ps.sites,
+            (unsigned long long)st.calls, (unsigned long long)st.het, (unsigned long long)st.hom, (unsigned long long)st.site_bases, (unsigned long long)st.low_qual);
+    check(h, real_hip_call_end(h), "real_hip_call_end");
+}
+
+// addAll(ctx, calls): every batch of reads with its final records to the pileup (calls = false) or to the calls on top of it
+template <class AddAll>
+void pileupPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, AddAll addAll)
+{
+    if (!o.pileup_given && !o.pileup_depth_given && !o.vcf_given) return;
     std::unique_ptr<OutFile> sites_out(o.pileup_given ? new OutFile(o.pileupfilename, false, "-pileup") : nullptr);
     std::unique_ptr<OutFile> depth_out(o.pileup_depth_given ? new OutFile(o.pileupdepthfilename, false, "-pileup_depth") : nullptr);
+    std::unique_ptr<OutFile> vcf_out(o.vcf_given ? new OutFile(o.vcffilename, false, "-vcf") : nullptr);
+    const SamRefs refs(RS.names, RS.starts);
+    if (vcf_out) {
+        const std::string head = vcfHeader(refs);
+        if (fwrite(head.data(), 1, head.size(), vcf_out->file()) != head.size()) throw std::runtime_error("write to the -vcf file failed");
+    }
     real_hip_pileup_params pp;
     pp.struct_size = sizeof pp; pp.min_qual = (uint32_t)o.pileup_minq;
     textPass(o, files, T, [&](CtxVec &ctx, unsigned fi, const GenomeText &G) {
         real_hip_ctx *h = ctx[0]->h;
         check(h, real_hip_pileup_begin(h, &pp), "real_hip_pileup_begin");
-        addAll(ctx);
+        addAll(ctx, false);
         uint64_t n_sites = 0;
         check(h, real_hip_pileup_finish(h, &n_sites), "real_hip_pileup_finish");
         if (sites_out) writeSites(h, n_sites, G, sites_out->file());
@@ -578,13 +619,14 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, Tim
                 files[fi].c_str(), (unsigned long long)st.placed, (unsigned long long)st.bases, (unsigned long long)st.covered,
                 st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
                 (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
+        if (vcf_out) writeCalls(o, ctx, files[fi], refs.names[fi], G, vcf_out->file(), addAll);
         check(h, real_hip_pileup_end(h), "real_hip_pileup_end");
     });
-    for (OutFile *f : {sites_out.get(), depth_out.get()}) {
+    for (OutFile *f : {sites_out.get(), depth_out.get(), vcf_out.get()}) {
         if (!f) continue;
         const bool bad = ferror(f->file()) != 0; // (a line that could not be written)
         f->close();
-        if (bad) throw std::runtime_error("write to the -pileup / -pileup_depth file failed");
+        if (bad) throw std::runtime_error("write to the -pileup / -pileup_depth / -vcf file failed");
     }
 }
 
@@ -738,13 +780,13 @@ int matchUnique(const RealOptions &o)
     std::cerr << "unique: " << unique << std::endl; // :1488
     if (passesBehindOutput(o)) ctx.clear(); // (the matching contexts go before the pass's own one comes)
     std::vector<uint64_t> kept; // -dedup: a batch's records without the duplicates
-    pileupPass(o, files, T, [&](CtxVec &pc) {
+    pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
                 if (!it.batch.n_reads) continue;
                 if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
-                check(pc[0]->h, real_hip_pileup_add(pc[0]->h, &it.batch, withoutDuplicates(info, dup, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
-                      "real_hip_pileup_add");
+                check(pc[0]->h, (calls ? real_hip_call_add : real_hip_pileup_add)(pc[0]->h, &it.batch, withoutDuplicates(info, dup, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
+                      calls ? "real_hip_call_add" : "real_hip_pileup_add");
             }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
@@ -1027,7 +1069,7 @@ int matchPairs(const RealOptions &o)
     }
     if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
     std::vector<real_hip_pair> kept; // -dedup: a batch's records without the duplicates
-    pileupPass(o, files, T, [&](CtxVec &pc) {
+    pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
@@ -1035,8 +1077,8 @@ int matchPairs(const RealOptions &o)
             if (!n) break;
             if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
             const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
-            check(pc[0]->h, real_hip_pileup_add_pairs(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, dup, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
-                  "real_hip_pileup_add_pairs");
+            check(pc[0]->h, (calls ? real_hip_call_add_pairs : real_hip_pileup_add_pairs)(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, dup, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
+                  calls ? "real_hip_call_add_pairs" : "real_hip_pileup_add_pairs");
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");

@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "real_hip_pair_insert_hist", "real_hip_insert_bounds", "real_hip_insert_stats_get",
     "real_hip_pileup_begin", "real_hip_pileup_add", "real_hip_pileup_add_pairs", "real_hip_pileup_finish", "real_hip_pileup_depth",
     "real_hip_pileup_sites", "real_hip_pileup_end", "real_hip_pileup_stats_get",
+    "real_hip_call_begin", "real_hip_call_add", "real_hip_call_add_pairs", "real_hip_call_finish", "real_hip_call_evidence",
+    "real_hip_call_variants", "real_hip_call_end", "real_hip_call_stats_get",
     "real_hip_mismatches", "real_hip_mismatches_pairs", "real_hip_mismatch_stats_get",
     "real_hip_read_summary", "real_hip_mark_duplicates", "real_hip_mark_duplicates_pairs", "real_hip_dup_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
@@ -149,6 +151,25 @@ PILEUP_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mis
 class RealHipPileupStats(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
                [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in PILEUP_STATS_FIELDS]
+
+
+class RealHipCallParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_call_qual", C.c_uint32), ("min_depth", C.c_uint32)]
+
+
+# the constants of the genotype model (include/real_hip.h, "variant calls")
+CALL_HET, CALL_ERR, CALL_PRIOR_HET, CALL_PRIOR_HOM, CALL_PRIOR_HET2 = 3, 5, 30, 33, 60
+# real_hip_call_evidence_rec (record s belongs to site s of the pileup) and real_hip_call as numpy dtypes
+CALL_EVIDENCE_DTYPE = np.dtype([("cnt", "<u4", (4,)), ("qsum", "<u4", (4,))])
+CALL_DTYPE = np.dtype([("pos", "<u4"), ("depth", "<u4"), ("cnt", "<u4", (4,)), ("qual", "<u4"), ("ref", "u1"), ("a1", "u1"), ("a2", "u1"), ("gq", "u1")])
+assert CALL_EVIDENCE_DTYPE.itemsize == 32 and CALL_DTYPE.itemsize == 32
+
+CALL_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "site_bases", "low_qual", "calls", "het", "hom", "launches", "kernel_ms")
+
+
+class RealHipCallStats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
+               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in CALL_STATS_FIELDS]
 
 
 class RealHipMismatch(C.Structure):
@@ -304,6 +325,14 @@ def load():
     L.real_hip_pileup_sites.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
     L.real_hip_pileup_end.argtypes = [vp]
     L.real_hip_pileup_stats_get.argtypes = [vp, C.POINTER(RealHipPileupStats), C.c_int]
+    L.real_hip_call_begin.argtypes = [vp]
+    L.real_hip_call_add.argtypes = [vp, C.POINTER(RealHipBatch), vp]
+    L.real_hip_call_add_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp]
+    L.real_hip_call_finish.argtypes = [vp, C.POINTER(RealHipCallParams), C.POINTER(u64)]
+    L.real_hip_call_evidence.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
+    L.real_hip_call_variants.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
+    L.real_hip_call_end.argtypes = [vp]
+    L.real_hip_call_stats_get.argtypes = [vp, C.POINTER(RealHipCallStats), C.c_int]
     L.real_hip_mismatches.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp, u64, C.POINTER(u64), vp]
     L.real_hip_mismatches_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp, vp, vp, vp, u64, C.POINTER(u64), vp]
     L.real_hip_mismatch_stats_get.argtypes = [vp, C.POINTER(RealHipMismatchStats), C.c_int]

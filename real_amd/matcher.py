@@ -553,6 +553,69 @@ class HipMatcher:
     def pileup_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipPileupStats, self._L.real_hip_pileup_stats_get, _lib.PILEUP_STATS_FIELDS, reset)
 
+    # -- variant calls: genotypes of the finished pileup's sites (include/real_hip.h, "variant calls") --
+    def call_begin(self):
+        """real_hip_call_begin: site bitmap, rank array and zeroed evidence of the finished pileup; a second begin starts again"""
+        self._check(self._L.real_hip_call_begin(self._h))
+
+    def call_add(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
+                 packed: bool = False, nflags=None):
+        """real_hip_call_add: the evidence of the placements of `info`; the arguments are pileup_add's"""
+        host_info = isinstance(info, np.ndarray)
+        if host_info:
+            info = np.ascontiguousarray(info, dtype=np.uint64)
+        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
+        if int(info.shape[0]) != int(b.n_reads):
+            raise ValueError("one record per read")
+        self.sync_inputs(info)
+        self._check(self._L.real_hip_call_add(self._h, C.byref(b), _ptr(info)))
+
+    def call_add_pairs(self, mate1, mate2, pairs):
+        """real_hip_call_add_pairs: both mates of every Unique record of `pairs`; the arguments are pileup_add_pairs'"""
+        host_pairs = isinstance(pairs, np.ndarray)
+        if host_pairs:
+            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
+        bs = []
+        for mate in (mate1, mate2):
+            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
+            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
+        self.sync_inputs(pairs)
+        self._check(self._L.real_hip_call_add_pairs(self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs)))
+
+    def call_finish(self, min_call_qual: int = 20, min_depth: int = 4) -> int:
+        """real_hip_call_finish: the genotypes and the compacted call list; returns the number of calls.  May be called again
+        with other thresholds"""
+        p = _lib.RealHipCallParams()
+        p.struct_size = C.sizeof(_lib.RealHipCallParams)
+        p.min_call_qual, p.min_depth = int(min_call_qual), int(min_depth)
+        n = C.c_uint64(0)
+        self._check(self._L.real_hip_call_finish(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def _call_list(self, call, dtype, cap: int) -> np.ndarray:
+        n = C.c_uint64(0)
+        out = np.zeros(int(cap), dtype=dtype)
+        rc = call(self._h, out.ctypes.data, int(cap), C.byref(n), 0)
+        if rc == _lib.REAL_HIP_E_OVERFLOW:
+            out = np.zeros(int(n.value), dtype=dtype)
+            rc = call(self._h, out.ctypes.data, int(n.value), C.byref(n), 0)
+        self._check(rc)
+        return out[:int(n.value)]
+
+    def call_evidence(self, cap: int = 1024) -> np.ndarray:
+        """the evidence table as lib.CALL_EVIDENCE_DTYPE, record s for site s of pileup_sites(); the buffer grows once"""
+        return self._call_list(self._L.real_hip_call_evidence, _lib.CALL_EVIDENCE_DTYPE, cap)
+
+    def call_variants(self, cap: int = 1024) -> np.ndarray:
+        """the call list as lib.CALL_DTYPE, ascending position; the buffer grows once to the size the library reports"""
+        return self._call_list(self._L.real_hip_call_variants, _lib.CALL_DTYPE, cap)
+
+    def call_end(self):
+        self._check(self._L.real_hip_call_end(self._h))
+
+    def call_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipCallStats, self._L.real_hip_call_stats_get, _lib.CALL_STATS_FIELDS, reset)
+
     # -- mismatch lists: where each placed read differs from the resident text (include/real_hip.h, "mismatch lists") --
     def _mismatch_call(self, call, lists: int, on_device: bool, cap: int):
         """one list call with its outputs: host numpy arrays, or device tensors when the records are; the buffer grows once to
