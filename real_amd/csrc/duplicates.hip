@@ -14,11 +14,11 @@
 //   dup_mark_kernel       one lane per sorted place: a place whose group part equals its predecessor's is a duplicate.
 // The tie-breaker sits inside the key: the sort is stable and the values start as 0 .. n-1, so inside a group the largest qsum
 // comes first and among equal qsum the smallest index.  The work per element is constant, whatever the group sizes; nothing
-// is hashed.  dup[] is cleared beforehand (the unplaced records), the marks are byte stores.  placed and groups are summed
-// per wave into striped lines.  No LDS of our own, no scratch memory, plain C++.
+// is hashed.  dup[] is cleared beforehand (the unplaced records), the marks are byte stores.  The key kernels read their
+// records through final_record.h's decoders; placed and groups go to the striped line with stage_common.h's rh_stats_add.
+// No LDS of our own, no scratch memory, plain C++.
 #include "real_hip_internal.h"
 #include "read_walk.h"
-#include "pair_state.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -117,7 +117,7 @@ __global__ void __launch_bounds__(RH_DUP_BLOCK) read_summary_kernel(const Summar
 // ---- keys ---------------------------------------------------------------------------------------------------------
 struct DupArgs {
     const uint64_t *info;          // single-end records, or
-    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (insert_hist.hip)
+    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (final_record.h)
     const uint2 *sum[2];           // real_hip_read_sum {len, qsum} of the reads / of mate 1 and mate 2
     uint64_t n;
     uint64_t *key;                 // single-end key / low word of the paired key: what the sort takes
@@ -129,16 +129,13 @@ __global__ void __launch_bounds__(RH_DUP_BLOCK) dup_key_kernel(const DupArgs A)
 {
     const uint64_t i = (uint64_t)blockIdx.x * RH_DUP_BLOCK + threadIdx.x;
     if (i >= A.n) return;
-    const uint64_t r = A.info[i];
-    const uint32_t st = (uint32_t)(r >> ST_SHIFT);
+    const RhPlace r = rh_place_info(A.info[i]);
     uint64_t key = RH_DUP_SENTINEL;
-    if (st == ST_STRAIGHT || st == ST_REVERSE) {
+    if (r.place) {
         const uint2 s = A.sum[0][i];
-        const uint64_t pos = r & POS_MASK;
-        const uint64_t end5 = (st == ST_REVERSE ? pos + s.x - 1 : pos) & ((1ull << RH_DUP_E5_BITS) - 1);
+        const uint64_t end5 = (r.inv ? r.pos + s.x - 1 : r.pos) & ((1ull << RH_DUP_E5_BITS) - 1);
         const uint32_t qmax = (1u << RH_DUP_Q_BITS) - 1;
-        const uint64_t file = (r >> FI_SHIFT) & ((1u << RH_DUP_FI_BITS) - 1);
-        key = (((file << 1 | (st == ST_REVERSE ? 1u : 0u)) << RH_DUP_E5_BITS | end5) << RH_DUP_Q_BITS) | (qmax - min(s.y, qmax));
+        key = ((((uint64_t)r.file << 1 | (r.inv ? 1u : 0u)) << RH_DUP_E5_BITS | end5) << RH_DUP_Q_BITS) | (qmax - min(s.y, qmax));
     }
     A.key[i] = key;
     A.val[i] = (uint32_t)i;
@@ -150,15 +147,15 @@ __global__ void __launch_bounds__(RH_DUP_BLOCK) dup_pair_key_kernel(const DupArg
     if (i >= A.n) return;
     const uint2 tail = A.pairs[i * 5 + 4];
     uint64_t lo = RH_DUP_SENTINEL >> (64 - RH_DUP_PE_BITS - RH_DUP_PQ_BITS), hi = 1ull << (RH_DUP_PHI_BITS - 1);
-    if (((tail.y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE) {
+    if (rh_pair_state(tail.y) == REAL_HIP_PAIR_UNIQUE) {
         const uint2 pos = A.pairs[i * 5 + 2];
         const uint2 s1 = A.sum[0][i], s2 = A.sum[1][i];
-        const uint32_t inv1 = ((tail.y >> 8) & 0xffu) != 0 ? 1u : 0u; // the forward mate is mate 1 iff inverted1 == 0
+        const uint32_t inv1 = rh_pair_inverted1(tail.y) ? 1u : 0u; // the forward mate is mate 1 iff inverted1 == 0
         const uint64_t start = inv1 ? pos.y : pos.x;
         const uint64_t end = ((inv1 ? (uint64_t)pos.x + s1.x : (uint64_t)pos.y + s2.x) - 1) & ((1ull << RH_DUP_PE_BITS) - 1);
         const uint32_t q1max = (1u << RH_DUP_Q_BITS) - 1, qmax = (1u << RH_DUP_PQ_BITS) - 1;
         lo = end << RH_DUP_PQ_BITS | (qmax - (min(s1.y, q1max) + min(s2.y, q1max)));
-        hi = ((uint64_t)((tail.x >> 16) & 0xffu) << 1 | inv1) << 32 | start;
+        hi = ((uint64_t)rh_pair_fileid(tail.x) << 1 | inv1) << 32 | start;
     }
     A.key[i] = lo;
     A.lo[i] = lo;
@@ -202,12 +199,8 @@ __global__ void __launch_bounds__(RH_DUP_BLOCK) dup_mark_kernel(const MarkArgs A
             placed = 1; first = same ? 0u : 1u;
         }
     }
-    for (int d = 32; d; d >>= 1) { placed += (uint32_t)__shfl_xor((int)placed, d); first += (uint32_t)__shfl_xor((int)first, d); }
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *s = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-        if (placed) atomicAdd(s, (unsigned long long)placed);
-        if (first) atomicAdd(s + 1, (unsigned long long)first);
-    }
+    uint32_t s[2] = {placed, first}; // (a wave's sums are at most 64)
+    rh_stats_add(A.stats, s);
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
@@ -233,9 +226,6 @@ int rh_launch_read_summary(real_hip_ctx *ctx, const DevBatch &b, uint32_t min_qu
 int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_pair *d_pairs, const real_hip_read_sum *d_sum1,
                               const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup)
 {
-    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
-                      offsetof(real_hip_pair, fileid) == 34 && offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
-                  "dup_pair_key_kernel reads words 2 and 4 of the record");
     if (!n) return REAL_HIP_OK;
     if (n > (1ull << 32)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: more than 2^32 records in one call", hipSuccess);
     const bool pairs = d_pairs != nullptr;

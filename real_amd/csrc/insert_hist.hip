@@ -2,7 +2,8 @@
 // (include/real_hip.h, "insert sizes").
 //
 // One grid-stride kernel.  A lane reads of a 40-byte record the two positions (8 bytes at offset 16) and the tail word with
-// inverted1 and state (8 bytes at offset 32), and of the lengths the reverse mate's; the two FP64 values are not loaded.
+// inverted1 and state (8 bytes at offset 32; final_record.h names its fields), and of the lengths the reverse mate's; the two
+// FP64 values are not loaded.
 // Each block keeps a private histogram of 32-bit counts in LDS and flushes its non-zero bins with 64-bit global atomic adds
 // at the end: insert sizes sit on a few hundred values, and one global atomic per record onto them would run at the
 // contention rate of those few lines, not at the rate of the memory.
@@ -22,7 +23,7 @@
 #define RH_IH_UNROLL 4u /* records a lane has in flight */
 
 struct InsertArgs {
-    const uint2 *rec;              // real_hip_pair records as five 8-byte words: word 2 = pos1, pos2; word 4 = frag:16 fileid:8 k1:8, k2:8 inverted1:8 state:8 reserved:8
+    const uint2 *rec;              // real_hip_pair records as five 8-byte words: word 2 = pos1, pos2; word 4 = the tail (final_record.h)
     const uint32_t *len[2];
     uint64_t n;
     unsigned long long *hist;      // n_bins counts, added to
@@ -53,14 +54,14 @@ __global__ void __launch_bounds__(RH_IH_BLOCK) insert_hist_kernel(const InsertAr
 #pragma unroll
         for (uint32_t u = 0; u < RH_IH_UNROLL; ++u) { // (state 0 of the lanes beyond the end: NoMatch)
             const uint64_t i = base + u * stride;
-            const bool unique = ((tail[u].y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE;
-            const bool fwd1 = ((tail[u].y >> 8) & 0xffu) == 0; // the forward mate is mate 1 iff inverted1 == 0: the reverse one is then mate 2
+            const bool unique = rh_pair_state(tail[u].y) == REAL_HIP_PAIR_UNIQUE;
+            const bool fwd1 = !rh_pair_inverted1(tail[u].y); // the forward mate is mate 1 iff inverted1 == 0: the reverse one is then mate 2
             if (unique) len_r[u] = (fwd1 ? A.len[1] : A.len[0])[i];
         }
 #pragma unroll
         for (uint32_t u = 0; u < RH_IH_UNROLL; ++u) {
-            if (((tail[u].y >> 16) & 0xffu) != REAL_HIP_PAIR_UNIQUE) continue;
-            const bool fwd1 = ((tail[u].y >> 8) & 0xffu) == 0;
+            if (rh_pair_state(tail[u].y) != REAL_HIP_PAIR_UNIQUE) continue;
+            const bool fwd1 = !rh_pair_inverted1(tail[u].y);
             const uint64_t fp = fwd1 ? pos[u].x : pos[u].y, rp = fwd1 ? pos[u].y : pos[u].x;
             if (fp > rp || rp + len_r[u] < fp) { ++invalid; continue; }
             const uint64_t outer = pair_outer(fp, rp, len_r[u]);
@@ -73,22 +74,13 @@ __global__ void __launch_bounds__(RH_IH_BLOCK) insert_hist_kernel(const InsertAr
     __syncthreads();
     for (uint32_t b = threadIdx.x; b < A.n_bins; b += RH_IH_BLOCK) // the flush
         if (bins[b]) atomicAdd(A.hist + b, (unsigned long long)bins[b]);
-    unsigned long long s0 = counted, s1 = over, s2 = invalid;
-    for (int d = 32; d; d >>= 1) { s0 += __shfl_xor(s0, d); s1 += __shfl_xor(s1, d); s2 += __shfl_xor(s2, d); }
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *s = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-        if (s0) atomicAdd(s, s0);
-        if (s1) atomicAdd(s + 1, s1);
-        if (s2) atomicAdd(s + 2, s2);
-    }
+    uint32_t s[3] = {counted, over, invalid}; // (32-bit sums: the lanes of a wave together see at most the n < 2^32 records of the call)
+    rh_stats_add(A.stats, s);
 }
 
 int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const uint32_t *d_len1, const uint32_t *d_len2, uint64_t n,
                           uint32_t n_bins, uint64_t *d_hist)
 {
-    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
-                      offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
-                  "insert_hist_kernel reads words 2 and 4 of the record");
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     if (n_bins < 2 || n_bins > REAL_HIP_INSERT_HIST_MAX_BINS) return rh_fail(ctx, REAL_HIP_E_INVALID, "n_bins out of range", hipSuccess);

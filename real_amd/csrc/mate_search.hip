@@ -232,8 +232,7 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
     if ((rc = rh_stats_reserve(ctx, ctx->search.stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
     MateSearchArgs A;
     memset(&A, 0, sizeof A);
-    A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p; A.t.frag_start = (const uint64_t *)ctx->frag.p;
-    A.t.n = ctx->n_bases; A.t.n_frag = ctx->n_frag; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = fileid;
+    A.t = rh_dev_text(ctx, fileid);
     A.b[0] = b1; A.b[1] = b2;
     A.L = L; // (its len[] may be null: the kernel takes the read lengths from the batches)
     A.n = n; A.pairs = d_pairs; A.LL = (const double *)ctx->LL.p;

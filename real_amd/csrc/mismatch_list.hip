@@ -2,18 +2,18 @@
 // read base} per read (include/real_hip.h, "mismatch lists"); what NM / MD of a SAM line are written from.
 //
 // Count, scan, emit (the pattern of pair_all.hip and of the pileup's sites).  One lane per placement in both passes (wave64,
-// blocks of 256).  The lane decodes its record -- an info word, a pair record, or the mate's single record where the pair
-// record has no placement -- into (placed, p, strand, k), then walks its read word by word with read_walk.h, the walk of
-// pileup_add_kernel: 32 bases per step, the oriented read XOR the funnel-shifted text, one flag per differing base.  Where
+// blocks of 256).  The lane takes its record -- an info word, a pair record, or the mate's single record where the pair
+// record has no placement -- as a placement on the text with read_walk.h's placed_read, the step the pileup and the calls
+// take, then walks its read word by word with read_walk.h, the walk of pileup_add_kernel: 32 bases per step, the oriented
+// read XOR the funnel-shifted text, one flag per differing base.  Where
 // the text holds an N at all, the N bits of the same 32 positions are ORed in: an N of the text is listed whatever the read
 // shows.  The count pass takes the popcount and writes it; rocPRIM's exclusive scan of the counts is mm_offsets; the emit
 // pass repeats the walk and writes every flagged base with one 4-byte vector store behind the lane's offset, in ascending
-// offset.  The statistics are taken in the count pass, summed per wave and striped.
+// offset.  The statistics are taken in the count pass and added to the striped line by stage_common.h's rh_stats_add.
 //
 // The output is a function of records, reads and text alone.  No LDS, no scratch memory, plain C++.
 #include "real_hip_internal.h"
 #include "read_walk.h"
-#include "pair_state.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -25,7 +25,7 @@ struct MismatchArgs {
     DevText  t;
     DevBatch b;                    // the reads of this launch (mate `mate` of a pair launch)
     const uint64_t *info;          // single-end records, or
-    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (insert_hist.hip) and
+    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (final_record.h) and
     const uint4 *singles;          // this mate's real_hip_single records (nullable)
     uint32_t mate;                 // pair launches: 0 = mate 1, 1 = mate 2
     uint32_t stride;               // read i of the launch is list i * stride + mate: 1 single-end, 2 pairs
@@ -35,30 +35,6 @@ struct MismatchArgs {
     unsigned long long *stats;     // RH_PAIR_STRIPES x 16 words: [0] placed, [1] other_file, [2] invalid, [3] bases, [4] mismatches,
                                    // [5] on_n, [6] disagree
 };
-
-// what a record says of its read: a placement or not, where, on which strand, with how many mismatches
-struct MmPlace {
-    bool place, inv;
-    uint32_t file, k;
-    uint64_t p;
-};
-static __device__ __forceinline__ MmPlace mm_decode_info(uint64_t r)
-{
-    const uint32_t st = (uint32_t)(r >> ST_SHIFT);
-    return MmPlace{st == ST_STRAIGHT || st == ST_REVERSE, st == ST_REVERSE, (uint32_t)(r >> FI_SHIFT) & 63u, (uint32_t)(r >> ER_SHIFT) & 15u, r & POS_MASK};
-}
-// words 2 and 4 of a pair record; *state: the record's
-static __device__ __forceinline__ MmPlace mm_decode_pair(uint2 pos, uint2 tail, uint32_t mate, uint32_t *state)
-{
-    *state = (tail.y >> 16) & 0xffu;
-    return MmPlace{*state == REAL_HIP_PAIR_UNIQUE, (((tail.y >> 8) & 0xffu) != 0) != (mate != 0), (tail.x >> 16) & 0xffu,
-                   mate ? tail.y & 0xffu : tail.x >> 24, mate ? pos.y : pos.x};
-}
-static __device__ __forceinline__ MmPlace mm_decode_single(uint4 s)
-{
-    const uint32_t tag = s.w >> 24;
-    return MmPlace{REAL_HIP_SINGLE_STATE(tag) == REAL_HIP_PAIR_UNIQUE, REAL_HIP_SINGLE_INVERTED(tag) != 0, (s.w >> 16) & 0xffu, REAL_HIP_SINGLE_K(tag), s.z};
-}
 
 // the text's N bits of the 32 positions from x on, as flags: position x + u at bit 62 - 2u
 static __device__ __forceinline__ uint64_t mm_n_flags(const uint64_t *__restrict__ wild, uint64_t x)
@@ -86,24 +62,12 @@ __global__ void __launch_bounds__(RH_MM_BLOCK) mismatch_list_kernel(const Mismat
         uint64_t at = 0, end = 0;
         bool live = true;
         if (EMIT) { at = A.off[list]; end = A.off[list + 1]; live = end > at; }
-        if (live) {
-            MmPlace c;
-            if (PAIRS) {
-                uint32_t state;
-                c = mm_decode_pair(A.pairs[i * 5 + 2], A.pairs[i * 5 + 4], A.mate, &state);
-                if (state == REAL_HIP_PAIR_NOMATCH && A.singles) c = mm_decode_single(A.singles[i]); // (a NonUnique pair places nothing)
-            } else {
-                c = mm_decode_info(A.info[i]);
-            }
-            if (c.place && c.file != A.t.fileid) { c.place = false; ++other; }
-            uint64_t start = 0;
-            uint32_t L = 0;
+        if (live) { // (a lane of the emit pass whose list is empty decodes nothing)
+            const PlacedRead c = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, A.singles, A.mate, i);
+            other = c.other; invalid = c.bad;
             if (c.place) {
-                L = read_extent(A.b, i, start);
-                if (c.p + L > A.t.n) { c.place = false; ++invalid; } // (35 bits of position in an info word: no wrap-around)
-            }
-            if (c.place) {
-                const uint32_t p = (uint32_t)c.p;
+                const uint32_t p = c.p, L = c.L;
+                const uint64_t start = c.start;
                 const uint32_t nw = (L + 31u) >> 5;
                 ReadWalk walk;
                 walk.begin(A.t.text, p, L);
@@ -137,17 +101,8 @@ __global__ void __launch_bounds__(RH_MM_BLOCK) mismatch_list_kernel(const Mismat
         if (!EMIT) A.cnt[list] = mism;
     }
     if (EMIT) return;
-    // the statistics: one sum per wave, added to a striped line
     uint32_t s[7] = {placed, other, invalid, bases, mism, on_n, disagree}; // (a wave's sums stay below 2^32: 64 reads of at most 2^14 bases)
-#pragma unroll
-    for (int k = 0; k < 7; ++k)
-        for (int d = 32; d; d >>= 1) s[k] += (uint32_t)__shfl_xor((int)s[k], d);
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *line = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-            if (s[k]) atomicAdd(line + k, (unsigned long long)s[k]);
-    }
+    rh_stats_add(A.stats, s);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------
@@ -155,17 +110,9 @@ static MismatchArgs mismatch_args(real_hip_ctx *ctx, const RhMismatchLaunch &l, 
 {
     static_assert(sizeof(real_hip_mismatch) == 4 && offsetof(real_hip_mismatch, ref) == 2 && offsetof(real_hip_mismatch, base) == 3,
                   "a mismatch is one 4-byte store: off | ref << 16 | base << 24");
-    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
-                      offsetof(real_hip_pair, fileid) == 34 && offsetof(real_hip_pair, k1) == 35 && offsetof(real_hip_pair, k2) == 36 &&
-                      offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
-                  "mm_decode_pair reads words 2 and 4 of the record");
-    static_assert(sizeof(real_hip_single) == 16 && offsetof(real_hip_single, pos) == 8 && offsetof(real_hip_single, fileid) == 14 &&
-                      offsetof(real_hip_single, tag) == 15,
-                  "mm_decode_single reads words z and w of the record");
     MismatchArgs A;
     memset(&A, 0, sizeof A);
-    A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p;
-    A.t.n = ctx->n_bases; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = ctx->fileid;
+    A.t = rh_dev_text(ctx, ctx->fileid);
     A.b = l.b;
     A.b.qual = nullptr; // (not read)
     A.info = l.info; A.pairs = (const uint2 *)l.pairs; A.singles = (const uint4 *)l.singles;

@@ -4,10 +4,9 @@
 // and the fold state of the pair records with the candidate made of two placements (the join and the mate search
 // mate_search.hip, which fold candidates of the same kind into the same records).
 #pragma once
-#include "real_hip_internal.h"
+#include "stage_common.h" // RH_PAIR_STRIPES: the statistics lines of every stage
 
 #define RH_PAIR_LANE_BUDGET 32u   /* product cells a lane walks itself */
-#define RH_PAIR_STRIPES 256u      /* the statistics are striped over this many 128-byte lines (see RH_CSTRIPES) */
 
 // real_hip_hit as a uint4: x read, y pos, z score bits, w frag:16 | k:8 | inverted:8.
 // Hit a of mate 1 and hit b of mate 2 (read lengths la, lb) are concordant: same fragment, opposite strands, the forward

@@ -2,8 +2,8 @@
 // placed read shows another base than the text, how often each base was seen (include/real_hip.h, "pileup").
 //
 // pileup_add_kernel: one lane per read, and the lane WALKS ITS READ WORD BY WORD -- 32 bases at a time, whatever the length
-// (up to REAL_HIP_MAX_PATL_LONG): no register array of the read, no second kernel for long reads (the walk itself is
-// read_walk.h, shared with mismatch_list.hip).  Per word the lane packs
+// (up to REAL_HIP_MAX_PATL_LONG): no register array of the read, no second kernel for long reads (the record's decode into a
+// placement and the walk itself are read_walk.h's, shared with snp_call.hip and mismatch_list.hip).  Per word the lane packs
 // the 32 read bases that lie over the next 32 text positions with match_common.h's pack_read / pack_read_packed (W = 1; a
 // packed read may start inside a byte) -- on the reverse strand those are the read's LAST unvisited bases, turned round with
 // revcomp_words -- loads the 2-bit text funnel-shifted to the placement and takes XOR: one flag per base.  Every flagged
@@ -12,15 +12,14 @@
 // arithmetic -- two atomics per read, not one per base.
 //
 // finish: rocPRIM's inclusive scan turns the difference array into depth[] in place; then count, scan, emit over the
-// positions (the pattern of pair_all.hip): a block of 256 positions counts its sites (alt sum > 0), the block counts are
-// scanned, and the emit pass writes the 32-byte site records in ascending position.  The count pass also sums `covered`
-// and takes `max_depth`.
+// positions (the pattern of pair_all.hip; the block's count and a site's slot are stage_common.h's): a block of 256
+// positions counts its sites (alt sum > 0), the block counts are scanned, and the emit pass writes the 32-byte site records
+// in ascending position.  The count pass also sums `covered` and takes `max_depth`.
 //
 // Everything is an integer sum: nothing depends on the order of reads, lanes, blocks or calls.  No LDS in the add kernel,
 // no scratch memory; plain C++ and vector stores.
 #include "real_hip_internal.h"
 #include "read_walk.h"
-#include "pair_state.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -32,7 +31,7 @@ struct PileupArgs {
     DevText  t;
     DevBatch b;                    // the reads of this launch (mate `mate` of a pair launch)
     const uint64_t *info;          // single-end records, or
-    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (insert_hist.hip)
+    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (final_record.h)
     uint32_t mate;                 // pair launches: 0 = mate 1, 1 = mate 2
     uint32_t min_qual;
     uint32_t *diff;                // n + 1: the depth's difference array
@@ -48,7 +47,7 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_add_kernel(const PileupArg
     uint32_t placed = 0, other = 0, invalid = 0, bases = 0, mism = 0, lowq = 0, ndrop = 0;
     if (i < A.b.n_reads) {
         // the record: is it a placement in this file, where, on which strand (read_walk.h)
-        const PlacedRead r = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, A.mate, i);
+        const PlacedRead r = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, nullptr, A.mate, i);
         other = r.other; invalid = r.bad;
         const bool inv = r.inv;
         const uint32_t p = r.p, L = r.L;
@@ -80,17 +79,8 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_add_kernel(const PileupArg
             }
         }
     }
-    // the statistics: one sum per wave, added to a striped line
     uint32_t s[7] = {placed, other, invalid, bases, mism, lowq, ndrop}; // (a wave's sums stay below 2^32: 64 reads of at most 2^14 bases)
-#pragma unroll
-    for (int k = 0; k < 7; ++k)
-        for (int d = 32; d; d >>= 1) s[k] += (uint32_t)__shfl_xor((int)s[k], d);
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *line = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-#pragma unroll
-        for (int k = 0; k < 7; ++k)
-            if (s[k]) atomicAdd(line + k, (unsigned long long)s[k]);
-    }
+    rh_stats_add(A.stats, s);
 }
 
 // ---- finish: the sites ------------------------------------------------------------------------------------------
@@ -114,7 +104,6 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupF
     __shared__ uint32_t wave_cov[RH_PU_BLOCK / 64];
     __shared__ uint32_t wave_max[RH_PU_BLOCK / 64];
     const uint64_t x = (uint64_t)blockIdx.x * RH_PU_BLOCK + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 a = make_uint4(0, 0, 0, 0);
     uint32_t d = 0;
     if (x < A.n) { a = A.alt[x]; d = A.depth[x]; }
@@ -124,11 +113,11 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupF
         const unsigned long long cov = __ballot(d != 0);
         uint32_t m = d;
         for (int k = 32; k; k >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, k));
-        if (lane == 0) { wave_cnt[wave] = (uint32_t)__popcll(mask); wave_cov[wave] = (uint32_t)__popcll(cov); wave_max[wave] = m; }
-        __syncthreads();
+        if ((threadIdx.x & 63u) == 0) { wave_cov[threadIdx.x >> 6] = (uint32_t)__popcll(cov); wave_max[threadIdx.x >> 6] = m; }
+        const uint32_t c = rh_block_count(mask, wave_cnt); // (its barrier is wave_cov's and wave_max's too)
         if (threadIdx.x == 0) {
-            uint32_t c = 0, v = 0, mx = 0;
-            for (uint32_t k = 0; k < RH_PU_BLOCK / 64; ++k) { c += wave_cnt[k]; v += wave_cov[k]; mx = max(mx, wave_max[k]); }
+            uint32_t v = 0, mx = 0;
+            for (uint32_t k = 0; k < RH_PU_BLOCK / 64; ++k) { v += wave_cov[k]; mx = max(mx, wave_max[k]); }
             A.blk[blockIdx.x] = c;
             if (blockIdx.x + 1 == gridDim.x) A.blk[gridDim.x] = 0;
             unsigned long long *line = A.fin + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
@@ -137,13 +126,8 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupF
         }
         return;
     }
-    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (!site) return;
-    uint64_t slot = A.blk_off[blockIdx.x];
-    for (uint32_t k = 0; k < wave; ++k) slot += wave_cnt[k];
-    slot += __popcll(mask & ((1ull << lane) - 1ull));
-    if (slot >= A.cap) return; // (cannot happen: the table is what the count saw)
+    const uint64_t slot = rh_emit_slot(mask, A.blk_off[blockIdx.x], wave_cnt);
+    if (!site || slot >= A.cap) return; // (the latter cannot happen: the table is what the count saw)
     const uint32_t ref = (uint32_t)(A.text[x >> 5] >> (62 - 2 * (x & 31))) & 3u;
     A.out[2 * slot] = make_uint4((uint32_t)x, d, a.x, a.y);
     A.out[2 * slot + 1] = make_uint4(a.z, a.w, ref, 0u);
@@ -189,15 +173,11 @@ void rh_pileup_end(real_hip_ctx *ctx)
 // asynchronous on the ctx's stream
 int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate)
 {
-    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
-                      offsetof(real_hip_pair, fileid) == 34 && offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
-                  "pileup_add_kernel reads words 2 and 4 of the record");
     const uint64_t n = b.n_reads;
     if (!n) return REAL_HIP_OK;
     PileupArgs A;
     memset(&A, 0, sizeof A);
-    A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p;
-    A.t.n = ctx->n_bases; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = ctx->fileid;
+    A.t = rh_dev_text(ctx, ctx->fileid);
     A.b = b;
     if (!ctx->pu_min_qual) A.b.qual = nullptr; // (not loaded)
     A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pu_min_qual;

@@ -1,8 +1,10 @@
-// read_walk.h -- a lane walks one placed read word by word against the 2-bit text: what pileup.hip (counts per text position)
-// and mismatch_list.hip (the list of one read) share.  32 bases per step, whatever the length (up to
-// REAL_HIP_MAX_PATL_LONG): no register array of the read.  No LDS, no scratch memory.
+// read_walk.h -- from a final record to a placement on the resident text (placed_read), and a lane's walk of the placed read
+// word by word against the 2-bit text: what pileup.hip (counts per text position), snp_call.hip (evidence per site) and
+// mismatch_list.hip (the list of one read) share.  32 bases per step, whatever the length (up to REAL_HIP_MAX_PATL_LONG):
+// no register array of the read.  No LDS, no scratch memory.
 #pragma once
 #include "match_common.h"
+#include "stage_common.h"
 
 // a read's bytes in place, a dword per request: the aligned dword that holds the first byte asked for and, where the request
 // straddles it and the row goes on, the next one.  Never a dword without a byte of the row in it (an aligned dword does not
@@ -72,44 +74,45 @@ static __device__ __forceinline__ uint32_t read_extent(const DevBatch &b, uint64
     return e >= start && e - start <= REAL_HIP_MAX_PATL_LONG ? (uint32_t)(e - start) : 0xffffffffu;
 }
 
-// Record i of a launch as a placement on the text t: single-end records `info`, or mate `mate` (0 = mate 1, 1 = mate 2) of the
-// real_hip_pair records `pairs`, read as five 8-byte words (insert_hist.hip).  A record of another state places nothing; then
-// one of another file id is flagged `other`; then one that ends behind the text (or holds more than 32 bits of position)
-// `bad`.  What pileup.hip and snp_call.hip share: the same records are skipped and counted in both.
+static_assert(RH_INFO_ST_SHIFT == ST_SHIFT && RH_INFO_ER_SHIFT == ER_SHIFT && RH_INFO_FI_SHIFT == FI_SHIFT && RH_INFO_POS_MASK == POS_MASK &&
+                  RH_INFO_STRAIGHT == ST_STRAIGHT && RH_INFO_REVERSE == ST_REVERSE,
+              "final_record.h reads the info word the matcher writes");
+
+// Record i of a launch as a placement on the text t, the one step from a record to a placement: single-end
+// records `info`, or mate `mate` (0 = mate 1, 1 = mate 2) of the real_hip_pair records `pairs`, read as five 8-byte words, and
+// -- where the pair's state is NoMatch and `singles` is not null -- the mate's own real_hip_single (a NonUnique pair places
+// nothing).  A record of another state places nothing; then one of another file id is flagged `other`; then one that ends
+// behind the text `bad`: one 64-bit comparison, which also catches the positions of an info word beyond 32 bits (t.n is
+// below 2^32: real_hip_set_text* refuse a longer text).  The same records are skipped and counted in every stage.
 struct PlacedRead {
     bool place, inv;   // a placement; on the reverse strand
     bool other, bad;   // no placement: a record of another file; one that ends behind the text
     uint32_t p, L;     // text position, length
+    uint32_t k;        // the record's mismatch count
     uint64_t start;    // first base in the batch
 };
 template <bool PAIRS>
-static __device__ __forceinline__ PlacedRead placed_read(const DevText &t, const DevBatch &b, const uint64_t *info, const uint2 *pairs, uint32_t mate,
-                                                         uint64_t i)
+static __device__ __forceinline__ PlacedRead placed_read(const DevText &t, const DevBatch &b, const uint64_t *info, const uint2 *pairs,
+                                                         const uint4 *singles, uint32_t mate, uint64_t i)
 {
-    PlacedRead r;
-    uint32_t file;
-    r.other = r.bad = false;
+    RhPlace c;
     if (PAIRS) {
         const uint2 pos = pairs[i * 5 + 2], tail = pairs[i * 5 + 4];
-        r.place = ((tail.y >> 16) & 0xffu) == REAL_HIP_PAIR_UNIQUE;
-        r.inv = (((tail.y >> 8) & 0xffu) != 0) != (mate != 0); // mate 2 has the other strand
-        file = (tail.x >> 16) & 0xffu;
-        r.p = mate ? pos.y : pos.x;
+        uint32_t state;
+        c = rh_place_pair(pos.x, pos.y, tail.x, tail.y, mate, &state);
+        if (state == REAL_HIP_PAIR_NOMATCH && singles) { const uint4 s = singles[i]; c = rh_place_single(s.z, s.w); }
     } else {
-        const uint64_t rec = info[i];
-        const uint32_t st = (uint32_t)(rec >> ST_SHIFT);
-        r.place = st == ST_STRAIGHT || st == ST_REVERSE;
-        r.inv = st == ST_REVERSE;
-        file = (uint32_t)(rec >> FI_SHIFT) & 63u;
-        const uint64_t p64 = rec & POS_MASK;
-        r.p = (uint32_t)p64;
-        if (r.place && file == t.fileid && p64 > 0xffffffffull) { r.place = false; r.bad = true; } // (35 bits of position, 32 of text)
+        c = rh_place_info(info[i]);
     }
-    if (r.place && file != t.fileid) { r.place = false; r.other = true; }
+    PlacedRead r;
+    r.inv = c.inv; r.k = c.k; r.p = (uint32_t)c.pos;
+    r.other = c.place && c.file != t.fileid;
+    r.place = c.place && !r.other;
+    r.bad = false;
     r.start = 0; r.L = 0;
     if (r.place) {
         r.L = read_extent(b, i, r.start);
-        if ((uint64_t)r.p + r.L > t.n) { r.place = false; r.bad = true; }
+        if (c.pos + r.L > t.n) { r.place = false; r.bad = true; }
     }
     return r;
 }

@@ -266,6 +266,44 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     if (!(ctx)) return REAL_HIP_E_INVALID;              \
     RH_HIP((ctx), hipSetDevice((ctx)->device));
 
+// every real_hip_*_stats_get: `what` is the stage's words for a wrong struct_size, `get` the stage's own read
+template <typename S>
+static int stats_get(real_hip_ctx *ctx, S *out, int reset, const char *what, int (*get)(real_hip_ctx *, S *, int))
+{
+    RH_ENTER(ctx);
+    if (out && out->struct_size != sizeof(S)) return rh_fail(ctx, REAL_HIP_E_INVALID, what, hipSuccess);
+    return get(ctx, out, reset);
+}
+// E_INVALID with the stage's prefix in front ("" : none)
+static int stage_invalid(real_hip_ctx *ctx, const char *stage, const char *what)
+{
+    return rh_fail(ctx, REAL_HIP_E_INVALID, (std::string(stage) + (*stage ? ": " : "") + what).c_str(), hipSuccess);
+}
+// The capacity protocol of a finished list of `total` records of `size` bytes at `src`: *n_out = total whatever happens next;
+// more than cap is E_OVERFLOW; then the copy.  `what` and `list` name the records and their list in the messages of `stage`.
+static int list_out(real_hip_ctx *ctx, bool finished, const char *stage, const char *what, const char *list, const void *src, uint64_t total, size_t size,
+                    void *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    if (!finished) return stage_invalid(ctx, stage, (std::string(what) + " before finish").c_str());
+    if (!n_out) return stage_invalid(ctx, stage, "null n_out");
+    *n_out = total;
+    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, (std::string(stage) + ": the " + list + " needs more room").c_str(), hipSuccess);
+    if (!total) return REAL_HIP_OK;
+    if (!out) return stage_invalid(ctx, stage, "null out");
+    RH_HIP(ctx, hipMemcpyAsync(out, src, (size_t)total * size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    return rh_sync_tail(ctx, REAL_HIP_OK);
+}
+// behind a finish: one that failed leaves nothing half-finished readable -- `release` what there is; the message of rc is kept
+static int finish_tail(real_hip_ctx *ctx, int rc, void (*release)(real_hip_ctx *))
+{
+    if (rc) {
+        const std::string msg = ctx->last_error;
+        release(ctx);
+        ctx->last_error = msg;
+    }
+    return rc;
+}
+
 extern "C" int real_hip_set_match_params(real_hip_ctx *ctx, uint32_t seedkmax, uint32_t totalkmax, uint32_t scores, double filter_mult)
 {
     if (!ctx) return REAL_HIP_E_INVALID;
@@ -845,19 +883,27 @@ static int search_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp
         return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "mate search: max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
     return REAL_HIP_OK;
 }
-// the two mates' batches: equal in n_reads and on_device; need_index: they are to be matched, text and index are set
-static int mate_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2], bool need_index)
+// the two mates' batches in every entry point that takes two: equal in n_reads and on_device; need_index: they are to be
+// matched, text and index are set.  `stage` is the prefix of the messages ("": none)
+static int mates_agree(real_hip_ctx *ctx, const char *stage, const real_hip_batch bv[2], bool need_index)
 {
-    if (bv[0].n_reads != bv[1].n_reads) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches hold different numbers of reads", hipSuccess);
-    if (bv[0].on_device != bv[1].on_device) return rh_fail(ctx, REAL_HIP_E_INVALID, "the two batches differ in on_device", hipSuccess);
+    if (bv[0].n_reads != bv[1].n_reads) return stage_invalid(ctx, stage, "the two batches hold different numbers of reads");
+    if (bv[0].on_device != bv[1].on_device) return stage_invalid(ctx, stage, "the two batches differ in on_device");
     if (need_index && (!ctx->have_text || !ctx->have_index)) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
     return REAL_HIP_OK;
+}
+// their views bv[], then that.  An entry point with a check of its own between the two steps (real_hip_pair_search: E_STATE
+// without a text; real_hip_mismatches_pairs: its outputs, *n_out = 0) makes the views itself and calls mates_agree
+static int mates_view(real_hip_ctx *ctx, const char *stage, const real_hip_batch *b1, const real_hip_batch *b2, bool need_index, real_hip_batch bv[2])
+{
+    int rc;
+    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1]))) return rc;
+    return mates_agree(ctx, stage, bv, need_index);
 }
 // what the mate search asks of them beyond that: no read longer than REAL_HIP_MAX_PATL
 static int search_batches_check(real_hip_ctx *ctx, const real_hip_batch bv[2])
 {
-    int rc = mate_batches_check(ctx, bv, false);
-    if (rc) return rc;
+    int rc;
     const uint64_t n = bv[0].n_reads;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one batch", hipSuccess);
     for (int m = 0; m < 2 && n; ++m) {
@@ -897,7 +943,7 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
     if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
     if (bv[0].on_device > 1) return rh_fail(ctx, REAL_HIP_E_INVALID, "real_hip_pair_search: on_device is 0 or 1", hipSuccess);
     if (!ctx->have_text) return rh_fail(ctx, REAL_HIP_E_STATE, "the text must be set", hipSuccess);
-    if ((rc = search_batches_check(ctx, bv))) return rc;
+    if ((rc = mates_agree(ctx, "", bv, false)) || (rc = search_batches_check(ctx, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
     if (!n) return REAL_HIP_OK;
     if (!off1 || !off2 || !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / pairs", hipSuccess);
@@ -961,9 +1007,7 @@ extern "C" int real_hip_single_hits(real_hip_ctx *ctx, const real_hip_hit *hits,
 
 extern "C" int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_single_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "single stats struct_size", hipSuccess);
-    return rh_single_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "single stats struct_size", rh_single_stats);
 }
 
 // ---- insert sizes (insert_hist.hip): staging as real_hip_pair_hits does it
@@ -996,9 +1040,7 @@ extern "C" int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair 
 
 extern "C" int real_hip_insert_stats_get(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_insert_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "insert stats struct_size", hipSuccess);
-    return rh_insert_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "insert stats struct_size", rh_insert_stats);
 }
 
 // the quartile rule on a histogram: host only, integers only (include/real_hip.h)
@@ -1051,6 +1093,38 @@ extern "C" int real_hip_pileup_begin(real_hip_ctx *ctx, const real_hip_pileup_pa
     return rh_pileup_begin(ctx, p->min_qual);
 }
 
+// Reads and the final records that place them, staged for the kernels: what real_hip_pileup_add*, real_hip_call_add* and
+// real_hip_mismatches* share.  bv[]: the views of the reads (mates == 1, with info) or of the two mates (mates == 2, with
+// pairs; mates_agree has checked them).  At most 2^32 reads, the null and alignment checks on the records, then the reads as a match stages
+// them into ctx->stage[m], then the records into `rec` where they are host memory, then the device views.  keep_qual: the
+// qualities are handed on whatever -q says; otherwise not at all.  n_reads == 0 is valid: nothing is copied.
+struct PlacedReads {
+    DevBatch b[2];
+    const uint64_t *info;
+    const real_hip_pair *pairs;
+};
+static int stage_placements(real_hip_ctx *ctx, const char *stage, const real_hip_batch bv[], int mates, const uint64_t *info, const real_hip_pair *pairs,
+                            DevBuf &rec, bool keep_qual, PlacedReads &p)
+{
+    const uint64_t n = bv[0].n_reads;
+    const bool dev = bv[0].on_device == 1;
+    if (n > 0xffffffffull) return stage_invalid(ctx, stage, "more than 2^32 reads in one call");
+    if (n && !(mates == 2 ? (const void *)pairs : (const void *)info)) return stage_invalid(ctx, stage, mates == 2 ? "null pairs" : "null info");
+    if (dev && ((uintptr_t)pairs & 7u)) return stage_invalid(ctx, stage, "the pair records must be 8-byte aligned");
+    int rc;
+    Staged st[2];
+    for (int m = 0; m < mates; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rc;
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    p.info = info; p.pairs = pairs;
+    if (n && (rc = mates == 2 ? io.in(rec, pairs, n, p.pairs) : io.in(rec, info, n, p.info))) return rc;
+    for (int m = 0; m < mates; ++m) {
+        p.b[m] = dev_batch(ctx, st[m], n);
+        p.b[m].qual = keep_qual ? st[m].qual : nullptr;
+    }
+    return REAL_HIP_OK;
+}
+
 // what real_hip_pileup_add* and real_hip_call_add* share: both hand the placements of a batch to a kernel of their own
 struct PlacementSink {
     const char *name;                    // the prefix of its messages
@@ -1058,56 +1132,17 @@ struct PlacementSink {
     DevBuf real_hip_ctx::*rec;           // the staged records when the caller's are host memory
     int (*launch)(real_hip_ctx *, const DevBatch &, const uint64_t *, const real_hip_pair *, uint32_t);
 };
-static int sink_invalid(real_hip_ctx *ctx, const PlacementSink &k, const char *what)
-{
-    return rh_fail(ctx, REAL_HIP_E_INVALID, (std::string(k.name) + ": " + what).c_str(), hipSuccess);
-}
-
-static int placements_add(real_hip_ctx *ctx, const PlacementSink &k, const real_hip_batch *b, const uint64_t *info)
-{
-    real_hip_batch bv;
-    int rc = batch_view(ctx, b, bv);
-    if (rc || (rc = k.check(ctx))) return rc;
-    const uint64_t n = bv.n_reads;
-    if (n > 0xffffffffull) return sink_invalid(ctx, k, "more than 2^32 reads in one call");
-    if (!n) return REAL_HIP_OK;
-    if (!info) return sink_invalid(ctx, k, "null info");
-    Staged s;
-    if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
-    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
-    const uint64_t *d_info = info;
-    rc = io.in(ctx->*k.rec, info, n, d_info);
-    if (!rc) {
-        DevBatch db = dev_batch(ctx, s, n);
-        db.qual = s.qual; // (the pileup's use of the qualities does not hang on -q)
-        rc = k.launch(ctx, db, d_info, nullptr, 0);
-    }
-    return rh_sync_tail(ctx, rc);
-}
-
-static int placements_add_pairs(real_hip_ctx *ctx, const PlacementSink &k, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
+// the placements of a batch (mates == 1: b1 and info) or of both mates of a batch of pairs (mates == 2: b1, b2 and pairs)
+static int placements_add(real_hip_ctx *ctx, const PlacementSink &k, int mates, const real_hip_batch *b1, const real_hip_batch *b2, const uint64_t *info,
+                          const real_hip_pair *pairs)
 {
     real_hip_batch bv[2];
-    int rc;
-    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1])) || (rc = k.check(ctx))) return rc;
-    if (bv[0].n_reads != bv[1].n_reads || bv[0].on_device != bv[1].on_device)
-        return sink_invalid(ctx, k, "the mates' batches must agree in n_reads and on_device");
-    const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return sink_invalid(ctx, k, "more than 2^32 reads in one call");
-    if (!n) return REAL_HIP_OK;
-    if (!pairs) return sink_invalid(ctx, k, "null pairs");
-    if (bv[0].on_device == 1 && ((uintptr_t)pairs & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the pair records must be 8-byte aligned", hipSuccess);
-    Staged st[2];
-    for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
-    const RhStaging io{ctx, bv[0].on_device != 1, ctx->stream, ctx->stream};
-    const real_hip_pair *d_pairs = pairs;
-    rc = io.in(ctx->*k.rec, pairs, n, d_pairs);
-    for (uint32_t m = 0; m < 2 && !rc; ++m) {
-        DevBatch db = dev_batch(ctx, st[m], n);
-        db.qual = st[m].qual;
-        rc = k.launch(ctx, db, nullptr, d_pairs, m);
-    }
+    int rc = mates == 2 ? mates_view(ctx, k.name, b1, b2, false, bv) : batch_view(ctx, b1, bv[0]);
+    if (rc || (rc = k.check(ctx))) return rc;
+    if (!bv[0].n_reads) return REAL_HIP_OK;
+    PlacedReads p;
+    rc = stage_placements(ctx, k.name, bv, mates, info, pairs, ctx->*k.rec, true, p);
+    for (int m = 0; m < mates && !rc; ++m) rc = k.launch(ctx, p.b[m], p.info, p.pairs, (uint32_t)m);
     return rh_sync_tail(ctx, rc);
 }
 
@@ -1116,13 +1151,13 @@ static const PlacementSink kPileupSink = {"pileup", pileup_add_check, &real_hip_
 extern "C" int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
 {
     RH_ENTER(ctx);
-    return placements_add(ctx, kPileupSink, b, info);
+    return placements_add(ctx, kPileupSink, 1, b, nullptr, info, nullptr);
 }
 
 extern "C" int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
 {
     RH_ENTER(ctx);
-    return placements_add_pairs(ctx, kPileupSink, b1, b2, pairs);
+    return placements_add(ctx, kPileupSink, 2, b1, b2, nullptr, pairs);
 }
 
 extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
@@ -1131,13 +1166,7 @@ extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
     if (ctx->pu_state != 1) return rh_fail(ctx, REAL_HIP_E_INVALID, ctx->pu_state ? "pileup: finish twice" : "pileup: finish without begin", hipSuccess);
     int rc = pileup_text_check(ctx);
     if (rc) return rc;
-    rc = rh_sync_tail(ctx, rh_pileup_finish(ctx, n_sites));
-    if (rc) { // nothing half-finished stays readable: the pileup is over, as after end (the message of rc is kept)
-        const std::string msg = ctx->last_error;
-        rh_pileup_end(ctx);
-        ctx->last_error = msg;
-    }
-    return rc;
+    return finish_tail(ctx, rh_sync_tail(ctx, rh_pileup_finish(ctx, n_sites)), rh_pileup_end); // (a failed finish: the pileup is over, as after end)
 }
 
 extern "C" int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device)
@@ -1155,16 +1184,7 @@ extern "C" int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t
 extern "C" int real_hip_pileup_sites(real_hip_ctx *ctx, real_hip_pileup_site *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: sites before finish", hipSuccess);
-    if (!n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null n_out", hipSuccess);
-    const uint64_t total = ctx->pu_n_sites;
-    *n_out = total;
-    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "pileup: the site list needs more room", hipSuccess);
-    if (!total) return REAL_HIP_OK;
-    if (!out) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null out", hipSuccess);
-    RH_HIP(ctx, hipMemcpyAsync(out, ctx->pu_sites.p, (size_t)total * sizeof(real_hip_pileup_site),
-                               on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    return rh_sync_tail(ctx, REAL_HIP_OK);
+    return list_out(ctx, ctx->pu_state == 2, "pileup", "sites", "site list", ctx->pu_sites.p, ctx->pu_n_sites, sizeof(real_hip_pileup_site), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_pileup_end(real_hip_ctx *ctx)
@@ -1176,9 +1196,7 @@ extern "C" int real_hip_pileup_end(real_hip_ctx *ctx)
 
 extern "C" int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_pileup_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup stats struct_size", hipSuccess);
-    return rh_pileup_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "pileup stats struct_size", rh_pileup_stats);
 }
 
 // ---- variant calls (snp_call.hip): on top of the finished pileup; the reads and records are staged as the pileup stages them
@@ -1208,13 +1226,13 @@ extern "C" int real_hip_call_begin(real_hip_ctx *ctx)
 extern "C" int real_hip_call_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
 {
     RH_ENTER(ctx);
-    return placements_add(ctx, kCallSink, b, info);
+    return placements_add(ctx, kCallSink, 1, b, nullptr, info, nullptr);
 }
 
 extern "C" int real_hip_call_add_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs)
 {
     RH_ENTER(ctx);
-    return placements_add_pairs(ctx, kCallSink, b1, b2, pairs);
+    return placements_add(ctx, kCallSink, 2, b1, b2, nullptr, pairs);
 }
 
 extern "C" int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_params *p, uint64_t *n_calls)
@@ -1224,38 +1242,19 @@ extern "C" int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_param
     if (ctx->cl_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: finish without begin", hipSuccess);
     int rc = call_pileup_check(ctx, "calls: finish without a finished pileup");
     if (rc) return rc;
-    rc = rh_sync_tail(ctx, rh_call_finish(ctx, p->min_call_qual, p->min_depth, n_calls));
-    if (rc) { // nothing half-finished stays readable (the message of rc is kept)
-        const std::string msg = ctx->last_error;
-        rh_call_release(ctx);
-        ctx->last_error = msg;
-    }
-    return rc;
-}
-
-// the capacity protocol of real_hip_pileup_sites over `total` records of `size` bytes at `src`
-static int call_list(real_hip_ctx *ctx, const char *what, const void *src, uint64_t total, size_t size, void *out, uint64_t cap, uint64_t *n_out, int on_device)
-{
-    if (ctx->cl_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, (std::string("calls: ") + what + " before finish").c_str(), hipSuccess);
-    if (!n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: null n_out", hipSuccess);
-    *n_out = total;
-    if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, (std::string("calls: the ") + what + " list needs more room").c_str(), hipSuccess);
-    if (!total) return REAL_HIP_OK;
-    if (!out) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: null out", hipSuccess);
-    RH_HIP(ctx, hipMemcpyAsync(out, src, (size_t)total * size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
-    return rh_sync_tail(ctx, REAL_HIP_OK);
+    return finish_tail(ctx, rh_sync_tail(ctx, rh_call_finish(ctx, p->min_call_qual, p->min_depth, n_calls)), rh_call_release);
 }
 
 extern "C" int real_hip_call_evidence(real_hip_ctx *ctx, real_hip_call_evidence_rec *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    return call_list(ctx, "evidence", ctx->cl_ev.p, ctx->pu_n_sites, sizeof(real_hip_call_evidence_rec), out, cap, n_out, on_device);
+    return list_out(ctx, ctx->cl_state == 2, "calls", "evidence", "evidence list", ctx->cl_ev.p, ctx->pu_n_sites, sizeof(real_hip_call_evidence_rec), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_call_variants(real_hip_ctx *ctx, real_hip_call *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    return call_list(ctx, "variants", ctx->cl_calls.p, ctx->cl_n_calls, sizeof(real_hip_call), out, cap, n_out, on_device);
+    return list_out(ctx, ctx->cl_state == 2, "calls", "variants", "variants list", ctx->cl_calls.p, ctx->cl_n_calls, sizeof(real_hip_call), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_call_end(real_hip_ctx *ctx)
@@ -1268,19 +1267,18 @@ extern "C" int real_hip_call_end(real_hip_ctx *ctx)
 
 extern "C" int real_hip_call_stats_get(real_hip_ctx *ctx, real_hip_call_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_call_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "call stats struct_size", hipSuccess);
-    return rh_call_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "call stats struct_size", rh_call_stats);
 }
 
 // ---- mismatch lists (mismatch_list.hip): the reads are staged as the pileup stages them, the records as the match's outputs;
 // count, then -- the total being known -- the overflow decision, then the lists (pair_all_run's protocol)
+static const char *const kMismatch = "mismatch lists";
 static int mismatch_outputs_check(real_hip_ctx *ctx, const real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, const uint64_t *mm_offsets, bool dev_out)
 {
-    if (!mm_offsets || !n_out) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null mm_offsets / n_out", hipSuccess);
+    if (!mm_offsets || !n_out) return stage_invalid(ctx, kMismatch, "null mm_offsets / n_out");
     *n_out = 0;
-    if (cap && !out) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null out", hipSuccess);
-    if (dev_out && ((uintptr_t)out & 3u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: out must be 4-byte aligned", hipSuccess);
+    if (cap && !out) return stage_invalid(ctx, kMismatch, "null out");
+    if (dev_out && ((uintptr_t)out & 3u)) return stage_invalid(ctx, kMismatch, "out must be 4-byte aligned");
     return REAL_HIP_OK;
 }
 static int mismatch_run(real_hip_ctx *ctx, const RhStaging &io, const RhMismatchLaunch l[], int n_launch, real_hip_mismatch *out, uint64_t cap,
@@ -1308,16 +1306,11 @@ extern "C" int real_hip_mismatches(real_hip_ctx *ctx, const real_hip_batch *b, c
     real_hip_batch bv;
     int rc = batch_view(ctx, b, bv);
     if (rc || (rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, bv.on_device == 1))) return rc;
-    const uint64_t n = bv.n_reads;
-    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: more than 2^32 reads in one call", hipSuccess);
-    if (n && !info) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null info", hipSuccess);
-    Staged s;
-    if ((rc = stage_batch(ctx, bv, s, ctx->stage[0], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    PlacedReads p;
+    if ((rc = stage_placements(ctx, kMismatch, &bv, 1, info, nullptr, ctx->mm_rec, false, p))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
-    RhMismatchLaunch l{dev_batch(ctx, s, n), info, nullptr, nullptr};
-    if (n) rc = io.in(ctx->mm_rec, info, n, l.info);
-    if (!rc) rc = mismatch_run(ctx, io, &l, 1, out, cap, n_out, mm_offsets);
-    return rh_sync_tail(ctx, rc);
+    const RhMismatchLaunch l{p.b[0], p.info, nullptr, nullptr};
+    return rh_sync_tail(ctx, mismatch_run(ctx, io, &l, 1, out, cap, n_out, mm_offsets)); // (n == 0 too: mm_offsets[0] is written)
 }
 
 extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs,
@@ -1329,22 +1322,14 @@ extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch
     int rc;
     if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1]))) return rc;
     const bool dev = bv[0].on_device == 1;
-    if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev))) return rc;
-    if (bv[0].n_reads != bv[1].n_reads || bv[0].on_device != bv[1].on_device)
-        return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: the mates' batches must agree in n_reads and on_device", hipSuccess);
-    if ((singles1 != nullptr) != (singles2 != nullptr)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: one singles array without the other", hipSuccess);
+    if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev)) || (rc = mates_agree(ctx, kMismatch, bv, false))) return rc;
+    if ((singles1 != nullptr) != (singles2 != nullptr)) return stage_invalid(ctx, kMismatch, "one singles array without the other");
+    if (dev && (((uintptr_t)singles1 | (uintptr_t)singles2) & 15u)) return stage_invalid(ctx, kMismatch, "the single records must be 16-byte aligned");
     const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: more than 2^32 reads in one call", hipSuccess);
-    if (n && !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: null pairs", hipSuccess);
-    if (dev && (((uintptr_t)pairs & 7u) || ((uintptr_t)singles1 & 15u) || ((uintptr_t)singles2 & 15u)))
-        return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch lists: the pair records must be 8-byte, the single records 16-byte aligned", hipSuccess);
-    Staged st[2];
-    for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    PlacedReads p;
+    if ((rc = stage_placements(ctx, kMismatch, bv, 2, nullptr, pairs, ctx->mm_rec, false, p))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
-    RhMismatchLaunch l[2] = {{dev_batch(ctx, st[0], n), nullptr, pairs, singles1}, {dev_batch(ctx, st[1], n), nullptr, pairs, singles2}};
-    if (n) rc = io.in(ctx->mm_rec, pairs, n, l[0].pairs);
-    l[1].pairs = l[0].pairs;
+    RhMismatchLaunch l[2] = {{p.b[0], nullptr, p.pairs, singles1}, {p.b[1], nullptr, p.pairs, singles2}};
     for (int m = 0; m < 2 && !rc && n && singles1; ++m) rc = io.in(ctx->mm_sg[m], m ? singles2 : singles1, n, l[m].singles);
     if (!rc) rc = mismatch_run(ctx, io, l, 2, out, cap, n_out, mm_offsets);
     return rh_sync_tail(ctx, rc);
@@ -1352,9 +1337,7 @@ extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch
 
 extern "C" int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_mismatch_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mismatch stats struct_size", hipSuccess);
-    return rh_mismatch_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "mismatch stats struct_size", rh_mismatch_stats);
 }
 
 // ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no
@@ -1441,9 +1424,7 @@ extern "C" int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_
 
 extern "C" int real_hip_dup_stats_get(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_dup_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicate stats struct_size", hipSuccess);
-    return rh_dup_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "duplicate stats struct_size", rh_dup_stats);
 }
 
 // matchAll of both mates of n fragments with the hits kept on the device: afterwards pair_hits[m] / pair_off[m] / pair_len[m]
@@ -1497,8 +1478,7 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
 {
     int rc;
     real_hip_batch bv[2];
-    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
-    if ((rc = mate_batches_check(ctx, bv, true))) return rc;
+    if ((rc = mates_view(ctx, "", batch1, batch2, true, bv))) return rc;
     if (sp && (rc = search_batches_check(ctx, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
     if (!n) return REAL_HIP_OK;
@@ -1558,16 +1538,12 @@ extern "C" int real_hip_match_pairs_singles(real_hip_ctx *ctx, const real_hip_ba
 
 extern "C" int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_mate_search_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "mate search stats struct_size", hipSuccess);
-    return rh_mate_search_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "mate search stats struct_size", rh_mate_search_stats);
 }
 
 extern "C" int real_hip_pair_stats_get(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_pair_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair stats struct_size", hipSuccess);
-    return rh_pair_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "pair stats struct_size", rh_pair_stats);
 }
 
 // ---- every concordant pair of a fragment (pair_all.hip) -----------------------------------------------------------
@@ -1643,8 +1619,7 @@ extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch 
     int rc = pair_params_check(ctx, pp);
     if (rc) return rc;
     real_hip_batch bv[2];
-    if ((rc = batch_view(ctx, batch1, bv[0])) || (rc = batch_view(ctx, batch2, bv[1]))) return rc;
-    if ((rc = mate_batches_check(ctx, bv, true))) return rc;
+    if ((rc = mates_view(ctx, "", batch1, batch2, true, bv))) return rc;
     const uint64_t n = bv[0].n_reads;
     const bool dev_out = bv[0].on_device == 1;
     bool done;
@@ -1657,9 +1632,7 @@ extern "C" int real_hip_match_pairs_all(real_hip_ctx *ctx, const real_hip_batch 
 
 extern "C" int real_hip_pair_all_stats_get(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset)
 {
-    RH_ENTER(ctx);
-    if (out && out->struct_size != sizeof(real_hip_pair_all_stats)) return rh_fail(ctx, REAL_HIP_E_INVALID, "pair all stats struct_size", hipSuccess);
-    return rh_pair_all_stats(ctx, out, reset);
+    return stats_get(ctx, out, reset, "pair all stats struct_size", rh_pair_all_stats);
 }
 
 // ---------------------------------------------------------------------------

@@ -8,7 +8,8 @@
 // index.  call_bitmap_kernel: one lane per bitmap word finds its first site by binary search in the (ascending) site list
 // and ORs its own bits together -- no atomics, no scan.
 //
-// call_add_kernel: one lane per read, the word-by-word walk of pileup_add_kernel (read_walk.h), but per turn of 32 bases
+// call_add_kernel: one lane per read, the placement and the word-by-word walk of pileup_add_kernel (read_walk.h: the same
+// records are placed, skipped and counted in both), but per turn of 32 bases
 // the lane first takes the 32 bitmap bits under the placement, funnel-shifted from at most two 64-bit words.  Most turns
 // find none and load nothing else: no read bases, no text (the calls need no text at all: the reference base is the site
 // record's).  For a set bit the lane takes the oriented base from the walk's oriented word, the quality byte (the reverse
@@ -23,7 +24,6 @@
 // stores.
 #include "real_hip_internal.h"
 #include "read_walk.h"
-#include "pair_state.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -55,7 +55,7 @@ struct CallArgs {
     DevText  t;
     DevBatch b;                    // the reads of this launch (mate `mate` of a pair launch)
     const uint64_t *info;          // single-end records, or
-    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (insert_hist.hip)
+    const uint2 *pairs;            // real_hip_pair records as five 8-byte words (final_record.h)
     uint32_t mate;                 // pair launches: 0 = mate 1, 1 = mate 2
     uint32_t min_qual;
     const uint64_t *bits;          // the site bitmap: n / 64 + 2 words
@@ -71,7 +71,7 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_add_kernel(const CallArgs A)
     const uint64_t i = (uint64_t)blockIdx.x * RH_CL_BLOCK + threadIdx.x;
     uint32_t placed = 0, other = 0, invalid = 0, sbases = 0, lowq = 0;
     if (i < A.b.n_reads) {
-        const PlacedRead r = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, A.mate, i);
+        const PlacedRead r = placed_read<PAIRS>(A.t, A.b, A.info, A.pairs, nullptr, A.mate, i);
         other = r.other; invalid = r.bad;
         if (r.place) {
             placed = 1;
@@ -106,17 +106,8 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_add_kernel(const CallArgs A)
             }
         }
     }
-    // the statistics: one sum per wave, added to a striped line
     uint32_t s[5] = {placed, other, invalid, sbases, lowq}; // (a wave's sums stay below 2^32: 64 reads of at most 2^14 bases)
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-        for (int d = 32; d; d >>= 1) s[k] += (uint32_t)__shfl_xor((int)s[k], d);
-    if ((threadIdx.x & 63u) == 0) {
-        unsigned long long *line = A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-            if (s[k]) atomicAdd(line + k, (unsigned long long)s[k]);
-    }
+    rh_stats_add(A.stats, s);
 }
 
 // ---- finish: the genotypes and the calls ----------------------------------------------------------------------------------
@@ -177,7 +168,6 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_sites_kernel(const CallFinAr
     __shared__ uint32_t wave_cnt[RH_CL_BLOCK / 64];
     __shared__ uint32_t wave_het[RH_CL_BLOCK / 64];
     const uint64_t s = (uint64_t)blockIdx.x * RH_CL_BLOCK + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint4 s0 = make_uint4(0, 0, 0, 0), s1 = s0, e0 = s0, e1 = s0;
     if (s < A.n_sites) { s0 = A.sites[2 * s]; s1 = A.sites[2 * s + 1]; e0 = A.ev[2 * s]; e1 = A.ev[2 * s + 1]; }
     const uint32_t cnt[4] = {e0.x, e0.y, e0.z, e0.w}, qsum[4] = {e1.x, e1.y, e1.z, e1.w};
@@ -188,11 +178,11 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_sites_kernel(const CallFinAr
     const unsigned long long mask = __ballot(call);
     if (!EMIT) {
         const unsigned long long het = __ballot(call && g.a1 != g.a2);
-        if (lane == 0) { wave_cnt[wave] = (uint32_t)__popcll(mask); wave_het[wave] = (uint32_t)__popcll(het); }
-        __syncthreads();
+        if ((threadIdx.x & 63u) == 0) wave_het[threadIdx.x >> 6] = (uint32_t)__popcll(het);
+        const uint32_t c = rh_block_count(mask, wave_cnt); // (its barrier is wave_het's too)
         if (threadIdx.x == 0) {
-            uint32_t c = 0, h = 0;
-            for (uint32_t k = 0; k < RH_CL_BLOCK / 64; ++k) { c += wave_cnt[k]; h += wave_het[k]; }
+            uint32_t h = 0;
+            for (uint32_t k = 0; k < RH_CL_BLOCK / 64; ++k) h += wave_het[k];
             A.blk[blockIdx.x] = c;
             if (blockIdx.x + 1 == gridDim.x) A.blk[gridDim.x] = 0;
             unsigned long long *line = A.fin + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16;
@@ -201,13 +191,8 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_sites_kernel(const CallFinAr
         }
         return;
     }
-    if (lane == 0) wave_cnt[wave] = (uint32_t)__popcll(mask);
-    __syncthreads();
-    if (!call) return;
-    uint64_t slot = A.blk_off[blockIdx.x];
-    for (uint32_t k = 0; k < wave; ++k) slot += wave_cnt[k];
-    slot += __popcll(mask & ((1ull << lane) - 1ull));
-    if (slot >= A.cap) return; // (cannot happen: the table is what the count saw)
+    const uint64_t slot = rh_emit_slot(mask, A.blk_off[blockIdx.x], wave_cnt);
+    if (!call || slot >= A.cap) return; // (the latter cannot happen: the table is what the count saw)
     A.out[2 * slot] = make_uint4(s0.x, s0.y, e0.x, e0.y);
     A.out[2 * slot + 1] = make_uint4(e0.z, e0.w, g.qual, ref | (g.a1 << 8) | (g.a2 << 16) | (g.gq << 24));
 }
@@ -255,15 +240,11 @@ int rh_call_begin(real_hip_ctx *ctx)
 
 int rh_launch_call_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate)
 {
-    static_assert(sizeof(real_hip_pair) == 40 && offsetof(real_hip_pair, pos1) == 16 && offsetof(real_hip_pair, frag) == 32 &&
-                      offsetof(real_hip_pair, fileid) == 34 && offsetof(real_hip_pair, inverted1) == 37 && offsetof(real_hip_pair, state) == 38,
-                  "placed_read reads words 2 and 4 of the record");
     const uint64_t n = b.n_reads;
     if (!n) return REAL_HIP_OK;
     CallArgs A;
     memset(&A, 0, sizeof A);
-    A.t.text = (const uint64_t *)ctx->text.p; A.t.wild = (const uint64_t *)ctx->wild.p;
-    A.t.n = ctx->n_bases; A.t.has_wild = ctx->n_wild ? 1 : 0; A.t.fileid = ctx->fileid;
+    A.t = rh_dev_text(ctx, ctx->fileid);
     A.b = b;
     A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pu_min_qual;
     A.bits = (const uint64_t *)ctx->cl_bits.p; A.rank = (const uint32_t *)ctx->cl_rank.p; A.ev = (uint32_t *)ctx->cl_ev.p;

@@ -8,7 +8,9 @@
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
-//   host_selftest lines <reads.fq> <outdir>       -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
+//   host_selftest records                         -> checks the decoders of the final records (csrc/final_record.h) against records written
+//       through the public structs, prints ok or the first disagreement
+//   host_selftest lines <reads.fq> <outdir>      -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
 //   host_selftest sam <dir> <fastq:0|1> <qoff> <scores:0|1> <paired:0|1> -> <dir>/block.sam chunk.sam: the -sam file of the reads <dir>/r1 (and r2)
 //       from the records in <dir> (names.txt: a line "file<TAB>start<TAB>name" per fragment and one "file<TAB>n<TAB>" behind a file's
 //       last; info.u64 score.f32, or pairs.bin s1.bin s2.bin; per genome file mm<fi>.bin moff<fi>.u64), formatted by Sam.hpp from
@@ -26,6 +28,7 @@
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "Sam.hpp"
+#include "final_record.h"
 #include "row_addr.h"
 #include <vector>
 
@@ -273,6 +276,64 @@ int main(int argc, char **argv)
             }
             std::cout << (bad ? "bad " : "ok ") << bad << std::endl;
             return bad ? 1 : 0;
+        }
+        if (cmd == "records" && argc == 2) {
+            // csrc/final_record.h as the library compiles it, against records written through the public structs and macros of
+            // real_hip.h (pairs, singles) and info words that Lines.hpp's unpack reads back as the fields they were made of
+            auto fail = [](const char *what, uint64_t a, uint64_t b, uint64_t c) { std::cout << "bad " << what << " " << a << " " << b << " " << c << std::endl; return 1; };
+            const uint32_t positions[3] = {0u, 1u, 0xffffffffu}, files[4] = {0, 1, 63, 255};
+            for (uint32_t state = 0; state < 3; ++state)
+                for (uint32_t inv1 = 0; inv1 < 2; ++inv1)
+                    for (uint32_t file : files)
+                        for (uint32_t p1 : positions)
+                            for (uint32_t p2 : positions) {
+                                real_hip_pair r;
+                                memset(&r, 0, sizeof r);
+                                r.best = -3.0; r.second = -5.0; r.score1 = 1.f; r.score2 = 1.f;
+                                r.pos1 = p1; r.pos2 = p2; r.frag = 0xfffe; r.fileid = (uint8_t)file; r.k1 = 3; r.k2 = 12;
+                                r.inverted1 = (uint8_t)inv1; r.state = (uint8_t)state; r.reserved = 0xff; // (reserved is 0 in real records: the decoders must not look)
+                                uint32_t w[10];
+                                memcpy(w, &r, sizeof r);
+                                const uint64_t id = (uint64_t)state << 40 | (uint64_t)inv1 << 32 | file;
+                                if (rh_pair_state(w[9]) != state || rh_pair_inverted1(w[9]) != (inv1 != 0) || rh_pair_fileid(w[8]) != file ||
+                                    rh_pair_k1(w[8]) != r.k1 || rh_pair_k2(w[9]) != r.k2) return fail("pair fields", id, p1, p2);
+                                for (uint32_t mate = 0; mate < 2; ++mate) {
+                                    uint32_t st = 99;
+                                    const RhPlace c = rh_place_pair(w[4], w[5], w[8], w[9], mate, &st);
+                                    if (st != state || c.place != (state == REAL_HIP_PAIR_UNIQUE) || c.inv != ((inv1 != 0) != (mate != 0)) || c.file != file ||
+                                        c.k != (mate ? r.k2 : r.k1) || c.pos != (mate ? p2 : p1)) return fail("pair mate", id, p1, p2);
+                                }
+                            }
+            for (uint32_t state = 0; state < 4; ++state) // every value REAL_HIP_SINGLE_STATE can give
+                for (uint32_t inv = 0; inv < 2; ++inv)
+                    for (uint32_t k = 0; k < 16; k += 15)
+                        for (uint32_t file : files)
+                            for (uint32_t p : positions) {
+                                real_hip_single s;
+                                memset(&s, 0, sizeof s);
+                                s.score = 1.f; s.second = -2.f; s.pos = p; s.frag = 0xfffe; s.fileid = (uint8_t)file;
+                                s.tag = (uint8_t)(k | inv << 4 | state << 5);
+                                if (REAL_HIP_SINGLE_K(s.tag) != k || REAL_HIP_SINGLE_INVERTED(s.tag) != inv || REAL_HIP_SINGLE_STATE(s.tag) != state) return fail("single tag", state, inv, k);
+                                uint32_t w[4];
+                                memcpy(w, &s, sizeof s);
+                                const RhPlace c = rh_place_single(w[2], w[3]);
+                                if (c.place != (state == REAL_HIP_PAIR_UNIQUE) || c.inv != (inv != 0) || c.file != file || c.k != k || c.pos != p)
+                                    return fail("single", (uint64_t)state << 8 | inv << 4 | k, file, p);
+                            }
+            const uint64_t ipos[4] = {0, 0xffffffffull, 1ull << 32, (1ull << 35) - 1};
+            for (uint64_t state = 0; state < 5; ++state)
+                for (uint64_t file = 0; file < 64; file += 63)
+                    for (uint64_t err = 0; err < 16; err += 15)
+                        for (uint64_t p : ipos) {
+                            const uint64_t rec = state << 61 | 0xfffeull << 45 | err << 41 | file << 35 | p;
+                            const Record u = unpack(rec);
+                            if (u.st != state || u.frag != 0xfffe || u.errors != err || u.file != file || u.pos != p) return fail("info word", state, file, p);
+                            const RhPlace c = rh_place_info(rec);
+                            if (c.place != (u.st == 1 || u.st == 2) || c.inv != (u.st == 2) || c.file != u.file || c.k != u.errors || c.pos != u.pos)
+                                return fail("info", state, file, p);
+                        }
+            std::cout << "ok" << std::endl;
+            return 0;
         }
         if (cmd == "lines" && argc == 4) {
             // Every read of a one-line-per-field FASTQ file formatted twice (Lines.hpp): from the host reader's blocks, and

@@ -174,3 +174,12 @@ def test_output_lines_from_blocks_and_from_text(selftest, tmp_path, threads, crl
     assert len(want) == 40 and max(len(w) for w in want) > 150
     for name in ("block.tsv", "chunk.tsv"):
         assert open(tmp_path / name, newline="").read().split("\n")[:-1] == want, name
+
+
+def test_final_record_decoders(selftest):
+    """csrc/final_record.h, the one decoder of info words, pair records and single records that the stages behind the matcher
+    share, compiled by the host compiler: `host_selftest records` checks it against records written through the public
+    structs and macros of real_hip.h -- every state, both strands, both mates, the file ids and positions at the ends of
+    their ranges -- and against info words as Lines.hpp's unpack reads them (35-bit positions included)."""
+    r = subprocess.run([selftest, "records"], stdout=subprocess.PIPE, universal_newlines=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
