@@ -130,7 +130,7 @@ def main():
     nout = C.c_uint64(0)
     out = torch.zeros(1, dtype=torch.int32, device=dev)
     for fmt, b in (("bytes", bases), ("packed", packed)):
-        rb = p._pileup_batch(b, None, None, patl, n, 0, fmt == "packed", None, False)
+        rb = p._read_batch(b, None, patl=patl, n_reads=n, packed=fmt == "packed")
         rc = p._L.real_hip_mismatches(p._h, C.byref(rb), info.data_ptr(), out.data_ptr(), 0, C.byref(nout), off.data_ptr())
         assert rc in (rlib.REAL_HIP_OK, rlib.REAL_HIP_E_OVERFLOW), rc      # cap 0: the count alone
         total = int(nout.value)

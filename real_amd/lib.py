@@ -57,6 +57,22 @@ ABI_SYMBOLS = [
 ]
 
 
+def sized(struct, **fields):
+    """a struct of the ABI with struct_size set and the fields given"""
+    return struct(struct_size=C.sizeof(struct), **fields)
+
+
+def _stats_struct(name: str, fields):
+    """a statistics struct of the ABI: struct_size, reserved, then the counts (uint64) and the times (*_ms, double)"""
+    return type(name, (C.Structure,), {"_fields_": [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] +
+                                                   [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in fields]})
+
+
+def stats_fields(struct):
+    """the names a statistics struct reports: everything behind struct_size, reserved"""
+    return tuple(k for k, _ in struct._fields_[2:])
+
+
 class RealHipParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("seedl", C.c_uint32), ("seedkmax", C.c_uint32),
                 ("totalkmax", C.c_uint32), ("scores", C.c_uint32), ("prefix_bits", C.c_uint32),
@@ -77,10 +93,7 @@ class RealHipParsed(C.Structure):
                 ("id_start", C.c_void_p), ("id_len", C.c_void_p)]
 
 
-class RealHipBuildStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("wall_ms", C.c_double), ("kernel_ms", C.c_double),
-                ("alloc_ms", C.c_double), ("free_ms", C.c_double), ("alloc_bytes", C.c_uint64), ("alloc_calls", C.c_uint64),
-                ("free_calls", C.c_uint64)]
+RealHipBuildStats = _stats_struct("RealHipBuildStats", ("wall_ms", "kernel_ms", "alloc_ms", "free_ms", "alloc_bytes", "alloc_calls", "free_calls"))
 
 
 class RealHipCounters(C.Structure):
@@ -96,29 +109,8 @@ class RealHipPairParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_insert", C.c_uint32), ("max_insert", C.c_uint32), ("orientation", C.c_uint32)]
 
 
-class RealHipPairStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("pairs", C.c_uint64), ("products", C.c_uint64),
-                ("handed_over", C.c_uint64)]
-
-
 class RealHipMateSearchParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_anchors", C.c_uint32), ("reserved", C.c_uint32 * 2)]
-
-
-class RealHipMateSearchStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fragments", C.c_uint64), ("anchors", C.c_uint64),
-                ("anchors_skipped", C.c_uint64), ("positions", C.c_uint64), ("placements", C.c_uint64), ("launches", C.c_uint64),
-                ("kernel_ms", C.c_double)]
-
-
-class RealHipPairAllStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("fragments", C.c_uint64), ("products", C.c_uint64),
-                ("pairs_out", C.c_uint64), ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
-
-
-class RealHipSingleStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("reads", C.c_uint64), ("hits", C.c_uint64),
-                ("handed_over", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
 
 
 class RealHipInsertEstimate(C.Structure):
@@ -126,9 +118,13 @@ class RealHipInsertEstimate(C.Structure):
                 ("q3", C.c_uint32), ("low", C.c_uint32), ("high", C.c_uint32), ("pad", C.c_uint32)]
 
 
-class RealHipInsertStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("records", C.c_uint64), ("counted", C.c_uint64),
-                ("overflow", C.c_uint64), ("invalid", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+# the work of the paired-end stages (real_hip_*_stats)
+RealHipPairStats = _stats_struct("RealHipPairStats", ("pairs", "products", "handed_over"))
+RealHipMateSearchStats = _stats_struct("RealHipMateSearchStats", ("fragments", "anchors", "anchors_skipped", "positions", "placements",
+                                                                  "launches", "kernel_ms"))
+RealHipPairAllStats = _stats_struct("RealHipPairAllStats", ("fragments", "products", "pairs_out", "handed_over", "launches", "kernel_ms"))
+RealHipSingleStats = _stats_struct("RealHipSingleStats", ("reads", "hits", "handed_over", "launches", "kernel_ms"))
+RealHipInsertStats = _stats_struct("RealHipInsertStats", ("records", "counted", "overflow", "invalid", "launches", "kernel_ms"))
 
 
 class RealHipPileupParams(C.Structure):
@@ -141,16 +137,12 @@ class RealHipPileupSite(C.Structure):
     _fields_ = [("pos", C.c_uint32), ("depth", C.c_uint32), ("alt", C.c_uint32 * 4), ("ref", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-PILEUP_SITE_DTYPE = np.dtype([("pos", "<u4"), ("depth", "<u4"), ("alt", "<u4", (4,)), ("ref", "<u4"), ("reserved", "<u4")])
-assert PILEUP_SITE_DTYPE.itemsize == 32 and C.sizeof(RealHipPileupSite) == 32
+PILEUP_SITE_DTYPE = np.dtype(RealHipPileupSite)
+assert PILEUP_SITE_DTYPE.itemsize == 32
 
 PILEUP_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mismatches", "low_qual", "n_dropped", "covered", "sites",
                        "max_depth", "launches", "kernel_ms")
-
-
-class RealHipPileupStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
-               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in PILEUP_STATS_FIELDS]
+RealHipPileupStats = _stats_struct("RealHipPileupStats", PILEUP_STATS_FIELDS)
 
 
 class RealHipCallParams(C.Structure):
@@ -165,11 +157,7 @@ CALL_DTYPE = np.dtype([("pos", "<u4"), ("depth", "<u4"), ("cnt", "<u4", (4,)), (
 assert CALL_EVIDENCE_DTYPE.itemsize == 32 and CALL_DTYPE.itemsize == 32
 
 CALL_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "site_bases", "low_qual", "calls", "het", "hom", "launches", "kernel_ms")
-
-
-class RealHipCallStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
-               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in CALL_STATS_FIELDS]
+RealHipCallStats = _stats_struct("RealHipCallStats", CALL_STATS_FIELDS)
 
 
 class RealHipMismatch(C.Structure):
@@ -177,15 +165,11 @@ class RealHipMismatch(C.Structure):
     _fields_ = [("off", C.c_uint16), ("ref", C.c_uint8), ("base", C.c_uint8)]
 
 
-MISMATCH_DTYPE = np.dtype([("off", "<u2"), ("ref", "u1"), ("base", "u1")])
-assert MISMATCH_DTYPE.itemsize == 4 and C.sizeof(RealHipMismatch) == 4
+MISMATCH_DTYPE = np.dtype(RealHipMismatch)
+assert MISMATCH_DTYPE.itemsize == 4
 
 MISMATCH_STATS_FIELDS = ("reads", "placed", "other_file", "invalid", "bases", "mismatches", "on_n", "disagree", "launches", "kernel_ms")
-
-
-class RealHipMismatchStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
-               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in MISMATCH_STATS_FIELDS]
+RealHipMismatchStats = _stats_struct("RealHipMismatchStats", MISMATCH_STATS_FIELDS)
 
 
 class RealHipReadSum(C.Structure):
@@ -193,15 +177,11 @@ class RealHipReadSum(C.Structure):
     _fields_ = [("len", C.c_uint32), ("qsum", C.c_uint32)]
 
 
-READ_SUM_DTYPE = np.dtype([("len", "<u4"), ("qsum", "<u4")])
-assert READ_SUM_DTYPE.itemsize == 8 and C.sizeof(RealHipReadSum) == 8
+READ_SUM_DTYPE = np.dtype(RealHipReadSum)
+assert READ_SUM_DTYPE.itemsize == 8
 
 DUP_STATS_FIELDS = ("reads", "placed", "groups", "duplicates", "launches", "kernel_ms")
-
-
-class RealHipDupStats(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32)] + \
-               [(k, C.c_double if k.endswith("_ms") else C.c_uint64) for k in DUP_STATS_FIELDS]
+RealHipDupStats = _stats_struct("RealHipDupStats", DUP_STATS_FIELDS)
 
 
 class RealHipPairHit(C.Structure):
@@ -211,9 +191,8 @@ class RealHipPairHit(C.Structure):
                 ("inverted1", C.c_uint8), ("k1", C.c_uint8), ("k2", C.c_uint8), ("reserved", C.c_uint16)]
 
 
-PAIR_HIT_DTYPE = np.dtype([("pair", "<u4"), ("pos1", "<u4"), ("pos2", "<u4"), ("outer", "<u4"), ("score1", "<f4"), ("score2", "<f4"),
-                           ("frag", "<u2"), ("fileid", "u1"), ("inverted1", "u1"), ("k1", "u1"), ("k2", "u1"), ("reserved", "<u2")])
-assert PAIR_HIT_DTYPE.itemsize == 32 and C.sizeof(RealHipPairHit) == 32
+PAIR_HIT_DTYPE = np.dtype(RealHipPairHit)
+assert PAIR_HIT_DTYPE.itemsize == 32
 
 # real_hip_pair: the in/out record of one fragment
 PAIR_DTYPE = np.dtype([("best", "<f8"), ("second", "<f8"), ("pos1", "<u4"), ("pos2", "<u4"), ("score1", "<f4"), ("score2", "<f4"),
@@ -261,88 +240,85 @@ def load():
         raise RealHipError(REAL_HIP_E_DEVICE, "libreal_hip.so is not built: run __graft_entry__.build() "
                                               "(make -C real_amd/csrc); there is no CPU fallback")
     L = C.CDLL(LIB_PATH)
-    vp, u64, u32 = C.c_void_p, C.c_uint64, C.c_uint32
+    vp, u64, u32, ci = C.c_void_p, C.c_uint64, C.c_uint32, C.c_int
+    pu64, batch, pairp, searchp = C.POINTER(u64), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), C.POINTER(RealHipMateSearchParams)
     L.real_hip_scoring_table.argtypes = [C.c_double] * 5 + [vp]
     L.real_hip_scoring_table.restype = None
     L.real_hip_create.argtypes = [C.POINTER(vp), C.POINTER(RealHipParams)]
     L.real_hip_destroy.argtypes = [vp]
     L.real_hip_destroy.restype = None
-    L.real_hip_strerror.argtypes = [C.c_int]
+    L.real_hip_strerror.argtypes = [ci]
     L.real_hip_strerror.restype = C.c_char_p
     L.real_hip_last_error.argtypes = [vp]
     L.real_hip_last_error.restype = C.c_char_p
     L.real_hip_set_match_params.argtypes = [vp, u32, u32, u32, C.c_double]
     L.real_hip_wait_event.argtypes = [vp, vp]
-    L.real_hip_device_memory.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.real_hip_device_memory.argtypes = [vp, pu64, pu64]
     L.real_hip_set_text.argtypes = [vp, u32, vp, vp, u64, vp, u32]
-    L.real_hip_set_text_symbols.argtypes = [vp, u32, vp, u64, C.c_int, vp, u32]
+    L.real_hip_set_text_symbols.argtypes = [vp, u32, vp, u64, ci, vp, u32]
     L.real_hip_set_index_block.argtypes = [vp, u64, C.POINTER(vp), C.POINTER(vp)]
-    L.real_hip_build_index_block.argtypes = [vp, u64, u64, C.POINTER(u64), C.POINTER(C.c_int)]
-    L.real_hip_index_build_stats.argtypes = [vp, C.POINTER(RealHipBuildStats), C.c_int]
-    L.real_hip_index_info.argtypes = [vp, C.POINTER(u64), C.POINTER(u32)]
+    L.real_hip_build_index_block.argtypes = [vp, u64, u64, pu64, C.POINTER(C.c_int)]
+    L.real_hip_index_build_stats.argtypes = [vp, C.POINTER(RealHipBuildStats), ci]
+    L.real_hip_index_info.argtypes = [vp, pu64, C.POINTER(u32)]
     L.real_hip_index_table_kind.argtypes = [vp, C.POINTER(u32)]
-    L.real_hip_parse_reads.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.c_int, C.POINTER(RealHipParsed)]
+    L.real_hip_parse_reads.argtypes = [vp, vp, u64, ci, ci, ci, C.POINTER(RealHipParsed)]
     L.real_hip_download.argtypes = [vp, vp, vp, C.c_size_t]
-    L.real_hip_index_download.argtypes = [vp, C.c_int, vp, vp]
-    L.real_hip_index_export.argtypes = [vp, C.c_int, vp, vp]
-    L.real_hip_match_unique.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp]
-    L.real_hip_match_unique_submit.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp, u32, C.c_int]
+    L.real_hip_index_download.argtypes = [vp, ci, vp, vp]
+    L.real_hip_index_export.argtypes = [vp, ci, vp, vp]
+    L.real_hip_match_unique.argtypes = [vp, batch, vp, vp]
+    L.real_hip_match_unique_submit.argtypes = [vp, batch, vp, vp, u32, ci]
     L.real_hip_wait.argtypes = [vp, u32]
     L.real_hip_host_alloc.argtypes = [C.c_size_t]
     L.real_hip_host_alloc.restype = vp
     L.real_hip_host_free.argtypes = [vp]
     L.real_hip_host_free.restype = None
     L.real_hip_comm_id.argtypes = [vp]
-    L.real_hip_comm_init.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.real_hip_comm_init.argtypes = [vp, vp, ci, ci]
     L.real_hip_comm_destroy.argtypes = [vp]
-    L.real_hip_gather_records.argtypes = [vp, C.c_int, vp, vp, u64, vp, vp, u64, C.POINTER(u64)]
-    L.real_hip_gather_hits.argtypes = [vp, C.c_int, vp, vp, u64, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(u64)]
-    L.real_hip_match_all.argtypes = [vp, C.POINTER(RealHipBatch), vp, u64, C.POINTER(u64), vp]
-    L.real_hip_pair_hits.argtypes = [vp, C.POINTER(RealHipPairParams), vp, vp, vp, vp, vp, vp, u64, u32, C.c_int, C.c_int, vp]
-    L.real_hip_match_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp]
-    L.real_hip_pair_stats_get.argtypes = [vp, C.POINTER(RealHipPairStats), C.c_int]
-    L.real_hip_pair_search.argtypes = [vp, C.POINTER(RealHipPairParams), C.POINTER(RealHipMateSearchParams), C.POINTER(RealHipBatch),
-                                       C.POINTER(RealHipBatch), vp, vp, vp, vp, u32, C.c_int, vp]
-    L.real_hip_match_pairs_search.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
-                                              C.POINTER(RealHipMateSearchParams), vp]
-    L.real_hip_mate_search_stats_get.argtypes = [vp, C.POINTER(RealHipMateSearchStats), C.c_int]
-    L.real_hip_pair_all_hits.argtypes = [vp, C.POINTER(RealHipPairParams), vp, vp, vp, vp, vp, vp, u64, u32, C.c_int, vp, u64, C.POINTER(u64), vp]
-    L.real_hip_match_pairs_all.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams), vp, u64,
-                                           C.POINTER(u64), vp]
-    L.real_hip_pair_all_stats_get.argtypes = [vp, C.POINTER(RealHipPairAllStats), C.c_int]
-    L.real_hip_single_hits.argtypes = [vp, vp, vp, vp, u64, u32, C.c_int, C.c_int, vp]
-    L.real_hip_match_pairs_singles.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), C.POINTER(RealHipPairParams),
-                                               C.POINTER(RealHipMateSearchParams), vp, vp, vp]
-    L.real_hip_single_stats_get.argtypes = [vp, C.POINTER(RealHipSingleStats), C.c_int]
-    L.real_hip_pair_insert_hist.argtypes = [vp, vp, vp, vp, u64, C.c_int, C.c_int, u32, vp]
+    L.real_hip_gather_records.argtypes = [vp, ci, vp, vp, u64, vp, vp, u64, pu64]
+    L.real_hip_gather_hits.argtypes = [vp, ci, vp, vp, u64, u64, vp, u64, vp, u64, pu64, pu64]
+    L.real_hip_match_all.argtypes = [vp, batch, vp, u64, pu64, vp]
+    L.real_hip_pair_hits.argtypes = [vp, pairp, vp, vp, vp, vp, vp, vp, u64, u32, ci, ci, vp]
+    L.real_hip_match_pairs.argtypes = [vp, batch, batch, pairp, vp]
+    L.real_hip_pair_stats_get.argtypes = [vp, C.POINTER(RealHipPairStats), ci]
+    L.real_hip_pair_search.argtypes = [vp, pairp, searchp, batch, batch, vp, vp, vp, vp, u32, ci, vp]
+    L.real_hip_match_pairs_search.argtypes = [vp, batch, batch, pairp, searchp, vp]
+    L.real_hip_mate_search_stats_get.argtypes = [vp, C.POINTER(RealHipMateSearchStats), ci]
+    L.real_hip_pair_all_hits.argtypes = [vp, pairp, vp, vp, vp, vp, vp, vp, u64, u32, ci, vp, u64, pu64, vp]
+    L.real_hip_match_pairs_all.argtypes = [vp, batch, batch, pairp, vp, u64, pu64, vp]
+    L.real_hip_pair_all_stats_get.argtypes = [vp, C.POINTER(RealHipPairAllStats), ci]
+    L.real_hip_single_hits.argtypes = [vp, vp, vp, vp, u64, u32, ci, ci, vp]
+    L.real_hip_match_pairs_singles.argtypes = [vp, batch, batch, pairp, searchp, vp, vp, vp]
+    L.real_hip_single_stats_get.argtypes = [vp, C.POINTER(RealHipSingleStats), ci]
+    L.real_hip_pair_insert_hist.argtypes = [vp, vp, vp, vp, u64, ci, ci, u32, vp]
     L.real_hip_insert_bounds.argtypes = [vp, u32, u64, u32, C.POINTER(RealHipInsertEstimate)]
-    L.real_hip_insert_stats_get.argtypes = [vp, C.POINTER(RealHipInsertStats), C.c_int]
+    L.real_hip_insert_stats_get.argtypes = [vp, C.POINTER(RealHipInsertStats), ci]
     L.real_hip_pileup_begin.argtypes = [vp, C.POINTER(RealHipPileupParams)]
-    L.real_hip_pileup_add.argtypes = [vp, C.POINTER(RealHipBatch), vp]
-    L.real_hip_pileup_add_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp]
-    L.real_hip_pileup_finish.argtypes = [vp, C.POINTER(u64)]
-    L.real_hip_pileup_depth.argtypes = [vp, u64, u64, vp, C.c_int]
-    L.real_hip_pileup_sites.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
+    L.real_hip_pileup_add.argtypes = [vp, batch, vp]
+    L.real_hip_pileup_add_pairs.argtypes = [vp, batch, batch, vp]
+    L.real_hip_pileup_finish.argtypes = [vp, pu64]
+    L.real_hip_pileup_depth.argtypes = [vp, u64, u64, vp, ci]
+    L.real_hip_pileup_sites.argtypes = [vp, vp, u64, pu64, ci]
     L.real_hip_pileup_end.argtypes = [vp]
-    L.real_hip_pileup_stats_get.argtypes = [vp, C.POINTER(RealHipPileupStats), C.c_int]
+    L.real_hip_pileup_stats_get.argtypes = [vp, C.POINTER(RealHipPileupStats), ci]
     L.real_hip_call_begin.argtypes = [vp]
-    L.real_hip_call_add.argtypes = [vp, C.POINTER(RealHipBatch), vp]
-    L.real_hip_call_add_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp]
-    L.real_hip_call_finish.argtypes = [vp, C.POINTER(RealHipCallParams), C.POINTER(u64)]
-    L.real_hip_call_evidence.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
-    L.real_hip_call_variants.argtypes = [vp, vp, u64, C.POINTER(u64), C.c_int]
+    L.real_hip_call_add.argtypes = [vp, batch, vp]
+    L.real_hip_call_add_pairs.argtypes = [vp, batch, batch, vp]
+    L.real_hip_call_finish.argtypes = [vp, C.POINTER(RealHipCallParams), pu64]
+    L.real_hip_call_evidence.argtypes = [vp, vp, u64, pu64, ci]
+    L.real_hip_call_variants.argtypes = [vp, vp, u64, pu64, ci]
     L.real_hip_call_end.argtypes = [vp]
-    L.real_hip_call_stats_get.argtypes = [vp, C.POINTER(RealHipCallStats), C.c_int]
-    L.real_hip_mismatches.argtypes = [vp, C.POINTER(RealHipBatch), vp, vp, u64, C.POINTER(u64), vp]
-    L.real_hip_mismatches_pairs.argtypes = [vp, C.POINTER(RealHipBatch), C.POINTER(RealHipBatch), vp, vp, vp, vp, u64, C.POINTER(u64), vp]
-    L.real_hip_mismatch_stats_get.argtypes = [vp, C.POINTER(RealHipMismatchStats), C.c_int]
-    L.real_hip_read_summary.argtypes = [vp, C.POINTER(RealHipBatch), u32, vp]
-    L.real_hip_mark_duplicates.argtypes = [vp, vp, vp, u64, C.c_int, vp]
-    L.real_hip_mark_duplicates_pairs.argtypes = [vp, vp, vp, vp, u64, C.c_int, vp]
-    L.real_hip_dup_stats_get.argtypes = [vp, C.POINTER(RealHipDupStats), C.c_int]
-    L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), C.c_int]
-    L.real_hip_kernel_time.argtypes = [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(u64), C.c_int]
-    L.real_hip_timing_enable.argtypes = [vp, C.c_int]
+    L.real_hip_call_stats_get.argtypes = [vp, C.POINTER(RealHipCallStats), ci]
+    L.real_hip_mismatches.argtypes = [vp, batch, vp, vp, u64, pu64, vp]
+    L.real_hip_mismatches_pairs.argtypes = [vp, batch, batch, vp, vp, vp, vp, u64, pu64, vp]
+    L.real_hip_mismatch_stats_get.argtypes = [vp, C.POINTER(RealHipMismatchStats), ci]
+    L.real_hip_read_summary.argtypes = [vp, batch, u32, vp]
+    L.real_hip_mark_duplicates.argtypes = [vp, vp, vp, u64, ci, vp]
+    L.real_hip_mark_duplicates_pairs.argtypes = [vp, vp, vp, vp, u64, ci, vp]
+    L.real_hip_dup_stats_get.argtypes = [vp, C.POINTER(RealHipDupStats), ci]
+    L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
+    L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
+    L.real_hip_timing_enable.argtypes = [vp, ci]
     _lib = L
     return L
 

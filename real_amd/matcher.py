@@ -181,6 +181,37 @@ def unpack_info(info: np.ndarray):
     return state, frag, err, fid, pos
 
 
+def _start_or_fold(records, fresh: Optional[bool], on_device: bool, new, what: str = "records"):
+    """In/out records across genome files -> (records, fresh).  None starts them: new() on the host (device inputs need the
+    caller's tensor), and the call is fresh; given records are folded into unless fresh says they are output only."""
+    if fresh is None:
+        fresh = records is None
+    if records is None:
+        if on_device:
+            raise ValueError("device inputs need a device tensor for the %s" % what)
+        records = new()
+    return records, bool(fresh)
+
+
+def _held_lists(mates, differ: str, batch: Optional[RealHipBatch] = None):
+    """Hit lists the caller holds, one (hits, offsets, lengths or None) per mate -> (on_device, n, the lists as the library
+    reads them): lib.HIT_DTYPE / uint64 / uint32 unless they are device tensors, all describing n reads, else
+    ValueError(differ).  Where they lie and n are the batch's when they come with one, else the first offsets'."""
+    on_device = bool(batch.on_device if batch is not None else getattr(mates[0][1], "is_cuda", False))
+    n = None if batch is None else int(batch.n_reads)
+    out = []
+    for hits, off, lens in mates:
+        if not on_device:
+            hits, off = np.ascontiguousarray(hits, dtype=HIT_DTYPE), np.ascontiguousarray(off, dtype=np.uint64)
+            lens = None if lens is None else np.ascontiguousarray(lens, dtype=np.uint32)
+        if n is None:
+            n = int(off.shape[0]) - 1
+        if int(off.shape[0]) - 1 != n or (lens is not None and int(lens.shape[0]) != n):
+            raise ValueError(differ)
+        out.append((hits, off, lens))
+    return on_device, n, out
+
+
 class HipMatcher:
     """One context on one MI355X: resident text + index block + matching calls."""
 
@@ -188,14 +219,10 @@ class HipMatcher:
                  table_kind: int = 0):
         self.opts = opts
         self._L = _lib.load()
-        p = RealHipParams()
-        p.struct_size = C.sizeof(RealHipParams)
-        p.seedl, p.seedkmax, p.totalkmax = opts.seedl, opts.seedkmax, opts.totalkmax
-        p.scores = int(bool(opts.scores))
-        p.prefix_bits = prefix_bits
-        p.table_kind = table_kind          # request: 0 auto, 1 bucket starts only, 2 directory entries, 3 bucket rows (real_hip.h)
-        p.device = device
-        p.filter_mult = opts.filter_mult
+        self._pinned = []                  # what host_alloc handed out: freed with the matcher
+        # table_kind is a request: 0 auto, 1 bucket starts only, 2 directory entries, 3 bucket rows (real_hip.h)
+        p = _lib.sized(RealHipParams, seedl=opts.seedl, seedkmax=opts.seedkmax, totalkmax=opts.totalkmax, scores=int(bool(opts.scores)),
+                       prefix_bits=prefix_bits, table_kind=table_kind, device=device, filter_mult=opts.filter_mult)
         if LL is None:
             LL = _lib.scoring_table(opts.similarity, opts.gc, opts.trans, opts.err, opts.gcmut_bias)
         self.LL = np.ascontiguousarray(LL, dtype=np.float64)
@@ -274,17 +301,15 @@ class HipMatcher:
         self._refresh_index_info()
         return int(n.value), bool(nxt.value)
 
-    def _stats(self, struct, entry, fields: Sequence[str], reset: bool) -> dict:
-        """one read of a statistics struct of the ABI: the named fields, times (*_ms) as float, counts as int"""
-        st = struct()
-        st.struct_size = C.sizeof(struct)
+    def _stats(self, struct, entry, reset: bool) -> dict:
+        """one read of a statistics struct of the ABI: every field the struct names, times (*_ms) as float, counts as int"""
+        st = _lib.sized(struct)
         self._check(entry(self._h, C.byref(st), int(reset)))
-        return {k: (float if k.endswith("_ms") else int)(getattr(st, k)) for k in fields}
+        return {k: (float if k.endswith("_ms") else int)(getattr(st, k)) for k in _lib.stats_fields(struct)}
 
     def index_build_stats(self, reset: bool = False) -> dict:
         """where the wall time of this context's index builds went (real_hip_index_build_stats)"""
-        return self._stats(_lib.RealHipBuildStats, self._L.real_hip_index_build_stats,
-                           ("wall_ms", "kernel_ms", "alloc_ms", "free_ms", "alloc_bytes", "alloc_calls", "free_calls"), reset)
+        return self._stats(_lib.RealHipBuildStats, self._L.real_hip_index_build_stats, reset)
 
     def _refresh_index_info(self):
         n = C.c_uint64(0)
@@ -325,17 +350,66 @@ class HipMatcher:
 
     @staticmethod
     def _batch(bases, qual, offsets, patl: int, n_reads: Optional[int], max_patl: int = 0) -> RealHipBatch:
-        b = RealHipBatch()
-        b.struct_size = C.sizeof(RealHipBatch)
-        on_device = bool(getattr(bases, "is_cuda", False))
-        b.on_device = int(on_device)
-        if offsets is not None:
-            b.n_reads = int(offsets.shape[0]) - 1
-        else:
-            b.n_reads = int(n_reads if n_reads is not None else bases.shape[0] // patl)
-        b.bases, b.qual, b.offsets = _ptr(bases), _ptr(qual), _ptr(offsets)
-        b.patl, b.max_patl = int(patl), int(max_patl)
+        """the struct alone, over arrays as they stand: where they lie, how many reads, the addresses"""
+        if offsets is not None and not isinstance(offsets, int):
+            n_reads = int(offsets.shape[0]) - 1
+        elif n_reads is None:
+            n_reads = bases.shape[0] // patl
+        return _lib.sized(RealHipBatch, on_device=int(bool(getattr(bases, "is_cuda", False))), n_reads=int(n_reads), bases=_ptr(bases),
+                          qual=_ptr(qual), offsets=_ptr(offsets), patl=int(patl), max_patl=int(max_patl))
+
+    @staticmethod
+    def _read_batch(bases, qual, offsets=None, *, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
+                    packed: bool = False, nflags=None, fresh: bool = False, host_records: bool = False,
+                    on_device: Optional[int] = None, copy: bool = True) -> RealHipBatch:
+        """The batch of every entry point.  Host numpy arrays are made contiguous uint8 / uint8 / uint64 (copy=False: the
+        arrays must stay the caller's, one that is not contiguous is refused); n_reads comes from the offsets, else from the
+        argument, else from patl.  on_device is 0 for host arrays, 1 for device tensors, 2 for device tensors whose records live
+        on the host (host_records), or what the caller says of raw addresses.  The struct keeps alive what it points to, and
+        the arrays are complete when this returns (sync_inputs)."""
+        if isinstance(bases, np.ndarray):
+            given = (bases, qual, offsets)
+            if copy:
+                bases, qual, offsets = (None if a is None else np.ascontiguousarray(a, dtype=t)
+                                        for a, t in zip(given, (np.uint8, np.uint8, np.uint64)))
+            elif not all(a is None or a.flags.c_contiguous for a in given):
+                raise ValueError("the arrays of a submitted batch are not copied: they must be contiguous")
+        if packed and offsets is None and n_reads is None:
+            raise ValueError("a packed batch of uniform length needs n_reads")
+        b = HipMatcher._batch(bases, qual, offsets, patl, n_reads, max_patl)
+        if on_device is not None:
+            b.on_device = on_device
+        elif b.on_device and host_records:
+            b.on_device = 2
+        b.packed, b.fresh, b.nflags = int(bool(packed)), int(bool(fresh)), _ptr(nflags)
+        b._keep = (bases, qual, offsets, nflags)
+        HipMatcher.sync_inputs(bases, qual, offsets, nflags)
         return b
+
+    def _mate_batch(self, mate, **kw) -> RealHipBatch:
+        """mate: a synth.ReadBatch-like object (bases, qual, offsets) or a tuple (bases, qual, offsets)"""
+        bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
+        return self._read_batch(bases, qual, offsets, **kw)
+
+    def _grown(self, call, room, cap: int, offsets=None):
+        """The overflow protocol of every list the library returns: call(out, cap, n_out, offsets) once with room(cap) records;
+        on REAL_HIP_E_OVERFLOW once more with exactly the count it reported -> the records written.  The count is exact, so a
+        second overflow is a fault and surfaces as RealHipError."""
+        n = C.c_uint64(0)
+
+        def attempt(cap):
+            out = room(cap)
+            self.sync_inputs(out, offsets)
+            return out, call(_ptr(out), cap, C.byref(n), _ptr(offsets))
+        out, rc = attempt(int(cap))
+        if rc == _lib.REAL_HIP_E_OVERFLOW:
+            out, rc = attempt(int(n.value))
+        self._check(rc)
+        return out[:int(n.value)]
+
+    def _host_list(self, entry, dtype, cap: int) -> np.ndarray:
+        """a list the context holds (sites, evidence, calls) as numpy records of `dtype`"""
+        return self._grown(lambda o, c, no, _: entry(self._h, o, c, no, 0), lambda c: np.zeros(c, dtype=dtype), cap)
 
     def match_unique(self, bases, qual, offsets=None, patl: int = 0, info=None, score=None,
                      n_reads: Optional[int] = None, max_patl: int = 0, packed: bool = False, nflags=None,
@@ -343,40 +417,24 @@ class HipMatcher:
         """UniqueMatcher::match over a pattern block, folding into info/score in place.
         Host numpy arrays or device torch tensors (all of one kind).  fresh: info / score are outputs only, every
         record starts as uniqueinfo(numpat) does (the first genome block of a run)."""
-        if isinstance(bases, np.ndarray):
-            bases = np.ascontiguousarray(bases, dtype=np.uint8)
-            qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
-            offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        if packed and offsets is None and n_reads is None:
-            raise ValueError("a packed batch of uniform length needs n_reads")
-        b = self._batch(bases, qual, offsets, patl, n_reads, max_patl)
-        b.packed = int(bool(packed))
-        b.nflags = _ptr(nflags)
-        b.fresh = int(bool(fresh))
+        b = self._read_batch(bases, qual, offsets, patl=patl, n_reads=n_reads, max_patl=max_patl, packed=packed, nflags=nflags, fresh=fresh)
+        return self._match_unique(b, info, score)
+
+    def _match_unique(self, b: RealHipBatch, info, score):
         if info is None:
             info, score = new_unique_info(int(b.n_reads), self.opts.scores)
-        self.sync_inputs(bases, qual, offsets, info, score)
+        self.sync_inputs(info, score)
         self._check(self._L.real_hip_match_unique(self._h, C.byref(b), _ptr(info), _ptr(score)))
         return info, score
 
     def match_all(self, bases, qual, offsets=None, patl: int = 0, n_reads: Optional[int] = None, cap: int = 0):
         """AllMatcher::match + unifyMatches over a host pattern block -> (hits, hit_offsets)."""
-        bases = np.ascontiguousarray(bases, dtype=np.uint8)
-        qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
-        offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        b = self._batch(bases, qual, offsets, patl, n_reads)
+        b = self._read_batch(np.asarray(bases), qual, offsets, patl=patl, n_reads=n_reads)
         n = int(b.n_reads)
-        cap = cap or max(1024, 4 * n)
-        while True:
-            out = np.zeros(cap, dtype=HIT_DTYPE)
-            hoff = np.zeros(n + 1, dtype=np.uint64)
-            nout = C.c_uint64(0)
-            rc = self._L.real_hip_match_all(self._h, C.byref(b), out.ctypes.data, cap, C.byref(nout), hoff.ctypes.data)
-            if rc == _lib.REAL_HIP_E_OVERFLOW:      # caller retries with the size the library reports
-                cap = int(nout.value)
-                continue
-            self._check(rc)
-            return out[:int(nout.value)], hoff
+        hoff = np.zeros(n + 1, dtype=np.uint64)
+        hits = self._grown(lambda o, c, no, po: self._L.real_hip_match_all(self._h, C.byref(b), o, c, no, po),
+                           lambda c: np.zeros(c, dtype=HIT_DTYPE), cap or max(1024, 4 * n), hoff)
+        return hits, hoff
 
     # -- pipelined host batches (submit / wait over two slots) --
     def host_alloc(self, shape, dtype) -> np.ndarray:
@@ -387,7 +445,6 @@ class HipMatcher:
         p = self._L.real_hip_host_alloc(max(1, n * dt.itemsize))
         if not p:
             raise RealHipError(_lib.REAL_HIP_E_NOMEM, "real_hip_host_alloc")
-        self._pinned = getattr(self, "_pinned", [])
         self._pinned.append(p)
         buf = (C.c_uint8 * (n * dt.itemsize)).from_address(p)
         return np.frombuffer(buf, dtype=dt, count=n).reshape(shape)
@@ -396,10 +453,7 @@ class HipMatcher:
                       packed: bool = False, nflags=None, fresh: bool = False):
         """real_hip_match_unique_submit: queue upload, kernels and download of one host batch; returns at once.  The
         arrays must stay alive and untouched until wait(slot)."""
-        b = self._batch(bases, qual, offsets, patl, n_reads)
-        b.on_device = 0
-        b.packed = int(bool(packed))
-        b.nflags = _ptr(nflags)
+        b = self._read_batch(bases, qual, offsets, patl=patl, n_reads=n_reads, packed=packed, nflags=nflags, on_device=0, copy=False)
         self._check(self._L.real_hip_match_unique_submit(self._h, C.byref(b), _ptr(info), _ptr(score), slot, int(bool(fresh))))
 
     def wait(self, slot: int):
@@ -453,16 +507,8 @@ class HipMatcher:
 
     def match_unique_parsed(self, parsed, info=None, score=None):
         """UniqueMatcher::match over the reads of a parse_reads() result (read arrays on the device, records on the host)."""
-        b = RealHipBatch()
-        b.struct_size = C.sizeof(RealHipBatch)
-        b.on_device = 2
-        b.n_reads = parsed.n_reads
-        b.bases, b.qual, b.offsets = parsed.bases, parsed.qual, parsed.offsets
-        b.patl, b.max_patl = 0, parsed.max_patl
-        if info is None:
-            info, score = new_unique_info(int(b.n_reads), self.opts.scores)
-        self._check(self._L.real_hip_match_unique(self._h, C.byref(b), _ptr(info), _ptr(score)))
-        return info, score
+        b = self._read_batch(parsed.bases, parsed.qual, parsed.offsets, n_reads=parsed.n_reads, max_patl=parsed.max_patl, on_device=2)
+        return self._match_unique(b, info, score)
 
     def download(self, dev_ptr, count: int, dtype):
         """copy `count` items of a device array the library returned to the host (tests, id strings)"""
@@ -474,52 +520,44 @@ class HipMatcher:
     # -- pileup: depth and mismatch base counts per position of the resident text (include/real_hip.h, "pileup") --
     def pileup_begin(self, min_qual: int = 0):
         """real_hip_pileup_begin: accumulators for the resident text, zeroed; a second begin starts again"""
-        p = _lib.RealHipPileupParams()
-        p.struct_size = C.sizeof(_lib.RealHipPileupParams)
-        p.min_qual = int(min_qual)
+        p = _lib.sized(_lib.RealHipPileupParams, min_qual=int(min_qual))
         self._check(self._L.real_hip_pileup_begin(self._h, C.byref(p)))
 
-    def _pileup_batch(self, bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, records_on_host) -> RealHipBatch:
-        if isinstance(bases, np.ndarray):
-            bases = np.ascontiguousarray(bases, dtype=np.uint8)
-            qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
-            offsets = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.uint64)
-        if packed and offsets is None and n_reads is None:
-            raise ValueError("a packed batch of uniform length needs n_reads")
-        b = self._batch(bases, qual, offsets, patl, n_reads, max_patl)
-        if b.on_device and records_on_host:
-            b.on_device = 2
-        b.packed = int(bool(packed))
-        b.nflags = _ptr(nflags)
-        b._keep = (bases, qual, offsets, nflags)
-        self.sync_inputs(bases, qual, offsets, nflags)
-        return b
+    # -- the stages behind the matching (pileup, calls, mismatch lists): reads and their final records --
+    def _placed(self, bases, qual, info, **kw):
+        """a batch and its records for a stage -> (batch, info): numpy records are made contiguous (with device reads they stay
+        on the host: on_device = 2), and there is one record per read"""
+        host = isinstance(info, np.ndarray)
+        if host:
+            info = np.ascontiguousarray(info, dtype=np.uint64)
+        b = self._read_batch(bases, qual, host_records=host, **kw)
+        if int(info.shape[0]) != int(b.n_reads):
+            raise ValueError("one record per read")
+        self.sync_inputs(info)
+        return b, info
+
+    def _placed_pairs(self, mate1, mate2, pairs, singles1=None, singles2=None):
+        """both mates' batches and the fragments' records for a stage -> (batch 1, batch 2, pairs, singles1, singles2)"""
+        host = isinstance(pairs, np.ndarray)
+        if host:
+            pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+            singles1, singles2 = (None if s is None else np.ascontiguousarray(s, dtype=SINGLE_DTYPE) for s in (singles1, singles2))
+        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
+        self.sync_inputs(pairs, singles1, singles2)
+        return b1, b2, pairs, singles1, singles2
 
     def pileup_add(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
                    packed: bool = False, nflags=None):
         """real_hip_pileup_add: the placements of the records `info` (what match_unique returned for this batch).  Host
         numpy arrays, device torch tensors, or device reads with numpy records (on_device = 2)."""
-        host_info = isinstance(info, np.ndarray)
-        if host_info:
-            info = np.ascontiguousarray(info, dtype=np.uint64)
-        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
-        if int(info.shape[0]) != int(b.n_reads):
-            raise ValueError("one record per read")
-        self.sync_inputs(info)
+        b, info = self._placed(bases, qual, info, offsets=offsets, patl=patl, n_reads=n_reads, max_patl=max_patl, packed=packed, nflags=nflags)
         self._check(self._L.real_hip_pileup_add(self._h, C.byref(b), _ptr(info)))
 
     def pileup_add_pairs(self, mate1, mate2, pairs):
         """real_hip_pileup_add_pairs: both mates of every Unique record of `pairs` (what match_pairs returned); mates as
         (bases, qual, offsets) tuples or ReadBatch-like objects, all host arrays or all device tensors"""
-        host_pairs = isinstance(pairs, np.ndarray)
-        if host_pairs:
-            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
-        bs = []
-        for mate in (mate1, mate2):
-            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
-            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
-        self.sync_inputs(pairs)
-        self._check(self._L.real_hip_pileup_add_pairs(self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs)))
+        b1, b2, pairs, _, _ = self._placed_pairs(mate1, mate2, pairs)
+        self._check(self._L.real_hip_pileup_add_pairs(self._h, C.byref(b1), C.byref(b2), _ptr(pairs)))
 
     def pileup_finish(self) -> int:
         """real_hip_pileup_finish: scans the depth and compacts the sites; returns the number of sites"""
@@ -538,20 +576,13 @@ class HipMatcher:
 
     def pileup_sites(self, cap: int = 1024) -> np.ndarray:
         """the site list as lib.PILEUP_SITE_DTYPE, ascending position; the buffer grows once to the size the library reports"""
-        n = C.c_uint64(0)
-        out = np.zeros(int(cap), dtype=_lib.PILEUP_SITE_DTYPE)
-        rc = self._L.real_hip_pileup_sites(self._h, out.ctypes.data, int(cap), C.byref(n), 0)
-        if rc == _lib.REAL_HIP_E_OVERFLOW:
-            out = np.zeros(int(n.value), dtype=_lib.PILEUP_SITE_DTYPE)
-            rc = self._L.real_hip_pileup_sites(self._h, out.ctypes.data, int(n.value), C.byref(n), 0)
-        self._check(rc)
-        return out[:int(n.value)]
+        return self._host_list(self._L.real_hip_pileup_sites, _lib.PILEUP_SITE_DTYPE, cap)
 
     def pileup_end(self):
         self._check(self._L.real_hip_pileup_end(self._h))
 
     def pileup_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipPileupStats, self._L.real_hip_pileup_stats_get, _lib.PILEUP_STATS_FIELDS, reset)
+        return self._stats(_lib.RealHipPileupStats, self._L.real_hip_pileup_stats_get, reset)
 
     # -- variant calls: genotypes of the finished pileup's sites (include/real_hip.h, "variant calls") --
     def call_begin(self):
@@ -561,88 +592,48 @@ class HipMatcher:
     def call_add(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
                  packed: bool = False, nflags=None):
         """real_hip_call_add: the evidence of the placements of `info`; the arguments are pileup_add's"""
-        host_info = isinstance(info, np.ndarray)
-        if host_info:
-            info = np.ascontiguousarray(info, dtype=np.uint64)
-        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
-        if int(info.shape[0]) != int(b.n_reads):
-            raise ValueError("one record per read")
-        self.sync_inputs(info)
+        b, info = self._placed(bases, qual, info, offsets=offsets, patl=patl, n_reads=n_reads, max_patl=max_patl, packed=packed, nflags=nflags)
         self._check(self._L.real_hip_call_add(self._h, C.byref(b), _ptr(info)))
 
     def call_add_pairs(self, mate1, mate2, pairs):
         """real_hip_call_add_pairs: both mates of every Unique record of `pairs`; the arguments are pileup_add_pairs'"""
-        host_pairs = isinstance(pairs, np.ndarray)
-        if host_pairs:
-            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
-        bs = []
-        for mate in (mate1, mate2):
-            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
-            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
-        self.sync_inputs(pairs)
-        self._check(self._L.real_hip_call_add_pairs(self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs)))
+        b1, b2, pairs, _, _ = self._placed_pairs(mate1, mate2, pairs)
+        self._check(self._L.real_hip_call_add_pairs(self._h, C.byref(b1), C.byref(b2), _ptr(pairs)))
 
     def call_finish(self, min_call_qual: int = 20, min_depth: int = 4) -> int:
         """real_hip_call_finish: the genotypes and the compacted call list; returns the number of calls.  May be called again
         with other thresholds"""
-        p = _lib.RealHipCallParams()
-        p.struct_size = C.sizeof(_lib.RealHipCallParams)
-        p.min_call_qual, p.min_depth = int(min_call_qual), int(min_depth)
+        p = _lib.sized(_lib.RealHipCallParams, min_call_qual=int(min_call_qual), min_depth=int(min_depth))
         n = C.c_uint64(0)
         self._check(self._L.real_hip_call_finish(self._h, C.byref(p), C.byref(n)))
         return int(n.value)
 
-    def _call_list(self, call, dtype, cap: int) -> np.ndarray:
-        n = C.c_uint64(0)
-        out = np.zeros(int(cap), dtype=dtype)
-        rc = call(self._h, out.ctypes.data, int(cap), C.byref(n), 0)
-        if rc == _lib.REAL_HIP_E_OVERFLOW:
-            out = np.zeros(int(n.value), dtype=dtype)
-            rc = call(self._h, out.ctypes.data, int(n.value), C.byref(n), 0)
-        self._check(rc)
-        return out[:int(n.value)]
-
     def call_evidence(self, cap: int = 1024) -> np.ndarray:
         """the evidence table as lib.CALL_EVIDENCE_DTYPE, record s for site s of pileup_sites(); the buffer grows once"""
-        return self._call_list(self._L.real_hip_call_evidence, _lib.CALL_EVIDENCE_DTYPE, cap)
+        return self._host_list(self._L.real_hip_call_evidence, _lib.CALL_EVIDENCE_DTYPE, cap)
 
     def call_variants(self, cap: int = 1024) -> np.ndarray:
         """the call list as lib.CALL_DTYPE, ascending position; the buffer grows once to the size the library reports"""
-        return self._call_list(self._L.real_hip_call_variants, _lib.CALL_DTYPE, cap)
+        return self._host_list(self._L.real_hip_call_variants, _lib.CALL_DTYPE, cap)
 
     def call_end(self):
         self._check(self._L.real_hip_call_end(self._h))
 
     def call_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipCallStats, self._L.real_hip_call_stats_get, _lib.CALL_STATS_FIELDS, reset)
+        return self._stats(_lib.RealHipCallStats, self._L.real_hip_call_stats_get, reset)
 
     # -- mismatch lists: where each placed read differs from the resident text (include/real_hip.h, "mismatch lists") --
     def _mismatch_call(self, call, lists: int, on_device: bool, cap: int):
         """one list call with its outputs: host numpy arrays, or device tensors when the records are; the buffer grows once to
         the size the library reports -> (lists as lib.MISMATCH_DTYPE, offsets)"""
-        n = C.c_uint64(0)
-        cap = int(cap)
-
-        def room(c):
-            if not on_device:
-                return np.zeros(c, dtype=_lib.MISMATCH_DTYPE)
-            import torch
-            return torch.zeros(max(c, 1), dtype=torch.int32, device="cuda")
         if on_device:
             import torch
             off = torch.zeros(lists + 1, dtype=torch.int64, device="cuda")
+            room = lambda c: torch.zeros(max(c, 1), dtype=torch.int32, device="cuda")       # noqa: E731
         else:
             off = np.zeros(lists + 1, dtype=np.uint64)
-        out = room(cap)
-        self.sync_inputs(out, off)
-        rc = call(_ptr(out), cap, C.byref(n), _ptr(off))
-        if rc == _lib.REAL_HIP_E_OVERFLOW:
-            cap = int(n.value)
-            out = room(cap)
-            self.sync_inputs(out)
-            rc = call(_ptr(out), cap, C.byref(n), _ptr(off))
-        self._check(rc)
-        return out[:int(n.value)], off
+            room = lambda c: np.zeros(c, dtype=_lib.MISMATCH_DTYPE)                         # noqa: E731
+        return self._grown(call, room, cap, off), off
 
     def mismatches(self, bases, qual, info, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
                    packed: bool = False, nflags=None, cap: int = 0):
@@ -650,38 +641,23 @@ class HipMatcher:
         this batch) -> (lists, offsets): lists[offsets[i] : offsets[i + 1]] is read i's.  Host numpy arrays, device torch
         tensors (the outputs then are device tensors: int32 words of lib.MISMATCH_DTYPE, int64 offsets), or device reads with
         numpy records (on_device = 2)."""
-        host_info = isinstance(info, np.ndarray)
-        if host_info:
-            info = np.ascontiguousarray(info, dtype=np.uint64)
-        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_info)
+        b, info = self._placed(bases, qual, info, offsets=offsets, patl=patl, n_reads=n_reads, max_patl=max_patl, packed=packed, nflags=nflags)
         n = int(b.n_reads)
-        if int(info.shape[0]) != n:
-            raise ValueError("one record per read")
-        self.sync_inputs(info)
         return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches(self._h, C.byref(b), _ptr(info), o, c, no, po),
-                                   n, not host_info, cap or max(1024, 4 * n))
+                                   n, not isinstance(info, np.ndarray), cap or max(1024, 4 * n))
 
     def mismatches_pairs(self, mate1, mate2, pairs, singles1=None, singles2=None, cap: int = 0):
         """real_hip_mismatches_pairs: the lists of both mates' final placements (mate 1 of fragment i is list 2i, mate 2 list
         2i + 1) from the pair records and, where given, the mates' single records; mates as (bases, qual, offsets) tuples or
         ReadBatch-like objects, all host arrays or all device tensors"""
-        host_pairs = isinstance(pairs, np.ndarray)
-        if host_pairs:
-            pairs = np.ascontiguousarray(pairs, dtype=_lib.PAIR_DTYPE)
-            singles1 = None if singles1 is None else np.ascontiguousarray(singles1, dtype=_lib.SINGLE_DTYPE)
-            singles2 = None if singles2 is None else np.ascontiguousarray(singles2, dtype=_lib.SINGLE_DTYPE)
-        bs = []
-        for mate in (mate1, mate2):
-            bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
-            bs.append(self._pileup_batch(bases, qual, offsets, 0, None, 0, False, None, host_pairs))
-        n = int(bs[0].n_reads)
-        self.sync_inputs(pairs, singles1, singles2)
+        b1, b2, pairs, singles1, singles2 = self._placed_pairs(mate1, mate2, pairs, singles1, singles2)
+        n = int(b1.n_reads)
         return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches_pairs(
-            self._h, C.byref(bs[0]), C.byref(bs[1]), _ptr(pairs), _ptr(singles1), _ptr(singles2), o, c, no, po),
-            2 * n, not host_pairs, cap or max(1024, 8 * n))
+            self._h, C.byref(b1), C.byref(b2), _ptr(pairs), _ptr(singles1), _ptr(singles2), o, c, no, po),
+            2 * n, not isinstance(pairs, np.ndarray), cap or max(1024, 8 * n))
 
     def mismatch_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipMismatchStats, self._L.real_hip_mismatch_stats_get, _lib.MISMATCH_STATS_FIELDS, reset)
+        return self._stats(_lib.RealHipMismatchStats, self._L.real_hip_mismatch_stats_get, reset)
 
     # -- duplicate marking: read summaries, then the marks of the placed reads / fragments (include/real_hip.h, "duplicates") --
     def read_summary(self, bases, qual, offsets=None, patl: int = 0, n_reads: Optional[int] = None, max_patl: int = 0,
@@ -691,7 +667,8 @@ class HipMatcher:
         from device reads (on_device = 2)."""
         on_device = bool(getattr(bases, "is_cuda", False))
         host_out = not on_device or isinstance(out, np.ndarray)
-        b = self._pileup_batch(bases, qual, offsets, patl, n_reads, max_patl, packed, nflags, host_out)
+        b = self._read_batch(bases, qual, offsets, patl=patl, n_reads=n_reads, max_patl=max_patl, packed=packed, nflags=nflags,
+                             host_records=host_out)
         n = int(b.n_reads)
         if out is None:
             if host_out:
@@ -732,7 +709,7 @@ class HipMatcher:
         return self._mark_call(self._L.real_hip_mark_duplicates_pairs, pairs, [sums1, sums2], _lib.PAIR_DTYPE)
 
     def dup_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipDupStats, self._L.real_hip_dup_stats_get, _lib.DUP_STATS_FIELDS, reset)
+        return self._stats(_lib.RealHipDupStats, self._L.real_hip_dup_stats_get, reset)
 
     # -- instrumentation --
     def counters(self, reset: bool = False) -> dict:
@@ -768,31 +745,13 @@ class PairMatcher(AllMatcher):
 
     @staticmethod
     def _pair_params(min_insert: int, max_insert: int, orientation: int = 0) -> "_lib.RealHipPairParams":
-        pp = _lib.RealHipPairParams()
-        pp.struct_size = C.sizeof(_lib.RealHipPairParams)
-        pp.min_insert, pp.max_insert, pp.orientation = int(min_insert), int(max_insert), int(orientation)
-        return pp
+        return _lib.sized(_lib.RealHipPairParams, min_insert=int(min_insert), max_insert=int(max_insert), orientation=int(orientation))
 
     new_pair_info = staticmethod(new_pair_info)
 
-    def _mate_batch(self, mate) -> RealHipBatch:
-        """mate: a synth.ReadBatch-like object (bases, qual, offsets) or a tuple (bases, qual, offsets)"""
-        bases, qual, offsets = (mate.bases, mate.qual, mate.offsets) if hasattr(mate, "bases") else mate
-        if isinstance(bases, np.ndarray):
-            bases = np.ascontiguousarray(bases, dtype=np.uint8)
-            qual = None if qual is None else np.ascontiguousarray(qual, dtype=np.uint8)
-            offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-        self.sync_inputs(bases, qual, offsets)
-        b = self._batch(bases, qual, offsets, 0, None)
-        b._keep = (bases, qual, offsets)
-        return b
-
     @staticmethod
     def _search_params(max_anchors: int = 0) -> "_lib.RealHipMateSearchParams":
-        sp = _lib.RealHipMateSearchParams()
-        sp.struct_size = C.sizeof(_lib.RealHipMateSearchParams)
-        sp.max_anchors = int(max_anchors)
-        return sp
+        return _lib.sized(_lib.RealHipMateSearchParams, max_anchors=int(max_anchors))
 
     def match_pairs(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, orientation: int = 0,
                     mate_search: bool = False, max_anchors: int = 0, fresh: Optional[bool] = None):
@@ -802,11 +761,8 @@ class PairMatcher(AllMatcher):
         hit's window is searched for a placement of the other mate the seeds missed (max_anchors: 0 = no limit)."""
         b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
         pp = self._pair_params(min_insert, max_insert, orientation)
-        if fresh is None:
-            fresh = pairs is None
-        if pairs is None:
-            pairs = new_pair_info(int(b1.n_reads))
-        b1.fresh = b2.fresh = int(bool(fresh))
+        pairs, fresh = _start_or_fold(pairs, fresh, bool(b1.on_device), lambda: new_pair_info(int(b1.n_reads)))
+        b1.fresh = b2.fresh = int(fresh)
         self.sync_inputs(pairs)
         if mate_search:
             sp = self._search_params(max_anchors)
@@ -820,52 +776,28 @@ class PairMatcher(AllMatcher):
         """real_hip_pair_search: the mate search alone on anchors the caller holds (numpy arrays of lib.HIT_DTYPE / uint64
         with host batches, device torch tensors of the same layout with device batches); needs the text, not the index."""
         b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
-        on_device = bool(b1.on_device)
-        if not on_device:
-            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
-            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
-        n = int(b1.n_reads)
-        if int(off1.shape[0]) - 1 != n or int(off2.shape[0]) - 1 != n:
-            raise ValueError("the anchors' offsets and the batches describe different numbers of fragments")
-        if fresh is None:
-            fresh = pairs is None
-        if pairs is None:
-            if on_device:
-                raise ValueError("device inputs need a device tensor for the records")
-            pairs = new_pair_info(n)
+        on_device, n, ((hits1, off1, _), (hits2, off2, _)) = _held_lists(
+            [(hits1, off1, None), (hits2, off2, None)], "the anchors' offsets and the batches describe different numbers of fragments", b1)
+        pairs, fresh = _start_or_fold(pairs, fresh, on_device, lambda: new_pair_info(n))
         pp = self._pair_params(min_insert, max_insert, orientation)
         sp = self._search_params(max_anchors)
         self.sync_inputs(hits1, off1, hits2, off2, pairs)
         self._check(self._L.real_hip_pair_search(self._h, C.byref(pp), C.byref(sp), C.byref(b1), C.byref(b2), _ptr(hits1), _ptr(off1),
-                                                 _ptr(hits2), _ptr(off2), int(fileid), int(bool(fresh)), _ptr(pairs)))
+                                                 _ptr(hits2), _ptr(off2), int(fileid), int(fresh), _ptr(pairs)))
         return pairs
 
     def mate_search_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipMateSearchStats, self._L.real_hip_mate_search_stats_get,
-                           ("fragments", "anchors", "anchors_skipped", "positions", "placements", "launches", "kernel_ms"), reset)
+        return self._stats(_lib.RealHipMateSearchStats, self._L.real_hip_mate_search_stats_get, reset)
 
     def pair_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0, pairs=None,
                   orientation: int = 0, fresh: Optional[bool] = None):
         """real_hip_pair_hits: the join alone, on hit lists the caller holds (numpy arrays of lib.HIT_DTYPE / uint64 /
         uint32, or device torch tensors of the same layout, all of one kind)."""
-        on_device = bool(getattr(off1, "is_cuda", False))
-        if not on_device:
-            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
-            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
-            len1, len2 = np.ascontiguousarray(len1, dtype=np.uint32), np.ascontiguousarray(len2, dtype=np.uint32)
-        n = int(off1.shape[0]) - 1
-        if int(off2.shape[0]) - 1 != n or int(len1.shape[0]) != n or int(len2.shape[0]) != n:
-            raise ValueError("the two mates' arrays describe different numbers of reads")
-        if fresh is None:
-            fresh = pairs is None
-        if pairs is None:
-            if on_device:
-                raise ValueError("device inputs need a device tensor for the records")
-            pairs = new_pair_info(n)
+        on_device, n, (m1, m2) = _held_lists([(hits1, off1, len1), (hits2, off2, len2)], "the two mates' arrays describe different numbers of reads")
+        pairs, fresh = _start_or_fold(pairs, fresh, on_device, lambda: new_pair_info(n))
         pp = self._pair_params(min_insert, max_insert, orientation)
-        self.sync_inputs(hits1, off1, len1, hits2, off2, len2, pairs)
-        self._check(self._L.real_hip_pair_hits(self._h, C.byref(pp), _ptr(hits1), _ptr(off1), _ptr(len1), _ptr(hits2), _ptr(off2), _ptr(len2),
-                                               n, int(fileid), int(on_device), int(bool(fresh)), _ptr(pairs)))
+        self.sync_inputs(*m1, *m2, pairs)
+        self._check(self._L.real_hip_pair_hits(self._h, C.byref(pp), *map(_ptr, m1 + m2), n, int(fileid), int(on_device), int(fresh), _ptr(pairs)))
         return pairs
 
     # -- single placements of a mate (real_hip_single records) --
@@ -875,23 +807,10 @@ class PairMatcher(AllMatcher):
         """real_hip_single_hits: the fold alone, on one mate's lists as the caller holds them (numpy arrays of lib.HIT_DTYPE /
         uint64 / uint32, or device torch tensors of the same layout, all of one kind; device inputs need `singles` as a device
         tensor of 16-byte records)."""
-        on_device = bool(getattr(off, "is_cuda", False))
-        if not on_device:
-            hits = np.ascontiguousarray(hits, dtype=HIT_DTYPE)
-            off = np.ascontiguousarray(off, dtype=np.uint64)
-            lens = np.ascontiguousarray(lens, dtype=np.uint32)
-        n = int(off.shape[0]) - 1
-        if int(lens.shape[0]) != n:
-            raise ValueError("the offsets and the lengths describe different numbers of reads")
-        if fresh is None:
-            fresh = singles is None
-        if singles is None:
-            if on_device:
-                raise ValueError("device inputs need a device tensor for the records")
-            singles = new_single_info(n)
-        self.sync_inputs(hits, off, lens, singles)
-        self._check(self._L.real_hip_single_hits(self._h, _ptr(hits), _ptr(off), _ptr(lens), n, int(fileid), int(on_device),
-                                                 int(bool(fresh)), _ptr(singles)))
+        on_device, n, (m,) = _held_lists([(hits, off, lens)], "the offsets and the lengths describe different numbers of reads")
+        singles, fresh = _start_or_fold(singles, fresh, on_device, lambda: new_single_info(n))
+        self.sync_inputs(*m, singles)
+        self._check(self._L.real_hip_single_hits(self._h, *map(_ptr, m), n, int(fileid), int(on_device), int(fresh), _ptr(singles)))
         return singles
 
     def match_pairs_singles(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, singles1=None, singles2=None,
@@ -904,12 +823,10 @@ class PairMatcher(AllMatcher):
         given = [x is not None for x in (pairs, singles1, singles2)]
         if any(given) and not all(given):
             raise ValueError("pairs, singles1 and singles2 are started together or folded into together")
-        if fresh is None:
-            fresh = pairs is None
-        if pairs is None:
-            n = int(b1.n_reads)
-            pairs, singles1, singles2 = new_pair_info(n), new_single_info(n), new_single_info(n)
-        b1.fresh = b2.fresh = int(bool(fresh))
+        n, on_device = int(b1.n_reads), bool(b1.on_device)
+        pairs, fresh = _start_or_fold(pairs, fresh, on_device, lambda: new_pair_info(n))
+        (singles1, _), (singles2, _) = (_start_or_fold(s, fresh, on_device, lambda: new_single_info(n)) for s in (singles1, singles2))
+        b1.fresh = b2.fresh = int(fresh)
         self.sync_inputs(pairs, singles1, singles2)
         sp = self._search_params(max_anchors) if mate_search else None
         self._check(self._L.real_hip_match_pairs_singles(self._h, C.byref(b1), C.byref(b2), C.byref(pp), C.byref(sp) if sp is not None else None,
@@ -917,8 +834,7 @@ class PairMatcher(AllMatcher):
         return pairs, singles1, singles2
 
     def single_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get,
-                           ("reads", "hits", "handed_over", "launches", "kernel_ms"), reset)
+        return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
 
     # -- insert sizes: the histogram of the Unique fragments' outer distances, and the bounds it suggests --
     def insert_hist(self, pairs, len1, len2, n_bins: int, hist=None, fresh: Optional[bool] = None):
@@ -935,18 +851,13 @@ class PairMatcher(AllMatcher):
             n = int(pairs.numel() * pairs.element_size() // 40)
         if int(len1.shape[0]) != n or int(len2.shape[0]) != n:
             raise ValueError("the records and the lengths describe different numbers of fragments")
-        if fresh is None:
-            fresh = hist is None
-        if hist is None:
-            if on_device:
-                raise ValueError("device inputs need a device tensor for the histogram")
-            hist = np.zeros(int(n_bins), dtype=np.uint64)
-        elif not on_device and (not isinstance(hist, np.ndarray) or hist.dtype != np.uint64 or not hist.flags.c_contiguous):
+        if hist is not None and not on_device and (not isinstance(hist, np.ndarray) or hist.dtype != np.uint64 or not hist.flags.c_contiguous):
             raise ValueError("hist must be a contiguous numpy uint64 array")
+        hist, fresh = _start_or_fold(hist, fresh, on_device, lambda: np.zeros(int(n_bins), dtype=np.uint64), "histogram")
         if int(hist.shape[0]) != int(n_bins):
             raise ValueError("hist must hold n_bins counts")
         self.sync_inputs(pairs, len1, len2, hist)
-        self._check(self._L.real_hip_pair_insert_hist(self._h, _ptr(pairs), _ptr(len1), _ptr(len2), n, int(on_device), int(bool(fresh)),
+        self._check(self._L.real_hip_pair_insert_hist(self._h, _ptr(pairs), _ptr(len1), _ptr(len2), n, int(on_device), int(fresh),
                                                       int(n_bins), _ptr(hist)))
         return hist
 
@@ -958,8 +869,7 @@ class PairMatcher(AllMatcher):
         if hasattr(hist, "cpu"):
             hist = hist.cpu().numpy().view(np.uint64)
         hist = np.ascontiguousarray(hist, dtype=np.uint64)
-        est = _lib.RealHipInsertEstimate()
-        est.struct_size = C.sizeof(_lib.RealHipInsertEstimate)
+        est = _lib.sized(_lib.RealHipInsertEstimate)
         L = _lib.load()
         rc = L.real_hip_insert_bounds(hist.ctypes.data, int(hist.shape[0]), int(min_count), int(iqr_mult), C.byref(est))
         if rc != _lib.REAL_HIP_OK:
@@ -968,16 +878,15 @@ class PairMatcher(AllMatcher):
         return {"n": int(est.n), "q1": int(est.q1), "median": int(est.median), "q3": int(est.q3), "low": int(est.low), "high": int(est.high)}
 
     def insert_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipInsertStats, self._L.real_hip_insert_stats_get,
-                           ("records", "counted", "overflow", "invalid", "launches", "kernel_ms"), reset)
+        return self._stats(_lib.RealHipInsertStats, self._L.real_hip_insert_stats_get, reset)
 
     def pair_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipPairStats, self._L.real_hip_pair_stats_get, ("pairs", "products", "handed_over"), reset)
+        return self._stats(_lib.RealHipPairStats, self._L.real_hip_pair_stats_get, reset)
 
     # -- every concordant pair of a fragment (real_hip_pair_hit records) --
     def _pair_all_call(self, call, n: int, on_device: bool, cap: int, out, pair_offsets):
-        """one enumeration call with the overflow retry of match_all: host outputs are allocated here and grow to the size
-        the library reports; device outputs are the caller's (a too small `out` raises)"""
+        """one enumeration call: host outputs are allocated here and grow once to the size the library reports (_grown);
+        device outputs are the caller's (a too small `out` raises, the error's .needed says how many records it takes)"""
         nout = C.c_uint64(0)
         if on_device:
             if out is None or pair_offsets is None:
@@ -990,36 +899,20 @@ class PairMatcher(AllMatcher):
                 raise err
             self._check(rc)
             return int(nout.value), pair_offsets
-        cap = cap or max(1024, 2 * n)
-        while True:
-            out = np.zeros(cap, dtype=PAIR_HIT_DTYPE)
-            poff = np.zeros(n + 1, dtype=np.uint64)
-            rc = call(out.ctypes.data, cap, C.byref(nout), poff.ctypes.data)
-            if rc == _lib.REAL_HIP_E_OVERFLOW:      # retry with the size the library reports
-                cap = int(nout.value)
-                continue
-            self._check(rc)
-            return out[:int(nout.value)], poff
+        poff = np.zeros(n + 1, dtype=np.uint64)
+        return self._grown(call, lambda c: np.zeros(c, dtype=PAIR_HIT_DTYPE), cap or max(1024, 2 * n), poff), poff
 
     def pair_all_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, fileid: int = 0,
                       orientation: int = 0, cap: int = 0, out=None, pair_offsets=None):
         """real_hip_pair_all_hits: every concordant pair of every fragment, row-major over the product of the two lists the
         caller holds.  Host arrays -> (pair hits as lib.PAIR_HIT_DTYPE, offsets); device tensors need `out` (32-byte
         records) and `pair_offsets` (n + 1 int64) as device tensors -> (number of pairs, pair_offsets)."""
-        on_device = bool(getattr(off1, "is_cuda", False))
-        if not on_device:
-            hits1, hits2 = np.ascontiguousarray(hits1, dtype=HIT_DTYPE), np.ascontiguousarray(hits2, dtype=HIT_DTYPE)
-            off1, off2 = np.ascontiguousarray(off1, dtype=np.uint64), np.ascontiguousarray(off2, dtype=np.uint64)
-            len1, len2 = np.ascontiguousarray(len1, dtype=np.uint32), np.ascontiguousarray(len2, dtype=np.uint32)
-        n = int(off1.shape[0]) - 1
-        if int(off2.shape[0]) - 1 != n or int(len1.shape[0]) != n or int(len2.shape[0]) != n:
-            raise ValueError("the two mates' arrays describe different numbers of reads")
+        on_device, n, (m1, m2) = _held_lists([(hits1, off1, len1), (hits2, off2, len2)], "the two mates' arrays describe different numbers of reads")
         pp = self._pair_params(min_insert, max_insert, orientation)
-        self.sync_inputs(hits1, off1, len1, hits2, off2, len2)
+        self.sync_inputs(*m1, *m2)
 
         def call(o, c, no, po):
-            return self._L.real_hip_pair_all_hits(self._h, C.byref(pp), _ptr(hits1), _ptr(off1), _ptr(len1), _ptr(hits2), _ptr(off2),
-                                                  _ptr(len2), n, int(fileid), int(on_device), o, c, no, po)
+            return self._L.real_hip_pair_all_hits(self._h, C.byref(pp), *map(_ptr, m1 + m2), n, int(fileid), int(on_device), o, c, no, po)
         return self._pair_all_call(call, n, on_device, cap, out, pair_offsets)
 
     def match_pairs_all(self, mate1, mate2, min_insert: int, max_insert: int, orientation: int = 0, cap: int = 0, out=None,
@@ -1035,5 +928,4 @@ class PairMatcher(AllMatcher):
         return self._pair_all_call(call, int(b1.n_reads), bool(b1.on_device), cap, out, pair_offsets)
 
     def pair_all_stats(self, reset: bool = False) -> dict:
-        return self._stats(_lib.RealHipPairAllStats, self._L.real_hip_pair_all_stats_get,
-                           ("fragments", "products", "pairs_out", "handed_over", "launches", "kernel_ms"), reset)
+        return self._stats(_lib.RealHipPairAllStats, self._L.real_hip_pair_all_stats_get, reset)

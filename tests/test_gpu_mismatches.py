@@ -134,7 +134,7 @@ def test_capacity_protocol_and_no_reads(ora, matchers):
     w = pw.workload()
     wl, wo, wst = _expected(ora, "main", 1)
     total, n = wl.shape[0], w.main.n_reads
-    b = m._pileup_batch(w.main.bases, None, w.main.offsets, 0, None, 0, False, None, True)
+    b = m._read_batch(w.main.bases, None, w.main.offsets, host_records=True)
     out = np.full(total + 1, 0x07070707, dtype=np.uint32)
     off = np.zeros(n + 1, dtype=np.uint64)
     nout = C.c_uint64(0)
@@ -150,7 +150,7 @@ def test_capacity_protocol_and_no_reads(ora, matchers):
     assert np.array_equal(out[:-1].view(rlib.MISMATCH_DTYPE)["off"], wl["off"])
     _same(_lists(m, w.main, rec["main"], cap=1), (wl, wo, wst), "the mirror grows its buffer once")
     # no reads: valid, offsets[0] = 0, nothing else written
-    e = m._pileup_batch(np.zeros(0, np.uint8), None, np.zeros(1, np.uint64), 0, None, 0, False, None, True)
+    e = m._read_batch(np.zeros(0, np.uint8), None, np.zeros(1, np.uint64), host_records=True)
     off[:] = 9
     nout.value = 5
     assert call(m._h, C.byref(e), None, None, 0, C.byref(nout), off.ctypes.data) == rlib.REAL_HIP_OK
@@ -291,7 +291,7 @@ def test_errors_are_loud_and_launch_nothing(matchers):
     w = pw.workload()
     a = _slice(w.main, 0, 200)
     info = rec["main"][:200]
-    b = m._pileup_batch(a.bases, None, a.offsets, 0, None, 0, False, None, True)
+    b = m._read_batch(a.bases, None, a.offsets, host_records=True)
     out = np.zeros(4096, dtype=rlib.MISMATCH_DTYPE)
     off = np.zeros(401, dtype=np.uint64)
     nout = C.c_uint64(0)
@@ -301,8 +301,8 @@ def test_errors_are_loud_and_launch_nothing(matchers):
     big = rlib.RealHipBatch()
     big.struct_size, big.n_reads, big.patl = C.sizeof(rlib.RealHipBatch), (1 << 32) + 1, 50
     big.bases = info.ctypes.data
-    short = m._pileup_batch(a.bases[:int(a.offsets[100])], None, a.offsets[:101], 0, None, 0, False, None, True)
-    dev = m._pileup_batch(a.bases, None, a.offsets, 0, None, 0, False, None, True)
+    short = m._read_batch(a.bases[:int(a.offsets[100])], None, a.offsets[:101], host_records=True)
+    dev = m._read_batch(a.bases, None, a.offsets, host_records=True)
     dev.on_device = 2
     m.mismatch_stats(reset=True)
     O, N, F, P = out.ctypes.data, C.byref(nout), off.ctypes.data, pairs.ctypes.data

@@ -153,8 +153,8 @@ def test_two_batch_calls_refuse_in_the_order_of_their_checks(case, matcher):
     real_hip_mismatches_pairs has looked at its outputs by then (*n_out is 0, and null outputs are what it reports), and
     real_hip_pair_search on a context without a text answers REAL_HIP_E_STATE."""
     m, b = matcher, case.b
-    full = m._pileup_batch(b.bases, None, b.offsets, 0, None, 0, False, None, True)
-    half = m._pileup_batch(b.bases[:int(b.offsets[100])], None, b.offsets[:101], 0, None, 0, False, None, True)
+    full = m._read_batch(b.bases, None, b.offsets, host_records=True)
+    half = m._read_batch(b.bases[:int(b.offsets[100])], None, b.offsets[:101], host_records=True)
     out, off, nout = np.zeros(64, dtype=rlib.MISMATCH_DTYPE), np.zeros(2 * READS + 1, dtype=np.uint64), C.c_uint64(77)
     two = m._L.real_hip_mismatches_pairs
     m.mismatch_stats(reset=True)

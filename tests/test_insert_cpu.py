@@ -3,12 +3,12 @@ the checker, what the bounds of a 200-fragment sample do on the whole-path workl
 -insert_hist / -insert_auto through the C++ parser and the Python mirror."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
+from abi_header import header_structs
 import insert_checker as ic
 import insert_workloads as iw
 import pairs_checker as pc
@@ -157,8 +157,7 @@ def test_bounds_of_a_sample_hold_the_library(ora, kind, ragged):
 def test_insert_abi_mirror():
     hdr = open(os.path.join(ROOT, "include", "real_hip.h")).read()
     for name, cls, size in (("real_hip_insert_estimate", rlib.RealHipInsertEstimate, 40), ("real_hip_insert_stats", rlib.RealHipInsertStats, 56)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
-        names = [n for decl in re.findall(r"^\s*(?:double|uint\d+_t)\s+([a-z0-9_, ]+);", body, re.M) for n in decl.replace(" ", "").split(",")]
+        names = header_structs()[name]
         assert names == [n for n, _ in cls._fields_] and C.sizeof(cls) == size, names
     assert "#define REAL_HIP_INSERT_HIST_MAX_BINS %du" % rlib.REAL_HIP_INSERT_HIST_MAX_BINS in hdr and rlib.REAL_HIP_INSERT_HIST_MAX_BINS == ic.MAX_BINS
     assert "#define REAL_HIP_INSERT_MIN_COUNT %du" % rlib.REAL_HIP_INSERT_MIN_COUNT in hdr and rlib.REAL_HIP_INSERT_MIN_COUNT == ic.MIN_COUNT

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_header import header_structs
 import mate_search_checker as mc
 import mate_search_workloads as mw
 import pairs_checker as pc
@@ -115,10 +116,7 @@ def test_mate_search_abi_mirror():
     assert C.sizeof(rlib.RealHipPairParams) == 16 and C.sizeof(rlib.RealHipPairStats) == 32 and rlib.PAIR_DTYPE.itemsize == 40
     assert "#define REAL_HIP_ABI_VERSION 2" in hdr and re.search(r"REAL_HIP_K_COUNT = 8\b", hdr)
     for name, cls in (("real_hip_mate_search_params", rlib.RealHipMateSearchParams), ("real_hip_mate_search_stats", rlib.RealHipMateSearchStats)):
-        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, re.S).group(1)
-        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-        names = [re.sub(r"\[\d+\]", "", n) for decl in re.findall(r"^\s*(?:double|uint\d+_t)\s+([a-z0-9_, \[\]]+);", body, re.M)
-                 for n in decl.replace(" ", "").split(",")]
+        names = header_structs()[name]
         assert names == [f for f, _ in cls._fields_], (name, names)
     assert int(re.search(r"#define REAL_HIP_MATE_SEARCH_MAX_INSERT (\d+)u", hdr).group(1)) == rlib.REAL_HIP_MATE_SEARCH_MAX_INSERT >= 2000
     new = ["real_hip_pair_search", "real_hip_match_pairs_search", "real_hip_mate_search_stats_get"]

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_header import header_structs
 import pairs_all_checker as pac
 import pairs_checker as pc
 from real_amd import lib as rlib
@@ -81,8 +82,7 @@ def test_pair_all_abi_mirror():
     for name, at in offsets.items():
         assert getattr(rlib.RealHipPairHit, name).offset == at and rlib.PAIR_HIT_DTYPE.fields[name][1] == at, name
     hdr = open(os.path.join(ROOT, "include", "real_hip.h")).read()
-    body = re.search(r"typedef struct real_hip_pair_hit \{(.*?)\} real_hip_pair_hit;", hdr, re.S).group(1)
-    names = [n for decl in re.findall(r"^\s*(?:float|uint\d+_t)\s+([a-z0-9_, ]+);", body, re.M) for n in decl.replace(" ", "").split(",")]
+    names = header_structs()["real_hip_pair_hit"]
     assert names == list(rlib.PAIR_HIT_DTYPE.names), names
     assert C.sizeof(rlib.RealHipPairAllStats) == 56
     assert "#define REAL_HIP_ABI_VERSION 2" in hdr and re.search(r"REAL_HIP_K_COUNT = 8", hdr)

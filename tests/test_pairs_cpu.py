@@ -7,6 +7,7 @@ import re
 
 import numpy as np
 
+from abi_header import header_structs
 import pairs_checker as pc
 from real_amd import lib as rlib
 from real_amd import synth
@@ -118,8 +119,7 @@ def test_pair_abi_mirror():
     hdr = open(rlib.LIB_PATH.replace("real_amd/libreal_hip.so", "include/real_hip.h")).read()
     assert C.sizeof(rlib.RealHipPairParams) == 16 and C.sizeof(rlib.RealHipPairStats) == 32
     assert rlib.PAIR_DTYPE.itemsize == 40 and rlib.PAIR_DTYPE == pc.REC_DTYPE
-    body = re.search(r"typedef struct real_hip_pair \{(.*?)\} real_hip_pair;", hdr, re.S).group(1)
-    names = [n for decl in re.findall(r"^\s*(?:double|float|uint\d+_t)\s+([a-z0-9_, ]+);", body, re.M) for n in decl.replace(" ", "").split(",")]
+    names = header_structs()["real_hip_pair"]
     assert names == list(rlib.PAIR_DTYPE.names), names
     m = re.search(r"REAL_HIP_K_PAIR = (\d+),.*?REAL_HIP_K_PAIR_WAVE = (\d+),.*?REAL_HIP_K_COUNT = (\d+)", hdr, re.S)
     assert (int(m.group(1)), int(m.group(2)), int(m.group(3))) == (rlib.K_PAIR, rlib.K_PAIR_WAVE, 8)

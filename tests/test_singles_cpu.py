@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_header import header_structs
 import singles_checker as sc
 import singles_workloads as sw
 from real_amd import lib as rlib
@@ -83,11 +84,9 @@ def test_merge_is_associative_and_commutative():
 def test_single_abi_mirror():
     hdr = open(os.path.join(ROOT, "include", "real_hip.h")).read()
     assert rlib.SINGLE_DTYPE.itemsize == 16 and rlib.SINGLE_DTYPE == sc.REC_DTYPE
-    body = re.search(r"typedef struct real_hip_single \{(.*?)\} real_hip_single;", hdr, re.S).group(1)
-    names = re.findall(r"^\s*(?:float|uint\d+_t)\s+([a-z0-9_]+);", body, re.M)
+    names = header_structs()["real_hip_single"]
     assert names == list(rlib.SINGLE_DTYPE.names), names
-    body = re.search(r"typedef struct real_hip_single_stats \{(.*?)\} real_hip_single_stats;", hdr, re.S).group(1)
-    names = [n for decl in re.findall(r"^\s*(?:double|uint\d+_t)\s+([a-z0-9_, ]+);", body, re.M) for n in decl.replace(" ", "").split(",")]
+    names = header_structs()["real_hip_single_stats"]
     assert names == [n for n, _ in rlib.RealHipSingleStats._fields_] and C.sizeof(rlib.RealHipSingleStats) == 48, names
     for macro in ("REAL_HIP_SINGLE_K", "REAL_HIP_SINGLE_INVERTED", "REAL_HIP_SINGLE_STATE"):
         assert "#define %s(tag)" % macro in hdr
