@@ -724,6 +724,104 @@ typedef struct real_hip_dup_stats {
 } real_hip_dup_stats;
 int real_hip_dup_stats_get(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset);
 
+/* ---- mapping quality: how sure a placement is, from ALL candidate locations of its read (fragment), not only the top two the
+ * records keep.  The reference has no such output; the semantics are this project's own.  Everything is integer
+ * arithmetic on the candidate multiset: nothing depends on the order of hits, lanes, waves, index blocks or genome files, and
+ * every result can be checked bit for bit.  Off unless these entry points are called.
+ * LEVEL of a candidate, one level = half a bit of log2-odds:
+ *   scores on   L = (int32) floor(2 * v), v the candidate's value as a double: (double)score of a hit, (double)score1 +
+ *               (double)score2 of a concordant pair (exact); a value whose 2 * v lies outside int32 counts as INT32_MIN + 1 /
+ *               INT32_MAX (no score of this library's matchers comes near)
+ *   scores off  L = -REAL_HIP_MAPQ_MISMATCH_LEVELS * k, or * (k1 + k2) for a pair: six bits per mismatch.  This is a CONVENTION,
+ *               not a calibration: it only makes the mismatch counts comparable on the scale the scores live on.
+ * ACCUMULATOR (real_hip_mapq_acc, in/out across index blocks and genome files as uniqueinfo[] is): level = the highest level
+ * seen; n = the candidates seen, saturating at 2^32 - 1; cnt[j] = the candidates at level - j, saturating at 255; candidates
+ * more than REAL_HIP_MAPQ_LEVELS - 1 levels below `level` are dropped (they still count in n).  EMPTY: n = 0, level = INT32_MIN,
+ * every cnt 0; an accumulator with n = 0 is empty whatever its other fields say on input.  MERGE of two accumulators: align
+ * both to the larger level, shift the other's counts down (what leaves the window is dropped), add with saturation.  The merge
+ * is associative and commutative; the window's top only rises, so what is dropped lies outside the final window too, and the
+ * result is a function of the candidate multiset alone.  A hit must not appear twice across the lists folded into one
+ * accumulator (real_hip_match_all's lists of different index blocks and files satisfy this).
+ * QUALITY of a placement of level Lp against an accumulator: j = level - Lp.  If j < 0, j > 31 or cnt[j] == 0 the placement is
+ * UNLISTED (a placement only the mate search found is the case in mind): a one-candidate accumulator at Lp is merged into a
+ * copy first and j recomputed.  With W[j] = round(2^24 * 2^(-j/2)) and A[Q] = round(16 * 10^(Q/10)), the literals below:
+ *   S = sum over t of cnt[t] * W[t],  E = S - W[j],  MAPQ = max{ Q in 0..60 : E * A[Q] <= 16 * S }
+ * all in uint64 (S < 2^34, E * A[60] < 2^58): the phred-scaled share of the other candidates in the total weight, capped at
+ * 60.  A lone candidate gives 60, two candidates at one level 3.  An accumulator that is empty before the merge gives 60.  An
+ * unlisted placement more than 31 levels below `level` is dropped by that merge as any candidate is: W[j] counts as 0 for
+ * j > 31 and the quality is 0.                                                                                                  */
+#define REAL_HIP_MAPQ_LEVELS 32
+#define REAL_HIP_MAPQ_MISMATCH_LEVELS 12
+#define REAL_HIP_MAPQ_MAX 60u
+#define REAL_HIP_MAPQ_NONE 255u   /* the MAPQ of a read (mate) without a final placement: SAM's "not available" */
+#define REAL_HIP_MAPQ_W_INIT { 16777216, 11863283, 8388608, 5931642, 4194304, 2965821, 2097152, 1482910, 1048576, 741455, 524288, \
+        370728, 262144, 185364, 131072, 92682, 65536, 46341, 32768, 23170, 16384, 11585, 8192, 5793, 4096, 2896, 2048, 1448, 1024, \
+        724, 512, 362 }
+#define REAL_HIP_MAPQ_A_INIT { 16, 20, 25, 32, 40, 51, 64, 80, 101, 127, 160, 201, 254, 319, 402, 506, 637, 802, 1010, 1271, 1600, \
+        2014, 2536, 3192, 4019, 5060, 6370, 8019, 10095, 12709, 16000, 20143, 25358, 31924, 40190, 50596, 63697, 80190, 100953, \
+        127093, 160000, 201428, 253583, 319242, 401902, 505964, 636971, 801900, 1009532, 1270925, 1600000, 2014281, 2535829, \
+        3192420, 4019018, 5059644, 6369715, 8018996, 10095318, 12709252, 16000000 }
+typedef struct real_hip_mapq_acc {   /* 40 bytes, 8-byte aligned on the device */
+    int32_t  level;                  /* the highest level seen; INT32_MIN: empty                       */
+    uint32_t n;                      /* candidates seen, saturating                                    */
+    uint8_t  cnt[REAL_HIP_MAPQ_LEVELS]; /* cnt[j]: candidates at level - j, saturating at 255          */
+} real_hip_mapq_acc;
+/* Host-only helpers, of the standing of real_hip_insert_bounds (no ctx, no GPU; the arithmetic is the kernels', compiled from
+ * the same header).  merge: a := merge(a, b).  of: the quality (0..60) of a placement of level `level`; *unlisted (nullable)
+ * receives 1 if the placement was unlisted, else 0.  NULL a / b / acc: REAL_HIP_E_INVALID.                                     */
+int real_hip_mapq_acc_merge(real_hip_mapq_acc *a, const real_hip_mapq_acc *b);
+int real_hip_mapq_of(const real_hip_mapq_acc *acc, int32_t level, int *unlisted);
+/* The folds alone, on hit lists the caller holds.  real_hip_mapq_hits: the candidates of read i are hits[off[i] .. off[i+1]);
+ * staging and checks are those of real_hip_single_hits (on_device 0: all pointers host memory, 1: all device pointers, acc
+ * 8-byte aligned; the offsets start at 0 and do not run backwards; fresh != 0: acc[] is output only, 0: in/out).
+ * real_hip_mapq_pair_hits: the candidates of fragment i are the CONCORDANT pairs (the paired-end block above) among its two
+ * mates' lists; inputs and checks are those of real_hip_pair_hits.  Both use the ctx's -q; they need neither text nor index.    */
+int real_hip_mapq_hits(real_hip_ctx *ctx, const real_hip_hit *hits, const uint64_t *off, uint64_t n_reads, int on_device, int fresh,
+                       real_hip_mapq_acc *acc);
+int real_hip_mapq_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
+                            const uint32_t *len1, const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                            uint64_t n_pairs, int on_device, int fresh, real_hip_mapq_acc *acc);
+/* real_hip_match_all of the batch against the resident text and index block with the hits kept on the device (the hit buffer
+ * grows inside), then the fold: only the accumulators cross to the host (on_device 0 / 2; 1: acc is a device pointer).
+ * batch->fresh governs acc[].                                                                                                 */
+int real_hip_match_mapq(real_hip_ctx *ctx, const real_hip_batch *batch, real_hip_mapq_acc *acc);
+/* Everything real_hip_match_pairs_singles does, and in the same call the three folds from the same device-resident lists:
+ * acc_pair[] over the concordant pairs, acc1[] / acc2[] over each mate's hits.  pairs[] / singles*[] are bit for bit what
+ * real_hip_match_pairs_singles gives; batch1->fresh governs all six arrays.  Pairs across index blocks are not seen, as there.
+ * Placements that only the mate search finds are not candidates: they arrive as UNLISTED at the finish.                      */
+int real_hip_match_pairs_mapq(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                              const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs,
+                              real_hip_single *singles1, real_hip_single *singles2, real_hip_mapq_acc *acc_pair,
+                              real_hip_mapq_acc *acc1, real_hip_mapq_acc *acc2);
+/* The finish: from the final records and the accumulators to one byte per read.  WHICH PLACEMENT is the rule of the mismatch
+ * lists.  Single-end (real_hip_mapq): an info record of state 1 or 2 places read i; its level comes from score[i] with scores
+ * on (score must then be given) and from the record's errors field with scores off; out[i] is its quality against acc[i], and
+ * REAL_HIP_MAPQ_NONE for every other state.  Paired-end (real_hip_mapq_pairs): out[2i] is mate 1 and out[2i + 1] mate 2 of
+ * fragment i.  A Unique pair record gives both mates the quality of acc_pair[i] at the level of `best` (of k1 + k2 with scores
+ * off).  Otherwise, if singles are given (both or neither NULL; acc1 / acc2 may be NULL without them) and the pair record is
+ * NoMatch, a mate whose single record is Unique takes its quality from its own accumulator at the level of its single
+ * record's score / k.  Everything else gets REAL_HIP_MAPQ_NONE.  File ids play no part: the accumulators span the files.
+ * on_device 0: all pointers host memory (copied), 1: all device pointers (pairs and acc 8-byte, singles 16-byte aligned).
+ * n == 0 is valid.  NULL arrays with n > 0, one singles pointer without the other, more than 2^32 items:
+ * REAL_HIP_E_INVALID with a message, nothing launched.  Uses the ctx's -q; needs neither text nor index.                     */
+int real_hip_mapq(real_hip_ctx *ctx, const uint64_t *info, const float *score, const real_hip_mapq_acc *acc, uint64_t n,
+                  int on_device, uint8_t *out);
+int real_hip_mapq_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_single *singles1, const real_hip_single *singles2,
+                        const real_hip_mapq_acc *acc_pair, const real_hip_mapq_acc *acc1, const real_hip_mapq_acc *acc2, uint64_t n,
+                        int on_device, uint8_t *out /* 2 * n bytes */);
+/* work of the stage, accumulated since the last reset; kernel_ms: HIP events on the ctx's stream around the kernels        */
+typedef struct real_hip_mapq_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_mapq_stats), 0                                           */
+    uint64_t folded;        /* reads and fragments folded (a list each)                                           */
+    uint64_t candidates;    /* hits walked by the single folds + product cells walked by the pair folds           */
+    uint64_t handed_over;   /* lists / products beyond a lane's budget: folded by a wave each                     */
+    uint64_t placements;    /* placements the finish gave a quality                                               */
+    uint64_t unlisted;      /* of those, the ones that were not among their accumulator's candidates              */
+    uint64_t launches;      /* kernels launched                                                                   */
+    double   kernel_ms;
+} real_hip_mapq_stats;
+int real_hip_mapq_stats_get(real_hip_ctx *ctx, real_hip_mapq_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -2,6 +2,7 @@
 // launches.  No CPU fallback: every entry point either runs the HIP path or fails.
 #include "real_hip_internal.h"
 #include "pair_state.h"
+#include "mapq_stage.h"
 
 #include <chrono>
 #include <cmath>
@@ -241,6 +242,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
+    rh_mapq_release(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -1010,6 +1012,128 @@ extern "C" int real_hip_single_stats_get(real_hip_ctx *ctx, real_hip_single_stat
     return stats_get(ctx, out, reset, "single stats struct_size", rh_single_stats);
 }
 
+// ---- mapping quality (mapq.hip): the in/out accumulators of `count` arrays (device records: 8-byte aligned)
+static int stage_mapq_accs(const RhStaging &io, int count, real_hip_mapq_acc *const accs[], uint64_t n, int fresh, real_hip_mapq_acc *d_accs[])
+{
+    int rc = REAL_HIP_OK;
+    for (int m = 0; m < count && !rc; ++m) {
+        if (!io.host && ((uintptr_t)accs[m] & 7u)) return rh_fail(io.ctx, REAL_HIP_E_INVALID, "the mapping quality accumulators must be 8-byte aligned", hipSuccess);
+        rc = io.inout(rh_mapq_stage(io.ctx).acc[m], accs[m], n, fresh != 0, d_accs[m]);
+    }
+    return rc;
+}
+
+extern "C" int real_hip_mapq_hits(real_hip_ctx *ctx, const real_hip_hit *hits, const uint64_t *off, uint64_t n_reads, int on_device, int fresh,
+                                  real_hip_mapq_acc *acc)
+{
+    RH_ENTER(ctx);
+    int rc;
+    const uint64_t n = n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
+    if (!off || !acc) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / accumulators", hipSuccess);
+    const real_hip_hit *const hv[2] = {hits, nullptr};
+    const uint64_t *const ov[2] = {off, nullptr};
+    MateLists L;
+    real_hip_mapq_acc *const av[1] = {acc};
+    real_hip_mapq_acc *d_acc[2] = {nullptr, nullptr};
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    if ((rc = stage_hit_lists(ctx, hv, ov, nullptr, n, on_device != 0, L, 1))) return rc;
+    rc = stage_mapq_accs(io, 1, av, n, fresh, d_acc);
+    if (!rc) rc = rh_launch_mapq_fold(ctx, 1, L, n, fresh, d_acc);
+    if (!rc) rc = io.back(acc, d_acc[0], n, "download of the mapping quality accumulators");
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_mapq_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_hit *hits1, const uint64_t *off1,
+                                       const uint32_t *len1, const real_hip_hit *hits2, const uint64_t *off2, const uint32_t *len2,
+                                       uint64_t n_pairs, int on_device, int fresh, real_hip_mapq_acc *acc)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc) return rc;
+    const uint64_t n = n_pairs;
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
+    if (!off1 || !off2 || !len1 || !len2 || !acc) return rh_fail(ctx, REAL_HIP_E_INVALID, "null offsets / lengths / accumulators", hipSuccess);
+    const real_hip_hit *const hits[2] = {hits1, hits2};
+    const uint64_t *const off[2] = {off1, off2};
+    const uint32_t *const len[2] = {len1, len2};
+    MateLists L;
+    real_hip_mapq_acc *const av[1] = {acc};
+    real_hip_mapq_acc *d_acc[1] = {nullptr};
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    if ((rc = stage_hit_lists(ctx, hits, off, len, n, on_device != 0, L))) return rc;
+    rc = stage_mapq_accs(io, 1, av, n, fresh, d_acc);
+    if (!rc) rc = rh_launch_mapq_pair_fold(ctx, *pp, L, n, fresh, d_acc[0]);
+    if (!rc) rc = io.back(acc, d_acc[0], n, "download of the mapping quality accumulators");
+    return rh_sync_tail(ctx, rc);
+}
+
+// the finish of n reads (pairs null) or fragments
+static int mapq_finish_run(real_hip_ctx *ctx, const uint64_t *info, const float *score, const real_hip_pair *pairs, const real_hip_single *const singles[2],
+                           const real_hip_mapq_acc *const accs[3], uint64_t n, int on_device, uint8_t *out)
+{
+    int rc;
+    RhMapqStage &S = rh_mapq_stage(ctx);
+    const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
+    const bool have_singles = pairs && singles[0];
+    if (!io.host && (((uintptr_t)pairs & 7u) || (have_singles && (((uintptr_t)singles[0] | (uintptr_t)singles[1]) & 15u))))
+        return rh_fail(ctx, REAL_HIP_E_INVALID, "mapq: the pair records must be 8-byte, the single records 16-byte aligned", hipSuccess);
+    const uint64_t *d_info = info;
+    const float *d_score = score;
+    const real_hip_pair *d_pairs = pairs;
+    const real_hip_single *d_singles[2] = {nullptr, nullptr};
+    const real_hip_mapq_acc *d_accs[3] = {nullptr, nullptr, nullptr};
+    uint8_t *d_out = out;
+    if (pairs) rc = io.in(S.rec, pairs, n, d_pairs);
+    else rc = io.in(S.rec, info, n, d_info);
+    if (!rc && score) rc = io.in(S.score, score, n, d_score);
+    for (int m = 0; m < 2 && !rc && have_singles; ++m) rc = io.in(S.sg[m], singles[m], n, d_singles[m]);
+    for (int m = 0; m < 3 && !rc; ++m) {
+        if (!accs[m]) continue;
+        if (!io.host && ((uintptr_t)accs[m] & 7u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "the mapping quality accumulators must be 8-byte aligned", hipSuccess);
+        rc = io.in(S.acc[m], accs[m], n, d_accs[m]);
+    }
+    const uint64_t n_out = pairs ? 2 * n : n;
+    if (!rc) rc = io.inout(S.out, out, n_out, true, d_out); // (an output: nothing is uploaded)
+    if (!rc) rc = rh_launch_mapq_finish(ctx, d_info, d_score, d_pairs, have_singles ? d_singles : nullptr, d_accs, n, d_out);
+    if (!rc) rc = io.back(out, d_out, n_out, "download of the mapping qualities");
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_mapq(real_hip_ctx *ctx, const uint64_t *info, const float *score, const real_hip_mapq_acc *acc, uint64_t n, int on_device,
+                             uint8_t *out)
+{
+    RH_ENTER(ctx);
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return stage_invalid(ctx, "mapq", "more than 2^32 reads in one call");
+    if (!info || !acc || !out) return stage_invalid(ctx, "mapq", "null info / accumulators / out");
+    if (ctx->prm.scores && !score) return stage_invalid(ctx, "mapq", "null score with scores on");
+    const real_hip_mapq_acc *const accs[3] = {acc, nullptr, nullptr};
+    return mapq_finish_run(ctx, info, ctx->prm.scores ? score : nullptr, nullptr, nullptr, accs, n, on_device, out);
+}
+
+extern "C" int real_hip_mapq_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_single *singles1, const real_hip_single *singles2,
+                                   const real_hip_mapq_acc *acc_pair, const real_hip_mapq_acc *acc1, const real_hip_mapq_acc *acc2, uint64_t n,
+                                   int on_device, uint8_t *out)
+{
+    RH_ENTER(ctx);
+    if ((singles1 == nullptr) != (singles2 == nullptr)) return stage_invalid(ctx, "mapq", "one singles pointer without the other");
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return stage_invalid(ctx, "mapq", "more than 2^32 pairs in one call");
+    if (!pairs || !acc_pair || !out) return stage_invalid(ctx, "mapq", "null pairs / accumulators / out");
+    if (singles1 && (!acc1 || !acc2)) return stage_invalid(ctx, "mapq", "singles without the mates' accumulators");
+    const real_hip_single *const singles[2] = {singles1, singles2};
+    const real_hip_mapq_acc *const accs[3] = {acc_pair, singles1 ? acc1 : nullptr, singles1 ? acc2 : nullptr};
+    return mapq_finish_run(ctx, nullptr, nullptr, pairs, singles, accs, n, on_device, out);
+}
+
+extern "C" int real_hip_mapq_stats_get(real_hip_ctx *ctx, real_hip_mapq_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "mapq stats struct_size", rh_mapq_stats);
+}
+
 // ---- insert sizes (insert_hist.hip): staging as real_hip_pair_hits does it
 extern "C" int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair *pairs, const uint32_t *len1, const uint32_t *len2,
                                          uint64_t n_pairs, int on_device, int fresh, uint32_t n_bins, uint64_t *hist)
@@ -1474,7 +1598,8 @@ static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_
 // real_hip_match_pairs, and with sp (real_hip_match_pairs_search) the mate search behind the join; with singles
 // (real_hip_match_pairs_singles: both arrays or none) each mate's hit list is folded into its records while it is resident
 static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2, const real_hip_pair_params *pp,
-                           const real_hip_mate_search_params *sp, real_hip_pair *pairs, real_hip_single *const singles[2] = nullptr)
+                           const real_hip_mate_search_params *sp, real_hip_pair *pairs, real_hip_single *const singles[2] = nullptr,
+                           real_hip_mapq_acc *const accs[3] = nullptr)
 {
     int rc;
     real_hip_batch bv[2];
@@ -1498,10 +1623,17 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
         rc = stage_singles(io, 2, singles, n, fresh, d_singles);
         if (!rc) rc = rh_launch_single(ctx, 2, L, n, ctx->fileid, fresh, d_singles);
     }
+    real_hip_mapq_acc *d_accs[3] = {nullptr, nullptr, nullptr};
+    if (!rc && accs) { // the pair's, then the two mates': seed hits only, as the singles
+        rc = stage_mapq_accs(io, 3, accs, n, fresh, d_accs);
+        if (!rc) rc = rh_launch_mapq_pair_fold(ctx, *pp, L, n, fresh, d_accs[0]);
+        if (!rc) rc = rh_launch_mapq_fold(ctx, 2, L, n, fresh, d_accs + 1);
+    }
     if (!rc && sp) // the records of the join are the search's in/out records
         rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, ctx->fileid, 0, d_pairs);
     if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
     if (!rc && singles) rc = download_singles(io, 2, singles, n, d_singles);
+    for (int m = 0; m < 3 && !rc && accs; ++m) rc = io.back(accs[m], d_accs[m], n, "download of the mapping quality accumulators");
     rc = rh_sync_tail(ctx, rc);
     return rc || !sp ? rc : rh_mate_search_finish(ctx);
 }
@@ -1534,6 +1666,68 @@ extern "C" int real_hip_match_pairs_singles(real_hip_ctx *ctx, const real_hip_ba
     if (!singles1 || !singles2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null singles", hipSuccess);
     real_hip_single *const singles[2] = {singles1, singles2};
     return match_pairs_run(ctx, batch1, batch2, pp, sp, pairs, singles);
+}
+
+extern "C" int real_hip_match_pairs_mapq(real_hip_ctx *ctx, const real_hip_batch *batch1, const real_hip_batch *batch2,
+                                         const real_hip_pair_params *pp, const real_hip_mate_search_params *sp, real_hip_pair *pairs,
+                                         real_hip_single *singles1, real_hip_single *singles2, real_hip_mapq_acc *acc_pair,
+                                         real_hip_mapq_acc *acc1, real_hip_mapq_acc *acc2)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc || (sp && (rc = search_params_check(ctx, pp, sp)))) return rc;
+    if (!singles1 || !singles2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null singles", hipSuccess);
+    if (!acc_pair || !acc1 || !acc2) return rh_fail(ctx, REAL_HIP_E_INVALID, "null mapping quality accumulators", hipSuccess);
+    real_hip_single *const singles[2] = {singles1, singles2};
+    real_hip_mapq_acc *const accs[3] = {acc_pair, acc1, acc2};
+    return match_pairs_run(ctx, batch1, batch2, pp, sp, pairs, singles, accs);
+}
+
+// matchAll of one batch with the hits kept on the device, in mate 1's buffers: pair_hits[0] / pair_off[0] hold the unified hit
+// lists and their n + 1 offsets, *total the hits.  The buffer only ever grows (pair_cap, the size BOTH mates' buffers have at
+// least, stays true); a match that needs more reports the size and is done again.
+static int match_resident(real_hip_ctx *ctx, const real_hip_batch &bv, uint64_t *total)
+{
+    int rc;
+    const uint64_t n = bv.n_reads;
+    if ((rc = rh_reserve(ctx, ctx->pair_off[0], (n + 1) * 8))) return rc;
+    uint64_t want = n + n / 4 + 1024;
+    for (int attempt = 0;; ++attempt) {
+        if ((rc = rh_reserve(ctx, ctx->pair_hits[0], want * sizeof(real_hip_hit)))) return rc;
+        const uint64_t cap = ctx->pair_hits[0].cap / sizeof(real_hip_hit);
+        Staged s;
+        rc = match_all_run(ctx, bv, true, (real_hip_hit *)ctx->pair_hits[0].p, cap, total, (uint64_t *)ctx->pair_off[0].p, &s);
+        if (rc != REAL_HIP_E_OVERFLOW) return rc;
+        if (attempt >= 2) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffer of the mapping quality fold kept overflowing", hipSuccess);
+        if (*total > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "more than 2^32 hits in one batch", hipSuccess);
+        want = *total;
+    }
+}
+
+extern "C" int real_hip_match_mapq(real_hip_ctx *ctx, const real_hip_batch *batch, real_hip_mapq_acc *acc)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = batch_view(ctx, batch, bv);
+    if (rc) return rc;
+    if (!ctx->have_text || !ctx->have_index) return rh_fail(ctx, REAL_HIP_E_STATE, "text and index must be set", hipSuccess);
+    const uint64_t n = bv.n_reads;
+    if (!n) return REAL_HIP_OK;
+    if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
+    if (!acc) return rh_fail(ctx, REAL_HIP_E_INVALID, "null mapping quality accumulators", hipSuccess);
+    uint64_t total = 0;
+    if ((rc = match_resident(ctx, bv, &total))) return rc;
+    MateLists L;
+    memset(&L, 0, sizeof L);
+    L.h[0] = (const uint4 *)ctx->pair_hits[0].p; L.o[0] = (const uint64_t *)ctx->pair_off[0].p; L.total[0] = total;
+    const int fresh = bv.fresh != 0;
+    real_hip_mapq_acc *const av[1] = {acc};
+    real_hip_mapq_acc *d_acc[2] = {nullptr, nullptr};
+    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
+    rc = stage_mapq_accs(io, 1, av, n, fresh, d_acc);
+    if (!rc) rc = rh_launch_mapq_fold(ctx, 1, L, n, fresh, d_acc);
+    if (!rc) rc = io.back(acc, d_acc[0], n, "download of the mapping quality accumulators");
+    return rh_sync_tail(ctx, rc);
 }
 
 extern "C" int real_hip_mate_search_stats_get(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset)

@@ -72,7 +72,7 @@ void RealOptions::printHelp() const
               << "-vcf_minqual <Q: with -vcf, a call needs QUAL >= Q, default=20>\n"
               << "-vcf_mindepth <D: with -vcf, a call needs D bases of sufficient quality, default=4>\n"
               << "-sam <file: after the output pass, write EVERY read as a SAM line (header: one @SQ per fragment of every genome file): a\n"
-              << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255, CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
+              << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255 (-mapq 1: 0..60), CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
               << "   its mismatch list, computed on one fresh context on -device (ZS:f: the score, with -q 1); an unplaced read with FLAG 4.\n"
               << "   With -p2 the final placement of a mate is its Unique pair's, else -- for a fragment without any concordant pair -- its\n"
               << "   own unique one (the rule of -unpaired), and the lines carry the pair flags, RNEXT / PNEXT and TLEN (the outer distance,\n"
@@ -85,6 +85,13 @@ void RealOptions::printHelp() const
               << "   -sam lines carry FLAG 1024 (both mates of a fragment), -pileup / -pileup_depth leave them out; -o and -unpaired are\n"
               << "   unchanged; a summary line goes to standard error; needs -u 1, not with -pairs_all 1, default=0>\n"
               << "-dedup_minq <n: with -dedup 1, a base quality below n does not count in the sum, 0..63, default=15>\n"
+              << "-mapq <0|1: mapping qualities: every candidate location of a read (with -p2: every concordant pair of a fragment, and every\n"
+              << "   hit of a mate) is counted by its score on the device, over all index blocks and genome files; after the matching a\n"
+              << "   finally placed read gets MAPQ 0..60 from the share of the other candidates (60: none): -sam writes it in the MAPQ\n"
+              << "   column instead of 255, and a summary line goes to standard error; -o is unchanged; the single-end matcher runs twice;\n"
+              << "   needs -u 1, not with -pairs_all 1, default=0>\n"
+              << "-pileup_minmapq <Q: with -mapq 1 and -pileup / -pileup_depth / -vcf, placements of a mapping quality below Q are left out of\n"
+              << "   them (-o and -sam are unchanged), 0..60, default=0>\n"
               << "-device <first HIP device, default=0>\n-gpus <number of devices, default=1>\n"
               << "-index <device|host, where the signature lists are sorted, default=device>\n"
               << "-block <positions per index block, default=as many as fit>\n-batch <reads per device batch>\n"
@@ -158,6 +165,8 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-sam") { samfilename = need("-sam"); sam_given = true; i += 2; }
         else if (a == "-dedup") { dedup = atoi(need("-dedup").c_str()) != 0; dedup_given = true; i += 2; }
         else if (a == "-dedup_minq") { dedup_minq = strtol(need("-dedup_minq").c_str(), 0, 10); dedup_minq_given = true; i += 2; }
+        else if (a == "-mapq") { mapq = atoi(need("-mapq").c_str()) != 0; i += 2; }
+        else if (a == "-pileup_minmapq") { pileup_minmapq = strtol(need("-pileup_minmapq").c_str(), 0, 10); pileup_minmapq_given = true; i += 2; }
         else if (a == "-table_kind") { table_kind = atoi(need("-table_kind").c_str()); i += 2; }
         else if (a == "-h") { printHelp(); i += 1; }
         else { std::cerr << "Ignoring unknown argument " << a << std::endl; i += 1; }
@@ -268,6 +277,15 @@ RealOptions::RealOptions(int argc, char *argv[])
     if (dedup_minq < 0 || dedup_minq > 63) throw std::runtime_error("-dedup_minq must be in 0..63.");
     if (pileup_minq_given && !pileup_given && !vcf_given) throw std::runtime_error("-pileup_minq is only meaningful with -pileup.");
     if (pileup_minq > 63) throw std::runtime_error("-pileup_minq takes a quality of at most 63.");
+    if (mapq) { // mapping quality: loud errors before anything runs
+        if (!match_unique) throw std::runtime_error("-mapq 1 rates the unique placement of a read: it cannot be combined with -u 0.");
+        if (pairs_all) throw std::runtime_error("-mapq 1 rates the unique placement of a fragment: it cannot be combined with -pairs_all 1.");
+    }
+    if (pileup_minmapq_given) {
+        if (!mapq) throw std::runtime_error("-pileup_minmapq needs -mapq 1.");
+        if (!pileup_given && !pileup_depth_given && !vcf_given) throw std::runtime_error("-pileup_minmapq is only meaningful with -pileup / -vcf.");
+        if (pileup_minmapq < 0 || pileup_minmapq > (long)REAL_HIP_MAPQ_MAX) throw std::runtime_error("-pileup_minmapq must be in 0..60.");
+    }
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
         if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");
         if (gpus > 1) throw std::runtime_error("-p2 (paired-end reads) runs on one device: it cannot be combined with -gpus > 1.");

@@ -68,6 +68,9 @@ struct RealOptions {
     bool dedup = false;               // -dedup: mark the copies of a placed read / fragment (real_hip_mark_duplicates*): FLAG 1024 in -sam, left out of -pileup
     long dedup_minq = 15;             // -dedup_minq: a base quality below it does not count in the sum that chooses the copy that stays
     bool dedup_given = false, dedup_minq_given = false;
+    bool mapq = false;                // -mapq: mapping qualities from all candidates of a read / fragment (real_hip_match_mapq, real_hip_match_pairs_mapq, real_hip_mapq*): MAPQ in -sam
+    long pileup_minmapq = 0;          // -pileup_minmapq: with -mapq 1, placements of a lower quality are left out of -pileup / -pileup_depth / -vcf
+    bool pileup_minmapq_given = false;
     uint64_t insert_auto = 0;         // -insert_auto: fragments the insert bounds are estimated from before the run (real_hip_insert_bounds), 0 = off
     bool insert_flags_given = false;  // (either flag was on the command line: an error without -p2)
     uint64_t chunk_bytes = 256ull << 20; // -chunk: bytes of read-file text handed to a device at a time (< 4 GiB)

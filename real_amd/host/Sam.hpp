@@ -49,6 +49,7 @@ struct SamPlace {
     unsigned file = 0, frag = 0;
     uint64_t pos = 0; // 0-based in the file's text
     float score = 0.f;
+    unsigned mapq = REAL_HIP_MAPQ_NONE; // -mapq 1: the placement's mapping quality (real_hip_mapq*); 255: not available
 };
 // single-end: a record of state 1 or 2
 inline SamPlace samPlace(const Record &r, float score)
@@ -108,7 +109,7 @@ inline void appendSam(std::string &out, const ReadView &r, const SamRefs &R, con
     const uint64_t pos1 = at ? at->pos - R.starts[at->file][at->frag] + 1 : 0;
     if (at) out += R.names[at->file][at->frag]; else out.push_back('*');
     out.push_back('\t'); samPutInt(out, (int64_t)pos1);
-    if (self.placed) { out += "\t255\t"; samPutInt(out, (int64_t)patl); out += "M\t"; } else out += "\t0\t*\t";
+    if (self.placed) { out.push_back('\t'); samPutInt(out, (int64_t)self.mapq); out.push_back('\t'); samPutInt(out, (int64_t)patl); out += "M\t"; } else out += "\t0\t*\t";
     // RNEXT PNEXT TLEN
     if (!mate || !at) out += "*\t0\t";
     else if (self.placed && mate->placed) {

@@ -703,6 +703,24 @@ const Rec *withoutDuplicates(const std::vector<Rec> &records, const std::vector<
     return scratch.data();
 }
 
+// ---- -mapq 1: the qualities of the final placements (real_hip_mapq*) ------------------------------------------
+// The accumulators are kept for the run beside the records and fold over every index block and genome file; behind "All
+// done.", where -dedup marks, one call on the first context turns them into one byte per read (two per fragment), and the
+// summary line goes to standard error.  -sam writes the bytes; -pileup_minmapq masks with them as -dedup masks.
+const real_hip_mapq_acc kNoCandidates = {INT32_MIN, 0, {0}};
+void reportMapq(real_hip_ctx *h, const std::vector<uint8_t> &mapq)
+{
+    real_hip_mapq_stats st;
+    memset(&st, 0, sizeof st);
+    st.struct_size = sizeof st;
+    check(h, real_hip_mapq_stats_get(h, &st, 1), "real_hip_mapq_stats_get");
+    uint64_t sum = 0, placed = 0;
+    for (const uint8_t q : mapq)
+        if (q != REAL_HIP_MAPQ_NONE) { sum += q; ++placed; }
+    fprintf(stderr, "mapq: placements=%llu unlisted=%llu mean=%.3f\n", (unsigned long long)st.placements, (unsigned long long)st.unlisted,
+            placed ? (double)sum / (double)placed : 0.0);
+}
+
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
 int matchUnique(const RealOptions &o)
 {
@@ -714,6 +732,9 @@ int matchUnique(const RealOptions &o)
     std::vector<float> score;
     std::vector<real_hip_read_sum> sums; // -dedup: kept for the run beside info
     std::vector<uint8_t> dup;            // -dedup: one mark per read, from behind "All done." on
+    std::vector<real_hip_mapq_acc> acc;  // -mapq: kept for the run beside info
+    std::vector<uint8_t> mapq;           // -mapq: one quality per read, from behind "All done." on
+    std::vector<uint8_t> drop;           // what the pileup leaves out: dup, and with -pileup_minmapq the placements below it
     uint64_t numpat = 0;
     bool counted = false;
     auto grow = [&](uint64_t n) {
@@ -721,6 +742,7 @@ int matchUnique(const RealOptions &o)
             const uint64_t to = std::max<uint64_t>(n, info.size() + info.size() / 2);
             info.resize(to, 0);
             if (o.dedup) sums.resize(to);
+            if (o.mapq) acc.resize(to, kNoCandidates);
             if (o.scores) score.resize(to, -FLT_MAX);
         }
     };
@@ -740,6 +762,8 @@ int matchUnique(const RealOptions &o)
                           "real_hip_match_unique");
                 if (o.dedup && !counted && rb.n_reads) // (the first pass over the reads: no pass of its own)
                     check(ctx[g]->h, real_hip_read_summary(ctx[g]->h, &rb, (uint32_t)o.dedup_minq, sums.data() + items[g].first_id), "real_hip_read_summary");
+                if (o.mapq && rb.n_reads) // (every index block of every file: the candidates of a read are all its hits)
+                    check(ctx[g]->h, real_hip_match_mapq(ctx[g]->h, &rb, acc.data() + items[g].first_id), "real_hip_match_mapq");
             });
             T.match += now_s() - tm;
             if (counted) std::cerr << "\r                                                              \r" << (double)end / (numpat ? numpat : 1) << std::flush;
@@ -755,6 +779,19 @@ int matchUnique(const RealOptions &o)
         check(ctx[0]->h, real_hip_mark_duplicates(ctx[0]->h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
         T.match += now_s() - tm;
         reportDuplicates(ctx[0]->h, o);
+    }
+    if (o.mapq) {
+        mapq.assign(numpat, REAL_HIP_MAPQ_NONE);
+        const double tm = now_s();
+        check(ctx[0]->h, real_hip_mapq(ctx[0]->h, info.data(), o.scores ? score.data() : nullptr, acc.data(), numpat, 0, mapq.data()), "real_hip_mapq");
+        T.match += now_s() - tm;
+        reportMapq(ctx[0]->h, mapq);
+    }
+    drop = dup;
+    if (o.pileup_minmapq > 0) {
+        drop.resize(numpat, 0);
+        for (uint64_t i = 0; i < numpat; ++i)
+            if (mapq[i] != REAL_HIP_MAPQ_NONE && mapq[i] < o.pileup_minmapq) drop[i] = 1;
     }
     // output, in read order (PatternIdReader re-stream, :1438-1486)
     OutFile out(o.outputfilename);
@@ -779,13 +816,13 @@ int matchUnique(const RealOptions &o)
     for (uint64_t i = 0; i < numpat; ++i) { const unsigned st = (unsigned)(info[i] >> 61); unique += (st == 1 || st == 2); }
     std::cerr << "unique: " << unique << std::endl; // :1488
     if (passesBehindOutput(o)) ctx.clear(); // (the matching contexts go before the pass's own one comes)
-    std::vector<uint64_t> kept; // -dedup: a batch's records without the duplicates
+    std::vector<uint64_t> kept; // -dedup / -pileup_minmapq: a batch's records without what they leave out
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
                 if (!it.batch.n_reads) continue;
                 if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
-                check(pc[0]->h, (calls ? real_hip_call_add : real_hip_pileup_add)(pc[0]->h, &it.batch, withoutDuplicates(info, dup, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
+                check(pc[0]->h, (calls ? real_hip_call_add : real_hip_pileup_add)(pc[0]->h, &it.batch, withoutDuplicates(info, drop, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
                       calls ? "real_hip_call_add" : "real_hip_pileup_add");
             }
         });
@@ -804,6 +841,7 @@ int matchUnique(const RealOptions &o)
                 formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
                     SamPlace at = samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f);
                     at.duplicate = o.dedup && dup[base + i];
+                    if (o.mapq) at.mapq = mapq[base + i];
                     appendSamRead(s, src[i], refs, at, fi, last, L.mm.data() + L.off[i], L.off[i + 1] - L.off[i], o.scores);
                 });
             }
@@ -915,16 +953,22 @@ int matchPairs(const RealOptions &o)
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
-    const bool singles = unpaired || o.sam_given; // (-sam places the mates of a fragment without a pair as -unpaired prints them)
+    const bool singles = unpaired || o.sam_given || o.mapq; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them)
     std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
     std::vector<real_hip_read_sum> sums1, sums2;     // -dedup: the mates' summaries, kept for the run beside pairs
     std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
+    std::vector<real_hip_mapq_acc> accp, acc1, acc2; // -mapq: the fragments' and the mates' accumulators, kept for the run beside pairs
+    std::vector<uint8_t> mapq;                       // -mapq: two qualities per fragment, from behind "All done." on
+    std::vector<uint8_t> drop;                       // what the pileup leaves out: dup, and with -pileup_minmapq the fragments below it
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
     // the call of a batch, for the run and for the probe of -insert_auto
-    auto matchBatch = [&](const real_hip_batch &rb1, const real_hip_batch &rb2, real_hip_pair *P, real_hip_single *S1, real_hip_single *S2) {
-        if (singles) check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2), "real_hip_match_pairs_singles");
+    // (A: the three accumulators of -mapq 1, null for the probe)
+    auto matchBatch = [&](const real_hip_batch &rb1, const real_hip_batch &rb2, real_hip_pair *P, real_hip_single *S1, real_hip_single *S2,
+                          real_hip_mapq_acc *const A[3] = nullptr) {
+        if (A) check(h, real_hip_match_pairs_mapq(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2, A[0], A[1], A[2]), "real_hip_match_pairs_mapq");
+        else if (singles) check(h, real_hip_match_pairs_singles(h, &rb1, &rb2, &pp, o.mate_search ? &sp : nullptr, P, S1, S2), "real_hip_match_pairs_singles");
         else if (o.mate_search) check(h, real_hip_match_pairs_search(h, &rb1, &rb2, &pp, &sp, P), "real_hip_match_pairs_search");
         else check(h, real_hip_match_pairs(h, &rb1, &rb2, &pp, P), "real_hip_match_pairs");
     };
@@ -984,10 +1028,13 @@ int matchPairs(const RealOptions &o)
             if (seen + n > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n, pairs.size() + pairs.size() / 2));
             if (singles && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
             if (o.dedup && pairs.size() > sums1.size()) { sums1.resize(pairs.size()); sums2.resize(pairs.size()); }
+            if (o.mapq && pairs.size() > accp.size())
+                for (auto *a : {&accp, &acc1, &acc2}) a->resize(pairs.size(), kNoCandidates);
             real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
+            real_hip_mapq_acc *const A[3] = {o.mapq ? accp.data() + seen : nullptr, o.mapq ? acc1.data() + seen : nullptr, o.mapq ? acc2.data() + seen : nullptr};
             const double tm = now_s();
-            matchBatch(rb1, rb2, pairs.data() + seen, singles ? singles1.data() + seen : nullptr, singles ? singles2.data() + seen : nullptr);
+            matchBatch(rb1, rb2, pairs.data() + seen, singles ? singles1.data() + seen : nullptr, singles ? singles2.data() + seen : nullptr, o.mapq ? A : nullptr);
             if (o.dedup && fi == 0) { // (the first pass over the reads: no pass of its own)
                 check(h, real_hip_read_summary(h, &rb1, (uint32_t)o.dedup_minq, sums1.data() + seen), "real_hip_read_summary");
                 check(h, real_hip_read_summary(h, &rb2, (uint32_t)o.dedup_minq, sums2.data() + seen), "real_hip_read_summary");
@@ -1005,6 +1052,19 @@ int matchPairs(const RealOptions &o)
         check(h, real_hip_mark_duplicates_pairs(h, pairs.data(), sums1.data(), sums2.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_pairs");
         T.match += now_s() - tm;
         reportDuplicates(h, o);
+    }
+    if (o.mapq) {
+        mapq.assign(2 * numpat, REAL_HIP_MAPQ_NONE);
+        const double tm = now_s();
+        check(h, real_hip_mapq_pairs(h, pairs.data(), singles1.data(), singles2.data(), accp.data(), acc1.data(), acc2.data(), numpat, 0, mapq.data()), "real_hip_mapq_pairs");
+        T.match += now_s() - tm;
+        reportMapq(h, mapq);
+    }
+    drop = dup;
+    if (o.pileup_minmapq > 0) { // (both mates of a Unique fragment carry the fragment's quality: "either below" is "both below")
+        drop.resize(numpat, 0);
+        for (uint64_t i = 0; i < numpat; ++i)
+            if (pairs[i].state == REAL_HIP_PAIR_UNIQUE && mapq[2 * i] < o.pileup_minmapq) drop[i] = 1;
     }
     OutFile out(o.outputfilename);
     std::unique_ptr<OutFile> uout(unpaired ? new OutFile(o.unpairedfilename, true) : nullptr);
@@ -1068,7 +1128,7 @@ int matchPairs(const RealOptions &o)
         else throw std::runtime_error("real_hip_insert_bounds failed");
     }
     if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
-    std::vector<real_hip_pair> kept; // -dedup: a batch's records without the duplicates
+    std::vector<real_hip_pair> kept; // -dedup / -pileup_minmapq: a batch's records without what they leave out
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
@@ -1077,7 +1137,7 @@ int matchPairs(const RealOptions &o)
             if (!n) break;
             if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
             const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
-            check(pc[0]->h, (calls ? real_hip_call_add_pairs : real_hip_pileup_add_pairs)(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, dup, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
+            check(pc[0]->h, (calls ? real_hip_call_add_pairs : real_hip_pileup_add_pairs)(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, drop, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
                   calls ? "real_hip_call_add_pairs" : "real_hip_pileup_add_pairs");
             seen += n;
         }
@@ -1100,6 +1160,7 @@ int matchPairs(const RealOptions &o)
                 const ReadView r[2] = {v1[i], v2[i]};
                 SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
                 at[0].duplicate = at[1].duplicate = o.dedup && dup[seen + i]; // (a duplicate fragment is Unique: both mates have lines)
+                if (o.mapq) { at[0].mapq = mapq[2 * (seen + i)]; at[1].mapq = mapq[2 * (seen + i) + 1]; }
                 appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
             });
             seen += n;

@@ -53,6 +53,8 @@ ABI_SYMBOLS = [
     "real_hip_call_variants", "real_hip_call_end", "real_hip_call_stats_get",
     "real_hip_mismatches", "real_hip_mismatches_pairs", "real_hip_mismatch_stats_get",
     "real_hip_read_summary", "real_hip_mark_duplicates", "real_hip_mark_duplicates_pairs", "real_hip_dup_stats_get",
+    "real_hip_mapq_acc_merge", "real_hip_mapq_of", "real_hip_mapq_hits", "real_hip_mapq_pair_hits", "real_hip_match_mapq",
+    "real_hip_match_pairs_mapq", "real_hip_mapq", "real_hip_mapq_pairs", "real_hip_mapq_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -182,6 +184,22 @@ assert READ_SUM_DTYPE.itemsize == 8
 
 DUP_STATS_FIELDS = ("reads", "placed", "groups", "duplicates", "launches", "kernel_ms")
 RealHipDupStats = _stats_struct("RealHipDupStats", DUP_STATS_FIELDS)
+
+
+# mapping quality (include/real_hip.h, "mapping quality"): real_hip_mapq_acc, the in/out accumulator of one read or fragment
+MAPQ_LEVELS, MAPQ_MISMATCH_LEVELS, MAPQ_MAX, MAPQ_NONE = 32, 12, 60, 255
+MAPQ_EMPTY_LEVEL = -(1 << 31)
+
+
+class RealHipMapqAcc(C.Structure):
+    """real_hip_mapq_acc: the candidates of one read or fragment by level (MAPQ_ACC_DTYPE is the same record as a numpy dtype)"""
+    _fields_ = [("level", C.c_int32), ("n", C.c_uint32), ("cnt", C.c_uint8 * MAPQ_LEVELS)]
+
+
+MAPQ_ACC_DTYPE = np.dtype(RealHipMapqAcc)
+assert MAPQ_ACC_DTYPE.itemsize == 40
+MAPQ_STATS_FIELDS = ("folded", "candidates", "handed_over", "placements", "unlisted", "launches", "kernel_ms")
+RealHipMapqStats = _stats_struct("RealHipMapqStats", MAPQ_STATS_FIELDS)
 
 
 class RealHipPairHit(C.Structure):
@@ -316,6 +334,15 @@ def load():
     L.real_hip_mark_duplicates.argtypes = [vp, vp, vp, u64, ci, vp]
     L.real_hip_mark_duplicates_pairs.argtypes = [vp, vp, vp, vp, u64, ci, vp]
     L.real_hip_dup_stats_get.argtypes = [vp, C.POINTER(RealHipDupStats), ci]
+    L.real_hip_mapq_acc_merge.argtypes = [vp, vp]
+    L.real_hip_mapq_of.argtypes = [vp, C.c_int32, C.POINTER(ci)]
+    L.real_hip_mapq_hits.argtypes = [vp, vp, vp, u64, ci, ci, vp]
+    L.real_hip_mapq_pair_hits.argtypes = [vp, pairp, vp, vp, vp, vp, vp, vp, u64, ci, ci, vp]
+    L.real_hip_match_mapq.argtypes = [vp, batch, vp]
+    L.real_hip_match_pairs_mapq.argtypes = [vp, batch, batch, pairp, searchp, vp, vp, vp, vp, vp, vp]
+    L.real_hip_mapq.argtypes = [vp, vp, vp, vp, u64, ci, vp]
+    L.real_hip_mapq_pairs.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, ci, vp]
+    L.real_hip_mapq_stats_get.argtypes = [vp, C.POINTER(RealHipMapqStats), ci]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
     L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
     L.real_hip_timing_enable.argtypes = [vp, ci]
@@ -328,6 +355,26 @@ def scoring_table(similarity=0.995, gc=0.41, trans=0.71, err=0.0, gcmut_bias=2.0
     LL = np.zeros(1024, dtype=np.float64)
     load().real_hip_scoring_table(similarity, gc, trans, err, gcmut_bias, LL.ctypes.data)
     return LL
+
+
+def mapq_acc_merge(a: np.ndarray, b: np.ndarray) -> np.ndarray:
+    """real_hip_mapq_acc_merge (host only): the merge of two accumulators (MAPQ_ACC_DTYPE records of one element) as a new one"""
+    out = np.array(a, dtype=MAPQ_ACC_DTYPE).reshape(1).copy()
+    other = np.ascontiguousarray(np.array(b, dtype=MAPQ_ACC_DTYPE).reshape(1))
+    rc = load().real_hip_mapq_acc_merge(out.ctypes.data, other.ctypes.data)
+    if rc != REAL_HIP_OK:
+        raise RealHipError(rc, "invalid argument")
+    return out[0]
+
+
+def mapq_of(acc: np.ndarray, level: int):
+    """real_hip_mapq_of (host only): (quality, unlisted) of a placement of `level` against one accumulator"""
+    rec = np.ascontiguousarray(np.array(acc, dtype=MAPQ_ACC_DTYPE).reshape(1))
+    unlisted = C.c_int(0)
+    q = load().real_hip_mapq_of(rec.ctypes.data, int(level), C.byref(unlisted))
+    if q < 0:
+        raise RealHipError(q, "invalid argument")
+    return int(q), bool(unlisted.value)
 
 
 def _ptr(a) -> Optional[int]:

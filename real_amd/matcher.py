@@ -170,6 +170,13 @@ def new_single_info(n: int) -> np.ndarray:
     return rec
 
 
+def new_mapq_acc(n: int) -> np.ndarray:
+    """the accumulators of n reads (fragments) before the first index block: empty (real_hip_mapq_acc)"""
+    rec = np.zeros(n, dtype=_lib.MAPQ_ACC_DTYPE)
+    rec["level"] = _lib.MAPQ_EMPTY_LEVEL
+    return rec
+
+
 def unpack_info(info: np.ndarray):
     """UniqueMatchInfo.hpp:29-39 -> state, fragment, errors, fileid, position."""
     rec = np.asarray(info, dtype=np.uint64)
@@ -711,6 +718,48 @@ class HipMatcher:
     def dup_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipDupStats, self._L.real_hip_dup_stats_get, reset)
 
+    # -- mapping quality (real_hip_mapq_acc accumulators; include/real_hip.h, "mapping quality") --
+    new_mapq_acc = staticmethod(new_mapq_acc)
+
+    def mapq_hits(self, hits, off, acc=None, fresh: Optional[bool] = None):
+        """real_hip_mapq_hits: the fold alone, on one read's lists as the caller holds them (numpy arrays of lib.HIT_DTYPE /
+        uint64, or device torch tensors of the same layout; device inputs need `acc` as a device tensor of 40-byte records)."""
+        on_device, n, ((hits, off, _),) = _held_lists([(hits, off, None)], "the offsets describe another number of reads")
+        acc, fresh = _start_or_fold(acc, fresh, on_device, lambda: new_mapq_acc(n), "accumulators")
+        self.sync_inputs(hits, off, acc)
+        self._check(self._L.real_hip_mapq_hits(self._h, _ptr(hits), _ptr(off), n, int(on_device), int(fresh), _ptr(acc)))
+        return acc
+
+    def match_mapq(self, bases, qual, offsets=None, patl: int = 0, acc=None, n_reads: Optional[int] = None, max_patl: int = 0,
+                   fresh: Optional[bool] = None):
+        """real_hip_match_mapq: matchAll of the batch with the hits kept on the device, folded into acc (None starts them)."""
+        b = self._read_batch(bases, qual, offsets, patl=patl, n_reads=n_reads, max_patl=max_patl)
+        acc, fresh = _start_or_fold(acc, fresh, bool(b.on_device), lambda: new_mapq_acc(int(b.n_reads)), "accumulators")
+        b.fresh = int(fresh)
+        self.sync_inputs(acc)
+        self._check(self._L.real_hip_match_mapq(self._h, C.byref(b), _ptr(acc)))
+        return acc
+
+    def mapq(self, info, score, acc):
+        """real_hip_mapq: one byte per read from the final records of match_unique and the accumulators (numpy arrays give a
+        numpy uint8 array, device tensors a device uint8 tensor); score may be None with scores off"""
+        host = isinstance(info, np.ndarray)
+        n = int(info.shape[0])
+        if host:
+            info = np.ascontiguousarray(info, dtype=np.uint64)
+            score = None if score is None else np.ascontiguousarray(score, dtype=np.float32)
+            acc = np.ascontiguousarray(acc, dtype=_lib.MAPQ_ACC_DTYPE)
+            out = np.zeros(n, dtype=np.uint8)
+        else:
+            import torch
+            out = torch.zeros(n, dtype=torch.uint8, device=info.device)
+        self.sync_inputs(info, score, acc, out)
+        self._check(self._L.real_hip_mapq(self._h, _ptr(info), _ptr(score), _ptr(acc), n, int(not host), _ptr(out)))
+        return out
+
+    def mapq_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipMapqStats, self._L.real_hip_mapq_stats_get, reset)
+
     # -- instrumentation --
     def counters(self, reset: bool = False) -> dict:
         c = RealHipCounters()
@@ -832,6 +881,59 @@ class PairMatcher(AllMatcher):
         self._check(self._L.real_hip_match_pairs_singles(self._h, C.byref(b1), C.byref(b2), C.byref(pp), C.byref(sp) if sp is not None else None,
                                                          _ptr(pairs), _ptr(singles1), _ptr(singles2)))
         return pairs, singles1, singles2
+
+    # -- mapping quality of fragments --
+    def mapq_pair_hits(self, hits1, off1, len1, hits2, off2, len2, min_insert: int, max_insert: int, acc=None, orientation: int = 0,
+                       fresh: Optional[bool] = None):
+        """real_hip_mapq_pair_hits: the fold of the concordant pairs alone, on hit lists the caller holds (as pair_hits)."""
+        on_device, n, (m1, m2) = _held_lists([(hits1, off1, len1), (hits2, off2, len2)], "the two mates' arrays describe different numbers of reads")
+        acc, fresh = _start_or_fold(acc, fresh, on_device, lambda: new_mapq_acc(n), "accumulators")
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        self.sync_inputs(*m1, *m2, acc)
+        self._check(self._L.real_hip_mapq_pair_hits(self._h, C.byref(pp), *map(_ptr, m1 + m2), n, int(on_device), int(fresh), _ptr(acc)))
+        return acc
+
+    def match_pairs_mapq(self, mate1, mate2, min_insert: int, max_insert: int, pairs=None, singles1=None, singles2=None, acc_pair=None,
+                         acc1=None, acc2=None, orientation: int = 0, mate_search: bool = False, max_anchors: int = 0,
+                         fresh: Optional[bool] = None):
+        """real_hip_match_pairs_mapq: match_pairs_singles and, in the same call, the three folds of the mapping quality ->
+        (pairs, singles1, singles2, acc_pair, acc1, acc2).  The six arrays are started together (None) or folded into together;
+        device batches need all six as device tensors (fresh=True: output only)."""
+        b1, b2 = self._mate_batch(mate1), self._mate_batch(mate2)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        given = [x is not None for x in (pairs, singles1, singles2, acc_pair, acc1, acc2)]
+        if any(given) and not all(given):
+            raise ValueError("pairs, singles and accumulators are started together or folded into together")
+        n, on_device = int(b1.n_reads), bool(b1.on_device)
+        pairs, fresh = _start_or_fold(pairs, fresh, on_device, lambda: new_pair_info(n))
+        (singles1, _), (singles2, _) = (_start_or_fold(s, fresh, on_device, lambda: new_single_info(n)) for s in (singles1, singles2))
+        accs = [_start_or_fold(a, fresh, on_device, lambda: new_mapq_acc(n), "accumulators")[0] for a in (acc_pair, acc1, acc2)]
+        b1.fresh = b2.fresh = int(fresh)
+        self.sync_inputs(pairs, singles1, singles2, *accs)
+        sp = self._search_params(max_anchors) if mate_search else None
+        self._check(self._L.real_hip_match_pairs_mapq(self._h, C.byref(b1), C.byref(b2), C.byref(pp), C.byref(sp) if sp is not None else None,
+                                                      _ptr(pairs), _ptr(singles1), _ptr(singles2), *map(_ptr, accs)))
+        return (pairs, singles1, singles2, *accs)
+
+    def mapq_pairs(self, pairs, acc_pair, singles1=None, singles2=None, acc1=None, acc2=None):
+        """real_hip_mapq_pairs: two bytes per fragment (mate 1, mate 2) from the final records and the accumulators; the
+        singles and the mates' accumulators are given together or not at all"""
+        host = isinstance(pairs, np.ndarray)
+        if host:
+            pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+            acc_pair = np.ascontiguousarray(acc_pair, dtype=_lib.MAPQ_ACC_DTYPE)
+            singles1, singles2 = (None if s is None else np.ascontiguousarray(s, dtype=SINGLE_DTYPE) for s in (singles1, singles2))
+            acc1, acc2 = (None if a is None else np.ascontiguousarray(a, dtype=_lib.MAPQ_ACC_DTYPE) for a in (acc1, acc2))
+            n = int(pairs.shape[0])
+            out = np.zeros(2 * n, dtype=np.uint8)
+        else:
+            import torch
+            n = int(pairs.numel() * pairs.element_size() // 40)
+            out = torch.zeros(2 * n, dtype=torch.uint8, device=pairs.device)
+        self.sync_inputs(pairs, singles1, singles2, acc_pair, acc1, acc2, out)
+        self._check(self._L.real_hip_mapq_pairs(self._h, _ptr(pairs), _ptr(singles1), _ptr(singles2), _ptr(acc_pair), _ptr(acc1), _ptr(acc2),
+                                                n, int(not host), _ptr(out)))
+        return out
 
     def single_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
