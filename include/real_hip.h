@@ -822,6 +822,96 @@ typedef struct real_hip_mapq_stats {
 } real_hip_mapq_stats;
 int real_hip_mapq_stats_get(real_hip_ctx *ctx, real_hip_mapq_stats *out, int reset);
 
+/* ---- gap rescue: place a mate that differs from the text by one insertion or deletion (off unless these entry points are
+ * called).  Every other placement of this library is ungapped: a read with one indel shows dozens of mismatches at its true
+ * position and is found nowhere.  With pairs the placed mate says where the other one must lie, and there an alignment with
+ * one gap is a prefix on one diagonal plus a suffix on a neighbouring one.  The reference has no counterpart (its -g is
+ * unfinished); the semantics are this project's own.  Everything is an integer and a function of reads, records
+ * and text alone: nothing depends on lanes, waves, tiles or calls, and two calls on the halves of a batch give the records of
+ * one call on the whole.
+ * WHICH FRAGMENTS.  The records are the FINAL ones, after all genome files, as real_hip_mismatches_pairs takes them.  Fragment i
+ * is ELIGIBLE in the resident genome file f (n bases) iff its pair record's state is REAL_HIP_PAIR_NOMATCH, exactly one mate's
+ * single record is Unique (the ANCHOR, at a on strand inv, length La), the other mate's single record is NoMatch (the TARGET,
+ * length L) and the anchor's fileid == f.  A fragment that meets the first three conditions with an anchor of another file is
+ * left untouched and counted as other_file.  An eligible fragment is SKIPPED and counted if the target holds a symbol > 3, is
+ * longer than REAL_HIP_MAX_PATL or shorter than 2 * min_flank + max_gap + 1, or if the anchor does not lie wholly inside
+ * fragment `frag` of the resident text (no record of this library's matchers does that); its record is NoMatch.
+ * WINDOW.  The target is searched on the strand opposite to the anchor's; R is the ORIENTED target: the read itself on '+', its
+ * reverse complement on '-'.  [lo, hi] is the set of start positions at which an ungapped hit of the target would be CONCORDANT
+ * with the anchor (the paired-end block above), in 64 bits:
+ *   anchor forward  p in [max(a, a + La - L, a + min_insert - L), a + max_insert - L]
+ *   anchor reverse  p in [a + La - max_insert, min(a, a + La - L, a + La - min_insert)]
+ * With [fs, fe) the anchor's fragment, every start p in [max(lo - max_gap, fs), min(hi + max_gap, fe - 1)] is EXAMINED (none if
+ * lo > hi).  max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT is REAL_HIP_E_UNSUPPORTED before anything is launched.
+ * CANDIDATES.  A candidate is a triple (p, g, j) with p examined and |g| <= max_gap:
+ *   g = 0            j = 0; R[0..L) on text[p..p+L); the span is L
+ *   g > 0  deletion  of g text bases: min_flank <= j <= L - min_flank; R[0..j) on text[p..p+j) and R[j..L) on
+ *                    text[p+j+g..p+L+g); the span is L + g
+ *   g < 0  insertion of d = -g read bases: min_flank <= j <= L - min_flank - d; R[0..j) on text[p..p+j), R[j..j+d) unaligned,
+ *                    R[j+d..L) on text[p+j..p+L-d); the span is L - d
+ * k is the number of mismatching aligned bases, cost = cost_mismatch * k + (g != 0 ? cost_open + cost_extend * |g| : 0).  A
+ * triple is a candidate iff [p, p + span) lies inside the anchor's fragment, no N bit is set in the span, k <= 15 and
+ * cost <= max_cost.
+ * RECORD.  best is the lexicographically smallest (cost, |g|, p, g, j): among equal costs the ungapped alignment wins, then the
+ * shorter gap, then the leftmost start, then an insertion before a deletion, then the leftmost split -- the VCF
+ * left-alignment of a gap inside a repeat.  second is the smallest cost among the candidates with |p - best.pos| > max_gap:
+ * every other alignment of the same locus starts within max_gap of best, so they do not vote against their own locus.  state:
+ * NoMatch without a candidate (every other field 0, second 0xFFFF), NonUnique if second <= cost + margin, else Unique.
+ * PARAMETERS (anything else is REAL_HIP_E_INVALID with a message, nothing launched): max_gap in 1..REAL_HIP_GAP_MAX, min_flank >=
+ * 1, the three costs <= 65535, max_cost <= 65534 (0xFFFF is "none"), margin <= 65535, reserved words 0.
+ * real_hip_gap_rescue: where the arrays live follows the batches' on_device as for real_hip_mismatches_pairs: records and out
+ * are host memory for 0 and 2, device memory for 1 (pairs 8-byte, singles and out 16-byte aligned).  fresh != 0: out is output
+ * only and every record starts NoMatch; 0: in/out, only the fragments eligible in the resident file are written -- how a run
+ * over several genome files fills one array.  Needs the text, not the index (REAL_HIP_E_STATE without it).  n_reads == 0 is
+ * valid.  REAL_HIP_E_INVALID with a message: NULL params, records or out with n_reads > 0, a wrong struct_size, batches that
+ * disagree in n_reads or on_device, more than 2^32 fragments.                                                                  */
+#define REAL_HIP_GAP_MAX 16u
+#define REAL_HIP_GAP_NONE 0xFFFFu   /* `second` of a record without a rival */
+typedef struct real_hip_gap_params {
+    uint32_t struct_size;    /* = sizeof(real_hip_gap_params)                                          */
+    uint32_t max_gap;        /* longest insertion or deletion, 1..REAL_HIP_GAP_MAX                     */
+    uint32_t min_flank;      /* fewest aligned bases on either side of a gap, >= 1                     */
+    uint32_t cost_mismatch, cost_open, cost_extend;
+    uint32_t max_cost;       /* a candidate costs at most this                                         */
+    uint32_t margin;         /* NonUnique if second <= cost + margin                                   */
+    uint32_t reserved[2];    /* 0                                                                      */
+} real_hip_gap_params;
+typedef struct real_hip_gap_place {   /* 16 bytes, 16-byte aligned on the device (one vector store) */
+    uint32_t pos;            /* p: 0-based start in the text of fileid                                 */
+    uint16_t frag;
+    uint8_t  fileid;
+    uint8_t  tag;            /* bit 0: which mate is the target (0 = mate 1); bit 4: inverted; bits 5-6: state */
+    uint16_t split;          /* j                                                                      */
+    int8_t   gap;            /* g: > 0 deletion, < 0 insertion                                         */
+    uint8_t  k;              /* mismatching aligned bases                                              */
+    uint16_t cost, second;   /* second: REAL_HIP_GAP_NONE = none                                       */
+} real_hip_gap_place;
+#define REAL_HIP_GAP_TARGET(tag)   ((tag) & 1u)
+#define REAL_HIP_GAP_INVERTED(tag) (((tag) >> 4) & 1u)
+#define REAL_HIP_GAP_STATE(tag)    (((tag) >> 5) & 3u)
+int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_gap_params *gp,
+                        const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_pair *pairs,
+                        const real_hip_single *singles1, const real_hip_single *singles2, int fresh, real_hip_gap_place *out);
+/* Host only: the CIGAR of a record of a read of `len` bases -- "100M", "40M2D60M", "40M3I57M" -- in forward-text coordinates
+ * (the ORIENTED read is what is aligned, so nothing is reversed).  Returns the string's length; REAL_HIP_E_INVALID for NULL
+ * arguments, a NoMatch record or a record that does not fit the length; REAL_HIP_E_OVERFLOW when cap is too small.       */
+int real_hip_gap_cigar(const real_hip_gap_place *g, uint32_t len, char *buf, size_t cap);
+/* work of the stage, accumulated since the last reset.  Every counter but the last two is a function of the inputs.       */
+typedef struct real_hip_gap_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_gap_stats), 0                                 */
+    uint64_t fragments;      /* fragments handed in                                                    */
+    uint64_t eligible;       /* eligible in the resident file, the skipped ones included               */
+    uint64_t other_file;     /* anchor in another file                                                 */
+    uint64_t skipped;
+    uint64_t positions;      /* sum of the numbers of examined starts                                  */
+    uint64_t placed;         /* records that are not NoMatch                                           */
+    uint64_t unique;
+    uint64_t gapped;         /* placed with g != 0                                                     */
+    uint64_t launches;       /* kernels launched                                                       */
+    double   kernel_ms;      /* HIP events on the ctx's stream around the kernels                      */
+} real_hip_gap_stats;
+int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -14,6 +14,7 @@
 // Nothing depends on the order of the anchors or of the lanes (pair_state.h).  Plain C++ and vector stores.
 #include "match_common.h"
 #include "pair_state.h"
+#include "read_words.h"
 
 #include <cstring>
 
@@ -32,32 +33,6 @@ struct MateSearchArgs {
     double filter_mult;
     uint32_t fresh, fileid, scores, min_insert, max_insert, seedl, totalkmax, max_anchors;
 };
-
-static __device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// word j of a read (32 bases, MSB first) from the batch; *bad is set if a base is > 3 (byte input)
-static __device__ __forceinline__ uint64_t ms_word(const DevBatch &b, uint64_t o0, uint32_t patl, uint32_t j, bool *bad)
-{
-    const uint32_t nb = min(32u, patl - 32u * j);
-    uint64_t w = 0;
-    if (b.packed) {
-        const uint64_t g0 = o0 + 32ull * j; // first base of the word inside the batch
-        const uint8_t *p = b.bases + (g0 >> 2);
-        const uint32_t sh = 2u * (uint32_t)(g0 & 3);
-        const uint32_t nbytes = (uint32_t)(((g0 & 3) + nb + 3) >> 2);
-        for (uint32_t k = 0; k < 8 && k < nbytes; ++k) w |= (uint64_t)p[k] << (56 - 8 * k);
-        if (sh) { w <<= sh; if (nbytes > 8) w |= (uint64_t)p[8] >> (8 - sh); }
-    } else {
-        const uint8_t *p = b.bases + o0 + 32ull * j;
-        for (uint32_t i = 0; i < nb; ++i) { const uint32_t c = p[i]; if (c > 3) *bad = true; w |= (uint64_t)(c & 3) << (62 - 2 * i); }
-    }
-    if (nb < 32) w &= ~0ull << (64 - 2 * nb);
-    return w;
-}
 
 template <bool SCORES>
 __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A)
@@ -116,15 +91,7 @@ __global__ void __launch_bounds__(256) mate_search_kernel(const MateSearchArgs A
             }
             wave_lds_sync();
 #pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const uint32_t nw = (len[m] + 31) >> 5, pad = 64 * nw - 2 * len[m];
-                const uint64_t *sO = sRead[wv][m][0];
-                for (uint32_t j = lane; j < nw; j += 64) { // revcomp: the complement of the 2-bit reversal, shifted by the pad
-                    const uint64_t x = rev2(sO[nw - 1 - j]), y = (j + 2 <= nw) ? rev2(sO[nw - 2 - j]) : 0ull;
-                    const uint64_t v = pad ? ((x << pad) | (y >> (64 - pad))) : x;
-                    sRead[wv][m][1][j] = ~v & ((j + 1 < nw) ? ~0ull : (~0ull << pad));
-                }
-            }
+            for (int m = 0; m < 2; ++m) ms_revcomp(sRead[wv][m][0], sRead[wv][m][1], len[m], lane);
             wave_lds_sync();
         }
         PairState st;

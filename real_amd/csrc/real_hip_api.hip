@@ -3,6 +3,7 @@
 #include "real_hip_internal.h"
 #include "pair_state.h"
 #include "mapq_stage.h"
+#include "gap_stage.h"
 
 #include <chrono>
 #include <cmath>
@@ -243,6 +244,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
     rh_mapq_release(c);
+    rh_gap_release(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -1462,6 +1464,56 @@ extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch
 extern "C" int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset)
 {
     return stats_get(ctx, out, reset, "mismatch stats struct_size", rh_mismatch_stats);
+}
+
+// ---- gap rescue (gap_rescue.hip): the reads and the pair records are staged as the mismatch lists stage them, the singles and
+// the in/out gap records beside them
+static const char *const kGap = "gap rescue";
+static int gap_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_gap_params *gp)
+{
+    if (!gp || gp->struct_size != sizeof(real_hip_gap_params)) return stage_invalid(ctx, kGap, "params struct_size");
+    if (pp->max_insert > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "gap rescue: max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
+    if (gp->max_gap < 1 || gp->max_gap > REAL_HIP_GAP_MAX) return stage_invalid(ctx, kGap, "max_gap must be in 1 .. REAL_HIP_GAP_MAX");
+    if (gp->min_flank < 1) return stage_invalid(ctx, kGap, "min_flank must be at least 1");
+    if (gp->cost_mismatch > 65535u || gp->cost_open > 65535u || gp->cost_extend > 65535u) return stage_invalid(ctx, kGap, "a cost beyond 65535");
+    if (gp->max_cost > 65534u) return stage_invalid(ctx, kGap, "max_cost beyond 65534");
+    if (gp->margin > 65535u) return stage_invalid(ctx, kGap, "margin beyond 65535");
+    if (gp->reserved[0] || gp->reserved[1]) return stage_invalid(ctx, kGap, "reserved words must be 0");
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_gap_params *gp, const real_hip_batch *b1,
+                                   const real_hip_batch *b2, const real_hip_pair *pairs, const real_hip_single *singles1, const real_hip_single *singles2,
+                                   int fresh, real_hip_gap_place *out)
+{
+    RH_ENTER(ctx);
+    int rc = pair_params_check(ctx, pp);
+    if (rc || (rc = gap_params_check(ctx, pp, gp))) return rc;
+    real_hip_batch bv[2];
+    if ((rc = mates_view(ctx, kGap, b1, b2, false, bv))) return rc;
+    const bool dev = bv[0].on_device == 1;
+    const uint64_t n = bv[0].n_reads;
+    if (n && (!singles1 || !singles2 || !out)) return stage_invalid(ctx, kGap, "null singles / out");
+    if (dev && (((uintptr_t)singles1 | (uintptr_t)singles2 | (uintptr_t)out) & 15u)) return stage_invalid(ctx, kGap, "the single and the gap records must be 16-byte aligned");
+    RhGapStage &S = rh_gap_stage(ctx);
+    PlacedReads p;
+    if ((rc = stage_placements(ctx, kGap, bv, 2, nullptr, pairs, S.rec, false, p))) return rh_sync_tail(ctx, rc);
+    if (!n) return REAL_HIP_OK;
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    const real_hip_single *d_singles[2] = {singles1, singles2};
+    real_hip_gap_place *d_out = out;
+    for (int m = 0; m < 2 && !rc; ++m) rc = io.in(S.sg[m], m ? singles2 : singles1, n, d_singles[m]);
+    if (!rc) rc = io.inout(S.out, out, n, fresh != 0, d_out);
+    if (!rc) rc = rh_launch_gap_rescue(ctx, *pp, *gp, p.b[0], p.b[1], p.pairs, d_singles, n, fresh, d_out);
+    if (!rc) rc = io.back(out, d_out, n, "download of the gap records");
+    rc = rh_sync_tail(ctx, rc);
+    return rc ? rc : rh_gap_finish(ctx);
+}
+
+extern "C" int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "gap stats struct_size", rh_gap_stats);
 }
 
 // ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no

@@ -49,6 +49,17 @@ void RealOptions::printHelp() const
               << "-unpaired <file: with -p2, receives the mates of the fragments WITHOUT a concordant pair (after the last genome file, and\n"
               << "   after the search with -mate_search 1) that are placed uniquely on their own: mate 1's line, then mate 2's, as the\n"
               << "   single-end mode prints that hit; -o is unchanged; not with -pairs_all 1>\n"
+              << "-gapped <file: with -p2, after the last genome file one more pass over the genome files (the text alone, one fresh context on\n"
+              << "   -device) places the mate of a fragment WITHOUT a concordant pair whose other mate is placed uniquely on its own and which\n"
+              << "   is itself placed nowhere, with at most ONE insertion or deletion, inside the window -insert_min .. -insert_max allows;\n"
+              << "   <file> gets one line per mate placed uniquely that way, in read order: read id, mate (1|2), strand, fragment name,\n"
+              << "   1-based position, CIGAR, NM, mismatches, cost, second best cost (* = none), 1-based position of the placed mate; a\n"
+              << "   summary line goes to standard error; -o, -unpaired and -sam are unchanged; -insert_max of at most "
+              << REAL_HIP_MATE_SEARCH_MAX_INSERT << "; not with -pairs_all 1>\n"
+              << "-gap_max <longest insertion or deletion, 1.." << REAL_HIP_GAP_MAX << ", default=8>\n"
+              << "-gap_flank <fewest aligned bases on either side of the gap, default=8>\n"
+              << "-gap_maxcost <a placement costs 4 per mismatch and 6 + its length for the gap, and at most this, default=4 * (-e) + 6 + (-gap_max)>\n"
+              << "-gap_margin <a placement is unique if no other locus of the window costs at most its cost + this, default=0>\n"
               << "-insert_hist <file: with -p2, receives the histogram of the outer distances of the Unique fragments (after the last\n"
               << "   genome file) as lines outer<TAB>count, the last bin (-insert_max + 1) holding what lies beyond; the quartiles go to\n"
               << "   standard error; -o is unchanged; not with -pairs_all 1>\n"
@@ -154,6 +165,11 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pairs_all") { pairs_all = atoi(need("-pairs_all").c_str()) != 0; pairs_all_given = true; i += 2; }
         else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
         else if (a == "-unpaired") { unpairedfilename = need("-unpaired"); unpaired_given = true; i += 2; }
+        else if (a == "-gapped") { gappedfilename = need("-gapped"); gapped_given = true; i += 2; }
+        else if (a == "-gap_max") { gap_max = strtoul(need("-gap_max").c_str(), 0, 10); gap_flags_given = true; i += 2; }
+        else if (a == "-gap_flank") { gap_flank = strtoul(need("-gap_flank").c_str(), 0, 10); gap_flags_given = true; i += 2; }
+        else if (a == "-gap_maxcost") { gap_maxcost = strtol(need("-gap_maxcost").c_str(), 0, 10); gap_flags_given = true; i += 2; }
+        else if (a == "-gap_margin") { gap_margin = strtoul(need("-gap_margin").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-insert_hist") { inserthistfilename = need("-insert_hist"); insert_flags_given = true; i += 2; }
         else if (a == "-insert_auto") { insert_auto = strtoull(need("-insert_auto").c_str(), 0, 10); insert_flags_given = true; i += 2; }
         else if (a == "-pileup") { pileupfilename = need("-pileup"); pileup_given = true; i += 2; }
@@ -285,6 +301,25 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (!mapq) throw std::runtime_error("-pileup_minmapq needs -mapq 1.");
         if (!pileup_given && !pileup_depth_given && !vcf_given) throw std::runtime_error("-pileup_minmapq is only meaningful with -pileup / -vcf.");
         if (pileup_minmapq < 0 || pileup_minmapq > (long)REAL_HIP_MAPQ_MAX) throw std::runtime_error("-pileup_minmapq must be in 0..60.");
+    }
+    if (gapped_given) { // gap rescue: loud errors before anything runs
+        if (pattern2filename.empty()) throw std::runtime_error("-gapped is only meaningful with -p2 (paired-end reads).");
+        if (pairs_all) throw std::runtime_error("-gapped places the mate of a fragment without a pair: it cannot be combined with -pairs_all 1.");
+        if (gappedfilename.empty()) throw std::runtime_error("-gapped needs a file name: an empty one was given.");
+        if (gappedfilename == "-") throw std::runtime_error("-gapped writes to a file: standard output (-) cannot be it.");
+        if (gappedfilename == outputfilename) throw std::runtime_error("-gapped must name a file of its own: it names the same file as -o.");
+        if ((unpaired_given && gappedfilename == unpairedfilename) || (sam_given && gappedfilename == samfilename) ||
+            (!inserthistfilename.empty() && gappedfilename == inserthistfilename) || (pileup_given && gappedfilename == pileupfilename) ||
+            (pileup_depth_given && gappedfilename == pileupdepthfilename) || (vcf_given && gappedfilename == vcffilename))
+            throw std::runtime_error("-gapped must name a file of its own: it names the same file as another output.");
+        if (gap_max < 1 || gap_max > REAL_HIP_GAP_MAX) throw std::runtime_error("-gap_max must be in 1.." + std::to_string(REAL_HIP_GAP_MAX) + ".");
+        if (gap_flank < 1) throw std::runtime_error("-gap_flank must be at least 1.");
+        if (gap_maxcost < 0) gap_maxcost = 4 * (long)totalkmax + 6 + (long)gap_max;
+        if (gap_maxcost > 65534 || gap_margin > 65535) throw std::runtime_error("-gap_maxcost takes at most 65534, -gap_margin at most 65535.");
+        if (insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+            throw std::runtime_error("-gapped takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
+    } else if (gap_flags_given) {
+        throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped.");
     }
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
         if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");

@@ -53,6 +53,10 @@ struct RealOptions {
     bool pairs_all_given = false;     // (the flag was on the command line: an error without -p2)
     std::string unpairedfilename;     // -unpaired: the file that receives the Unique mates of the fragments without a pair (real_hip_match_pairs_singles)
     bool unpaired_given = false;      // (the flag was on the command line: an error without -p2)
+    std::string gappedfilename;       // -gapped: the file that receives the mates placed with one insertion or deletion (real_hip_gap_rescue)
+    bool gapped_given = false, gap_flags_given = false; // (-gapped / one of -gap_* was on the command line)
+    unsigned long gap_max = 8, gap_flank = 8, gap_margin = 0; // -gap_max, -gap_flank, -gap_margin
+    long gap_maxcost = -1;            // -gap_maxcost: -1 = 4 * (-e) + 6 + (-gap_max)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
     std::string inserthistfilename;   // -insert_hist: the file that receives the histogram of the Unique fragments' outer distances (real_hip_pair_insert_hist)
     std::string pileupfilename;       // -pileup: the file that receives the sites of the pileup of the final placements (real_hip_pileup_*)

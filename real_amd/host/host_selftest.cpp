@@ -6,6 +6,7 @@
 //   host_selftest pair_options <args...>          -> prints the parsed paired-end flags
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
+//   host_selftest gapped_options <args...>        -> prints the parsed -gapped file ("." if none), -gap_max, -gap_flank, -gap_maxcost, -gap_margin
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 //   host_selftest records                         -> checks the decoders of the final records (csrc/final_record.h) against records written
@@ -396,6 +397,12 @@ int main(int argc, char **argv)
         if (cmd == "unpaired_options") { // -unpaired
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.unpairedfilename.empty() ? "." : o.unpairedfilename) << "\n";
+            return 0;
+        }
+        if (cmd == "gapped_options") { // -gapped and its -gap_* flags
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.gappedfilename.empty() ? "." : o.gappedfilename) << " " << o.gap_max << " " << o.gap_flank << " " << o.gap_maxcost << " "
+                      << o.gap_margin << "\n";
             return 0;
         }
         if (cmd == "insert_options") { // -insert_hist, -insert_auto

@@ -553,7 +553,7 @@ void textPass(const RealOptions &o, const std::vector<std::string> &files, Timer
         perFile(ctx, fi, G);
     }
 }
-inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.vcf_given || o.sam_given; }
+inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.vcf_given || o.sam_given || o.gapped_given; }
 
 // -vcf: the calls of the finished pileup of one genome file (real_hip_call_*) -- the reads once more through
 // addAll(ctx, true), which hands every batch with its final records to real_hip_call_add / _add_pairs -- as VCF lines, and a
@@ -934,6 +934,78 @@ inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, b
 // Per genome file real_hip_match_pairs (-mate_search 1: real_hip_match_pairs_search) folds into the fragments' in/out
 // records, as uniqueinfo[] folds for matchUnique.
 // A Unique fragment prints the 11-column line of mate 1 and then of mate 2; NoMatch / NonUnique print nothing.
+// ---- -gapped: the mate of a fragment without a pair, placed with one insertion or deletion (real_hip_gap_rescue) ----
+// Runs where samPass runs, through the same textPass: per genome file the reads once more, each batch with its FINAL records;
+// the first file starts the gap records, the others fold into them.  Then the reads a last time for the ids: one line per Unique
+// record, in read order, and the summary line on standard error.
+void gapPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, const real_hip_pair_params &pp,
+             const std::vector<real_hip_pair> &pairs, const std::vector<real_hip_single> &singles1, const std::vector<real_hip_single> &singles2,
+             uint64_t numpat, int qoff1, int qoff2, ReadBlock &b1, ReadBlock &b2)
+{
+    if (!o.gapped_given) return;
+    OutFile out(o.gappedfilename, false, "-gapped");
+    real_hip_gap_params gp;
+    memset(&gp, 0, sizeof gp);
+    gp.struct_size = sizeof gp; gp.max_gap = (uint32_t)o.gap_max; gp.min_flank = (uint32_t)o.gap_flank;
+    gp.cost_mismatch = 4; gp.cost_open = 6; gp.cost_extend = 1; gp.max_cost = (uint32_t)o.gap_maxcost; gp.margin = (uint32_t)o.gap_margin;
+    std::vector<real_hip_gap_place> gaps(numpat);
+    real_hip_gap_stats sum;
+    memset(&sum, 0, sizeof sum);
+    textPass(o, files, T, [&](CtxVec &gc, unsigned fi, const GenomeText &) {
+        real_hip_ctx *h = gc[0]->h;
+        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
+            if (!n) break;
+            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
+            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            const double tm = now_s();
+            check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, fi == 0, gaps.data() + seen),
+                  "real_hip_gap_rescue");
+            T.match += now_s() - tm;
+            seen += n;
+        }
+        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        real_hip_gap_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        check(h, real_hip_gap_stats_get(h, &st, 1), "real_hip_gap_stats_get");
+        sum.eligible += st.eligible; sum.placed += st.placed; sum.unique += st.unique; sum.gapped += st.gapped;
+    });
+    ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
+    const ReadSource m1(b1), m2(b2);
+    uint64_t base = 0;
+    for (;;) {
+        const uint64_t n = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
+        if (n != n2 || base + n > numpat) throw std::runtime_error("the read files changed between two passes");
+        if (!n) break;
+        formatAndWrite(n, out.file(), T, [&](uint64_t i, std::string &s) {
+            const real_hip_gap_place &g = gaps[base + i];
+            if (REAL_HIP_GAP_STATE(g.tag) != REAL_HIP_PAIR_UNIQUE) return;
+            const unsigned tm = REAL_HIP_GAP_TARGET(g.tag);
+            const ReadView r = tm ? m2[i] : m1[i];
+            const real_hip_single &a = tm ? singles1[base + i] : singles2[base + i]; // the anchor: the other mate
+            char cigar[48], tail[160];
+            real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
+            char second[16] = "*";
+            if (g.second != REAL_HIP_GAP_NONE) snprintf(second, sizeof second, "%u", (unsigned)g.second);
+            const int absg = g.gap < 0 ? -g.gap : g.gap;
+            snprintf(tail, sizeof tail, "\t%llu\t%s\t%u\t%u\t%u\t%s\t%llu\n", (unsigned long long)((uint64_t)g.pos - RS.starts[g.fileid][g.frag] + 1), cigar,
+                     (unsigned)(g.k + absg), (unsigned)g.k, (unsigned)g.cost, second, (unsigned long long)((uint64_t)a.pos - RS.starts[a.fileid][a.frag] + 1));
+            s.append(r.id, r.idlen);
+            s += tm ? "\t2\t" : "\t1\t";
+            s += REAL_HIP_GAP_INVERTED(g.tag) ? "-\t" : "+\t";
+            s += RS.names[g.fileid][g.frag];
+            s += tail;
+        });
+        base += n;
+    }
+    if (base != numpat) throw std::runtime_error("the read files changed between two passes");
+    out.close();
+    std::cerr << "gap rescue: eligible=" << sum.eligible << " placed=" << sum.placed << " unique=" << sum.unique << " gapped=" << sum.gapped << std::endl;
+}
+
 // -unpaired <file>: real_hip_match_pairs_singles folds each mate's own hits beside the pairs; a fragment whose final pair
 // state is NoMatch writes to <file> the line of mate 1 if it is Unique on its own, then mate 2's likewise, as the
 // single-end mode would print that hit.  The main output does not change.
@@ -953,7 +1025,7 @@ int matchPairs(const RealOptions &o)
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
-    const bool singles = unpaired || o.sam_given || o.mapq; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them)
+    const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped takes its anchors from them)
     std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
     std::vector<real_hip_read_sum> sums1, sums2;     // -dedup: the mates' summaries, kept for the run beside pairs
     std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
@@ -1167,6 +1239,7 @@ int matchPairs(const RealOptions &o)
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
     });
+    gapPass(o, files, RS, T, pp, pairs, singles1, singles2, numpat, qoff1, qoff2, b1, b2);
     T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;
 }

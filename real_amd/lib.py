@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "real_hip_read_summary", "real_hip_mark_duplicates", "real_hip_mark_duplicates_pairs", "real_hip_dup_stats_get",
     "real_hip_mapq_acc_merge", "real_hip_mapq_of", "real_hip_mapq_hits", "real_hip_mapq_pair_hits", "real_hip_match_mapq",
     "real_hip_match_pairs_mapq", "real_hip_mapq", "real_hip_mapq_pairs", "real_hip_mapq_stats_get",
+    "real_hip_gap_rescue", "real_hip_gap_cigar", "real_hip_gap_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -202,6 +203,29 @@ MAPQ_STATS_FIELDS = ("folded", "candidates", "handed_over", "placements", "unlis
 RealHipMapqStats = _stats_struct("RealHipMapqStats", MAPQ_STATS_FIELDS)
 
 
+# gap rescue (include/real_hip.h, "gap rescue"): a mate placed with one insertion or deletion beside its uniquely placed mate
+GAP_MAX, GAP_NONE = 16, 0xFFFF
+
+
+class RealHipGapParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_gap", C.c_uint32), ("min_flank", C.c_uint32), ("cost_mismatch", C.c_uint32),
+                ("cost_open", C.c_uint32), ("cost_extend", C.c_uint32), ("max_cost", C.c_uint32), ("margin", C.c_uint32),
+                ("reserved", C.c_uint32 * 2)]
+
+
+class RealHipGapPlace(C.Structure):
+    """real_hip_gap_place: the record of one fragment (GAP_PLACE_DTYPE is the same record as a numpy dtype); tag = the target
+    mate (bit 0) | inverted << 4 | state << 5"""
+    _fields_ = [("pos", C.c_uint32), ("frag", C.c_uint16), ("fileid", C.c_uint8), ("tag", C.c_uint8), ("split", C.c_uint16),
+                ("gap", C.c_int8), ("k", C.c_uint8), ("cost", C.c_uint16), ("second", C.c_uint16)]
+
+
+GAP_PLACE_DTYPE = np.dtype(RealHipGapPlace)
+assert GAP_PLACE_DTYPE.itemsize == 16
+GAP_STATS_FIELDS = ("fragments", "eligible", "other_file", "skipped", "positions", "placed", "unique", "gapped", "launches", "kernel_ms")
+RealHipGapStats = _stats_struct("RealHipGapStats", GAP_STATS_FIELDS)
+
+
 class RealHipPairHit(C.Structure):
     """real_hip_pair_hit: one concordant pair (PAIR_HIT_DTYPE is the same record as a numpy dtype)"""
     _fields_ = [("pair", C.c_uint32), ("pos1", C.c_uint32), ("pos2", C.c_uint32), ("outer", C.c_uint32),
@@ -343,6 +367,9 @@ def load():
     L.real_hip_mapq.argtypes = [vp, vp, vp, vp, u64, ci, vp]
     L.real_hip_mapq_pairs.argtypes = [vp, vp, vp, vp, vp, vp, vp, u64, ci, vp]
     L.real_hip_mapq_stats_get.argtypes = [vp, C.POINTER(RealHipMapqStats), ci]
+    L.real_hip_gap_rescue.argtypes = [vp, pairp, C.POINTER(RealHipGapParams), batch, batch, vp, vp, vp, ci, vp]
+    L.real_hip_gap_cigar.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
+    L.real_hip_gap_stats_get.argtypes = [vp, C.POINTER(RealHipGapStats), ci]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
     L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
     L.real_hip_timing_enable.argtypes = [vp, ci]
@@ -355,6 +382,16 @@ def scoring_table(similarity=0.995, gc=0.41, trans=0.71, err=0.0, gcmut_bias=2.0
     LL = np.zeros(1024, dtype=np.float64)
     load().real_hip_scoring_table(similarity, gc, trans, err, gcmut_bias, LL.ctypes.data)
     return LL
+
+
+def gap_cigar(rec, length: int) -> str:
+    """real_hip_gap_cigar (host only): the CIGAR of one GAP_PLACE_DTYPE record of a read of `length` bases"""
+    r = np.ascontiguousarray(np.array(rec, dtype=GAP_PLACE_DTYPE).reshape(1))
+    buf = C.create_string_buffer(48)
+    rc = load().real_hip_gap_cigar(r.ctypes.data, int(length), buf, len(buf))
+    if rc < 0:
+        raise RealHipError(rc, "real_hip_gap_cigar")
+    return buf.value.decode()
 
 
 def mapq_acc_merge(a: np.ndarray, b: np.ndarray) -> np.ndarray:

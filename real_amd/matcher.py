@@ -57,6 +57,11 @@ class RealOptions:
     unpairedfilename: str = ""      # -unpaired: with -p2, the file that receives the Unique mates of the fragments without a pair
     inserthistfilename: str = ""    # -insert_hist: with -p2, the file that receives the histogram of the Unique fragments' outer distances
     insert_auto: int = 0            # -insert_auto: with -p2, fragments the insert bounds are estimated from before the run (0: off)
+    gappedfilename: str = ""        # -gapped: with -p2, the file that receives the mates placed with one insertion or deletion
+    gap_max: int = 8                # -gap_max / -gap_flank / -gap_maxcost (-1: 4 * totalkmax + 6 + gap_max) / -gap_margin
+    gap_flank: int = 8
+    gap_maxcost: int = -1
+    gap_margin: int = 0
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -71,6 +76,21 @@ class RealOptions:
             raise ValueError("cannot handle seed length < 4")
         if self.seedkmax > 2:
             self.seedkmax = 2
+        if self.gappedfilename:         # the loud errors of `real -gapped`
+            if not self.pattern2filename:
+                raise ValueError("-gapped needs -p2 (paired-end reads)")
+            if self.pairs_all:
+                raise ValueError("-gapped cannot be combined with -pairs_all 1")
+            if self.gappedfilename in (self.outputfilename, self.unpairedfilename, self.inserthistfilename):
+                raise ValueError("-gapped names the same file as another output")
+            if not 1 <= self.gap_max <= _lib.GAP_MAX:
+                raise ValueError("-gap_max must be in 1..%d" % _lib.GAP_MAX)
+            if self.gap_flank < 1:
+                raise ValueError("-gap_flank must be at least 1")
+            if self.gap_maxcost < 0:
+                self.gap_maxcost = 4 * self.totalkmax + 6 + self.gap_max
+            if self.insert_max > _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT:
+                raise ValueError("-gapped takes an -insert_max of at most %d" % _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT)
         if self.pattern2filename:       # the loud errors of `real -p2`
             if not self.match_unique:
                 raise ValueError("-p2 (paired-end reads) cannot be combined with -u 0 (every concordant pair: -pairs_all 1)")
@@ -131,7 +151,9 @@ class RealOptions:
                  "-insert_max": ("insert_max", int), "-gpus": ("gpus", int),
                  "-mate_search": ("mate_search", lambda v: bool(int(v))), "-mate_search_anchors": ("mate_search_anchors", int),
                  "-pairs_all": ("pairs_all", lambda v: bool(int(v))), "-unpaired": ("unpairedfilename", str),
-                 "-insert_hist": ("inserthistfilename", str), "-insert_auto": ("insert_auto", int)}
+                 "-insert_hist": ("inserthistfilename", str), "-insert_auto": ("insert_auto", int),
+                 "-gapped": ("gappedfilename", str), "-gap_max": ("gap_max", int), "-gap_flank": ("gap_flank", int),
+                 "-gap_maxcost": ("gap_maxcost", int), "-gap_margin": ("gap_margin", int)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -167,6 +189,13 @@ def new_single_info(n: int) -> np.ndarray:
     """the records of n reads before the first genome file: empty (state NoMatch, score 0, second -inf; real_hip_single)"""
     rec = np.zeros(n, dtype=SINGLE_DTYPE)
     rec["second"] = -np.inf
+    return rec
+
+
+def new_gap_place(n: int) -> np.ndarray:
+    """the gap records of n fragments before the first genome file: NoMatch (real_hip_gap_place)"""
+    rec = np.zeros(n, dtype=_lib.GAP_PLACE_DTYPE)
+    rec["second"] = _lib.GAP_NONE
     return rec
 
 
@@ -934,6 +963,40 @@ class PairMatcher(AllMatcher):
         self._check(self._L.real_hip_mapq_pairs(self._h, _ptr(pairs), _ptr(singles1), _ptr(singles2), _ptr(acc_pair), _ptr(acc1), _ptr(acc2),
                                                 n, int(not host), _ptr(out)))
         return out
+
+    # -- gap rescue: a mate with one insertion or deletion, placed beside its uniquely placed mate --
+    new_gap_place = staticmethod(new_gap_place)
+
+    @staticmethod
+    def _gap_params(max_gap: int = 8, min_flank: int = 8, cost_mismatch: int = 4, cost_open: int = 6, cost_extend: int = 1,
+                    max_cost: Optional[int] = None, margin: int = 0, totalkmax: int = 0) -> "_lib.RealHipGapParams":
+        """the command line's defaults: costs 4 / 6 / 1, max_cost = 4 * (-e) + 6 + max_gap"""
+        if max_cost is None:
+            max_cost = 4 * int(totalkmax) + 6 + int(max_gap)
+        return _lib.sized(_lib.RealHipGapParams, max_gap=int(max_gap), min_flank=int(min_flank), cost_mismatch=int(cost_mismatch),
+                          cost_open=int(cost_open), cost_extend=int(cost_extend), max_cost=int(max_cost), margin=int(margin))
+
+    def gap_rescue(self, mate1, mate2, pairs, singles1, singles2, min_insert: int, max_insert: int, out=None, fresh: Optional[bool] = None,
+                   orientation: int = 0, **gap):
+        """real_hip_gap_rescue: per fragment whose pair record is NoMatch with one mate Unique on its own and the other nowhere,
+        the other mate placed with at most one insertion or deletion inside the window the insert bounds allow -> gap records
+        (lib.GAP_PLACE_DTYPE).  pairs / singles are the FINAL records (what match_pairs_singles left after all genome files);
+        out: records to fold into (another genome file's), None starts them.  Needs the text of the genome file, not its index.
+        gap: max_gap, min_flank, cost_mismatch, cost_open, cost_extend, max_cost, margin (_gap_params)."""
+        b1, b2, pairs, singles1, singles2 = self._placed_pairs(mate1, mate2, pairs, singles1, singles2)
+        host = isinstance(pairs, np.ndarray)
+        out, fresh = _start_or_fold(out, fresh, not host, lambda: new_gap_place(int(b1.n_reads)), "gap records")
+        if host:
+            out = np.ascontiguousarray(out, dtype=_lib.GAP_PLACE_DTYPE)
+        pp = self._pair_params(min_insert, max_insert, orientation)
+        gp = self._gap_params(**dict({"totalkmax": self.opts.totalkmax}, **gap))
+        self.sync_inputs(out)
+        self._check(self._L.real_hip_gap_rescue(self._h, C.byref(pp), C.byref(gp), C.byref(b1), C.byref(b2), _ptr(pairs), _ptr(singles1),
+                                                _ptr(singles2), int(fresh), _ptr(out)))
+        return out
+
+    def gap_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipGapStats, self._L.real_hip_gap_stats_get, reset)
 
     def single_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
