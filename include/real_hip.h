@@ -912,6 +912,57 @@ typedef struct real_hip_gap_stats {
 } real_hip_gap_stats;
 int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset);
 
+/* ---- gapped mismatch lists: where a gap-rescued mate differs from the resident text, and which text bases its deletion skips
+ * -- what CIGAR, NM and MD of such a mate's SAM line are written from.  ORIENTED read and the resident text (n
+ * bases, file id f) are those of the block "mismatch lists".
+ * List i belongs to fragment i's gap record.  The read is the record's target mate: REAL_HIP_GAP_TARGET(tag) picks b1 (0) or
+ * b2 (1); it is oriented by REAL_HIP_GAP_INVERTED(tag).  With L the read's length, p = pos, j = split, g = gap, d = max(-g, 0)
+ * and span = L + g, in this order:
+ *   1. a record whose state is not Unique gets an empty list;
+ *   2. a Unique record of another file id than f gets an empty list and is counted as other_file;
+ *   3. a Unique record of file f that does not FIT gets an empty list and is counted as invalid, and no byte of text or read
+ *      outside their arrays is read for it.  It does not fit when |g| > REAL_HIP_GAP_MAX; or g != 0 and not (1 <= j and
+ *      j + d <= L - 1); or g == 0 and j != 0; or p + span > n; or L > REAL_HIP_MAX_PATL.  The geometry is the whole contract:
+ *      no min_flank is checked;
+ *   4. otherwise the list holds one entry per LISTED text offset t in 0 .. span - 1, ascending; off = t, ref is the text's
+ *      base at p + t, or 4 where the text's N bit is set there.
+ *      DELETED position (g > 0 and j <= t < j + g): always listed, base = REAL_HIP_MISMATCH_DELETED.
+ *      ALIGNED position: oriented read offset t aligns with text offset t when t < j; read offset t - g aligns with text offset
+ *      t when t >= j + max(g, 0).  With an insertion the read offsets j .. j + d - 1 align with nothing.  An aligned position is
+ *      listed by the rule of the ungapped lists: where the N bit is set (ref = 4, whatever the read shows) and, elsewhere,
+ *      where the oriented base differs from the text; base is the oriented base.
+ *      For g == 0 the list is what real_hip_mismatches gives for that placement.
+ * Everything else is real_hip_mismatches_pairs' rule word for word: gaps, out and mm_offsets are host memory for on_device 0 and
+ * 2, device memory for 1 (gaps 16-byte, out 4-byte aligned); n_out is host memory and always receives the total; when the total
+ * exceeds cap the call returns REAL_HIP_E_OVERFLOW and writes nothing to out (mm_offsets, n_reads + 1 entries from 0, is still
+ * written); n_reads == 0 is valid; REAL_HIP_E_STATE without a text; REAL_HIP_E_INVALID with a message, nothing launched: a NULL
+ * mm_offsets or n_out, a NULL out with cap > 0, NULL gaps with n_reads > 0, batches that disagree in n_reads or on_device, more
+ * than 2^32 fragments.  The output is a function of records, reads and text alone, and two calls on the halves of a batch give
+ * the lists of one call on the whole, up to rebasing the offsets.                                                             */
+#define REAL_HIP_MISMATCH_DELETED 4u   /* real_hip_mismatch::base of a text position the read's deletion skips */
+int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2,
+                               const real_hip_gap_place *gaps,
+                               real_hip_mismatch *out, uint64_t cap, uint64_t *n_out,
+                               uint64_t *mm_offsets /* n_reads + 1 */);
+/* work of the gapped lists, accumulated since the last reset.  disagree is 0 for records of real_hip_gap_rescue: it admits no N
+ * in a span, and its k is the number of differing aligned bases.                                                               */
+typedef struct real_hip_gapped_list_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_gapped_list_stats), 0                          */
+    uint64_t fragments;      /* lists asked for                                                        */
+    uint64_t placed;         /* Unique records of this file that fit: placements walked                */
+    uint64_t other_file;     /* Unique records of another file id                                      */
+    uint64_t invalid;        /* Unique records of this file that do not fit                            */
+    uint64_t aligned_bases;  /* sum of L - d over the placed records                                   */
+    uint64_t mismatches;     /* entries on aligned positions, written or counted by a call that overflowed */
+    uint64_t deleted;        /* entries on deleted positions: sum of max(g, 0) over the placed records */
+    uint64_t inserted;       /* sum of d over the placed records                                       */
+    uint64_t on_n;           /* entries with ref = 4, aligned or deleted                               */
+    uint64_t disagree;       /* placed records whose number of aligned entries is not the record's k   */
+    uint64_t launches;       /* kernels launched (the scan counts one)                                 */
+    double   kernel_ms;      /* HIP events on the ctx's stream around count, scan and emit             */
+} real_hip_gapped_list_stats;
+int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped_list_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -36,22 +36,6 @@ struct MismatchArgs {
                                    // [5] on_n, [6] disagree
 };
 
-// the text's N bits of the 32 positions from x on, as flags: position x + u at bit 62 - 2u
-static __device__ __forceinline__ uint64_t mm_n_flags(const uint64_t *__restrict__ wild, uint64_t x)
-{
-    const uint64_t w = x >> 6;
-    const uint32_t s = (uint32_t)(x & 63u);
-    uint64_t v = wild[w] << s;
-    if (s > 32) v |= wild[w + 1] >> (64 - s); // (the vector is padded behind its end)
-    v >>= 32; // bit 31 - u = position x + u; now every bit to twice its place
-    v = (v | (v << 16)) & 0x0000ffff0000ffffull;
-    v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
-    v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
-    v = (v | (v << 2)) & 0x3333333333333333ull;
-    v = (v | (v << 1)) & M55;
-    return v;
-}
-
 template <bool PAIRS, bool EMIT>
 __global__ void __launch_bounds__(RH_MM_BLOCK) mismatch_list_kernel(const MismatchArgs A)
 {

@@ -39,30 +39,66 @@ struct ReadWalk {
         text = T; wi = p >> 5; sh = 2u * (p & 31u);
         t0 = L ? T[wi] : 0;
     }
-    // word j of the oriented read alone (step's `o` and `nb`): what a caller takes that needs no text (snp_call.hip)
-    static __device__ __forceinline__ uint64_t oriented(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb)
+    // the nb <= 32 bases of the ORIENTED read from its offset r on (r + nb <= L), whatever r is: forward the read's bases
+    // r .. r + nb - 1, turned round the reverse complement of its bases L - r - nb .. L - r - 1
+    static __device__ __forceinline__ uint64_t oriented_from(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t r, uint32_t nb)
     {
-        nb = min(32u, L - 32u * j);
-        const uint64_t s = start + (inv ? L - 32u * j - nb : 32u * j);
+        const uint64_t s = start + (inv ? L - r - nb : r);
         uint64_t w, o;
         if (b.packed) pack_read_packed<1>(DwordRow{b.bases + (s >> 2)}, nb, (uint32_t)(s & 3u), &w);
         else (void)pack_read<1>(DwordRow{b.bases + s}, nb, &w);
         if (inv) revcomp_words<1>(&w, &o, nb); else o = w;
         return o;
     }
-    __device__ __forceinline__ uint64_t step(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb, uint64_t &al,
-                                             uint64_t &o)
+    // word j of the oriented read alone (step's `o` and `nb`): what a caller takes that needs no text (snp_call.hip)
+    static __device__ __forceinline__ uint64_t oriented(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb)
     {
-        o = oriented(b, start, L, inv, j, nb);
+        nb = min(32u, L - 32u * j);
+        return oriented_from(b, start, L, inv, 32u * j, nb);
+    }
+    // word j of the text alone (step's `al`), j ascending from 0
+    __device__ __forceinline__ uint64_t text_step(uint32_t j)
+    {
         const uint64_t t1 = text[wi + j + 1]; // (the text is padded behind its end)
-        al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
+        const uint64_t al = sh ? ((t0 << sh) | (t1 >> (64 - sh))) : t0;
         t0 = t1;
+        return al;
+    }
+    // word j of a SEGMENT: `len` bases of the oriented read from its offset r0 on, aligned with the len text positions
+    // begin() was given (gapped_list.hip: the two diagonals of a gapped placement start at arbitrary read and text offsets)
+    __device__ __forceinline__ uint64_t step_from(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t r0, uint32_t len, uint32_t j,
+                                                  uint32_t &nb, uint64_t &al, uint64_t &o)
+    {
+        nb = min(32u, len - 32u * j);
+        o = oriented_from(b, start, L, inv, r0 + 32u * j, nb);
+        al = text_step(j);
         const uint64_t x = al ^ o;
         uint64_t flags = ((x >> 1) | x) & M55;
         if (nb < 32) flags &= ~0ull << (64 - 2 * nb);
         return flags;
     }
+    __device__ __forceinline__ uint64_t step(const DevBatch &b, uint64_t start, uint32_t L, bool inv, uint32_t j, uint32_t &nb, uint64_t &al,
+                                             uint64_t &o)
+    {
+        return step_from(b, start, L, inv, 0u, L, j, nb, al, o);
+    }
 };
+
+// the text's N bits of the 32 positions from x on, as flags: position x + u at bit 62 - 2u
+static __device__ __forceinline__ uint64_t mm_n_flags(const uint64_t *__restrict__ wild, uint64_t x)
+{
+    const uint64_t w = x >> 6;
+    const uint32_t s = (uint32_t)(x & 63u);
+    uint64_t v = wild[w] << s;
+    if (s > 32) v |= wild[w + 1] >> (64 - s); // (the vector is padded behind its end)
+    v >>= 32; // bit 31 - u = position x + u; now every bit to twice its place
+    v = (v | (v << 16)) & 0x0000ffff0000ffffull;
+    v = (v | (v << 8)) & 0x00ff00ff00ff00ffull;
+    v = (v | (v << 4)) & 0x0f0f0f0f0f0f0f0full;
+    v = (v | (v << 2)) & 0x3333333333333333ull;
+    v = (v | (v << 1)) & M55;
+    return v;
+}
 
 // where a read starts in its batch and how long it is; 0xffffffff for a read of a ragged batch whose offsets run backwards or
 // span more than REAL_HIP_MAX_PATL_LONG (no placement of it fits any text)

@@ -1399,12 +1399,13 @@ extern "C" int real_hip_call_stats_get(real_hip_ctx *ctx, real_hip_call_stats *o
 // ---- mismatch lists (mismatch_list.hip): the reads are staged as the pileup stages them, the records as the match's outputs;
 // count, then -- the total being known -- the overflow decision, then the lists (pair_all_run's protocol)
 static const char *const kMismatch = "mismatch lists";
-static int mismatch_outputs_check(real_hip_ctx *ctx, const real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, const uint64_t *mm_offsets, bool dev_out)
+static int mismatch_outputs_check(real_hip_ctx *ctx, const real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, const uint64_t *mm_offsets, bool dev_out,
+                                  const char *stage = kMismatch)
 {
-    if (!mm_offsets || !n_out) return stage_invalid(ctx, kMismatch, "null mm_offsets / n_out");
+    if (!mm_offsets || !n_out) return stage_invalid(ctx, stage, "null mm_offsets / n_out");
     *n_out = 0;
-    if (cap && !out) return stage_invalid(ctx, kMismatch, "null out");
-    if (dev_out && ((uintptr_t)out & 3u)) return stage_invalid(ctx, kMismatch, "out must be 4-byte aligned");
+    if (cap && !out) return stage_invalid(ctx, stage, "null out");
+    if (dev_out && ((uintptr_t)out & 3u)) return stage_invalid(ctx, stage, "out must be 4-byte aligned");
     return REAL_HIP_OK;
 }
 static int mismatch_run(real_hip_ctx *ctx, const RhStaging &io, const RhMismatchLaunch l[], int n_launch, real_hip_mismatch *out, uint64_t cap,
@@ -1514,6 +1515,51 @@ extern "C" int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params
 extern "C" int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset)
 {
     return stats_get(ctx, out, reset, "gap stats struct_size", rh_gap_stats);
+}
+
+// ---- gapped mismatch lists (gapped_list.hip): the reads are staged as the mismatch lists stage them, the gap records where the
+// pair records would be; count, the overflow decision, then the lists (mismatch_run's protocol)
+static const char *const kGapped = "gapped mismatch lists";
+extern "C" int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps,
+                                          real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, uint64_t *mm_offsets)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv[2];
+    int rc;
+    if ((rc = batch_view(ctx, b1, bv[0])) || (rc = batch_view(ctx, b2, bv[1]))) return rc;
+    const bool dev = bv[0].on_device == 1;
+    if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev, kGapped)) || (rc = mates_agree(ctx, kGapped, bv, false))) return rc;
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return stage_invalid(ctx, kGapped, "more than 2^32 fragments in one call");
+    if (n && !gaps) return stage_invalid(ctx, kGapped, "null gaps");
+    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, kGapped, "the gap records must be 16-byte aligned");
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    const DevBatch d1 = dev_batch(ctx, st[0], n), d2 = dev_batch(ctx, st[1], n);
+    RhGapStage &S = rh_gap_stage(ctx);
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    const real_hip_gap_place *d_gaps = gaps;
+    uint64_t *d_off = mm_offsets;
+    real_hip_mismatch *d_out = out;
+    uint64_t total = 0;
+    if (n) rc = io.in(S.gl_rec, gaps, n, d_gaps);
+    if (!rc) rc = io.inout(S.gl_off, mm_offsets, n + 1, true, d_off); // (outputs: nothing is uploaded)
+    if (!rc) rc = rh_gapped_list_count(ctx, d1, d2, d_gaps, n, d_off, &total);
+    if (!rc) {
+        *n_out = total;
+        rc = io.back(mm_offsets, d_off, n + 1, "download of the gapped mismatch offsets");
+    }
+    if (!rc && total > cap) rc = rh_fail(ctx, REAL_HIP_E_OVERFLOW, "gapped mismatch lists: the buffer needs more room", hipSuccess);
+    if (!rc) rc = io.inout(S.gl_out, out, total, true, d_out, sizeof(real_hip_mismatch));
+    if (!rc) rc = rh_gapped_list_emit(ctx, d1, d2, d_gaps, n, d_off, d_out, total);
+    if (!rc) rc = io.back(out, d_out, total, "download of the gapped mismatch lists");
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped_list_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "gapped list stats struct_size", rh_gapped_list_stats);
 }
 
 // ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no

@@ -60,6 +60,11 @@ void RealOptions::printHelp() const
               << "-gap_flank <fewest aligned bases on either side of the gap, default=8>\n"
               << "-gap_maxcost <a placement costs 4 per mismatch and 6 + its length for the gap, and at most this, default=4 * (-e) + 6 + (-gap_max)>\n"
               << "-gap_margin <a placement is unique if no other locus of the window costs at most its cost + this, default=0>\n"
+              << "-sam_gapped <0|1: with -sam, -gapped and -p2, a mate -gapped places uniquely is written to the -sam file as placed: FLAG,\n"
+              << "   POS, the CIGAR with its insertion or deletion (40M2D60M), NM:i, MD:Z (40^AC60) and ZC:i:<cost>, MAPQ 255; its mate's line\n"
+              << "   names it (RNEXT, PNEXT, TLEN over the span on the text, FLAG 32), and both carry FLAG 2 if the outer distance lies in\n"
+              << "   -insert_min .. -insert_max; the rescue then runs with the -sam pass, once; the -gapped file is unchanged; a summary line\n"
+              << "   goes to standard error; default=0: the -sam file is what it is without -gapped>\n"
               << "-insert_hist <file: with -p2, receives the histogram of the outer distances of the Unique fragments (after the last\n"
               << "   genome file) as lines outer<TAB>count, the last bin (-insert_max + 1) holding what lies beyond; the quartiles go to\n"
               << "   standard error; -o is unchanged; not with -pairs_all 1>\n"
@@ -169,6 +174,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-gap_max") { gap_max = strtoul(need("-gap_max").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-gap_flank") { gap_flank = strtoul(need("-gap_flank").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-gap_maxcost") { gap_maxcost = strtol(need("-gap_maxcost").c_str(), 0, 10); gap_flags_given = true; i += 2; }
+        else if (a == "-sam_gapped") { sam_gapped = atoi(need("-sam_gapped").c_str()) != 0; sam_gapped_given = true; i += 2; }
         else if (a == "-gap_margin") { gap_margin = strtoul(need("-gap_margin").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-insert_hist") { inserthistfilename = need("-insert_hist"); insert_flags_given = true; i += 2; }
         else if (a == "-insert_auto") { insert_auto = strtoull(need("-insert_auto").c_str(), 0, 10); insert_flags_given = true; i += 2; }
@@ -301,6 +307,12 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (!mapq) throw std::runtime_error("-pileup_minmapq needs -mapq 1.");
         if (!pileup_given && !pileup_depth_given && !vcf_given) throw std::runtime_error("-pileup_minmapq is only meaningful with -pileup / -vcf.");
         if (pileup_minmapq < 0 || pileup_minmapq > (long)REAL_HIP_MAPQ_MAX) throw std::runtime_error("-pileup_minmapq must be in 0..60.");
+    }
+    if (sam_gapped) { // the rescued mates in the -sam file: loud errors before anything runs
+        if (pattern2filename.empty()) throw std::runtime_error("-sam_gapped 1 is only meaningful with -p2 (paired-end reads).");
+        if (!sam_given) throw std::runtime_error("-sam_gapped 1 writes the rescued mates into the -sam file: it needs -sam.");
+        if (!gapped_given) throw std::runtime_error("-sam_gapped 1 writes the mates the gap rescue places: it needs -gapped.");
+        if (pairs_all) throw std::runtime_error("-sam_gapped 1 cannot be combined with -pairs_all 1.");
     }
     if (gapped_given) { // gap rescue: loud errors before anything runs
         if (pattern2filename.empty()) throw std::runtime_error("-gapped is only meaningful with -p2 (paired-end reads).");

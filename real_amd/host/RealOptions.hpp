@@ -57,6 +57,7 @@ struct RealOptions {
     bool gapped_given = false, gap_flags_given = false; // (-gapped / one of -gap_* was on the command line)
     unsigned long gap_max = 8, gap_flank = 8, gap_margin = 0; // -gap_max, -gap_flank, -gap_margin
     long gap_maxcost = -1;            // -gap_maxcost: -1 = 4 * (-e) + 6 + (-gap_max)
+    bool sam_gapped = false, sam_gapped_given = false; // -sam_gapped: with -sam and -gapped, the rescued mates' SAM lines carry their gapped placement (real_hip_mismatches_gapped)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
     std::string inserthistfilename;   // -insert_hist: the file that receives the histogram of the Unique fragments' outer distances (real_hip_pair_insert_hist)
     std::string pileupfilename;       // -pileup: the file that receives the sites of the pileup of the final placements (real_hip_pileup_*)

@@ -7,6 +7,7 @@
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
 //   host_selftest gapped_options <args...>        -> prints the parsed -gapped file ("." if none), -gap_max, -gap_flank, -gap_maxcost, -gap_margin
+//   host_selftest sam_gapped_options <args...>    -> prints the parsed -sam_gapped flag (0|1), the -sam and the -gapped file ("." if none)
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
 //   host_selftest records                         -> checks the decoders of the final records (csrc/final_record.h) against records written
@@ -16,6 +17,9 @@
 //       from the records in <dir> (names.txt: a line "file<TAB>start<TAB>name" per fragment and one "file<TAB>n<TAB>" behind a file's
 //       last; info.u64 score.f32, or pairs.bin s1.bin s2.bin; per genome file mm<fi>.bin moff<fi>.u64), formatted by Sam.hpp from
 //       the host reader's blocks and (single-end) from the text
+//   host_selftest sam_gapped <dir> <fastq:0|1> <qoff> <insert_min> <insert_max> -> <dir>/block.sam: the -sam file of `real -sam_gapped 1` for the
+//       mates <dir>/r1 and r2: the files of the paired `sam` command and gaps.bin (the gap records), cigars.txt (a line per fragment: the
+//       record's CIGAR, * without one), per genome file gmm<fi>.bin goff<fi>.u64 (the gapped lists)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -51,7 +55,8 @@ static std::vector<T> slurp(const std::string &fn)
 }
 
 // the -sam file from records and lists on disk, through the functions `real` formats with
-static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, bool paired)
+static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, bool paired, bool gapped = false, uint64_t insert_min = 0,
+                       uint64_t insert_max = 0)
 {
     std::vector<std::vector<std::string>> names;
     std::vector<std::vector<uint64_t>> starts;
@@ -68,6 +73,14 @@ static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, 
     const std::vector<float> score = slurp<float>(d + "/score.f32");
     const std::vector<real_hip_pair> pairs = slurp<real_hip_pair>(d + "/pairs.bin");
     const std::vector<real_hip_single> s1 = slurp<real_hip_single>(d + "/s1.bin"), s2 = slurp<real_hip_single>(d + "/s2.bin");
+    std::vector<real_hip_gap_place> gaps;
+    std::vector<std::string> cigars;
+    if (gapped) {
+        gaps = slurp<real_hip_gap_place>(d + "/gaps.bin");
+        std::ifstream cf((d + "/cigars.txt").c_str());
+        for (std::string line; std::getline(cf, line);) cigars.push_back(line);
+        if (gaps.size() != pairs.size() || cigars.size() != pairs.size()) return 5;
+    }
     // the reads, whole: as one block of the host reader and (single-end) as one chunk of text with its spans
     ReadBlock b1, b2;
     ReadReader r1(d + "/r1", fastq, qoff);
@@ -98,6 +111,9 @@ static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, 
         for (unsigned fi = 0; fi < names.size(); ++fi) {
             const std::vector<real_hip_mismatch> mm = slurp<real_hip_mismatch>(d + "/mm" + std::to_string(fi) + ".bin");
             const std::vector<uint64_t> moff = slurp<uint64_t>(d + "/moff" + std::to_string(fi) + ".u64");
+            std::vector<real_hip_mismatch> gmm;
+            std::vector<uint64_t> goff;
+            if (gapped) { gmm = slurp<real_hip_mismatch>(d + "/gmm" + std::to_string(fi) + ".bin"); goff = slurp<uint64_t>(d + "/goff" + std::to_string(fi) + ".u64"); }
             const bool last = fi + 1 == names.size();
             for (uint64_t i = 0; i < n; ++i) {
                 if (!paired) {
@@ -105,7 +121,10 @@ static int samSelftest(const std::string &d, bool fastq, int qoff, bool scores, 
                 } else {
                     const ReadView r[2] = {v1[i], v2[i]};
                     const SamPlace at[2] = {samPlace(pairs[i], s1[i], 0), samPlace(pairs[i], s2[i], 1)};
-                    appendSamFragment(out, r, refs, at, fi, last, mm.data(), moff.data(), i, scores);
+                    if (gapped && REAL_HIP_GAP_STATE(gaps[i].tag) == REAL_HIP_PAIR_UNIQUE)
+                        appendSamRescued(out, r, refs, at, gaps[i], cigars[i].c_str(), fi, insert_min, insert_max, mm.data(), moff.data(), i, gmm.data() + goff[i],
+                                         goff[i + 1] - goff[i], scores);
+                    else appendSamFragment(out, r, refs, at, fi, last, mm.data(), moff.data(), i, scores);
                 }
             }
         }
@@ -121,6 +140,8 @@ int main(int argc, char **argv)
         if (argc < 2) return 2;
         std::string cmd = argv[1];
         if (cmd == "sam" && argc == 7) return samSelftest(argv[2], atoi(argv[3]) != 0, atoi(argv[4]), atoi(argv[5]) != 0, atoi(argv[6]) != 0);
+        if (cmd == "sam_gapped" && argc == 7)
+            return samSelftest(argv[2], atoi(argv[3]) != 0, atoi(argv[4]), false, true, true, strtoull(argv[5], 0, 10), strtoull(argv[6], 0, 10));
         if (cmd == "genome" && argc == 4) {
             GenomeText G; G.load(argv[2]);
             std::string d = argv[3];
@@ -403,6 +424,11 @@ int main(int argc, char **argv)
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.gappedfilename.empty() ? "." : o.gappedfilename) << " " << o.gap_max << " " << o.gap_flank << " " << o.gap_maxcost << " "
                       << o.gap_margin << "\n";
+            return 0;
+        }
+        if (cmd == "sam_gapped_options") { // -sam_gapped
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.sam_gapped ? 1 : 0) << " " << (o.samfilename.empty() ? "." : o.samfilename) << " " << (o.gappedfilename.empty() ? "." : o.gappedfilename) << "\n";
             return 0;
         }
         if (cmd == "insert_options") { // -insert_hist, -insert_auto

@@ -661,6 +661,31 @@ struct SamLists {
     }
 };
 
+// -sam_gapped 1: the lists of the mates the gap rescue placed, list i for fragment i of the batch (real_hip_mismatches_gapped);
+// the protocol of SamLists::fill, the stage's own statistics summed over the run
+struct GappedLists {
+    std::vector<real_hip_mismatch> mm = std::vector<real_hip_mismatch>(1024);
+    std::vector<uint64_t> off;
+    uint64_t mates = 0, deleted = 0, inserted = 0, disagree = 0;
+    void fill(real_hip_ctx *h, uint64_t n, const real_hip_batch *rb1, const real_hip_batch *rb2, const real_hip_gap_place *gaps)
+    {
+        off.assign(n + 1, 0);
+        uint64_t total = 0;
+        real_hip_gapped_list_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        int rc = real_hip_mismatches_gapped(h, rb1, rb2, gaps, mm.data(), mm.size(), &total, off.data());
+        if (rc == REAL_HIP_E_OVERFLOW) {
+            check(h, real_hip_gapped_list_stats_get(h, &st, 1), "real_hip_gapped_list_stats_get");
+            mm.resize(total + total / 8 + 16);
+            rc = real_hip_mismatches_gapped(h, rb1, rb2, gaps, mm.data(), mm.size(), &total, off.data());
+        }
+        check(h, rc, "real_hip_mismatches_gapped");
+        check(h, real_hip_gapped_list_stats_get(h, &st, 1), "real_hip_gapped_list_stats_get");
+        mates += st.placed; deleted += st.deleted; inserted += st.inserted; disagree += st.disagree;
+    }
+};
+
 template <class WriteAll>
 void samPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, WriteAll writeAll)
 {
@@ -938,20 +963,50 @@ inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, b
 // Runs where samPass runs, through the same textPass: per genome file the reads once more, each batch with its FINAL records;
 // the first file starts the gap records, the others fold into them.  Then the reads a last time for the ids: one line per Unique
 // record, in read order, and the summary line on standard error.
-void gapPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, const real_hip_pair_params &pp,
-             const std::vector<real_hip_pair> &pairs, const std::vector<real_hip_single> &singles1, const std::vector<real_hip_single> &singles2,
-             uint64_t numpat, int qoff1, int qoff2, ReadBlock &b1, ReadBlock &b2)
+// -sam_gapped 1: the rescue of a genome file has run with that file's -sam pass (GapRun::rescue, every record started NoMatch,
+// every file folded into them: the same array), so the records and the summed counters are already here and no pass is run.
+inline real_hip_gap_params gapParams(const RealOptions &o)
 {
-    if (!o.gapped_given) return;
-    OutFile out(o.gappedfilename, false, "-gapped");
     real_hip_gap_params gp;
     memset(&gp, 0, sizeof gp);
     gp.struct_size = sizeof gp; gp.max_gap = (uint32_t)o.gap_max; gp.min_flank = (uint32_t)o.gap_flank;
     gp.cost_mismatch = 4; gp.cost_open = 6; gp.cost_extend = 1; gp.max_cost = (uint32_t)o.gap_maxcost; gp.margin = (uint32_t)o.gap_margin;
-    std::vector<real_hip_gap_place> gaps(numpat);
+    return gp;
+}
+// the gap records of the run and the counters of its rescue calls
+struct GapRun {
+    std::vector<real_hip_gap_place> gaps;
     real_hip_gap_stats sum;
-    memset(&sum, 0, sizeof sum);
-    textPass(o, files, T, [&](CtxVec &gc, unsigned fi, const GenomeText &) {
+    bool rescued = false; // the -sam pass ran the rescue
+    GapRun() { memset(&sum, 0, sizeof sum); }
+    // every record NoMatch, as a call with fresh != 0 starts them
+    void start(uint64_t numpat)
+    {
+        real_hip_gap_place none;
+        memset(&none, 0, sizeof none);
+        none.second = REAL_HIP_GAP_NONE;
+        gaps.assign(numpat, none);
+    }
+    void addStats(real_hip_ctx *h)
+    {
+        real_hip_gap_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        check(h, real_hip_gap_stats_get(h, &st, 1), "real_hip_gap_stats_get");
+        sum.eligible += st.eligible; sum.placed += st.placed; sum.unique += st.unique; sum.gapped += st.gapped;
+    }
+};
+void gapPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, const real_hip_pair_params &pp,
+             const std::vector<real_hip_pair> &pairs, const std::vector<real_hip_single> &singles1, const std::vector<real_hip_single> &singles2,
+             uint64_t numpat, int qoff1, int qoff2, ReadBlock &b1, ReadBlock &b2, GapRun &run)
+{
+    if (!o.gapped_given) return;
+    OutFile out(o.gappedfilename, false, "-gapped");
+    const real_hip_gap_params gp = gapParams(o);
+    if (!run.rescued) run.gaps.assign(numpat, real_hip_gap_place());
+    std::vector<real_hip_gap_place> &gaps = run.gaps;
+    real_hip_gap_stats &sum = run.sum;
+    if (!run.rescued) textPass(o, files, T, [&](CtxVec &gc, unsigned fi, const GenomeText &) {
         real_hip_ctx *h = gc[0]->h;
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
@@ -967,11 +1022,7 @@ void gapPass(const RealOptions &o, const std::vector<std::string> &files, const 
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-        real_hip_gap_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
-        check(h, real_hip_gap_stats_get(h, &st, 1), "real_hip_gap_stats_get");
-        sum.eligible += st.eligible; sum.placed += st.placed; sum.unique += st.unique; sum.gapped += st.gapped;
+        run.addStats(h);
     });
     ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
     const ReadSource m1(b1), m2(b2);
@@ -1215,6 +1266,12 @@ int matchPairs(const RealOptions &o)
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
     });
+    // -sam_gapped 1: the pass of a genome file rescues the fragments whose anchor lies in it (the text is resident: what the
+    // rescue needs), lists the rescued mates in gapped coordinates and writes their lines; gapPass then finds the records made
+    GapRun gap_run;
+    GappedLists GL;
+    const real_hip_gap_params gp = gapParams(o);
+    if (o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         const ReadSource v1 = m1.withQuality(o.fastq, qoff1), v2 = m2.withQuality(o.fastq2, qoff2);
@@ -1227,19 +1284,34 @@ int matchPairs(const RealOptions &o)
             const double tm = now_s();
             L.fill(sc[0]->h, "real_hip_mismatches_pairs", 2 * n, real_hip_mismatches_pairs, &rb1, &rb2, (const real_hip_pair *)pairs.data() + seen,
                    (const real_hip_single *)singles1.data() + seen, (const real_hip_single *)singles2.data() + seen);
+            if (o.sam_gapped) {
+                check(sc[0]->h, real_hip_gap_rescue(sc[0]->h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0,
+                                                    gap_run.gaps.data() + seen), "real_hip_gap_rescue");
+                GL.fill(sc[0]->h, n, &rb1, &rb2, gap_run.gaps.data() + seen);
+            }
             T.match += now_s() - tm;
             formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
                 const ReadView r[2] = {v1[i], v2[i]};
                 SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
                 at[0].duplicate = at[1].duplicate = o.dedup && dup[seen + i]; // (a duplicate fragment is Unique: both mates have lines)
                 if (o.mapq) { at[0].mapq = mapq[2 * (seen + i)]; at[1].mapq = mapq[2 * (seen + i) + 1]; }
-                appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
+                if (o.sam_gapped && REAL_HIP_GAP_STATE(gap_run.gaps[seen + i].tag) == REAL_HIP_PAIR_UNIQUE) {
+                    const real_hip_gap_place &g = gap_run.gaps[seen + i];
+                    char cigar[48] = "*";
+                    real_hip_gap_cigar(&g, (uint32_t)r[REAL_HIP_GAP_TARGET(g.tag)].patl, cigar, sizeof cigar);
+                    appendSamRescued(s, r, refs, at, g, cigar, fi, pp.min_insert, pp.max_insert, L.mm.data(), L.off.data(), i, GL.mm.data() + GL.off[i],
+                                     GL.off[i + 1] - GL.off[i], o.scores);
+                } else appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
             });
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        if (o.sam_gapped) gap_run.addStats(sc[0]->h);
     });
-    gapPass(o, files, RS, T, pp, pairs, singles1, singles2, numpat, qoff1, qoff2, b1, b2);
+    if (o.sam_gapped)
+        fprintf(stderr, "sam gapped: mates=%llu deleted=%llu inserted=%llu disagree=%llu\n", (unsigned long long)GL.mates, (unsigned long long)GL.deleted,
+                (unsigned long long)GL.inserted, (unsigned long long)GL.disagree);
+    gapPass(o, files, RS, T, pp, pairs, singles1, singles2, numpat, qoff1, qoff2, b1, b2, gap_run);
     T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;
 }

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "real_hip_mapq_acc_merge", "real_hip_mapq_of", "real_hip_mapq_hits", "real_hip_mapq_pair_hits", "real_hip_match_mapq",
     "real_hip_match_pairs_mapq", "real_hip_mapq", "real_hip_mapq_pairs", "real_hip_mapq_stats_get",
     "real_hip_gap_rescue", "real_hip_gap_cigar", "real_hip_gap_stats_get",
+    "real_hip_mismatches_gapped", "real_hip_gapped_list_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -224,6 +225,11 @@ GAP_PLACE_DTYPE = np.dtype(RealHipGapPlace)
 assert GAP_PLACE_DTYPE.itemsize == 16
 GAP_STATS_FIELDS = ("fragments", "eligible", "other_file", "skipped", "positions", "placed", "unique", "gapped", "launches", "kernel_ms")
 RealHipGapStats = _stats_struct("RealHipGapStats", GAP_STATS_FIELDS)
+# gapped mismatch lists (include/real_hip.h, "gapped mismatch lists"): MISMATCH_DTYPE records in the text coordinates of a gap record
+MISMATCH_DELETED = 4   # `base` of a text position the read's deletion skips
+GAPPED_LIST_STATS_FIELDS = ("fragments", "placed", "other_file", "invalid", "aligned_bases", "mismatches", "deleted", "inserted", "on_n",
+                            "disagree", "launches", "kernel_ms")
+RealHipGappedListStats = _stats_struct("RealHipGappedListStats", GAPPED_LIST_STATS_FIELDS)
 
 
 class RealHipPairHit(C.Structure):
@@ -370,6 +376,8 @@ def load():
     L.real_hip_gap_rescue.argtypes = [vp, pairp, C.POINTER(RealHipGapParams), batch, batch, vp, vp, vp, ci, vp]
     L.real_hip_gap_cigar.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
     L.real_hip_gap_stats_get.argtypes = [vp, C.POINTER(RealHipGapStats), ci]
+    L.real_hip_mismatches_gapped.argtypes = [vp, batch, batch, vp, vp, u64, pu64, vp]
+    L.real_hip_gapped_list_stats_get.argtypes = [vp, C.POINTER(RealHipGappedListStats), ci]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
     L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
     L.real_hip_timing_enable.argtypes = [vp, ci]

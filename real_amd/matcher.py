@@ -998,6 +998,24 @@ class PairMatcher(AllMatcher):
     def gap_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipGapStats, self._L.real_hip_gap_stats_get, reset)
 
+    # -- gapped mismatch lists: where a rescued mate differs from the text, in the coordinates of its gapped placement --
+    def mismatches_gapped(self, mate1, mate2, gaps, cap: int = 0):
+        """real_hip_mismatches_gapped: list i is that of fragment i's gap record (what gap_rescue returned): the aligned bases
+        of the record's target mate that differ from the text and the text bases its deletion skips (base =
+        lib.MISMATCH_DELETED) -> (lists as lib.MISMATCH_DTYPE, offsets).  Mates and records as for mismatches_pairs: all host
+        arrays, all device tensors, or device reads with numpy records"""
+        host = isinstance(gaps, np.ndarray)
+        if host:
+            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
+        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
+        self.sync_inputs(gaps)
+        n = int(b1.n_reads)
+        return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches_gapped(
+            self._h, C.byref(b1), C.byref(b2), _ptr(gaps), o, c, no, po), n, not host, cap or max(1024, 4 * n))
+
+    def gapped_list_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipGappedListStats, self._L.real_hip_gapped_list_stats_get, reset)
+
     def single_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
 
