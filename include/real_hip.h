@@ -963,6 +963,106 @@ typedef struct real_hip_gapped_list_stats {
 } real_hip_gapped_list_stats;
 int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped_list_stats *out, int reset);
 
+/* ---- indel calls: what the gap-rescued mates add up to over one genome file -- which insertions and deletions they show, how
+ * many mates show each, and with which genotype (off unless these entry points are called).  The reference has no caller and
+ * no finished gapped mode; the semantics are this project's own.  Everything is an integer.
+ * PROTOCOL.  The stage sits on a FINISHED pileup of the resident text (n bases, file id f), as the variant calls do, and uses
+ * that pileup's depth[] and its min_qual.  indel_begin (a second begin starts again), any number of indel_add, indel_finish
+ * (synchronises; may be called again with other thresholds, it then only re-reads the grouped events), indel_events /
+ * indel_calls any number of times after a finish (the capacity protocol of real_hip_pileup_sites: *n_out always receives the
+ * count, REAL_HIP_E_OVERFLOW writes nothing), indel_end.  real_hip_pileup_end and a new real_hip_pileup_begin end the stage as
+ * well.  REAL_HIP_E_INVALID with a message, nothing launched: calls out of turn (begin without a finished pileup, add without
+ * begin or after finish, finish without begin, events / calls before finish), a text replaced by one of another n_bases or
+ * file id, NULL batches, NULL gaps with n_reads > 0, batches that disagree in n_reads or on_device, a wrong struct_size, more
+ * than 2^32 fragments in one call.  gaps and the output lists live where real_hip_mismatches_gapped's live for the batches'
+ * on_device: gaps are host memory for 0 and 2, device memory (16-byte aligned) for 1; the lists go to host memory unless the
+ * list call's own on_device says otherwise.
+ * WHICH RECORDS.  Fragment i's record, its target mate REAL_HIP_GAP_TARGET(tag), its orientation and the ORIENTED read R are
+ * those of the block "gapped mismatch lists", word for word.  In this order: 1. a record that is not Unique is skipped; 2. a
+ * Unique record of another file id than f is skipped and counted as other_file; 3. a Unique record of file f that does not FIT
+ * by that block's rule, or whose frag is not a fragment of the text, or whose span [p, p + L + g) does not lie inside fragment
+ * frag = [fs, fe), is counted as invalid, and nothing outside the arrays is read for it; 4. a fitting record with g == 0 is
+ * counted as ungapped and gives no event.
+ * EVENT.  A fitting record with g != 0, p = pos, j = split and d = max(-g, 0) gives one event (x, g, S) with x = p + j: for
+ * g > 0 the text bases [x, x + g) are deleted and S is empty; for g < 0 S = R[j .. j + d) is inserted in front of text position
+ * x.  The ANCHOR is text position x - 1 (>= fs, because j >= 1).  If the text's N bit is set at the anchor or anywhere in
+ * [x, x + max(g, 0)), the event is dropped and counted as on_n.
+ * QUALITY.  q is the minimum of the quality bytes of the oriented read offsets j - 1, j + d and, for an insertion,
+ * j .. j + d - 1 (the reverse strand indexes L - 1 - i, as the pileup does; a batch without qualities counts as 30).  If
+ * q < min_qual of the pileup the event is dropped and counted as low_qual.
+ * LEFT-NORMALISATION against the text, so that two reads name one event whatever the rescue's split was.  At most
+ * REAL_HIP_INDEL_SHIFT_MAX times, while x - 1 > fs, the N bits at x - 1 and x - 2 are clear, and
+ *   deletion:  text[x - 1] == text[x + g - 1]                       then x -= 1
+ *   insertion: text[x - 1] == S[d - 1]                              then S = text[x - 1] . S[0 .. d - 1), x -= 1
+ * An event that stops only because of the cap is counted as shift_capped.  (The number of shifts is the length of the run,
+ * ending at x, of positions i with T'[i] == T'[i + |g|], T' the text for a deletion and text[0, x) . S for an insertion.)
+ * GROUPS.  Two events are equal iff (x, g, S) are equal after normalisation; S is packed 2 bits a base, the first base lowest,
+ * in a u32 (REAL_HIP_GAP_MAX bases fill it exactly; 0 for a deletion).  Per distinct event: alt_n, the supporting mates;
+ * alt_fwd, those whose record is not inverted; qsum, the sum of their q; ref_n = min(depth[x - 1], depth[x]) of the finished
+ * pileup (it holds only ungapped placements: no mate counts on both sides).  All counters are u32.  The event list is in
+ * ascending (x, g, S), g compared as a signed number.
+ * GENOTYPE, in phred units: PL(0/0) = qsum, PL(0/1) = REAL_HIP_CALL_HET * (ref_n + alt_n) + REAL_HIP_INDEL_PRIOR_HET,
+ * PL(1/1) = REAL_HIP_INDEL_REF_Q * ref_n + REAL_HIP_INDEL_PRIOR_HOM (the SNP priors plus 10: indels are about ten times
+ * rarer).  The best genotype is the first of minimal PL in the order 0/0, 0/1, 1/1; QUAL = PL(0/0) - PL(best) (as u32; beyond
+ * 2^32 - 1 it counts as that), GQ = min(99, smallest other PL - PL(best)).  A CALL is an event with best != 0/0, QUAL >=
+ * min_call_qual, alt_n >= min_alt and ref_n + alt_n >= min_depth.  The call list is the calls in the events' order.
+ * Nothing depends on lanes, waves, the order of the records, the split into add calls or on_device: two adds give what one add
+ * on the concatenation gives.                                                                                                 */
+#define REAL_HIP_INDEL_SHIFT_MAX 256u
+#define REAL_HIP_INDEL_REF_Q     30u /* phred cost of a read without the indel under a homozygous indel                   */
+#define REAL_HIP_INDEL_PRIOR_HET 40u
+#define REAL_HIP_INDEL_PRIOR_HOM 43u
+typedef struct real_hip_indel_params {
+    uint32_t struct_size;   /* = sizeof(real_hip_indel_params)                                        */
+    uint32_t min_call_qual; /* a call needs QUAL >= this                                              */
+    uint32_t min_alt;       /* and alt_n >= this                                                      */
+    uint32_t min_depth;     /* and ref_n + alt_n >= this                                              */
+} real_hip_indel_params;
+typedef struct real_hip_indel {   /* 32 bytes; the records of the event list and of the call list */
+    uint32_t pos;           /* the anchor x - 1, 0-based position in the text                         */
+    uint32_t ref_n;
+    uint32_t alt_n;
+    uint32_t alt_fwd;
+    uint32_t qsum;
+    uint32_t qual;          /* QUAL                                                                   */
+    uint32_t seq;           /* the packed S; 0 for a deletion                                         */
+    int8_t   gap;           /* g: > 0 deletion, < 0 insertion                                         */
+    uint8_t  gt;            /* 0: no call under the last finish's thresholds, 1: 0/1, 2: 1/1          */
+    uint8_t  gq;            /* GQ                                                                     */
+    uint8_t  ref;           /* the text's base 0..3 at the anchor                                     */
+} real_hip_indel;
+int real_hip_indel_begin(real_hip_ctx *ctx);
+/* batch1 and batch2 must agree in n_reads and on_device; gaps: what real_hip_gap_rescue wrote for them */
+int real_hip_indel_add(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps);
+int real_hip_indel_finish(real_hip_ctx *ctx, const real_hip_indel_params *p, uint64_t *n_events, uint64_t *n_calls);
+int real_hip_indel_events(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device);
+int real_hip_indel_calls(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device);
+int real_hip_indel_end(real_hip_ctx *ctx);
+/* work of the stage.  fragments .. shift_capped, launches and kernel_ms are accumulated since the last reset; distinct ..
+ * insertions are those of the last finish (0 from begin until then)                                                       */
+typedef struct real_hip_indel_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_indel_stats), 0                              */
+    uint64_t fragments;      /* fragments handed in                                                    */
+    uint64_t placed;         /* Unique records of this file that fit                                   */
+    uint64_t other_file;     /* Unique records of another file id                                      */
+    uint64_t invalid;        /* Unique records of this file that do not fit                            */
+    uint64_t ungapped;       /* placed with g == 0                                                     */
+    uint64_t events;         /* increments of alt_n                                                    */
+    uint64_t on_n;           /* events dropped on an N of the text                                     */
+    uint64_t low_qual;       /* events that min_qual dropped                                           */
+    uint64_t shifted;        /* events the normalisation moved by at least one base                    */
+    uint64_t shift_capped;   /* events that stopped only at REAL_HIP_INDEL_SHIFT_MAX                   */
+    uint64_t distinct;       /* distinct events                                                        */
+    uint64_t calls;
+    uint64_t het;
+    uint64_t hom;
+    uint64_t deletions;      /* calls with g > 0                                                       */
+    uint64_t insertions;     /* calls with g < 0                                                       */
+    uint64_t launches;       /* kernels launched (a sort or a scan counts one)                         */
+    double   kernel_ms;      /* HIP events on the ctx's stream around the kernels of add and finish    */
+} real_hip_indel_stats;
+int real_hip_indel_stats_get(real_hip_ctx *ctx, real_hip_indel_stats *out, int reset);
+
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a
  * concatenation in rank order, nothing is reduced because no read is seen by two ranks.  The reference is a single

@@ -20,6 +20,7 @@
 // no scratch memory; plain C++ and vector stores.
 #include "real_hip_internal.h"
 #include "read_walk.h"
+#include "indel_stage.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -137,6 +138,7 @@ __global__ void __launch_bounds__(RH_PU_BLOCK) pileup_sites_kernel(const PileupF
 static void pileup_release(real_hip_ctx *ctx)
 {
     rh_call_release(ctx); // (the calls stand on this pileup's sites: they go with it)
+    rh_indel_release(ctx); // (the indel calls on its depth)
     rh_release(ctx, ctx->pu_diff); rh_release(ctx, ctx->pu_alt); rh_release(ctx, ctx->pu_blk); rh_release(ctx, ctx->pu_sites);
     ctx->pu_state = 0; ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
 }

@@ -4,6 +4,7 @@
 #include "pair_state.h"
 #include "mapq_stage.h"
 #include "gap_stage.h"
+#include "indel_stage.h"
 
 #include <chrono>
 #include <cmath>
@@ -245,6 +246,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     rh_comm_destroy(c);
     rh_mapq_release(c);
     rh_gap_release(c);
+    rh_indel_drop(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -1560,6 +1562,93 @@ extern "C" int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batc
 extern "C" int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped_list_stats *out, int reset)
 {
     return stats_get(ctx, out, reset, "gapped list stats struct_size", rh_gapped_list_stats);
+}
+
+// ---- indel calls (indel_call.hip): on top of the finished pileup; the reads are staged as the gapped mismatch lists stage
+// them (with their qualities), the gap records where the pair records would be.  Every check comes before the first launch
+static const char *const kIndel = "indel calls";
+static int indel_pileup_check(real_hip_ctx *ctx, const char *unfinished)
+{
+    if (ctx->pu_state != 2) return stage_invalid(ctx, kIndel, unfinished);
+    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+        return stage_invalid(ctx, kIndel, "the text was replaced since the pileup's begin");
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_indel_begin(real_hip_ctx *ctx)
+{
+    RH_ENTER(ctx);
+    int rc = indel_pileup_check(ctx, "begin needs a finished pileup");
+    if (rc) return rc;
+    return rh_sync_tail(ctx, rh_indel_begin(ctx));
+}
+
+extern "C" int real_hip_indel_add(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv[2];
+    int rc;
+    if ((rc = mates_view(ctx, kIndel, b1, b2, false, bv))) return rc;
+    RhIndelStage &S = rh_indel_stage(ctx);
+    if (S.state == 0) return stage_invalid(ctx, kIndel, "add without begin");
+    if (S.state == 2) return stage_invalid(ctx, kIndel, "add after finish");
+    if ((rc = indel_pileup_check(ctx, "add without a finished pileup"))) return rc;
+    const bool dev = bv[0].on_device == 1;
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return stage_invalid(ctx, kIndel, "more than 2^32 fragments in one call");
+    if (n && !gaps) return stage_invalid(ctx, kIndel, "null gaps");
+    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, kIndel, "the gap records must be 16-byte aligned");
+    if (!n) return REAL_HIP_OK;
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    DevBatch d[2];
+    for (int m = 0; m < 2; ++m) {
+        d[m] = dev_batch(ctx, st[m], n);
+        d[m].qual = st[m].qual; // (handed on whatever -q says, as the pileup does)
+    }
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    const real_hip_gap_place *d_gaps = gaps;
+    rc = io.in(S.rec, gaps, n, d_gaps);
+    if (!rc) rc = rh_indel_add(ctx, d[0], d[1], d_gaps, n);
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_indel_finish(real_hip_ctx *ctx, const real_hip_indel_params *p, uint64_t *n_events, uint64_t *n_calls)
+{
+    RH_ENTER(ctx);
+    if (!p || p->struct_size != sizeof(real_hip_indel_params)) return stage_invalid(ctx, kIndel, "params struct_size");
+    if (rh_indel_stage(ctx).state == 0) return stage_invalid(ctx, kIndel, "finish without begin");
+    int rc = indel_pileup_check(ctx, "finish without a finished pileup");
+    if (rc) return rc;
+    return finish_tail(ctx, rh_sync_tail(ctx, rh_indel_finish(ctx, *p, n_events, n_calls)), rh_indel_release);
+}
+
+extern "C" int real_hip_indel_events(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    RH_ENTER(ctx);
+    RhIndelStage &S = rh_indel_stage(ctx);
+    return list_out(ctx, S.state == 2, kIndel, "events", "event list", S.events.p, S.n_groups, sizeof(real_hip_indel), out, cap, n_out, on_device);
+}
+
+extern "C" int real_hip_indel_calls(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device)
+{
+    RH_ENTER(ctx);
+    RhIndelStage &S = rh_indel_stage(ctx);
+    return list_out(ctx, S.state == 2, kIndel, "calls", "call list", S.calls.p, S.n_calls, sizeof(real_hip_indel), out, cap, n_out, on_device);
+}
+
+extern "C" int real_hip_indel_end(real_hip_ctx *ctx)
+{
+    RH_ENTER(ctx);
+    (void)hipStreamSynchronize(ctx->stream);
+    rh_indel_release(ctx);
+    return REAL_HIP_OK;
+}
+
+extern "C" int real_hip_indel_stats_get(real_hip_ctx *ctx, real_hip_indel_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "indel stats struct_size", rh_indel_stats);
 }
 
 // ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no

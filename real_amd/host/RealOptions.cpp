@@ -84,9 +84,15 @@ void RealOptions::printHelp() const
               << "-pileup_minq <Q: with -pileup, a mismatch of quality below Q is not counted, 0..63, default=0>\n"
               << "-vcf <file: after the pileup of a genome file (it runs also without -pileup; -pileup_minq then applies to it), call SNPs at\n"
               << "   its sites: the reads once more, bases of quality >= -pileup_minq counted per site, ten genotype likelihoods in integers,\n"
-              << "   VCF 4.2 with GT:GQ:DP:AD; same conditions as -pileup; -dedup 1 leaves the duplicates out; no indels, one sample>\n"
+              << "   VCF 4.2 with GT:GQ:DP:AD; same conditions as -pileup; -dedup 1 leaves the duplicates out; indels only with -vcf_indels 1, one sample>\n"
               << "-vcf_minqual <Q: with -vcf, a call needs QUAL >= Q, default=20>\n"
               << "-vcf_mindepth <D: with -vcf, a call needs D bases of sufficient quality, default=4>\n"
+              << "-vcf_indels <0|1: with -vcf and -p2, behind the SNP calls of a genome file the reads once more: the gap rescue (-gap_* apply; it\n"
+              << "   runs once per run, -gapped and -sam_gapped 1 find its records), and the insertions and deletions the rescued mates show,\n"
+              << "   left-aligned, added up and genotyped on the device; their lines (INFO DP;INDEL;SF;SR) are merged into the -vcf file by\n"
+              << "   position; -vcf_minqual and -vcf_mindepth apply; -dedup and -pileup_minmapq do NOT reach the rescued mates; a summary line\n"
+              << "   per genome file goes to standard error, default=0>\n"
+              << "-vcf_minalt <N: with -vcf_indels 1, an indel call needs N rescued mates that show it, default=2>\n"
               << "-sam <file: after the output pass, write EVERY read as a SAM line (header: one @SQ per fragment of every genome file): a\n"
               << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255 (-mapq 1: 0..60), CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
               << "   its mismatch list, computed on one fresh context on -device (ZS:f: the score, with -q 1); an unplaced read with FLAG 4.\n"
@@ -183,6 +189,8 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
         else if (a == "-vcf") { vcffilename = need("-vcf"); vcf_given = true; i += 2; }
         else if (a == "-vcf_minqual") { vcf_minqual = strtoul(need("-vcf_minqual").c_str(), 0, 10); vcf_minqual_given = true; i += 2; }
+        else if (a == "-vcf_indels") { vcf_indels = atoi(need("-vcf_indels").c_str()) != 0; vcf_indels_given = true; i += 2; }
+        else if (a == "-vcf_minalt") { vcf_minalt = strtoul(need("-vcf_minalt").c_str(), 0, 10); vcf_minalt_given = true; i += 2; }
         else if (a == "-vcf_mindepth") { vcf_mindepth = strtoul(need("-vcf_mindepth").c_str(), 0, 10); vcf_mindepth_given = true; i += 2; }
         else if (a == "-sam") { samfilename = need("-sam"); sam_given = true; i += 2; }
         else if (a == "-dedup") { dedup = atoi(need("-dedup").c_str()) != 0; dedup_given = true; i += 2; }
@@ -289,6 +297,12 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (sam_given && vcffilename == samfilename) throw std::runtime_error("-vcf must name a file of its own: it names the same file as -sam.");
         if (vcf_minqual > 0xfffffffful || vcf_mindepth > 0xfffffffful) throw std::runtime_error("-vcf_minqual / -vcf_mindepth take a number below 2^32.");
     }
+    if (vcf_indels) { // indel calls: loud errors before anything runs
+        if (!vcf_given) throw std::runtime_error("-vcf_indels 1 writes its calls into the -vcf file: it needs -vcf.");
+        if (pattern2filename.empty()) throw std::runtime_error("-vcf_indels 1 calls the indels of gap-rescued mates: it is only meaningful with -p2 (paired-end reads).");
+        if (vcf_minalt > 0xfffffffful) throw std::runtime_error("-vcf_minalt takes a number below 2^32.");
+    }
+    if (vcf_minalt_given && !vcf_indels) throw std::runtime_error("-vcf_minalt is only meaningful with -vcf_indels 1.");
     if (vcf_minqual_given && !vcf_given) throw std::runtime_error("-vcf_minqual is only meaningful with -vcf.");
     if (vcf_mindepth_given && !vcf_given) throw std::runtime_error("-vcf_mindepth is only meaningful with -vcf.");
     if (dedup) { // duplicate marking: loud errors before anything runs
@@ -324,12 +338,14 @@ RealOptions::RealOptions(int argc, char *argv[])
             (!inserthistfilename.empty() && gappedfilename == inserthistfilename) || (pileup_given && gappedfilename == pileupfilename) ||
             (pileup_depth_given && gappedfilename == pileupdepthfilename) || (vcf_given && gappedfilename == vcffilename))
             throw std::runtime_error("-gapped must name a file of its own: it names the same file as another output.");
+    }
+    if (gapped_given || vcf_indels) { // the rescue's own parameters: -gapped and -vcf_indels 1 run it
         if (gap_max < 1 || gap_max > REAL_HIP_GAP_MAX) throw std::runtime_error("-gap_max must be in 1.." + std::to_string(REAL_HIP_GAP_MAX) + ".");
         if (gap_flank < 1) throw std::runtime_error("-gap_flank must be at least 1.");
         if (gap_maxcost < 0) gap_maxcost = 4 * (long)totalkmax + 6 + (long)gap_max;
         if (gap_maxcost > 65534 || gap_margin > 65535) throw std::runtime_error("-gap_maxcost takes at most 65534, -gap_margin at most 65535.");
         if (insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
-            throw std::runtime_error("-gapped takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
+            throw std::runtime_error(std::string(gapped_given ? "-gapped" : "-vcf_indels 1") + " takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
     } else if (gap_flags_given) {
         throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped.");
     }

@@ -70,6 +70,9 @@ struct RealOptions {
     unsigned long vcf_minqual = 20;   // -vcf_minqual: a call needs QUAL of at least this
     unsigned long vcf_mindepth = 4;   // -vcf_mindepth: and this many bases of sufficient quality
     bool vcf_given = false, vcf_minqual_given = false, vcf_mindepth_given = false;
+    bool vcf_indels = false, vcf_indels_given = false; // -vcf_indels: with -vcf and -p2, the indels the gap-rescued mates show are called too (real_hip_indel_*)
+    unsigned long vcf_minalt = 2;     // -vcf_minalt: an indel call needs this many rescued mates
+    bool vcf_minalt_given = false;
     bool dedup = false;               // -dedup: mark the copies of a placed read / fragment (real_hip_mark_duplicates*): FLAG 1024 in -sam, left out of -pileup
     long dedup_minq = 15;             // -dedup_minq: a base quality below it does not count in the sum that chooses the copy that stays
     bool dedup_given = false, dedup_minq_given = false;

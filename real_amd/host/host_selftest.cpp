@@ -20,6 +20,9 @@
 //   host_selftest sam_gapped <dir> <fastq:0|1> <qoff> <insert_min> <insert_max> -> <dir>/block.sam: the -sam file of `real -sam_gapped 1` for the
 //       mates <dir>/r1 and r2: the files of the paired `sam` command and gaps.bin (the gap records), cigars.txt (a line per fragment: the
 //       record's CIGAR, * without one), per genome file gmm<fi>.bin goff<fi>.u64 (the gapped lists)
+//   host_selftest vcf_indels <dir>               -> <dir>/out.vcf: the -vcf file of `real -vcf_indels 1` for one genome file, from sym.u8, frag.u64,
+//       names.txt (a fragment name per line), calls.bin (real_hip_call records) and indels.bin (real_hip_indel records), through Vcf.hpp
+//   host_selftest vcf_indel_options <args...>     -> prints the parsed -vcf_indels flag (0|1), -vcf_minalt, -vcf_minqual, -vcf_mindepth
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +36,7 @@
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "Sam.hpp"
+#include "Vcf.hpp"
 #include "final_record.h"
 #include "row_addr.h"
 #include <vector>
@@ -434,6 +438,30 @@ int main(int argc, char **argv)
         if (cmd == "insert_options") { // -insert_hist, -insert_auto
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.inserthistfilename.empty() ? "." : o.inserthistfilename) << " " << o.insert_auto << " " << o.insert_min << " " << o.insert_max << "\n";
+            return 0;
+        }
+        if (cmd == "vcf_indel_options") { // -vcf_indels, -vcf_minalt
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.vcf_indels ? 1 : 0) << " " << o.vcf_minalt << " " << o.vcf_minqual << " " << o.vcf_mindepth << "\n";
+            return 0;
+        }
+        if (cmd == "vcf_indels" && argc == 3) { // the header and the merged lines of one genome file
+            const std::string d = argv[2];
+            const std::vector<uint8_t> sym = slurp<uint8_t>(d + "/sym.u8");
+            const std::vector<uint64_t> frag = slurp<uint64_t>(d + "/frag.u64");
+            const std::vector<real_hip_call> calls = slurp<real_hip_call>(d + "/calls.bin");
+            const std::vector<real_hip_indel> indels = slurp<real_hip_indel>(d + "/indels.bin");
+            std::vector<std::string> names;
+            std::ifstream nf((d + "/names.txt").c_str());
+            for (std::string line; std::getline(nf, line);) names.push_back(line);
+            if (names.size() + 1 != frag.size()) throw std::runtime_error("names.txt and frag.u64 disagree");
+            const SamRefs refs(std::vector<std::vector<std::string>>(1, names), std::vector<std::vector<uint64_t>>(1, frag));
+            FILE *f = fopen((d + "/out.vcf").c_str(), "w");
+            if (!f) throw std::runtime_error("cannot write out.vcf");
+            const std::string head = vcfHeader(refs, true);
+            fwrite(head.data(), 1, head.size(), f);
+            writeVcfMerged(f, refs.names[0], frag.data(), sym.data(), calls.data(), calls.size(), indels.data(), indels.size());
+            fclose(f);
             return 0;
         }
         if (cmd == "pairs_all_options") { // -pairs_all

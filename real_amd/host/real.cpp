@@ -557,9 +557,13 @@ inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || 
 
 // -vcf: the calls of the finished pileup of one genome file (real_hip_call_*) -- the reads once more through
 // addAll(ctx, true), which hands every batch with its final records to real_hip_call_add / _add_pairs -- as VCF lines, and a
-// summary line to standard error
-template <class AddAll>
-void writeCalls(const RealOptions &o, CtxVec &ctx, const std::string &file, const std::vector<std::string> &names, const GenomeText &G, FILE *f, AddAll addAll)
+// summary line to standard error.
+// -vcf_indels 1 (real_hip_indel_*): behind the SNP calls, on the same finished pileup, indelAll(ctx, fi) hands the
+// reads once more to the gap rescue and every batch's gap records to real_hip_indel_add; the indel calls are merged into the
+// file's lines by position, and a second summary line goes to standard error
+template <class AddAll, class IndelAll>
+void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::string &file, const std::vector<std::string> &names, const GenomeText &G, FILE *f,
+                AddAll addAll, IndelAll indelAll)
 {
     real_hip_ctx *h = ctx[0]->h;
     check(h, real_hip_call_begin(h), "real_hip_call_begin");
@@ -570,11 +574,18 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, const std::string &file, cons
     check(h, real_hip_call_finish(h, &cp, &n_calls), "real_hip_call_finish");
     std::vector<real_hip_call> calls(n_calls);
     check(h, real_hip_call_variants(h, calls.data(), calls.size(), &n, 0), "real_hip_call_variants");
-    size_t fr = 0;
-    for (uint64_t k = 0; k < n; ++k) {
-        while (fr + 1 < names.size() && G.frag_start[fr + 1] <= calls[k].pos) ++fr; // (ascending positions)
-        writeVcfLine(f, names[fr], calls[k].pos - G.frag_start[fr] + 1, calls[k]);
+    std::vector<real_hip_indel> indels;
+    if (o.vcf_indels) {
+        check(h, real_hip_indel_begin(h), "real_hip_indel_begin");
+        indelAll(ctx, fi);
+        real_hip_indel_params ip;
+        ip.struct_size = sizeof ip; ip.min_call_qual = (uint32_t)o.vcf_minqual; ip.min_alt = (uint32_t)o.vcf_minalt; ip.min_depth = (uint32_t)o.vcf_mindepth;
+        uint64_t n_events = 0, n_indels = 0, ni = 0;
+        check(h, real_hip_indel_finish(h, &ip, &n_events, &n_indels), "real_hip_indel_finish");
+        indels.resize(n_indels);
+        check(h, real_hip_indel_calls(h, indels.data(), indels.size(), &ni, 0), "real_hip_indel_calls");
     }
+    writeVcfMerged(f, names, G.frag_start.data(), G.sym.data(), calls.data(), n, indels.data(), indels.size());
     real_hip_pileup_stats ps;
     memset(&ps, 0, sizeof ps);
     ps.struct_size = sizeof ps;
@@ -585,12 +596,24 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, const std::string &file, cons
     check(h, real_hip_call_stats_get(h, &st, 1), "real_hip_call_stats_get");
     fprintf(stderr, "calls: file=%s sites=%llu calls=%llu het=%llu hom=%llu site_bases=%llu low_qual=%llu\n", file.c_str(), (unsigned long long)ps.sites,
             (unsigned long long)st.calls, (unsigned long long)st.het, (unsigned long long)st.hom, (unsigned long long)st.site_bases, (unsigned long long)st.low_qual);
+    if (o.vcf_indels) {
+        real_hip_indel_stats is;
+        memset(&is, 0, sizeof is);
+        is.struct_size = sizeof is;
+        check(h, real_hip_indel_stats_get(h, &is, 1), "real_hip_indel_stats_get");
+        fprintf(stderr, "indels: file=%s events=%llu distinct=%llu calls=%llu het=%llu hom=%llu deletions=%llu insertions=%llu shifted=%llu low_qual=%llu\n",
+                file.c_str(), (unsigned long long)is.events, (unsigned long long)is.distinct, (unsigned long long)is.calls, (unsigned long long)is.het,
+                (unsigned long long)is.hom, (unsigned long long)is.deletions, (unsigned long long)is.insertions, (unsigned long long)is.shifted,
+                (unsigned long long)is.low_qual);
+        check(h, real_hip_indel_end(h), "real_hip_indel_end");
+    }
     check(h, real_hip_call_end(h), "real_hip_call_end");
 }
 
 // addAll(ctx, calls): every batch of reads with its final records to the pileup (calls = false) or to the calls on top of it
-template <class AddAll>
-void pileupPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, AddAll addAll)
+// indelAll(ctx, fi): with -vcf_indels 1, every batch of mates through the gap rescue to real_hip_indel_add (writeCalls)
+template <class AddAll, class IndelAll>
+void pileupPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, AddAll addAll, IndelAll indelAll)
 {
     if (!o.pileup_given && !o.pileup_depth_given && !o.vcf_given) return;
     std::unique_ptr<OutFile> sites_out(o.pileup_given ? new OutFile(o.pileupfilename, false, "-pileup") : nullptr);
@@ -598,7 +621,7 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
     std::unique_ptr<OutFile> vcf_out(o.vcf_given ? new OutFile(o.vcffilename, false, "-vcf") : nullptr);
     const SamRefs refs(RS.names, RS.starts);
     if (vcf_out) {
-        const std::string head = vcfHeader(refs);
+        const std::string head = vcfHeader(refs, o.vcf_indels);
         if (fwrite(head.data(), 1, head.size(), vcf_out->file()) != head.size()) throw std::runtime_error("write to the -vcf file failed");
     }
     real_hip_pileup_params pp;
@@ -619,7 +642,7 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
                 files[fi].c_str(), (unsigned long long)st.placed, (unsigned long long)st.bases, (unsigned long long)st.covered,
                 st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
                 (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
-        if (vcf_out) writeCalls(o, ctx, files[fi], refs.names[fi], G, vcf_out->file(), addAll);
+        if (vcf_out) writeCalls(o, ctx, fi, files[fi], refs.names[fi], G, vcf_out->file(), addAll, indelAll);
         check(h, real_hip_pileup_end(h), "real_hip_pileup_end");
     });
     for (OutFile *f : {sites_out.get(), depth_out.get(), vcf_out.get()}) {
@@ -852,7 +875,7 @@ int matchUnique(const RealOptions &o)
             }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
-    });
+    }, [](CtxVec &, unsigned) {}); // (-vcf_indels needs -p2: RealOptions refuses it here)
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         const uint64_t seen = streamReads(o, sc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
@@ -1076,7 +1099,7 @@ int matchPairs(const RealOptions &o)
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
-    const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped takes its anchors from them)
+    const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given || o.vcf_indels; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped and -vcf_indels 1 take the rescue's anchors from them)
     std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
     std::vector<real_hip_read_sum> sums1, sums2;     // -dedup: the mates' summaries, kept for the run beside pairs
     std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
@@ -1252,6 +1275,11 @@ int matchPairs(const RealOptions &o)
     }
     if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
     std::vector<real_hip_pair> kept; // -dedup / -pileup_minmapq: a batch's records without what they leave out
+    // the gap rescue runs once per run: with -vcf_indels 1 in the pileup pass of each genome file (the text is resident: what the
+    // rescue needs), else with -sam_gapped 1 in the -sam pass, else in gapPass; the later passes find the records made
+    GapRun gap_run;
+    const real_hip_gap_params gp = gapParams(o);
+    if (o.vcf_indels || o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
@@ -1265,13 +1293,29 @@ int matchPairs(const RealOptions &o)
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+    }, [&](CtxVec &pc, unsigned) {
+        real_hip_ctx *h = pc[0]->h;
+        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
+        uint64_t seen = 0;
+        for (;;) {
+            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
+            if (!n) break;
+            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
+            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+            const double tm = now_s();
+            check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0, gap_run.gaps.data() + seen),
+                  "real_hip_gap_rescue");
+            check(h, real_hip_indel_add(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_indel_add");
+            T.match += now_s() - tm;
+            seen += n;
+        }
+        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        gap_run.addStats(h);
     });
-    // -sam_gapped 1: the pass of a genome file rescues the fragments whose anchor lies in it (the text is resident: what the
-    // rescue needs), lists the rescued mates in gapped coordinates and writes their lines; gapPass then finds the records made
-    GapRun gap_run;
+    // -sam_gapped 1: the pass of a genome file rescues the fragments whose anchor lies in it (unless -vcf_indels 1 has done so), lists
+    // the rescued mates in gapped coordinates and writes their lines; gapPass then finds the records made
     GappedLists GL;
-    const real_hip_gap_params gp = gapParams(o);
-    if (o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
+    const bool sam_rescues = o.sam_gapped && !o.vcf_indels;
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         const ReadSource v1 = m1.withQuality(o.fastq, qoff1), v2 = m2.withQuality(o.fastq2, qoff2);
@@ -1285,8 +1329,9 @@ int matchPairs(const RealOptions &o)
             L.fill(sc[0]->h, "real_hip_mismatches_pairs", 2 * n, real_hip_mismatches_pairs, &rb1, &rb2, (const real_hip_pair *)pairs.data() + seen,
                    (const real_hip_single *)singles1.data() + seen, (const real_hip_single *)singles2.data() + seen);
             if (o.sam_gapped) {
-                check(sc[0]->h, real_hip_gap_rescue(sc[0]->h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0,
-                                                    gap_run.gaps.data() + seen), "real_hip_gap_rescue");
+                if (sam_rescues)
+                    check(sc[0]->h, real_hip_gap_rescue(sc[0]->h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0,
+                                                        gap_run.gaps.data() + seen), "real_hip_gap_rescue");
                 GL.fill(sc[0]->h, n, &rb1, &rb2, gap_run.gaps.data() + seen);
             }
             T.match += now_s() - tm;
@@ -1295,7 +1340,7 @@ int matchPairs(const RealOptions &o)
                 SamPlace at[2] = {samPlace(pairs[seen + i], singles1[seen + i], 0), samPlace(pairs[seen + i], singles2[seen + i], 1)};
                 at[0].duplicate = at[1].duplicate = o.dedup && dup[seen + i]; // (a duplicate fragment is Unique: both mates have lines)
                 if (o.mapq) { at[0].mapq = mapq[2 * (seen + i)]; at[1].mapq = mapq[2 * (seen + i) + 1]; }
-                if (o.sam_gapped && REAL_HIP_GAP_STATE(gap_run.gaps[seen + i].tag) == REAL_HIP_PAIR_UNIQUE) {
+                if (o.sam_gapped && REAL_HIP_GAP_STATE(gap_run.gaps[seen + i].tag) == REAL_HIP_PAIR_UNIQUE && gap_run.gaps[seen + i].fileid <= fi) { // (a later file's record: -vcf_indels 1 ran the rescue of every file first)
                     const real_hip_gap_place &g = gap_run.gaps[seen + i];
                     char cigar[48] = "*";
                     real_hip_gap_cigar(&g, (uint32_t)r[REAL_HIP_GAP_TARGET(g.tag)].patl, cigar, sizeof cigar);
@@ -1306,7 +1351,7 @@ int matchPairs(const RealOptions &o)
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-        if (o.sam_gapped) gap_run.addStats(sc[0]->h);
+        if (sam_rescues) gap_run.addStats(sc[0]->h);
     });
     if (o.sam_gapped)
         fprintf(stderr, "sam gapped: mates=%llu deleted=%llu inserted=%llu disagree=%llu\n", (unsigned long long)GL.mates, (unsigned long long)GL.deleted,

@@ -57,6 +57,8 @@ ABI_SYMBOLS = [
     "real_hip_match_pairs_mapq", "real_hip_mapq", "real_hip_mapq_pairs", "real_hip_mapq_stats_get",
     "real_hip_gap_rescue", "real_hip_gap_cigar", "real_hip_gap_stats_get",
     "real_hip_mismatches_gapped", "real_hip_gapped_list_stats_get",
+    "real_hip_indel_begin", "real_hip_indel_add", "real_hip_indel_finish", "real_hip_indel_events", "real_hip_indel_calls",
+    "real_hip_indel_end", "real_hip_indel_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -231,6 +233,27 @@ GAPPED_LIST_STATS_FIELDS = ("fragments", "placed", "other_file", "invalid", "ali
                             "disagree", "launches", "kernel_ms")
 RealHipGappedListStats = _stats_struct("RealHipGappedListStats", GAPPED_LIST_STATS_FIELDS)
 
+# indel calls (include/real_hip.h, "indel calls"): the rescued mates' insertions and deletions, grouped and genotyped
+INDEL_SHIFT_MAX, INDEL_REF_Q, INDEL_PRIOR_HET, INDEL_PRIOR_HOM = 256, 30, 40, 43
+
+
+class RealHipIndelParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_call_qual", C.c_uint32), ("min_alt", C.c_uint32), ("min_depth", C.c_uint32)]
+
+
+class RealHipIndel(C.Structure):
+    """real_hip_indel: one distinct event of the event list or the call list (INDEL_DTYPE is the same record as a numpy dtype);
+    pos = the anchor, seq = the inserted bases 2 bits each, the first lowest"""
+    _fields_ = [("pos", C.c_uint32), ("ref_n", C.c_uint32), ("alt_n", C.c_uint32), ("alt_fwd", C.c_uint32), ("qsum", C.c_uint32),
+                ("qual", C.c_uint32), ("seq", C.c_uint32), ("gap", C.c_int8), ("gt", C.c_uint8), ("gq", C.c_uint8), ("ref", C.c_uint8)]
+
+
+INDEL_DTYPE = np.dtype(RealHipIndel)
+assert INDEL_DTYPE.itemsize == 32
+INDEL_STATS_FIELDS = ("fragments", "placed", "other_file", "invalid", "ungapped", "events", "on_n", "low_qual", "shifted", "shift_capped",
+                      "distinct", "calls", "het", "hom", "deletions", "insertions", "launches", "kernel_ms")
+RealHipIndelStats = _stats_struct("RealHipIndelStats", INDEL_STATS_FIELDS)
+
 
 class RealHipPairHit(C.Structure):
     """real_hip_pair_hit: one concordant pair (PAIR_HIT_DTYPE is the same record as a numpy dtype)"""
@@ -378,6 +401,13 @@ def load():
     L.real_hip_gap_stats_get.argtypes = [vp, C.POINTER(RealHipGapStats), ci]
     L.real_hip_mismatches_gapped.argtypes = [vp, batch, batch, vp, vp, u64, pu64, vp]
     L.real_hip_gapped_list_stats_get.argtypes = [vp, C.POINTER(RealHipGappedListStats), ci]
+    L.real_hip_indel_begin.argtypes = [vp]
+    L.real_hip_indel_add.argtypes = [vp, batch, batch, vp]
+    L.real_hip_indel_finish.argtypes = [vp, C.POINTER(RealHipIndelParams), pu64, pu64]
+    L.real_hip_indel_events.argtypes = [vp, vp, u64, pu64, ci]
+    L.real_hip_indel_calls.argtypes = [vp, vp, u64, pu64, ci]
+    L.real_hip_indel_end.argtypes = [vp]
+    L.real_hip_indel_stats_get.argtypes = [vp, C.POINTER(RealHipIndelStats), ci]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
     L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
     L.real_hip_timing_enable.argtypes = [vp, ci]

@@ -1016,6 +1016,43 @@ class PairMatcher(AllMatcher):
     def gapped_list_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipGappedListStats, self._L.real_hip_gapped_list_stats_get, reset)
 
+    # -- indel calls: the rescued mates' insertions and deletions over the finished pileup (include/real_hip.h, "indel calls") --
+    def indel_begin(self):
+        """real_hip_indel_begin: needs a finished pileup of the resident text; a second begin starts again"""
+        self._check(self._L.real_hip_indel_begin(self._h))
+
+    def indel_add(self, mate1, mate2, gaps):
+        """real_hip_indel_add: the events of the Unique gapped records among `gaps` (what gap_rescue returned for these mates).
+        Mates and records as for mismatches_gapped: all host arrays, all device tensors, or device reads with numpy records"""
+        host = isinstance(gaps, np.ndarray)
+        if host:
+            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
+        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
+        self.sync_inputs(gaps)
+        self._check(self._L.real_hip_indel_add(self._h, C.byref(b1), C.byref(b2), _ptr(gaps)))
+
+    def indel_finish(self, min_call_qual: int = 20, min_alt: int = 2, min_depth: int = 4):
+        """real_hip_indel_finish: the events grouped and genotyped -> (distinct events, calls).  May be called again with other
+        thresholds"""
+        p = _lib.sized(_lib.RealHipIndelParams, min_call_qual=int(min_call_qual), min_alt=int(min_alt), min_depth=int(min_depth))
+        n_events, n_calls = C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.real_hip_indel_finish(self._h, C.byref(p), C.byref(n_events), C.byref(n_calls)))
+        return int(n_events.value), int(n_calls.value)
+
+    def indel_events(self, cap: int = 1024) -> np.ndarray:
+        """the distinct events as lib.INDEL_DTYPE, ascending (pos, gap, seq); the buffer grows once to the size the library reports"""
+        return self._host_list(self._L.real_hip_indel_events, _lib.INDEL_DTYPE, cap)
+
+    def indel_calls(self, cap: int = 1024) -> np.ndarray:
+        """the calls among them as lib.INDEL_DTYPE, in the events' order; the buffer grows once"""
+        return self._host_list(self._L.real_hip_indel_calls, _lib.INDEL_DTYPE, cap)
+
+    def indel_end(self):
+        self._check(self._L.real_hip_indel_end(self._h))
+
+    def indel_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipIndelStats, self._L.real_hip_indel_stats_get, reset)
+
     def single_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
 
