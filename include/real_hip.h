@@ -912,6 +912,87 @@ typedef struct real_hip_gap_stats {
 } real_hip_gap_stats;
 int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset);
 
+/* ---- anchored gap placement: place a SINGLE read that differs from the text by one insertion or deletion (off unless these
+ * entry points are called).  Without a mate nothing says where to look; the matcher itself does: an alignment with one gap is
+ * a prefix on one diagonal plus a suffix on a neighbouring one, so whenever 2 A + max_gap <= L either the first A or the last A
+ * bases of the read lie wholly on one diagonal, and matchAll finds that sub-read ungapped.  Those hits are the ANCHORS; around
+ * each the search is the gap rescue's, in a window of 2 * max_gap + 1 starts.  The semantics are this project's own (DESIGN.md
+ * 7k): all integers, a function of reads, records, hit lists and text alone -- nothing depends on lanes, waves, the order of a
+ * hit list or the split of a batch into calls.  G = max_gap, m = min_flank; the costs, max_cost and margin are those of
+ * real_hip_gap_params with its parameter checks; A = anchor_len in 1..REAL_HIP_MAX_PATL and max_anchors in
+ * 1..REAL_HIP_GAP_ANCHORS_MAX are the fields of struct real_hip_gap_anchor_params; its reserved words are 0.
+ * SUB-READ BATCH S(b, A).  2 n reads of uniform length A: sub-read 2i holds bases and qualities [0, A) of read i (the prefix,
+ * e = 0), sub-read 2i + 1 holds [L_i - A, L_i) (the suffix, e = 1).  The anchor hits of read i are the real_hip_hit entries of
+ * these two sub-reads in one hit list with 2 n + 1 offsets; real_hip_match_gapped takes exactly what real_hip_match_all returns
+ * for S(b, A) under the context's current match parameters.
+ * WHICH READS.  Read i is ELIGIBLE iff info == NULL or the state of info[i] is NoMatch (the state of a fresh record); info holds
+ * the FINAL records of the run.  An eligible read is SKIPPED and counted if it holds a symbol > 3, or L > REAL_HIP_MAX_PATL, or
+ * L < 2 m + G + 1, or L < A.  An eligible read that is not skipped is CROWDED and counted if its two sub-reads have more than
+ * max_anchors hits together, UNANCHORED and counted if they have none; every other one is SEARCHED.  Skipped, crowded and
+ * unanchored reads give NoMatch.
+ * ANCHOR DIAGONAL.  A hit of sub-read 2i + e at q, strand v (inverted), fragment f = [fs, fe) orients the read as v says: R is
+ * the read for v = 0, its reverse complement for v = 1.  It names the start c of R's ungapped diagonal, in 64 bits: c = q if
+ * e == v (the sub-read is the head of R), c = q - (L - A) otherwise (it is the tail of R; c may be negative).  A hit with
+ * f >= n_frag, q < fs or q + A > fe is counted as invalid and ignored; no byte outside the arrays is read for it.  `anchors`
+ * counts the valid hits of the searched reads, `invalid_anchors` their other hits.
+ * EXAMINED STARTS.  For each valid anchor the starts (v, p) with p in [max(c - G, fs), min(c + G, fe - 1)].  `positions` is the
+ * sum of these window sizes over the valid anchors: overlapping windows count twice.
+ * CANDIDATES.  A candidate is (v, p, g, j) with (v, p) examined; the rest is the CANDIDATES paragraph of the gap rescue word for
+ * word: the geometry of g = 0, g > 0 and g < 0, k <= 15, cost <= max_cost, no N bit in the span, the span inside fragment f.
+ * The candidates of a read are a SET: an alignment two anchors reach counts once.
+ * RECORD.  best is the smallest (cost, |g|, p, v, g, j); second is the smallest cost among the candidates with v != best.v or
+ * |p - best.pos| > G.  State and fields as in the gap rescue; tag bit 0 (target) is 0, bit 4 is v, bits 5-6 the state; fileid
+ * is the resident file.  placed / unique / gapped count these records, before any fold.
+ * FOLD (fresh == 0).  A searched read with a candidate gets out[i] = M(out[i], r); every other record is untouched.  NoMatch is
+ * M's neutral element.  Otherwise the winner w is the smaller by (cost, |g|, fileid, pos, v, g, j) and l the other; they are the
+ * SAME LOCUS iff fileid and v are equal and |w.pos - l.pos| <= G; the result is w with second = min(w.second, l.second, same
+ * locus ? NONE : l.cost) and the state recomputed with the call's margin.  Across genome files M is exact, commutative and
+ * associative (loci of different files are never the same).  Across index blocks of ONE file it is CONSERVATIVE: a rival of the
+ * loser's call that lies at the winner's locus still counts in l.second, so a record may turn NonUnique; it never turns
+ * wrongly Unique.  fresh != 0: every record starts NoMatch and all are written.
+ * COVERAGE (a remark).  If 2 A + G <= L, every candidate of cost <= max_cost whose wholly aligned sub-read is found by the
+ * matcher is examined.  Shorter reads are searched with partial coverage.
+ * real_hip_gap_anchor_hits: the stage on hit lists the caller holds.  Where the arrays live follows batch->on_device as for
+ * real_hip_gap_rescue: info, hits, hit_offsets and out are host memory for 0 and 2, device memory for 1 (info and hit_offsets
+ * 8-byte, hits and out 16-byte aligned).  Needs the text, not the index (REAL_HIP_E_STATE without it).  hit_offsets start at 0;
+ * host offsets must not run backwards, device offsets are clamped.  n_reads == 0 is valid.
+ * real_hip_match_gapped: the composite.  Needs the text and a resident index block (REAL_HIP_E_STATE otherwise).  On the device
+ * it selects the eligible, not skipped reads, writes their sub-reads, runs the library's matchAll on them with hits and offsets
+ * left on the device, then the stage: its records equal real_hip_gap_anchor_hits on real_hip_match_all(S(b, A)).
+ * REAL_HIP_E_INVALID with a message, nothing launched: NULL params, batch, hit_offsets or out with n_reads > 0, NULL hits with
+ * hits in the lists, a wrong struct_size, a parameter out of range, misaligned device arrays, more than 2^32 reads.        */
+#define REAL_HIP_GAP_ANCHORS_MAX 64u
+typedef struct real_hip_gap_anchor_params {
+    uint32_t struct_size;    /* = sizeof(real_hip_gap_anchor_params)                                   */
+    uint32_t anchor_len;     /* A: bases of the prefix and of the suffix sub-read, 1..REAL_HIP_MAX_PATL */
+    uint32_t max_anchors;    /* a read with more hits of its two sub-reads is crowded, 1..REAL_HIP_GAP_ANCHORS_MAX */
+    uint32_t reserved[2];    /* 0                                                                      */
+} real_hip_gap_anchor_params;
+int real_hip_gap_anchor_hits(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch *batch,
+                             const uint64_t *info /* nullable */, const real_hip_hit *hits, const uint64_t *hit_offsets /* 2 n + 1 */, int fresh,
+                             real_hip_gap_place *out);
+int real_hip_match_gapped(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch *batch,
+                          const uint64_t *info /* nullable */, int fresh, real_hip_gap_place *out);
+/* work of the stage, accumulated since the last reset.  Every counter but the last two is a function of the inputs; launches
+ * and kernel_ms cover the stage's own kernels, not the matcher's.                                                          */
+typedef struct real_hip_gap_anchor_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_gap_anchor_stats), 0                          */
+    uint64_t reads;          /* reads handed in                                                        */
+    uint64_t eligible;       /* the skipped ones included                                              */
+    uint64_t skipped;
+    uint64_t crowded;
+    uint64_t unanchored;
+    uint64_t anchors;        /* valid hits of the searched reads                                       */
+    uint64_t invalid_anchors;
+    uint64_t positions;      /* sum of the numbers of examined starts                                  */
+    uint64_t placed;         /* records of the calls that are not NoMatch                              */
+    uint64_t unique;
+    uint64_t gapped;         /* placed with g != 0                                                     */
+    uint64_t launches;       /* kernels launched                                                       */
+    double   kernel_ms;      /* HIP events on the ctx's stream around the kernels                      */
+} real_hip_gap_anchor_stats;
+int real_hip_gap_anchor_stats_get(real_hip_ctx *ctx, real_hip_gap_anchor_stats *out, int reset);
+
 /* ---- gapped mismatch lists: where a gap-rescued mate differs from the resident text, and which text bases its deletion skips
  * -- what CIGAR, NM and MD of such a mate's SAM line are written from.  ORIENTED read and the resident text (n
  * bases, file id f) are those of the block "mismatch lists".

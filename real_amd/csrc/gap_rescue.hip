@@ -9,7 +9,8 @@
 // wave packs the oriented target into words of 32 bases in LDS and stages the text words of the window there.  Lane t of a
 // tile owns start p = first + 64 tile + t.  First every diagonal q of the tile and of its max_gap neighbours on either side
 // gets three numbers from one pass over its words (funnel-shifted text XOR read, popcount): the mismatches of the first
-// min_flank bases, of the last min_flank bases and of the whole read, into LDS.  A candidate (p, g, j) is the prefix of
+// min_flank bases, of the last min_flank bases and of the whole read, into LDS (gap_core.h, shared with gap_anchor.hip).
+// A candidate (p, g, j) is the prefix of
 // diagonal p plus the suffix of diagonal p + g, and whatever j is, the first min_flank bases of p and the last min_flank of
 // p + g are part of it: a pair of diagonals whose two numbers already exceed what max_cost allows is dropped -- exact, and on
 // random text about one pair in a thousand passes.  A pair that passes walks the split points once, one base a step, adding
@@ -20,7 +21,7 @@
 // the best one, from LDS, and a second butterfly.  Lane 0 writes the record with one 16-byte store.
 //
 // Nothing depends on lanes, tiles or the order of the list.  No scratch memory; plain C++ and vector stores.
-#include "read_words.h"
+#include "gap_core.h"   // read_words.h; gap_mm, gap_diagonal, gap_best_split, the record packing
 #include "pair_state.h" // pair_hand_over, stage_common.h
 #include "gap_stage.h"
 
@@ -76,19 +77,6 @@ struct GapArgs {
     uint32_t *err_flags;           // bit 0: a window wider than the LDS regions
     uint32_t fresh, min_insert, max_insert, max_gap, min_flank, cost_mismatch, cost_open, cost_extend, max_cost, margin;
 };
-static_assert(sizeof(real_hip_gap_place) == 16 && offsetof(real_hip_gap_place, frag) == 4 && offsetof(real_hip_gap_place, fileid) == 6 &&
-                  offsetof(real_hip_gap_place, tag) == 7 && offsetof(real_hip_gap_place, split) == 8 && offsetof(real_hip_gap_place, gap) == 10 &&
-                  offsetof(real_hip_gap_place, k) == 11 && offsetof(real_hip_gap_place, cost) == 12 && offsetof(real_hip_gap_place, second) == 14,
-              "the kernels write a gap record as one uint4");
-
-static __device__ __forceinline__ uint4 gap_empty_record() { return make_uint4(0u, 0u, 0u, (uint32_t)REAL_HIP_GAP_NONE << 16); }
-// length and first base of read i of a batch
-static __device__ __forceinline__ uint64_t gap_read_span(const DevBatch &b, uint64_t i, uint64_t *o0)
-{
-    *o0 = b.off ? b.off[i] : i * (uint64_t)b.upatl;
-    return b.off ? (b.off[i + 1] >= *o0 ? b.off[i + 1] - *o0 : 0) : (uint64_t)b.upatl;
-}
-
 // what the two single records say of a fragment whose pair record is NoMatch: true iff exactly one is Unique and the other
 // NoMatch; *tm: the target mate (0 = mate 1), *ra: the anchor's record
 static __device__ __forceinline__ bool gap_roles(const uint4 r1, const uint4 r2, uint32_t *tm, uint4 *ra)
@@ -136,35 +124,6 @@ __global__ void __launch_bounds__(256) gap_select_kernel(const GapArgs A)
     if ((threadIdx.x & 63u) == 0 && om) atomicAdd(A.stats + (size_t)(blockIdx.x % RH_PAIR_STRIPES) * 16 + 2, (unsigned long long)__popcll(om));
 }
 
-// does base i of the oriented read R differ from the staged text at base trel + i
-static __device__ __forceinline__ uint32_t gap_mm(const uint64_t *R, const uint64_t *sT, uint32_t trel, uint32_t i)
-{
-    const uint32_t u = trel + i;
-    return (((R[i >> 5] >> (62u - 2u * (i & 31u))) ^ (sT[u >> 5] >> (62u - 2u * (u & 31u)))) & 3ull) ? 1u : 0u;
-}
-// the diagonal at staged base trel: total:16 | head:8 | tail:8 = the mismatches of the whole read, of its first m and of its
-// last m bases (m < 256: a read of at most REAL_HIP_MAX_PATL bases holds two flanks and a gap)
-static __device__ __forceinline__ uint32_t gap_diagonal(const uint64_t *R, const uint64_t *sT, uint32_t trel, uint32_t L, uint32_t m)
-{
-    const uint32_t nw = (L + 31u) >> 5, wi = trel >> 5, sh = 2u * (trel & 31u);
-    uint32_t total = 0, head = 0, tail = 0;
-    uint64_t t0 = sT[wi];
-    for (uint32_t j = 0; j < nw; ++j) {
-        const uint64_t t1 = sT[wi + j + 1];
-        const uint64_t al = sh ? ((t0 << sh) | (t1 >> (64u - sh))) : t0;
-        const uint64_t xw = al ^ R[j];
-        uint64_t d = ((xw >> 1) | xw) & M55;
-        const uint32_t nb = min(32u, L - 32u * j);                // bases of this word
-        if (nb < 32u) d &= ~0ull << (64u - 2u * nb);
-        const uint32_t nh = m > 32u * j ? min(32u, m - 32u * j) : 0u;                // of them in the first m of the read
-        const uint32_t lt = L - m > 32u * j ? min(32u, L - m - 32u * j) : 0u;        // of them in front of the last m
-        total += __popcll(d);
-        if (nh) head += __popcll(d & (~0ull << (64u - 2u * nh)));
-        if (lt < 32u) tail += __popcll(d & (~0ull >> (2u * lt)));
-        t0 = t1;
-    }
-    return (total << 16) | (head << 8) | tail;
-}
 // the key of a candidate: cost:16 | |g|:5 | p - first:13 | deletion:1 | j:9 | k:4 -- ascending keys are ascending (cost, |g|, p, g, j)
 static __device__ __forceinline__ uint64_t gap_key(uint32_t cost, uint32_t ag, uint32_t prel, bool deletion, uint32_t j, uint32_t k)
 {
@@ -256,18 +215,8 @@ __global__ void __launch_bounds__(256) gap_search_kernel(const GapArgs A)
                         if ((g ? head + (dq & 0xffu) : dp >> 16) > kmax) continue; // these bases are aligned whatever j is
                         if (A.t.has_wild && !wild_free(A.t.wild, (uint32_t)p, (uint32_t)(Ls + g))) continue;
                         uint32_t k = dp >> 16, bj = 0;
-                        if (g) { // the split points, left to right: c = mismatches of R[0..j) on p + those of R[j+d..L) on p + g
-                            const uint32_t d = g < 0 ? ag : 0u, qrel = (uint32_t)((int64_t)prel + g), jhi = L - m - d;
-                            uint32_t c = dq >> 16;
-                            for (uint32_t x = 0; x < m + d; ++x) c -= gap_mm(R, sT, qrel, x);
-                            c += head;
-                            k = c; bj = m;
-                            for (uint32_t j = m; j < jhi; ++j) {
-                                c += gap_mm(R, sT, prel, j);
-                                c -= gap_mm(R, sT, qrel, j + d);
-                                if (c < k) { k = c; bj = j + 1; }
-                            }
-                        }
+                        if (g) // the split points, left to right (gap_core.h)
+                            k = gap_best_split(R, sT, prel, (uint32_t)((int64_t)prel + g), L, m, g < 0 ? ag : 0u, head, dq >> 16, &bj);
                         if (k > kmax) continue;
                         const uint32_t cost = A.cost_mismatch * k + gc;
                         const uint64_t key = gap_key(cost, ag, (uint32_t)(p - P0), g > 0, bj, k);
@@ -293,8 +242,7 @@ __global__ void __launch_bounds__(256) gap_search_kernel(const GapArgs A)
             const bool rival = second != REAL_HIP_GAP_NONE && second <= cost + A.margin;
             const uint32_t state = rival ? REAL_HIP_PAIR_NONUNIQUE : REAL_HIP_PAIR_UNIQUE;
             const uint32_t tag = tm | ((inva ? 0u : 1u) << 4) | (state << 5);
-            r = make_uint4((uint32_t)(P0 + (int64_t)((best >> 14) & 0x1fffu)), frag | (A.t.fileid << 16) | (tag << 24),
-                           bj | (((uint32_t)g & 0xffu) << 16) | (k << 24), cost | (second << 16));
+            r = gap_pack_record((uint32_t)(P0 + (int64_t)((best >> 14) & 0x1fffu)), frag, A.t.fileid, tag, bj, g, k, cost, second);
             cF += 1; cU += rival ? 0 : 1; cG += ag ? 1 : 0;
         }
         if (lane == 0) A.out[i] = r;

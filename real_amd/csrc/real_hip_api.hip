@@ -1225,19 +1225,20 @@ extern "C" int real_hip_pileup_begin(real_hip_ctx *ctx, const real_hip_pileup_pa
 // real_hip_mismatches* share.  bv[]: the views of the reads (mates == 1, with info) or of the two mates (mates == 2, with
 // pairs; mates_agree has checked them).  At most 2^32 reads, the null and alignment checks on the records, then the reads as a match stages
 // them into ctx->stage[m], then the records into `rec` where they are host memory, then the device views.  keep_qual: the
-// qualities are handed on whatever -q says; otherwise not at all.  n_reads == 0 is valid: nothing is copied.
+// qualities are handed on whatever -q says; otherwise not at all.  n_reads == 0 is valid: nothing is copied.  need_rec false:
+// the stage takes null records (anchored gap placement: every read is eligible).
 struct PlacedReads {
     DevBatch b[2];
     const uint64_t *info;
     const real_hip_pair *pairs;
 };
 static int stage_placements(real_hip_ctx *ctx, const char *stage, const real_hip_batch bv[], int mates, const uint64_t *info, const real_hip_pair *pairs,
-                            DevBuf &rec, bool keep_qual, PlacedReads &p)
+                            DevBuf &rec, bool keep_qual, PlacedReads &p, bool need_rec = true)
 {
     const uint64_t n = bv[0].n_reads;
     const bool dev = bv[0].on_device == 1;
     if (n > 0xffffffffull) return stage_invalid(ctx, stage, "more than 2^32 reads in one call");
-    if (n && !(mates == 2 ? (const void *)pairs : (const void *)info)) return stage_invalid(ctx, stage, mates == 2 ? "null pairs" : "null info");
+    if (n && need_rec && !(mates == 2 ? (const void *)pairs : (const void *)info)) return stage_invalid(ctx, stage, mates == 2 ? "null pairs" : "null info");
     if (dev && ((uintptr_t)pairs & 7u)) return stage_invalid(ctx, stage, "the pair records must be 8-byte aligned");
     int rc;
     Staged st[2];
@@ -1245,7 +1246,7 @@ static int stage_placements(real_hip_ctx *ctx, const char *stage, const real_hip
         if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rc;
     const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
     p.info = info; p.pairs = pairs;
-    if (n && (rc = mates == 2 ? io.in(rec, pairs, n, p.pairs) : io.in(rec, info, n, p.info))) return rc;
+    if (n && (pairs || info) && (rc = mates == 2 ? io.in(rec, pairs, n, p.pairs) : io.in(rec, info, n, p.info))) return rc;
     for (int m = 0; m < mates; ++m) {
         p.b[m] = dev_batch(ctx, st[m], n);
         p.b[m].qual = keep_qual ? st[m].qual : nullptr;
@@ -1472,18 +1473,24 @@ extern "C" int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_
 // ---- gap rescue (gap_rescue.hip): the reads and the pair records are staged as the mismatch lists stage them, the singles and
 // the in/out gap records beside them
 static const char *const kGap = "gap rescue";
+// what real_hip_gap_params may hold, for both stages that take it; `stage` is the prefix of the messages
+static int gap_costs_check(real_hip_ctx *ctx, const char *stage, const real_hip_gap_params *gp)
+{
+    if (!gp || gp->struct_size != sizeof(real_hip_gap_params)) return stage_invalid(ctx, stage, "params struct_size");
+    if (gp->max_gap < 1 || gp->max_gap > REAL_HIP_GAP_MAX) return stage_invalid(ctx, stage, "max_gap must be in 1 .. REAL_HIP_GAP_MAX");
+    if (gp->min_flank < 1) return stage_invalid(ctx, stage, "min_flank must be at least 1");
+    if (gp->cost_mismatch > 65535u || gp->cost_open > 65535u || gp->cost_extend > 65535u) return stage_invalid(ctx, stage, "a cost beyond 65535");
+    if (gp->max_cost > 65534u) return stage_invalid(ctx, stage, "max_cost beyond 65534");
+    if (gp->margin > 65535u) return stage_invalid(ctx, stage, "margin beyond 65535");
+    if (gp->reserved[0] || gp->reserved[1]) return stage_invalid(ctx, stage, "reserved words must be 0");
+    return REAL_HIP_OK;
+}
 static int gap_params_check(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_gap_params *gp)
 {
     if (!gp || gp->struct_size != sizeof(real_hip_gap_params)) return stage_invalid(ctx, kGap, "params struct_size");
     if (pp->max_insert > REAL_HIP_MATE_SEARCH_MAX_INSERT)
         return rh_fail(ctx, REAL_HIP_E_UNSUPPORTED, "gap rescue: max_insert beyond REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
-    if (gp->max_gap < 1 || gp->max_gap > REAL_HIP_GAP_MAX) return stage_invalid(ctx, kGap, "max_gap must be in 1 .. REAL_HIP_GAP_MAX");
-    if (gp->min_flank < 1) return stage_invalid(ctx, kGap, "min_flank must be at least 1");
-    if (gp->cost_mismatch > 65535u || gp->cost_open > 65535u || gp->cost_extend > 65535u) return stage_invalid(ctx, kGap, "a cost beyond 65535");
-    if (gp->max_cost > 65534u) return stage_invalid(ctx, kGap, "max_cost beyond 65534");
-    if (gp->margin > 65535u) return stage_invalid(ctx, kGap, "margin beyond 65535");
-    if (gp->reserved[0] || gp->reserved[1]) return stage_invalid(ctx, kGap, "reserved words must be 0");
-    return REAL_HIP_OK;
+    return gap_costs_check(ctx, kGap, gp);
 }
 
 extern "C" int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params *pp, const real_hip_gap_params *gp, const real_hip_batch *b1,
@@ -1517,6 +1524,111 @@ extern "C" int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params
 extern "C" int real_hip_gap_stats_get(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset)
 {
     return stats_get(ctx, out, reset, "gap stats struct_size", rh_gap_stats);
+}
+
+// ---- anchored gap placement (gap_anchor.hip): the reads and the info words are staged as the mismatch lists stage them
+// (qualities kept: the sub-reads carry them to the matcher), the in/out gap records beside them.  Every check comes before
+// the first launch
+static const char *const kAnchor = "anchored gap placement";
+static int anchor_checks(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch *batch,
+                         const uint64_t *info, const real_hip_gap_place *out, bool need_index, real_hip_batch &bv)
+{
+    int rc = gap_costs_check(ctx, kAnchor, gp);
+    if (rc) return rc;
+    if (!ap || ap->struct_size != sizeof(real_hip_gap_anchor_params)) return stage_invalid(ctx, kAnchor, "anchor params struct_size");
+    if (ap->anchor_len < 1 || ap->anchor_len > REAL_HIP_MAX_PATL) return stage_invalid(ctx, kAnchor, "anchor_len must be in 1 .. REAL_HIP_MAX_PATL");
+    if (ap->max_anchors < 1 || ap->max_anchors > REAL_HIP_GAP_ANCHORS_MAX) return stage_invalid(ctx, kAnchor, "max_anchors must be in 1 .. REAL_HIP_GAP_ANCHORS_MAX");
+    if (ap->reserved[0] || ap->reserved[1]) return stage_invalid(ctx, kAnchor, "reserved words of the anchor params must be 0");
+    if ((rc = batch_view(ctx, batch, bv))) return rc;
+    if (!ctx->have_text || (need_index && !ctx->have_index))
+        return rh_fail(ctx, REAL_HIP_E_STATE, need_index ? "text and index must be set" : "the text must be set", hipSuccess);
+    if (bv.n_reads > 0xffffffffull) return stage_invalid(ctx, kAnchor, "more than 2^32 reads in one call");
+    if (bv.n_reads && !out) return stage_invalid(ctx, kAnchor, "null out");
+    if (bv.on_device == 1 && ((uintptr_t)out & 15u)) return stage_invalid(ctx, kAnchor, "the gap records must be 16-byte aligned");
+    if (bv.on_device == 1 && ((uintptr_t)info & 7u)) return stage_invalid(ctx, kAnchor, "the info words must be 8-byte aligned");
+    return REAL_HIP_OK;
+}
+// the reads, info words and gap records staged -> what the launchers take
+static int anchor_stage(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch &bv,
+                        const uint64_t *info, int fresh, real_hip_gap_place *out, const RhStaging &io, RhAnchorRun &r)
+{
+    RhGapStage &S = rh_gap_stage(ctx);
+    PlacedReads p;
+    int rc;
+    if ((rc = stage_placements(ctx, kAnchor, &bv, 1, info, nullptr, S.an_info, true, p, false))) return rc;
+    r.gp = *gp; r.ap = *ap; r.b = p.b[0]; r.d_info = info ? p.info : nullptr; r.n = bv.n_reads; r.fresh = fresh; r.d_out = out;
+    return io.inout(S.an_out, out, r.n, fresh != 0, r.d_out);
+}
+
+extern "C" int real_hip_gap_anchor_hits(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch *batch,
+                                        const uint64_t *info, const real_hip_hit *hits, const uint64_t *hit_offsets, int fresh, real_hip_gap_place *out)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = anchor_checks(ctx, gp, ap, batch, info, out, false, bv);
+    if (rc) return rc;
+    const uint64_t n = bv.n_reads;
+    if (!n) return REAL_HIP_OK;
+    const bool dev = bv.on_device == 1;
+    if (!hit_offsets) return stage_invalid(ctx, kAnchor, "null hit_offsets");
+    if (dev && (((uintptr_t)hits & 15u) || ((uintptr_t)hit_offsets & 7u))) return stage_invalid(ctx, kAnchor, "the hits must be 16-byte, their offsets 8-byte aligned");
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    const real_hip_hit *const hv[2] = {hits, nullptr};
+    const uint64_t *const ov[2] = {hit_offsets, nullptr};
+    MateLists L;
+    RhAnchorRun r;
+    if ((rc = stage_hit_lists(ctx, hv, ov, nullptr, 2 * n, dev, L, 1))) return rh_sync_tail(ctx, rc); // (a device list: its ends are read back)
+    if ((rc = anchor_stage(ctx, gp, ap, bv, info, fresh, out, io, r))) return rh_sync_tail(ctx, rc);
+    rc = rh_gap_anchor_select(ctx, r, nullptr);
+    if (!rc) rc = rh_gap_anchor_search(ctx, r, (const real_hip_hit *)L.h[0], L.o[0], L.total[0], false);
+    if (!rc) rc = io.back(out, r.d_out, n, "download of the gap records");
+    rc = rh_sync_tail(ctx, rc);
+    return rc ? rc : rh_gap_anchor_finish(ctx);
+}
+
+extern "C" int real_hip_match_gapped(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch *batch,
+                                     const uint64_t *info, int fresh, real_hip_gap_place *out)
+{
+    RH_ENTER(ctx);
+    real_hip_batch bv;
+    int rc = anchor_checks(ctx, gp, ap, batch, info, out, true, bv);
+    if (rc) return rc;
+    const uint64_t n = bv.n_reads;
+    if (!n) return REAL_HIP_OK;
+    const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
+    RhGapStage &S = rh_gap_stage(ctx);
+    RhAnchorRun r;
+    uint64_t count = 0, total = 0;
+    if ((rc = anchor_stage(ctx, gp, ap, bv, info, fresh, out, io, r))) return rh_sync_tail(ctx, rc);
+    if ((rc = rh_gap_anchor_select(ctx, r, &count))) return rh_sync_tail(ctx, rc);
+    if (count) {
+        // the listed reads' sub-reads as a device batch of uniform length, matched with the hits left on the device; the
+        // buffer only ever grows: a match that needs more reports the size and is done again
+        real_hip_batch sub;
+        memset(&sub, 0, sizeof sub);
+        sub.struct_size = sizeof sub; sub.on_device = 1; sub.n_reads = 2 * count; sub.patl = ap->anchor_len;
+        if ((rc = rh_gap_anchor_extract(ctx, r, count, &sub.bases, &sub.qual))) return rh_sync_tail(ctx, rc);
+        if ((rc = rh_reserve(ctx, S.an_off, (2 * count + 1) * 8))) return rh_sync_tail(ctx, rc);
+        uint64_t want = 2 * count + count / 2 + 1024;
+        for (int attempt = 0;; ++attempt) {
+            if ((rc = rh_reserve(ctx, S.an_hits, want * sizeof(real_hip_hit)))) return rh_sync_tail(ctx, rc);
+            rc = match_all_run(ctx, sub, true, (real_hip_hit *)S.an_hits.p, S.an_hits.cap / sizeof(real_hip_hit), &total, (uint64_t *)S.an_off.p, nullptr);
+            if (rc != REAL_HIP_E_OVERFLOW) break;
+            if (attempt >= 2) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "anchored gap placement: the hit buffer kept overflowing", hipSuccess);
+            if (total > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "anchored gap placement: more than 2^32 anchor hits in one batch", hipSuccess);
+            want = total;
+        }
+        if (rc) return rc;
+        rc = rh_gap_anchor_search(ctx, r, (const real_hip_hit *)S.an_hits.p, (const uint64_t *)S.an_off.p, total, true);
+    }
+    if (!rc) rc = io.back(out, r.d_out, n, "download of the gap records");
+    rc = rh_sync_tail(ctx, rc);
+    return rc ? rc : rh_gap_anchor_finish(ctx);
+}
+
+extern "C" int real_hip_gap_anchor_stats_get(real_hip_ctx *ctx, real_hip_gap_anchor_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "gap anchor stats struct_size", rh_gap_anchor_stats);
 }
 
 // ---- gapped mismatch lists (gapped_list.hip): the reads are staged as the mismatch lists stage them, the gap records where the

@@ -2,6 +2,7 @@
 
 #include "real_hip.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -56,6 +57,14 @@ void RealOptions::printHelp() const
               << "   1-based position, CIGAR, NM, mismatches, cost, second best cost (* = none), 1-based position of the placed mate; a\n"
               << "   summary line goes to standard error; -o, -unpaired and -sam are unchanged; -insert_max of at most "
               << REAL_HIP_MATE_SEARCH_MAX_INSERT << "; not with -pairs_all 1>\n"
+              << "-gapped_single <file: WITHOUT -p2, behind the other passes one more pass over every genome file and every index block of\n"
+              << "   it places each read that is placed nowhere with at most ONE insertion or deletion, around the ungapped hits of its\n"
+              << "   first and of its last -gap_anchor bases (-gap_max, -gap_flank, -gap_maxcost and -gap_margin apply); <file> gets one\n"
+              << "   line per read placed uniquely that way, in read order: read id, strand, fragment name, 1-based position, CIGAR, NM,\n"
+              << "   mismatches, cost, second best cost (* = none); a summary line goes to standard error; -o and every other output are\n"
+              << "   unchanged; with -p2: -gapped>\n"
+              << "-gap_anchor <bases of the two sub-reads that anchor a read, 1.." << REAL_HIP_MAX_PATL << ", default=max(-l, 32)>\n"
+              << "-gap_anchors <a read whose two sub-reads have more hits than this together is left alone, 1.." << REAL_HIP_GAP_ANCHORS_MAX << ", default=32>\n"
               << "-gap_max <longest insertion or deletion, 1.." << REAL_HIP_GAP_MAX << ", default=8>\n"
               << "-gap_flank <fewest aligned bases on either side of the gap, default=8>\n"
               << "-gap_maxcost <a placement costs 4 per mismatch and 6 + its length for the gap, and at most this, default=4 * (-e) + 6 + (-gap_max)>\n"
@@ -177,6 +186,9 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-mate_search_anchors") { mate_search_anchors = (uint32_t)strtoul(need("-mate_search_anchors").c_str(), 0, 10); mate_search_given = true; i += 2; }
         else if (a == "-unpaired") { unpairedfilename = need("-unpaired"); unpaired_given = true; i += 2; }
         else if (a == "-gapped") { gappedfilename = need("-gapped"); gapped_given = true; i += 2; }
+        else if (a == "-gapped_single") { gappedsinglefilename = need("-gapped_single"); gapped_single_given = true; i += 2; }
+        else if (a == "-gap_anchor") { gap_anchor = strtol(need("-gap_anchor").c_str(), 0, 10); gap_anchor_flags_given = true; i += 2; }
+        else if (a == "-gap_anchors") { gap_anchors = strtoul(need("-gap_anchors").c_str(), 0, 10); gap_anchor_flags_given = true; i += 2; }
         else if (a == "-gap_max") { gap_max = strtoul(need("-gap_max").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-gap_flank") { gap_flank = strtoul(need("-gap_flank").c_str(), 0, 10); gap_flags_given = true; i += 2; }
         else if (a == "-gap_maxcost") { gap_maxcost = strtol(need("-gap_maxcost").c_str(), 0, 10); gap_flags_given = true; i += 2; }
@@ -339,15 +351,31 @@ RealOptions::RealOptions(int argc, char *argv[])
             (pileup_depth_given && gappedfilename == pileupdepthfilename) || (vcf_given && gappedfilename == vcffilename))
             throw std::runtime_error("-gapped must name a file of its own: it names the same file as another output.");
     }
-    if (gapped_given || vcf_indels) { // the rescue's own parameters: -gapped and -vcf_indels 1 run it
+    if (gapped_single_given) { // anchored gap placement of single reads: loud errors before anything runs
+        const std::string &f = gappedsinglefilename;
+        if (!pattern2filename.empty()) throw std::runtime_error("-gapped_single places single reads: with -p2 (paired-end reads) the flag is -gapped.");
+        if (!match_unique) throw std::runtime_error("-gapped_single places the reads the unique matcher places nowhere: it cannot be combined with -u 0.");
+        if (f.empty()) throw std::runtime_error("-gapped_single needs a file name: an empty one was given.");
+        if (f == "-") throw std::runtime_error("-gapped_single writes to a file: standard output (-) cannot be it.");
+        if (f == outputfilename) throw std::runtime_error("-gapped_single must name a file of its own: it names the same file as -o.");
+        if ((sam_given && f == samfilename) || (pileup_given && f == pileupfilename) || (pileup_depth_given && f == pileupdepthfilename) ||
+            (vcf_given && f == vcffilename))
+            throw std::runtime_error("-gapped_single must name a file of its own: it names the same file as another output.");
+        if (gap_anchor < 0) gap_anchor = std::max<long>((long)seedl, 32);
+        if (gap_anchor < 1 || gap_anchor > (long)REAL_HIP_MAX_PATL) throw std::runtime_error("-gap_anchor must be in 1.." + std::to_string(REAL_HIP_MAX_PATL) + ".");
+        if (gap_anchors < 1 || gap_anchors > REAL_HIP_GAP_ANCHORS_MAX) throw std::runtime_error("-gap_anchors must be in 1.." + std::to_string(REAL_HIP_GAP_ANCHORS_MAX) + ".");
+    } else if (gap_anchor_flags_given) {
+        throw std::runtime_error("-gap_anchor / -gap_anchors need -gapped_single.");
+    }
+    if (gapped_given || vcf_indels || gapped_single_given) { // the rescue's own parameters: -gapped, -vcf_indels 1 and -gapped_single run it
         if (gap_max < 1 || gap_max > REAL_HIP_GAP_MAX) throw std::runtime_error("-gap_max must be in 1.." + std::to_string(REAL_HIP_GAP_MAX) + ".");
         if (gap_flank < 1) throw std::runtime_error("-gap_flank must be at least 1.");
         if (gap_maxcost < 0) gap_maxcost = 4 * (long)totalkmax + 6 + (long)gap_max;
         if (gap_maxcost > 65534 || gap_margin > 65535) throw std::runtime_error("-gap_maxcost takes at most 65534, -gap_margin at most 65535.");
-        if (insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        if ((gapped_given || vcf_indels) && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
             throw std::runtime_error(std::string(gapped_given ? "-gapped" : "-vcf_indels 1") + " takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
     } else if (gap_flags_given) {
-        throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped.");
+        throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped (with -p2) or -gapped_single.");
     }
     if (!pattern2filename.empty()) { // paired-end reads: loud errors, not silent differences
         if (!match_unique) throw std::runtime_error("-p2 (paired-end reads) reports one placement per fragment: it cannot be combined with -u 0 (every concordant pair: -pairs_all 1).");

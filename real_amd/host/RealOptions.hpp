@@ -57,6 +57,10 @@ struct RealOptions {
     bool gapped_given = false, gap_flags_given = false; // (-gapped / one of -gap_* was on the command line)
     unsigned long gap_max = 8, gap_flank = 8, gap_margin = 0; // -gap_max, -gap_flank, -gap_margin
     long gap_maxcost = -1;            // -gap_maxcost: -1 = 4 * (-e) + 6 + (-gap_max)
+    std::string gappedsinglefilename; // -gapped_single: the file that receives the single reads placed with one insertion or deletion (real_hip_match_gapped)
+    bool gapped_single_given = false, gap_anchor_flags_given = false; // (-gapped_single / one of -gap_anchor, -gap_anchors was on the command line)
+    long gap_anchor = -1;             // -gap_anchor: bases of the two sub-reads that anchor a read, -1 = max(-l, 32)
+    unsigned long gap_anchors = 32;   // -gap_anchors: a read whose sub-reads have more hits is left alone
     bool sam_gapped = false, sam_gapped_given = false; // -sam_gapped: with -sam and -gapped, the rescued mates' SAM lines carry their gapped placement (real_hip_mismatches_gapped)
     bool mate_search_given = false;   // (either flag was on the command line: an error without -p2)
     std::string inserthistfilename;   // -insert_hist: the file that receives the histogram of the Unique fragments' outer distances (real_hip_pair_insert_hist)

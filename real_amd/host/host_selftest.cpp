@@ -7,6 +7,7 @@
 //   host_selftest pairs_all_options <args...>     -> prints the parsed -pairs_all flag
 //   host_selftest unpaired_options <args...>      -> prints the parsed -unpaired file ("." if none)
 //   host_selftest gapped_options <args...>        -> prints the parsed -gapped file ("." if none), -gap_max, -gap_flank, -gap_maxcost, -gap_margin
+//   host_selftest gapped_single_options <args...> -> prints the parsed -gapped_single file ("." if none), -gap_anchor, -gap_anchors, -gap_max, -gap_flank, -gap_maxcost, -gap_margin
 //   host_selftest sam_gapped_options <args...>    -> prints the parsed -sam_gapped flag (0|1), the -sam and the -gapped file ("." if none)
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
@@ -428,6 +429,12 @@ int main(int argc, char **argv)
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.gappedfilename.empty() ? "." : o.gappedfilename) << " " << o.gap_max << " " << o.gap_flank << " " << o.gap_maxcost << " "
                       << o.gap_margin << "\n";
+            return 0;
+        }
+        if (cmd == "gapped_single_options") { // -gapped_single and its -gap_* flags
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.gappedsinglefilename.empty() ? "." : o.gappedsinglefilename) << " " << o.gap_anchor << " " << o.gap_anchors << " " << o.gap_max << " "
+                      << o.gap_flank << " " << o.gap_maxcost << " " << o.gap_margin << "\n";
             return 0;
         }
         if (cmd == "sam_gapped_options") { // -sam_gapped

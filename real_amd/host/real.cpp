@@ -553,7 +553,10 @@ void textPass(const RealOptions &o, const std::vector<std::string> &files, Timer
         perFile(ctx, fi, G);
     }
 }
-inline bool passesBehindOutput(const RealOptions &o) { return o.pileup_given || o.pileup_depth_given || o.vcf_given || o.sam_given || o.gapped_given; }
+inline bool passesBehindOutput(const RealOptions &o)
+{
+    return o.pileup_given || o.pileup_depth_given || o.vcf_given || o.sam_given || o.gapped_given || o.gapped_single_given;
+}
 
 // -vcf: the calls of the finished pileup of one genome file (real_hip_call_*) -- the reads once more through
 // addAll(ctx, true), which hands every batch with its final records to real_hip_call_add / _add_pairs -- as VCF lines, and a
@@ -769,6 +772,86 @@ void reportMapq(real_hip_ctx *h, const std::vector<uint8_t> &mapq)
             placed ? (double)sum / (double)placed : 0.0);
 }
 
+// ---- -gapped_single: a single read placed nowhere, placed with one insertion or deletion (real_hip_match_gapped) ----
+// Runs behind every other pass, on one fresh context on -device: every genome file and every index block of it once more
+// (genomePass: the block loop of the matching passes, no one-block restriction), the reads through each block with their FINAL
+// info words; the first block of the run starts the gap records, every other one folds into them.  Then the reads a last
+// time for the ids: one line per Unique record, in read order, and the summary line on standard error.  eligible is the
+// run's (the info words are final: it is the same in every block); anchored and crowded add up over the blocks -- a read
+// counts once per block that anchors it; placed, unique and gapped count the final records.
+real_hip_gap_params gapParams(const RealOptions &o);
+void gapSinglePass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, int qoff, const std::vector<uint64_t> &info,
+                   uint64_t numpat)
+{
+    if (!o.gapped_single_given) return;
+    OutFile out(o.gappedsinglefilename, false, "-gapped_single");
+    const real_hip_gap_params gp = gapParams(o);
+    real_hip_gap_anchor_params ap;
+    memset(&ap, 0, sizeof ap);
+    ap.struct_size = sizeof ap; ap.anchor_len = (uint32_t)o.gap_anchor; ap.max_anchors = (uint32_t)o.gap_anchors;
+    real_hip_gap_place none;
+    memset(&none, 0, sizeof none);
+    none.second = REAL_HIP_GAP_NONE;
+    std::vector<real_hip_gap_place> gaps(numpat, none);
+    double t0 = now_s();
+    CtxVec gc = makeContexts(o, 1);
+    T.index += now_s() - t0;
+    real_hip_ctx *h = gc[0]->h;
+    uint64_t eligible = 0, anchored = 0, crowded = 0, placed = 0, unique = 0, gapped = 0;
+    bool first = true;
+    for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, gc, files, fi, 0, T, nullptr, [&](Resident &) {
+        const uint64_t seen = streamReads(o, gc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
+            for (const ReadItem &it : items) {
+                if (!it.batch.n_reads) continue;
+                if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
+                const double tm = now_s();
+                check(h, real_hip_match_gapped(h, &gp, &ap, &it.batch, info.data() + it.first_id, first ? 1 : 0, gaps.data() + it.first_id), "real_hip_match_gapped");
+                T.match += now_s() - tm;
+            }
+        });
+        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+        real_hip_gap_anchor_stats st;
+        memset(&st, 0, sizeof st);
+        st.struct_size = sizeof st;
+        check(h, real_hip_gap_anchor_stats_get(h, &st, 1), "real_hip_gap_anchor_stats_get");
+        if (first) eligible = st.eligible;
+        anchored += st.eligible - st.skipped - st.crowded - st.unanchored; crowded += st.crowded;
+        first = false;
+    });
+    const uint64_t seen = streamReads(o, gc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
+        for (const ReadItem &it : items) {
+            const ReadSource src = it.src;
+            if (!src.size()) continue;
+            const uint64_t base = it.first_id;
+            if (base + src.size() > numpat) throw std::runtime_error("the read file changed between two passes");
+            formatAndWrite(src.size(), out.file(), T, [&](uint64_t i, std::string &s) {
+                const real_hip_gap_place &g = gaps[base + i];
+                if (REAL_HIP_GAP_STATE(g.tag) != REAL_HIP_PAIR_UNIQUE) return;
+                const ReadView r = src[i];
+                char cigar[48], tail[160];
+                real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
+                char second[16] = "*";
+                if (g.second != REAL_HIP_GAP_NONE) snprintf(second, sizeof second, "%u", (unsigned)g.second);
+                const int absg = g.gap < 0 ? -g.gap : g.gap;
+                snprintf(tail, sizeof tail, "\t%llu\t%s\t%u\t%u\t%u\t%s\n", (unsigned long long)((uint64_t)g.pos - RS.starts[g.fileid][g.frag] + 1), cigar,
+                         (unsigned)(g.k + absg), (unsigned)g.k, (unsigned)g.cost, second);
+                s.append(r.id, r.idlen);
+                s += REAL_HIP_GAP_INVERTED(g.tag) ? "\t-\t" : "\t+\t";
+                s += RS.names[g.fileid][g.frag];
+                s += tail;
+            });
+        }
+    });
+    if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+    out.close();
+    for (const real_hip_gap_place &g : gaps) {
+        const unsigned st = REAL_HIP_GAP_STATE(g.tag);
+        placed += st != REAL_HIP_PAIR_NOMATCH; unique += st == REAL_HIP_PAIR_UNIQUE; gapped += st != REAL_HIP_PAIR_NOMATCH && g.gap != 0;
+    }
+    std::cerr << "gap single: eligible=" << eligible << " anchored=" << anchored << " crowded=" << crowded << " placed=" << placed << " unique=" << unique
+              << " gapped=" << gapped << std::endl;
+}
+
 // ---- EnumerateUniqueMatches::doMatching -------------------------------------------------
 int matchUnique(const RealOptions &o)
 {
@@ -896,6 +979,7 @@ int matchUnique(const RealOptions &o)
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
+    gapSinglePass(o, files, RS, T, qoff, info, numpat);
     T.finish(numpat, unique);
     return EXIT_SUCCESS;
 }
@@ -988,7 +1072,7 @@ inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, b
 // record, in read order, and the summary line on standard error.
 // -sam_gapped 1: the rescue of a genome file has run with that file's -sam pass (GapRun::rescue, every record started NoMatch,
 // every file folded into them: the same array), so the records and the summed counters are already here and no pass is run.
-inline real_hip_gap_params gapParams(const RealOptions &o)
+real_hip_gap_params gapParams(const RealOptions &o)
 {
     real_hip_gap_params gp;
     memset(&gp, 0, sizeof gp);

@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "real_hip_mapq_acc_merge", "real_hip_mapq_of", "real_hip_mapq_hits", "real_hip_mapq_pair_hits", "real_hip_match_mapq",
     "real_hip_match_pairs_mapq", "real_hip_mapq", "real_hip_mapq_pairs", "real_hip_mapq_stats_get",
     "real_hip_gap_rescue", "real_hip_gap_cigar", "real_hip_gap_stats_get",
+    "real_hip_gap_anchor_hits", "real_hip_match_gapped", "real_hip_gap_anchor_stats_get",
     "real_hip_mismatches_gapped", "real_hip_gapped_list_stats_get",
     "real_hip_indel_begin", "real_hip_indel_add", "real_hip_indel_finish", "real_hip_indel_events", "real_hip_indel_calls",
     "real_hip_indel_end", "real_hip_indel_stats_get",
@@ -227,6 +228,17 @@ GAP_PLACE_DTYPE = np.dtype(RealHipGapPlace)
 assert GAP_PLACE_DTYPE.itemsize == 16
 GAP_STATS_FIELDS = ("fragments", "eligible", "other_file", "skipped", "positions", "placed", "unique", "gapped", "launches", "kernel_ms")
 RealHipGapStats = _stats_struct("RealHipGapStats", GAP_STATS_FIELDS)
+# anchored gap placement (include/real_hip.h, "anchored gap placement"): a single read placed around the hits of its two ends
+GAP_ANCHORS_MAX = 64
+
+
+class RealHipGapAnchorParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("anchor_len", C.c_uint32), ("max_anchors", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+GAP_ANCHOR_STATS_FIELDS = ("reads", "eligible", "skipped", "crowded", "unanchored", "anchors", "invalid_anchors", "positions", "placed", "unique",
+                           "gapped", "launches", "kernel_ms")
+RealHipGapAnchorStats = _stats_struct("RealHipGapAnchorStats", GAP_ANCHOR_STATS_FIELDS)
 # gapped mismatch lists (include/real_hip.h, "gapped mismatch lists"): MISMATCH_DTYPE records in the text coordinates of a gap record
 MISMATCH_DELETED = 4   # `base` of a text position the read's deletion skips
 GAPPED_LIST_STATS_FIELDS = ("fragments", "placed", "other_file", "invalid", "aligned_bases", "mismatches", "deleted", "inserted", "on_n",
@@ -399,6 +411,9 @@ def load():
     L.real_hip_gap_rescue.argtypes = [vp, pairp, C.POINTER(RealHipGapParams), batch, batch, vp, vp, vp, ci, vp]
     L.real_hip_gap_cigar.argtypes = [vp, u32, C.c_char_p, C.c_size_t]
     L.real_hip_gap_stats_get.argtypes = [vp, C.POINTER(RealHipGapStats), ci]
+    L.real_hip_gap_anchor_hits.argtypes = [vp, C.POINTER(RealHipGapParams), C.POINTER(RealHipGapAnchorParams), batch, vp, vp, vp, ci, vp]
+    L.real_hip_match_gapped.argtypes = [vp, C.POINTER(RealHipGapParams), C.POINTER(RealHipGapAnchorParams), batch, vp, ci, vp]
+    L.real_hip_gap_anchor_stats_get.argtypes = [vp, C.POINTER(RealHipGapAnchorStats), ci]
     L.real_hip_mismatches_gapped.argtypes = [vp, batch, batch, vp, vp, u64, pu64, vp]
     L.real_hip_gapped_list_stats_get.argtypes = [vp, C.POINTER(RealHipGappedListStats), ci]
     L.real_hip_indel_begin.argtypes = [vp]

@@ -62,6 +62,9 @@ class RealOptions:
     gap_flank: int = 8
     gap_maxcost: int = -1
     gap_margin: int = 0
+    gappedsinglefilename: str = ""  # -gapped_single: without -p2, the file that receives the reads placed with one insertion or deletion
+    gap_anchor: int = -1            # -gap_anchor (-1: max(seedl, 32)) / -gap_anchors
+    gap_anchors: int = 32
     gpus: int = 1
 
     def normalise(self) -> "RealOptions":
@@ -91,6 +94,25 @@ class RealOptions:
                 self.gap_maxcost = 4 * self.totalkmax + 6 + self.gap_max
             if self.insert_max > _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT:
                 raise ValueError("-gapped takes an -insert_max of at most %d" % _lib.REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        if self.gappedsinglefilename:   # the loud errors of `real -gapped_single`
+            if self.pattern2filename:
+                raise ValueError("-gapped_single places single reads: with -p2 the flag is -gapped")
+            if not self.match_unique:
+                raise ValueError("-gapped_single cannot be combined with -u 0")
+            if self.gappedsinglefilename == self.outputfilename:
+                raise ValueError("-gapped_single names the same file as -o")
+            if not 1 <= self.gap_max <= _lib.GAP_MAX:
+                raise ValueError("-gap_max must be in 1..%d" % _lib.GAP_MAX)
+            if self.gap_flank < 1:
+                raise ValueError("-gap_flank must be at least 1")
+            if self.gap_maxcost < 0:
+                self.gap_maxcost = 4 * self.totalkmax + 6 + self.gap_max
+            if self.gap_anchor < 0:
+                self.gap_anchor = max(self.seedl, 32)
+            if not 1 <= self.gap_anchor <= _lib.REAL_HIP_MAX_PATL:
+                raise ValueError("-gap_anchor must be in 1..%d" % _lib.REAL_HIP_MAX_PATL)
+            if not 1 <= self.gap_anchors <= _lib.GAP_ANCHORS_MAX:
+                raise ValueError("-gap_anchors must be in 1..%d" % _lib.GAP_ANCHORS_MAX)
         if self.pattern2filename:       # the loud errors of `real -p2`
             if not self.match_unique:
                 raise ValueError("-p2 (paired-end reads) cannot be combined with -u 0 (every concordant pair: -pairs_all 1)")
@@ -153,7 +175,8 @@ class RealOptions:
                  "-pairs_all": ("pairs_all", lambda v: bool(int(v))), "-unpaired": ("unpairedfilename", str),
                  "-insert_hist": ("inserthistfilename", str), "-insert_auto": ("insert_auto", int),
                  "-gapped": ("gappedfilename", str), "-gap_max": ("gap_max", int), "-gap_flank": ("gap_flank", int),
-                 "-gap_maxcost": ("gap_maxcost", int), "-gap_margin": ("gap_margin", int)}
+                 "-gap_maxcost": ("gap_maxcost", int), "-gap_margin": ("gap_margin", int),
+                 "-gapped_single": ("gappedsinglefilename", str), "-gap_anchor": ("gap_anchor", int), "-gap_anchors": ("gap_anchors", int)}
         argv = list(argv)
         while i < len(argv):
             a = argv[i]
@@ -816,6 +839,65 @@ class AllMatcher(HipMatcher):
     def match(self, bases, qual, offsets=None, patl: int = 0, **kw):
         return self.match_all(bases, qual, offsets, patl, **kw)
 
+    # -- anchored gap placement: a single read with one insertion or deletion, placed around the hits of its two ends --
+    new_gap_place = staticmethod(new_gap_place)
+
+    @staticmethod
+    def _gap_params(max_gap: int = 8, min_flank: int = 8, cost_mismatch: int = 4, cost_open: int = 6, cost_extend: int = 1,
+                    max_cost: Optional[int] = None, margin: int = 0, totalkmax: int = 0) -> "_lib.RealHipGapParams":
+        """the command line's defaults: costs 4 / 6 / 1, max_cost = 4 * (-e) + 6 + max_gap"""
+        if max_cost is None:
+            max_cost = 4 * int(totalkmax) + 6 + int(max_gap)
+        return _lib.sized(_lib.RealHipGapParams, max_gap=int(max_gap), min_flank=int(min_flank), cost_mismatch=int(cost_mismatch),
+                          cost_open=int(cost_open), cost_extend=int(cost_extend), max_cost=int(max_cost), margin=int(margin))
+
+    @staticmethod
+    def _gap_anchor_params(anchor_len: int, max_anchors: int = 32) -> "_lib.RealHipGapAnchorParams":
+        return _lib.sized(_lib.RealHipGapAnchorParams, anchor_len=int(anchor_len), max_anchors=int(max_anchors))
+
+    def _gap_anchor_call(self, b: RealHipBatch, info, out, fresh: Optional[bool], anchor_len: int, max_anchors: int, gap: dict, call):
+        """what gap_anchor_hits and match_gapped share: the records started or folded into, the two parameter structs, the call"""
+        on_device = b.on_device == 1
+        out, fresh = _start_or_fold(out, fresh, on_device, lambda: new_gap_place(int(b.n_reads)), "gap records")
+        if not on_device:
+            out = np.ascontiguousarray(out, dtype=_lib.GAP_PLACE_DTYPE)
+            info = None if info is None else np.ascontiguousarray(info, dtype=np.uint64)
+        gp = self._gap_params(**dict({"totalkmax": self.opts.totalkmax}, **gap))
+        ap = self._gap_anchor_params(anchor_len, max_anchors)
+        self.sync_inputs(info, out)
+        self._check(call(C.byref(gp), C.byref(ap), C.byref(b), _ptr(info), int(fresh), _ptr(out)))
+        return out
+
+    def gap_anchor_hits(self, reads, hits, hit_offsets, anchor_len: int, info=None, out=None, fresh: Optional[bool] = None,
+                        max_anchors: int = 32, **gap):
+        """real_hip_gap_anchor_hits: reads (a batch-like object or a (bases, qual, offsets) tuple) whose FINAL info word is NoMatch
+        (info None: all of them) placed with at most one insertion or deletion around the hits of their first and last
+        anchor_len bases -> gap records (lib.GAP_PLACE_DTYPE).  hits / hit_offsets: the lists of the 2 n sub-reads as match_all
+        returns them (numpy arrays with host reads or with numpy info / out, device tensors with device reads and records).
+        out: records to fold into (another genome file's or index block's), None starts them.  Needs the text, not the index.
+        gap: max_gap, min_flank, cost_mismatch, cost_open, cost_extend, max_cost, margin (_gap_params)."""
+        host = isinstance(hits, np.ndarray)
+        b = self._mate_batch(reads, host_records=host)
+        if host:
+            hits, hit_offsets = np.ascontiguousarray(hits, dtype=HIT_DTYPE), np.ascontiguousarray(hit_offsets, dtype=np.uint64)
+        if int(hit_offsets.shape[0]) != 2 * int(b.n_reads) + 1:
+            raise ValueError("the hit offsets describe another number of sub-reads than two per read")
+        self.sync_inputs(hits, hit_offsets)
+        return self._gap_anchor_call(b, info, out, fresh, anchor_len, max_anchors, gap, lambda gp, ap, bb, i, f, o: self._L.real_hip_gap_anchor_hits(
+            self._h, gp, ap, bb, i, _ptr(hits), _ptr(hit_offsets), f, o))
+
+    def match_gapped(self, reads, anchor_len: int, info=None, out=None, fresh: Optional[bool] = None, max_anchors: int = 32,
+                     host_records: bool = False, **gap):
+        """real_hip_match_gapped: gap_anchor_hits on the library's own matchAll of the eligible reads' sub-reads, everything in
+        between left on the device.  Needs the text and a resident index block.  host_records: device reads with numpy info /
+        out."""
+        b = self._mate_batch(reads, host_records=host_records)
+        return self._gap_anchor_call(b, info, out, fresh, anchor_len, max_anchors, gap, lambda gp, ap, bb, i, f, o: self._L.real_hip_match_gapped(
+            self._h, gp, ap, bb, i, f, o))
+
+    def gap_anchor_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipGapAnchorStats, self._L.real_hip_gap_anchor_stats_get, reset)
+
 
 class PairMatcher(AllMatcher):
     """Paired-end reads: matchAll of both mates and the join of their hit lists on the device, one record per fragment
@@ -964,18 +1046,7 @@ class PairMatcher(AllMatcher):
                                                 n, int(not host), _ptr(out)))
         return out
 
-    # -- gap rescue: a mate with one insertion or deletion, placed beside its uniquely placed mate --
-    new_gap_place = staticmethod(new_gap_place)
-
-    @staticmethod
-    def _gap_params(max_gap: int = 8, min_flank: int = 8, cost_mismatch: int = 4, cost_open: int = 6, cost_extend: int = 1,
-                    max_cost: Optional[int] = None, margin: int = 0, totalkmax: int = 0) -> "_lib.RealHipGapParams":
-        """the command line's defaults: costs 4 / 6 / 1, max_cost = 4 * (-e) + 6 + max_gap"""
-        if max_cost is None:
-            max_cost = 4 * int(totalkmax) + 6 + int(max_gap)
-        return _lib.sized(_lib.RealHipGapParams, max_gap=int(max_gap), min_flank=int(min_flank), cost_mismatch=int(cost_mismatch),
-                          cost_open=int(cost_open), cost_extend=int(cost_extend), max_cost=int(max_cost), margin=int(margin))
-
+    # -- gap rescue: a mate with one insertion or deletion, placed beside its uniquely placed mate (_gap_params: AllMatcher's) --
     def gap_rescue(self, mate1, mate2, pairs, singles1, singles2, min_insert: int, max_insert: int, out=None, fresh: Optional[bool] = None,
                    orientation: int = 0, **gap):
         """real_hip_gap_rescue: per fragment whose pair record is NoMatch with one mate Unique on its own and the other nowhere,
