@@ -157,7 +157,14 @@ int real_hip_index_export(real_hip_ctx *ctx, int list, void *sign, uint32_t *pos
 
 /* ---- read batch: a decoded pattern block (PatternBlock / FastSubDecoder::
  * fillPatternBlock, FastSubDecoder.hpp:107-161): mapped symbols A,C,G,T->0..3,
- * other->4 (acgtnMap.hpp:39-50) and quality = ASCII - offset in 0..63.        */
+ * other->4 (acgtnMap.hpp:39-50) and quality = ASCII - offset in 0..63.
+ * Quality bytes 64..127 (offset 33 hands over up to 93 for characters up to
+ * '~') are taken as the reference takes them: the score's table index is
+ * (ref<<8)|(read<<6)|q, so bit 6 of q falls into the read-base bits and the
+ * entry read is that of read base (read | 1) with quality q - 64.  Every other
+ * stage takes the byte as a number (pileup and call thresholds, quality sums).
+ * Bytes 128..255 are outside the reference's defined behaviour (it reads the
+ * byte as a signed char and indexes in front of its table): not supported.   */
 typedef struct real_hip_batch {
     uint32_t        struct_size;
     uint32_t        on_device;  /* 0: all pointers of the call are host memory (copied);
@@ -172,7 +179,9 @@ typedef struct real_hip_batch {
     uint32_t        patl;       /* uniform read length if offsets == NULL               */
     uint32_t        max_patl;   /* upper bound of read length when offsets != NULL and
                                    on_device (0: library computes it); a read that turns out
-                                   longer fails the call with REAL_HIP_E_INVALID          */
+                                   longer fails the call with REAL_HIP_E_INVALID: its own
+                                   record stays as it was, those of other reads of the
+                                   batch may have been written by then                    */
     /* -- since ABI version 2 (struct_size tells; a version-1 struct of 48 bytes is still accepted) -- */
     uint32_t        packed;     /* 1: bases holds 2 bits per base instead of a byte: base g of the
                                    concatenated batch at bits 7-2(g%4)-1.. of byte g/4 (MSB first, the

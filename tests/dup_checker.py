@@ -60,9 +60,18 @@ def keys_pairs(pairs, s1, s2):
     return out
 
 
-def mark(keys, quality):
+QSUM_TOP = (1 << 20) - 1             # "a qsum beyond 2^20 - 1 counts as 2^20 - 1" (per mate for pairs)
+
+
+def clamped(qsum):
+    return np.minimum(np.asarray(qsum, dtype=np.int64), QSUM_TOP)
+
+
+def mark(keys, quality, quality2=None):
     """-> (dup, stats, groups): dup[i] = 1 iff record i has a key and is not its group's representative (largest quality, among
-    equals the smallest index); groups: key -> the members' indices in ascending order"""
+    equals the smallest index); groups: key -> the members' indices in ascending order.  quality: the qsum of every read,
+    clamped here; quality2: for pairs the other mate's, clamped on its own and added"""
+    quality = clamped(quality) if quality2 is None else clamped(quality) + clamped(quality2)
     groups = {}
     for i, k in enumerate(keys):
         if k is not None:
@@ -77,11 +86,11 @@ def mark(keys, quality):
 
 
 def mark_single(info, sums):
-    return mark(keys_single(info, sums), np.asarray(sums["qsum"], dtype=np.int64))
+    return mark(keys_single(info, sums), sums["qsum"])
 
 
 def mark_pairs(pairs, s1, s2):
-    return mark(keys_pairs(pairs, s1, s2), np.asarray(s1["qsum"], dtype=np.int64) + np.asarray(s2["qsum"], dtype=np.int64))
+    return mark(keys_pairs(pairs, s1, s2), s1["qsum"], s2["qsum"])
 
 
 def representatives(groups, quality):
