@@ -1088,8 +1088,9 @@ int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped_list_stats
  * ending at x, of positions i with T'[i] == T'[i + |g|], T' the text for a deletion and text[0, x) . S for an insertion.)
  * GROUPS.  Two events are equal iff (x, g, S) are equal after normalisation; S is packed 2 bits a base, the first base lowest,
  * in a u32 (REAL_HIP_GAP_MAX bases fill it exactly; 0 for a deletion).  Per distinct event: alt_n, the supporting mates;
- * alt_fwd, those whose record is not inverted; qsum, the sum of their q; ref_n = min(depth[x - 1], depth[x]) of the finished
- * pileup (it holds only ungapped placements: no mate counts on both sides).  All counters are u32.  The event list is in
+ * alt_fwd, those whose record is not inverted; qsum, the sum of their q; ref_n = min(u[x - 1], u[x]) with u = depth - gdepth
+ * of the finished pileup: the ungapped placements alone, whether or not gapped ones were piled up beside them ("gapped
+ * placements in the pileup and the calls"), so no mate counts on both sides.  All counters are u32.  The event list is in
  * ascending (x, g, S), g compared as a signed number.
  * GENOTYPE, in phred units: PL(0/0) = qsum, PL(0/1) = REAL_HIP_CALL_HET * (ref_n + alt_n) + REAL_HIP_INDEL_PRIOR_HET,
  * PL(1/1) = REAL_HIP_INDEL_REF_Q * ref_n + REAL_HIP_INDEL_PRIOR_HOM (the SNP priors plus 10: indels are about ten times
@@ -1152,6 +1153,69 @@ typedef struct real_hip_indel_stats {
     double   kernel_ms;      /* HIP events on the ctx's stream around the kernels of add and finish    */
 } real_hip_indel_stats;
 int real_hip_indel_stats_get(real_hip_ctx *ctx, real_hip_indel_stats *out, int reset);
+
+/* ---- gapped placements in the pileup and the calls: the placements with one insertion or deletion (the records of
+ * real_hip_gap_rescue and real_hip_match_gapped) in the per-position accounting, so that the depth does not dip and a site is
+ * not genotyped short of reads where the reads carry an indel (off unless these entry points are called).
+ * Everything is an integer sum.
+ * WHICH RECORDS.  Fragment i's record, its target mate REAL_HIP_GAP_TARGET(tag), its orientation REAL_HIP_GAP_INVERTED(tag) and
+ * the ORIENTED read R are those of the block "gapped mismatch lists", word for word.  In this order: 1. a record that is not
+ * Unique is skipped; 2. a Unique record of another file id than f is skipped and counted as other_file; 3. a Unique record of
+ * file f that does not FIT by that block's rule (p + span <= n, L <= REAL_HIP_MAX_PATL, the split inside the read, |g| <=
+ * REAL_HIP_GAP_MAX) is counted as invalid, and no byte of read or text is touched for it.  Single-end records of
+ * real_hip_match_gapped are passed with the batch given as both mates.
+ * WHAT A FITTING RECORD ADDS.  With p = pos, j = split, g = gap and d = max(-g, 0), the ALIGNED text positions are
+ * [p, p + L - d) for g <= 0 and [p, p + j) and [p + j + g, p + L + g) for g > 0: a deleted position is not covered, the read
+ * shows no base there.  Text offset t < j pairs with oriented read offset t; text offset t >= j + max(g, 0) pairs with oriented
+ * read offset t - g; the read offsets j .. j + d - 1 of an insertion pair with nothing.
+ *   depth[x] += 1 on the aligned positions, in the pileup's difference array (a deletion costs four atomics, anything else
+ *     two), and the same increments go into a second difference array of n + 1 u32, allocated and zeroed by the first
+ *     add_gapped of a pileup (REAL_HIP_E_NOMEM with a message when that fails; the pileup stays valid) and scanned by the
+ *     pileup's finish into gdepth[x], the gapped placements' share of depth[x];
+ *   alt[x][b] += 1 by the pileup's rule on every aligned pair (x, r): the oriented base R[r] = b differs from ref[x], the
+ *     quality byte of oriented offset r (on the reverse strand the byte at index L - 1 - r; a batch without qualities counts
+ *     as 30) is >= min_qual, and the text's N bit at x is clear -- the quality is tested first, then the N bit;
+ *   call_add_gapped adds the evidence of the same aligned pairs over the sites of the finished pileup by the rule of "variant
+ *     calls"; cnt[s][b] == site.alt[b] for b != ref keeps holding when the same records went to both.
+ * real_hip_pileup_depth returns the total; real_hip_pileup_depth_gapped returns gdepth (zeros when no gapped add was made;
+ * the window checks are real_hip_pileup_depth's).  The indel calls take ref_n from depth - gdepth: they do not move.
+ * PROTOCOL AND ERRORS are the pileup's and the calls' own: pileup_add_gapped between the pileup's begin and finish, in any
+ * order with add / add_pairs; call_add_gapped between call_begin and call_finish, in any order with call_add / call_add_pairs.
+ * REAL_HIP_E_INVALID with a message, nothing launched: pileup_add_gapped without a begin or after finish, call_add_gapped
+ * without call_begin or before the pileup's finish, a text replaced by one of another n_bases or file id, NULL batches, NULL
+ * gaps with n_reads > 0, batches that disagree in n_reads or on_device, more than 2^32 fragments in one call.  n_reads == 0 is
+ * valid.  gaps live where real_hip_mismatches_gapped's live: host memory for on_device 0 and 2, device memory, 16-byte aligned,
+ * for 1.  real_hip_pileup_end, a new real_hip_pileup_begin and real_hip_destroy release the second array.  Nothing depends on
+ * lanes, waves, the order of the records, the split into add calls or on_device: two adds give what one add on the
+ * concatenation gives.
+ * STATISTICS.  The counters of real_hip_pileup_stats and real_hip_call_stats that add / add_pairs count keep their meaning
+ * (reads .. n_dropped, site_bases, low_qual: ungapped records only); covered, sites and max_depth are read from the arrays, so
+ * they see everything.  The sum of depth[] equals real_hip_pileup_stats::bases + real_hip_pileup_gapped_stats::aligned_bases.  */
+int real_hip_pileup_add_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps);
+int real_hip_call_add_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps);
+/* gdepth[first .. first + count) into depth (host memory, or device memory if on_device); after finish */
+int real_hip_pileup_depth_gapped(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device);
+/* work of the stage, accumulated since the last reset.  records .. n_dropped are the pileup leg's (real_hip_pileup_add_gapped),
+ * site_bases and site_low_qual the call leg's (real_hip_call_add_gapped); launches and kernel_ms are those of both.          */
+typedef struct real_hip_pileup_gapped_stats {
+    uint32_t struct_size, reserved; /* = sizeof(real_hip_pileup_gapped_stats), 0                       */
+    uint64_t records;        /* records handed to real_hip_pileup_add_gapped                           */
+    uint64_t placed;         /* Unique records of this file that fit: placements piled up              */
+    uint64_t other_file;     /* Unique records of another file id                                      */
+    uint64_t invalid;        /* Unique records of this file that do not fit                            */
+    uint64_t ungapped;       /* placed with g == 0                                                     */
+    uint64_t aligned_bases;  /* sum of L - d over the placed records = their share of the sum of depth[] */
+    uint64_t deleted;        /* sum of max(g, 0) over the placed records                               */
+    uint64_t inserted;       /* sum of d over the placed records                                       */
+    uint64_t mismatches;     /* increments of alt                                                      */
+    uint64_t low_qual;       /* mismatches that min_qual dropped                                       */
+    uint64_t n_dropped;      /* mismatches of sufficient quality on an N of the text                   */
+    uint64_t site_bases;     /* increments of cnt                                                      */
+    uint64_t site_low_qual;  /* bases on a site that min_qual dropped                                  */
+    uint64_t launches;       /* kernels launched                                                       */
+    double   kernel_ms;      /* HIP events on the ctx's stream around the kernels of both legs         */
+} real_hip_pileup_gapped_stats;
+int real_hip_pileup_gapped_stats_get(real_hip_ctx *ctx, real_hip_pileup_gapped_stats *out, int reset);
 
 /* ---- multi-GPU: one process per GPU, reads sharded contiguously over the ranks, the index replicated.
  * The path has ONE collective: the shards' results to the root, over RCCL (xGMI point-to-point links) -- a

@@ -24,6 +24,7 @@
 #include "read_walk.h"
 #include "pair_state.h" // pair_hand_over
 #include "indel_stage.h"
+#include "pileup_gapped_stage.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -249,6 +250,7 @@ struct IndelGroupArgs {
     const uint32_t *starts;        // n_groups + 1
     uint64_t n_groups;
     const uint32_t *depth;         // the finished pileup's
+    const uint32_t *gdepth;        // its gapped placements' share (null: none were piled up)
     uint4 *table;                  // real_hip_indel records, two uint4 each; gt = the best genotype
 };
 
@@ -266,7 +268,9 @@ __global__ void __launch_bounds__(RH_ID_BLOCK) indel_group_kernel(const IndelGro
         qsum += w & 0xffu;
     }
     const uint32_t x = first.x, alt_n = e - a; // (1 <= x <= n - 1: the add kernel's geometry)
-    const uint32_t ref_n = min(A.depth[x - 1], A.depth[x]);
+    uint32_t u0 = A.depth[x - 1], u1 = A.depth[x]; // the ungapped placements alone: no mate counts on both sides
+    if (A.gdepth) { u0 -= A.gdepth[x - 1]; u1 -= A.gdepth[x]; }
+    const uint32_t ref_n = min(u0, u1);
     const uint32_t ref = (uint32_t)(A.t.text[(x - 1) >> 5] >> (62 - 2 * ((x - 1) & 31u))) & 3u;
     // the three PLs, the first of minimal PL in the order 0/0, 0/1, 1/1
     const uint64_t pl0 = qsum, pl1 = (uint64_t)REAL_HIP_CALL_HET * ((uint64_t)ref_n + alt_n) + REAL_HIP_INDEL_PRIOR_HET,
@@ -444,6 +448,7 @@ static int indel_group(real_hip_ctx *ctx, RhIndelStage &S)
     G.t = rh_dev_text(ctx, ctx->fileid);
     G.ev = ev; G.starts = (const uint32_t *)S.starts.p; G.n_groups = groups;
     G.depth = (const uint32_t *)ctx->pu_diff.p; // (scanned in place by the pileup's finish)
+    G.gdepth = rh_pileup_gapped_array(ctx);
     G.table = (uint4 *)S.table.p;
     rh_time_begin(ctx, ctx->stream, S.stage);
     hipLaunchKernelGGL(indel_heads_kernel<true>, grid, block, 0, ctx->stream, ev, n, blk, blk_off, (uint32_t *)S.starts.p, groups);

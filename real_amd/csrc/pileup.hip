@@ -11,7 +11,8 @@
 // alt table (4 x u32 per text position).  The depth is a difference array of n + 1 u32: +1 at p, -1 at p + L in wrap-around
 // arithmetic -- two atomics per read, not one per base.
 //
-// finish: rocPRIM's inclusive scan turns the difference array into depth[] in place; then count, scan, emit over the
+// finish: rocPRIM's inclusive scan turns the difference array into depth[] in place (and, where real_hip_pileup_add_gapped made
+// one, the gapped placements' second difference array into gdepth[]: pileup_gapped.hip); then count, scan, emit over the
 // positions (the pattern of pair_all.hip; the block's count and a site's slot are stage_common.h's): a block of 256
 // positions counts its sites (alt sum > 0), the block counts are scanned, and the emit pass writes the 32-byte site records
 // in ascending position.  The count pass also sums `covered` and takes `max_depth`.
@@ -21,6 +22,7 @@
 #include "real_hip_internal.h"
 #include "read_walk.h"
 #include "indel_stage.h"
+#include "pileup_gapped_stage.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -139,6 +141,7 @@ static void pileup_release(real_hip_ctx *ctx)
 {
     rh_call_release(ctx); // (the calls stand on this pileup's sites: they go with it)
     rh_indel_release(ctx); // (the indel calls on its depth)
+    rh_pileup_gapped_release(ctx); // (the gapped placements' share of its depth)
     rh_release(ctx, ctx->pu_diff); rh_release(ctx, ctx->pu_alt); rh_release(ctx, ctx->pu_blk); rh_release(ctx, ctx->pu_sites);
     ctx->pu_state = 0; ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
 }
@@ -217,6 +220,12 @@ int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
     rh_time_begin(ctx, ctx->stream, ctx->pileup); // (no return inside the bracket: a failing step is reported behind rh_time_end)
     size_t t = tmp;
     hipError_t e = rocprim::inclusive_scan(ctx->sort_tmp.p, t, depth, depth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+    uint32_t *gdepth = rh_pileup_gapped_array(ctx); // (the gapped placements' difference array, when an add_gapped made one)
+    if (e == hipSuccess && gdepth) {
+        t = tmp;
+        e = rocprim::inclusive_scan(ctx->sort_tmp.p, t, gdepth, gdepth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
+        ctx->pileup.launches += 1;
+    }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pileup_sites_kernel<false>, dim3((unsigned)blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, F);
         e = hipGetLastError();

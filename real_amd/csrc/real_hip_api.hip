@@ -5,6 +5,7 @@
 #include "mapq_stage.h"
 #include "gap_stage.h"
 #include "indel_stage.h"
+#include "pileup_gapped_stage.h"
 
 #include <chrono>
 #include <cmath>
@@ -247,6 +248,7 @@ extern "C" void real_hip_destroy(real_hip_ctx *c)
     rh_mapq_release(c);
     rh_gap_release(c);
     rh_indel_drop(c);
+    rh_pileup_gapped_drop(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -1761,6 +1763,70 @@ extern "C" int real_hip_indel_end(real_hip_ctx *ctx)
 extern "C" int real_hip_indel_stats_get(real_hip_ctx *ctx, real_hip_indel_stats *out, int reset)
 {
     return stats_get(ctx, out, reset, "indel stats struct_size", rh_indel_stats);
+}
+
+// ---- gapped placements in the pileup and the calls (pileup_gapped.hip): the reads are staged as the indel calls stage them
+// (with their qualities), the gap records where the pair records would be.  Every check comes before the first launch
+static int gapped_add(real_hip_ctx *ctx, const char *stage, int (*check)(real_hip_ctx *), const real_hip_batch *b1, const real_hip_batch *b2,
+                      const real_hip_gap_place *gaps,
+                      int (*add)(real_hip_ctx *, const DevBatch &, const DevBatch &, const real_hip_gap_place *, uint64_t))
+{
+    real_hip_batch bv[2];
+    int rc;
+    if ((rc = mates_view(ctx, stage, b1, b2, false, bv)) || (rc = check(ctx))) return rc;
+    const bool dev = bv[0].on_device == 1;
+    const uint64_t n = bv[0].n_reads;
+    if (n > 0xffffffffull) return stage_invalid(ctx, stage, "more than 2^32 fragments in one call");
+    if (n && !gaps) return stage_invalid(ctx, stage, "null gaps");
+    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, stage, "the gap records must be 16-byte aligned");
+    if (!n) return REAL_HIP_OK;
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
+    DevBatch d[2];
+    for (int m = 0; m < 2; ++m) {
+        d[m] = dev_batch(ctx, st[m], n);
+        d[m].qual = st[m].qual; // (handed on whatever -q says, as the pileup does)
+    }
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    const real_hip_gap_place *d_gaps = gaps;
+    rc = io.in(rh_pileup_gapped_stage(ctx).rec, gaps, n, d_gaps);
+    if (!rc) rc = add(ctx, d[0], d[1], d_gaps, n);
+    return rh_sync_tail(ctx, rc);
+}
+
+extern "C" int real_hip_pileup_add_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps)
+{
+    RH_ENTER(ctx);
+    return gapped_add(ctx, "pileup", pileup_add_check, b1, b2, gaps, rh_pileup_gapped_add);
+}
+
+extern "C" int real_hip_call_add_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps)
+{
+    RH_ENTER(ctx);
+    return gapped_add(ctx, "calls", call_add_check, b1, b2, gaps, rh_call_gapped_add);
+}
+
+extern "C" int real_hip_pileup_depth_gapped(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device)
+{
+    RH_ENTER(ctx);
+    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
+    if (first > ctx->pu_n || count > ctx->pu_n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
+    if (!count) return REAL_HIP_OK;
+    if (!depth) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null depth", hipSuccess);
+    const uint32_t *g = rh_pileup_gapped_array(ctx);
+    if (!g) { // (no gapped add was made: zeros)
+        if (on_device) RH_HIP(ctx, hipMemsetAsync(depth, 0, (size_t)count * 4, ctx->stream));
+        else memset(depth, 0, (size_t)count * 4);
+    } else {
+        RH_HIP(ctx, hipMemcpyAsync(depth, g + first, (size_t)count * 4, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
+    }
+    return rh_sync_tail(ctx, REAL_HIP_OK);
+}
+
+extern "C" int real_hip_pileup_gapped_stats_get(real_hip_ctx *ctx, real_hip_pileup_gapped_stats *out, int reset)
+{
+    return stats_get(ctx, out, reset, "pileup gapped stats struct_size", rh_pileup_gapped_stats);
 }
 
 // ---- duplicates (duplicates.hip): the summary stages the offsets and the qualities alone (it reads no bases and needs no

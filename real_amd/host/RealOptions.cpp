@@ -91,6 +91,12 @@ void RealOptions::printHelp() const
               << "-pileup_depth <file: the depth as runs: fragment name, 0-based start, end, depth, for the maximal runs of equal\n"
               << "   non-zero depth inside a fragment; same conditions as -pileup>\n"
               << "-pileup_minq <Q: with -pileup, a mismatch of quality below Q is not counted, 0..63, default=0>\n"
+              << "-pileup_gapped <0|1: with -p2 and one of -pileup / -pileup_depth / -vcf, the mates the gap rescue places with one insertion or\n"
+              << "   deletion are piled up too: in the pileup pass of a genome file, behind the ungapped placements, the reads once more through\n"
+              << "   the gap rescue (-gap_* apply; it runs once per run, -vcf_indels 1, -gapped and -sam_gapped 1 find its records); depth and\n"
+              << "   mismatch counts on the aligned positions, none on the deleted ones; with -vcf the same mates count as evidence at the\n"
+              << "   sites; the indel lines of -vcf_indels 1 do not change; -dedup and -pileup_minmapq do NOT apply to gapped placements (they\n"
+              << "   carry no duplicate mark and their MAPQ is 255); a summary line per genome file goes to standard error, default=0>\n"
               << "-vcf <file: after the pileup of a genome file (it runs also without -pileup; -pileup_minq then applies to it), call SNPs at\n"
               << "   its sites: the reads once more, bases of quality >= -pileup_minq counted per site, ten genotype likelihoods in integers,\n"
               << "   VCF 4.2 with GT:GQ:DP:AD; same conditions as -pileup; -dedup 1 leaves the duplicates out; indels only with -vcf_indels 1, one sample>\n"
@@ -201,6 +207,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         else if (a == "-pileup_minq") { pileup_minq = strtoul(need("-pileup_minq").c_str(), 0, 10); pileup_minq_given = true; i += 2; }
         else if (a == "-vcf") { vcffilename = need("-vcf"); vcf_given = true; i += 2; }
         else if (a == "-vcf_minqual") { vcf_minqual = strtoul(need("-vcf_minqual").c_str(), 0, 10); vcf_minqual_given = true; i += 2; }
+        else if (a == "-pileup_gapped") { pileup_gapped = atoi(need("-pileup_gapped").c_str()) != 0; pileup_gapped_given = true; i += 2; }
         else if (a == "-vcf_indels") { vcf_indels = atoi(need("-vcf_indels").c_str()) != 0; vcf_indels_given = true; i += 2; }
         else if (a == "-vcf_minalt") { vcf_minalt = strtoul(need("-vcf_minalt").c_str(), 0, 10); vcf_minalt_given = true; i += 2; }
         else if (a == "-vcf_mindepth") { vcf_mindepth = strtoul(need("-vcf_mindepth").c_str(), 0, 10); vcf_mindepth_given = true; i += 2; }
@@ -314,6 +321,12 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (pattern2filename.empty()) throw std::runtime_error("-vcf_indels 1 calls the indels of gap-rescued mates: it is only meaningful with -p2 (paired-end reads).");
         if (vcf_minalt > 0xfffffffful) throw std::runtime_error("-vcf_minalt takes a number below 2^32.");
     }
+    if (pileup_gapped) { // gapped placements in the pileup: loud errors before anything runs
+        if (pattern2filename.empty())
+            throw std::runtime_error("-pileup_gapped 1 piles up the mates the gap rescue places: it needs -p2 (paired-end reads); the single-end drivers are not there yet.");
+        if (!pileup_given && !pileup_depth_given && !vcf_given) throw std::runtime_error("-pileup_gapped 1 needs one of -pileup / -pileup_depth / -vcf.");
+        if (pairs_all) throw std::runtime_error("-pileup_gapped 1 cannot be combined with -pairs_all 1.");
+    }
     if (vcf_minalt_given && !vcf_indels) throw std::runtime_error("-vcf_minalt is only meaningful with -vcf_indels 1.");
     if (vcf_minqual_given && !vcf_given) throw std::runtime_error("-vcf_minqual is only meaningful with -vcf.");
     if (vcf_mindepth_given && !vcf_given) throw std::runtime_error("-vcf_mindepth is only meaningful with -vcf.");
@@ -367,13 +380,13 @@ RealOptions::RealOptions(int argc, char *argv[])
     } else if (gap_anchor_flags_given) {
         throw std::runtime_error("-gap_anchor / -gap_anchors need -gapped_single.");
     }
-    if (gapped_given || vcf_indels || gapped_single_given) { // the rescue's own parameters: -gapped, -vcf_indels 1 and -gapped_single run it
+    if (gapped_given || vcf_indels || pileup_gapped || gapped_single_given) { // the rescue's own parameters: -gapped, -vcf_indels 1, -pileup_gapped 1 and -gapped_single run it
         if (gap_max < 1 || gap_max > REAL_HIP_GAP_MAX) throw std::runtime_error("-gap_max must be in 1.." + std::to_string(REAL_HIP_GAP_MAX) + ".");
         if (gap_flank < 1) throw std::runtime_error("-gap_flank must be at least 1.");
         if (gap_maxcost < 0) gap_maxcost = 4 * (long)totalkmax + 6 + (long)gap_max;
         if (gap_maxcost > 65534 || gap_margin > 65535) throw std::runtime_error("-gap_maxcost takes at most 65534, -gap_margin at most 65535.");
-        if ((gapped_given || vcf_indels) && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
-            throw std::runtime_error(std::string(gapped_given ? "-gapped" : "-vcf_indels 1") + " takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
+        if ((gapped_given || vcf_indels || pileup_gapped) && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+            throw std::runtime_error(std::string(gapped_given ? "-gapped" : vcf_indels ? "-vcf_indels 1" : "-pileup_gapped 1") + " takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
     } else if (gap_flags_given) {
         throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped (with -p2) or -gapped_single.");
     }

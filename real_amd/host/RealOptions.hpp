@@ -74,6 +74,7 @@ struct RealOptions {
     unsigned long vcf_minqual = 20;   // -vcf_minqual: a call needs QUAL of at least this
     unsigned long vcf_mindepth = 4;   // -vcf_mindepth: and this many bases of sufficient quality
     bool vcf_given = false, vcf_minqual_given = false, vcf_mindepth_given = false;
+    bool pileup_gapped = false, pileup_gapped_given = false; // -pileup_gapped: with -p2 and -pileup / -pileup_depth / -vcf, the gap-rescued mates are piled up and counted as evidence too (real_hip_pileup_add_gapped, real_hip_call_add_gapped)
     bool vcf_indels = false, vcf_indels_given = false; // -vcf_indels: with -vcf and -p2, the indels the gap-rescued mates show are called too (real_hip_indel_*)
     unsigned long vcf_minalt = 2;     // -vcf_minalt: an indel call needs this many rescued mates
     bool vcf_minalt_given = false;

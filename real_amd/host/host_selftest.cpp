@@ -24,6 +24,7 @@
 //   host_selftest vcf_indels <dir>               -> <dir>/out.vcf: the -vcf file of `real -vcf_indels 1` for one genome file, from sym.u8, frag.u64,
 //       names.txt (a fragment name per line), calls.bin (real_hip_call records) and indels.bin (real_hip_indel records), through Vcf.hpp
 //   host_selftest vcf_indel_options <args...>     -> prints the parsed -vcf_indels flag (0|1), -vcf_minalt, -vcf_minqual, -vcf_mindepth
+//   host_selftest pileup_gapped_options <args...> -> prints the parsed -pileup_gapped flag (0|1), -gap_max, -gap_flank
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -445,6 +446,11 @@ int main(int argc, char **argv)
         if (cmd == "insert_options") { // -insert_hist, -insert_auto
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.inserthistfilename.empty() ? "." : o.inserthistfilename) << " " << o.insert_auto << " " << o.insert_min << " " << o.insert_max << "\n";
+            return 0;
+        }
+        if (cmd == "pileup_gapped_options") { // -pileup_gapped
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.pileup_gapped ? 1 : 0) << " " << o.gap_max << " " << o.gap_flank << "\n";
             return 0;
         }
         if (cmd == "vcf_indel_options") { // -vcf_indels, -vcf_minalt

@@ -564,13 +564,17 @@ inline bool passesBehindOutput(const RealOptions &o)
 // -vcf_indels 1 (real_hip_indel_*): behind the SNP calls, on the same finished pileup, indelAll(ctx, fi) hands the
 // reads once more to the gap rescue and every batch's gap records to real_hip_indel_add; the indel calls are merged into the
 // file's lines by position, and a second summary line goes to standard error
-template <class AddAll, class IndelAll>
+// -pileup_gapped 1: behind the ungapped evidence, gapAll(ctx, fi, kGapCalls) hands the gap records the pileup pass
+// made to real_hip_call_add_gapped
+enum GapLeg { kGapPileup, kGapCalls, kGapIndels };
+template <class AddAll, class GapAll>
 void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::string &file, const std::vector<std::string> &names, const GenomeText &G, FILE *f,
-                AddAll addAll, IndelAll indelAll)
+                AddAll addAll, GapAll gapAll)
 {
     real_hip_ctx *h = ctx[0]->h;
     check(h, real_hip_call_begin(h), "real_hip_call_begin");
     addAll(ctx, true);
+    if (o.pileup_gapped) gapAll(ctx, fi, kGapCalls);
     real_hip_call_params cp;
     cp.struct_size = sizeof cp; cp.min_call_qual = (uint32_t)o.vcf_minqual; cp.min_depth = (uint32_t)o.vcf_mindepth;
     uint64_t n_calls = 0, n = 0;
@@ -580,7 +584,7 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::strin
     std::vector<real_hip_indel> indels;
     if (o.vcf_indels) {
         check(h, real_hip_indel_begin(h), "real_hip_indel_begin");
-        indelAll(ctx, fi);
+        gapAll(ctx, fi, kGapIndels);
         real_hip_indel_params ip;
         ip.struct_size = sizeof ip; ip.min_call_qual = (uint32_t)o.vcf_minqual; ip.min_alt = (uint32_t)o.vcf_minalt; ip.min_depth = (uint32_t)o.vcf_mindepth;
         uint64_t n_events = 0, n_indels = 0, ni = 0;
@@ -614,9 +618,11 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::strin
 }
 
 // addAll(ctx, calls): every batch of reads with its final records to the pileup (calls = false) or to the calls on top of it
-// indelAll(ctx, fi): with -vcf_indels 1, every batch of mates through the gap rescue to real_hip_indel_add (writeCalls)
-template <class AddAll, class IndelAll>
-void pileupPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, AddAll addAll, IndelAll indelAll)
+// gapAll(ctx, fi, leg): every batch of mates with its gap records to one leg -- kGapPileup (-pileup_gapped 1): through the gap
+// rescue to real_hip_pileup_add_gapped, behind the ungapped adds and before the finish; kGapCalls: to real_hip_call_add_gapped
+// (writeCalls); kGapIndels (-vcf_indels 1): to real_hip_indel_add, through the gap rescue unless kGapPileup has run it
+template <class AddAll, class GapAll>
+void pileupPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, AddAll addAll, GapAll gapAll)
 {
     if (!o.pileup_given && !o.pileup_depth_given && !o.vcf_given) return;
     std::unique_ptr<OutFile> sites_out(o.pileup_given ? new OutFile(o.pileupfilename, false, "-pileup") : nullptr);
@@ -633,6 +639,7 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
         real_hip_ctx *h = ctx[0]->h;
         check(h, real_hip_pileup_begin(h, &pp), "real_hip_pileup_begin");
         addAll(ctx, false);
+        if (o.pileup_gapped) gapAll(ctx, fi, kGapPileup);
         uint64_t n_sites = 0;
         check(h, real_hip_pileup_finish(h, &n_sites), "real_hip_pileup_finish");
         if (sites_out) writeSites(h, n_sites, G, sites_out->file());
@@ -645,7 +652,16 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
                 files[fi].c_str(), (unsigned long long)st.placed, (unsigned long long)st.bases, (unsigned long long)st.covered,
                 st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
                 (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
-        if (vcf_out) writeCalls(o, ctx, fi, files[fi], refs.names[fi], G, vcf_out->file(), addAll, indelAll);
+        if (o.pileup_gapped) {
+            real_hip_pileup_gapped_stats gs;
+            memset(&gs, 0, sizeof gs);
+            gs.struct_size = sizeof gs;
+            check(h, real_hip_pileup_gapped_stats_get(h, &gs, 1), "real_hip_pileup_gapped_stats_get");
+            fprintf(stderr, "pileup gapped: file=%s placements=%llu ungapped=%llu aligned=%llu deleted=%llu inserted=%llu mismatches=%llu low_qual=%llu\n",
+                    files[fi].c_str(), (unsigned long long)gs.placed, (unsigned long long)gs.ungapped, (unsigned long long)gs.aligned_bases,
+                    (unsigned long long)gs.deleted, (unsigned long long)gs.inserted, (unsigned long long)gs.mismatches, (unsigned long long)gs.low_qual);
+        }
+        if (vcf_out) writeCalls(o, ctx, fi, files[fi], refs.names[fi], G, vcf_out->file(), addAll, gapAll);
         check(h, real_hip_pileup_end(h), "real_hip_pileup_end");
     });
     for (OutFile *f : {sites_out.get(), depth_out.get(), vcf_out.get()}) {
@@ -958,7 +974,7 @@ int matchUnique(const RealOptions &o)
             }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
-    }, [](CtxVec &, unsigned) {}); // (-vcf_indels needs -p2: RealOptions refuses it here)
+    }, [](CtxVec &, unsigned, GapLeg) {}); // (-vcf_indels and -pileup_gapped need -p2: RealOptions refuses them here)
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         const uint64_t seen = streamReads(o, sc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
@@ -1183,7 +1199,7 @@ int matchPairs(const RealOptions &o)
     sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
-    const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given || o.vcf_indels; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped and -vcf_indels 1 take the rescue's anchors from them)
+    const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given || o.vcf_indels || o.pileup_gapped; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped and -vcf_indels 1 take the rescue's anchors from them)
     std::vector<real_hip_single> singles1, singles2; // -unpaired / -sam: kept across the genome files as pairs is
     std::vector<real_hip_read_sum> sums1, sums2;     // -dedup: the mates' summaries, kept for the run beside pairs
     std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
@@ -1359,11 +1375,12 @@ int matchPairs(const RealOptions &o)
     }
     if (passesBehindOutput(o)) ctx.clear(); // (the matching context goes before the pass's own one comes)
     std::vector<real_hip_pair> kept; // -dedup / -pileup_minmapq: a batch's records without what they leave out
-    // the gap rescue runs once per run: with -vcf_indels 1 in the pileup pass of each genome file (the text is resident: what the
-    // rescue needs), else with -sam_gapped 1 in the -sam pass, else in gapPass; the later passes find the records made
+    // the gap rescue runs once per run: with -pileup_gapped 1 or -vcf_indels 1 in the pileup pass of each genome file (the text is
+    // resident: what the rescue needs; with both, the pileup's leg runs it and the indel leg finds the records), else with
+    // -sam_gapped 1 in the -sam pass, else in gapPass; the later passes find the records made
     GapRun gap_run;
     const real_hip_gap_params gp = gapParams(o);
-    if (o.vcf_indels || o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
+    if (o.vcf_indels || o.pileup_gapped || o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
@@ -1377,8 +1394,9 @@ int matchPairs(const RealOptions &o)
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-    }, [&](CtxVec &pc, unsigned) {
+    }, [&](CtxVec &pc, unsigned, GapLeg leg) {
         real_hip_ctx *h = pc[0]->h;
+        const bool rescue = leg == kGapPileup || (leg == kGapIndels && !o.pileup_gapped);
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         uint64_t seen = 0;
         for (;;) {
@@ -1387,19 +1405,22 @@ int matchPairs(const RealOptions &o)
             if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
             const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             const double tm = now_s();
-            check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0, gap_run.gaps.data() + seen),
-                  "real_hip_gap_rescue");
-            check(h, real_hip_indel_add(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_indel_add");
+            if (rescue)
+                check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0, gap_run.gaps.data() + seen),
+                      "real_hip_gap_rescue");
+            if (leg == kGapPileup) check(h, real_hip_pileup_add_gapped(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_pileup_add_gapped");
+            else if (leg == kGapCalls) check(h, real_hip_call_add_gapped(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_call_add_gapped");
+            else check(h, real_hip_indel_add(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_indel_add");
             T.match += now_s() - tm;
             seen += n;
         }
         if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
-        gap_run.addStats(h);
+        if (rescue) gap_run.addStats(h);
     });
     // -sam_gapped 1: the pass of a genome file rescues the fragments whose anchor lies in it (unless -vcf_indels 1 has done so), lists
     // the rescued mates in gapped coordinates and writes their lines; gapPass then finds the records made
     GappedLists GL;
-    const bool sam_rescues = o.sam_gapped && !o.vcf_indels;
+    const bool sam_rescues = o.sam_gapped && !o.vcf_indels && !o.pileup_gapped;
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         const ReadSource v1 = m1.withQuality(o.fastq, qoff1), v2 = m2.withQuality(o.fastq2, qoff2);

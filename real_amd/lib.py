@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "real_hip_mismatches_gapped", "real_hip_gapped_list_stats_get",
     "real_hip_indel_begin", "real_hip_indel_add", "real_hip_indel_finish", "real_hip_indel_events", "real_hip_indel_calls",
     "real_hip_indel_end", "real_hip_indel_stats_get",
+    "real_hip_pileup_add_gapped", "real_hip_call_add_gapped", "real_hip_pileup_depth_gapped", "real_hip_pileup_gapped_stats_get",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -265,6 +266,10 @@ assert INDEL_DTYPE.itemsize == 32
 INDEL_STATS_FIELDS = ("fragments", "placed", "other_file", "invalid", "ungapped", "events", "on_n", "low_qual", "shifted", "shift_capped",
                       "distinct", "calls", "het", "hom", "deletions", "insertions", "launches", "kernel_ms")
 RealHipIndelStats = _stats_struct("RealHipIndelStats", INDEL_STATS_FIELDS)
+# gapped placements in the pileup and the calls (include/real_hip.h, the block of that name)
+PILEUP_GAPPED_STATS_FIELDS = ("records", "placed", "other_file", "invalid", "ungapped", "aligned_bases", "deleted", "inserted", "mismatches",
+                              "low_qual", "n_dropped", "site_bases", "site_low_qual", "launches", "kernel_ms")
+RealHipPileupGappedStats = _stats_struct("RealHipPileupGappedStats", PILEUP_GAPPED_STATS_FIELDS)
 
 
 class RealHipPairHit(C.Structure):
@@ -423,6 +428,10 @@ def load():
     L.real_hip_indel_calls.argtypes = [vp, vp, u64, pu64, ci]
     L.real_hip_indel_end.argtypes = [vp]
     L.real_hip_indel_stats_get.argtypes = [vp, C.POINTER(RealHipIndelStats), ci]
+    L.real_hip_pileup_add_gapped.argtypes = [vp, batch, batch, vp]
+    L.real_hip_call_add_gapped.argtypes = [vp, batch, batch, vp]
+    L.real_hip_pileup_depth_gapped.argtypes = [vp, u64, u64, vp, ci]
+    L.real_hip_pileup_gapped_stats_get.argtypes = [vp, C.POINTER(RealHipPileupGappedStats), ci]
     L.real_hip_counters_get.argtypes = [vp, C.POINTER(RealHipCounters), ci]
     L.real_hip_kernel_time.argtypes = [vp, ci, C.POINTER(C.c_double), pu64, ci]
     L.real_hip_timing_enable.argtypes = [vp, ci]

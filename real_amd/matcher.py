@@ -1124,6 +1124,41 @@ class PairMatcher(AllMatcher):
     def indel_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipIndelStats, self._L.real_hip_indel_stats_get, reset)
 
+    # -- gapped placements in the pileup and the calls (include/real_hip.h, the block of that name) --
+    def _gapped_records(self, mate1, mate2, gaps):
+        """both mates' batches and the fragments' gap records for a stage -> (batch 1, batch 2, gaps): all host arrays, all device
+        tensors, or device reads with numpy records, as for mismatches_gapped"""
+        host = isinstance(gaps, np.ndarray)
+        if host:
+            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
+        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
+        self.sync_inputs(gaps)
+        return b1, b2, gaps
+
+    def pileup_add_gapped(self, mate1, mate2, gaps):
+        """real_hip_pileup_add_gapped: the Unique records among `gaps` (what gap_rescue returned for these mates, or match_gapped
+        with the batch given as both mates) into the begun pileup: depth and alt on the aligned positions, not on the deleted ones"""
+        b1, b2, gaps = self._gapped_records(mate1, mate2, gaps)
+        self._check(self._L.real_hip_pileup_add_gapped(self._h, C.byref(b1), C.byref(b2), _ptr(gaps)))
+
+    def call_add_gapped(self, mate1, mate2, gaps):
+        """real_hip_call_add_gapped: the evidence of the same records over the sites of the finished pileup"""
+        b1, b2, gaps = self._gapped_records(mate1, mate2, gaps)
+        self._check(self._L.real_hip_call_add_gapped(self._h, C.byref(b1), C.byref(b2), _ptr(gaps)))
+
+    def pileup_depth_gapped(self, first: int, count: int, out=None) -> np.ndarray:
+        """gdepth[first .. first + count), the gapped placements' share of the depth, as numpy uint32 (out: a device torch tensor
+        of count 32-bit words instead); zeros when no gapped add was made"""
+        on_device = bool(getattr(out, "is_cuda", False))
+        if out is None:
+            out = np.zeros(int(count), dtype=np.uint32)
+        self.sync_inputs(out)
+        self._check(self._L.real_hip_pileup_depth_gapped(self._h, int(first), int(count), _ptr(out), int(on_device)))
+        return out
+
+    def pileup_gapped_stats(self, reset: bool = False) -> dict:
+        return self._stats(_lib.RealHipPileupGappedStats, self._L.real_hip_pileup_gapped_stats_get, reset)
+
     def single_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipSingleStats, self._L.real_hip_single_stats_get, reset)
 
