@@ -67,3 +67,46 @@ static inline RH_HD RhPlace rh_place_single(uint32_t z, uint32_t w)
     const uint32_t tag = w >> 24;
     return RhPlace{REAL_HIP_SINGLE_STATE(tag) == REAL_HIP_PAIR_UNIQUE, REAL_HIP_SINGLE_INVERTED(tag) != 0, (w >> 16) & 0xffu, REAL_HIP_SINGLE_K(tag), z};
 }
+
+// ---- the gap record ---------------------------------------------------------------------------------------------
+// The kernels write and read a real_hip_gap_place as one uint4 {x, y, z, w} (little endian): x = pos, y = frag:16 | fileid:8 |
+// tag:8, z = split:16 | gap:8 | k:8, w = cost:16 | second:16 (gap_core.h packs it).  Every shift below rests on this:
+static_assert(sizeof(real_hip_gap_place) == 16 && offsetof(real_hip_gap_place, pos) == 0 && offsetof(real_hip_gap_place, frag) == 4 &&
+                  offsetof(real_hip_gap_place, fileid) == 6 && offsetof(real_hip_gap_place, tag) == 7 && offsetof(real_hip_gap_place, split) == 8 &&
+                  offsetof(real_hip_gap_place, gap) == 10 && offsetof(real_hip_gap_place, k) == 11 && offsetof(real_hip_gap_place, cost) == 12 &&
+                  offsetof(real_hip_gap_place, second) == 14,
+              "a gap record is one uint4");
+static_assert(REAL_HIP_GAP_TARGET(0x01u) == 1u && REAL_HIP_GAP_TARGET(0xfeu) == 0u && REAL_HIP_GAP_INVERTED(0x10u) == 1u &&
+                  REAL_HIP_GAP_INVERTED(0xefu) == 0u && REAL_HIP_GAP_STATE(0x60u) == 3u && REAL_HIP_GAP_STATE(0x9fu) == 0u,
+              "the tag: bit 0 the target mate, bit 4 inverted, bits 5-6 the state");
+static_assert(REAL_HIP_GAP_MAX < 128u && REAL_HIP_MAX_PATL + REAL_HIP_GAP_MAX < 65536u, "a gap fits its int8, a split and a text offset of a span 16 bits");
+
+// what a gap record says: the state, the file, which mate is placed (target: 0 = mate 1) and on which strand, the fragment of
+// the text, the position p, the split j, the gap g (> 0 deleted text positions, < 0 inserted read bases) and the mismatch count
+struct RhGapRecord {
+    uint32_t state, file, target, inv, frag, p, j, k; // (a register each)
+    int32_t g;
+};
+static inline RH_HD RhGapRecord rh_place_gap(uint32_t x, uint32_t y, uint32_t z, uint32_t w)
+{
+    (void)w; // (cost and second say nothing of the placement)
+    const uint32_t tag = y >> 24;
+    return RhGapRecord{REAL_HIP_GAP_STATE(tag), (y >> 16) & 0xffu, REAL_HIP_GAP_TARGET(tag), REAL_HIP_GAP_INVERTED(tag), y & 0xffffu, x, z & 0xffffu, z >> 24,
+                       (int32_t)(int8_t)((z >> 16) & 0xffu)};
+}
+// The geometry of a gapped placement of a read of L bases at p in a text of n: the two diagonals read[0, j) on text[p, p + j)
+// and read[j + d, L) on text[p + j + del, p + L + g), with d = max(-g, 0) inserted read bases and del = max(g, 0) deleted text
+// positions.  It fits iff the read is no longer than REAL_HIP_MAX_PATL (read_extent's 0xffffffff is not), |g| <=
+// REAL_HIP_GAP_MAX, the split leaves a base on either side of a gap (1 <= j, j + d + 1 <= L; j == 0 without a gap) and the span
+// ends inside the text (L + g >= 2 for a split that fits).
+struct RhGapFit {
+    uint32_t fits, d, del;
+};
+static inline RH_HD RhGapFit rh_gap_fit(uint32_t L, int32_t g, uint32_t j, uint32_t p, uint64_t n)
+{
+    const uint32_t ag = (uint32_t)(g < 0 ? -g : g), d = g < 0 ? ag : 0u, del = g > 0 ? ag : 0u;
+    bool fits = L <= REAL_HIP_MAX_PATL && ag <= REAL_HIP_GAP_MAX;
+    if (fits) fits = g ? (j >= 1u && j + d + 1u <= L) : j == 0u;
+    if (fits) fits = (uint64_t)p + (uint64_t)((int64_t)L + g) <= n;
+    return RhGapFit{fits ? 1u : 0u, d, del};
+}

@@ -28,7 +28,7 @@
 // stores.
 #include "gap_core.h"   // read_words.h; gap_mm, gap_diagonal, gap_best_split, the record packing
 #include "pair_state.h" // pair_hand_over, stage_common.h
-#include "gap_stage.h"
+#include "ctx_side.h" // gap_stage.h
 
 #include <cstring>
 

@@ -5,10 +5,7 @@
 #pragma once
 #include "read_words.h"
 
-static_assert(sizeof(real_hip_gap_place) == 16 && offsetof(real_hip_gap_place, frag) == 4 && offsetof(real_hip_gap_place, fileid) == 6 &&
-                  offsetof(real_hip_gap_place, tag) == 7 && offsetof(real_hip_gap_place, split) == 8 && offsetof(real_hip_gap_place, gap) == 10 &&
-                  offsetof(real_hip_gap_place, k) == 11 && offsetof(real_hip_gap_place, cost) == 12 && offsetof(real_hip_gap_place, second) == 14,
-              "the kernels write a gap record as one uint4");
+#include "final_record.h" // the layout of a gap record, asserted there
 
 // real_hip_gap_place as a uint4: x pos, y frag:16 | fileid:8 | tag:8, z split:16 | gap:8 | k:8, w cost:16 | second:16
 static __device__ __forceinline__ uint4 gap_empty_record() { return make_uint4(0u, 0u, 0u, (uint32_t)REAL_HIP_GAP_NONE << 16); }

@@ -23,40 +23,10 @@
 // Nothing depends on lanes, tiles or the order of the list.  No scratch memory; plain C++ and vector stores.
 #include "gap_core.h"   // read_words.h; gap_mm, gap_diagonal, gap_best_split, the record packing
 #include "pair_state.h" // pair_hand_over, stage_common.h
-#include "gap_stage.h"
+#include "ctx_side.h" // gap_stage.h
 
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
-
-// ---- the stage's state, beside the ctx (gap_stage.h) ----------------------------------------------------------------------
-// (the table is never destroyed: no device memory is freed from a static destructor, behind the HIP runtime's own end)
-static std::mutex g_stage_lock;
-static std::unordered_map<real_hip_ctx *, RhGapStage *> &stage_table()
-{
-    static auto *t = new std::unordered_map<real_hip_ctx *, RhGapStage *>();
-    return *t;
-}
-RhGapStage &rh_gap_stage(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_stage_lock);
-    RhGapStage *&s = stage_table()[ctx];
-    if (!s) s = new RhGapStage();
-    return *s;
-}
-void rh_gap_release(real_hip_ctx *ctx)
-{
-    RhGapStage *s = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_stage_lock);
-        auto it = stage_table().find(ctx);
-        if (it == stage_table().end()) return;
-        s = it->second;
-        stage_table().erase(it);
-    }
-    delete s; // (its DevBufs go with it)
-}
 
 // ---- the kernels ------------------------------------------------------------------------------------------------------------
 #define RH_GAP_NP (REAL_HIP_MATE_SEARCH_MAX_INSERT + 2u * REAL_HIP_GAP_MAX + 1u) /* examined starts of a window: hi - lo <= max_insert */

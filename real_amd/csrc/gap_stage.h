@@ -1,8 +1,6 @@
 // gap_stage.h -- what gap_rescue.hip and the entry points of real_hip_api.hip share of the gap rescue (include/real_hip.h, "gap
 // rescue"): the stage's state and its launcher.
-// The state lives BESIDE the ctx, in a table keyed by it, as the mapping quality's does and for its reason (mapq_stage.h):
-// real_hip_internal.h is among the sources bench.py hashes.  rh_gap_stage creates the entry on first use; real_hip_destroy
-// releases it (rh_gap_release).
+// The state lives BESIDE the ctx, as RhCtxSide::gap: ctx_side.h says why, and has rh_gap_stage(ctx).
 #pragma once
 #include "real_hip_internal.h"
 
@@ -23,8 +21,6 @@ struct RhGapStage {
     RhStage anchor;
     uint32_t an_err = 0;
 };
-RhGapStage &rh_gap_stage(real_hip_ctx *ctx);
-void rh_gap_release(real_hip_ctx *ctx);
 
 // select + search over n fragments, all arrays on the device; asynchronous on the ctx's stream.  After the stream was
 // synchronised rh_gap_finish reports what the kernels flagged

@@ -3,10 +3,9 @@
 // NM and MD of such a mate's SAM line are written from.
 //
 // Count, scan, emit, the shape of mismatch_list.hip.  One lane per fragment in both passes (wave64, blocks of 256).  The lane
-// reads its gap record with one 16-byte load and leaves unless the record is Unique (about one fragment in four is placed,
-// one in fifty with a gap: DESIGN.md 7h); then file id, then the geometry -- every check comes before the first byte of read
-// or text is touched.  A gapped placement is two diagonals joined at the split: read[0, j) on text[0, j) and
-// read[j + d, L) on text[j + max(g, 0), L + g).  Each is a SEGMENT of read_walk.h's walk: 32 bases a step, the oriented read
+// takes its gap record to a placement with read_walk.h's placed_gap (about one fragment in four is placed, one in fifty with a
+// gap: DESIGN.md 7h) -- every check comes before the first byte of read or text is touched.  A gapped placement is two
+// diagonals joined at the split, where placed_gap says they lie.  Each is a SEGMENT of read_walk.h's walk: 32 bases a step, the oriented read
 // taken from an arbitrary offset (a byte- or base-shifted pack), the text funnel-shifted to the segment's first position, XOR,
 // one flag per differing base; the N bits of the same 32 positions are ORed in as in the ungapped lists.  Between the two
 // segments the g <= 16 deleted text positions are one more word of the text, every position flagged.  The count pass takes
@@ -16,7 +15,7 @@
 // The output is a function of records, reads and text alone.  No LDS, no scratch memory (no mask of the read is kept: a
 // register array indexed at run time would go there), plain C++.
 #include "read_walk.h"
-#include "gap_stage.h"
+#include "ctx_side.h" // gap_stage.h
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -24,11 +23,7 @@
 
 #define RH_GL_BLOCK 256u
 
-struct GappedArgs {
-    DevText  t;
-    DevBatch b[2];                 // the mates' reads
-    const uint4 *gaps;             // real_hip_gap_place records (gap_rescue.hip names the words)
-    uint64_t n;                    // fragments
+struct GappedArgs : GapRecordArgs {
     uint64_t *cnt;                 // count pass: entries per list
     const uint64_t *off;           // emit pass: their exclusive scan (n + 1)
     uint32_t *out;                 // emit pass: real_hip_mismatch records as one word each
@@ -90,44 +85,26 @@ __global__ void __launch_bounds__(RH_GL_BLOCK) gapped_list_kernel(const GappedAr
         if (EMIT) { at = A.off[i]; end = A.off[i + 1]; live = end > at; }
         uint32_t entries = 0;
         if (live) { // (a lane of the emit pass whose list is empty decodes nothing)
-            const uint4 r = A.gaps[i];
-            const uint32_t tag = r.y >> 24;
-            if (REAL_HIP_GAP_STATE(tag) == REAL_HIP_PAIR_UNIQUE) {
-                if (((r.y >> 16) & 0xffu) != A.t.fileid) {
-                    other = 1;
-                } else {
-                    const bool second = REAL_HIP_GAP_TARGET(tag) != 0, inv = REAL_HIP_GAP_INVERTED(tag) != 0;
-                    DevBatch b = A.b[0];
-                    if (second) b = A.b[1];
-                    uint64_t start;
-                    const uint32_t L = read_extent(b, i, start); // (0xffffffff: offsets that run backwards, or longer than any read)
-                    const uint32_t p = r.x, j = r.z & 0xffffu, k = r.z >> 24;
-                    const int32_t g = (int32_t)(int8_t)((r.z >> 16) & 0xffu);
-                    const uint32_t ag = (uint32_t)(g < 0 ? -g : g), d = g < 0 ? ag : 0u, del = g > 0 ? ag : 0u;
-                    // the geometry, before anything is read: |g|, the split, the span inside the text, the length
-                    bool fits = L <= REAL_HIP_MAX_PATL && ag <= REAL_HIP_GAP_MAX;
-                    if (fits) fits = g ? (j >= 1u && j + d + 1u <= L) : j == 0u;
-                    if (fits) fits = (uint64_t)p + (uint64_t)((int64_t)L + g) <= A.t.n; // (L + g >= 2 for a split that fits)
-                    if (!fits) {
-                        invalid = 1;
-                    } else {
-                        const uint32_t la = g ? j : L; // the first segment; the second starts behind the gap
-                        gl_segment<EMIT>(A, b, start, L, inv, p, 0u, 0u, la, mism, on_n, at, end);
-                        if (del) {
-                            ReadWalk walk;
-                            walk.begin(A.t.text, p + j, del);
-                            const uint64_t al = walk.text_step(0);
-                            const uint64_t flags = M55 & (~0ull << (64 - 2 * del));
-                            const uint64_t nf = A.t.has_wild ? mm_n_flags(A.t.wild, (uint64_t)p + j) & flags : 0ull;
-                            if (!EMIT) on_n += (uint32_t)__popcll(nf);
-                            else gl_emit<true>(A.out, at, end, flags, nf, al, 0ull, j);
-                        }
-                        if (g) gl_segment<EMIT>(A, b, start, L, inv, p, j + d, j + del, L - j - d, mism, on_n, at, end);
-                        placed = 1; bases = L - d; deleted = del; inserted = d;
-                        disagree = mism != k ? 1u : 0u;
-                        entries = mism + del;
-                    }
+            const PlacedGap c = placed_gap(A, i);
+            other = c.other; invalid = c.bad;
+            if (c.place) {
+                const DevBatch b = A.mate(c.second);
+                const uint32_t p = c.p, del = c.del;
+                gl_segment<EMIT>(A, b, c.start, c.L, c.inv, p, 0u, 0u, c.len1(), mism, on_n, at, end);
+                if (del) { // between the two segments: one more word of the text, every position flagged
+                    const uint32_t j = c.len1();
+                    ReadWalk walk;
+                    walk.begin(A.t.text, p + j, del);
+                    const uint64_t al = walk.text_step(0);
+                    const uint64_t flags = M55 & (~0ull << (64 - 2 * del));
+                    const uint64_t nf = A.t.has_wild ? mm_n_flags(A.t.wild, (uint64_t)p + j) & flags : 0ull;
+                    if (!EMIT) on_n += (uint32_t)__popcll(nf);
+                    else gl_emit<true>(A.out, at, end, flags, nf, al, 0ull, j);
                 }
+                if (c.gapped()) gl_segment<EMIT>(A, b, c.start, c.L, c.inv, p, c.r2(), c.t2(), c.len2(), mism, on_n, at, end);
+                placed = 1; bases = c.L - c.d; deleted = del; inserted = c.d;
+                disagree = mism != c.k ? 1u : 0u;
+                entries = mism + del;
             }
         }
         if (!EMIT) A.cnt[i] = entries;
@@ -143,14 +120,10 @@ static GappedArgs gapped_args(real_hip_ctx *ctx, RhGapStage &S, const DevBatch &
 {
     static_assert(sizeof(real_hip_mismatch) == 4 && offsetof(real_hip_mismatch, ref) == 2 && offsetof(real_hip_mismatch, base) == 3,
                   "a mismatch is one 4-byte store: off | ref << 16 | base << 24");
-    static_assert(REAL_HIP_MAX_PATL + REAL_HIP_GAP_MAX < 65536u, "a text offset of a span fits real_hip_mismatch::off");
     GappedArgs A;
     memset(&A, 0, sizeof A);
-    A.t = rh_dev_text(ctx, ctx->fileid);
-    A.b[0] = b1; A.b[1] = b2;
+    rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
     A.b[0].qual = A.b[1].qual = nullptr; // (not read)
-    A.gaps = (const uint4 *)d_gaps;
-    A.n = n;
     A.cnt = (uint64_t *)S.gl_cnt.p;
     A.stats = (unsigned long long *)S.lists.stats.p;
     return A;

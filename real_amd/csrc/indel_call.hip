@@ -2,9 +2,9 @@
 // deletion every rescued mate shows, left-normalised against the text, the mates that show the same one added up, the
 // pileup's depth beside them, three genotype likelihoods per distinct event and the compacted call list.
 //
-// indel_add_kernel: one lane per fragment (wave64, blocks of 256).  One 16-byte load of the gap record; the lane leaves unless
-// the record is Unique (about one fragment in fifty carries a gap: DESIGN.md 7h, so nothing is compacted).  File id, then the
-// geometry -- every check comes before the first byte of read or text is touched.  The N bits of the anchor and of the
+// indel_add_kernel: one lane per fragment (wave64, blocks of 256).  read_walk.h's placed_gap takes the gap record to a placement
+// (about one fragment in fifty carries a gap: DESIGN.md 7h, so nothing is compacted), then the span must lie inside the
+// record's fragment -- every check comes before the first byte of read or text is touched.  The N bits of the anchor and of the
 // deleted range are one funnel-shifted word of the N vector; the quality is the minimum over the at most 18 oriented read
 // offsets j - 1 .. j + d; the inserted bases are ReadWalk::oriented_from's word.  The left shift is the length of the run,
 // ending at x, of positions i with T'[i] == T'[i + |g|] (T' = the text, for an insertion with S spliced in at x): 32 positions
@@ -23,56 +23,22 @@
 // indexed at run time; plain C++ and vector stores.
 #include "read_walk.h"
 #include "pair_state.h" // pair_hand_over
-#include "indel_stage.h"
-#include "pileup_gapped_stage.h"
+#include "ctx_side.h" // indel_stage.h, pileup_gapped_stage.h
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 #include <algorithm>
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 #define RH_ID_BLOCK 256u
 
-// ---- the stage's state, beside the ctx (indel_stage.h) --------------------------------------------------------------------
-// (the table is never destroyed: no device memory is freed from a static destructor, behind the HIP runtime's own end)
-static std::mutex g_indel_lock;
-static std::unordered_map<real_hip_ctx *, RhIndelStage *> &indel_table()
-{
-    static auto *t = new std::unordered_map<real_hip_ctx *, RhIndelStage *>();
-    return *t;
-}
-RhIndelStage &rh_indel_stage(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_indel_lock);
-    RhIndelStage *&s = indel_table()[ctx];
-    if (!s) s = new RhIndelStage();
-    return *s;
-}
-static RhIndelStage *indel_stage_if(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_indel_lock);
-    auto it = indel_table().find(ctx);
-    return it == indel_table().end() ? nullptr : it->second;
-}
-void rh_indel_drop(real_hip_ctx *ctx)
-{
-    RhIndelStage *s = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_indel_lock);
-        auto it = indel_table().find(ctx);
-        if (it == indel_table().end()) return;
-        s = it->second;
-        indel_table().erase(it);
-    }
-    delete s; // (its DevBufs go with it)
-}
+// ---- the stage's state, beside the ctx (ctx_side.h) ----------------------------------------------------------------------
 void rh_indel_release(real_hip_ctx *ctx)
 {
-    RhIndelStage *s = indel_stage_if(ctx);
-    if (!s) return;
+    RhCtxSide *side = rh_side_if(ctx);
+    if (!side) return;
+    RhIndelStage *s = &side->indel;
     rh_release(ctx, s->ev); rh_release(ctx, s->ev2); rh_release(ctx, s->key[0]); rh_release(ctx, s->key[1]); rh_release(ctx, s->blk);
     rh_release(ctx, s->starts); rh_release(ctx, s->table); rh_release(ctx, s->events); rh_release(ctx, s->calls);
     s->state = 0; s->grouped = false;
@@ -80,11 +46,7 @@ void rh_indel_release(real_hip_ctx *ctx)
 }
 
 // ---- add: the events of the records ---------------------------------------------------------------------------------------
-struct IndelAddArgs {
-    DevText  t;
-    DevBatch b[2];                 // the mates' reads
-    const uint4 *gaps;             // real_hip_gap_place records (gap_rescue.hip names the words)
-    uint64_t n;                    // fragments
+struct IndelAddArgs : GapRecordArgs {
     uint32_t min_qual;
     uint4 *ev;                     // the event list
     unsigned long long *ev_count;  // its length
@@ -117,82 +79,73 @@ __global__ void __launch_bounds__(RH_ID_BLOCK) indel_add_kernel(const IndelAddAr
     bool live = false;
     uint4 event = make_uint4(0, 0, 0, 0);
     if (i < A.n) {
-        const uint4 r = A.gaps[i];
-        const uint32_t tag = r.y >> 24;
-        if (REAL_HIP_GAP_STATE(tag) == REAL_HIP_PAIR_UNIQUE) {
-            if (((r.y >> 16) & 0xffu) != A.t.fileid) {
-                other = 1;
+        const PlacedGap c = placed_gap(A, i);
+        other = c.other; invalid = c.bad;
+        if (c.place) {
+            const DevBatch b = A.mate(c.second);
+            const bool inv = c.inv != 0;
+            const uint32_t p = c.p, L = c.L, j = c.j, d = c.d, del = c.del, ag = d | del; // (one of d, del is 0)
+            const uint64_t start = c.start;
+            const int32_t g = (int32_t)del - (int32_t)d;
+            // the fragment, on top of the rule of the gapped lists and as that before anything is read
+            const uint64_t end = (uint64_t)p + L - d + del;
+            bool fits = c.frag < A.t.n_frag;
+            uint64_t fs = 0;
+            if (fits) {
+                fs = A.t.frag_start[c.frag];
+                fits = p >= fs && end <= A.t.frag_start[c.frag + 1];
+            }
+            if (!fits) {
+                invalid = 1;
+            } else if (!ag) {
+                placed = 1; ungapped = 1;
             } else {
-                const bool second = REAL_HIP_GAP_TARGET(tag) != 0, inv = REAL_HIP_GAP_INVERTED(tag) != 0;
-                DevBatch b = A.b[0];
-                if (second) b = A.b[1];
-                uint64_t start;
-                const uint32_t L = read_extent(b, i, start); // (0xffffffff: offsets that run backwards, or longer than any read)
-                const uint32_t p = r.x, frag = r.y & 0xffffu, j = r.z & 0xffffu;
-                const int32_t g = (int32_t)(int8_t)((r.z >> 16) & 0xffu);
-                const uint32_t ag = (uint32_t)(g < 0 ? -g : g), d = g < 0 ? ag : 0u, del = g > 0 ? ag : 0u;
-                // the geometry, before anything is read: the rule of the gapped lists, then the fragment
-                bool fits = L <= REAL_HIP_MAX_PATL && ag <= REAL_HIP_GAP_MAX;
-                if (fits) fits = g ? (j >= 1u && j + d + 1u <= L) : j == 0u;
-                const uint64_t end = (uint64_t)p + (uint64_t)((int64_t)L + g);
-                if (fits) fits = end <= A.t.n && frag < A.t.n_frag;
-                uint64_t fs = 0;
-                if (fits) {
-                    fs = A.t.frag_start[frag];
-                    fits = p >= fs && end <= A.t.frag_start[frag + 1];
-                }
-                if (!fits) {
-                    invalid = 1;
-                } else if (!g) {
-                    placed = 1; ungapped = 1;
+                placed = 1;
+                const uint64_t x = (uint64_t)p + c.len1(); // behind the first diagonal (x - 1 >= p >= fs; x + del <= end - 1 < n)
+                // the N bits of the anchor and of the deleted range: positions x - 1 .. x + del - 1
+                const uint64_t nf = A.t.has_wild ? mm_n_flags(A.t.wild, x - 1) & (~0ull << (62 - 2 * del)) : 0ull;
+                if (nf) {
+                    on_n = 1;
                 } else {
-                    placed = 1;
-                    const uint64_t x = (uint64_t)p + j; // (x - 1 >= p >= fs; x + del <= end - 1 < n)
-                    // the N bits of the anchor and of the deleted range: positions x - 1 .. x + del - 1
-                    const uint64_t nf = A.t.has_wild ? mm_n_flags(A.t.wild, x - 1) & (~0ull << (62 - 2 * del)) : 0ull;
-                    if (nf) {
-                        on_n = 1;
+                    uint32_t q = 30u;
+                    if (b.qual) {
+                        q = 0xffu;
+                        for (uint32_t k = j - 1; k <= j + d; ++k) q = min(q, (uint32_t)b.qual[start + (inv ? L - 1 - k : k)]);
+                    }
+                    if (q < A.min_qual) {
+                        lowq = 1;
                     } else {
-                        uint32_t q = 30u;
-                        if (b.qual) {
-                            q = 0xffu;
-                            for (uint32_t k = j - 1; k <= j + d; ++k) q = min(q, (uint32_t)b.qual[start + (inv ? L - 1 - k : k)]);
+                        const bool ins = d != 0;
+                        uint64_t sw = 0;
+                        if (ins) sw = ReadWalk::oriented_from(b, start, L, inv, j, d) & (~0ull << (64 - 2 * d));
+                        // the run of T'[i] == T'[i + |g|] below x, the steps allowed being i > fs with the N bits of i and
+                        // i - 1 clear; one step beyond the cap is looked at: is the cap what stops the event
+                        const uint64_t room = x - 1 - fs;
+                        const uint32_t lim = room > REAL_HIP_INDEL_SHIFT_MAX ? REAL_HIP_INDEL_SHIFT_MAX + 1u : (uint32_t)room;
+                        uint32_t done = 0;
+                        while (done < lim) {
+                            const uint32_t nb = min(32u, lim - done);
+                            const uint64_t a = x - done - nb; // (>= fs + 1)
+                            const uint64_t df = id_tprime_at(A.t.text, a, ins, x, sw) ^ id_tprime_at(A.t.text, a + ag, ins, x, sw);
+                            uint64_t flags = ((df >> 1) | df) & M55;
+                            if (A.t.has_wild) flags |= mm_n_flags(A.t.wild, a) | mm_n_flags(A.t.wild, a - 1);
+                            flags >>= 64 - 2 * nb; // position a + nb - 1 at bit 0
+                            const uint32_t run = flags ? (uint32_t)__builtin_ctzll(flags) >> 1 : nb;
+                            done += run;
+                            if (run < nb) break;
                         }
-                        if (q < A.min_qual) {
-                            lowq = 1;
-                        } else {
-                            const bool ins = d != 0;
-                            uint64_t sw = 0;
-                            if (ins) sw = ReadWalk::oriented_from(b, start, L, inv, j, d) & (~0ull << (64 - 2 * d));
-                            // the run of T'[i] == T'[i + |g|] below x, the steps allowed being i > fs with the N bits of i and
-                            // i - 1 clear; one step beyond the cap is looked at: is the cap what stops the event
-                            const uint64_t room = x - 1 - fs;
-                            const uint32_t lim = room > REAL_HIP_INDEL_SHIFT_MAX ? REAL_HIP_INDEL_SHIFT_MAX + 1u : (uint32_t)room;
-                            uint32_t done = 0;
-                            while (done < lim) {
-                                const uint32_t nb = min(32u, lim - done);
-                                const uint64_t a = x - done - nb; // (>= fs + 1)
-                                const uint64_t df = id_tprime_at(A.t.text, a, ins, x, sw) ^ id_tprime_at(A.t.text, a + ag, ins, x, sw);
-                                uint64_t flags = ((df >> 1) | df) & M55;
-                                if (A.t.has_wild) flags |= mm_n_flags(A.t.wild, a) | mm_n_flags(A.t.wild, a - 1);
-                                flags >>= 64 - 2 * nb; // position a + nb - 1 at bit 0
-                                const uint32_t run = flags ? (uint32_t)__builtin_ctzll(flags) >> 1 : nb;
-                                done += run;
-                                if (run < nb) break;
-                            }
-                            if (done > REAL_HIP_INDEL_SHIFT_MAX) { capped = 1; done = REAL_HIP_INDEL_SHIFT_MAX; }
-                            shifted = done ? 1u : 0u;
-                            const uint64_t xf = x - done;
-                            uint32_t seq = 0;
-                            if (ins) {
-                                // S after the shifts is T' from xf on; its first base goes lowest: the 2-bit groups turned round
-                                const uint32_t hi = (uint32_t)((id_tprime_at(A.t.text, xf, true, x, sw) & (~0ull << (64 - 2 * d))) >> 32);
-                                const uint32_t rv = __brev(hi);
-                                seq = ((rv >> 1) & 0x55555555u) | ((rv & 0x55555555u) << 1);
-                            }
-                            live = true;
-                            event = make_uint4((uint32_t)xf, (uint32_t)(g + 128), seq, q | (inv ? 0u : 256u));
+                        if (done > REAL_HIP_INDEL_SHIFT_MAX) { capped = 1; done = REAL_HIP_INDEL_SHIFT_MAX; }
+                        shifted = done ? 1u : 0u;
+                        const uint64_t xf = x - done;
+                        uint32_t seq = 0;
+                        if (ins) {
+                            // S after the shifts is T' from xf on; its first base goes lowest: the 2-bit groups turned round
+                            const uint32_t hi = (uint32_t)((id_tprime_at(A.t.text, xf, true, x, sw) & (~0ull << (64 - 2 * d))) >> 32);
+                            const uint32_t rv = __brev(hi);
+                            seq = ((rv >> 1) & 0x55555555u) | ((rv & 0x55555555u) << 1);
                         }
+                        live = true;
+                        event = make_uint4((uint32_t)xf, (uint32_t)(g + 128), seq, q | (inv ? 0u : 256u));
                     }
                 }
             }
@@ -376,10 +329,7 @@ int rh_indel_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, cons
     if ((rc = indel_grow(ctx, S.ev, (size_t)S.n_ev * 16, (size_t)(S.n_ev + n) * 16))) return rc;
     IndelAddArgs A;
     memset(&A, 0, sizeof A);
-    A.t = rh_dev_text(ctx, ctx->fileid);
-    A.b[0] = b1; A.b[1] = b2;
-    A.gaps = (const uint4 *)d_gaps;
-    A.n = n;
+    rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
     A.min_qual = ctx->pu_min_qual;
     A.ev = (uint4 *)S.ev.p; A.ev_count = (unsigned long long *)S.count.p;
     A.stats = (unsigned long long *)S.stage.stats.p;

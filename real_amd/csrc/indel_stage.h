@@ -1,8 +1,7 @@
 // indel_stage.h -- what indel_call.hip and the entry points of real_hip_api.hip share of the indel calls (include/real_hip.h,
 // "indel calls"): the stage's state and its steps.
-// The state lives BESIDE the ctx, in a table keyed by it, as the gap rescue's does and for its reason (gap_stage.h):
-// real_hip_internal.h is among the sources bench.py hashes.  rh_indel_stage creates the entry on first use; real_hip_destroy
-// drops it (rh_indel_drop); rh_indel_release ends the stage and keeps the entry (the pileup's end calls it).
+// The state lives BESIDE the ctx, as RhCtxSide::indel: ctx_side.h says why, and has rh_indel_stage(ctx).  rh_indel_release ends
+// the stage and keeps the record (the pileup's end calls it).
 #pragma once
 #include "real_hip_internal.h"
 
@@ -19,9 +18,7 @@ struct RhIndelStage {
     uint64_t n_ev = 0;         // events appended so far (read back behind every add)
     uint64_t n_groups = 0, n_calls = 0, het = 0, hom = 0, dels = 0, ins = 0; // the last finish
 };
-RhIndelStage &rh_indel_stage(real_hip_ctx *ctx);
 void rh_indel_release(real_hip_ctx *ctx); // ends the stage: its device memory goes, its statistics stay
-void rh_indel_drop(real_hip_ctx *ctx);    // the entry itself (real_hip_destroy)
 
 int rh_indel_begin(real_hip_ctx *ctx);
 // the events of n fragments, all arrays on the device; synchronises (the number of events is read back)

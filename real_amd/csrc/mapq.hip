@@ -14,39 +14,9 @@
 #include "real_hip_internal.h"
 #include "single_state.h" // RH_SINGLE_LANE_BUDGET, pair_state.h
 #include "mapq_state.h"
-#include "mapq_stage.h"
+#include "ctx_side.h" // mapq_stage.h
 
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
-
-// ---- the stage's state, beside the ctx (mapq_stage.h) ---------------------------------------------------------------------------
-// (the table is never destroyed: no device memory is freed from a static destructor, behind the HIP runtime's own end)
-static std::mutex g_stage_lock;
-static std::unordered_map<real_hip_ctx *, RhMapqStage *> &stage_table()
-{
-    static auto *t = new std::unordered_map<real_hip_ctx *, RhMapqStage *>();
-    return *t;
-}
-RhMapqStage &rh_mapq_stage(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_stage_lock);
-    RhMapqStage *&s = stage_table()[ctx];
-    if (!s) s = new RhMapqStage();
-    return *s;
-}
-void rh_mapq_release(real_hip_ctx *ctx)
-{
-    RhMapqStage *s = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_stage_lock);
-        auto it = stage_table().find(ctx);
-        if (it == stage_table().end()) return;
-        s = it->second;
-        stage_table().erase(it);
-    }
-    delete s; // (its DevBufs go with it)
-}
 
 typedef unsigned long long mq_word;
 

@@ -1,8 +1,6 @@
 // mapq_stage.h -- what mapq.hip and the entry points of real_hip_api.hip share of the mapping quality stage (include/real_hip.h,
 // "mapping quality"): the stage's state and its launchers.
-// The state lives BESIDE the ctx, in a table keyed by it, not in real_hip_ctx: real_hip_internal.h is among the sources
-// bench.py hashes to tie profiles/traffic.json to the matcher it was measured on, and a stage that does not touch the matcher
-// stays out of them.  rh_mapq_stage creates the entry on first use; real_hip_destroy releases it (rh_mapq_release).
+// The state lives BESIDE the ctx, as RhCtxSide::mapq: ctx_side.h says why, and has rh_mapq_stage(ctx).
 #pragma once
 #include "real_hip_internal.h"
 
@@ -14,8 +12,6 @@ struct RhMapqStage {
     DevBuf list, pair_list, acc[3], rec, score, sg[2], out;
     RhStage stage;
 };
-RhMapqStage &rh_mapq_stage(real_hip_ctx *ctx);
-void rh_mapq_release(real_hip_ctx *ctx);
 
 // the folds of `lists` (1 or 2) hit lists / of the concordant pairs into the in/out accumulators, and the finish (d_pairs null:
 // single-end, d_acc[0] alone; else d_acc = the pair's, mate 1's, mate 2's and d_singles nullable); all arrays on the device;

@@ -2,10 +2,9 @@
 // their depth and mismatch base counts into the begun pileup, their evidence into the calls of the finished one
 // (include/real_hip.h, "gapped placements in the pileup and the calls").
 //
-// One lane per record in both kernels (wave64, blocks of 256), the shape of gapped_list.hip: the lane reads its gap record with
-// one 16-byte load and leaves unless the record is Unique; then file id, then the geometry -- every check comes before the
-// first byte of read or text is touched.  A gapped placement is two diagonals joined at the split: read[0, j) on text[0, j)
-// and read[j + d, L) on text[j + max(g, 0), L + g); a deleted text position is covered by nothing.
+// One lane per record in both kernels (wave64, blocks of 256), the shape of gapped_list.hip: read_walk.h's placed_gap takes the
+// lane's gap record to a placement -- every check comes before the first byte of read or text is touched -- and says where its
+// two diagonals lie; a deleted text position is covered by nothing.
 //
 // pileup_gapped_add_kernel: the depth goes into the pileup's difference array AND into a second one, gdiff, with the same
 // wrap-around increments -- +1 at p, -1 behind the span, and for a deletion -1 / +1 round the deleted range: four atomics per
@@ -19,106 +18,29 @@
 // Everything is an integer sum: nothing depends on the order of records, lanes, blocks or calls.  No LDS, no scratch memory,
 // plain C++ with vector stores and atomics.
 #include "read_walk.h"
-#include "pileup_gapped_stage.h"
+#include "ctx_side.h"
 
 #include <cstring>
-#include <mutex>
-#include <unordered_map>
 
 #define RH_PG_BLOCK 256u
 
-// ---- the stage's state, beside the ctx (pileup_gapped_stage.h) ---------------------------------------------------------------
-// (the table is never destroyed: no device memory is freed from a static destructor, behind the HIP runtime's own end)
-static std::mutex g_pg_lock;
-static std::unordered_map<real_hip_ctx *, RhPileupGappedStage *> &pg_table()
-{
-    static auto *t = new std::unordered_map<real_hip_ctx *, RhPileupGappedStage *>();
-    return *t;
-}
-RhPileupGappedStage &rh_pileup_gapped_stage(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_pg_lock);
-    RhPileupGappedStage *&s = pg_table()[ctx];
-    if (!s) s = new RhPileupGappedStage();
-    return *s;
-}
-static RhPileupGappedStage *pg_stage_if(real_hip_ctx *ctx)
-{
-    std::lock_guard<std::mutex> g(g_pg_lock);
-    auto it = pg_table().find(ctx);
-    return it == pg_table().end() ? nullptr : it->second;
-}
-void rh_pileup_gapped_drop(real_hip_ctx *ctx)
-{
-    RhPileupGappedStage *s = nullptr;
-    {
-        std::lock_guard<std::mutex> g(g_pg_lock);
-        auto it = pg_table().find(ctx);
-        if (it == pg_table().end()) return;
-        s = it->second;
-        pg_table().erase(it);
-    }
-    delete s; // (its DevBufs go with it)
-}
+// ---- the stage's state, beside the ctx (ctx_side.h) ------------------------------------------------------------------------
 void rh_pileup_gapped_release(real_hip_ctx *ctx)
 {
-    RhPileupGappedStage *s = pg_stage_if(ctx);
-    if (!s) return;
-    rh_release(ctx, s->gdiff); rh_release(ctx, s->rec);
-    s->have_gdiff = false;
+    RhCtxSide *side = rh_side_if(ctx);
+    if (!side) return;
+    RhPileupGappedStage &s = side->pileup_gapped;
+    rh_release(ctx, s.gdiff); rh_release(ctx, s.rec);
+    s.have_gdiff = false;
 }
 uint32_t *rh_pileup_gapped_array(real_hip_ctx *ctx)
 {
-    RhPileupGappedStage *s = pg_stage_if(ctx);
-    return s && s->have_gdiff ? (uint32_t *)s->gdiff.p : nullptr;
-}
-
-// ---- the record ------------------------------------------------------------------------------------------------------------
-// Fragment i's gap record as a placement on the text t, by the rule of the gapped mismatch lists: not Unique places nothing;
-// then another file id is `other`; then a record that does not FIT is `bad`.  Nothing but the record and the read's offsets is
-// read.
-struct GappedPlace {
-    uint32_t place, inv, other, bad; // flags, a register each
-    uint32_t second;   // the target is mate 2
-    uint32_t p, L, j;  // text position, length, split
-    uint32_t d, del;   // inserted read bases, deleted text positions
-    uint64_t start;    // first base in the target's batch
-};
-static __device__ __forceinline__ GappedPlace gapped_place(const DevText &t, const DevBatch &b1, const DevBatch &b2, const uint4 *gaps, uint64_t i)
-{
-    GappedPlace c;
-    c.place = c.inv = c.other = c.bad = c.second = 0;
-    c.p = c.L = c.j = c.d = c.del = 0;
-    c.start = 0;
-    const uint4 r = gaps[i];
-    const uint32_t tag = r.y >> 24;
-    if (REAL_HIP_GAP_STATE(tag) != REAL_HIP_PAIR_UNIQUE) return c;
-    if (((r.y >> 16) & 0xffu) != t.fileid) { c.other = 1; return c; }
-    c.second = REAL_HIP_GAP_TARGET(tag);
-    c.inv = REAL_HIP_GAP_INVERTED(tag);
-    DevBatch b = b1;
-    if (c.second) b = b2;
-    uint64_t start;
-    c.L = read_extent(b, i, start); // (0xffffffff: offsets that run backwards, or longer than any read)
-    c.start = start;
-    c.p = r.x; c.j = r.z & 0xffffu;
-    const int32_t g = (int32_t)(int8_t)((r.z >> 16) & 0xffu);
-    const uint32_t ag = (uint32_t)(g < 0 ? -g : g);
-    c.d = g < 0 ? ag : 0u; c.del = g > 0 ? ag : 0u;
-    // the geometry, before anything is read: |g|, the split, the span inside the text, the length
-    bool fits = c.L <= REAL_HIP_MAX_PATL && ag <= REAL_HIP_GAP_MAX;
-    if (fits) fits = g ? (c.j >= 1u && c.j + c.d + 1u <= c.L) : c.j == 0u;
-    if (fits) fits = (uint64_t)c.p + (uint64_t)((int64_t)c.L + g) <= t.n;
-    c.place = fits ? 1u : 0u; c.bad = fits ? 0u : 1u;
-    return c;
+    RhCtxSide *side = rh_side_if(ctx);
+    return side && side->pileup_gapped.have_gdiff ? (uint32_t *)side->pileup_gapped.gdiff.p : nullptr;
 }
 
 // ---- the pileup leg ----------------------------------------------------------------------------------------------------------
-struct PileupGappedArgs {
-    DevText  t;
-    DevBatch b[2];                 // the mates' reads
-    const uint4 *gaps;             // real_hip_gap_place records (gap_rescue.hip names the words)
-    uint64_t n;                    // fragments
+struct PileupGappedArgs : GapRecordArgs {
     uint32_t min_qual;
     uint32_t *diff;                // n + 1: the depth's difference array (the pileup's)
     uint32_t *gdiff;               // n + 1: the same increments, of the gapped placements alone
@@ -163,20 +85,18 @@ __global__ void __launch_bounds__(RH_PG_BLOCK) pileup_gapped_add_kernel(const Pi
     const uint64_t i = (uint64_t)blockIdx.x * RH_PG_BLOCK + threadIdx.x;
     uint32_t placed = 0, other = 0, invalid = 0, ungapped = 0, bases = 0, deleted = 0, inserted = 0, mism = 0, lowq = 0, ndrop = 0;
     if (i < A.n) {
-        const GappedPlace c = gapped_place(A.t, A.b[0], A.b[1], A.gaps, i);
+        const PlacedGap c = placed_gap(A, i);
         other = c.other; invalid = c.bad;
         if (c.place) {
-            DevBatch b = A.b[0];
-            if (c.second) b = A.b[1];
-            const uint32_t p = c.p, L = c.L, j = c.j, d = c.d, del = c.del;
-            const bool gapped = (d | del) != 0;
-            placed = 1; ungapped = gapped ? 0u : 1u; bases = L - d; deleted = del; inserted = d;
+            const DevBatch b = A.mate(c.second);
+            const uint32_t p = c.p, L = c.L, d = c.d, del = c.del;
+            placed = 1; ungapped = c.gapped() ? 0u : 1u; bases = L - d; deleted = del; inserted = d;
             // the depth: [p, p + L - d), or for a deletion [p, p + j) and [p + j + del, p + L + del) (all <= n: the record fits)
             const uint64_t end = (uint64_t)p + L - d + del;
             atomicAdd(A.diff + p, 1u);
             atomicAdd(A.gdiff + p, 1u);
             if (del) {
-                const uint64_t x = (uint64_t)p + j;
+                const uint64_t x = (uint64_t)p + c.len1();
                 atomicAdd(A.diff + x, 0xffffffffu);
                 atomicAdd(A.gdiff + x, 0xffffffffu);
                 atomicAdd(A.diff + x + del, 1u);
@@ -185,8 +105,8 @@ __global__ void __launch_bounds__(RH_PG_BLOCK) pileup_gapped_add_kernel(const Pi
             atomicAdd(A.diff + end, 0xffffffffu);
             atomicAdd(A.gdiff + end, 0xffffffffu);
             // the aligned pairs: the first segment; the second starts behind the gap
-            pg_add_segment(A, b, c.start, L, c.inv, p, 0u, gapped ? j : L, mism, lowq, ndrop);
-            if (gapped) pg_add_segment(A, b, c.start, L, c.inv, p + j + del, j + d, L - j - d, mism, lowq, ndrop);
+            pg_add_segment(A, b, c.start, L, c.inv, p, 0u, c.len1(), mism, lowq, ndrop);
+            if (c.gapped()) pg_add_segment(A, b, c.start, L, c.inv, p + c.t2(), c.r2(), c.len2(), mism, lowq, ndrop);
         }
     }
     // (a wave's sums stay below 2^32: 64 reads of at most REAL_HIP_MAX_PATL bases)
@@ -195,11 +115,7 @@ __global__ void __launch_bounds__(RH_PG_BLOCK) pileup_gapped_add_kernel(const Pi
 }
 
 // ---- the call leg ------------------------------------------------------------------------------------------------------------
-struct CallGappedArgs {
-    DevText  t;
-    DevBatch b[2];
-    const uint4 *gaps;
-    uint64_t n;
+struct CallGappedArgs : GapRecordArgs {
     uint32_t min_qual;
     const uint64_t *bits;          // the site bitmap: n / 64 + 2 words (snp_call.hip)
     const uint32_t *rank;          // sites before each bitmap word
@@ -251,13 +167,11 @@ __global__ void __launch_bounds__(RH_PG_BLOCK) pileup_gapped_call_kernel(const C
     const uint64_t i = (uint64_t)blockIdx.x * RH_PG_BLOCK + threadIdx.x;
     uint32_t sbases = 0, lowq = 0;
     if (i < A.n) {
-        const GappedPlace c = gapped_place(A.t, A.b[0], A.b[1], A.gaps, i);
+        const PlacedGap c = placed_gap(A, i);
         if (c.place) {
-            DevBatch b = A.b[0];
-            if (c.second) b = A.b[1];
-            const bool gapped = (c.d | c.del) != 0;
-            pg_call_segment(A, b, c.start, c.L, c.inv, c.p, 0u, gapped ? c.j : c.L, sbases, lowq);
-            if (gapped) pg_call_segment(A, b, c.start, c.L, c.inv, c.p + c.j + c.del, c.j + c.d, c.L - c.j - c.d, sbases, lowq);
+            const DevBatch b = A.mate(c.second);
+            pg_call_segment(A, b, c.start, c.L, c.inv, c.p, 0u, c.len1(), sbases, lowq);
+            if (c.gapped()) pg_call_segment(A, b, c.start, c.L, c.inv, c.p + c.t2(), c.r2(), c.len2(), sbases, lowq);
         }
     }
     uint32_t s[2] = {sbases, lowq}; // (a wave's sums stay below 2^32: 64 reads of at most REAL_HIP_MAX_PATL bases)
@@ -281,11 +195,8 @@ int rh_pileup_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &
     }
     PileupGappedArgs A;
     memset(&A, 0, sizeof A);
-    A.t = rh_dev_text(ctx, ctx->fileid);
-    A.b[0] = b1; A.b[1] = b2;
+    rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
     if (!ctx->pu_min_qual) A.b[0].qual = A.b[1].qual = nullptr; // (not loaded)
-    A.gaps = (const uint4 *)d_gaps;
-    A.n = n;
     A.min_qual = ctx->pu_min_qual;
     A.diff = (uint32_t *)ctx->pu_diff.p; A.gdiff = (uint32_t *)S.gdiff.p; A.alt = (uint32_t *)ctx->pu_alt.p;
     A.stats = (unsigned long long *)S.add.stats.p;
@@ -307,10 +218,7 @@ int rh_call_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2
     if ((rc = rh_stats_reserve(ctx, S.call.stats, RH_PAIR_STRIPES, 0))) return rc;
     CallGappedArgs A;
     memset(&A, 0, sizeof A);
-    A.t = rh_dev_text(ctx, ctx->fileid);
-    A.b[0] = b1; A.b[1] = b2;
-    A.gaps = (const uint4 *)d_gaps;
-    A.n = n;
+    rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
     A.min_qual = ctx->pu_min_qual;
     A.bits = (const uint64_t *)ctx->cl_bits.p; A.rank = (const uint32_t *)ctx->cl_rank.p; A.ev = (uint32_t *)ctx->cl_ev.p;
     A.n_sites = ctx->pu_n_sites;

@@ -1,10 +1,8 @@
 // pileup_gapped_stage.h -- what pileup_gapped.hip, pileup.hip, indel_call.hip and the entry points of real_hip_api.hip share of
 // the gapped placements in the pileup and the calls (include/real_hip.h, "gapped placements in the pileup and the calls"): the
 // stage's state and its steps.
-// The state lives BESIDE the ctx, in a table keyed by it, as the indel calls' does and for its reason (indel_stage.h):
-// real_hip_internal.h is among the sources bench.py hashes.  rh_pileup_gapped_stage creates the entry on first use;
-// real_hip_destroy drops it (rh_pileup_gapped_drop); rh_pileup_gapped_release ends the stage and keeps the entry (the pileup's
-// begin and end call it).
+// The state lives BESIDE the ctx, as RhCtxSide::pileup_gapped: ctx_side.h says why, and has rh_pileup_gapped_stage(ctx).
+// rh_pileup_gapped_release ends the stage and keeps the record (the pileup's begin and end call it).
 #pragma once
 #include "real_hip_internal.h"
 
@@ -15,9 +13,7 @@ struct RhPileupGappedStage {
     bool have_gdiff = false;
     RhStage add, call; // the pileup leg's statistics and the call leg's
 };
-RhPileupGappedStage &rh_pileup_gapped_stage(real_hip_ctx *ctx);
 void rh_pileup_gapped_release(real_hip_ctx *ctx); // ends the stage: gdiff and the staged records go, the statistics stay
-void rh_pileup_gapped_drop(real_hip_ctx *ctx);    // the entry itself (real_hip_destroy)
 
 // the placements of n fragments into the begun pileup (all arrays on the device; asynchronous on the ctx's stream); the first
 // one of a pileup allocates and zeroes gdiff: REAL_HIP_E_NOMEM with a message when that fails, the pileup stays valid

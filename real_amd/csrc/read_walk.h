@@ -1,6 +1,7 @@
-// read_walk.h -- from a final record to a placement on the resident text (placed_read), and a lane's walk of the placed read
-// word by word against the 2-bit text: what pileup.hip (counts per text position), snp_call.hip (evidence per site) and
-// mismatch_list.hip (the list of one read) share.  32 bases per step, whatever the length (up to REAL_HIP_MAX_PATL_LONG):
+// read_walk.h -- from a final record to a placement on the resident text (placed_read; placed_gap for a gap record), and a
+// lane's walk of the placed read word by word against the 2-bit text: what pileup.hip (counts per text position), snp_call.hip
+// (evidence per site), mismatch_list.hip (the list of one read) and the stages of the gapped placements (gapped_list.hip,
+// indel_call.hip, pileup_gapped.hip) share.  32 bases per step, whatever the length (up to REAL_HIP_MAX_PATL_LONG):
 // no register array of the read.  No LDS, no scratch memory.
 #pragma once
 #include "match_common.h"
@@ -151,4 +152,70 @@ static __device__ __forceinline__ PlacedRead placed_read(const DevText &t, const
         if (c.pos + r.L > t.n) { r.place = false; r.bad = true; }
     }
     return r;
+}
+
+// ---- gap records ------------------------------------------------------------------------------------------------
+// what every stage that consumes real_hip_gap_place records is launched with: the text, the two mates' reads, the records
+struct GapRecordArgs {
+    DevText  t;
+    DevBatch b[2];                 // the mates' reads
+    const uint4 *gaps;             // real_hip_gap_place records (final_record.h names the words)
+    uint64_t n;                    // fragments
+    // the reads of mate 2 iff `second` (two copies and a select: an index chosen by the lane would be scratch memory)
+    __device__ __forceinline__ DevBatch mate(uint32_t second) const
+    {
+        DevBatch m = b[0];
+        if (second) m = b[1];
+        return m;
+    }
+};
+// the stage decides which of them drops the qualities
+static inline void rh_gap_record_args(GapRecordArgs &A, const real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, const real_hip_gap_place *d_gaps,
+                                      uint64_t n)
+{
+    A.t = rh_dev_text(ctx, ctx->fileid);
+    A.b[0] = b1; A.b[1] = b2;
+    A.gaps = (const uint4 *)d_gaps;
+    A.n = n;
+}
+
+// Fragment i's gap record as a placement on the text A.t, the one step from a gap record to a placement: one 16-byte load; a
+// record that is not Unique places nothing; then one of another file id is `other`; then one that does not FIT (final_record.h,
+// rh_gap_fit) is `bad`.  Nothing but the record and the read's offsets is read: every check comes before the first byte of read
+// or text is touched.  The same records are skipped and counted in every stage.
+// A gapped placement is two diagonals joined at the split, and this is the one place that says where they lie: the first is
+// read[0, len1()) on text[p, ..), the second read[r2(), r2() + len2()) on text[p + t2(), ..); the del text positions from
+// p + len1() on are covered by nothing.  Without a gap the first is the whole read and the second is empty.
+struct PlacedGap {
+    uint32_t place, inv, other, bad; // flags, a register each
+    uint32_t second;   // the target is mate 2
+    uint32_t p, L, j;  // text position, length, split
+    uint32_t d, del;   // inserted read bases, deleted text positions
+    uint32_t frag, k;  // the record's fragment of the text and mismatch count
+    uint64_t start;    // first base in the target's batch
+    __device__ __forceinline__ uint32_t gapped() const { return d | del; }
+    __device__ __forceinline__ uint32_t len1() const { return gapped() ? j : L; }
+    __device__ __forceinline__ uint32_t r2() const { return j + d; }
+    __device__ __forceinline__ uint32_t t2() const { return j + del; }
+    __device__ __forceinline__ uint32_t len2() const { return gapped() ? L - j - d : 0u; } // (>= 1 with a gap: the record fits)
+};
+static __device__ __forceinline__ PlacedGap placed_gap(const GapRecordArgs &A, uint64_t i)
+{
+    PlacedGap c;
+    c.place = c.inv = c.other = c.bad = c.second = 0;
+    c.p = c.L = c.j = c.d = c.del = c.frag = c.k = 0;
+    c.start = 0;
+    const uint4 w = A.gaps[i];
+    const RhGapRecord r = rh_place_gap(w.x, w.y, w.z, w.w);
+    if (r.state != REAL_HIP_PAIR_UNIQUE) return c;
+    if (r.file != A.t.fileid) { c.other = 1; return c; }
+    c.second = r.target; c.inv = r.inv; c.frag = r.frag; c.k = r.k;
+    c.p = r.p; c.j = r.j;
+    uint64_t start;
+    c.L = read_extent(A.mate(c.second), i, start); // (0xffffffff: offsets that run backwards, or longer than any read)
+    c.start = start;
+    const RhGapFit f = rh_gap_fit(c.L, r.g, r.j, r.p, A.t.n);
+    c.d = f.d; c.del = f.del;
+    c.place = f.fits; c.bad = 1u - f.fits;
+    return c;
 }

@@ -2,10 +2,8 @@
 // launches.  No CPU fallback: every entry point either runs the HIP path or fails.
 #include "real_hip_internal.h"
 #include "pair_state.h"
-#include "mapq_stage.h"
-#include "gap_stage.h"
-#include "indel_stage.h"
-#include "pileup_gapped_stage.h"
+#include "ctx_side.h" // the stages' state beside the ctx: mapq_stage.h, gap_stage.h, indel_stage.h, pileup_gapped_stage.h
+#include "side_table.h"
 
 #include <chrono>
 #include <cmath>
@@ -239,16 +237,19 @@ extern "C" int real_hip_create(real_hip_ctx **out, const real_hip_params *p)
     return REAL_HIP_OK;
 }
 
+// the stages' state beside the ctx (ctx_side.h)
+static RhSideTable<RhCtxSide> g_side;
+RhCtxSide &rh_side(real_hip_ctx *ctx) { return g_side.at(ctx); }
+RhCtxSide *rh_side_if(real_hip_ctx *ctx) { return g_side.find(ctx); }
+void rh_side_drop(real_hip_ctx *ctx) { g_side.drop(ctx); }
+
 extern "C" void real_hip_destroy(real_hip_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
-    rh_mapq_release(c);
-    rh_gap_release(c);
-    rh_indel_drop(c);
-    rh_pileup_gapped_drop(c);
+    rh_side_drop(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -1256,6 +1257,36 @@ static int stage_placements(real_hip_ctx *ctx, const char *stage, const real_hip
     return REAL_HIP_OK;
 }
 
+// The same for the stages that consume gap records (real_hip_mismatches_gapped, real_hip_indel_add, real_hip_pileup_add_gapped,
+// real_hip_call_add_gapped): bv[] are the views of the two mates (mates_agree has checked them).  At most 2^32
+// fragments, the null and alignment checks on the records, then both mates' reads into ctx->stage[m], then the records into
+// `rec` where they are host memory, then the device views.  n_reads == 0 is valid: nothing is copied.
+struct GappedReads {
+    DevBatch b[2];
+    const real_hip_gap_place *gaps;
+};
+static int stage_gapped(real_hip_ctx *ctx, const char *stage, const real_hip_batch bv[2], const real_hip_gap_place *gaps, DevBuf &rec, bool keep_qual,
+                        GappedReads &p)
+{
+    const uint64_t n = bv[0].n_reads;
+    const bool dev = bv[0].on_device == 1;
+    if (n > 0xffffffffull) return stage_invalid(ctx, stage, "more than 2^32 fragments in one call");
+    if (n && !gaps) return stage_invalid(ctx, stage, "null gaps");
+    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, stage, "the gap records must be 16-byte aligned");
+    int rc;
+    Staged st[2];
+    for (int m = 0; m < 2; ++m)
+        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rc;
+    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
+    p.gaps = gaps;
+    if (n && (rc = io.in(rec, gaps, n, p.gaps))) return rc;
+    for (int m = 0; m < 2; ++m) {
+        p.b[m] = dev_batch(ctx, st[m], n);
+        p.b[m].qual = keep_qual ? st[m].qual : nullptr; // (handed on whatever -q says, as the pileup does; or not at all)
+    }
+    return REAL_HIP_OK;
+}
+
 // what real_hip_pileup_add* and real_hip_call_add* share: both hand the placements of a batch to a kernel of their own
 struct PlacementSink {
     const char *name;                    // the prefix of its messages
@@ -1633,8 +1664,8 @@ extern "C" int real_hip_gap_anchor_stats_get(real_hip_ctx *ctx, real_hip_gap_anc
     return stats_get(ctx, out, reset, "gap anchor stats struct_size", rh_gap_anchor_stats);
 }
 
-// ---- gapped mismatch lists (gapped_list.hip): the reads are staged as the mismatch lists stage them, the gap records where the
-// pair records would be; count, the overflow decision, then the lists (mismatch_run's protocol)
+// ---- gapped mismatch lists (gapped_list.hip): reads and gap records through stage_gapped, without the qualities; count, the
+// overflow decision, then the lists (mismatch_run's protocol)
 static const char *const kGapped = "gapped mismatch lists";
 extern "C" int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps,
                                           real_hip_mismatch *out, uint64_t cap, uint64_t *n_out, uint64_t *mm_offsets)
@@ -1646,29 +1677,22 @@ extern "C" int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batc
     const bool dev = bv[0].on_device == 1;
     if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev, kGapped)) || (rc = mates_agree(ctx, kGapped, bv, false))) return rc;
     const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return stage_invalid(ctx, kGapped, "more than 2^32 fragments in one call");
-    if (n && !gaps) return stage_invalid(ctx, kGapped, "null gaps");
-    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, kGapped, "the gap records must be 16-byte aligned");
-    Staged st[2];
-    for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
-    const DevBatch d1 = dev_batch(ctx, st[0], n), d2 = dev_batch(ctx, st[1], n);
     RhGapStage &S = rh_gap_stage(ctx);
+    GappedReads p;
+    if ((rc = stage_gapped(ctx, kGapped, bv, gaps, S.gl_rec, false, p))) return rh_sync_tail(ctx, rc); // (n == 0 goes on: offsets of one entry)
     const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
-    const real_hip_gap_place *d_gaps = gaps;
     uint64_t *d_off = mm_offsets;
     real_hip_mismatch *d_out = out;
     uint64_t total = 0;
-    if (n) rc = io.in(S.gl_rec, gaps, n, d_gaps);
-    if (!rc) rc = io.inout(S.gl_off, mm_offsets, n + 1, true, d_off); // (outputs: nothing is uploaded)
-    if (!rc) rc = rh_gapped_list_count(ctx, d1, d2, d_gaps, n, d_off, &total);
+    rc = io.inout(S.gl_off, mm_offsets, n + 1, true, d_off); // (outputs: nothing is uploaded)
+    if (!rc) rc = rh_gapped_list_count(ctx, p.b[0], p.b[1], p.gaps, n, d_off, &total);
     if (!rc) {
         *n_out = total;
         rc = io.back(mm_offsets, d_off, n + 1, "download of the gapped mismatch offsets");
     }
     if (!rc && total > cap) rc = rh_fail(ctx, REAL_HIP_E_OVERFLOW, "gapped mismatch lists: the buffer needs more room", hipSuccess);
     if (!rc) rc = io.inout(S.gl_out, out, total, true, d_out, sizeof(real_hip_mismatch));
-    if (!rc) rc = rh_gapped_list_emit(ctx, d1, d2, d_gaps, n, d_off, d_out, total);
+    if (!rc) rc = rh_gapped_list_emit(ctx, p.b[0], p.b[1], p.gaps, n, d_off, d_out, total);
     if (!rc) rc = io.back(out, d_out, total, "download of the gapped mismatch lists");
     return rh_sync_tail(ctx, rc);
 }
@@ -1678,8 +1702,8 @@ extern "C" int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped
     return stats_get(ctx, out, reset, "gapped list stats struct_size", rh_gapped_list_stats);
 }
 
-// ---- indel calls (indel_call.hip): on top of the finished pileup; the reads are staged as the gapped mismatch lists stage
-// them (with their qualities), the gap records where the pair records would be.  Every check comes before the first launch
+// ---- indel calls (indel_call.hip): on top of the finished pileup; reads and gap records through stage_gapped, with the
+// qualities.  Every check comes before the first launch
 static const char *const kIndel = "indel calls";
 static int indel_pileup_check(real_hip_ctx *ctx, const char *unfinished)
 {
@@ -1707,25 +1731,10 @@ extern "C" int real_hip_indel_add(real_hip_ctx *ctx, const real_hip_batch *b1, c
     if (S.state == 0) return stage_invalid(ctx, kIndel, "add without begin");
     if (S.state == 2) return stage_invalid(ctx, kIndel, "add after finish");
     if ((rc = indel_pileup_check(ctx, "add without a finished pileup"))) return rc;
-    const bool dev = bv[0].on_device == 1;
-    const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return stage_invalid(ctx, kIndel, "more than 2^32 fragments in one call");
-    if (n && !gaps) return stage_invalid(ctx, kIndel, "null gaps");
-    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, kIndel, "the gap records must be 16-byte aligned");
-    if (!n) return REAL_HIP_OK;
-    Staged st[2];
-    for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
-    DevBatch d[2];
-    for (int m = 0; m < 2; ++m) {
-        d[m] = dev_batch(ctx, st[m], n);
-        d[m].qual = st[m].qual; // (handed on whatever -q says, as the pileup does)
-    }
-    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
-    const real_hip_gap_place *d_gaps = gaps;
-    rc = io.in(S.rec, gaps, n, d_gaps);
-    if (!rc) rc = rh_indel_add(ctx, d[0], d[1], d_gaps, n);
-    return rh_sync_tail(ctx, rc);
+    GappedReads p;
+    if ((rc = stage_gapped(ctx, kIndel, bv, gaps, S.rec, true, p))) return rh_sync_tail(ctx, rc);
+    if (!bv[0].n_reads) return REAL_HIP_OK;
+    return rh_sync_tail(ctx, rh_indel_add(ctx, p.b[0], p.b[1], p.gaps, bv[0].n_reads));
 }
 
 extern "C" int real_hip_indel_finish(real_hip_ctx *ctx, const real_hip_indel_params *p, uint64_t *n_events, uint64_t *n_calls)
@@ -1765,8 +1774,8 @@ extern "C" int real_hip_indel_stats_get(real_hip_ctx *ctx, real_hip_indel_stats 
     return stats_get(ctx, out, reset, "indel stats struct_size", rh_indel_stats);
 }
 
-// ---- gapped placements in the pileup and the calls (pileup_gapped.hip): the reads are staged as the indel calls stage them
-// (with their qualities), the gap records where the pair records would be.  Every check comes before the first launch
+// ---- gapped placements in the pileup and the calls (pileup_gapped.hip): reads and gap records through stage_gapped, with the
+// qualities.  Every check comes before the first launch
 static int gapped_add(real_hip_ctx *ctx, const char *stage, int (*check)(real_hip_ctx *), const real_hip_batch *b1, const real_hip_batch *b2,
                       const real_hip_gap_place *gaps,
                       int (*add)(real_hip_ctx *, const DevBatch &, const DevBatch &, const real_hip_gap_place *, uint64_t))
@@ -1774,25 +1783,10 @@ static int gapped_add(real_hip_ctx *ctx, const char *stage, int (*check)(real_hi
     real_hip_batch bv[2];
     int rc;
     if ((rc = mates_view(ctx, stage, b1, b2, false, bv)) || (rc = check(ctx))) return rc;
-    const bool dev = bv[0].on_device == 1;
-    const uint64_t n = bv[0].n_reads;
-    if (n > 0xffffffffull) return stage_invalid(ctx, stage, "more than 2^32 fragments in one call");
-    if (n && !gaps) return stage_invalid(ctx, stage, "null gaps");
-    if (dev && ((uintptr_t)gaps & 15u)) return stage_invalid(ctx, stage, "the gap records must be 16-byte aligned");
-    if (!n) return REAL_HIP_OK;
-    Staged st[2];
-    for (int m = 0; m < 2; ++m)
-        if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rh_sync_tail(ctx, rc);
-    DevBatch d[2];
-    for (int m = 0; m < 2; ++m) {
-        d[m] = dev_batch(ctx, st[m], n);
-        d[m].qual = st[m].qual; // (handed on whatever -q says, as the pileup does)
-    }
-    const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
-    const real_hip_gap_place *d_gaps = gaps;
-    rc = io.in(rh_pileup_gapped_stage(ctx).rec, gaps, n, d_gaps);
-    if (!rc) rc = add(ctx, d[0], d[1], d_gaps, n);
-    return rh_sync_tail(ctx, rc);
+    GappedReads p;
+    if ((rc = stage_gapped(ctx, stage, bv, gaps, rh_pileup_gapped_stage(ctx).rec, true, p))) return rh_sync_tail(ctx, rc);
+    if (!bv[0].n_reads) return REAL_HIP_OK;
+    return rh_sync_tail(ctx, add(ctx, p.b[0], p.b[1], p.gaps, bv[0].n_reads));
 }
 
 extern "C" int real_hip_pileup_add_gapped(real_hip_ctx *ctx, const real_hip_batch *b1, const real_hip_batch *b2, const real_hip_gap_place *gaps)

@@ -11,8 +11,10 @@
 //   host_selftest sam_gapped_options <args...>    -> prints the parsed -sam_gapped flag (0|1), the -sam and the -gapped file ("." if none)
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
-//   host_selftest records                         -> checks the decoders of the final records (csrc/final_record.h) against records written
-//       through the public structs, prints ok or the first disagreement
+//   host_selftest records                         -> checks the decoders of the final records and of the gap records (csrc/final_record.h)
+//       against records written through the public structs, prints ok or the first disagreement
+//   host_selftest gap_grid <n>                    -> the geometry rule of a gapped placement in a text of n bases (csrc/final_record.h, rh_gap_fit)
+//       over a grid of lengths, gaps, splits and positions: a line "L g j p fits d del" each
 //   host_selftest lines <reads.fq> <outdir>      -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
 //   host_selftest sam <dir> <fastq:0|1> <qoff> <scores:0|1> <paired:0|1> -> <dir>/block.sam chunk.sam: the -sam file of the reads <dir>/r1 (and r2)
 //       from the records in <dir> (names.txt: a line "file<TAB>start<TAB>name" per fragment and one "file<TAB>n<TAB>" behind a file's
@@ -360,7 +362,51 @@ int main(int argc, char **argv)
                             if (c.place != (u.st == 1 || u.st == 2) || c.inv != (u.st == 2) || c.file != u.file || c.k != u.errors || c.pos != u.pos)
                                 return fail("info", state, file, p);
                         }
+            // gap records: every state, both targets, both strands, the file ids, positions, splits, gaps and mismatch counts at
+            // the ends of their ranges; cost and second are not the decoder's business
+            const uint32_t splits[4] = {0u, 1u, 319u, 0xffffu};
+            const int gapv[7] = {-128, -17, -1, 0, 1, 17, 127};
+            for (uint32_t state = 0; state < 4; ++state)
+                for (uint32_t target = 0; target < 2; ++target)
+                    for (uint32_t inv = 0; inv < 2; ++inv)
+                        for (uint32_t file : files)
+                            for (uint32_t p1 : positions)
+                                for (uint32_t j : splits)
+                                    for (int g : gapv) {
+                                        real_hip_gap_place r;
+                                        memset(&r, 0, sizeof r);
+                                        r.pos = p1; r.frag = (uint16_t)(0xfffe - state); r.fileid = (uint8_t)file;
+                                        r.tag = (uint8_t)(target | 0x0eu | inv << 4 | state << 5 | 0x80u); // (the bits no macro reads are set: the decoder must not look)
+                                        r.split = (uint16_t)j; r.gap = (int8_t)g; r.k = (uint8_t)(255 - file); r.cost = 0xfffd; r.second = 0xfffc;
+                                        if (REAL_HIP_GAP_TARGET(r.tag) != target || REAL_HIP_GAP_INVERTED(r.tag) != inv || REAL_HIP_GAP_STATE(r.tag) != state)
+                                            return fail("gap tag", state, target, inv);
+                                        uint32_t w[4];
+                                        memcpy(w, &r, sizeof r);
+                                        const RhGapRecord c = rh_place_gap(w[0], w[1], w[2], w[3]);
+                                        if (c.state != state || c.file != file || c.target != target || c.inv != inv || c.frag != r.frag || c.p != p1 || c.j != j ||
+                                            c.g != g || c.k != r.k) return fail("gap record", (uint64_t)state << 8 | target << 4 | inv, p1, (uint64_t)(int64_t)g);
+                                    }
             std::cout << "ok" << std::endl;
+            return 0;
+        }
+        if (cmd == "gap_grid" && argc == 3) {
+            // the geometry rule of a gapped placement (csrc/final_record.h, rh_gap_fit) over a grid, a line "L g j p fits d del" each:
+            // the lengths at the ends of the range and round a word of 32 bases, every gap one beyond REAL_HIP_GAP_MAX on either
+            // side, every split one beyond the read, spans that end one before, on and one behind the text's end, a far position
+            const uint64_t n = strtoull(argv[2], 0, 10);
+            const uint32_t lengths[7] = {1, 2, 31, 32, 33, 320, 321};
+            std::string out;
+            char line[96];
+            for (uint32_t L : lengths)
+                for (int g = -17; g <= 17; ++g)
+                    for (uint32_t j = 0; j <= L + 1; ++j)
+                        for (int e = -1; e <= 2; ++e) {
+                            const uint32_t p = e == 2 ? 0xFFFFFF00u : (uint32_t)((int64_t)n + e - (int64_t)L - g);
+                            const RhGapFit f = rh_gap_fit(L, g, j, p, n);
+                            snprintf(line, sizeof line, "%u %d %u %u %u %u %u\n", L, g, j, p, f.fits, f.d, f.del);
+                            out += line;
+                        }
+            fwrite(out.data(), 1, out.size(), stdout);
             return 0;
         }
         if (cmd == "lines" && argc == 4) {

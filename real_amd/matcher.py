@@ -1075,14 +1075,10 @@ class PairMatcher(AllMatcher):
         of the record's target mate that differ from the text and the text bases its deletion skips (base =
         lib.MISMATCH_DELETED) -> (lists as lib.MISMATCH_DTYPE, offsets).  Mates and records as for mismatches_pairs: all host
         arrays, all device tensors, or device reads with numpy records"""
-        host = isinstance(gaps, np.ndarray)
-        if host:
-            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
-        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
-        self.sync_inputs(gaps)
+        b1, b2, gaps = self._gapped_records(mate1, mate2, gaps)
         n = int(b1.n_reads)
         return self._mismatch_call(lambda o, c, no, po: self._L.real_hip_mismatches_gapped(
-            self._h, C.byref(b1), C.byref(b2), _ptr(gaps), o, c, no, po), n, not host, cap or max(1024, 4 * n))
+            self._h, C.byref(b1), C.byref(b2), _ptr(gaps), o, c, no, po), n, not isinstance(gaps, np.ndarray), cap or max(1024, 4 * n))
 
     def gapped_list_stats(self, reset: bool = False) -> dict:
         return self._stats(_lib.RealHipGappedListStats, self._L.real_hip_gapped_list_stats_get, reset)
@@ -1095,11 +1091,7 @@ class PairMatcher(AllMatcher):
     def indel_add(self, mate1, mate2, gaps):
         """real_hip_indel_add: the events of the Unique gapped records among `gaps` (what gap_rescue returned for these mates).
         Mates and records as for mismatches_gapped: all host arrays, all device tensors, or device reads with numpy records"""
-        host = isinstance(gaps, np.ndarray)
-        if host:
-            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
-        b1, b2 = self._mate_batch(mate1, host_records=host), self._mate_batch(mate2, host_records=host)
-        self.sync_inputs(gaps)
+        b1, b2, gaps = self._gapped_records(mate1, mate2, gaps)
         self._check(self._L.real_hip_indel_add(self._h, C.byref(b1), C.byref(b2), _ptr(gaps)))
 
     def indel_finish(self, min_call_qual: int = 20, min_alt: int = 2, min_depth: int = 4):

@@ -183,3 +183,23 @@ def test_final_record_decoders(selftest):
     their ranges -- and against info words as Lines.hpp's unpack reads them (35-bit positions included)."""
     r = subprocess.run([selftest, "records"], stdout=subprocess.PIPE, universal_newlines=True)
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
+
+
+def test_gap_record_geometry_against_the_checkers_rule(selftest):
+    """csrc/final_record.h's rh_gap_fit, the one geometry rule of the stages that consume gap records, against the rule of
+    tests/gapped_list_checker.py over `host_selftest gap_grid`: L in {1, 2, 31, 32, 33, 320, 321}, g in -17 .. 17, every split
+    0 .. L + 1, spans that end one before, on and one behind the text's end, and the position 0xFFFFFF00.  (`host_selftest
+    records` above checks the decoder of the record's fields.)"""
+    import gapped_list_checker as glc
+    n = 100_013
+    r = subprocess.run([selftest, "gap_grid", str(n)], stdout=subprocess.PIPE, universal_newlines=True)
+    assert r.returncode == 0
+    got = np.array([line.split() for line in r.stdout.split("\n")[:-1]], dtype=np.int64)
+    assert got.shape == (sum(L + 2 for L in (1, 2, 31, 32, 33, 320, 321)) * 35 * 4, 7)
+    assert set(got[:, 0]) == {1, 2, 31, 32, 33, 320, 321} and set(got[:, 1]) == set(range(-17, 18)) and (got[:, 3] == 0xFFFFFF00).sum() * 4 == got.shape[0]
+    bad = [row.tolist() for row in got
+           if (bool(row[4]), row[5], row[6]) != (glc.fits({"gap": row[1], "split": row[2], "pos": row[3]}, int(row[0]), n), max(-row[1], 0), max(row[1], 0))]
+    assert not bad, bad[:10]
+    fit = got[got[:, 4] == 1]
+    assert 0 < fit.shape[0] < got.shape[0] // 3 and set(fit[:, 0]) == {1, 2, 31, 32, 33, 320}      # (L = 1 fits without a gap only)
+    assert not fit[fit[:, 0] == 1][:, 1].any() and set(fit[:, 1]) == set(range(-16, 17)) and (fit[:, 3] + fit[:, 0] + fit[:, 1] <= n).all()
