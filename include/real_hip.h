@@ -705,6 +705,16 @@ int real_hip_mismatch_stats_get(real_hip_ctx *ctx, real_hip_mismatch_stats *out,
  * forward mate f is mate 1 iff inverted1 == 0, r is the other one; START = f.pos, END = r.pos + len_r - 1 in 64 bits; KEY =
  * (fileid, inverted1, START, END); the quality of a fragment is qsum1 + qsum2; representative and dup[] as above, one byte
  * per fragment.  Single records of unpaired mates take no part.
+ * SINGLE-END WITH GAPPED PLACEMENTS (real_hip_mark_duplicates_gapped): read i has an info word and a gap record
+ * (real_hip_match_gapped's).  It is PLACED UNGAPPED iff its info word has state 1 or 2 -- the single-end rule, with its END5 and
+ * its reverse bit (state 2).  Otherwise it is PLACED GAPPED iff gaps[i] has state REAL_HIP_PAIR_UNIQUE: the info word wins
+ * where both hold, a NonUnique or NoMatch gap record places nothing.  Of a gapped placement reverse =
+ * REAL_HIP_GAP_INVERTED(tag) and END5 = pos if forward, pos + len + gap - 1 if reverse (len from the summary; gap > 0 is a
+ * deletion, gap < 0 an insertion: len + gap is the span on the text), in 64 bits and then modulo 2^36; the file id is taken
+ * modulo 64.  KEY = (fileid, reverse, END5) is ONE key space for both kinds: a gapped and an ungapped read of one key are one
+ * group.  Representative and dup[] as above.  When no gap record is Unique, dup[] is real_hip_mark_duplicates' bit for bit and
+ * the statistics count the same; placed, groups and duplicates count both kinds.  gaps: host memory, or 16-byte aligned device
+ * memory; NULL with n > 0 or misaligned: REAL_HIP_E_INVALID, nothing launched; 16 more bytes per record when staged.
  * Both: a qsum beyond 2^20 - 1 counts as 2^20 - 1; END5 is taken modulo 2^36 and END modulo 2^33 (summaries of
  * real_hip_read_summary and records of this library's matchers stay inside).  on_device 0: all pointers host memory
  * (copied), 1: all device pointers, dup included (pairs 8-byte, summaries 8-byte aligned).  n == 0 is valid.  NULL arrays
@@ -717,6 +727,9 @@ typedef struct real_hip_read_sum {
 int real_hip_read_summary(real_hip_ctx *ctx, const real_hip_batch *b, uint32_t min_qual, real_hip_read_sum *out);
 int real_hip_mark_duplicates(real_hip_ctx *ctx, const uint64_t *info, const real_hip_read_sum *sum,
                              uint64_t n_reads, int on_device, uint8_t *dup);
+struct real_hip_gap_place; /* (defined below, "gap rescue") */
+int real_hip_mark_duplicates_gapped(real_hip_ctx *ctx, const uint64_t *info, const struct real_hip_gap_place *gaps,
+                                    const real_hip_read_sum *sum, uint64_t n_reads, int on_device, uint8_t *dup);
 int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
                                    const real_hip_read_sum *sum2, uint64_t n_pairs, int on_device, uint8_t *dup);
 /* work of the marking, accumulated since the last reset.  placed, groups and duplicates count the marking calls; launches and

@@ -1,13 +1,15 @@
 // duplicates.hip -- duplicate marking: the placed reads (fragments) grouped by their 5' ends, the copy of the highest quality sum
 // kept, every other one marked (include/real_hip.h, "duplicates").
 //
-// Four kernels and rocPRIM's stable radix sort:
+// Five kernels and rocPRIM's stable radix sort:
 //   read_summary_kernel   one lane per read walks the read's quality bytes in place, an aligned 16-byte chunk per load (rows at
 //                         any byte address, by the rule of read_walk.h's DwordRow) and writes {len, qsum}; a read beyond
 //                         REAL_HIP_MAX_PATL is summed by the whole wave it falls into (ballot, then 64 chunks per step) -- no
 //                         list, no second launch.
 //   dup_key_kernel        one lane per info record: key = fileid:6 | reverse:1 | END5:36 | (2^20 - 1 - qsum):20, value = index;
 //                         an unplaced record gets the all-ones sentinel (bit 63: no placed key has it).
+//   dup_gapped_key_kernel the same key for a read with an info word and a gap record: the info word's placement, else the Unique
+//                         gap record's (END5 over the span len + gap); only an unplaced lane loads its gap record.
 //   dup_pair_key_kernel   one lane per pair record: low word END:33 | (2^21 - 1 - qsum1 - qsum2):21, high word
 //                         unplaced:1 | fileid:8 | inverted1:1 | START:32; two stable passes, low word first (the high words are
 //                         gathered into the first pass' order by dup_gather_kernel in between).
@@ -19,6 +21,7 @@
 // No LDS of our own, no scratch memory, plain C++.
 #include "real_hip_internal.h"
 #include "read_walk.h"
+#include "dup_gapped_stage.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -123,6 +126,7 @@ struct DupArgs {
     uint64_t *key;                 // single-end key / low word of the paired key: what the sort takes
     uint64_t *lo, *hi;             // pairs: the low word once more and the high word, both staying in record order
     uint32_t *val;                 // the record's index
+    const uint4 *gaps;             // dup_gapped_key_kernel: real_hip_gap_place records beside the info words, a uint4 each
 };
 
 __global__ void __launch_bounds__(RH_DUP_BLOCK) dup_key_kernel(const DupArgs A)
@@ -136,6 +140,35 @@ __global__ void __launch_bounds__(RH_DUP_BLOCK) dup_key_kernel(const DupArgs A)
         const uint64_t end5 = (r.inv ? r.pos + s.x - 1 : r.pos) & ((1ull << RH_DUP_E5_BITS) - 1);
         const uint32_t qmax = (1u << RH_DUP_Q_BITS) - 1;
         key = ((((uint64_t)r.file << 1 | (r.inv ? 1u : 0u)) << RH_DUP_E5_BITS | end5) << RH_DUP_Q_BITS) | (qmax - min(s.y, qmax));
+    }
+    A.key[i] = key;
+    A.val[i] = (uint32_t)i;
+}
+
+// The joint key of a read that has an info word and a gap record: the info word's placement where it has one --
+// dup_key_kernel's key, bit for bit --, else the gap record's where that is Unique: END5 = p forward, p + len + g - 1 reverse
+// (len + g is the span on the text), in 64 bits.  Only a lane whose read the matcher did not place loads the gap record, as
+// one 16-byte load; one key space for both kinds, so that the copies of a molecule meet in one group whichever way they were placed.
+__global__ void __launch_bounds__(RH_DUP_BLOCK) dup_gapped_key_kernel(const DupArgs A)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * RH_DUP_BLOCK + threadIdx.x;
+    if (i >= A.n) return;
+    const RhPlace r = rh_place_info(A.info[i]);
+    bool place = r.place, inv = r.inv;
+    uint32_t file = r.file;
+    uint64_t pos = r.pos;
+    int64_t g = 0;
+    if (!place) {
+        const uint4 w = A.gaps[i];
+        const RhGapRecord q = rh_place_gap(w.x, w.y, w.z, w.w);
+        place = q.state == REAL_HIP_PAIR_UNIQUE; inv = q.inv != 0; file = q.file & ((1u << RH_DUP_FI_BITS) - 1); pos = q.p; g = q.g;
+    }
+    uint64_t key = RH_DUP_SENTINEL;
+    if (place) {
+        const uint2 s = A.sum[0][i];
+        const uint64_t end5 = (inv ? pos + s.x + (uint64_t)g - 1 : pos) & ((1ull << RH_DUP_E5_BITS) - 1);
+        const uint32_t qmax = (1u << RH_DUP_Q_BITS) - 1;
+        key = ((((uint64_t)file << 1 | (inv ? 1u : 0u)) << RH_DUP_E5_BITS | end5) << RH_DUP_Q_BITS) | (qmax - min(s.y, qmax));
     }
     A.key[i] = key;
     A.val[i] = (uint32_t)i;
@@ -222,13 +255,12 @@ int rh_launch_read_summary(real_hip_ctx *ctx, const DevBatch &b, uint32_t min_qu
     return REAL_HIP_OK;
 }
 
-// dup[i] of n records, all arrays on the device: info and sum1 (single-end), or pairs, sum1 and sum2; asynchronous
-int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_pair *d_pairs, const real_hip_read_sum *d_sum1,
-                              const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup)
+// The tail every marking shares: the buffers, `key_kernel` over K's records (K.n, K.key, K.lo, K.hi and K.val are set here), the
+// sort -- pairs: low word, gather, high word -- and the marks into d_dup; asynchronous
+static int dup_sort_mark(real_hip_ctx *ctx, DupArgs K, void (*key_kernel)(const DupArgs), bool pairs, uint64_t n, uint8_t *d_dup)
 {
     if (!n) return REAL_HIP_OK;
     if (n > (1ull << 32)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: more than 2^32 records in one call", hipSuccess);
-    const bool pairs = d_pairs != nullptr;
     int rc;
     if ((rc = rh_stats_reserve(ctx, ctx->dup.stats, RH_PAIR_STRIPES, 0))) return rc;
     for (int k = 0; k < 2; ++k) {
@@ -246,15 +278,11 @@ int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const r
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
     RH_HIP(ctx, hipMemsetAsync(d_dup, 0, (size_t)n, ctx->stream));
 
-    DupArgs K;
-    memset(&K, 0, sizeof K);
-    K.info = d_info; K.pairs = (const uint2 *)d_pairs; K.sum[0] = (const uint2 *)d_sum1; K.sum[1] = (const uint2 *)d_sum2;
     K.n = n; K.key = keys.current(); K.lo = (uint64_t *)ctx->dup_lo.p; K.hi = (uint64_t *)ctx->dup_hi.p; K.val = vals.current();
     const dim3 grid = dup_grid(n), block(RH_DUP_BLOCK);
     uint64_t launches = 0;
     rh_time_begin(ctx, ctx->stream, ctx->dup); // (no return inside the bracket: a failing step is reported behind rh_time_end)
-    if (pairs) hipLaunchKernelGGL(dup_pair_key_kernel, grid, block, 0, ctx->stream, K);
-    else hipLaunchKernelGGL(dup_key_kernel, grid, block, 0, ctx->stream, K);
+    hipLaunchKernelGGL(key_kernel, grid, block, 0, ctx->stream, K);
     hipError_t e = hipGetLastError();
     ++launches;
     if (e == hipSuccess) { e = rocprim::radix_sort_pairs(ctx->sort_tmp.p, tmp, keys, vals, (size_t)n, 0u, bits0, ctx->stream); ++launches; }
@@ -286,6 +314,27 @@ int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const r
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "duplicates: key / sort / mark", e);
     ctx->dup.items += n;
     return REAL_HIP_OK;
+}
+
+// dup[i] of n records, all arrays on the device: info and sum1 (single-end), or pairs, sum1 and sum2; asynchronous
+int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_pair *d_pairs, const real_hip_read_sum *d_sum1,
+                              const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup)
+{
+    const bool pairs = d_pairs != nullptr;
+    DupArgs K;
+    memset(&K, 0, sizeof K);
+    K.info = d_info; K.pairs = (const uint2 *)d_pairs; K.sum[0] = (const uint2 *)d_sum1; K.sum[1] = (const uint2 *)d_sum2;
+    return dup_sort_mark(ctx, K, pairs ? dup_pair_key_kernel : dup_key_kernel, pairs, n, d_dup);
+}
+
+// the same over info words AND gap records (dup_gapped_stage.h): one key space, one sort, one marking
+int rh_launch_mark_duplicates_gapped(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_gap_place *d_gaps, const real_hip_read_sum *d_sum,
+                                     uint64_t n, uint8_t *d_dup)
+{
+    DupArgs K;
+    memset(&K, 0, sizeof K);
+    K.info = d_info; K.gaps = (const uint4 *)d_gaps; K.sum[0] = (const uint2 *)d_sum;
+    return dup_sort_mark(ctx, K, dup_gapped_key_kernel, false, n, d_dup);
 }
 
 int rh_dup_stats(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset)

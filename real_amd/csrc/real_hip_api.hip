@@ -2,7 +2,7 @@
 // launches.  No CPU fallback: every entry point either runs the HIP path or fails.
 #include "real_hip_internal.h"
 #include "pair_state.h"
-#include "ctx_side.h" // the stages' state beside the ctx: mapq_stage.h, gap_stage.h, indel_stage.h, pileup_gapped_stage.h
+#include "ctx_side.h" // the stages' state beside the ctx: mapq_stage.h, gap_stage.h, indel_stage.h, pileup_gapped_stage.h, dup_gapped_stage.h
 #include "side_table.h"
 
 #include <chrono>
@@ -1868,23 +1868,28 @@ extern "C" int real_hip_read_summary(real_hip_ctx *ctx, const real_hip_batch *b,
     return rh_sync_tail(ctx, rc);
 }
 
-static int mark_duplicates_run(real_hip_ctx *ctx, const uint64_t *info, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
-                               const real_hip_read_sum *sum2, uint64_t n, int on_device, uint8_t *dup)
+// gaps (nullable): the reads' gap records beside their info words -- the joint marking (dup_gapped_stage.h)
+static int mark_duplicates_run(real_hip_ctx *ctx, const uint64_t *info, const real_hip_pair *pairs, const real_hip_gap_place *gaps,
+                               const real_hip_read_sum *sum1, const real_hip_read_sum *sum2, uint64_t n, int on_device, uint8_t *dup)
 {
     if (n > (1ull << 32)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: more than 2^32 records in one call", hipSuccess);
     if (!n) return REAL_HIP_OK;
     if ((!info && !pairs) || !sum1 || (pairs && !sum2) || !dup) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null records / summaries / dup", hipSuccess);
     if (on_device && (((uintptr_t)info | (uintptr_t)pairs | (uintptr_t)sum1 | (uintptr_t)sum2) & 7u))
         return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: records and summaries must be 8-byte aligned", hipSuccess);
+    if (on_device && ((uintptr_t)gaps & 15u)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: gap records must be 16-byte aligned", hipSuccess);
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     const uint64_t *d_info = info;
     const real_hip_pair *d_pairs = pairs;
+    const real_hip_gap_place *d_gaps = gaps;
     const real_hip_read_sum *d_sum[2] = {sum1, sum2};
     uint8_t *d_dup = dup;
     int rc = info ? io.in(ctx->dup_rec, info, n, d_info) : io.in(ctx->dup_rec, pairs, n, d_pairs);
+    if (!rc && gaps) rc = io.in(rh_dup_gapped_stage(ctx).rec, gaps, n, d_gaps);
     for (int m = 0; m < (pairs ? 2 : 1) && !rc; ++m) rc = io.in(ctx->dup_sum[m], m ? sum2 : sum1, n, d_sum[m]);
     if (!rc) rc = io.inout(ctx->dup_out, dup, n, true, d_dup);
-    if (!rc) rc = rh_launch_mark_duplicates(ctx, d_info, d_pairs, d_sum[0], d_sum[1], n, d_dup);
+    if (!rc) rc = gaps ? rh_launch_mark_duplicates_gapped(ctx, d_info, d_gaps, d_sum[0], n, d_dup)
+                       : rh_launch_mark_duplicates(ctx, d_info, d_pairs, d_sum[0], d_sum[1], n, d_dup);
     if (!rc) rc = io.back(dup, d_dup, n, "download of the duplicate marks");
     return rh_sync_tail(ctx, rc);
 }
@@ -1894,7 +1899,15 @@ extern "C" int real_hip_mark_duplicates(real_hip_ctx *ctx, const uint64_t *info,
 {
     RH_ENTER(ctx);
     if (n_reads && !info) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null info", hipSuccess);
-    return mark_duplicates_run(ctx, info, nullptr, sum, nullptr, n_reads, on_device, dup);
+    return mark_duplicates_run(ctx, info, nullptr, nullptr, sum, nullptr, n_reads, on_device, dup);
+}
+
+extern "C" int real_hip_mark_duplicates_gapped(real_hip_ctx *ctx, const uint64_t *info, const real_hip_gap_place *gaps,
+                                               const real_hip_read_sum *sum, uint64_t n_reads, int on_device, uint8_t *dup)
+{
+    RH_ENTER(ctx);
+    if (n_reads <= (1ull << 32) && n_reads && (!info || !gaps)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null info / gap records", hipSuccess);
+    return mark_duplicates_run(ctx, info, nullptr, gaps, sum, nullptr, n_reads, on_device, dup);
 }
 
 extern "C" int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_pair *pairs, const real_hip_read_sum *sum1,
@@ -1902,7 +1915,7 @@ extern "C" int real_hip_mark_duplicates_pairs(real_hip_ctx *ctx, const real_hip_
 {
     RH_ENTER(ctx);
     if (n_pairs && !pairs) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: null pairs", hipSuccess);
-    return mark_duplicates_run(ctx, nullptr, pairs, sum1, sum2, n_pairs, on_device, dup);
+    return mark_duplicates_run(ctx, nullptr, pairs, nullptr, sum1, sum2, n_pairs, on_device, dup);
 }
 
 extern "C" int real_hip_dup_stats_get(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset)

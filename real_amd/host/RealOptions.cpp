@@ -73,7 +73,10 @@ void RealOptions::printHelp() const
               << "   POS, the CIGAR with its insertion or deletion (40M2D60M), NM:i, MD:Z (40^AC60) and ZC:i:<cost>, MAPQ 255; its mate's line\n"
               << "   names it (RNEXT, PNEXT, TLEN over the span on the text, FLAG 32), and both carry FLAG 2 if the outer distance lies in\n"
               << "   -insert_min .. -insert_max; the rescue then runs with the -sam pass, once; the -gapped file is unchanged; a summary line\n"
-              << "   goes to standard error; default=0: the -sam file is what it is without -gapped>\n"
+              << "   goes to standard error; default=0: the -sam file is what it is without -gapped.  WITHOUT -p2 (it then needs -sam and\n"
+              << "   -gapped_single): a read -gapped_single places uniquely is written as placed, in the pass of its genome file: FLAG 0 / 16\n"
+              << "   (+ 1024 with -dedup 1 if marked), POS, CIGAR, MAPQ 255, NM:i, MD:Z, ZC:i:<cost>; every other line and the -gapped_single\n"
+              << "   file are unchanged; the gapped pass then runs before the -sam pass>\n"
               << "-insert_hist <file: with -p2, receives the histogram of the outer distances of the Unique fragments (after the last\n"
               << "   genome file) as lines outer<TAB>count, the last bin (-insert_max + 1) holding what lies beyond; the quartiles go to\n"
               << "   standard error; -o is unchanged; not with -pairs_all 1>\n"
@@ -95,8 +98,11 @@ void RealOptions::printHelp() const
               << "   deletion are piled up too: in the pileup pass of a genome file, behind the ungapped placements, the reads once more through\n"
               << "   the gap rescue (-gap_* apply; it runs once per run, -vcf_indels 1, -gapped and -sam_gapped 1 find its records); depth and\n"
               << "   mismatch counts on the aligned positions, none on the deleted ones; with -vcf the same mates count as evidence at the\n"
-              << "   sites; the indel lines of -vcf_indels 1 do not change; -dedup and -pileup_minmapq do NOT apply to gapped placements (they\n"
-              << "   carry no duplicate mark and their MAPQ is 255); a summary line per genome file goes to standard error, default=0>\n"
+              << "   sites; the indel lines of -vcf_indels 1 do not change; with -p2, -dedup and -pileup_minmapq do NOT apply to gapped placements\n"
+              << "   (they carry no duplicate mark and their MAPQ is 255); a summary line per genome file goes to standard error, default=0.\n"
+              << "   WITHOUT -p2 (it then needs -gapped_single): the single reads -gapped_single places uniquely are piled up and counted as\n"
+              << "   evidence the same way, from the records of the gapped pass, which then runs before the pileup; -dedup 1 DOES apply (gapped\n"
+              << "   and ungapped reads of one 5' end are marked together), -pileup_minmapq does not (their MAPQ is 255)>\n"
               << "-vcf <file: after the pileup of a genome file (it runs also without -pileup; -pileup_minq then applies to it), call SNPs at\n"
               << "   its sites: the reads once more, bases of quality >= -pileup_minq counted per site, ten genotype likelihoods in integers,\n"
               << "   VCF 4.2 with GT:GQ:DP:AD; same conditions as -pileup; -dedup 1 leaves the duplicates out; indels only with -vcf_indels 1, one sample>\n"
@@ -106,7 +112,8 @@ void RealOptions::printHelp() const
               << "   runs once per run, -gapped and -sam_gapped 1 find its records), and the insertions and deletions the rescued mates show,\n"
               << "   left-aligned, added up and genotyped on the device; their lines (INFO DP;INDEL;SF;SR) are merged into the -vcf file by\n"
               << "   position; -vcf_minqual and -vcf_mindepth apply; -dedup and -pileup_minmapq do NOT reach the rescued mates; a summary line\n"
-              << "   per genome file goes to standard error, default=0>\n"
+              << "   per genome file goes to standard error, default=0.  WITHOUT -p2 (it then needs -gapped_single): the insertions and\n"
+              << "   deletions of the single reads -gapped_single places uniquely are called the same way; -dedup 1 leaves the marked ones out>\n"
               << "-vcf_minalt <N: with -vcf_indels 1, an indel call needs N rescued mates that show it, default=2>\n"
               << "-sam <file: after the output pass, write EVERY read as a SAM line (header: one @SQ per fragment of every genome file): a\n"
               << "   finally placed read with FLAG, RNAME, 1-based POS, MAPQ 255 (-mapq 1: 0..60), CIGAR <length>M, the sequence as placed, and NM:i / MD:Z from\n"
@@ -318,12 +325,13 @@ RealOptions::RealOptions(int argc, char *argv[])
     }
     if (vcf_indels) { // indel calls: loud errors before anything runs
         if (!vcf_given) throw std::runtime_error("-vcf_indels 1 writes its calls into the -vcf file: it needs -vcf.");
-        if (pattern2filename.empty()) throw std::runtime_error("-vcf_indels 1 calls the indels of gap-rescued mates: it is only meaningful with -p2 (paired-end reads).");
+        if (pattern2filename.empty() && !gapped_single_given)
+            throw std::runtime_error("-vcf_indels 1 calls the indels of gap-rescued mates with -p2 (paired-end reads); without -p2 it calls those of the single reads -gapped_single places: it needs -gapped_single.");
         if (vcf_minalt > 0xfffffffful) throw std::runtime_error("-vcf_minalt takes a number below 2^32.");
     }
     if (pileup_gapped) { // gapped placements in the pileup: loud errors before anything runs
-        if (pattern2filename.empty())
-            throw std::runtime_error("-pileup_gapped 1 piles up the mates the gap rescue places: it needs -p2 (paired-end reads); the single-end drivers are not there yet.");
+        if (pattern2filename.empty() && !gapped_single_given)
+            throw std::runtime_error("-pileup_gapped 1 piles up the mates the gap rescue places with -p2 (paired-end reads); without -p2 it needs -gapped_single: without it the single-end drivers are not there yet, nothing places a single read with a gap.");
         if (!pileup_given && !pileup_depth_given && !vcf_given) throw std::runtime_error("-pileup_gapped 1 needs one of -pileup / -pileup_depth / -vcf.");
         if (pairs_all) throw std::runtime_error("-pileup_gapped 1 cannot be combined with -pairs_all 1.");
     }
@@ -348,9 +356,10 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (pileup_minmapq < 0 || pileup_minmapq > (long)REAL_HIP_MAPQ_MAX) throw std::runtime_error("-pileup_minmapq must be in 0..60.");
     }
     if (sam_gapped) { // the rescued mates in the -sam file: loud errors before anything runs
-        if (pattern2filename.empty()) throw std::runtime_error("-sam_gapped 1 is only meaningful with -p2 (paired-end reads).");
+        if (pattern2filename.empty() && !gapped_single_given)
+            throw std::runtime_error("-sam_gapped 1 writes the mates the gap rescue places with -p2 (paired-end reads); without -p2 it writes the single reads -gapped_single places: it needs -gapped_single.");
         if (!sam_given) throw std::runtime_error("-sam_gapped 1 writes the rescued mates into the -sam file: it needs -sam.");
-        if (!gapped_given) throw std::runtime_error("-sam_gapped 1 writes the mates the gap rescue places: it needs -gapped.");
+        if (!pattern2filename.empty() && !gapped_given) throw std::runtime_error("-sam_gapped 1 writes the mates the gap rescue places: it needs -gapped.");
         if (pairs_all) throw std::runtime_error("-sam_gapped 1 cannot be combined with -pairs_all 1.");
     }
     if (gapped_given) { // gap rescue: loud errors before anything runs
@@ -385,7 +394,7 @@ RealOptions::RealOptions(int argc, char *argv[])
         if (gap_flank < 1) throw std::runtime_error("-gap_flank must be at least 1.");
         if (gap_maxcost < 0) gap_maxcost = 4 * (long)totalkmax + 6 + (long)gap_max;
         if (gap_maxcost > 65534 || gap_margin > 65535) throw std::runtime_error("-gap_maxcost takes at most 65534, -gap_margin at most 65535.");
-        if ((gapped_given || vcf_indels || pileup_gapped) && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
+        if (!pattern2filename.empty() && (gapped_given || vcf_indels || pileup_gapped) && insert_max > REAL_HIP_MATE_SEARCH_MAX_INSERT)
             throw std::runtime_error(std::string(gapped_given ? "-gapped" : vcf_indels ? "-vcf_indels 1" : "-pileup_gapped 1") + " takes an -insert_max of at most " + std::to_string(REAL_HIP_MATE_SEARCH_MAX_INSERT) + ".");
     } else if (gap_flags_given) {
         throw std::runtime_error("-gap_max / -gap_flank / -gap_maxcost / -gap_margin need -gapped (with -p2) or -gapped_single.");

@@ -27,6 +27,8 @@
 //       names.txt (a fragment name per line), calls.bin (real_hip_call records) and indels.bin (real_hip_indel records), through Vcf.hpp
 //   host_selftest vcf_indel_options <args...>     -> prints the parsed -vcf_indels flag (0|1), -vcf_minalt, -vcf_minqual, -vcf_mindepth
 //   host_selftest pileup_gapped_options <args...> -> prints the parsed -pileup_gapped flag (0|1), -gap_max, -gap_flank
+//   host_selftest single_gapped_options <args...> -> prints the parsed -sam_gapped, -vcf_indels, -pileup_gapped and -dedup flags (0|1) and the
+//                                                    -gapped_single file ("." if none): the single-end consumers of the gap records
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -497,6 +499,12 @@ int main(int argc, char **argv)
         if (cmd == "pileup_gapped_options") { // -pileup_gapped
             RealOptions o(argc - 1, argv + 1);
             std::cout << (o.pileup_gapped ? 1 : 0) << " " << o.gap_max << " " << o.gap_flank << "\n";
+            return 0;
+        }
+        if (cmd == "single_gapped_options") { // -sam_gapped / -vcf_indels / -pileup_gapped without -p2
+            RealOptions o(argc - 1, argv + 1);
+            std::cout << (o.sam_gapped ? 1 : 0) << " " << (o.vcf_indels ? 1 : 0) << " " << (o.pileup_gapped ? 1 : 0) << " " << (o.dedup ? 1 : 0) << " "
+                      << (o.gappedsinglefilename.empty() ? "." : o.gappedsinglefilename) << "\n";
             return 0;
         }
         if (cmd == "vcf_indel_options") { // -vcf_indels, -vcf_minalt

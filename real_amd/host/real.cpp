@@ -795,45 +795,70 @@ void reportMapq(real_hip_ctx *h, const std::vector<uint8_t> &mapq)
 // time for the ids: one line per Unique record, in read order, and the summary line on standard error.  eligible is the
 // run's (the info words are final: it is the same in every block); anchored and crowded add up over the blocks -- a read
 // counts once per block that anchors it; placed, unique and gapped count the final records.
+// The pass has two halves.  The MATCHING half leaves the run's gap records; the WRITING half writes the file and the summary line.
+// Without a consumer of the records both run here, on the pass's own context.  With one (-sam_gapped 1, -vcf_indels 1,
+// -pileup_gapped 1 without -p2) the matching half runs behind "All done." on the matching contexts, before the
+// marks of -dedup and the pileup and SAM passes, which read its records; the writing half stays here.
 real_hip_gap_params gapParams(const RealOptions &o);
-void gapSinglePass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, int qoff, const std::vector<uint64_t> &info,
-                   uint64_t numpat)
+inline real_hip_gap_place noGapRecord()
 {
-    if (!o.gapped_single_given) return;
-    OutFile out(o.gappedsinglefilename, false, "-gapped_single");
+    real_hip_gap_place none;
+    memset(&none, 0, sizeof none);
+    none.second = REAL_HIP_GAP_NONE;
+    return none;
+}
+struct GapSingleRun {
+    std::vector<real_hip_gap_place> gaps; // one record per read, from the matching half on
+    uint64_t eligible = 0, anchored = 0, crowded = 0;
+    bool matched = false;
+};
+// the matching half: every genome file and index block on the contexts gc (item g of a round on context g, as in the matching passes)
+void gapSingleMatch(const RealOptions &o, CtxVec &gc, const std::vector<std::string> &files, Timers &T, int qoff, const std::vector<uint64_t> &info, uint64_t numpat,
+                    GapSingleRun &run)
+{
     const real_hip_gap_params gp = gapParams(o);
     real_hip_gap_anchor_params ap;
     memset(&ap, 0, sizeof ap);
     ap.struct_size = sizeof ap; ap.anchor_len = (uint32_t)o.gap_anchor; ap.max_anchors = (uint32_t)o.gap_anchors;
-    real_hip_gap_place none;
-    memset(&none, 0, sizeof none);
-    none.second = REAL_HIP_GAP_NONE;
-    std::vector<real_hip_gap_place> gaps(numpat, none);
-    double t0 = now_s();
-    CtxVec gc = makeContexts(o, 1);
-    T.index += now_s() - t0;
-    real_hip_ctx *h = gc[0]->h;
-    uint64_t eligible = 0, anchored = 0, crowded = 0, placed = 0, unique = 0, gapped = 0;
+    run.gaps.assign(numpat, noGapRecord());
     bool first = true;
     for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, gc, files, fi, 0, T, nullptr, [&](Resident &) {
         const uint64_t seen = streamReads(o, gc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
-            for (const ReadItem &it : items) {
-                if (!it.batch.n_reads) continue;
+            const double tm = now_s();
+            onEach(items.size(), [&](size_t g) {
+                const ReadItem &it = items[g];
+                if (!it.batch.n_reads) return;
                 if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
-                const double tm = now_s();
-                check(h, real_hip_match_gapped(h, &gp, &ap, &it.batch, info.data() + it.first_id, first ? 1 : 0, gaps.data() + it.first_id), "real_hip_match_gapped");
-                T.match += now_s() - tm;
-            }
+                check(gc[g]->h, real_hip_match_gapped(gc[g]->h, &gp, &ap, &it.batch, info.data() + it.first_id, first ? 1 : 0, run.gaps.data() + it.first_id), "real_hip_match_gapped");
+            });
+            T.match += now_s() - tm;
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
-        real_hip_gap_anchor_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
-        check(h, real_hip_gap_anchor_stats_get(h, &st, 1), "real_hip_gap_anchor_stats_get");
-        if (first) eligible = st.eligible;
-        anchored += st.eligible - st.skipped - st.crowded - st.unanchored; crowded += st.crowded;
+        uint64_t eligible = 0;
+        for (auto &c : gc) {
+            real_hip_gap_anchor_stats st;
+            memset(&st, 0, sizeof st);
+            st.struct_size = sizeof st;
+            check(c->h, real_hip_gap_anchor_stats_get(c->h, &st, 1), "real_hip_gap_anchor_stats_get");
+            eligible += st.eligible;
+            run.anchored += st.eligible - st.skipped - st.crowded - st.unanchored; run.crowded += st.crowded;
+        }
+        if (first) run.eligible = eligible;
         first = false;
     });
+    run.matched = true;
+}
+void gapSinglePass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, int qoff, const std::vector<uint64_t> &info,
+                   uint64_t numpat, GapSingleRun &run)
+{
+    if (!o.gapped_single_given) return;
+    OutFile out(o.gappedsinglefilename, false, "-gapped_single");
+    double t0 = now_s();
+    CtxVec gc = makeContexts(o, 1);
+    T.index += now_s() - t0;
+    if (!run.matched) gapSingleMatch(o, gc, files, T, qoff, info, numpat, run);
+    const std::vector<real_hip_gap_place> &gaps = run.gaps;
+    uint64_t placed = 0, unique = 0, gapped = 0;
     const uint64_t seen = streamReads(o, gc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
         for (const ReadItem &it : items) {
             const ReadSource src = it.src;
@@ -864,7 +889,7 @@ void gapSinglePass(const RealOptions &o, const std::vector<std::string> &files, 
         const unsigned st = REAL_HIP_GAP_STATE(g.tag);
         placed += st != REAL_HIP_PAIR_NOMATCH; unique += st == REAL_HIP_PAIR_UNIQUE; gapped += st != REAL_HIP_PAIR_NOMATCH && g.gap != 0;
     }
-    std::cerr << "gap single: eligible=" << eligible << " anchored=" << anchored << " crowded=" << crowded << " placed=" << placed << " unique=" << unique
+    std::cerr << "gap single: eligible=" << run.eligible << " anchored=" << run.anchored << " crowded=" << run.crowded << " placed=" << placed << " unique=" << unique
               << " gapped=" << gapped << std::endl;
 }
 
@@ -920,12 +945,27 @@ int matchUnique(const RealOptions &o)
         std::cerr << std::endl;
     });
     std::cerr << "All done." << std::endl;
+    // the consumers of the gap records (single-end here: RealOptions has sorted out -p2, and each of them needs -gapped_single): with
+    // one of them the matching half of the gapped pass runs now, on the matching contexts -- the only ones that hold an index
+    const bool consumers = o.sam_gapped || o.vcf_indels || o.pileup_gapped;
+    GapSingleRun gap_run;
+    if (consumers) gapSingleMatch(o, ctx, files, T, qoff, info, numpat, gap_run);
+    const std::vector<real_hip_gap_place> &gaps = gap_run.gaps;
     if (o.dedup) {
         dup.assign(numpat, 0);
         const double tm = now_s();
-        check(ctx[0]->h, real_hip_mark_duplicates(ctx[0]->h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
+        if (consumers) // gapped and ungapped reads of one 5' end are one molecule's copies: one key space, one sort
+            check(ctx[0]->h, real_hip_mark_duplicates_gapped(ctx[0]->h, info.data(), gaps.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_gapped");
+        else
+            check(ctx[0]->h, real_hip_mark_duplicates(ctx[0]->h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
         T.match += now_s() - tm;
         reportDuplicates(ctx[0]->h, o);
+        if (consumers) {
+            uint64_t placements = 0, marked = 0;
+            for (uint64_t i = 0; i < numpat; ++i)
+                if (REAL_HIP_GAP_STATE(gaps[i].tag) == REAL_HIP_PAIR_UNIQUE) { ++placements; marked += dup[i] != 0; }
+            fprintf(stderr, "duplicates gapped: placements=%llu duplicates=%llu\n", (unsigned long long)placements, (unsigned long long)marked);
+        }
     }
     if (o.mapq) {
         mapq.assign(numpat, REAL_HIP_MAPQ_NONE);
@@ -964,6 +1004,8 @@ int matchUnique(const RealOptions &o)
     std::cerr << "unique: " << unique << std::endl; // :1488
     if (passesBehindOutput(o)) ctx.clear(); // (the matching contexts go before the pass's own one comes)
     std::vector<uint64_t> kept; // -dedup / -pileup_minmapq: a batch's records without what they leave out
+    std::vector<real_hip_gap_place> kept_gaps; // -dedup: a batch's gap records without the marked ones (-pileup_minmapq masks info words only)
+    const real_hip_gap_place no_gap = noGapRecord();
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
         const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
@@ -974,7 +1016,24 @@ int matchUnique(const RealOptions &o)
             }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
-    }, [](CtxVec &, unsigned, GapLeg) {}); // (-vcf_indels and -pileup_gapped need -p2: RealOptions refuses them here)
+    }, [&](CtxVec &pc, unsigned, GapLeg leg) { // (-pileup_gapped 1, -vcf_indels 1: the batch given as both mates, its gap records from the matching half)
+        real_hip_ctx *h = pc[0]->h;
+        const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
+            for (const ReadItem &it : items) {
+                const uint64_t n = it.batch.n_reads;
+                if (!n) continue;
+                if (it.first_id + n > numpat) throw std::runtime_error("the read file changed between two passes");
+                const real_hip_gap_place *g = withoutDuplicates(gaps, dup, it.first_id, n, kept_gaps, [&](real_hip_gap_place &r) { r = no_gap; });
+                const double tm = now_s();
+                if (leg == kGapPileup) check(h, real_hip_pileup_add_gapped(h, &it.batch, &it.batch, g), "real_hip_pileup_add_gapped");
+                else if (leg == kGapCalls) check(h, real_hip_call_add_gapped(h, &it.batch, &it.batch, g), "real_hip_call_add_gapped");
+                else check(h, real_hip_indel_add(h, &it.batch, &it.batch, g), "real_hip_indel_add");
+                T.match += now_s() - tm;
+            }
+        });
+        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+    });
+    GappedLists GL; // -sam_gapped 1: the lists of the reads the gapped pass placed
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
         const uint64_t seen = streamReads(o, sc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
             for (const ReadItem &it : items) {
@@ -983,19 +1042,35 @@ int matchUnique(const RealOptions &o)
                 if (base + n > numpat) throw std::runtime_error("the read file changed between two passes");
                 const double tm = now_s();
                 L.fill(sc[0]->h, "real_hip_mismatches", n, real_hip_mismatches, &it.batch, (const uint64_t *)info.data() + base);
+                if (o.sam_gapped) GL.fill(sc[0]->h, n, &it.batch, &it.batch, gaps.data() + base);
                 T.match += now_s() - tm;
                 const ReadSource src = it.src.withQuality(o.fastq, qoff);
                 formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
                     SamPlace at = samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f);
                     at.duplicate = o.dedup && dup[base + i];
                     if (o.mapq) at.mapq = mapq[base + i];
+                    if (o.sam_gapped && !at.placed && REAL_HIP_GAP_STATE(gaps[base + i].tag) == REAL_HIP_PAIR_UNIQUE) {
+                        // placed by its gap record: a line as placed in the pass of the RECORD's file, and none as unplaced in the last one
+                        const real_hip_gap_place &g = gaps[base + i];
+                        if (g.fileid != fi) return;
+                        const ReadView r = src[i];
+                        char cigar[48] = "*";
+                        real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
+                        SamPlace p = samPlaceGapped(g, r.patl, cigar);
+                        p.duplicate = at.duplicate;
+                        appendSam(s, r, refs, p, nullptr, 0, 0, GL.mm.data() + GL.off[i], GL.off[i + 1] - GL.off[i], o.scores);
+                        return;
+                    }
                     appendSamRead(s, src[i], refs, at, fi, last, L.mm.data() + L.off[i], L.off[i + 1] - L.off[i], o.scores);
                 });
             }
         });
         if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
-    gapSinglePass(o, files, RS, T, qoff, info, numpat);
+    if (o.sam_gapped)
+        fprintf(stderr, "sam gapped: reads=%llu deleted=%llu inserted=%llu disagree=%llu\n", (unsigned long long)GL.mates, (unsigned long long)GL.deleted,
+                (unsigned long long)GL.inserted, (unsigned long long)GL.disagree);
+    gapSinglePass(o, files, RS, T, qoff, info, numpat, gap_run);
     T.finish(numpat, unique);
     return EXIT_SUCCESS;
 }

@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "real_hip_indel_begin", "real_hip_indel_add", "real_hip_indel_finish", "real_hip_indel_events", "real_hip_indel_calls",
     "real_hip_indel_end", "real_hip_indel_stats_get",
     "real_hip_pileup_add_gapped", "real_hip_call_add_gapped", "real_hip_pileup_depth_gapped", "real_hip_pileup_gapped_stats_get",
+    "real_hip_mark_duplicates_gapped",
     "real_hip_parse_reads", "real_hip_download", "real_hip_counters_get", "real_hip_kernel_time", "real_hip_timing_enable",
 ]
 
@@ -403,6 +404,7 @@ def load():
     L.real_hip_read_summary.argtypes = [vp, batch, u32, vp]
     L.real_hip_mark_duplicates.argtypes = [vp, vp, vp, u64, ci, vp]
     L.real_hip_mark_duplicates_pairs.argtypes = [vp, vp, vp, vp, u64, ci, vp]
+    L.real_hip_mark_duplicates_gapped.argtypes = [vp, vp, vp, vp, u64, ci, vp]
     L.real_hip_dup_stats_get.argtypes = [vp, C.POINTER(RealHipDupStats), ci]
     L.real_hip_mapq_acc_merge.argtypes = [vp, vp]
     L.real_hip_mapq_of.argtypes = [vp, C.c_int32, C.POINTER(ci)]

@@ -762,6 +762,21 @@ class HipMatcher:
         of match_unique (numpy uint64, or a device tensor of n 64-bit words), sums: what read_summary returned for them"""
         return self._mark_call(self._L.real_hip_mark_duplicates, info, [sums], np.uint64)
 
+    def mark_duplicates_gapped(self, info, gaps, sums):
+        """real_hip_mark_duplicates_gapped: the joint marking of a single-end run -- read i is placed by its info word or, where
+        that places nothing, by its Unique gap record (match_gapped's), and both kinds meet in one group per 5' end.  info and
+        sums as for mark_duplicates, gaps as lib.GAP_PLACE_DTYPE (or a device tensor holding the 16-byte records, first
+        dimension n): all numpy or all device tensors"""
+        host = isinstance(info, np.ndarray)
+        if host != isinstance(gaps, np.ndarray):
+            raise ValueError("info words and gap records live on one side: all numpy or all device tensors")
+        if host:
+            gaps = np.ascontiguousarray(gaps, dtype=_lib.GAP_PLACE_DTYPE)
+        if int(gaps.shape[0]) != int(info.shape[0]):
+            raise ValueError("one gap record per info word")
+        self.sync_inputs(gaps)
+        return self._mark_call(lambda h, rec, *rest: self._L.real_hip_mark_duplicates_gapped(h, rec, _ptr(gaps), *rest), info, [sums], np.uint64)
+
     def mark_duplicates_pairs(self, pairs, sums1, sums2):
         """real_hip_mark_duplicates_pairs: one byte per fragment; pairs as lib.PAIR_DTYPE (or a device tensor holding the
         records, first dimension n), sums1 / sums2 the two mates' summaries"""
