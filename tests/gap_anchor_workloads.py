@@ -45,13 +45,15 @@ def default_params(patl=100, **kw):
     return gc.default_params(1 if patl <= 33 else TOTALKMAX, **kw)
 
 
-def workload(seed=1, patl=100, prm=None, n=150, size=150_000, per_class=PER_CLASS, fileid=0, classes=CLASSES):
-    """{g: synth.Genome, b: Batch, plants: [dict], prm, patl, fileid, seedl}"""
+def workload(seed=1, patl=100, prm=None, n=150, size=150_000, per_class=PER_CLASS, fileid=0, classes=CLASSES,
+             seedl=None, qual=None, n_frag=6, n_runs=4):
+    """{g: synth.Genome, b: Batch, plants: [dict], prm, patl, fileid, seedl}; seedl: the seed length of the run (None: seedl_of
+    the read length), qual: Batch's quality generator, n_frag / n_runs: the text's fragments and N runs"""
     from real_amd import synth
     prm = prm or default_params(patl)
     G, m = prm.max_gap, prm.min_flank
     rng = np.random.default_rng(seed)
-    g = synth.random_genome(size, seed + 11, n_frag=6, n_runs=4)
+    g = synth.random_genome(size, seed + 11, n_frag=n_frag, n_runs=n_runs)
     sym, fstart = g.sym, [int(x) for x in g.frag_start]
     busy = sym > 3
     for c in fstart[1:-1]:
@@ -146,7 +148,7 @@ def workload(seed=1, patl=100, prm=None, n=150, size=150_000, per_class=PER_CLAS
             a[5] = 4                                                        # a read the matcher and the stage skip: a symbol > 3
         reads.append(a)
     ids = ["r%d" % i for i in range(len(reads))]
-    return dict(g=g2, b=Batch(reads, ids), plants=plants, prm=prm, patl=patl, fileid=fileid, seedl=seedl_of(patl))
+    return dict(g=g2, b=Batch(reads, ids, qual), plants=plants, prm=prm, patl=patl, fileid=fileid, seedl=seedl or seedl_of(patl))
 
 
 def intended(plant, rec, w):

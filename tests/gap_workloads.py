@@ -30,9 +30,16 @@ SEEDL, TOTALKMAX = 32, 3
 
 class Batch:
     """a ragged batch of reads: what synth.ReadBatch holds of it"""
-    def __init__(self, reads, ids=None):
+    def __init__(self, reads, ids=None, qual=None):
+        """qual: None (35 per base), a callable length -> the qualities of one read, asked read by read, or the concatenated array"""
         self.bases = np.concatenate(reads).astype(np.uint8) if reads else np.zeros(0, np.uint8)
-        self.qual = np.full(self.bases.shape[0], 35, dtype=np.uint8)
+        if qual is None:
+            self.qual = np.full(self.bases.shape[0], 35, dtype=np.uint8)
+        elif callable(qual):
+            self.qual = np.concatenate([qual(len(r)) for r in reads]).astype(np.uint8) if reads else np.zeros(0, np.uint8)
+        else:
+            self.qual = np.ascontiguousarray(qual, dtype=np.uint8)
+            assert self.qual.shape == self.bases.shape
         self.offsets = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
         self.ids = ids
 
@@ -44,7 +51,8 @@ class Batch:
         return self.bases[int(self.offsets[i]):int(self.offsets[i + 1])]
 
     def part(self, lo, hi):
-        return Batch([self.read(i) for i in range(lo, hi)], None if self.ids is None else self.ids[lo:hi])
+        return Batch([self.read(i) for i in range(lo, hi)], None if self.ids is None else self.ids[lo:hi],
+                     self.qual[int(self.offsets[lo]):int(self.offsets[hi])])
 
 
 def split_offsets(patl, prm):
@@ -55,15 +63,18 @@ def gap_lengths(prm):
     return sorted({g for g in (1, 2, prm.max_gap - 1, prm.max_gap) if g >= 1})
 
 
-def workload(seed=1, patl=100, prm=None, n=250, size=100_000, min_ins=MIN_INS, max_ins=MAX_INS, frag_l=None, per_class=PER_CLASS, fileid=0):
-    """{g: synth.Genome, b1, b2: Batch, plants: [dict], prm, min_ins, max_ins}"""
+def workload(seed=1, patl=100, prm=None, n=250, size=100_000, min_ins=MIN_INS, max_ins=MAX_INS, frag_l=None, per_class=PER_CLASS, fileid=0,
+             seedl=SEEDL, anchor_l=ANCHOR_L, qual=None, n_frag=8, n_runs=6):
+    """{g: synth.Genome, b1, b2: Batch, plants: [dict], prm, min_ins, max_ins}; seedl: the seed length of the run (class U puts
+    its substitutions inside the first seed), anchor_l: the anchor mate's length, qual: Batch's quality generator (mate 1's
+    batch is asked first), n_frag / n_runs: the text's fragments and N runs"""
     from real_amd import synth
     prm = prm or gc.default_params(TOTALKMAX)
     G, m = prm.max_gap, prm.min_flank
-    frag_l = frag_l or max(FRAG_L, min_ins, patl + ANCHOR_L + 20)
-    assert min_ins <= frag_l <= max_ins and patl + ANCHOR_L <= frag_l
+    frag_l = frag_l or max(FRAG_L, min_ins, patl + anchor_l + 20)
+    assert min_ins <= frag_l <= max_ins and patl + anchor_l <= frag_l
     rng = np.random.default_rng(seed)
-    g = synth.random_genome(size, seed + 11, n_frag=8, n_runs=6)
+    g = synth.random_genome(size, seed + 11, n_frag=n_frag, n_runs=n_runs)
     sym, fstart = g.sym, [int(x) for x in g.frag_start]
     busy = sym > 3
     for c in fstart:
@@ -107,7 +118,7 @@ def workload(seed=1, patl=100, prm=None, n=250, size=100_000, min_ins=MIN_INS, m
             s = free_spot(frag_l)
         span = patl + (glen if deletion else -glen) if cls_eff in "DIHRNE" else patl
         xs = s if tfwd else s + frag_l - span                           # the target's footprint [xs, xs + span)
-        ys = s + frag_l - ANCHOR_L if tfwd else s                        # the anchor's
+        ys = s + frag_l - anchor_l if tfwd else s                        # the anchor's
         split = splits[rnd % len(splits)]
         if not deletion:
             split = min(split, patl - m - glen)
@@ -144,30 +155,30 @@ def workload(seed=1, patl=100, prm=None, n=250, size=100_000, min_ins=MIN_INS, m
             sym[at:at + span] = sym[xs:xs + span]
             plant.update(copy=at)
         if cls_eff == "U":
-            where = rng.choice(min(SEEDL, patl), size=3, replace=False)
+            where = rng.choice(min(seedl, patl), size=3, replace=False)
             rd = r if tfwd else gc.COMP[r[::-1]]
             rd = rd.copy()
             rd[where] ^= 2
             r = rd if tfwd else gc.COMP[rd[::-1]]
         x_read = r if tfwd else gc.COMP[r[::-1]]
-        y = sym[ys:ys + ANCHOR_L].copy()
+        y = sym[ys:ys + anchor_l].copy()
         y_read = gc.COMP[y[::-1]] if tfwd else y
         reads1.append(x_read if tm == 0 else y_read)
         reads2.append(y_read if tm == 0 else x_read)
         plants.append(dict(plant, i=len(reads1) - 1))
     # the sampled fragments, behind the planted ones: nearly all of them are concordant pairs the stage leaves alone
     g2 = synth.Genome(sym=sym, frag_start=g.frag_start, frag_names=g.frag_names)
-    bl = min(max(patl, SEEDL), ANCHOR_L)
-    s1, s2 = synth.sample_pairs(g2, n, bl, ANCHOR_L, frag_l, 25, 0.02, seed + 3, insert_min=max(min_ins, ANCHOR_L), insert_max=max_ins)
+    bl = min(max(patl, seedl), anchor_l)
+    s1, s2 = synth.sample_pairs(g2, n, bl, anchor_l, frag_l, 25, 0.02, seed + 3, insert_min=max(min_ins, anchor_l), insert_max=max_ins)
     for i in range(n):
-        a, b = s1.bases[i * bl:(i + 1) * bl].copy(), s2.bases[i * ANCHOR_L:(i + 1) * ANCHOR_L].copy()
+        a, b = s1.bases[i * bl:(i + 1) * bl].copy(), s2.bases[i * anchor_l:(i + 1) * anchor_l].copy()
         if i % 41 == 7:
             a[5] = 4                                                    # a mate the matcher skips: a symbol > 3
         reads1.append(a)
         reads2.append(b)
     ids = ["f%d" % i for i in range(len(reads1))]
-    return dict(g=g2, b1=Batch(reads1, [x + "/1" for x in ids]), b2=Batch(reads2, [x + "/2" for x in ids]), plants=plants, prm=prm,
-                min_ins=min_ins, max_ins=max_ins, fileid=fileid, patl=patl)
+    return dict(g=g2, b1=Batch(reads1, [x + "/1" for x in ids], qual), b2=Batch(reads2, [x + "/2" for x in ids], qual), plants=plants, prm=prm,
+                min_ins=min_ins, max_ins=max_ins, fileid=fileid, patl=patl, seedl=seedl)
 
 
 def intended(plant, rec, w):
