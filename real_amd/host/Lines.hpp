@@ -3,6 +3,8 @@
 // its spans, or a block of the host reader), one line for a read and a placement (appendLine), and the lines of a
 // block of reads formatted by all host threads and written in read order (formatAndWrite).  formatAndWrite accounts
 // its time, so the run's clock and stage timers are here too (now_s, Timers), and Chunk, the text a ReadSource reads.
+// Beside this file: RawChunker.hpp cuts the read file into Chunks; Sam.hpp and Vcf.hpp hold the lines of -sam and -vcf;
+// real.cpp holds the passes of a run and everything that calls the library.
 // Host code only: nothing here calls into the library.
 #pragma once
 #include <omp.h>
@@ -35,7 +37,7 @@ struct Timers {
 };
 
 // ---- a read for output ------------------------------------------------------------------------------------------
-// A chunk of whole records of the read file, as text (real.cpp: RawChunker), and what the device parser found in it:
+// A chunk of whole records of the read file, as text (RawChunker.hpp), and what the device parser found in it:
 // per read where its id starts and how long it is, and the running sum of the sequence lengths.
 struct Chunk {
     char *text = nullptr;

@@ -16,6 +16,8 @@
 //   host_selftest gap_grid <n>                    -> the geometry rule of a gapped placement in a text of n bases (csrc/final_record.h, rh_gap_fit)
 //       over a grid of lengths, gaps, splits and positions: a line "L g j p fits d del" each
 //   host_selftest lines <reads.fq> <outdir>      -> block.tsv chunk.tsv: a line per read, formatted from the host reader's blocks and from the text
+//   host_selftest chunks <reads> <fastq:0|1> <capacity> <buffers> <out> -> <out>: the text chunks RawChunker cuts the read file into with
+//       <buffers> buffers of <capacity> bytes (malloc / free), per chunk file_offset and size as u64 and then the bytes
 //   host_selftest sam <dir> <fastq:0|1> <qoff> <scores:0|1> <paired:0|1> -> <dir>/block.sam chunk.sam: the -sam file of the reads <dir>/r1 (and r2)
 //       from the records in <dir> (names.txt: a line "file<TAB>start<TAB>name" per fragment and one "file<TAB>n<TAB>" behind a file's
 //       last; info.u64 score.f32, or pairs.bin s1.bin s2.bin; per genome file mm<fi>.bin moff<fi>.u64), formatted by Sam.hpp from
@@ -39,6 +41,7 @@
 #include "GenomeText.hpp"
 #include "HostIndex.hpp"
 #include "Lines.hpp"
+#include "RawChunker.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "Sam.hpp"
@@ -450,6 +453,19 @@ int main(int argc, char **argv)
             const ReadSource chunk(c, sp);
             formatAndWrite(chunk.size(), fc, T, [&](uint64_t i, std::string &s) { line(chunk, 0, i, s); });
             return (fclose(fb) == 0) & (fclose(fc) == 0) ? 0 : 1;
+        }
+        if (cmd == "chunks" && argc == 7) {
+            RawChunker rc(argv[2], atoi(argv[3]) != 0, strtoull(argv[4], 0, 10), strtoull(argv[5], 0, 10), malloc, free);
+            std::ofstream out(argv[6], std::ios::binary);
+            Chunk c;
+            double wait_s = 0;
+            while (rc.next(c, wait_s)) {
+                const uint64_t head[2] = {c.file_offset, c.size};
+                out.write((const char *)head, sizeof head);
+                out.write(c.text, (std::streamsize)c.size);
+                rc.release(c);
+            }
+            return out.good() ? 0 : 1;
         }
         if (cmd == "options") {
             RealOptions o(argc - 1, argv + 1);

@@ -14,19 +14,20 @@
 // its cores and writes them with large sequential writes.  A file (or a later part of one) that is not in
 // one-line-per-field form is read by the host reader from that record on.
 //
-// Here: what the four drivers share (genomePass, streamReads, OutFile, fillMates) and the drivers.  Each formats through
-// one lambda -- read i of a ReadSource and a Placement, whatever parsed the read (Lines.hpp: all about the lines).
+// Here: what the four drivers share and the drivers.  Shared: an ABI struct made and a stage's statistics read one way
+// (sized, readStats), genomePass, the read file streamed (streamReads; restreamReads for a later pass, which must find the
+// reads of the first) and the two mate files likewise (streamMates, restreamMates), OutFile, the lists that grow
+// (listGrowing, Lists::fill), one gap leg, gap line and empty gap record, and the marks behind "All done.".  Each driver reads top
+// to bottom as the run goes: match, "All done.", marks, output, the passes behind the output.  Each formats through one lambda --
+// read i of a ReadSource and a Placement, whatever parsed the read (Lines.hpp: all about the lines; RawChunker.hpp: the read
+// file as text chunks).
 //
 // Deliberate differences from reference quirks (SURVEY 8a "quirks"): matchAll handles FASTQ input
 // (quirk 1) and writes every line (quirk 2); the exit status is non-zero on errors (quirk 6).
-#include <fcntl.h>
-#include <unistd.h>
-
 #include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <future>
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -37,6 +38,7 @@
 #include "GenomeText.hpp"
 #include "HostIndex.hpp"
 #include "Lines.hpp"
+#include "RawChunker.hpp"
 #include "ReadReader.hpp"
 #include "RealOptions.hpp"
 #include "Sam.hpp"
@@ -60,13 +62,28 @@ void check(real_hip_ctx *h, int rc, const char *what)
     throw std::runtime_error(msg);
 }
 
+// An ABI struct as the library takes it: every field zero, which each of them reads as "absent", and struct_size set.
+template <class S>
+S sized()
+{
+    S s = S();
+    s.struct_size = sizeof s;
+    return s;
+}
+// the statistics of a stage: get(h, &st, reset) into such a struct
+template <class S>
+S readStats(real_hip_ctx *h, int (*get)(real_hip_ctx *, S *, int), int reset, const char *what)
+{
+    S st = sized<S>();
+    check(h, get(h, &st, reset), what);
+    return st;
+}
+
 // the contexts of the run: one per device of -gpus, or `gpus` of them (the pileup pass: one, on -device)
 CtxVec makeContexts(const RealOptions &o, int gpus = 0)
 {
     if (!gpus) gpus = o.gpus;
-    real_hip_params p;
-    memset(&p, 0, sizeof p);
-    p.struct_size = sizeof p;
+    real_hip_params p = sized<real_hip_params>();
     p.seedl = o.seedl; p.seedkmax = o.seedkmax; p.totalkmax = o.totalkmax; p.scores = o.scores;
     p.prefix_bits = o.prefix_bits; p.table_kind = o.table_kind; p.filter_mult = o.filter_mult;
     real_hip_scoring_table(o.similarity, o.gc, o.trans, o.err, o.gcmut_bias, p.LL); // Scoring(opts...) :1115
@@ -238,147 +255,17 @@ void genomePass(const RealOptions &o, CtxVec &ctx, const std::vector<std::string
     }
 }
 
-// ---- the read file as text chunks ----------------------------------------------------------------------
-// Chunks of whole records for real_hip_parse_reads: a chunk ends behind a newline whose index is a multiple of the
-// lines per record (4 FASTQ, 2 FASTA) -- only text in one-line-per-field form parses, and only for such text the cuts
-// are record boundaries.  Buffers are pinned (real_hip_host_alloc): they cross PCIe by DMA.  The next chunk is read by
-// a prefetch thread while the devices work on the current ones.
-class RawChunker {
-public:
-    RawChunker(const std::string &fn, bool fastq, size_t chunk_bytes, size_t n_buffers) : lpr_(fastq ? 4 : 2)
-    {
-        fd_ = open(fn.c_str(), O_RDONLY);
-        if (fd_ < 0) throw std::runtime_error("Unable to open pattern file.");
-        for (size_t i = 0; i < n_buffers; ++i) {
-            Chunk c;
-            c.text = (char *)real_hip_host_alloc(chunk_bytes);
-            if (!c.text) throw std::bad_alloc();
-            c.cap = chunk_bytes;
-            pool_.push_back(c);
-            free_.push_back((int)i);
-        }
-        prefetch();
-    }
-    ~RawChunker()
-    {
-        if (next_.valid()) next_.wait();
-        for (auto &c : pool_) real_hip_host_free(c.text);
-        if (fd_ >= 0) close(fd_);
-    }
-    // the next chunk (the caller's until it hands it back with release); false at the end of the file
-    bool next(Chunk &out, double &wait_s)
-    {
-        if (!next_.valid()) prefetch();
-        if (!next_.valid()) return false;
-        const double t0 = now_s();
-        const int got = next_.get(); // (an exception of the reader thread surfaces here)
-        wait_s += now_s() - t0;
-        if (got < 0) { done_ = true; return false; }
-        out = pool_[(size_t)got];
-        prefetch();
-        return true;
-    }
-    void release(const Chunk &c)
-    {
-        for (size_t i = 0; i < pool_.size(); ++i)
-            if (pool_[i].text == c.text) free_.push_back((int)i);
-        prefetch();
-    }
-private:
-    // (only the thread that owns the chunker calls this, and only while no read is in flight: the reader thread is the
-    // only one that touches the file state then)
-    void prefetch()
-    {
-        if (done_ || next_.valid() || free_.empty()) return;
-        const int id = free_.back();
-        free_.pop_back();
-        next_ = std::async(std::launch::async, [this, id]() { return fill(id) ? id : -1; });
-    }
-    // reads the next chunk with kReaders threads (pread of a slice each, then the newlines of the slice are counted
-    // while it is hot), cuts it behind the last newline whose index is a multiple of the lines per record
-    bool fill(int id)
-    {
-        Chunk &c = pool_[(size_t)id];
-        const size_t have = carry_.size();
-        if (have > c.cap) throw std::runtime_error("a read record longer than the text chunk");
-        if (have) memcpy(c.text, carry_.data(), have);
-        c.file_offset = offset_;
-        carry_.clear();
-        const size_t want = eof_ ? 0 : c.cap - have;
-        constexpr int kReaders = 4;
-        size_t got_s[kReaders] = {0, 0, 0, 0}, nl_s[kReaders] = {0, 0, 0, 0};
-        bool err = false;
-        auto slice = [&](int k) {
-            const size_t lo = want * (size_t)k / kReaders, hi = want * (size_t)(k + 1) / kReaders;
-            size_t done = 0;
-            while (lo + done < hi) {
-                const ssize_t r = pread(fd_, c.text + have + lo + done, hi - lo - done, (off_t)(fpos_ + lo + done));
-                if (r < 0) { err = true; break; }
-                if (r == 0) break; // end of file
-                done += (size_t)r;
-            }
-            got_s[k] = done;
-            size_t nl = 0;
-            const char *b = c.text + have + lo, *e = b + done;
-            if (k == 0) b = c.text; // (the carry belongs to the first slice)
-            for (const char *q = b; (q = (const char *)memchr(q, '\n', (size_t)(e - q))); ++q) nl++;
-            nl_s[k] = nl;
-        };
-        if (want) {
-            std::thread th[kReaders - 1];
-            for (int k = 1; k < kReaders; ++k) th[k - 1] = std::thread(slice, k);
-            slice(0);
-            for (auto &t : th) t.join();
-        } else {
-            slice(0); // (nothing to read: the newlines of the carry)
-        }
-        if (err) throw std::runtime_error("reading the pattern file failed");
-        size_t got = 0, lines = 0;
-        for (int k = 0; k < kReaders; ++k) { got += got_s[k]; lines += nl_s[k]; } // (a short slice = the end of the file: the slices behind it are empty)
-        fpos_ += got;
-        if (got < want || !want) eof_ = true;
-        c.size = have + got;
-        if (!c.size) return false;
-        if (!eof_) {
-            // behind newline number lines - lines % lpr: walk back over the lines % lpr newlines of the incomplete record
-            size_t back = lines % lpr_, cut = c.size;
-            const char *q = c.text + c.size;
-            for (size_t k = 0; k <= back; ++k) {
-                q = (const char *)memrchr(c.text, '\n', (size_t)(q - c.text));
-                if (!q) { cut = 0; break; }
-                cut = (size_t)(q - c.text) + 1;
-            }
-            if (lines < lpr_ || !cut) throw std::runtime_error("a read record longer than the text chunk");
-            carry_.assign(c.text + cut, c.text + c.size);
-            c.size = cut;
-        }
-        offset_ += c.size;
-        return true;
-    }
-    int fd_ = -1;
-    uint64_t fpos_ = 0; // file position behind the bytes read so far
-    size_t lpr_;
-    bool eof_ = false, done_ = false;
-    uint64_t offset_ = 0;
-    std::vector<char> carry_;
-    std::vector<Chunk> pool_;
-    std::vector<int> free_;
-    std::future<int> next_;
-};
-
 real_hip_batch makeBatch(const ReadBlock &b)
 {
-    real_hip_batch rb;
-    memset(&rb, 0, sizeof rb);
-    rb.struct_size = sizeof rb; rb.on_device = 0; rb.n_reads = b.size();
+    real_hip_batch rb = sized<real_hip_batch>();
+    rb.on_device = 0; rb.n_reads = b.size();
     rb.bases = b.bases.data(); rb.qual = b.qual.data(); rb.offsets = b.offsets.data();
     return rb;
 }
 real_hip_batch makeBatch(const real_hip_parsed &p)
 {
-    real_hip_batch rb;
-    memset(&rb, 0, sizeof rb);
-    rb.struct_size = sizeof rb; rb.on_device = 2; rb.n_reads = p.n_reads;
+    real_hip_batch rb = sized<real_hip_batch>();
+    rb.on_device = 2; rb.n_reads = p.n_reads;
     rb.bases = p.bases; rb.qual = p.qual; rb.offsets = p.offsets; rb.max_patl = p.max_patl;
     return rb;
 }
@@ -417,7 +304,7 @@ uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids,
     std::vector<ReadItem> items;
     std::vector<Spans> spans(ctx.size());
     if (!host) {
-        RawChunker rc(o.patternfilename, o.fastq, o.chunk_bytes, 2 * ctx.size());
+        RawChunker rc(o.patternfilename, o.fastq, o.chunk_bytes, 2 * ctx.size(), real_hip_host_alloc, real_hip_host_free); // (pinned: the chunks cross PCIe by DMA)
         while (!host) {
             std::vector<Chunk> ch;
             for (size_t g = 0; g < ctx.size(); ++g) {
@@ -470,6 +357,26 @@ uint64_t streamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids,
         }
     }
     return next_id;
+}
+
+// A later pass over the read file, which must hold the numpat reads the first pass counted: onItem(g, item) runs with every
+// item that has reads, the items of a round each on a host thread of its own (item g belongs to context g; one context: one
+// item, on the caller's thread).  round_s, where given, receives the wall time of the rounds.
+const char *const kReadFileChanged = "the read file changed between two passes";
+template <class OnItem>
+void restreamReads(const RealOptions &o, CtxVec &ctx, int qoff, bool want_ids, Timers &T, uint64_t numpat, double *round_s, OnItem onItem)
+{
+    const uint64_t seen = streamReads(o, ctx, qoff, want_ids, T, [&](const std::vector<ReadItem> &items) {
+        const double tm = now_s();
+        onEach(items.size(), [&](size_t g) {
+            const ReadItem &it = items[g];
+            if (!it.batch.n_reads) return;
+            if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error(kReadFileChanged);
+            onItem(g, it);
+        });
+        if (round_s) *round_s += now_s() - tm;
+    });
+    if (seen != numpat) throw std::runtime_error(kReadFileChanged);
 }
 
 // list(h, in..., hits, room, &n, offsets) lists into hits and answers REAL_HIP_E_OVERFLOW with the number it has to list:
@@ -575,8 +482,8 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::strin
     check(h, real_hip_call_begin(h), "real_hip_call_begin");
     addAll(ctx, true);
     if (o.pileup_gapped) gapAll(ctx, fi, kGapCalls);
-    real_hip_call_params cp;
-    cp.struct_size = sizeof cp; cp.min_call_qual = (uint32_t)o.vcf_minqual; cp.min_depth = (uint32_t)o.vcf_mindepth;
+    real_hip_call_params cp = sized<real_hip_call_params>();
+    cp.min_call_qual = (uint32_t)o.vcf_minqual; cp.min_depth = (uint32_t)o.vcf_mindepth;
     uint64_t n_calls = 0, n = 0;
     check(h, real_hip_call_finish(h, &cp, &n_calls), "real_hip_call_finish");
     std::vector<real_hip_call> calls(n_calls);
@@ -585,29 +492,20 @@ void writeCalls(const RealOptions &o, CtxVec &ctx, unsigned fi, const std::strin
     if (o.vcf_indels) {
         check(h, real_hip_indel_begin(h), "real_hip_indel_begin");
         gapAll(ctx, fi, kGapIndels);
-        real_hip_indel_params ip;
-        ip.struct_size = sizeof ip; ip.min_call_qual = (uint32_t)o.vcf_minqual; ip.min_alt = (uint32_t)o.vcf_minalt; ip.min_depth = (uint32_t)o.vcf_mindepth;
+        real_hip_indel_params ip = sized<real_hip_indel_params>();
+        ip.min_call_qual = (uint32_t)o.vcf_minqual; ip.min_alt = (uint32_t)o.vcf_minalt; ip.min_depth = (uint32_t)o.vcf_mindepth;
         uint64_t n_events = 0, n_indels = 0, ni = 0;
         check(h, real_hip_indel_finish(h, &ip, &n_events, &n_indels), "real_hip_indel_finish");
         indels.resize(n_indels);
         check(h, real_hip_indel_calls(h, indels.data(), indels.size(), &ni, 0), "real_hip_indel_calls");
     }
     writeVcfMerged(f, names, G.frag_start.data(), G.sym.data(), calls.data(), n, indels.data(), indels.size());
-    real_hip_pileup_stats ps;
-    memset(&ps, 0, sizeof ps);
-    ps.struct_size = sizeof ps;
-    check(h, real_hip_pileup_stats_get(h, &ps, 0), "real_hip_pileup_stats_get");
-    real_hip_call_stats st;
-    memset(&st, 0, sizeof st);
-    st.struct_size = sizeof st;
-    check(h, real_hip_call_stats_get(h, &st, 1), "real_hip_call_stats_get");
+    const real_hip_pileup_stats ps = readStats(h, real_hip_pileup_stats_get, 0, "real_hip_pileup_stats_get");
+    const real_hip_call_stats st = readStats(h, real_hip_call_stats_get, 1, "real_hip_call_stats_get");
     fprintf(stderr, "calls: file=%s sites=%llu calls=%llu het=%llu hom=%llu site_bases=%llu low_qual=%llu\n", file.c_str(), (unsigned long long)ps.sites,
             (unsigned long long)st.calls, (unsigned long long)st.het, (unsigned long long)st.hom, (unsigned long long)st.site_bases, (unsigned long long)st.low_qual);
     if (o.vcf_indels) {
-        real_hip_indel_stats is;
-        memset(&is, 0, sizeof is);
-        is.struct_size = sizeof is;
-        check(h, real_hip_indel_stats_get(h, &is, 1), "real_hip_indel_stats_get");
+        const real_hip_indel_stats is = readStats(h, real_hip_indel_stats_get, 1, "real_hip_indel_stats_get");
         fprintf(stderr, "indels: file=%s events=%llu distinct=%llu calls=%llu het=%llu hom=%llu deletions=%llu insertions=%llu shifted=%llu low_qual=%llu\n",
                 file.c_str(), (unsigned long long)is.events, (unsigned long long)is.distinct, (unsigned long long)is.calls, (unsigned long long)is.het,
                 (unsigned long long)is.hom, (unsigned long long)is.deletions, (unsigned long long)is.insertions, (unsigned long long)is.shifted,
@@ -633,8 +531,8 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
         const std::string head = vcfHeader(refs, o.vcf_indels);
         if (fwrite(head.data(), 1, head.size(), vcf_out->file()) != head.size()) throw std::runtime_error("write to the -vcf file failed");
     }
-    real_hip_pileup_params pp;
-    pp.struct_size = sizeof pp; pp.min_qual = (uint32_t)o.pileup_minq;
+    real_hip_pileup_params pp = sized<real_hip_pileup_params>();
+    pp.min_qual = (uint32_t)o.pileup_minq;
     textPass(o, files, T, [&](CtxVec &ctx, unsigned fi, const GenomeText &G) {
         real_hip_ctx *h = ctx[0]->h;
         check(h, real_hip_pileup_begin(h, &pp), "real_hip_pileup_begin");
@@ -644,19 +542,13 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
         check(h, real_hip_pileup_finish(h, &n_sites), "real_hip_pileup_finish");
         if (sites_out) writeSites(h, n_sites, G, sites_out->file());
         if (depth_out) writeDepthRuns(h, G, depth_out->file());
-        real_hip_pileup_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
-        check(h, real_hip_pileup_stats_get(h, &st, 1), "real_hip_pileup_stats_get");
+        const real_hip_pileup_stats st = readStats(h, real_hip_pileup_stats_get, 1, "real_hip_pileup_stats_get");
         fprintf(stderr, "pileup: file=%s placements=%llu bases=%llu covered=%llu mean_depth=%.3f max_depth=%llu sites=%llu mismatches=%llu low_qual=%llu\n",
                 files[fi].c_str(), (unsigned long long)st.placed, (unsigned long long)st.bases, (unsigned long long)st.covered,
                 st.covered ? (double)st.bases / (double)st.covered : 0.0, (unsigned long long)st.max_depth, (unsigned long long)st.sites,
                 (unsigned long long)st.mismatches, (unsigned long long)st.low_qual);
         if (o.pileup_gapped) {
-            real_hip_pileup_gapped_stats gs;
-            memset(&gs, 0, sizeof gs);
-            gs.struct_size = sizeof gs;
-            check(h, real_hip_pileup_gapped_stats_get(h, &gs, 1), "real_hip_pileup_gapped_stats_get");
+            const real_hip_pileup_gapped_stats gs = readStats(h, real_hip_pileup_gapped_stats_get, 1, "real_hip_pileup_gapped_stats_get");
             fprintf(stderr, "pileup gapped: file=%s placements=%llu ungapped=%llu aligned=%llu deleted=%llu inserted=%llu mismatches=%llu low_qual=%llu\n",
                     files[fi].c_str(), (unsigned long long)gs.placed, (unsigned long long)gs.ungapped, (unsigned long long)gs.aligned_bases,
                     (unsigned long long)gs.deleted, (unsigned long long)gs.inserted, (unsigned long long)gs.mismatches, (unsigned long long)gs.low_qual);
@@ -675,55 +567,47 @@ void pileupPass(const RealOptions &o, const std::vector<std::string> &files, con
 // ---- -sam: every read as a SAM line, NM / MD from the mismatch lists of the final placements ----------------------------
 // Runs where pileupPass runs, through the same textPass.  The header names the fragments of all genome files (RS).  Per file
 // writeAll(ctx, fi, last, refs, lists, out) streams the reads once more, takes each batch's lists from real_hip_mismatches /
-// _pairs with the final records (SamLists::fill), and writes the lines of the reads placed in this file -- and, in the pass
+// _pairs with the final records (SamLists::add), and writes the lines of the reads placed in this file -- and, in the pass
 // of the last file, of those placed nowhere (Sam.hpp: all about the lines).  A summary line per file goes to standard error.
-struct SamLists {
+// The lists of a batch and the protocol that fills them: list(h, in..., mm, room, &n, off) lists n_lists reads into mm.  A call
+// that overflows has counted and written nothing: its statistics are dropped (read and reset through get) and the call is
+// repeated with room for what it reported (and an eighth more).  Returns the statistics of the call that listed.
+struct Lists {
     std::vector<real_hip_mismatch> mm = std::vector<real_hip_mismatch>(1024); // (grows by the count the library reports)
     std::vector<uint64_t> off;
-    uint64_t placed = 0, mismatches = 0, on_n = 0, disagree = 0; // of the calls that listed, summed over a genome file
-    // list(h, in..., mm, room, &n, off): the lists of one batch of n_lists reads.  A call that overflows has counted and written
-    // nothing: its statistics are dropped and the call is repeated with room for what it reported (and an eighth more).
-    template <class List, class... In>
-    void fill(real_hip_ctx *h, const char *what, uint64_t n_lists, List list, In... in)
+    template <class Stats, class List, class... In>
+    Stats fill(real_hip_ctx *h, const char *what, int (*get)(real_hip_ctx *, Stats *, int), const char *get_name, uint64_t n_lists, List list, In... in)
     {
         off.assign(n_lists + 1, 0);
         uint64_t n = 0;
-        real_hip_mismatch_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
         int rc = list(h, in..., mm.data(), mm.size(), &n, off.data());
         if (rc == REAL_HIP_E_OVERFLOW) {
-            check(h, real_hip_mismatch_stats_get(h, &st, 1), "real_hip_mismatch_stats_get");
+            readStats(h, get, 1, get_name);
             mm.resize(n + n / 8 + 16);
             rc = list(h, in..., mm.data(), mm.size(), &n, off.data());
         }
         check(h, rc, what);
-        check(h, real_hip_mismatch_stats_get(h, &st, 1), "real_hip_mismatch_stats_get");
+        return readStats(h, get, 1, get_name);
+    }
+};
+// real_hip_mismatches / _pairs: the sums over a genome file
+struct SamLists : Lists {
+    uint64_t placed = 0, mismatches = 0, on_n = 0, disagree = 0;
+    template <class List, class... In>
+    void add(real_hip_ctx *h, const char *what, uint64_t n_lists, List list, In... in)
+    {
+        const real_hip_mismatch_stats st = fill(h, what, real_hip_mismatch_stats_get, "real_hip_mismatch_stats_get", n_lists, list, in...);
         placed += st.placed; mismatches += st.mismatches; on_n += st.on_n; disagree += st.disagree;
     }
 };
-
 // -sam_gapped 1: the lists of the mates the gap rescue placed, list i for fragment i of the batch (real_hip_mismatches_gapped);
-// the protocol of SamLists::fill, the stage's own statistics summed over the run
-struct GappedLists {
-    std::vector<real_hip_mismatch> mm = std::vector<real_hip_mismatch>(1024);
-    std::vector<uint64_t> off;
+// the stage's own statistics summed over the run
+struct GappedLists : Lists {
     uint64_t mates = 0, deleted = 0, inserted = 0, disagree = 0;
-    void fill(real_hip_ctx *h, uint64_t n, const real_hip_batch *rb1, const real_hip_batch *rb2, const real_hip_gap_place *gaps)
+    void add(real_hip_ctx *h, uint64_t n, const real_hip_batch *rb1, const real_hip_batch *rb2, const real_hip_gap_place *gaps)
     {
-        off.assign(n + 1, 0);
-        uint64_t total = 0;
-        real_hip_gapped_list_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
-        int rc = real_hip_mismatches_gapped(h, rb1, rb2, gaps, mm.data(), mm.size(), &total, off.data());
-        if (rc == REAL_HIP_E_OVERFLOW) {
-            check(h, real_hip_gapped_list_stats_get(h, &st, 1), "real_hip_gapped_list_stats_get");
-            mm.resize(total + total / 8 + 16);
-            rc = real_hip_mismatches_gapped(h, rb1, rb2, gaps, mm.data(), mm.size(), &total, off.data());
-        }
-        check(h, rc, "real_hip_mismatches_gapped");
-        check(h, real_hip_gapped_list_stats_get(h, &st, 1), "real_hip_gapped_list_stats_get");
+        const real_hip_gapped_list_stats st = fill(h, "real_hip_mismatches_gapped", real_hip_gapped_list_stats_get, "real_hip_gapped_list_stats_get", n,
+                                                   real_hip_mismatches_gapped, rb1, rb2, gaps);
         mates += st.placed; deleted += st.deleted; inserted += st.inserted; disagree += st.disagree;
     }
 };
@@ -750,12 +634,15 @@ void samPass(const RealOptions &o, const std::vector<std::string> &files, const 
 // The summaries are taken with the first pass over the reads and kept beside the records; behind "All done." one call marks
 // all records on the first context (duplicates in different batches, host blocks and parser chunks meet), and the summary line
 // goes to standard error.  The pileup then gets, per batch, a scratch copy of the records with the duplicates set to NoMatch.
-void reportDuplicates(real_hip_ctx *h, const RealOptions &o)
+// mark(): the driver's real_hip_mark_duplicates* call, which fills dup
+template <class Mark>
+void markDuplicates(real_hip_ctx *h, const RealOptions &o, Timers &T, uint64_t numpat, std::vector<uint8_t> &dup, Mark mark)
 {
-    real_hip_dup_stats st;
-    memset(&st, 0, sizeof st);
-    st.struct_size = sizeof st;
-    check(h, real_hip_dup_stats_get(h, &st, 1), "real_hip_dup_stats_get");
+    dup.assign(numpat, 0);
+    const double tm = now_s();
+    mark();
+    T.match += now_s() - tm;
+    const real_hip_dup_stats st = readStats(h, real_hip_dup_stats_get, 1, "real_hip_dup_stats_get");
     fprintf(stderr, "duplicates: placed=%llu groups=%llu duplicates=%llu rate=%.4f min_qual=%ld\n", (unsigned long long)st.placed, (unsigned long long)st.groups,
             (unsigned long long)st.duplicates, st.placed ? (double)st.duplicates / (double)st.placed : 0.0, o.dedup_minq);
 }
@@ -775,17 +662,85 @@ const Rec *withoutDuplicates(const std::vector<Rec> &records, const std::vector<
 // done.", where -dedup marks, one call on the first context turns them into one byte per read (two per fragment), and the
 // summary line goes to standard error.  -sam writes the bytes; -pileup_minmapq masks with them as -dedup masks.
 const real_hip_mapq_acc kNoCandidates = {INT32_MIN, 0, {0}};
-void reportMapq(real_hip_ctx *h, const std::vector<uint8_t> &mapq)
+// rate(): the driver's real_hip_mapq* call, which fills the n bytes of mapq
+template <class Rate>
+void rateMapq(real_hip_ctx *h, Timers &T, uint64_t n, std::vector<uint8_t> &mapq, Rate rate)
 {
-    real_hip_mapq_stats st;
-    memset(&st, 0, sizeof st);
-    st.struct_size = sizeof st;
-    check(h, real_hip_mapq_stats_get(h, &st, 1), "real_hip_mapq_stats_get");
+    mapq.assign(n, REAL_HIP_MAPQ_NONE);
+    const double tm = now_s();
+    rate();
+    T.match += now_s() - tm;
+    const real_hip_mapq_stats st = readStats(h, real_hip_mapq_stats_get, 1, "real_hip_mapq_stats_get");
     uint64_t sum = 0, placed = 0;
     for (const uint8_t q : mapq)
         if (q != REAL_HIP_MAPQ_NONE) { sum += q; ++placed; }
     fprintf(stderr, "mapq: placements=%llu unlisted=%llu mean=%.3f\n", (unsigned long long)st.placements, (unsigned long long)st.unlisted,
             placed ? (double)sum / (double)placed : 0.0);
+}
+// what the pileup leaves out: the duplicates, and with -pileup_minmapq the records i with below(i)
+template <class Below>
+std::vector<uint8_t> dropMask(const RealOptions &o, uint64_t numpat, const std::vector<uint8_t> &dup, Below below)
+{
+    std::vector<uint8_t> drop = dup;
+    if (o.pileup_minmapq > 0) {
+        drop.resize(numpat, 0);
+        for (uint64_t i = 0; i < numpat; ++i)
+            if (below(i)) drop[i] = 1;
+    }
+    return drop;
+}
+
+// ---- gap records: what -gapped (paired) and -gapped_single share -------------------------------------------------------------
+real_hip_gap_params gapParams(const RealOptions &o)
+{
+    real_hip_gap_params gp = sized<real_hip_gap_params>();
+    gp.max_gap = (uint32_t)o.gap_max; gp.min_flank = (uint32_t)o.gap_flank;
+    gp.cost_mismatch = 4; gp.cost_open = 6; gp.cost_extend = 1; gp.max_cost = (uint32_t)o.gap_maxcost; gp.margin = (uint32_t)o.gap_margin;
+    return gp;
+}
+// the record of a read without a gapped placement: NoMatch, as a call with fresh != 0 starts every record
+inline real_hip_gap_place noGapRecord()
+{
+    real_hip_gap_place none;
+    memset(&none, 0, sizeof none);
+    none.second = REAL_HIP_GAP_NONE;
+    return none;
+}
+// the CIGAR of a record of a read of patl bases ("*" where the library writes none)
+struct Cigar { char s[48]; };
+inline Cigar gapCigar(const real_hip_gap_place &g, uint64_t patl)
+{
+    Cigar c;
+    strcpy(c.s, "*");
+    real_hip_gap_cigar(&g, (uint32_t)patl, c.s, sizeof c.s);
+    return c;
+}
+// The line of a Unique record in the -gapped / -gapped_single file: id, [mate 1|2,] strand, fragment, 1-based position, CIGAR,
+// edit distance, mismatches, cost, the runner-up's cost or *[, the 1-based position of the anchor: the other mate].
+inline void appendGapLine(std::string &s, const real_hip_gap_place &g, const ReadView &r, const Ranges &RS, int mate, const real_hip_single *anchor)
+{
+    char second[16] = "*", tail[160];
+    if (g.second != REAL_HIP_GAP_NONE) snprintf(second, sizeof second, "%u", (unsigned)g.second);
+    const int absg = g.gap < 0 ? -g.gap : g.gap;
+    s.append(r.id, r.idlen);
+    if (mate) s += mate == 2 ? "\t2" : "\t1";
+    s += REAL_HIP_GAP_INVERTED(g.tag) ? "\t-\t" : "\t+\t";
+    s += RS.names[g.fileid][g.frag];
+    snprintf(tail, sizeof tail, "\t%llu\t%s\t%u\t%u\t%u\t%s", (unsigned long long)((uint64_t)g.pos - RS.starts[g.fileid][g.frag] + 1), gapCigar(g, r.patl).s,
+             (unsigned)(g.k + absg), (unsigned)g.k, (unsigned)g.cost, second);
+    s += tail;
+    if (anchor) {
+        snprintf(tail, sizeof tail, "\t%llu", (unsigned long long)((uint64_t)anchor->pos - RS.starts[anchor->fileid][anchor->frag] + 1));
+        s += tail;
+    }
+    s += '\n';
+}
+// a batch's gap records to one leg of the pileup pass (pileupPass: gapAll)
+void addGapLeg(real_hip_ctx *h, GapLeg leg, const real_hip_batch &rb1, const real_hip_batch &rb2, const real_hip_gap_place *gaps)
+{
+    if (leg == kGapPileup) check(h, real_hip_pileup_add_gapped(h, &rb1, &rb2, gaps), "real_hip_pileup_add_gapped");
+    else if (leg == kGapCalls) check(h, real_hip_call_add_gapped(h, &rb1, &rb2, gaps), "real_hip_call_add_gapped");
+    else check(h, real_hip_indel_add(h, &rb1, &rb2, gaps), "real_hip_indel_add");
 }
 
 // ---- -gapped_single: a single read placed nowhere, placed with one insertion or deletion (real_hip_match_gapped) ----
@@ -799,14 +754,6 @@ void reportMapq(real_hip_ctx *h, const std::vector<uint8_t> &mapq)
 // Without a consumer of the records both run here, on the pass's own context.  With one (-sam_gapped 1, -vcf_indels 1,
 // -pileup_gapped 1 without -p2) the matching half runs behind "All done." on the matching contexts, before the
 // marks of -dedup and the pileup and SAM passes, which read its records; the writing half stays here.
-real_hip_gap_params gapParams(const RealOptions &o);
-inline real_hip_gap_place noGapRecord()
-{
-    real_hip_gap_place none;
-    memset(&none, 0, sizeof none);
-    none.second = REAL_HIP_GAP_NONE;
-    return none;
-}
 struct GapSingleRun {
     std::vector<real_hip_gap_place> gaps; // one record per read, from the matching half on
     uint64_t eligible = 0, anchored = 0, crowded = 0;
@@ -817,29 +764,17 @@ void gapSingleMatch(const RealOptions &o, CtxVec &gc, const std::vector<std::str
                     GapSingleRun &run)
 {
     const real_hip_gap_params gp = gapParams(o);
-    real_hip_gap_anchor_params ap;
-    memset(&ap, 0, sizeof ap);
-    ap.struct_size = sizeof ap; ap.anchor_len = (uint32_t)o.gap_anchor; ap.max_anchors = (uint32_t)o.gap_anchors;
+    real_hip_gap_anchor_params ap = sized<real_hip_gap_anchor_params>();
+    ap.anchor_len = (uint32_t)o.gap_anchor; ap.max_anchors = (uint32_t)o.gap_anchors;
     run.gaps.assign(numpat, noGapRecord());
     bool first = true;
     for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, gc, files, fi, 0, T, nullptr, [&](Resident &) {
-        const uint64_t seen = streamReads(o, gc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
-            const double tm = now_s();
-            onEach(items.size(), [&](size_t g) {
-                const ReadItem &it = items[g];
-                if (!it.batch.n_reads) return;
-                if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
-                check(gc[g]->h, real_hip_match_gapped(gc[g]->h, &gp, &ap, &it.batch, info.data() + it.first_id, first ? 1 : 0, run.gaps.data() + it.first_id), "real_hip_match_gapped");
-            });
-            T.match += now_s() - tm;
+        restreamReads(o, gc, qoff, false, T, numpat, &T.match, [&](size_t g, const ReadItem &it) {
+            check(gc[g]->h, real_hip_match_gapped(gc[g]->h, &gp, &ap, &it.batch, info.data() + it.first_id, first ? 1 : 0, run.gaps.data() + it.first_id), "real_hip_match_gapped");
         });
-        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
         uint64_t eligible = 0;
         for (auto &c : gc) {
-            real_hip_gap_anchor_stats st;
-            memset(&st, 0, sizeof st);
-            st.struct_size = sizeof st;
-            check(c->h, real_hip_gap_anchor_stats_get(c->h, &st, 1), "real_hip_gap_anchor_stats_get");
+            const real_hip_gap_anchor_stats st = readStats(c->h, real_hip_gap_anchor_stats_get, 1, "real_hip_gap_anchor_stats_get");
             eligible += st.eligible;
             run.anchored += st.eligible - st.skipped - st.crowded - st.unanchored; run.crowded += st.crowded;
         }
@@ -859,31 +794,14 @@ void gapSinglePass(const RealOptions &o, const std::vector<std::string> &files, 
     if (!run.matched) gapSingleMatch(o, gc, files, T, qoff, info, numpat, run);
     const std::vector<real_hip_gap_place> &gaps = run.gaps;
     uint64_t placed = 0, unique = 0, gapped = 0;
-    const uint64_t seen = streamReads(o, gc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
-        for (const ReadItem &it : items) {
-            const ReadSource src = it.src;
-            if (!src.size()) continue;
-            const uint64_t base = it.first_id;
-            if (base + src.size() > numpat) throw std::runtime_error("the read file changed between two passes");
-            formatAndWrite(src.size(), out.file(), T, [&](uint64_t i, std::string &s) {
-                const real_hip_gap_place &g = gaps[base + i];
-                if (REAL_HIP_GAP_STATE(g.tag) != REAL_HIP_PAIR_UNIQUE) return;
-                const ReadView r = src[i];
-                char cigar[48], tail[160];
-                real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
-                char second[16] = "*";
-                if (g.second != REAL_HIP_GAP_NONE) snprintf(second, sizeof second, "%u", (unsigned)g.second);
-                const int absg = g.gap < 0 ? -g.gap : g.gap;
-                snprintf(tail, sizeof tail, "\t%llu\t%s\t%u\t%u\t%u\t%s\n", (unsigned long long)((uint64_t)g.pos - RS.starts[g.fileid][g.frag] + 1), cigar,
-                         (unsigned)(g.k + absg), (unsigned)g.k, (unsigned)g.cost, second);
-                s.append(r.id, r.idlen);
-                s += REAL_HIP_GAP_INVERTED(g.tag) ? "\t-\t" : "\t+\t";
-                s += RS.names[g.fileid][g.frag];
-                s += tail;
-            });
-        }
+    restreamReads(o, gc, qoff, true, T, numpat, nullptr, [&](size_t, const ReadItem &it) {
+        const ReadSource src = it.src;
+        const uint64_t base = it.first_id;
+        formatAndWrite(src.size(), out.file(), T, [&](uint64_t i, std::string &s) {
+            const real_hip_gap_place &g = gaps[base + i];
+            if (REAL_HIP_GAP_STATE(g.tag) == REAL_HIP_PAIR_UNIQUE) appendGapLine(s, g, src[i], RS, 0, nullptr);
+        });
     });
-    if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     out.close();
     for (const real_hip_gap_place &g : gaps) {
         const unsigned st = REAL_HIP_GAP_STATE(g.tag);
@@ -906,7 +824,6 @@ int matchUnique(const RealOptions &o)
     std::vector<uint8_t> dup;            // -dedup: one mark per read, from behind "All done." on
     std::vector<real_hip_mapq_acc> acc;  // -mapq: kept for the run beside info
     std::vector<uint8_t> mapq;           // -mapq: one quality per read, from behind "All done." on
-    std::vector<uint8_t> drop;           // what the pileup leaves out: dup, and with -pileup_minmapq the placements below it
     uint64_t numpat = 0;
     bool counted = false;
     auto grow = [&](uint64_t n) {
@@ -941,7 +858,7 @@ int matchUnique(const RealOptions &o)
             if (counted) std::cerr << "\r                                                              \r" << (double)end / (numpat ? numpat : 1) << std::flush;
         });
         if (!counted) { numpat = seen; counted = true; std::cerr << "number of reads " << numpat << std::endl; } // :1096
-        else if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
+        else if (seen != numpat) throw std::runtime_error(kReadFileChanged);
         std::cerr << std::endl;
     });
     std::cerr << "All done." << std::endl;
@@ -951,35 +868,23 @@ int matchUnique(const RealOptions &o)
     GapSingleRun gap_run;
     if (consumers) gapSingleMatch(o, ctx, files, T, qoff, info, numpat, gap_run);
     const std::vector<real_hip_gap_place> &gaps = gap_run.gaps;
-    if (o.dedup) {
-        dup.assign(numpat, 0);
-        const double tm = now_s();
+    real_hip_ctx *h = ctx[0]->h;
+    if (o.dedup) markDuplicates(h, o, T, numpat, dup, [&]() {
         if (consumers) // gapped and ungapped reads of one 5' end are one molecule's copies: one key space, one sort
-            check(ctx[0]->h, real_hip_mark_duplicates_gapped(ctx[0]->h, info.data(), gaps.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_gapped");
+            check(h, real_hip_mark_duplicates_gapped(h, info.data(), gaps.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_gapped");
         else
-            check(ctx[0]->h, real_hip_mark_duplicates(ctx[0]->h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
-        T.match += now_s() - tm;
-        reportDuplicates(ctx[0]->h, o);
-        if (consumers) {
-            uint64_t placements = 0, marked = 0;
-            for (uint64_t i = 0; i < numpat; ++i)
-                if (REAL_HIP_GAP_STATE(gaps[i].tag) == REAL_HIP_PAIR_UNIQUE) { ++placements; marked += dup[i] != 0; }
-            fprintf(stderr, "duplicates gapped: placements=%llu duplicates=%llu\n", (unsigned long long)placements, (unsigned long long)marked);
-        }
-    }
-    if (o.mapq) {
-        mapq.assign(numpat, REAL_HIP_MAPQ_NONE);
-        const double tm = now_s();
-        check(ctx[0]->h, real_hip_mapq(ctx[0]->h, info.data(), o.scores ? score.data() : nullptr, acc.data(), numpat, 0, mapq.data()), "real_hip_mapq");
-        T.match += now_s() - tm;
-        reportMapq(ctx[0]->h, mapq);
-    }
-    drop = dup;
-    if (o.pileup_minmapq > 0) {
-        drop.resize(numpat, 0);
+            check(h, real_hip_mark_duplicates(h, info.data(), sums.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates");
+    });
+    if (o.dedup && consumers) {
+        uint64_t placements = 0, marked = 0;
         for (uint64_t i = 0; i < numpat; ++i)
-            if (mapq[i] != REAL_HIP_MAPQ_NONE && mapq[i] < o.pileup_minmapq) drop[i] = 1;
+            if (REAL_HIP_GAP_STATE(gaps[i].tag) == REAL_HIP_PAIR_UNIQUE) { ++placements; marked += dup[i] != 0; }
+        fprintf(stderr, "duplicates gapped: placements=%llu duplicates=%llu\n", (unsigned long long)placements, (unsigned long long)marked);
     }
+    if (o.mapq) rateMapq(h, T, numpat, mapq, [&]() {
+        check(h, real_hip_mapq(h, info.data(), o.scores ? score.data() : nullptr, acc.data(), numpat, 0, mapq.data()), "real_hip_mapq");
+    });
+    const std::vector<uint8_t> drop = dropMask(o, numpat, dup, [&](uint64_t i) { return mapq[i] != REAL_HIP_MAPQ_NONE && mapq[i] < o.pileup_minmapq; });
     // output, in read order (PatternIdReader re-stream, :1438-1486)
     OutFile out(o.outputfilename);
     uint64_t unique = 0;
@@ -1007,65 +912,45 @@ int matchUnique(const RealOptions &o)
     std::vector<real_hip_gap_place> kept_gaps; // -dedup: a batch's gap records without the marked ones (-pileup_minmapq masks info words only)
     const real_hip_gap_place no_gap = noGapRecord();
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
-        const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
-            for (const ReadItem &it : items) {
-                if (!it.batch.n_reads) continue;
-                if (it.first_id + it.batch.n_reads > numpat) throw std::runtime_error("the read file changed between two passes");
-                check(pc[0]->h, (calls ? real_hip_call_add : real_hip_pileup_add)(pc[0]->h, &it.batch, withoutDuplicates(info, drop, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
-                      calls ? "real_hip_call_add" : "real_hip_pileup_add");
-            }
+        restreamReads(o, pc, qoff, false, T, numpat, nullptr, [&](size_t, const ReadItem &it) {
+            check(pc[0]->h, (calls ? real_hip_call_add : real_hip_pileup_add)(pc[0]->h, &it.batch, withoutDuplicates(info, drop, it.first_id, it.batch.n_reads, kept, [](uint64_t &r) { r = 0; })),
+                  calls ? "real_hip_call_add" : "real_hip_pileup_add");
         });
-        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     }, [&](CtxVec &pc, unsigned, GapLeg leg) { // (-pileup_gapped 1, -vcf_indels 1: the batch given as both mates, its gap records from the matching half)
-        real_hip_ctx *h = pc[0]->h;
-        const uint64_t seen = streamReads(o, pc, qoff, false, T, [&](const std::vector<ReadItem> &items) {
-            for (const ReadItem &it : items) {
-                const uint64_t n = it.batch.n_reads;
-                if (!n) continue;
-                if (it.first_id + n > numpat) throw std::runtime_error("the read file changed between two passes");
-                const real_hip_gap_place *g = withoutDuplicates(gaps, dup, it.first_id, n, kept_gaps, [&](real_hip_gap_place &r) { r = no_gap; });
-                const double tm = now_s();
-                if (leg == kGapPileup) check(h, real_hip_pileup_add_gapped(h, &it.batch, &it.batch, g), "real_hip_pileup_add_gapped");
-                else if (leg == kGapCalls) check(h, real_hip_call_add_gapped(h, &it.batch, &it.batch, g), "real_hip_call_add_gapped");
-                else check(h, real_hip_indel_add(h, &it.batch, &it.batch, g), "real_hip_indel_add");
-                T.match += now_s() - tm;
-            }
+        restreamReads(o, pc, qoff, false, T, numpat, nullptr, [&](size_t, const ReadItem &it) {
+            const real_hip_gap_place *g = withoutDuplicates(gaps, dup, it.first_id, it.batch.n_reads, kept_gaps, [&](real_hip_gap_place &r) { r = no_gap; });
+            const double tm = now_s();
+            addGapLeg(pc[0]->h, leg, it.batch, it.batch, g);
+            T.match += now_s() - tm;
         });
-        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
     GappedLists GL; // -sam_gapped 1: the lists of the reads the gapped pass placed
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
-        const uint64_t seen = streamReads(o, sc, qoff, true, T, [&](const std::vector<ReadItem> &items) {
-            for (const ReadItem &it : items) {
-                const uint64_t n = it.batch.n_reads, base = it.first_id;
-                if (!n) continue;
-                if (base + n > numpat) throw std::runtime_error("the read file changed between two passes");
-                const double tm = now_s();
-                L.fill(sc[0]->h, "real_hip_mismatches", n, real_hip_mismatches, &it.batch, (const uint64_t *)info.data() + base);
-                if (o.sam_gapped) GL.fill(sc[0]->h, n, &it.batch, &it.batch, gaps.data() + base);
-                T.match += now_s() - tm;
-                const ReadSource src = it.src.withQuality(o.fastq, qoff);
-                formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
-                    SamPlace at = samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f);
-                    at.duplicate = o.dedup && dup[base + i];
-                    if (o.mapq) at.mapq = mapq[base + i];
-                    if (o.sam_gapped && !at.placed && REAL_HIP_GAP_STATE(gaps[base + i].tag) == REAL_HIP_PAIR_UNIQUE) {
-                        // placed by its gap record: a line as placed in the pass of the RECORD's file, and none as unplaced in the last one
-                        const real_hip_gap_place &g = gaps[base + i];
-                        if (g.fileid != fi) return;
-                        const ReadView r = src[i];
-                        char cigar[48] = "*";
-                        real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
-                        SamPlace p = samPlaceGapped(g, r.patl, cigar);
-                        p.duplicate = at.duplicate;
-                        appendSam(s, r, refs, p, nullptr, 0, 0, GL.mm.data() + GL.off[i], GL.off[i + 1] - GL.off[i], o.scores);
-                        return;
-                    }
-                    appendSamRead(s, src[i], refs, at, fi, last, L.mm.data() + L.off[i], L.off[i + 1] - L.off[i], o.scores);
-                });
-            }
+        restreamReads(o, sc, qoff, true, T, numpat, nullptr, [&](size_t, const ReadItem &it) {
+            const uint64_t n = it.batch.n_reads, base = it.first_id;
+            const double tm = now_s();
+            L.add(sc[0]->h, "real_hip_mismatches", n, real_hip_mismatches, &it.batch, (const uint64_t *)info.data() + base);
+            if (o.sam_gapped) GL.add(sc[0]->h, n, &it.batch, &it.batch, gaps.data() + base);
+            T.match += now_s() - tm;
+            const ReadSource src = it.src.withQuality(o.fastq, qoff);
+            formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
+                SamPlace at = samPlace(unpack(info[base + i]), o.scores ? score[base + i] : 0.f);
+                at.duplicate = o.dedup && dup[base + i];
+                if (o.mapq) at.mapq = mapq[base + i];
+                if (o.sam_gapped && !at.placed && REAL_HIP_GAP_STATE(gaps[base + i].tag) == REAL_HIP_PAIR_UNIQUE) {
+                    // placed by its gap record: a line as placed in the pass of the RECORD's file, and none as unplaced in the last one
+                    const real_hip_gap_place &g = gaps[base + i];
+                    if (g.fileid != fi) return;
+                    const ReadView r = src[i];
+                    const Cigar cigar = gapCigar(g, r.patl);
+                    SamPlace p = samPlaceGapped(g, r.patl, cigar.s);
+                    p.duplicate = at.duplicate;
+                    appendSam(s, r, refs, p, nullptr, 0, 0, GL.mm.data() + GL.off[i], GL.off[i + 1] - GL.off[i], o.scores);
+                    return;
+                }
+                appendSamRead(s, src[i], refs, at, fi, last, L.mm.data() + L.off[i], L.off[i + 1] - L.off[i], o.scores);
+            });
         });
-        if (seen != numpat) throw std::runtime_error("the read file changed between two passes");
     });
     if (o.sam_gapped)
         fprintf(stderr, "sam gapped: reads=%llu deleted=%llu inserted=%llu disagree=%llu\n", (unsigned long long)GL.mates, (unsigned long long)GL.deleted,
@@ -1121,20 +1006,51 @@ int matchAll(const RealOptions &o)
 // ---- paired-end reads: what the two drivers share (no counterpart in the reference) --------------------------
 real_hip_pair_params pairParams(const RealOptions &o)
 {
-    real_hip_pair_params pp;
-    memset(&pp, 0, sizeof pp);
-    pp.struct_size = sizeof pp; pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
+    real_hip_pair_params pp = sized<real_hip_pair_params>();
+    pp.min_insert = o.insert_min; pp.max_insert = o.insert_max; pp.orientation = 0;
     return pp;
 }
 
-// The next block of each of the two mate files, read in step by the host reader: read i of each are mates.  Returns the
-// number of fragments, 0 at the end of both.
-uint64_t fillMates(const RealOptions &o, ReadReader &r1, ReadReader &r2, ReadBlock &b1, ReadBlock &b2, bool want_ids, uint64_t max_reads = 0)
+// The two mate files of a run and the blocks their reads pass through (a ReadSource made of b1 / b2 follows them).
+struct MateFiles {
+    const RealOptions &o;
+    int qoff1, qoff2;
+    ReadBlock &b1, &b2;
+};
+const char *const kReadFilesChanged = "the read files changed between two passes";
+// One pass over the two mate files from their start, the next block of each read in step by the host reader: read i of each
+// are mates.  onBatch(first, n, rb1, rb2) runs with every batch -- fragments [first, first + n) of the run, in M.b1 / M.b2 and
+// as the batches rb1 / rb2.  limit: at most so many fragments (the probe of -insert_auto), 0: all.  read_s, where given,
+// receives the time spent in the reader.  again: a later pass, in which files that disagree have changed.  Returns the number
+// of fragments seen.
+template <class OnBatch>
+uint64_t streamMates(const MateFiles &M, bool want_ids, uint64_t limit, double *read_s, bool again, OnBatch onBatch)
 {
-    if (!max_reads) max_reads = o.batch_reads;
-    const uint64_t n1 = r1.fillBlock(b1, max_reads, want_ids), n2 = r2.fillBlock(b2, max_reads, want_ids);
-    if (n1 != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
-    return n1;
+    const RealOptions &o = M.o;
+    ReadReader r1(o.patternfilename, o.fastq, M.qoff1), r2(o.pattern2filename, o.fastq2, M.qoff2);
+    uint64_t seen = 0;
+    while (!limit || seen < limit) {
+        const uint64_t room = limit ? std::min<uint64_t>(o.batch_reads, limit - seen) : o.batch_reads;
+        const double t0 = now_s();
+        const uint64_t n = r1.fillBlock(M.b1, room, want_ids), n2 = r2.fillBlock(M.b2, room, want_ids);
+        if (read_s) *read_s += now_s() - t0;
+        if (n != n2 && again) throw std::runtime_error(kReadFilesChanged);
+        if (n != n2) throw std::runtime_error("the two read files hold different numbers of reads (" + o.patternfilename + ", " + o.pattern2filename + ")");
+        if (!n) break;
+        onBatch(seen, n, makeBatch(M.b1), makeBatch(M.b2));
+        seen += n;
+    }
+    return seen;
+}
+// a later pass, which must find the numpat fragments the first pass counted
+template <class OnBatch>
+void restreamMates(const MateFiles &M, bool want_ids, uint64_t numpat, OnBatch onBatch)
+{
+    const uint64_t seen = streamMates(M, want_ids, 0, nullptr, true, [&](uint64_t first, uint64_t n, const real_hip_batch &rb1, const real_hip_batch &rb2) {
+        if (first + n > numpat) throw std::runtime_error(kReadFilesChanged);
+        onBatch(first, n, rb1, rb2);
+    });
+    if (seen != numpat) throw std::runtime_error(kReadFilesChanged);
 }
 
 // the lengths of a block's reads, from its offsets
@@ -1163,94 +1079,48 @@ inline void appendPair(std::string &s, const ReadView &m1, const ReadView &m2, b
 // record, in read order, and the summary line on standard error.
 // -sam_gapped 1: the rescue of a genome file has run with that file's -sam pass (GapRun::rescue, every record started NoMatch,
 // every file folded into them: the same array), so the records and the summed counters are already here and no pass is run.
-real_hip_gap_params gapParams(const RealOptions &o)
-{
-    real_hip_gap_params gp;
-    memset(&gp, 0, sizeof gp);
-    gp.struct_size = sizeof gp; gp.max_gap = (uint32_t)o.gap_max; gp.min_flank = (uint32_t)o.gap_flank;
-    gp.cost_mismatch = 4; gp.cost_open = 6; gp.cost_extend = 1; gp.max_cost = (uint32_t)o.gap_maxcost; gp.margin = (uint32_t)o.gap_margin;
-    return gp;
-}
 // the gap records of the run and the counters of its rescue calls
 struct GapRun {
     std::vector<real_hip_gap_place> gaps;
     real_hip_gap_stats sum;
     bool rescued = false; // the -sam pass ran the rescue
     GapRun() { memset(&sum, 0, sizeof sum); }
-    // every record NoMatch, as a call with fresh != 0 starts them
-    void start(uint64_t numpat)
-    {
-        real_hip_gap_place none;
-        memset(&none, 0, sizeof none);
-        none.second = REAL_HIP_GAP_NONE;
-        gaps.assign(numpat, none);
-    }
+    void start(uint64_t numpat) { gaps.assign(numpat, noGapRecord()); }
     void addStats(real_hip_ctx *h)
     {
-        real_hip_gap_stats st;
-        memset(&st, 0, sizeof st);
-        st.struct_size = sizeof st;
-        check(h, real_hip_gap_stats_get(h, &st, 1), "real_hip_gap_stats_get");
+        const real_hip_gap_stats st = readStats(h, real_hip_gap_stats_get, 1, "real_hip_gap_stats_get");
         sum.eligible += st.eligible; sum.placed += st.placed; sum.unique += st.unique; sum.gapped += st.gapped;
     }
 };
 void gapPass(const RealOptions &o, const std::vector<std::string> &files, const Ranges &RS, Timers &T, const real_hip_pair_params &pp,
              const std::vector<real_hip_pair> &pairs, const std::vector<real_hip_single> &singles1, const std::vector<real_hip_single> &singles2,
-             uint64_t numpat, int qoff1, int qoff2, ReadBlock &b1, ReadBlock &b2, GapRun &run)
+             uint64_t numpat, const MateFiles &M, GapRun &run)
 {
     if (!o.gapped_given) return;
     OutFile out(o.gappedfilename, false, "-gapped");
     const real_hip_gap_params gp = gapParams(o);
-    if (!run.rescued) run.gaps.assign(numpat, real_hip_gap_place());
+    if (!run.rescued) run.start(numpat); // (the first file's calls have fresh != 0: they ignore what the records hold and start each of them so)
     std::vector<real_hip_gap_place> &gaps = run.gaps;
     real_hip_gap_stats &sum = run.sum;
     if (!run.rescued) textPass(o, files, T, [&](CtxVec &gc, unsigned fi, const GenomeText &) {
         real_hip_ctx *h = gc[0]->h;
-        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
-            if (!n) break;
-            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
-            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+        restreamMates(M, false, numpat, [&](uint64_t seen, uint64_t, const real_hip_batch &rb1, const real_hip_batch &rb2) {
             const double tm = now_s();
             check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, fi == 0, gaps.data() + seen),
                   "real_hip_gap_rescue");
             T.match += now_s() - tm;
-            seen += n;
-        }
-        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        });
         run.addStats(h);
     });
-    ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
-    const ReadSource m1(b1), m2(b2);
-    uint64_t base = 0;
-    for (;;) {
-        const uint64_t n = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
-        if (n != n2 || base + n > numpat) throw std::runtime_error("the read files changed between two passes");
-        if (!n) break;
+    const ReadSource m1(M.b1), m2(M.b2);
+    restreamMates(M, true, numpat, [&](uint64_t base, uint64_t n, const real_hip_batch &, const real_hip_batch &) {
         formatAndWrite(n, out.file(), T, [&](uint64_t i, std::string &s) {
             const real_hip_gap_place &g = gaps[base + i];
             if (REAL_HIP_GAP_STATE(g.tag) != REAL_HIP_PAIR_UNIQUE) return;
             const unsigned tm = REAL_HIP_GAP_TARGET(g.tag);
-            const ReadView r = tm ? m2[i] : m1[i];
-            const real_hip_single &a = tm ? singles1[base + i] : singles2[base + i]; // the anchor: the other mate
-            char cigar[48], tail[160];
-            real_hip_gap_cigar(&g, (uint32_t)r.patl, cigar, sizeof cigar);
-            char second[16] = "*";
-            if (g.second != REAL_HIP_GAP_NONE) snprintf(second, sizeof second, "%u", (unsigned)g.second);
-            const int absg = g.gap < 0 ? -g.gap : g.gap;
-            snprintf(tail, sizeof tail, "\t%llu\t%s\t%u\t%u\t%u\t%s\t%llu\n", (unsigned long long)((uint64_t)g.pos - RS.starts[g.fileid][g.frag] + 1), cigar,
-                     (unsigned)(g.k + absg), (unsigned)g.k, (unsigned)g.cost, second, (unsigned long long)((uint64_t)a.pos - RS.starts[a.fileid][a.frag] + 1));
-            s.append(r.id, r.idlen);
-            s += tm ? "\t2\t" : "\t1\t";
-            s += REAL_HIP_GAP_INVERTED(g.tag) ? "-\t" : "+\t";
-            s += RS.names[g.fileid][g.frag];
-            s += tail;
+            appendGapLine(s, g, tm ? m2[i] : m1[i], RS, tm ? 2 : 1, tm ? &singles1[base + i] : &singles2[base + i]); // the anchor: the other mate
         });
-        base += n;
-    }
-    if (base != numpat) throw std::runtime_error("the read files changed between two passes");
+    });
     out.close();
     std::cerr << "gap rescue: eligible=" << sum.eligible << " placed=" << sum.placed << " unique=" << sum.unique << " gapped=" << sum.gapped << std::endl;
 }
@@ -1269,9 +1139,8 @@ int matchPairs(const RealOptions &o)
     CtxVec ctx = makeContexts(o);
     real_hip_ctx *h = ctx[0]->h;
     real_hip_pair_params pp = pairParams(o); // (-insert_auto narrows the bounds before the first batch of the run)
-    real_hip_mate_search_params sp; // -mate_search 1: the search behind the join
-    memset(&sp, 0, sizeof sp);
-    sp.struct_size = sizeof sp; sp.max_anchors = o.mate_search_anchors;
+    real_hip_mate_search_params sp = sized<real_hip_mate_search_params>(); // -mate_search 1: the search behind the join
+    sp.max_anchors = o.mate_search_anchors;
     std::vector<real_hip_pair> pairs;
     const bool unpaired = !o.unpairedfilename.empty();
     const bool singles = unpaired || o.sam_given || o.mapq || o.gapped_given || o.vcf_indels || o.pileup_gapped; // (-sam places the mates of a fragment without a pair as -unpaired prints them; -mapq rates them; -gapped and -vcf_indels 1 take the rescue's anchors from them)
@@ -1280,10 +1149,10 @@ int matchPairs(const RealOptions &o)
     std::vector<uint8_t> dup;                        // -dedup: one mark per fragment, from behind "All done." on
     std::vector<real_hip_mapq_acc> accp, acc1, acc2; // -mapq: the fragments' and the mates' accumulators, kept for the run beside pairs
     std::vector<uint8_t> mapq;                       // -mapq: two qualities per fragment, from behind "All done." on
-    std::vector<uint8_t> drop;                       // what the pileup leaves out: dup, and with -pileup_minmapq the fragments below it
     uint64_t numpat = 0;
     Ranges RS;
     ReadBlock b1, b2;
+    const MateFiles M{o, qoff1, qoff2, b1, b2};
     // the call of a batch, for the run and for the probe of -insert_auto
     // (A: the three accumulators of -mapq 1, null for the probe)
     auto matchBatch = [&](const real_hip_batch &rb1, const real_hip_batch &rb2, real_hip_pair *P, real_hip_single *S1, real_hip_single *S2,
@@ -1302,25 +1171,17 @@ int matchPairs(const RealOptions &o)
     // -insert_auto N: the first N fragments against the first genome file under the window -insert_min .. -insert_max; the
     // quartiles of their Unique outer distances give the bounds of the run
     auto estimateBounds = [&]() {
-        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
         std::vector<real_hip_pair> probe;
         std::vector<real_hip_single> ps1, ps2;
         std::vector<uint64_t> hist((size_t)o.insert_max + 2, 0);
-        uint64_t seen = 0;
-        while (seen < o.insert_auto) {
-            const uint64_t n = fillMates(o, r1, r2, b1, b2, false, std::min<uint64_t>(o.batch_reads, o.insert_auto - seen));
-            if (!n) break;
+        const uint64_t seen = streamMates(M, false, o.insert_auto, nullptr, false, [&](uint64_t first, uint64_t n, real_hip_batch rb1, real_hip_batch rb2) {
             probe.resize(n);
             if (singles) { ps1.resize(n); ps2.resize(n); }
-            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = 1;
             matchBatch(rb1, rb2, probe.data(), ps1.data(), ps2.data());
-            insertHist(probe.data(), n, seen == 0, hist);
-            seen += n;
-        }
-        real_hip_insert_estimate est;
-        memset(&est, 0, sizeof est);
-        est.struct_size = sizeof est;
+            insertHist(probe.data(), n, first == 0, hist);
+        });
+        real_hip_insert_estimate est = sized<real_hip_insert_estimate>();
         const int rc = real_hip_insert_bounds(hist.data(), (uint32_t)hist.size(), REAL_HIP_INSERT_MIN_COUNT, 3, &est);
         if (rc == REAL_HIP_E_STATE)
             throw std::runtime_error("-insert_auto: only " + std::to_string(est.n) + " of the first " + std::to_string(seen) + " fragments are placed uniquely (" +
@@ -1339,57 +1200,37 @@ int matchPairs(const RealOptions &o)
             estimateBounds();
             T.match += now_s() - tm;
         }
-        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const double t0 = now_s();
-            const uint64_t n = fillMates(o, r1, r2, b1, b2, false);
-            T.read += now_s() - t0;
-            if (!n) break;
-            if (seen + n > pairs.size()) pairs.resize(std::max<uint64_t>(seen + n, pairs.size() + pairs.size() / 2));
+        const uint64_t seen = streamMates(M, false, 0, &T.read, false, [&](uint64_t first, uint64_t n, real_hip_batch rb1, real_hip_batch rb2) {
+            if (first + n > pairs.size()) pairs.resize(std::max<uint64_t>(first + n, pairs.size() + pairs.size() / 2));
             if (singles && pairs.size() > singles1.size()) { singles1.resize(pairs.size()); singles2.resize(pairs.size()); }
             if (o.dedup && pairs.size() > sums1.size()) { sums1.resize(pairs.size()); sums2.resize(pairs.size()); }
             if (o.mapq && pairs.size() > accp.size())
                 for (auto *a : {&accp, &acc1, &acc2}) a->resize(pairs.size(), kNoCandidates);
-            real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
             rb1.fresh = rb2.fresh = (fi == 0); // first genome file: the records start on the device
-            real_hip_mapq_acc *const A[3] = {o.mapq ? accp.data() + seen : nullptr, o.mapq ? acc1.data() + seen : nullptr, o.mapq ? acc2.data() + seen : nullptr};
+            real_hip_mapq_acc *const A[3] = {o.mapq ? accp.data() + first : nullptr, o.mapq ? acc1.data() + first : nullptr, o.mapq ? acc2.data() + first : nullptr};
             const double tm = now_s();
-            matchBatch(rb1, rb2, pairs.data() + seen, singles ? singles1.data() + seen : nullptr, singles ? singles2.data() + seen : nullptr, o.mapq ? A : nullptr);
+            matchBatch(rb1, rb2, pairs.data() + first, singles ? singles1.data() + first : nullptr, singles ? singles2.data() + first : nullptr, o.mapq ? A : nullptr);
             if (o.dedup && fi == 0) { // (the first pass over the reads: no pass of its own)
-                check(h, real_hip_read_summary(h, &rb1, (uint32_t)o.dedup_minq, sums1.data() + seen), "real_hip_read_summary");
-                check(h, real_hip_read_summary(h, &rb2, (uint32_t)o.dedup_minq, sums2.data() + seen), "real_hip_read_summary");
+                check(h, real_hip_read_summary(h, &rb1, (uint32_t)o.dedup_minq, sums1.data() + first), "real_hip_read_summary");
+                check(h, real_hip_read_summary(h, &rb2, (uint32_t)o.dedup_minq, sums2.data() + first), "real_hip_read_summary");
             }
             T.match += now_s() - tm;
-            seen += n;
-        }
+        });
         if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
-        else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        else if (seen != numpat) throw std::runtime_error(kReadFilesChanged);
     });
     std::cerr << "All done." << std::endl;
-    if (o.dedup) {
-        dup.assign(numpat, 0);
-        const double tm = now_s();
+    if (o.dedup) markDuplicates(h, o, T, numpat, dup, [&]() {
         check(h, real_hip_mark_duplicates_pairs(h, pairs.data(), sums1.data(), sums2.data(), numpat, 0, dup.data()), "real_hip_mark_duplicates_pairs");
-        T.match += now_s() - tm;
-        reportDuplicates(h, o);
-    }
-    if (o.mapq) {
-        mapq.assign(2 * numpat, REAL_HIP_MAPQ_NONE);
-        const double tm = now_s();
+    });
+    if (o.mapq) rateMapq(h, T, 2 * numpat, mapq, [&]() {
         check(h, real_hip_mapq_pairs(h, pairs.data(), singles1.data(), singles2.data(), accp.data(), acc1.data(), acc2.data(), numpat, 0, mapq.data()), "real_hip_mapq_pairs");
-        T.match += now_s() - tm;
-        reportMapq(h, mapq);
-    }
-    drop = dup;
-    if (o.pileup_minmapq > 0) { // (both mates of a Unique fragment carry the fragment's quality: "either below" is "both below")
-        drop.resize(numpat, 0);
-        for (uint64_t i = 0; i < numpat; ++i)
-            if (pairs[i].state == REAL_HIP_PAIR_UNIQUE && mapq[2 * i] < o.pileup_minmapq) drop[i] = 1;
-    }
+    });
+    // (both mates of a Unique fragment carry the fragment's quality: "either below" is "both below")
+    const std::vector<uint8_t> drop = dropMask(o, numpat, dup, [&](uint64_t i) { return pairs[i].state == REAL_HIP_PAIR_UNIQUE && mapq[2 * i] < o.pileup_minmapq; });
     OutFile out(o.outputfilename);
     std::unique_ptr<OutFile> uout(unpaired ? new OutFile(o.unpairedfilename, true) : nullptr);
-    uint64_t unique = 0, base = 0;
+    uint64_t unique = 0;
     // -insert_hist <file>: the outer distances of the final Unique records, batch by batch (the last bin: what lies beyond the bounds)
     const bool insert_hist = !o.inserthistfilename.empty();
     std::vector<uint64_t> hist(insert_hist ? (size_t)pp.max_insert + 2 : 0, 0);
@@ -1401,12 +1242,8 @@ int matchPairs(const RealOptions &o)
         appendLine(s, r, o.scores, Placement{S.score, REAL_HIP_SINGLE_INVERTED(S.tag) != 0, RS.names[S.fileid][S.frag],
                                              (uint64_t)S.pos - RS.starts[S.fileid][S.frag] + 1, REAL_HIP_SINGLE_K(S.tag)});
     };
-    ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
     const ReadSource m1(b1), m2(b2);
-    for (;;) {
-        const uint64_t n = r1.fillBlock(b1, o.batch_reads, true), n2 = r2.fillBlock(b2, o.batch_reads, true);
-        if (n != n2 || base + n > numpat) throw std::runtime_error("the read files changed between two passes");
-        if (!n) break;
+    restreamMates(M, true, numpat, [&](uint64_t base, uint64_t n, const real_hip_batch &, const real_hip_batch &) {
         if (insert_hist) insertHist(pairs.data() + base, n, base == 0, hist);
         if (unpaired)
             formatAndWrite(n, uout->file(), T, [&](uint64_t i, std::string &s) {
@@ -1419,9 +1256,7 @@ int matchPairs(const RealOptions &o)
             if (P.state != REAL_HIP_PAIR_UNIQUE) return;
             appendPair(s, m1[i], m2[i], o.scores, P, RS.names[P.fileid][P.frag], RS.starts[P.fileid][P.frag]);
         });
-        base += n;
-    }
-    if (base != numpat) throw std::runtime_error("the read files changed between two passes");
+    });
     out.close();
     for (uint64_t i = 0; i < numpat; ++i) unique += pairs[i].state == REAL_HIP_PAIR_UNIQUE;
     std::cerr << "unique fragments: " << unique << std::endl;
@@ -1438,9 +1273,7 @@ int matchPairs(const RealOptions &o)
         for (size_t d = 0; d < hist.size(); ++d)
             if (hist[d]) ok = fprintf(hist_file, "%zu\t%llu\n", d, (unsigned long long)hist[d]) > 0 && ok;
         if ((fclose(hist_file) != 0) || !ok) throw std::runtime_error("write to the -insert_hist file failed");
-        real_hip_insert_estimate est;
-        memset(&est, 0, sizeof est);
-        est.struct_size = sizeof est;
+        real_hip_insert_estimate est = sized<real_hip_insert_estimate>();
         const int rc = real_hip_insert_bounds(hist.data(), (uint32_t)hist.size(), REAL_HIP_INSERT_MIN_COUNT, 3, &est);
         if (rc == REAL_HIP_E_STATE)
             std::cerr << "insert size: fewer than " << REAL_HIP_INSERT_MIN_COUNT << " unique fragments (n=" << est.n << "), no quartiles" << std::endl;
@@ -1457,39 +1290,21 @@ int matchPairs(const RealOptions &o)
     const real_hip_gap_params gp = gapParams(o);
     if (o.vcf_indels || o.pileup_gapped || o.sam_gapped) { gap_run.start(numpat); gap_run.rescued = true; }
     pileupPass(o, files, RS, T, [&](CtxVec &pc, bool calls) {
-        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
-            if (!n) break;
-            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
-            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+        restreamMates(M, false, numpat, [&](uint64_t seen, uint64_t n, const real_hip_batch &rb1, const real_hip_batch &rb2) {
             check(pc[0]->h, (calls ? real_hip_call_add_pairs : real_hip_pileup_add_pairs)(pc[0]->h, &rb1, &rb2, withoutDuplicates(pairs, drop, seen, n, kept, [](real_hip_pair &P) { P.state = REAL_HIP_PAIR_NOMATCH; })),
                   calls ? "real_hip_call_add_pairs" : "real_hip_pileup_add_pairs");
-            seen += n;
-        }
-        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        });
     }, [&](CtxVec &pc, unsigned, GapLeg leg) {
         real_hip_ctx *h = pc[0]->h;
         const bool rescue = leg == kGapPileup || (leg == kGapIndels && !o.pileup_gapped);
-        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const uint64_t n = fillMates(o, q1, q2, b1, b2, false);
-            if (!n) break;
-            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
-            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+        restreamMates(M, false, numpat, [&](uint64_t seen, uint64_t, const real_hip_batch &rb1, const real_hip_batch &rb2) {
             const double tm = now_s();
             if (rescue)
                 check(h, real_hip_gap_rescue(h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0, gap_run.gaps.data() + seen),
                       "real_hip_gap_rescue");
-            if (leg == kGapPileup) check(h, real_hip_pileup_add_gapped(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_pileup_add_gapped");
-            else if (leg == kGapCalls) check(h, real_hip_call_add_gapped(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_call_add_gapped");
-            else check(h, real_hip_indel_add(h, &rb1, &rb2, gap_run.gaps.data() + seen), "real_hip_indel_add");
+            addGapLeg(h, leg, rb1, rb2, gap_run.gaps.data() + seen);
             T.match += now_s() - tm;
-            seen += n;
-        }
-        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        });
         if (rescue) gap_run.addStats(h);
     });
     // -sam_gapped 1: the pass of a genome file rescues the fragments whose anchor lies in it (unless -vcf_indels 1 has done so), lists
@@ -1497,22 +1312,16 @@ int matchPairs(const RealOptions &o)
     GappedLists GL;
     const bool sam_rescues = o.sam_gapped && !o.vcf_indels && !o.pileup_gapped;
     samPass(o, files, RS, T, [&](CtxVec &sc, unsigned fi, bool last, const SamRefs &refs, SamLists &L, FILE *sam) {
-        ReadReader q1(o.patternfilename, o.fastq, qoff1), q2(o.pattern2filename, o.fastq2, qoff2);
         const ReadSource v1 = m1.withQuality(o.fastq, qoff1), v2 = m2.withQuality(o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const uint64_t n = fillMates(o, q1, q2, b1, b2, true);
-            if (!n) break;
-            if (seen + n > numpat) throw std::runtime_error("the read files changed between two passes");
-            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+        restreamMates(M, true, numpat, [&](uint64_t seen, uint64_t n, const real_hip_batch &rb1, const real_hip_batch &rb2) {
             const double tm = now_s();
-            L.fill(sc[0]->h, "real_hip_mismatches_pairs", 2 * n, real_hip_mismatches_pairs, &rb1, &rb2, (const real_hip_pair *)pairs.data() + seen,
-                   (const real_hip_single *)singles1.data() + seen, (const real_hip_single *)singles2.data() + seen);
+            L.add(sc[0]->h, "real_hip_mismatches_pairs", 2 * n, real_hip_mismatches_pairs, &rb1, &rb2, (const real_hip_pair *)pairs.data() + seen,
+                  (const real_hip_single *)singles1.data() + seen, (const real_hip_single *)singles2.data() + seen);
             if (o.sam_gapped) {
                 if (sam_rescues)
                     check(sc[0]->h, real_hip_gap_rescue(sc[0]->h, &pp, &gp, &rb1, &rb2, pairs.data() + seen, singles1.data() + seen, singles2.data() + seen, 0,
                                                         gap_run.gaps.data() + seen), "real_hip_gap_rescue");
-                GL.fill(sc[0]->h, n, &rb1, &rb2, gap_run.gaps.data() + seen);
+                GL.add(sc[0]->h, n, &rb1, &rb2, gap_run.gaps.data() + seen);
             }
             T.match += now_s() - tm;
             formatAndWrite(n, sam, T, [&](uint64_t i, std::string &s) {
@@ -1522,21 +1331,17 @@ int matchPairs(const RealOptions &o)
                 if (o.mapq) { at[0].mapq = mapq[2 * (seen + i)]; at[1].mapq = mapq[2 * (seen + i) + 1]; }
                 if (o.sam_gapped && REAL_HIP_GAP_STATE(gap_run.gaps[seen + i].tag) == REAL_HIP_PAIR_UNIQUE && gap_run.gaps[seen + i].fileid <= fi) { // (a later file's record: -vcf_indels 1 ran the rescue of every file first)
                     const real_hip_gap_place &g = gap_run.gaps[seen + i];
-                    char cigar[48] = "*";
-                    real_hip_gap_cigar(&g, (uint32_t)r[REAL_HIP_GAP_TARGET(g.tag)].patl, cigar, sizeof cigar);
-                    appendSamRescued(s, r, refs, at, g, cigar, fi, pp.min_insert, pp.max_insert, L.mm.data(), L.off.data(), i, GL.mm.data() + GL.off[i],
-                                     GL.off[i + 1] - GL.off[i], o.scores);
+                    appendSamRescued(s, r, refs, at, g, gapCigar(g, r[REAL_HIP_GAP_TARGET(g.tag)].patl).s, fi, pp.min_insert, pp.max_insert, L.mm.data(), L.off.data(), i,
+                                     GL.mm.data() + GL.off[i], GL.off[i + 1] - GL.off[i], o.scores);
                 } else appendSamFragment(s, r, refs, at, fi, last, L.mm.data(), L.off.data(), i, o.scores);
             });
-            seen += n;
-        }
-        if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        });
         if (sam_rescues) gap_run.addStats(sc[0]->h);
     });
     if (o.sam_gapped)
         fprintf(stderr, "sam gapped: mates=%llu deleted=%llu inserted=%llu disagree=%llu\n", (unsigned long long)GL.mates, (unsigned long long)GL.deleted,
                 (unsigned long long)GL.inserted, (unsigned long long)GL.disagree);
-    gapPass(o, files, RS, T, pp, pairs, singles1, singles2, numpat, qoff1, qoff2, b1, b2, gap_run);
+    gapPass(o, files, RS, T, pp, pairs, singles1, singles2, numpat, M, gap_run);
     T.finish(2 * numpat, 2 * unique);
     return EXIT_SUCCESS;
 }
@@ -1558,16 +1363,10 @@ int matchPairsAll(const RealOptions &o)
     std::vector<uint64_t> poff;
     uint64_t numpat = 0, n_pairs = 0;
     ReadBlock b1, b2;
+    const MateFiles M{o, qoff1, qoff2, b1, b2};
     const ReadSource m1(b1), m2(b2);
     for (unsigned fi = 0; fi < files.size(); ++fi) genomePass(o, ctx, files, fi, kSayLast | kOneBlock, T, nullptr, [&](Resident &R) {
-        ReadReader r1(o.patternfilename, o.fastq, qoff1), r2(o.pattern2filename, o.fastq2, qoff2);
-        uint64_t seen = 0;
-        for (;;) {
-            const double t0 = now_s();
-            const uint64_t n = fillMates(o, r1, r2, b1, b2, true);
-            T.read += now_s() - t0;
-            if (!n) break;
-            const real_hip_batch rb1 = makeBatch(b1), rb2 = makeBatch(b2);
+        const uint64_t seen = streamMates(M, true, 0, &T.read, false, [&](uint64_t, uint64_t n, const real_hip_batch &rb1, const real_hip_batch &rb2) {
             poff.assign(n + 1, 0);
             if (hits.size() < n + n / 4 + 1024) hits.resize(n + n / 4 + 1024); // (about one pair per fragment is the rule: room for a quarter more)
             const double tm = now_s();
@@ -1580,10 +1379,9 @@ int matchPairsAll(const RealOptions &o)
                     appendPair(s, v1, v2, o.scores, P, R.G.frag_names[P.frag], R.G.frag_start[P.frag]);
                 }
             });
-            seen += n;
-        }
+        });
         if (fi == 0) { numpat = seen; std::cerr << "number of fragments " << numpat << std::endl; }
-        else if (seen != numpat) throw std::runtime_error("the read files changed between two passes");
+        else if (seen != numpat) throw std::runtime_error(kReadFilesChanged);
     });
     out.close();
     std::cerr << "All done." << std::endl;

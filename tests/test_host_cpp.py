@@ -203,3 +203,58 @@ def test_gap_record_geometry_against_the_checkers_rule(selftest):
     fit = got[got[:, 4] == 1]
     assert 0 < fit.shape[0] < got.shape[0] // 3 and set(fit[:, 0]) == {1, 2, 31, 32, 33, 320}      # (L = 1 fits without a gap only)
     assert not fit[fit[:, 0] == 1][:, 1].any() and set(fit[:, 1]) == set(range(-16, 17)) and (fit[:, 3] + fit[:, 0] + fit[:, 1] <= n).all()
+
+
+def _chunk_records(fmt, nl, final_newline):
+    """seven records of lengths 1, 36, 100, 1, 5, 100, 2 with ids of different lengths, one line per field"""
+    recs = []
+    for k, n in enumerate([1, 36, 100, 1, 5, 100, 2]):
+        rid, seq = "r" + "x" * (3 * k) + str(k), "ACGT" * (n // 4) + "ACGT"[:n % 4]
+        recs.append(("@" + rid + nl + seq + nl + "+" + nl + "I" * n + nl) if fmt == "fastq" else (">" + rid + nl + seq + nl))
+    if not final_newline:
+        recs[-1] = recs[-1][:-len(nl)]
+    return [r.encode() for r in recs]
+
+
+@pytest.mark.parametrize("buffers", [1, 2])
+@pytest.mark.parametrize("fmt,nl,final_newline", [("fastq", "\n", True), ("fasta", "\n", True), ("fastq", "\r\n", True), ("fastq", "\n", False),
+                                                  ("empty", "\n", True)])
+def test_read_chunks(selftest, tmp_path, fmt, nl, final_newline, buffers):
+    """RawChunker (real_amd/host/RawChunker.hpp) through `host_selftest chunks`: the text chunks of a read file, with malloc'd
+    buffers.  What must hold follows from the file alone: the chunks concatenated are the file, file_offset is the running sum
+    of the sizes, no chunk is empty or larger than the capacity, and every chunk but the last ends behind a newline and holds a
+    multiple of 4 (FASTQ) or 2 (FASTA) lines -- whole records.  Capacities: exactly the longest record, one byte more, the
+    longest plus the shortest, the whole file, the whole file plus one; one buffer (every chunk is handed back before the next
+    is read) and two (the prefetch runs ahead).  An empty file gives no chunk.  A capacity below the longest record ends with
+    the message of `real` and a non-zero status."""
+    recs = [] if fmt == "empty" else _chunk_records(fmt, nl, final_newline)
+    data = b"".join(recs)
+    path, out = tmp_path / "reads.txt", tmp_path / "chunks.bin"
+    open(path, "wb").write(data)
+    fastq, lpr = ("0", 2) if fmt == "fasta" else ("1", 4)
+
+    def run(cap):
+        r = subprocess.run([selftest, "chunks", str(path), fastq, str(cap), str(buffers), str(out)], stderr=subprocess.PIPE, universal_newlines=True)
+        raw, chunks, at = open(out, "rb").read(), [], 0
+        while r.returncode == 0 and at < len(raw):
+            off, size = (int(v) for v in np.frombuffer(raw[at:at + 16], dtype=np.uint64))
+            chunks.append((off, raw[at + 16:at + 16 + size]))
+            assert len(chunks[-1][1]) == size
+            at += 16 + size
+        return r, chunks
+
+    if not recs:
+        r, chunks = run(64)
+        assert r.returncode == 0 and chunks == []
+        return
+    longest, shortest = max(len(r) for r in recs), min(len(r) for r in recs)
+    for cap in (longest, longest + 1, longest + shortest, len(data), len(data) + 1):
+        r, chunks = run(cap)
+        assert r.returncode == 0, (cap, r.stderr)
+        assert b"".join(c for _, c in chunks) == data, cap
+        assert [off for off, _ in chunks] == [int(v) for v in np.cumsum([0] + [len(c) for _, c in chunks[:-1]])], cap
+        assert all(0 < len(c) <= cap for _, c in chunks), cap
+        assert all(c.endswith(b"\n") and c.count(b"\n") % lpr == 0 for _, c in chunks[:-1]), cap
+        assert len(chunks) > 1 or cap >= len(data), cap
+    r, chunks = run(longest - 1)
+    assert r.returncode != 0 and r.returncode > 0 and "a read record longer than the text chunk" in r.stderr, (r.returncode, r.stderr)
