@@ -11,6 +11,7 @@
 // fragment, none per cell).  No LDS, no scratch memory; plain C++ and 16-byte vector stores.
 #include "real_hip_internal.h"
 #include "pair_state.h"
+#include "rocprim_call.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -136,20 +137,19 @@ int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const M
     if ((rc = rh_reserve(ctx, ctx->pa_cnt, (n + 1) * 8))) return rc;
     const PairAllArgs A = pair_all_args(ctx, pp, L, n, 0, d_off);
     RH_HIP(ctx, hipMemsetAsync(ctx->pair_list.p, 0, 8, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, ctx->pair_all);
-    hipLaunchKernelGGL(pair_all_lane_kernel<false>, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, ctx->stream, A);
-    RH_HIP(ctx, hipGetLastError());
-    if (n) {
-        hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+    { // (the bracket ends before the read-back)
+        RhTimed timed(ctx, ctx->stream, ctx->pair_all);
+        rh_launch_each(pair_all_lane_kernel<false>, n + 1, ctx->stream, A);
         RH_HIP(ctx, hipGetLastError());
+        if (n) {
+            hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+            RH_HIP(ctx, hipGetLastError());
+            ctx->pair_all.launches += 1;
+        }
         ctx->pair_all.launches += 1;
+        auto scan = [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, A.cnt, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream); };
+        if ((rc = rh_prim_run(ctx, ctx->sort_tmp, scan, "pair count scan"))) return rc;
     }
-    ctx->pair_all.launches += 1;
-    size_t tmp = 0;
-    RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, A.cnt, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream));
-    if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
-    RH_HIP(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, A.cnt, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream));
-    rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ctx->pair_all.items += n;
@@ -164,11 +164,12 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Ma
     if (!n || !total) return REAL_HIP_OK;
     PairAllArgs A = pair_all_args(ctx, pp, L, n, fileid, d_off);
     A.out = (uint4 *)d_out; A.cap = cap;
-    rh_time_begin(ctx, ctx->stream, ctx->pair_all);
-    hipLaunchKernelGGL(pair_all_lane_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
-    RH_HIP(ctx, hipGetLastError());
-    hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
-    rh_time_end(ctx, ctx->stream);
+    {
+        RhTimed timed(ctx, ctx->stream, ctx->pair_all);
+        rh_launch_each(pair_all_lane_kernel<true>, n, ctx->stream, A);
+        RH_HIP(ctx, hipGetLastError());
+        hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
+    }
     RH_HIP(ctx, hipGetLastError());
     ctx->pair_all.launches += 2;
     ctx->pa_pairs_out += total;

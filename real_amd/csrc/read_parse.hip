@@ -9,6 +9,7 @@
 // reader (real_amd/host/ReadReader.cpp), which implements the general form.
 #include "real_hip_internal.h"
 
+#include "rocprim_call.h"
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -307,10 +308,8 @@ int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int 
         uint32_t *bc = (uint32_t *)ctx->p_len1.p, *bo = bc + nblk + 1;
         hipLaunchKernelGGL(nl_count_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_text, n_bytes, bc, d_cr);
         RH_HIP(ctx, hipMemsetAsync(bc + nblk, 0, 4, ctx->stream));
-        size_t tmp = 0;
-        RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, bc, bo, 0u, (size_t)(nblk + 1), rocprim::plus<uint32_t>(), ctx->stream));
-        if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
-        RH_HIP(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, bc, bo, 0u, (size_t)(nblk + 1), rocprim::plus<uint32_t>(), ctx->stream));
+        auto scan = [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, bc, bo, 0u, (size_t)(nblk + 1), rocprim::plus<uint32_t>(), ctx->stream); };
+        if ((rc = rh_prim_run(ctx, ctx->sort_tmp, scan, "newline scan"))) return rc;
         hipLaunchKernelGGL(nl_fill_kernel, dim3((unsigned)nblk), dim3(256), 0, ctx->stream, d_text, n_bytes, (const uint32_t *)bo,
                            (uint32_t *)ctx->p_nl.p);
         uint32_t h_m = 0;
@@ -322,12 +321,10 @@ int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int 
         const unsigned int one = 1;
         RH_HIP(ctx, hipMemcpyAsync(d_cr, &one, 4, hipMemcpyHostToDevice, ctx->stream));
         IsNewline pred{d_text};
-        size_t tmp = 0;
-        RH_HIP(ctx, rocprim::select(nullptr, tmp, rocprim::counting_iterator<uint32_t>(0), (uint32_t *)ctx->p_nl.p, d_count,
-                                    (size_t)n_bytes, pred, ctx->stream));
-        if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
-        RH_HIP(ctx, rocprim::select(ctx->sort_tmp.p, tmp, rocprim::counting_iterator<uint32_t>(0), (uint32_t *)ctx->p_nl.p, d_count,
-                                    (size_t)n_bytes, pred, ctx->stream));
+        auto select = [&](void *tmp, size_t &bytes) {
+            return rocprim::select(tmp, bytes, rocprim::counting_iterator<uint32_t>(0), (uint32_t *)ctx->p_nl.p, d_count, (size_t)n_bytes, pred, ctx->stream);
+        };
+        if ((rc = rh_prim_run(ctx, ctx->sort_tmp, select, "newline select"))) return rc;
         RH_HIP(ctx, hipMemcpyAsync(&m, d_count, sizeof(size_t), hipMemcpyDeviceToHost, ctx->stream));
         RH_HIP(ctx, hipMemcpyAsync(&last, d_text + n_bytes - 1, 1, hipMemcpyDeviceToHost, ctx->stream));
         RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -350,12 +347,10 @@ int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int 
         RH_HIP(ctx, hipMemcpyAsync(ctx->p_len1.p, seq_len, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
         RH_HIP(ctx, hipMemsetAsync((uint32_t *)ctx->p_len1.p + n, 0, 4, ctx->stream));
         rocprim::transform_iterator<const uint32_t *, LenToU64, uint64_t> in((const uint32_t *)ctx->p_len1.p, LenToU64());
-        size_t tmp = 0;
-        RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, in, (uint64_t *)ctx->p_off.p, (uint64_t)0, (size_t)(n + 1),
-                                            rocprim::plus<uint64_t>(), ctx->stream));
-        if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
-        RH_HIP(ctx, rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, in, (uint64_t *)ctx->p_off.p, (uint64_t)0, (size_t)(n + 1),
-                                            rocprim::plus<uint64_t>(), ctx->stream));
+        auto scan = [&](void *tmp, size_t &bytes) {
+            return rocprim::exclusive_scan(tmp, bytes, in, (uint64_t *)ctx->p_off.p, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream);
+        };
+        if ((rc = rh_prim_run(ctx, ctx->sort_tmp, scan, "read offsets scan"))) return rc;
     }
     uint64_t total = 0;
     unsigned int h[4] = {0, 0, 0, 0};

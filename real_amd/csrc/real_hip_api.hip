@@ -12,8 +12,6 @@
 #include <cstring>
 #include <new>
 
-int rh_count_wild(real_hip_ctx *ctx, uint64_t n);
-
 // ---------------------------------------------------------------------------
 // plumbing
 // ---------------------------------------------------------------------------
@@ -477,16 +475,15 @@ extern "C" int real_hip_index_download(real_hip_ctx *ctx, int list, uint32_t *en
     if (list < 0 || list > 5) return rh_fail(ctx, REAL_HIP_E_INVALID, "list", hipSuccess);
     const uint64_t n = ctx->n_entries;
     if (ctx->layout == RH_LAYOUT_ROWS) { // bucket rows: entries and bucket starts by an ordered traversal of the rows
+        const size_t nbk = ((size_t)1 << ctx->pb) + 1;
         ScopedBuf e(ctx), st(ctx);
+        RhSyncOnExit sync(ctx); // (before the two go)
         int rc;
         if ((rc = rh_reserve(ctx, e, (n ? n : 1) * sizeof(uint2)))) return rc;
-        if ((rc = rh_reserve(ctx, st, (((size_t)1 << ctx->pb) + 1) * 4))) return rc;
-        rc = rh_rows_unpack(ctx, list, (uint2 *)e.p, (uint32_t *)st.p, true); // (the canonical order, not the physical one)
-        hipError_t he = hipSuccess;
-        if (!rc && n && entries) he = hipMemcpy(entries, e.p, n * sizeof(uint2), hipMemcpyDeviceToHost);
-        if (!rc && he == hipSuccess && bucket) he = hipMemcpy(bucket, st.p, (((size_t)1 << ctx->pb) + 1) * 4, hipMemcpyDeviceToHost);
-        if (rc) return rc;
-        if (he != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "index download", he);
+        if ((rc = rh_reserve(ctx, st, nbk * 4))) return rc;
+        if ((rc = rh_rows_unpack(ctx, list, (uint2 *)e.p, (uint32_t *)st.p, true))) return rc; // (the canonical order, not the physical one)
+        if (n && entries) RH_HIP(ctx, hipMemcpy(entries, e.p, n * sizeof(uint2), hipMemcpyDeviceToHost));
+        if (bucket) RH_HIP(ctx, hipMemcpy(bucket, st.p, nbk * 4, hipMemcpyDeviceToHost));
         return REAL_HIP_OK;
     }
     if (n && entries) RH_HIP(ctx, hipMemcpy(entries, ctx->ent[list].p, n * sizeof(uint2), hipMemcpyDeviceToHost));
@@ -498,7 +495,6 @@ extern "C" int real_hip_index_download(real_hip_ctx *ctx, int list, uint32_t *en
     return REAL_HIP_OK;
 }
 
-int rh_index_export(real_hip_ctx *ctx, int list, void *h_sign, uint32_t *h_pos);
 extern "C" int real_hip_index_export(real_hip_ctx *ctx, int list, void *sign, uint32_t *pos)
 {
     RH_ENTER(ctx);

@@ -28,9 +28,7 @@ struct DevText {
     uint32_t fileid;
 };
 
-// The resident index layout, what the bucket tables bkt[] hold (the values real_hip_index_table_kind reports): 2^pb + 1 bucket
-// starts (u32); a digest or a fingerprint directory (uint4 per bucket, below); one 128-byte row per bucket (format below)
-enum RhLayout : uint32_t { RH_LAYOUT_STARTS = 0, RH_LAYOUT_DIGEST = 1, RH_LAYOUT_FINGERPRINT = 2, RH_LAYOUT_ROWS = 3 };
+#include "index_plan.h" // RhLayout, RhTables, rh_index_geometry, rh_digest_geometry, rh_plan_tables (no HIP: the host self-test compiles it too)
 
 // One entry of a sorted list: {fingerprint, window start}.  The fingerprint is
 // 32 bits of the signature just below the bucket prefix; entries of a bucket
@@ -56,9 +54,7 @@ static inline __host__ __device__ bool rh_wide_entries(const DevIndex &ix) { ret
 // (bit tables: la is a run-time value in some callers, an array indexed by it would live in scratch memory)
 static inline __host__ __device__ uint2 rh_list_segs(uint32_t la) { return make_uint2((0x940u >> (2 * la)) & 3u, (0xfb9u >> (2 * la)) & 3u); }
 
-// digest directories: uint4 {start, 8 x {size:4, partner digest:8}}: the prefix is all signature bits but one to three, so a
-// bucket has at most eight key groups (= signature values) and its 16-byte table entry describes each of them
-static inline bool rh_digest_geometry(uint32_t l, uint32_t pb) { return l >= pb && l - pb >= 1 && l - pb <= 3; }
+// digest directories (geometry: index_plan.h): uint4 {start, 8 x {size:4, partner digest:8}} per bucket
 #define RH_DIGEST_SAT 15u /* group size field: 15 = "15 or more", bounds by binary search */
 // fingerprint directories: uint4 {start, count:8 | 8 x fingerprint:11}: the first eight entries of the bucket by an
 // 11-bit hash of their 32-bit key; a lookup whose own fingerprint is not among them reads no entry at all
@@ -129,21 +125,6 @@ static inline __host__ __device__ uint2 rh_row_entry(const uint32_t *row, uint32
 // reference's equal range in its order (the sort is stable: ascending position inside equal signatures; the order of
 // DIFFERENT signatures in the device list is the mixed one, real_hip_index_export sorts it back).
 #include "row_addr.h" // RH_MIX32 / rh_mix32 / rh_mix64 and the addressing of the pair tables (no HIP: the host self-test compiles it too)
-
-// entry geometry shared by the index build and the matcher
-static inline void rh_index_geometry(uint32_t l, uint32_t pb, uint32_t *pshift, uint32_t *fshift, uint32_t *fbits, uint32_t *pbits)
-{
-    const uint32_t R = l - pb; // signature bits below the bucket prefix
-    *pshift = R;
-    if (R <= 30) {
-        uint32_t pbts = (32 - R) & ~1u;
-        if (pbts > l) pbts = l;
-        if (pbts > 30) pbts = 30;
-        *fshift = 0; *fbits = R; *pbits = pbts;
-    } else {
-        *fshift = R - 32; *fbits = 32; *pbits = 0;
-    }
-}
 
 // a batch of reads as the caller holds it (real_hip_batch): the matcher reads these arrays itself
 struct DevBatch {
@@ -393,6 +374,15 @@ struct RhTimer { // HIP events on the ctx stream around a group of launches
     ~RhTimer();
 };
 
+// the launch of a kernel that takes one thread per element, 256 to a block; nothing is launched for n = 0.  The arguments
+// convert as they do in a plain launch: implicitly, so a pointer of another type does not compile
+template <typename... P, typename... A>
+static inline void rh_launch_each(void (*kernel)(P...), uint64_t n, hipStream_t st, const A &...args)
+{
+    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
+    if (n) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, args...);
+}
+
 // ---- kernels launchers (match_kernels.hip) -----------------------------------
 void rh_comm_destroy(real_hip_ctx *ctx);
 int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &a, bool all, int state_slot);
@@ -403,6 +393,26 @@ void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, int which);   // a public 
 void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, RhStage &stage); // a paired stage: its kernel_ms
 void rh_time_end(real_hip_ctx *ctx, hipStream_t st);
 void rh_time_resolve(real_hip_ctx *ctx); // call after the streams were synchronised
+// the bracket as a scope: a return between begin and end (RH_HIP) still closes it, so no Pending record stays without its end
+// event.  The end is recorded where the scope ends: braces where that is before a host synchronisation.
+struct RhTimed {
+    real_hip_ctx *c;
+    hipStream_t st;
+    RhTimed(real_hip_ctx *ctx, hipStream_t s, int which) : c(ctx), st(s) { rh_time_begin(c, st, which); }
+    RhTimed(real_hip_ctx *ctx, hipStream_t s, RhStage &stage) : c(ctx), st(s) { rh_time_begin(c, st, stage); }
+    RhTimed(const RhTimed &) = delete;
+    RhTimed &operator=(const RhTimed &) = delete;
+    ~RhTimed() { rh_time_end(c, st); }
+};
+// synchronises the ctx's stream on the way out of a scope, whichever way: declared BEHIND the ScopedBufs a function's kernels
+// use, it runs before they are released
+struct RhSyncOnExit {
+    real_hip_ctx *c;
+    explicit RhSyncOnExit(real_hip_ctx *ctx) : c(ctx) {}
+    RhSyncOnExit(const RhSyncOnExit &) = delete;
+    RhSyncOnExit &operator=(const RhSyncOnExit &) = delete;
+    ~RhSyncOnExit() { (void)hipStreamSynchronize(c->stream); }
+};
 int rh_max_patl(real_hip_ctx *ctx, const uint64_t *d_off, uint64_t n_reads, uint32_t *out);
 int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int fastq, int qoff, real_hip_parsed *out);
 int rh_all_finish(real_hip_ctx *ctx, uint64_t n_raw, uint64_t n_reads, real_hip_hit *d_out,
@@ -490,13 +500,13 @@ int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const r
                               const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup);
 int rh_dup_stats(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset);
 
-// ---- text + index (index_build.hip) ------------------------------------------
+// ---- text + index (index_build.hip; the plan itself: index_plan.h) ---------------
 int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);
+int rh_count_wild(real_hip_ctx *ctx, uint64_t n); // n_wild of a text that was set packed
 int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const sign[6], const uint32_t *const pos[6], unsigned sig_bytes);
 int rh_index_build_device(real_hip_ctx *ctx, uint64_t first_window, uint64_t max_entries,
                           uint64_t *n_entries, int *have_next);
-// the bucket prefix width and layout of an index of n_entries per list (the ABI request: real_hip_params.table_kind)
-struct RhTables { uint32_t pb; RhLayout layout; };
-RhTables rh_plan_tables(uint32_t seedl, uint32_t request, uint32_t prefix_bits, uint64_t n_entries, uint64_t device_bytes, bool no_rows);
-void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries); // sets ctx->pb and ctx->layout
+void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries); // sets ctx->pb and ctx->layout (rh_plan_tables for this device)
+// ---- read-back of the resident index (index_readback.hip: tests, CPU baseline) ----
 int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts, bool canonical);
+int rh_index_export(real_hip_ctx *ctx, int list, void *h_sign, uint32_t *h_pos);

@@ -11,6 +11,8 @@
 //   host_selftest sam_gapped_options <args...>    -> prints the parsed -sam_gapped flag (0|1), the -sam and the -gapped file ("." if none)
 //   host_selftest insert_options <args...>        -> prints the parsed -insert_hist file ("." if none), -insert_auto, -insert_min, -insert_max
 //   host_selftest rowaddr <seedl>                 -> checks the row addressing of the pair and canonical tables (csrc/row_addr.h), prints ok
+//   host_selftest plan                            -> the table plan (csrc/index_plan.h, rh_plan_tables) over a grid of seed lengths, requests,
+//       prefix widths, entry counts and device sizes: a line "l request prefix_bits n_entries device_bytes no_rows -> pb layout" each
 //   host_selftest records                         -> checks the decoders of the final records and of the gap records (csrc/final_record.h)
 //       against records written through the public structs, prints ok or the first disagreement
 //   host_selftest gap_grid <n>                    -> the geometry rule of a gapped placement in a text of n bases (csrc/final_record.h, rh_gap_fit)
@@ -47,6 +49,7 @@
 #include "Sam.hpp"
 #include "Vcf.hpp"
 #include "final_record.h"
+#include "index_plan.h"
 #include "row_addr.h"
 #include <vector>
 
@@ -236,6 +239,18 @@ int main(int argc, char **argv)
             }
             std::cout << bad << std::endl;
             return bad ? 1 : 0;
+        }
+        if (cmd == "plan" && argc == 2) {
+            // rh_plan_tables as the library compiles it, over a grid that reaches every branch (big = 2^27 entries or more)
+            const uint32_t ls[] = {8, 12, 16, 20, 24, 28, 32, 36, 48, 64}, pbs[] = {0, 5, 12, 13, 20, 28, 30};
+            const uint64_t ns[] = {0, 1, 1000, 32000, 1ull << 20, (1ull << 27) - 1, 1ull << 27, 3000000000ull, (1ull << 32) - 1};
+            const uint64_t devs[] = {16ull << 30, 288ull << 30, 1ull << 62};
+            for (uint32_t l : ls) for (uint32_t req = 0; req < 4; ++req) for (uint32_t pb : pbs) for (uint64_t n : ns) for (uint64_t dev : devs)
+                for (int nr = 0; nr < 2; ++nr) {
+                    const RhTables t = rh_plan_tables(l, req, pb, n, dev, nr != 0);
+                    printf("%u %u %u %llu %llu %d -> %u %u\n", l, req, pb, (unsigned long long)n, (unsigned long long)dev, nr, t.pb, (unsigned)t.layout);
+                }
+            return 0;
         }
         if (cmd == "rowaddr" && argc == 3) {
             // rh_sig_rcform / rh_canon / rh_row_addr as the library compiles them: the rc-form against a base-by-base

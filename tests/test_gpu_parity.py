@@ -263,10 +263,13 @@ def test_index_blocks_compose(ora, kind, pb, device_build):
 def test_index_layout_device_equals_host(ora):
     g = synth.random_genome(50_000, seed=77, n_frag=3, n_runs=10, repeats=10)
     for seedl, kw in ((32, {}), (64, {}), (12, {}), (16, dict(table_kind=3, prefix_bits=12)), (16, dict(table_kind=3)),
-                      (64, dict(table_kind=3, prefix_bits=13))):
+                      (64, dict(table_kind=3, prefix_bits=13)), (16, dict(table_kind=2, prefix_bits=13)),
+                      (64, dict(table_kind=2, prefix_bits=15))):
         a = UniqueMatcher(_opts(seedl, 2, 3, 1), **kw)
         a.set_text_symbols(0, g.sym, g.frag_start)
         a.build_index_block()
+        if kw.get("table_kind") == 2:       # the two directories: digest (narrow signatures), fingerprint (wide)
+            assert a.table_kind == (1 if seedl <= 32 else 2)
         h = UniqueMatcher(_opts(seedl, 2, 3, 1), **kw)
         text, wild = host_index.pack_text(g.sym)
         h.set_text(0, text, wild, g.n, g.frag_start)

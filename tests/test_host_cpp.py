@@ -185,6 +185,43 @@ def test_final_record_decoders(selftest):
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout
 
 
+def test_table_plan(selftest):
+    """csrc/index_plan.h's rh_plan_tables -- which layout and prefix width an index gets -- compiled by the host compiler:
+    `host_selftest plan` prints it over seedl x request x prefix_bits x entries x device memory x no_rows (15120 lines,
+    the large-index branches included, which no GPU test reaches).  The whole output is pinned to what the function
+    printed when it still sat in index_build.hip; the rows spelled out are there for the reader.
+    Layouts: 0 bucket starts, 1 digest directory, 2 fingerprint directory, 3 bucket rows."""
+    import hashlib
+    r = subprocess.run([selftest, "plan"], stdout=subprocess.PIPE, universal_newlines=True)
+    assert r.returncode == 0
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == 10 * 4 * 7 * 9 * 3 * 2
+    G16, G288, HUGE = 16 << 30, 288 << 30, 1 << 62
+    want = {
+        # l request prefix_bits n_entries device_bytes no_rows -> pb layout
+        (32, 0, 0, 3_000_000_000, G288, 0): (28, 3),   # BASELINE: a 3 Gbp genome on 288 GiB gets bucket rows, 2^28 of them
+        (32, 0, 0, 3_000_000_000, G288, 1): (29, 1),   # ... the rows did not fit once: digest directories, all bits but three
+        (32, 0, 0, 3_000_000_000, G16, 0): (29, 1),    # ... a 16 GiB device: no room for the rows
+        (64, 0, 0, 3_000_000_000, G288, 0): (28, 3),   # 64-bit signatures: rows too
+        (64, 0, 0, 3_000_000_000, G16, 0): (29, 2),    # ... and fingerprint directories where they do not fit
+        (32, 0, 0, (1 << 27) - 1, G288, 0): (25, 0),   # one entry below `big`: bucket starts, mean bucket 2..4
+        (32, 0, 0, 1 << 27, G288, 0): (29, 1),         # big, but 2^28 rows would hold half an entry each: digest directories
+        (32, 1, 0, 3_000_000_000, G288, 0): (30, 0),   # bucket starts on request: the prefix stops at 30 bits
+        (12, 0, 0, 1000, G16, 0): (8, 0),              # a tiny index: at least 8 prefix bits
+        (16, 3, 12, 32000, G16, 0): (12, 3),           # rows on request, four group bits
+        (16, 2, 13, 32000, G16, 0): (13, 1),           # a directory on request, three bits below the prefix: digest
+        (64, 2, 13, 32000, G16, 0): (13, 2),          # ... wide signatures: fingerprints
+        (48, 0, 0, (1 << 32) - 1, HUGE, 0): (29, 0),   # seedl 48: no 32 key bits below a row prefix, and an entry holds all 19 bits below this one: bucket starts
+    }
+    got = {}
+    for line in lines:
+        a, b = line.split(" -> ")
+        got[tuple(int(x) for x in a.split())] = tuple(int(x) for x in b.split())
+    assert len(got) == len(lines)
+    assert {k: got[k] for k in want} == want
+    assert hashlib.sha256(r.stdout.encode()).hexdigest() == "ba72e8f549613b49c08bd4ce9a3fac91d500e77d89c5a924c8cf4a492297364d"
+
+
 def test_gap_record_geometry_against_the_checkers_rule(selftest):
     """csrc/final_record.h's rh_gap_fit, the one geometry rule of the stages that consume gap records, against the rule of
     tests/gapped_list_checker.py over `host_selftest gap_grid`: L in {1, 2, 31, 32, 33, 320, 321}, g in -17 .. 17, every split
