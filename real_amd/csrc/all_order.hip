@@ -1,6 +1,6 @@
 // all_order.hip -- the matchAll post-pass (the `order` leg): the raw hit records of a batch put into the per-read order of
 // unifyMatches (matchAllImplementation.cpp:122-161).  Nothing of the index is touched here.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "rocprim_call.h"
 
 #include <rocprim/device/device_scan.hpp>

@@ -1,5 +1,6 @@
 // batch_kernel.hip -- small helpers over a read batch that lives on the device.
 #include "kernel_common.h"
+#include "real_hip_ctx.h" // the launchers
 
 // longest read of a ragged device batch (decides the register form of the matcher)
 __global__ void max_patl_kernel(const uint64_t *__restrict__ off, uint64_t n, uint32_t *out)

@@ -1,10 +1,10 @@
 // dup_gapped_stage.h -- what duplicates.hip and the entry point of real_hip_api.hip share of the joint duplicate marking over
 // info words and gap records (include/real_hip.h, "duplicates", SINGLE-END WITH GAPPED PLACEMENTS): the stage's
 // state and its launcher.
-// The state lives BESIDE the ctx, as RhCtxSide::dup_gapped: ctx_side.h says why, and has rh_dup_gapped_stage(ctx).  The keys,
-// the sort's buffers and the statistics are the marking's own (real_hip_ctx::dup*): only what the ctx has no room for is here.
+// The state is a member of the ctx, real_hip_ctx::dup_gapped (real_hip_ctx.h).  The keys, the sort's buffers and the statistics
+// are the marking's own (real_hip_ctx::dup, dup_stage.h): only what the joint marking adds to them is here.
 #pragma once
-#include "real_hip_internal.h"
+#include "host_buf.h"
 
 struct RhDupGappedStage {
     DevBuf rec; // when the caller's gap records are host memory, their staged copy

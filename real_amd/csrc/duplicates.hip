@@ -19,9 +19,8 @@
 // is hashed.  dup[] is cleared beforehand (the unplaced records), the marks are byte stores.  The key kernels read their
 // records through final_record.h's decoders; placed and groups go to the striped line with stage_common.h's rh_stats_add.
 // No LDS of our own, no scratch memory, plain C++.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "read_walk.h"
-#include "dup_gapped_stage.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -247,11 +246,11 @@ int rh_launch_read_summary(real_hip_ctx *ctx, const DevBatch &b, uint32_t min_qu
     SummaryArgs A;
     memset(&A, 0, sizeof A);
     A.b = b; A.min_qual = min_qual; A.out = (uint2 *)d_out;
-    rh_time_begin(ctx, ctx->stream, ctx->dup);
+    rh_time_begin(ctx, ctx->stream, ctx->dup.stage);
     hipLaunchKernelGGL(read_summary_kernel, dup_grid(b.n_reads), dim3(RH_DUP_BLOCK), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->dup.launches += 1;
+    ctx->dup.stage.launches += 1;
     return REAL_HIP_OK;
 }
 
@@ -262,14 +261,14 @@ static int dup_sort_mark(real_hip_ctx *ctx, DupArgs K, void (*key_kernel)(const 
     if (!n) return REAL_HIP_OK;
     if (n > (1ull << 32)) return rh_fail(ctx, REAL_HIP_E_INVALID, "duplicates: more than 2^32 records in one call", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->dup.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->dup.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     for (int k = 0; k < 2; ++k) {
-        if ((rc = rh_reserve(ctx, ctx->dup_key[k], (size_t)n * 8))) return rc;
-        if ((rc = rh_reserve(ctx, ctx->dup_val[k], (size_t)n * 4))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->dup.key[k], (size_t)n * 8))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->dup.val[k], (size_t)n * 4))) return rc;
     }
-    if (pairs && ((rc = rh_reserve(ctx, ctx->dup_hi, (size_t)n * 8)) || (rc = rh_reserve(ctx, ctx->dup_lo, (size_t)n * 8)))) return rc;
-    rocprim::double_buffer<uint64_t> keys((uint64_t *)ctx->dup_key[0].p, (uint64_t *)ctx->dup_key[1].p);
-    rocprim::double_buffer<uint32_t> vals((uint32_t *)ctx->dup_val[0].p, (uint32_t *)ctx->dup_val[1].p);
+    if (pairs && ((rc = rh_reserve(ctx, ctx->dup.hi, (size_t)n * 8)) || (rc = rh_reserve(ctx, ctx->dup.lo, (size_t)n * 8)))) return rc;
+    rocprim::double_buffer<uint64_t> keys((uint64_t *)ctx->dup.key[0].p, (uint64_t *)ctx->dup.key[1].p);
+    rocprim::double_buffer<uint32_t> vals((uint32_t *)ctx->dup.val[0].p, (uint32_t *)ctx->dup.val[1].p);
     const unsigned bits0 = pairs ? RH_DUP_PE_BITS + RH_DUP_PQ_BITS : 64u; // (single-end: bit 63 is the sentinel's)
     size_t tmp = 0, tmp1 = 0;
     RH_HIP(ctx, rocprim::radix_sort_pairs(nullptr, tmp, keys, vals, (size_t)n, 0u, bits0, ctx->stream));
@@ -278,10 +277,10 @@ static int dup_sort_mark(real_hip_ctx *ctx, DupArgs K, void (*key_kernel)(const 
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
     RH_HIP(ctx, hipMemsetAsync(d_dup, 0, (size_t)n, ctx->stream));
 
-    K.n = n; K.key = keys.current(); K.lo = (uint64_t *)ctx->dup_lo.p; K.hi = (uint64_t *)ctx->dup_hi.p; K.val = vals.current();
+    K.n = n; K.key = keys.current(); K.lo = (uint64_t *)ctx->dup.lo.p; K.hi = (uint64_t *)ctx->dup.hi.p; K.val = vals.current();
     const dim3 grid = dup_grid(n), block(RH_DUP_BLOCK);
     uint64_t launches = 0;
-    rh_time_begin(ctx, ctx->stream, ctx->dup); // (no return inside the bracket: a failing step is reported behind rh_time_end)
+    rh_time_begin(ctx, ctx->stream, ctx->dup.stage); // (no return inside the bracket: a failing step is reported behind rh_time_end)
     hipLaunchKernelGGL(key_kernel, grid, block, 0, ctx->stream, K);
     hipError_t e = hipGetLastError();
     ++launches;
@@ -290,7 +289,7 @@ static int dup_sort_mark(real_hip_ctx *ctx, DupArgs K, void (*key_kernel)(const 
         // the second pass sorts the high words, brought into the first pass' order: the gather writes the buffer the sort has
         // finished with
         uint64_t *lo_sorted = keys.current(), *spare = keys.alternate();
-        hipLaunchKernelGGL(dup_gather_kernel, grid, block, 0, ctx->stream, (const uint64_t *)ctx->dup_hi.p, (const uint32_t *)vals.current(), n, spare);
+        hipLaunchKernelGGL(dup_gather_kernel, grid, block, 0, ctx->stream, (const uint64_t *)ctx->dup.hi.p, (const uint32_t *)vals.current(), n, spare);
         e = hipGetLastError();
         ++launches;
         if (e == hipSuccess) {
@@ -302,17 +301,17 @@ static int dup_sort_mark(real_hip_ctx *ctx, DupArgs K, void (*key_kernel)(const 
     if (e == hipSuccess) {
         MarkArgs M;
         memset(&M, 0, sizeof M);
-        M.key = keys.current(); M.lo = pairs ? (const uint64_t *)ctx->dup_lo.p : nullptr; M.val = vals.current();
-        M.n = n; M.dup = d_dup; M.stats = (unsigned long long *)ctx->dup.stats.p;
+        M.key = keys.current(); M.lo = pairs ? (const uint64_t *)ctx->dup.lo.p : nullptr; M.val = vals.current();
+        M.n = n; M.dup = d_dup; M.stats = (unsigned long long *)ctx->dup.stage.stats.p;
         if (pairs) hipLaunchKernelGGL(dup_mark_kernel<true>, grid, block, 0, ctx->stream, M);
         else hipLaunchKernelGGL(dup_mark_kernel<false>, grid, block, 0, ctx->stream, M);
         e = hipGetLastError();
         ++launches;
     }
     rh_time_end(ctx, ctx->stream);
-    ctx->dup.launches += launches;
+    ctx->dup.stage.launches += launches;
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "duplicates: key / sort / mark", e);
-    ctx->dup.items += n;
+    ctx->dup.stage.items += n;
     return REAL_HIP_OK;
 }
 
@@ -342,7 +341,7 @@ int rh_dup_stats(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset)
     uint64_t h[2];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->dup, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->dup.stage, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->placed = h[0]; out->groups = h[1]; out->duplicates = h[0] - h[1];

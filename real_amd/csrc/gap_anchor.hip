@@ -28,7 +28,6 @@
 // stores.
 #include "gap_core.h"   // read_words.h; gap_mm, gap_diagonal, gap_best_split, the record packing
 #include "pair_state.h" // pair_hand_over, stage_common.h
-#include "ctx_side.h" // gap_stage.h
 
 #include <cstring>
 
@@ -295,7 +294,7 @@ __global__ void __launch_bounds__(256) gap_anchor_search_kernel(const AnchorArgs
 // ---- the launchers ---------------------------------------------------------------------------------------------------------
 static int anchor_args(real_hip_ctx *ctx, const RhAnchorRun &r, AnchorArgs &A)
 {
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     int rc;
     const size_t stat_bytes = (size_t)RH_PAIR_STRIPES * 16 * 8;
     if ((rc = rh_stats_reserve(ctx, S.anchor.stats, RH_PAIR_STRIPES, 8))) return rc; // (the error flags behind the stripes)
@@ -318,7 +317,7 @@ int rh_gap_anchor_select(real_hip_ctx *ctx, const RhAnchorRun &r, uint64_t *coun
     if (count) *count = 0;
     if (!r.n) return REAL_HIP_OK;
     if (r.n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "anchored gap placement: more than 2^32 reads in one call", hipSuccess);
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     AnchorArgs A;
     int rc;
     if ((rc = anchor_args(ctx, r, A))) return rc;
@@ -343,7 +342,7 @@ int rh_gap_anchor_extract(real_hip_ctx *ctx, const RhAnchorRun &r, uint64_t coun
 {
     *d_bases = *d_qual = nullptr;
     if (!count) return REAL_HIP_OK;
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     AnchorArgs A;
     int rc;
     if ((rc = anchor_args(ctx, r, A))) return rc;
@@ -363,7 +362,7 @@ int rh_gap_anchor_extract(real_hip_ctx *ctx, const RhAnchorRun &r, uint64_t coun
 int rh_gap_anchor_search(real_hip_ctx *ctx, const RhAnchorRun &r, const real_hip_hit *d_hits, const uint64_t *d_off, uint64_t total, bool compact)
 {
     if (!r.n) return REAL_HIP_OK;
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     AnchorArgs A;
     int rc;
     if ((rc = anchor_args(ctx, r, A))) return rc;
@@ -380,7 +379,7 @@ int rh_gap_anchor_search(real_hip_ctx *ctx, const RhAnchorRun &r, const real_hip
 
 int rh_gap_anchor_finish(real_hip_ctx *ctx)
 {
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     const uint32_t e = S.an_err;
     S.an_err = 0;
     if (e & 1u) return rh_fail(ctx, REAL_HIP_E_INVALID, "anchored gap placement: an anchor wider than REAL_HIP_GAP_MAX and REAL_HIP_MAX_PATL allow", hipSuccess);
@@ -392,7 +391,7 @@ int rh_gap_anchor_stats(real_hip_ctx *ctx, real_hip_gap_anchor_stats *out, int r
     uint64_t h[10];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, rh_gap_stage(ctx).anchor, RH_PAIR_STRIPES, 10, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->gap.anchor, RH_PAIR_STRIPES, 10, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->eligible = h[0]; out->skipped = h[0] - h[1]; out->crowded = h[2]; out->unanchored = h[3];

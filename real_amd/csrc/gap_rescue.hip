@@ -23,7 +23,6 @@
 // Nothing depends on lanes, tiles or the order of the list.  No scratch memory; plain C++ and vector stores.
 #include "gap_core.h"   // read_words.h; gap_mm, gap_diagonal, gap_best_split, the record packing
 #include "pair_state.h" // pair_hand_over, stage_common.h
-#include "ctx_side.h" // gap_stage.h
 
 #include <cstdio>
 #include <cstring>
@@ -232,7 +231,7 @@ int rh_launch_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params &pp, cons
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "gap rescue: more than 2^32 fragments in one call", hipSuccess);
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     int rc;
     const size_t stat_bytes = (size_t)RH_PAIR_STRIPES * 16 * 8;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 8))) return rc; // (the error flags behind the stripes)
@@ -267,7 +266,7 @@ int rh_launch_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params &pp, cons
 
 int rh_gap_finish(real_hip_ctx *ctx)
 {
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     const uint32_t e = S.err;
     S.err = 0;
     if (e & 1u) return rh_fail(ctx, REAL_HIP_E_INVALID, "gap rescue: a window wider than REAL_HIP_MATE_SEARCH_MAX_INSERT allows", hipSuccess);
@@ -279,7 +278,7 @@ int rh_gap_stats(real_hip_ctx *ctx, real_hip_gap_stats *out, int reset)
     uint64_t h[7];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, rh_gap_stage(ctx).stage, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->gap.stage, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->fragments = was.items; out->eligible = h[0]; out->other_file = h[2]; out->skipped = h[0] - h[1]; out->positions = h[3];

@@ -1,8 +1,8 @@
 // gap_stage.h -- what gap_rescue.hip and the entry points of real_hip_api.hip share of the gap rescue (include/real_hip.h, "gap
 // rescue"): the stage's state and its launcher.
-// The state lives BESIDE the ctx, as RhCtxSide::gap: ctx_side.h says why, and has rh_gap_stage(ctx).
+// The state is a member of the ctx, real_hip_ctx::gap (real_hip_ctx.h).
 #pragma once
-#include "real_hip_internal.h"
+#include "host_buf.h"
 
 // the list of the fragments to search, and when the caller's arrays are host memory the staged pair records, singles and gap
 // records; the stage record with the kernels' error flags behind its statistics

@@ -15,7 +15,6 @@
 // The output is a function of records, reads and text alone.  No LDS, no scratch memory (no mask of the read is kept: a
 // register array indexed at run time would go there), plain C++.
 #include "read_walk.h"
-#include "ctx_side.h" // gap_stage.h
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -136,7 +135,7 @@ int rh_gapped_list_count(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &
                          uint64_t *total)
 {
     *total = 0;
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.lists.stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, S.gl_cnt, (size_t)(n + 1) * 8))) return rc;
@@ -169,7 +168,7 @@ int rh_gapped_list_emit(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b
                         real_hip_mismatch *d_out, uint64_t total)
 {
     if (!total) return REAL_HIP_OK;
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     GappedArgs A = gapped_args(ctx, S, b1, b2, d_gaps, n);
     A.off = d_off; A.out = (uint32_t *)d_out;
     rh_time_begin(ctx, ctx->stream, S.lists);
@@ -186,7 +185,7 @@ int rh_gapped_list_stats(real_hip_ctx *ctx, real_hip_gapped_list_stats *out, int
     uint64_t h[9];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, rh_gap_stage(ctx).lists, RH_PAIR_STRIPES, 9, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->gap.lists, RH_PAIR_STRIPES, 9, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->fragments = was.items; out->placed = h[0]; out->other_file = h[1]; out->invalid = h[2]; out->aligned_bases = h[3];

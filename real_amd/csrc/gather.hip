@@ -8,7 +8,7 @@
 //
 // librccl is opened at run time (dlopen): the library has no link dependency on it, single-GPU users never load it,
 // and a process that already carries a librccl (PyTorch's) shares that one.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 
 #include <dlfcn.h>
 #include <cstring>

@@ -23,7 +23,6 @@
 // indexed at run time; plain C++ and vector stores.
 #include "read_walk.h"
 #include "pair_state.h" // pair_hand_over
-#include "ctx_side.h" // indel_stage.h, pileup_gapped_stage.h
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
@@ -33,12 +32,10 @@
 
 #define RH_ID_BLOCK 256u
 
-// ---- the stage's state, beside the ctx (ctx_side.h) ----------------------------------------------------------------------
+// ---- the stage's state (real_hip_ctx::indel) ------------------------------------------------------------------------------
 void rh_indel_release(real_hip_ctx *ctx)
 {
-    RhCtxSide *side = rh_side_if(ctx);
-    if (!side) return;
-    RhIndelStage *s = &side->indel;
+    RhIndelStage *s = &ctx->indel; // (releasing a buffer that was never made does nothing)
     rh_release(ctx, s->ev); rh_release(ctx, s->ev2); rh_release(ctx, s->key[0]); rh_release(ctx, s->key[1]); rh_release(ctx, s->blk);
     rh_release(ctx, s->starts); rh_release(ctx, s->table); rh_release(ctx, s->events); rh_release(ctx, s->calls);
     s->state = 0; s->grouped = false;
@@ -309,7 +306,7 @@ int rh_indel_begin(real_hip_ctx *ctx)
     static_assert(REAL_HIP_GAP_MAX == 16u, "S fills a u32 exactly");
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rh_indel_release(ctx);
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, S.fin, (size_t)RH_PAIR_STRIPES * 16 * 8)) || (rc = rh_reserve(ctx, S.count, 8))) return rc;
@@ -322,7 +319,7 @@ int rh_indel_begin(real_hip_ctx *ctx)
 int rh_indel_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, const real_hip_gap_place *d_gaps, uint64_t n)
 {
     if (!n) return REAL_HIP_OK;
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     // the worst case of this call: one event per fragment
@@ -330,7 +327,7 @@ int rh_indel_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, cons
     IndelAddArgs A;
     memset(&A, 0, sizeof A);
     rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
-    A.min_qual = ctx->pu_min_qual;
+    A.min_qual = ctx->pileup.min_qual;
     A.ev = (uint4 *)S.ev.p; A.ev_count = (unsigned long long *)S.count.p;
     A.stats = (unsigned long long *)S.stage.stats.p;
     rh_time_begin(ctx, ctx->stream, S.stage);
@@ -397,7 +394,7 @@ static int indel_group(real_hip_ctx *ctx, RhIndelStage &S)
     IndelGroupArgs G;
     G.t = rh_dev_text(ctx, ctx->fileid);
     G.ev = ev; G.starts = (const uint32_t *)S.starts.p; G.n_groups = groups;
-    G.depth = (const uint32_t *)ctx->pu_diff.p; // (scanned in place by the pileup's finish)
+    G.depth = (const uint32_t *)ctx->pileup.diff.p; // (scanned in place by the pileup's finish)
     G.gdepth = rh_pileup_gapped_array(ctx);
     G.table = (uint4 *)S.table.p;
     rh_time_begin(ctx, ctx->stream, S.stage);
@@ -417,7 +414,7 @@ static int indel_group(real_hip_ctx *ctx, RhIndelStage &S)
 
 int rh_indel_finish(real_hip_ctx *ctx, const real_hip_indel_params &p, uint64_t *n_events, uint64_t *n_calls)
 {
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     int rc;
     S.n_calls = S.het = S.hom = S.dels = S.ins = 0;
     if (!S.grouped && (rc = indel_group(ctx, S))) return rc;
@@ -474,7 +471,7 @@ int rh_indel_stats(real_hip_ctx *ctx, real_hip_indel_stats *out, int reset)
 {
     uint64_t h[9];
     RhStageCount was;
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     int rc;
     if ((rc = rh_stage_read(ctx, S.stage, RH_PAIR_STRIPES, 9, reset, h, was))) return rc;
     if (out) {

@@ -1,9 +1,9 @@
 // indel_stage.h -- what indel_call.hip and the entry points of real_hip_api.hip share of the indel calls (include/real_hip.h,
 // "indel calls"): the stage's state and its steps.
-// The state lives BESIDE the ctx, as RhCtxSide::indel: ctx_side.h says why, and has rh_indel_stage(ctx).  rh_indel_release ends
-// the stage and keeps the record (the pileup's end calls it).
+// The state is a member of the ctx, real_hip_ctx::indel (real_hip_ctx.h).  rh_indel_release ends the stage and keeps the
+// record (the pileup's end calls it).
 #pragma once
-#include "real_hip_internal.h"
+#include "host_buf.h"
 
 struct RhIndelStage {
     // the event list (16 bytes an event, key and payload; sorted in place by the first finish) with its counter in front of the

@@ -1,7 +1,7 @@
 // index_device.h -- what the index files share (index_build.hip, index_rows.hip, index_readback.hip): reading a window's
 // signature from the 2-bit text, the bucket-start rule of a sorted list, the key-group mask, the dispatch on the signature width.
 #pragma once
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "rocprim_call.h"
 
 #include <rocprim/device/device_radix_sort.hpp>

@@ -1,7 +1,7 @@
 // index_rows.h -- what the index build (index_build.hip) and the cutting of the bucket rows (index_rows.hip) share: where a
 // list lies in the resident tables, the scratch of one build, the row cutter.
 #pragma once
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 
 // Where list `list` lies and what its entries hold.  Pair tables (narrow rows): list 0 / 1 fills a table of twice the rows,
 // list 5 / 4 (`second`) is merged into it: the row takes one prefix bit more, the `which` bit of the second list's key groups is

@@ -16,7 +16,7 @@
 //
 // Counts are integers: nothing depends on the order of the records, the lanes or the blocks.  No scratch memory; plain C++
 // and vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "pair_state.h"
 
 #define RH_IH_BLOCK 512u
@@ -85,21 +85,21 @@ int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     if (n_bins < 2 || n_bins > REAL_HIP_INSERT_HIST_MAX_BINS) return rh_fail(ctx, REAL_HIP_E_INVALID, "n_bins out of range", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->insert.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->insert.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     InsertArgs A;
     A.rec = (const uint2 *)d_pairs; A.len[0] = d_len1; A.len[1] = d_len2;
-    A.n = n; A.hist = (unsigned long long *)d_hist; A.stats = (unsigned long long *)ctx->insert.stats.p;
+    A.n = n; A.hist = (unsigned long long *)d_hist; A.stats = (unsigned long long *)ctx->insert.stage.stats.p;
     A.n_bins = n_bins;
     int n_cu = 0;
     if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || n_cu < 1) n_cu = 256;
     const uint64_t resident = (uint64_t)n_cu * 2, need = (n + RH_IH_BLOCK - 1) / RH_IH_BLOCK;
     const unsigned blocks = (unsigned)(need < resident ? need : resident);
-    rh_time_begin(ctx, ctx->stream, ctx->insert);
+    rh_time_begin(ctx, ctx->stream, ctx->insert.stage);
     hipLaunchKernelGGL(insert_hist_kernel, dim3(blocks), dim3(RH_IH_BLOCK), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->insert.items += n;
-    ctx->insert.launches += 1;
+    ctx->insert.stage.items += n;
+    ctx->insert.stage.launches += 1;
     return REAL_HIP_OK;
 }
 
@@ -108,7 +108,7 @@ int rh_insert_stats(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset)
     uint64_t h[3];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->insert, RH_PAIR_STRIPES, 3, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->insert.stage, RH_PAIR_STRIPES, 3, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->records = was.items; out->counted = h[0]; out->overflow = h[1]; out->invalid = h[2];

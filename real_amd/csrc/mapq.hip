@@ -11,10 +11,9 @@
 //
 // Nothing depends on the order of the hits, the lanes or the waves: the merge (mapq_state.h) is associative and commutative.
 // No LDS, no scratch memory; plain C++ and vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "single_state.h" // RH_SINGLE_LANE_BUDGET, pair_state.h
 #include "mapq_state.h"
-#include "ctx_side.h" // mapq_stage.h
 
 #include <cstring>
 
@@ -108,7 +107,7 @@ int rh_launch_mapq_fold(real_hip_ctx *ctx, int lists, const MateLists &L, uint64
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
-    RhMapqStage &S = rh_mapq_stage(ctx);
+    RhMapqStage &S = ctx->mapq;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, S.list, (size_t)lists * n * 8 + 8))) return rc;
@@ -216,7 +215,7 @@ int rh_launch_mapq_pair_fold(real_hip_ctx *ctx, const real_hip_pair_params &pp, 
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
-    RhMapqStage &S = rh_mapq_stage(ctx);
+    RhMapqStage &S = ctx->mapq;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     if ((rc = rh_reserve(ctx, S.pair_list, n * 4 + 8))) return rc;
@@ -307,7 +306,7 @@ int rh_launch_mapq_finish(real_hip_ctx *ctx, const uint64_t *d_info, const float
 {
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 records in one call", hipSuccess);
-    RhMapqStage &S = rh_mapq_stage(ctx);
+    RhMapqStage &S = ctx->mapq;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
     MapqFinishArgs A;
@@ -330,7 +329,7 @@ int rh_mapq_stats(real_hip_ctx *ctx, real_hip_mapq_stats *out, int reset)
     uint64_t h[4];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, rh_mapq_stage(ctx).stage, RH_PAIR_STRIPES, 4, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->mapq.stage, RH_PAIR_STRIPES, 4, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->folded = was.items; out->candidates = h[0]; out->handed_over = h[1]; out->placements = h[2]; out->unlisted = h[3];

@@ -1,8 +1,8 @@
 // mapq_stage.h -- what mapq.hip and the entry points of real_hip_api.hip share of the mapping quality stage (include/real_hip.h,
 // "mapping quality"): the stage's state and its launchers.
-// The state lives BESIDE the ctx, as RhCtxSide::mapq: ctx_side.h says why, and has rh_mapq_stage(ctx).
+// The state is a member of the ctx, real_hip_ctx::mapq (real_hip_ctx.h).
 #pragma once
-#include "real_hip_internal.h"
+#include "host_buf.h"
 
 struct MateLists; // pair_state.h
 

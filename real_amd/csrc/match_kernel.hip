@@ -34,6 +34,7 @@
 // the decode of the rows weighs as much: DESIGN.md section 4), not by arithmetic (no MFMA: XOR/popcount and a short FP64
 // add chain).
 #include "match_common.h"
+#include "real_hip_ctx.h" // the launch code at the bottom
 #include "row_bytes.h"
 #include "complex_walk.h"
 

@@ -1,7 +1,7 @@
 // match_launch.hip -- launches of the per-read matcher: the lane-per-read kernel over the whole batch (one
 // translation unit per read width, match_kernel.hip) and, behind it on the same stream, the wave-per-read kernel
 // over the reads it handed over (match_wave.hip).
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 
 #define RH_DECL_W(N)                                                                        \
     void rh_launch_match_w##N(real_hip_ctx *ctx, const MatchArgs &a, bool all, bool pass2); \

@@ -18,6 +18,7 @@
 // All four table kinds are read here without their shortcuts (digests, fingerprints): bucket bounds, then the
 // entries themselves.
 #include "match_common.h"
+#include "real_hip_ctx.h" // the launch code at the bottom
 
 #define WV_W RH_MAXW // words of a read that the lane-per-read kernels take (REAL_HIP_MAX_PATL bases): the short form of this kernel holds as many
 

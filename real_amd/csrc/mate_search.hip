@@ -196,35 +196,35 @@ int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, con
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
     const size_t stat_bytes = (size_t)RH_MS_STRIPES * 16 * 8;
-    if ((rc = rh_stats_reserve(ctx, ctx->search.stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
+    if ((rc = rh_stats_reserve(ctx, ctx->search.stage.stats, RH_MS_STRIPES, 8))) return rc; // (the error flags behind the stripes)
     MateSearchArgs A;
     memset(&A, 0, sizeof A);
     A.t = rh_dev_text(ctx, fileid);
     A.b[0] = b1; A.b[1] = b2;
     A.L = L; // (its len[] may be null: the kernel takes the read lengths from the batches)
     A.n = n; A.pairs = d_pairs; A.LL = (const double *)ctx->LL.p;
-    A.stats = (unsigned long long *)ctx->search.stats.p;
-    A.err_flags = (uint32_t *)((char *)ctx->search.stats.p + stat_bytes);
+    A.stats = (unsigned long long *)ctx->search.stage.stats.p;
+    A.err_flags = (uint32_t *)((char *)ctx->search.stage.stats.p + stat_bytes);
     A.filter_mult = ctx->prm.filter_mult;
     A.fresh = fresh ? 1u : 0u; A.fileid = fileid; A.scores = ctx->prm.scores ? 1u : 0u;
     A.min_insert = pp.min_insert; A.max_insert = pp.max_insert; A.seedl = ctx->prm.seedl; A.totalkmax = ctx->prm.totalkmax;
     A.max_anchors = sp.max_anchors;
     RH_HIP(ctx, hipMemsetAsync(A.err_flags, 0, 4, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, ctx->search);
+    rh_time_begin(ctx, ctx->stream, ctx->search.stage);
     if (A.scores) hipLaunchKernelGGL(mate_search_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     else hipLaunchKernelGGL(mate_search_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    RH_HIP(ctx, hipMemcpyAsync(&ctx->ms_err, A.err_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
-    ctx->search.items += n;
-    ctx->search.launches += 1;
+    RH_HIP(ctx, hipMemcpyAsync(&ctx->search.err, A.err_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+    ctx->search.stage.items += n;
+    ctx->search.stage.launches += 1;
     return REAL_HIP_OK;
 }
 
 int rh_mate_search_finish(real_hip_ctx *ctx)
 {
-    const uint32_t e = ctx->ms_err;
-    ctx->ms_err = 0;
+    const uint32_t e = ctx->search.err;
+    ctx->search.err = 0;
     if (e & 1u) return rh_fail(ctx, REAL_HIP_E_INVALID, "mate search: a read is longer than the declared bound and REAL_HIP_MAX_PATL", hipSuccess);
     if (e & 2u) return rh_fail(ctx, REAL_HIP_E_INVALID, "mate search: a window wider than REAL_HIP_MATE_SEARCH_MAX_INSERT", hipSuccess);
     return REAL_HIP_OK;
@@ -235,7 +235,7 @@ int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int
     uint64_t h[4];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->search, RH_MS_STRIPES, 4, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->search.stage, RH_MS_STRIPES, 4, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->fragments = was.items; out->anchors = h[0]; out->anchors_skipped = h[1]; out->positions = h[2]; out->placements = h[3];

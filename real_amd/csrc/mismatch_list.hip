@@ -12,7 +12,7 @@
 // offset.  The statistics are taken in the count pass and added to the striped line by stage_common.h's rh_stats_add.
 //
 // The output is a function of records, reads and text alone.  No LDS, no scratch memory, plain C++.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "read_walk.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -101,8 +101,8 @@ static MismatchArgs mismatch_args(real_hip_ctx *ctx, const RhMismatchLaunch &l, 
     A.b.qual = nullptr; // (not read)
     A.info = l.info; A.pairs = (const uint2 *)l.pairs; A.singles = (const uint4 *)l.singles;
     A.mate = mate; A.stride = stride;
-    A.cnt = (uint64_t *)ctx->mm_cnt.p;
-    A.stats = (unsigned long long *)ctx->mismatch.stats.p;
+    A.cnt = (uint64_t *)ctx->mismatch.cnt.p;
+    A.stats = (unsigned long long *)ctx->mismatch.stage.stats.p;
     return A;
 }
 
@@ -122,25 +122,25 @@ int rh_mismatch_count(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launc
     *total = 0;
     const uint64_t n = l[0].b.n_reads, lists = n * (uint64_t)n_launch;
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->mismatch.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->mm_cnt, (size_t)(lists + 1) * 8))) return rc;
-    uint64_t *cnt = (uint64_t *)ctx->mm_cnt.p;
+    if ((rc = rh_stats_reserve(ctx, ctx->mismatch.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->mismatch.cnt, (size_t)(lists + 1) * 8))) return rc;
+    uint64_t *cnt = (uint64_t *)ctx->mismatch.cnt.p;
     size_t tmp = 0;
     RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, cnt, d_off, (uint64_t)0, (size_t)(lists + 1), rocprim::plus<uint64_t>(), ctx->stream));
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
     RH_HIP(ctx, hipMemsetAsync(cnt + lists, 0, 8, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, ctx->mismatch); // (no return inside the bracket: a failing step is reported behind rh_time_end)
+    rh_time_begin(ctx, ctx->stream, ctx->mismatch.stage); // (no return inside the bracket: a failing step is reported behind rh_time_end)
     hipError_t e = hipSuccess;
     for (int m = 0; m < n_launch && e == hipSuccess && n; ++m) {
         mismatch_launch<false>(ctx, mismatch_args(ctx, l[m], (uint32_t)m, (uint32_t)n_launch));
         e = hipGetLastError();
-        ctx->mismatch.launches += 1;
+        ctx->mismatch.stage.launches += 1;
     }
     if (e == hipSuccess) e = rocprim::exclusive_scan(ctx->sort_tmp.p, tmp, cnt, d_off, (uint64_t)0, (size_t)(lists + 1), rocprim::plus<uint64_t>(), ctx->stream);
     rh_time_end(ctx, ctx->stream);
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "mismatch lists: count / scan", e);
-    ctx->mismatch.launches += 1;
-    ctx->mismatch.items += lists;
+    ctx->mismatch.stage.launches += 1;
+    ctx->mismatch.stage.items += lists;
     RH_HIP(ctx, hipMemcpyAsync(total, d_off + lists, 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return REAL_HIP_OK;
@@ -151,14 +151,14 @@ int rh_mismatch_count(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launc
 int rh_mismatch_emit(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, const uint64_t *d_off, real_hip_mismatch *d_out, uint64_t total)
 {
     if (!total) return REAL_HIP_OK;
-    rh_time_begin(ctx, ctx->stream, ctx->mismatch);
+    rh_time_begin(ctx, ctx->stream, ctx->mismatch.stage);
     hipError_t e = hipSuccess;
     for (int m = 0; m < n_launch && e == hipSuccess; ++m) {
         MismatchArgs A = mismatch_args(ctx, l[m], (uint32_t)m, (uint32_t)n_launch);
         A.off = d_off; A.out = (uint32_t *)d_out;
         mismatch_launch<true>(ctx, A);
         e = hipGetLastError();
-        ctx->mismatch.launches += 1;
+        ctx->mismatch.stage.launches += 1;
     }
     rh_time_end(ctx, ctx->stream);
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "mismatch lists: emit", e);
@@ -170,7 +170,7 @@ int rh_mismatch_stats(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset
     uint64_t h[7];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->mismatch, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->mismatch.stage, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->placed = h[0]; out->other_file = h[1]; out->invalid = h[2]; out->bases = h[3];

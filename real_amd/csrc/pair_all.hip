@@ -9,7 +9,7 @@
 // full whichever list is the long one, and a ballot with a prefix popcount gives every concordant cell its slot in cell
 // order -- the output order is a function of the input order alone.  x and y are carried along (one small division per
 // fragment, none per cell).  No LDS, no scratch memory; plain C++ and 16-byte vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "pair_state.h"
 #include "rocprim_call.h"
 
@@ -120,9 +120,9 @@ static PairAllArgs pair_all_args(real_hip_ctx *ctx, const real_hip_pair_params &
 {
     PairAllArgs A;
     A.L = L; A.n = n;
-    A.cnt = (uint64_t *)ctx->pa_cnt.p; A.off = d_off; A.out = nullptr; A.cap = 0;
-    A.list_count = (unsigned long long *)ctx->pair_list.p; A.list = (uint32_t *)ctx->pair_list.p + 2;
-    A.stats = (unsigned long long *)ctx->pair_all.stats.p;
+    A.cnt = (uint64_t *)ctx->pair_all.cnt.p; A.off = d_off; A.out = nullptr; A.cap = 0;
+    A.list_count = (unsigned long long *)ctx->join.list.p; A.list = (uint32_t *)ctx->join.list.p + 2;
+    A.stats = (unsigned long long *)ctx->pair_all.stage.stats.p;
     A.fileid = fileid; A.min_insert = pp.min_insert; A.max_insert = pp.max_insert;
     return A;
 }
@@ -132,27 +132,27 @@ int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const M
     *total = 0;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->pair_all.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->pair_list, n * 4 + 8))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->pa_cnt, (n + 1) * 8))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->pair_all.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->join.list, n * 4 + 8))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->pair_all.cnt, (n + 1) * 8))) return rc;
     const PairAllArgs A = pair_all_args(ctx, pp, L, n, 0, d_off);
-    RH_HIP(ctx, hipMemsetAsync(ctx->pair_list.p, 0, 8, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->join.list.p, 0, 8, ctx->stream));
     { // (the bracket ends before the read-back)
-        RhTimed timed(ctx, ctx->stream, ctx->pair_all);
+        RhTimed timed(ctx, ctx->stream, ctx->pair_all.stage);
         rh_launch_each(pair_all_lane_kernel<false>, n + 1, ctx->stream, A);
         RH_HIP(ctx, hipGetLastError());
         if (n) {
             hipLaunchKernelGGL(pair_all_wave_kernel<false>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
             RH_HIP(ctx, hipGetLastError());
-            ctx->pair_all.launches += 1;
+            ctx->pair_all.stage.launches += 1;
         }
-        ctx->pair_all.launches += 1;
+        ctx->pair_all.stage.launches += 1;
         auto scan = [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, A.cnt, d_off, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), ctx->stream); };
         if ((rc = rh_prim_run(ctx, ctx->sort_tmp, scan, "pair count scan"))) return rc;
     }
     RH_HIP(ctx, hipMemcpyAsync(total, d_off + n, 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pair_all.items += n;
+    ctx->pair_all.stage.items += n;
     return REAL_HIP_OK;
 }
 
@@ -165,14 +165,14 @@ int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Ma
     PairAllArgs A = pair_all_args(ctx, pp, L, n, fileid, d_off);
     A.out = (uint4 *)d_out; A.cap = cap;
     {
-        RhTimed timed(ctx, ctx->stream, ctx->pair_all);
+        RhTimed timed(ctx, ctx->stream, ctx->pair_all.stage);
         rh_launch_each(pair_all_lane_kernel<true>, n, ctx->stream, A);
         RH_HIP(ctx, hipGetLastError());
         hipLaunchKernelGGL(pair_all_wave_kernel<true>, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     }
     RH_HIP(ctx, hipGetLastError());
-    ctx->pair_all.launches += 2;
-    ctx->pa_pairs_out += total;
+    ctx->pair_all.stage.launches += 2;
+    ctx->pair_all.pairs_out += total;
     return REAL_HIP_OK;
 }
 
@@ -181,12 +181,12 @@ int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset
     uint64_t h[2];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->pair_all, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->pair_all.stage, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
-        out->fragments = was.items; out->products = h[0]; out->pairs_out = ctx->pa_pairs_out; out->handed_over = h[1];
+        out->fragments = was.items; out->products = h[0]; out->pairs_out = ctx->pair_all.pairs_out; out->handed_over = h[1];
         out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
-    if (reset) ctx->pa_pairs_out = 0;
+    if (reset) ctx->pair_all.pairs_out = 0;
     return REAL_HIP_OK;
 }

@@ -11,7 +11,7 @@
 // Nothing depends on the order of the hits or of the lanes: the fold state is the top two of a set under the total
 // order (value descending, location ascending), and merging two states is associative and commutative.  No LDS, no
 // scratch memory; plain C++ and vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "pair_state.h"
 
 struct PairArgs {
@@ -118,16 +118,16 @@ int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Mate
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 pairs in one call", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->join.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->pair_list, n * 4 + 8))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->join.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->join.list, n * 4 + 8))) return rc;
     PairArgs A;
     A.L = L; A.n = n; A.pairs = d_pairs;
-    A.list_count = (unsigned long long *)ctx->pair_list.p; A.list = (uint32_t *)ctx->pair_list.p + 2;
-    A.stats = (unsigned long long *)ctx->join.stats.p;
+    A.list_count = (unsigned long long *)ctx->join.list.p; A.list = (uint32_t *)ctx->join.list.p + 2;
+    A.stats = (unsigned long long *)ctx->join.stage.stats.p;
     A.filter_mult = ctx->prm.filter_mult;
     A.fresh = fresh ? 1u : 0u; A.fileid = fileid; A.scores = ctx->prm.scores ? 1u : 0u;
     A.min_insert = pp.min_insert; A.max_insert = pp.max_insert;
-    RH_HIP(ctx, hipMemsetAsync(ctx->pair_list.p, 0, 8, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->join.list.p, 0, 8, ctx->stream));
     rh_time_begin(ctx, ctx->stream, REAL_HIP_K_PAIR);
     hipLaunchKernelGGL(pair_lane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
@@ -136,7 +136,7 @@ int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const Mate
     hipLaunchKernelGGL(pair_wave_kernel, dim3(rh_wave_blocks(n)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->join.items += n;
+    ctx->join.stage.items += n;
     return REAL_HIP_OK;
 }
 
@@ -144,8 +144,8 @@ int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset)
 {
     uint64_t h[2];
     int rc;
-    if ((rc = rh_stats_read(ctx, ctx->join.stats, RH_PAIR_STRIPES, 2, reset, h))) return rc; // (its times are read by real_hip_kernel_time)
-    if (out) { out->pairs = ctx->join.items; out->products = h[0]; out->handed_over = h[1]; }
-    if (reset) ctx->join.items = 0;
+    if ((rc = rh_stats_read(ctx, ctx->join.stage.stats, RH_PAIR_STRIPES, 2, reset, h))) return rc; // (its times are read by real_hip_kernel_time)
+    if (out) { out->pairs = ctx->join.stage.items; out->products = h[0]; out->handed_over = h[1]; }
+    if (reset) ctx->join.stage.items = 0;
     return REAL_HIP_OK;
 }

@@ -19,10 +19,8 @@
 //
 // Everything is an integer sum: nothing depends on the order of reads, lanes, blocks or calls.  No LDS in the add kernel,
 // no scratch memory; plain C++ and vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "read_walk.h"
-#include "indel_stage.h"
-#include "pileup_gapped_stage.h"
 
 #include <rocprim/device/device_scan.hpp>
 
@@ -142,8 +140,8 @@ static void pileup_release(real_hip_ctx *ctx)
     rh_call_release(ctx); // (the calls stand on this pileup's sites: they go with it)
     rh_indel_release(ctx); // (the indel calls on its depth)
     rh_pileup_gapped_release(ctx); // (the gapped placements' share of its depth)
-    rh_release(ctx, ctx->pu_diff); rh_release(ctx, ctx->pu_alt); rh_release(ctx, ctx->pu_blk); rh_release(ctx, ctx->pu_sites);
-    ctx->pu_state = 0; ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
+    rh_release(ctx, ctx->pileup.diff); rh_release(ctx, ctx->pileup.alt); rh_release(ctx, ctx->pileup.blk); rh_release(ctx, ctx->pileup.sites);
+    ctx->pileup.state = 0; ctx->pileup.n_sites = 0; ctx->pileup.covered = 0; ctx->pileup.max_depth = 0;
 }
 
 int rh_pileup_begin(real_hip_ctx *ctx, uint32_t min_qual)
@@ -153,18 +151,18 @@ int rh_pileup_begin(real_hip_ctx *ctx, uint32_t min_qual)
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     pileup_release(ctx);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->pileup.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->pu_fin, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->pu_diff, (size_t)(n + 1) * 4)) || (rc = rh_reserve(ctx, ctx->pu_alt, (size_t)(n ? n : 1) * 16))) {
+    if ((rc = rh_stats_reserve(ctx, ctx->pileup.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->pileup.fin, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->pileup.diff, (size_t)(n + 1) * 4)) || (rc = rh_reserve(ctx, ctx->pileup.alt, (size_t)(n ? n : 1) * 16))) {
         pileup_release(ctx);
         return rh_fail(ctx, REAL_HIP_E_NOMEM, "pileup: the accumulators (20 bytes per base of the text) do not fit the device memory", hipSuccess);
     }
-    RH_HIP(ctx, hipMemsetAsync(ctx->pu_diff.p, 0, (size_t)(n + 1) * 4, ctx->stream));
-    RH_HIP(ctx, hipMemsetAsync(ctx->pu_alt.p, 0, (size_t)(n ? n : 1) * 16, ctx->stream));
-    RH_HIP(ctx, hipMemsetAsync(ctx->pu_fin.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->pileup.diff.p, 0, (size_t)(n + 1) * 4, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->pileup.alt.p, 0, (size_t)(n ? n : 1) * 16, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->pileup.fin.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->pu_n = n; ctx->pu_fileid = ctx->fileid; ctx->pu_min_qual = min_qual;
-    ctx->pu_state = 1;
+    ctx->pileup.n = n; ctx->pileup.fileid = ctx->fileid; ctx->pileup.min_qual = min_qual;
+    ctx->pileup.state = 1;
     return REAL_HIP_OK;
 }
 
@@ -184,47 +182,47 @@ int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d
     memset(&A, 0, sizeof A);
     A.t = rh_dev_text(ctx, ctx->fileid);
     A.b = b;
-    if (!ctx->pu_min_qual) A.b.qual = nullptr; // (not loaded)
-    A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pu_min_qual;
-    A.diff = (uint32_t *)ctx->pu_diff.p; A.alt = (uint32_t *)ctx->pu_alt.p;
-    A.stats = (unsigned long long *)ctx->pileup.stats.p;
+    if (!ctx->pileup.min_qual) A.b.qual = nullptr; // (not loaded)
+    A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pileup.min_qual;
+    A.diff = (uint32_t *)ctx->pileup.diff.p; A.alt = (uint32_t *)ctx->pileup.alt.p;
+    A.stats = (unsigned long long *)ctx->pileup.stage.stats.p;
     const unsigned blocks = (unsigned)((n + RH_PU_BLOCK - 1) / RH_PU_BLOCK);
-    rh_time_begin(ctx, ctx->stream, ctx->pileup);
+    rh_time_begin(ctx, ctx->stream, ctx->pileup.stage);
     if (d_pairs) hipLaunchKernelGGL(pileup_add_kernel<true>, dim3(blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, A);
     else hipLaunchKernelGGL(pileup_add_kernel<false>, dim3(blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->pileup.items += n;
-    ctx->pileup.launches += 1;
+    ctx->pileup.stage.items += n;
+    ctx->pileup.stage.launches += 1;
     return REAL_HIP_OK;
 }
 
 int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
 {
-    const uint64_t n = ctx->pu_n;
+    const uint64_t n = ctx->pileup.n;
     const uint64_t blocks = (n + RH_PU_BLOCK - 1) / RH_PU_BLOCK;
-    uint32_t *depth = (uint32_t *)ctx->pu_diff.p;
+    uint32_t *depth = (uint32_t *)ctx->pileup.diff.p;
     int rc;
-    ctx->pu_n_sites = 0; ctx->pu_covered = 0; ctx->pu_max_depth = 0;
-    if (!n) { ctx->pu_state = 2; if (n_sites) *n_sites = 0; return REAL_HIP_OK; }
-    if ((rc = rh_reserve(ctx, ctx->pu_blk, (size_t)(blocks + 1) * 16))) return rc;
+    ctx->pileup.n_sites = 0; ctx->pileup.covered = 0; ctx->pileup.max_depth = 0;
+    if (!n) { ctx->pileup.state = 2; if (n_sites) *n_sites = 0; return REAL_HIP_OK; }
+    if ((rc = rh_reserve(ctx, ctx->pileup.blk, (size_t)(blocks + 1) * 16))) return rc;
     size_t tmp = 0, tmp2 = 0;
     RH_HIP(ctx, rocprim::inclusive_scan(nullptr, tmp, depth, depth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream));
-    uint64_t *blk = (uint64_t *)ctx->pu_blk.p, *blk_off = blk + blocks + 1;
+    uint64_t *blk = (uint64_t *)ctx->pileup.blk.p, *blk_off = blk + blocks + 1;
     RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp2, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream));
     if (tmp2 > tmp) tmp = tmp2;
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
     PileupFinArgs F;
-    F.text = (const uint64_t *)ctx->text.p; F.depth = depth; F.alt = (const uint4 *)ctx->pu_alt.p; F.n = n;
-    F.blk = blk; F.blk_off = blk_off; F.out = nullptr; F.cap = 0; F.fin = (unsigned long long *)ctx->pu_fin.p;
-    rh_time_begin(ctx, ctx->stream, ctx->pileup); // (no return inside the bracket: a failing step is reported behind rh_time_end)
+    F.text = (const uint64_t *)ctx->text.p; F.depth = depth; F.alt = (const uint4 *)ctx->pileup.alt.p; F.n = n;
+    F.blk = blk; F.blk_off = blk_off; F.out = nullptr; F.cap = 0; F.fin = (unsigned long long *)ctx->pileup.fin.p;
+    rh_time_begin(ctx, ctx->stream, ctx->pileup.stage); // (no return inside the bracket: a failing step is reported behind rh_time_end)
     size_t t = tmp;
     hipError_t e = rocprim::inclusive_scan(ctx->sort_tmp.p, t, depth, depth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
     uint32_t *gdepth = rh_pileup_gapped_array(ctx); // (the gapped placements' difference array, when an add_gapped made one)
     if (e == hipSuccess && gdepth) {
         t = tmp;
         e = rocprim::inclusive_scan(ctx->sort_tmp.p, t, gdepth, gdepth, (size_t)n, rocprim::plus<uint32_t>(), ctx->stream);
-        ctx->pileup.launches += 1;
+        ctx->pileup.stage.launches += 1;
     }
     if (e == hipSuccess) {
         hipLaunchKernelGGL(pileup_sites_kernel<false>, dim3((unsigned)blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, F);
@@ -234,29 +232,29 @@ int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
     if (e == hipSuccess) e = rocprim::exclusive_scan(ctx->sort_tmp.p, t, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream);
     rh_time_end(ctx, ctx->stream);
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "pileup: scan of the depth / count of the sites", e);
-    ctx->pileup.launches += 3;
+    ctx->pileup.stage.launches += 3;
     uint64_t total = 0;
     std::vector<uint64_t> fin((size_t)RH_PAIR_STRIPES * 16);
     RH_HIP(ctx, hipMemcpyAsync(&total, blk_off + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RH_HIP(ctx, hipMemcpyAsync(fin.data(), ctx->pu_fin.p, fin.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RH_HIP(ctx, hipMemcpyAsync(fin.data(), ctx->pileup.fin.p, fin.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (size_t s = 0; s < RH_PAIR_STRIPES; ++s) {
-        ctx->pu_covered += fin[s * 16];
-        if (fin[s * 16 + 1] > ctx->pu_max_depth) ctx->pu_max_depth = fin[s * 16 + 1];
+        ctx->pileup.covered += fin[s * 16];
+        if (fin[s * 16 + 1] > ctx->pileup.max_depth) ctx->pileup.max_depth = fin[s * 16 + 1];
     }
     if (total) {
-        if ((rc = rh_reserve(ctx, ctx->pu_sites, (size_t)total * sizeof(real_hip_pileup_site)))) return rc;
-        F.out = (uint4 *)ctx->pu_sites.p; F.cap = total;
-        rh_time_begin(ctx, ctx->stream, ctx->pileup);
+        if ((rc = rh_reserve(ctx, ctx->pileup.sites, (size_t)total * sizeof(real_hip_pileup_site)))) return rc;
+        F.out = (uint4 *)ctx->pileup.sites.p; F.cap = total;
+        rh_time_begin(ctx, ctx->stream, ctx->pileup.stage);
         hipLaunchKernelGGL(pileup_sites_kernel<true>, dim3((unsigned)blocks), dim3(RH_PU_BLOCK), 0, ctx->stream, F);
         rh_time_end(ctx, ctx->stream);
         RH_HIP(ctx, hipGetLastError());
-        ctx->pileup.launches += 1;
+        ctx->pileup.stage.launches += 1;
         RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     rh_time_resolve(ctx);
-    ctx->pu_n_sites = total;
-    ctx->pu_state = 2; // (only now: a finish that failed leaves nothing to read, real_hip_pileup_finish releases the accumulators)
+    ctx->pileup.n_sites = total;
+    ctx->pileup.state = 2; // (only now: a finish that failed leaves nothing to read, real_hip_pileup_finish releases the accumulators)
     if (n_sites) *n_sites = total;
     return REAL_HIP_OK;
 }
@@ -266,12 +264,12 @@ int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset)
     uint64_t h[7];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->pileup, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->pileup.stage, RH_PAIR_STRIPES, 7, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->placed = h[0]; out->other_file = h[1]; out->invalid = h[2]; out->bases = h[3];
         out->mismatches = h[4]; out->low_qual = h[5]; out->n_dropped = h[6];
-        out->covered = ctx->pu_covered; out->sites = ctx->pu_n_sites; out->max_depth = ctx->pu_max_depth;
+        out->covered = ctx->pileup.covered; out->sites = ctx->pileup.n_sites; out->max_depth = ctx->pileup.max_depth;
         out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
     return REAL_HIP_OK;

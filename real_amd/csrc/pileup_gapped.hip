@@ -18,25 +18,21 @@
 // Everything is an integer sum: nothing depends on the order of records, lanes, blocks or calls.  No LDS, no scratch memory,
 // plain C++ with vector stores and atomics.
 #include "read_walk.h"
-#include "ctx_side.h"
 
 #include <cstring>
 
 #define RH_PG_BLOCK 256u
 
-// ---- the stage's state, beside the ctx (ctx_side.h) ------------------------------------------------------------------------
+// ---- the stage's state (real_hip_ctx::pileup_gapped) -----------------------------------------------------------------------
 void rh_pileup_gapped_release(real_hip_ctx *ctx)
 {
-    RhCtxSide *side = rh_side_if(ctx);
-    if (!side) return;
-    RhPileupGappedStage &s = side->pileup_gapped;
+    RhPileupGappedStage &s = ctx->pileup_gapped; // (releasing a buffer that was never made does nothing)
     rh_release(ctx, s.gdiff); rh_release(ctx, s.rec);
     s.have_gdiff = false;
 }
 uint32_t *rh_pileup_gapped_array(real_hip_ctx *ctx)
 {
-    RhCtxSide *side = rh_side_if(ctx);
-    return side && side->pileup_gapped.have_gdiff ? (uint32_t *)side->pileup_gapped.gdiff.p : nullptr;
+    return ctx->pileup_gapped.have_gdiff ? (uint32_t *)ctx->pileup_gapped.gdiff.p : nullptr;
 }
 
 // ---- the pileup leg ----------------------------------------------------------------------------------------------------------
@@ -182,11 +178,11 @@ __global__ void __launch_bounds__(RH_PG_BLOCK) pileup_gapped_call_kernel(const C
 int rh_pileup_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, const real_hip_gap_place *d_gaps, uint64_t n)
 {
     if (!n) return REAL_HIP_OK;
-    RhPileupGappedStage &S = rh_pileup_gapped_stage(ctx);
+    RhPileupGappedStage &S = ctx->pileup_gapped;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.add.stats, RH_PAIR_STRIPES, 0))) return rc;
     if (!S.have_gdiff) {
-        const size_t bytes = (size_t)(ctx->pu_n + 1) * 4;
+        const size_t bytes = (size_t)(ctx->pileup.n + 1) * 4;
         if (rh_reserve(ctx, S.gdiff, bytes))
             return rh_fail(ctx, REAL_HIP_E_NOMEM, "pileup: the gapped placements' difference array (4 bytes per base of the text) does not fit the device memory",
                            hipSuccess);
@@ -196,9 +192,9 @@ int rh_pileup_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &
     PileupGappedArgs A;
     memset(&A, 0, sizeof A);
     rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
-    if (!ctx->pu_min_qual) A.b[0].qual = A.b[1].qual = nullptr; // (not loaded)
-    A.min_qual = ctx->pu_min_qual;
-    A.diff = (uint32_t *)ctx->pu_diff.p; A.gdiff = (uint32_t *)S.gdiff.p; A.alt = (uint32_t *)ctx->pu_alt.p;
+    if (!ctx->pileup.min_qual) A.b[0].qual = A.b[1].qual = nullptr; // (not loaded)
+    A.min_qual = ctx->pileup.min_qual;
+    A.diff = (uint32_t *)ctx->pileup.diff.p; A.gdiff = (uint32_t *)S.gdiff.p; A.alt = (uint32_t *)ctx->pileup.alt.p;
     A.stats = (unsigned long long *)S.add.stats.p;
     rh_time_begin(ctx, ctx->stream, S.add);
     hipLaunchKernelGGL(pileup_gapped_add_kernel, dim3((unsigned)((n + RH_PG_BLOCK - 1) / RH_PG_BLOCK)), dim3(RH_PG_BLOCK), 0, ctx->stream, A);
@@ -213,15 +209,15 @@ int rh_pileup_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &
 int rh_call_gapped_add(real_hip_ctx *ctx, const DevBatch &b1, const DevBatch &b2, const real_hip_gap_place *d_gaps, uint64_t n)
 {
     if (!n) return REAL_HIP_OK;
-    RhPileupGappedStage &S = rh_pileup_gapped_stage(ctx);
+    RhPileupGappedStage &S = ctx->pileup_gapped;
     int rc;
     if ((rc = rh_stats_reserve(ctx, S.call.stats, RH_PAIR_STRIPES, 0))) return rc;
     CallGappedArgs A;
     memset(&A, 0, sizeof A);
     rh_gap_record_args(A, ctx, b1, b2, d_gaps, n);
-    A.min_qual = ctx->pu_min_qual;
-    A.bits = (const uint64_t *)ctx->cl_bits.p; A.rank = (const uint32_t *)ctx->cl_rank.p; A.ev = (uint32_t *)ctx->cl_ev.p;
-    A.n_sites = ctx->pu_n_sites;
+    A.min_qual = ctx->pileup.min_qual;
+    A.bits = (const uint64_t *)ctx->call.bits.p; A.rank = (const uint32_t *)ctx->call.rank.p; A.ev = (uint32_t *)ctx->call.ev.p;
+    A.n_sites = ctx->pileup.n_sites;
     A.stats = (unsigned long long *)S.call.stats.p;
     rh_time_begin(ctx, ctx->stream, S.call);
     hipLaunchKernelGGL(pileup_gapped_call_kernel, dim3((unsigned)((n + RH_PG_BLOCK - 1) / RH_PG_BLOCK)), dim3(RH_PG_BLOCK), 0, ctx->stream, A);
@@ -237,7 +233,7 @@ int rh_pileup_gapped_stats(real_hip_ctx *ctx, real_hip_pileup_gapped_stats *out,
 {
     uint64_t h[10], c[2];
     RhStageCount was, wasc;
-    RhPileupGappedStage &S = rh_pileup_gapped_stage(ctx);
+    RhPileupGappedStage &S = ctx->pileup_gapped;
     int rc;
     if ((rc = rh_stage_read(ctx, S.add, RH_PAIR_STRIPES, 10, reset, h, was)) || (rc = rh_stage_read(ctx, S.call, RH_PAIR_STRIPES, 2, reset, c, wasc))) return rc;
     if (out) {

@@ -1,10 +1,10 @@
 // pileup_gapped_stage.h -- what pileup_gapped.hip, pileup.hip, indel_call.hip and the entry points of real_hip_api.hip share of
 // the gapped placements in the pileup and the calls (include/real_hip.h, "gapped placements in the pileup and the calls"): the
 // stage's state and its steps.
-// The state lives BESIDE the ctx, as RhCtxSide::pileup_gapped: ctx_side.h says why, and has rh_pileup_gapped_stage(ctx).
+// The state is a member of the ctx, real_hip_ctx::pileup_gapped (real_hip_ctx.h).
 // rh_pileup_gapped_release ends the stage and keeps the record (the pileup's begin and end call it).
 #pragma once
-#include "real_hip_internal.h"
+#include "host_buf.h"
 
 struct RhPileupGappedStage {
     // the second difference array (n + 1 u32; scanned in place into gdepth[] by the pileup's finish), there from the first

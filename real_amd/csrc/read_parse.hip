@@ -7,7 +7,7 @@
 // The reference's readers are character-level state machines that also accept wrapped sequences and stray
 // white space; text that is not canonical is refused here (REAL_HIP_E_UNSUPPORTED) and stays with the host
 // reader (real_amd/host/ReadReader.cpp), which implements the general form.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 
 #include "rocprim_call.h"
 #include <rocprim/device/device_scan.hpp>

@@ -6,6 +6,7 @@
 #pragma once
 #include "match_common.h"
 #include "stage_common.h"
+#include "real_hip_ctx.h" // rh_gap_record_args
 
 // a read's bytes in place, a dword per request: the aligned dword that holds the first byte asked for and, where the request
 // straddles it and the row goes on, the next one.  Never a dword without a byte of the row in it (an aligned dword does not

@@ -1,9 +1,7 @@
 // real_hip_api.hip -- the C ABI of include/real_hip.h: context, uploads, staging,
 // launches.  No CPU fallback: every entry point either runs the HIP path or fails.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "pair_state.h"
-#include "ctx_side.h" // the stages' state beside the ctx: mapq_stage.h, gap_stage.h, indel_stage.h, pileup_gapped_stage.h, dup_gapped_stage.h
-#include "side_table.h"
 
 #include <chrono>
 #include <cmath>
@@ -235,19 +233,12 @@ extern "C" int real_hip_create(real_hip_ctx **out, const real_hip_params *p)
     return REAL_HIP_OK;
 }
 
-// the stages' state beside the ctx (ctx_side.h)
-static RhSideTable<RhCtxSide> g_side;
-RhCtxSide &rh_side(real_hip_ctx *ctx) { return g_side.at(ctx); }
-RhCtxSide *rh_side_if(real_hip_ctx *ctx) { return g_side.find(ctx); }
-void rh_side_drop(real_hip_ctx *ctx) { g_side.drop(ctx); }
-
 extern "C" void real_hip_destroy(real_hip_ctx *c)
 {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     rh_comm_destroy(c);
-    rh_side_drop(c);
     if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     if (c->down_stream) (void)hipStreamSynchronize(c->down_stream);
     for (int i = 0; i < REAL_HIP_SLOTS; ++i) {
@@ -837,11 +828,11 @@ static int stage_hit_lists(real_hip_ctx *ctx, const real_hip_hit *const hits[2],
     }
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     for (int m = 0; m < lists; ++m) {
-        if ((rc = io.in(ctx->pair_hits[m], (const uint4 *)hits[m], L.total[m], L.h[m], sizeof(real_hip_hit)))) return rc;
-        if ((rc = io.in(ctx->pair_off[m], off[m], n + 1, L.o[m]))) return rc;
-        if (len && (rc = io.in(ctx->pair_len[m], len[m], n, L.len[m]))) return rc;
+        if ((rc = io.in(ctx->join.hits[m], (const uint4 *)hits[m], L.total[m], L.h[m], sizeof(real_hip_hit)))) return rc;
+        if ((rc = io.in(ctx->join.off[m], off[m], n + 1, L.o[m]))) return rc;
+        if (len && (rc = io.in(ctx->join.len[m], len[m], n, L.len[m]))) return rc;
     }
-    if (!on_device) ctx->pair_cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
+    if (!on_device) ctx->join.cap = 0; // (the two hit buffers may now differ in size: real_hip_match_pairs sizes them again)
     return REAL_HIP_OK;
 }
 // the lists match_mates leaves resident in the ctx's pair buffers
@@ -849,8 +840,8 @@ static MateLists resident_lists(real_hip_ctx *ctx, const uint64_t total[2])
 {
     MateLists L;
     for (int m = 0; m < 2; ++m) {
-        L.h[m] = (const uint4 *)ctx->pair_hits[m].p; L.o[m] = (const uint64_t *)ctx->pair_off[m].p;
-        L.len[m] = (const uint32_t *)ctx->pair_len[m].p; L.total[m] = total[m];
+        L.h[m] = (const uint4 *)ctx->join.hits[m].p; L.o[m] = (const uint64_t *)ctx->join.off[m].p;
+        L.len[m] = (const uint32_t *)ctx->join.len[m].p; L.total[m] = total[m];
     }
     return L;
 }
@@ -874,7 +865,7 @@ extern "C" int real_hip_pair_hits(real_hip_ctx *ctx, const real_hip_pair_params 
     real_hip_pair *d_pairs = pairs;
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     if ((rc = stage_hit_lists(ctx, hits, off, len, n, on_device != 0, L))) return rc;
-    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
+    if ((rc = io.inout(ctx->join.rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_pair(ctx, *pp, L, n, fileid, fresh, d_pairs);
     if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
     return rh_sync_tail(ctx, rc);
@@ -962,7 +953,7 @@ extern "C" int real_hip_pair_search(real_hip_ctx *ctx, const real_hip_pair_param
         if ((rc = stage_batch(ctx, bv[m], st[m], ctx->stage[m], ctx->stream, nullptr, false))) return rc;
     real_hip_pair *d_pairs = pairs;
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
-    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
+    if ((rc = io.inout(ctx->join.rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_mate_search(ctx, *pp, *sp, dev_batch(ctx, st[0], n), dev_batch(ctx, st[1], n), L, n, fileid, fresh, d_pairs);
     if (!rc) rc = io.back(pairs, d_pairs, n, "download of the pair records");
     rc = rh_sync_tail(ctx, rc);
@@ -975,7 +966,7 @@ static int stage_singles(const RhStaging &io, int lists, real_hip_single *const 
     int rc = REAL_HIP_OK;
     for (int m = 0; m < lists && !rc; ++m) {
         if (!io.host && ((uintptr_t)singles[m] & 15u)) return rh_fail(io.ctx, REAL_HIP_E_INVALID, "the single records must be 16-byte aligned", hipSuccess);
-        rc = io.inout(io.ctx->sg_rec[m], singles[m], n, fresh != 0, d_singles[m]);
+        rc = io.inout(io.ctx->single.rec[m], singles[m], n, fresh != 0, d_singles[m]);
     }
     return rc;
 }
@@ -1021,7 +1012,7 @@ static int stage_mapq_accs(const RhStaging &io, int count, real_hip_mapq_acc *co
     int rc = REAL_HIP_OK;
     for (int m = 0; m < count && !rc; ++m) {
         if (!io.host && ((uintptr_t)accs[m] & 7u)) return rh_fail(io.ctx, REAL_HIP_E_INVALID, "the mapping quality accumulators must be 8-byte aligned", hipSuccess);
-        rc = io.inout(rh_mapq_stage(io.ctx).acc[m], accs[m], n, fresh != 0, d_accs[m]);
+        rc = io.inout(io.ctx->mapq.acc[m], accs[m], n, fresh != 0, d_accs[m]);
     }
     return rc;
 }
@@ -1078,7 +1069,7 @@ static int mapq_finish_run(real_hip_ctx *ctx, const uint64_t *info, const float 
                            const real_hip_mapq_acc *const accs[3], uint64_t n, int on_device, uint8_t *out)
 {
     int rc;
-    RhMapqStage &S = rh_mapq_stage(ctx);
+    RhMapqStage &S = ctx->mapq;
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
     const bool have_singles = pairs && singles[0];
     if (!io.host && (((uintptr_t)pairs & 7u) || (have_singles && (((uintptr_t)singles[0] | (uintptr_t)singles[1]) & 15u))))
@@ -1153,11 +1144,11 @@ extern "C" int real_hip_pair_insert_hist(real_hip_ctx *ctx, const real_hip_pair 
     const uint32_t *d_len[2] = {len1, len2};
     uint64_t *d_hist = hist;
     const RhStaging io{ctx, !on_device, ctx->stream, ctx->stream};
-    if ((rc = io.inout(ctx->ih_hist, hist, n_bins, fresh != 0, d_hist))) return rc;
+    if ((rc = io.inout(ctx->insert.hist, hist, n_bins, fresh != 0, d_hist))) return rc;
     if (n) {
-        if ((rc = io.in(ctx->ih_rec, pairs, n, d_pairs))) return rc;
+        if ((rc = io.in(ctx->insert.rec, pairs, n, d_pairs))) return rc;
         for (int m = 0; m < 2; ++m)
-            if ((rc = io.in(ctx->ih_len[m], m ? len2 : len1, n, d_len[m]))) return rc;
+            if ((rc = io.in(ctx->insert.len[m], m ? len2 : len1, n, d_len[m]))) return rc;
     }
     if (fresh) RH_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)n_bins * 8, ctx->stream));
     rc = rh_launch_insert_hist(ctx, d_pairs, d_len[0], d_len[1], n, n_bins, d_hist);
@@ -1200,14 +1191,14 @@ extern "C" int real_hip_insert_bounds(const uint64_t *hist, uint32_t n_bins, uin
 // the resident text is still the one begin saw (add reads it, finish takes the sites' reference bases from it)
 static int pileup_text_check(real_hip_ctx *ctx)
 {
-    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+    if (!ctx->have_text || ctx->n_bases != ctx->pileup.n || ctx->fileid != ctx->pileup.fileid)
         return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the text was replaced since begin", hipSuccess);
     return REAL_HIP_OK;
 }
 static int pileup_add_check(real_hip_ctx *ctx)
 {
-    if (ctx->pu_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add without begin", hipSuccess);
-    if (ctx->pu_state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add after finish", hipSuccess);
+    if (ctx->pileup.state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add without begin", hipSuccess);
+    if (ctx->pileup.state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: add after finish", hipSuccess);
     return pileup_text_check(ctx);
 }
 
@@ -1287,7 +1278,7 @@ static int stage_gapped(real_hip_ctx *ctx, const char *stage, const real_hip_bat
 struct PlacementSink {
     const char *name;                    // the prefix of its messages
     int (*check)(real_hip_ctx *);        // may an add come now
-    DevBuf real_hip_ctx::*rec;           // the staged records when the caller's are host memory
+    DevBuf &(*rec)(real_hip_ctx *);      // the staged records when the caller's are host memory
     int (*launch)(real_hip_ctx *, const DevBatch &, const uint64_t *, const real_hip_pair *, uint32_t);
 };
 // the placements of a batch (mates == 1: b1 and info) or of both mates of a batch of pairs (mates == 2: b1, b2 and pairs)
@@ -1299,12 +1290,12 @@ static int placements_add(real_hip_ctx *ctx, const PlacementSink &k, int mates, 
     if (rc || (rc = k.check(ctx))) return rc;
     if (!bv[0].n_reads) return REAL_HIP_OK;
     PlacedReads p;
-    rc = stage_placements(ctx, k.name, bv, mates, info, pairs, ctx->*k.rec, true, p);
+    rc = stage_placements(ctx, k.name, bv, mates, info, pairs, k.rec(ctx), true, p);
     for (int m = 0; m < mates && !rc; ++m) rc = k.launch(ctx, p.b[m], p.info, p.pairs, (uint32_t)m);
     return rh_sync_tail(ctx, rc);
 }
 
-static const PlacementSink kPileupSink = {"pileup", pileup_add_check, &real_hip_ctx::pu_rec, rh_launch_pileup_add};
+static const PlacementSink kPileupSink = {"pileup", pileup_add_check, [](real_hip_ctx *c) -> DevBuf & { return c->pileup.rec; }, rh_launch_pileup_add};
 
 extern "C" int real_hip_pileup_add(real_hip_ctx *ctx, const real_hip_batch *b, const uint64_t *info)
 {
@@ -1321,7 +1312,7 @@ extern "C" int real_hip_pileup_add_pairs(real_hip_ctx *ctx, const real_hip_batch
 extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
 {
     RH_ENTER(ctx);
-    if (ctx->pu_state != 1) return rh_fail(ctx, REAL_HIP_E_INVALID, ctx->pu_state ? "pileup: finish twice" : "pileup: finish without begin", hipSuccess);
+    if (ctx->pileup.state != 1) return rh_fail(ctx, REAL_HIP_E_INVALID, ctx->pileup.state ? "pileup: finish twice" : "pileup: finish without begin", hipSuccess);
     int rc = pileup_text_check(ctx);
     if (rc) return rc;
     return finish_tail(ctx, rh_sync_tail(ctx, rh_pileup_finish(ctx, n_sites)), rh_pileup_end); // (a failed finish: the pileup is over, as after end)
@@ -1330,11 +1321,11 @@ extern "C" int real_hip_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites)
 extern "C" int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device)
 {
     RH_ENTER(ctx);
-    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
-    if (first > ctx->pu_n || count > ctx->pu_n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
+    if (ctx->pileup.state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
+    if (first > ctx->pileup.n || count > ctx->pileup.n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
     if (!count) return REAL_HIP_OK;
     if (!depth) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null depth", hipSuccess);
-    RH_HIP(ctx, hipMemcpyAsync(depth, (const uint32_t *)ctx->pu_diff.p + first, (size_t)count * 4,
+    RH_HIP(ctx, hipMemcpyAsync(depth, (const uint32_t *)ctx->pileup.diff.p + first, (size_t)count * 4,
                                on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, ctx->stream));
     return rh_sync_tail(ctx, REAL_HIP_OK);
 }
@@ -1342,7 +1333,7 @@ extern "C" int real_hip_pileup_depth(real_hip_ctx *ctx, uint64_t first, uint64_t
 extern "C" int real_hip_pileup_sites(real_hip_ctx *ctx, real_hip_pileup_site *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    return list_out(ctx, ctx->pu_state == 2, "pileup", "sites", "site list", ctx->pu_sites.p, ctx->pu_n_sites, sizeof(real_hip_pileup_site), out, cap, n_out, on_device);
+    return list_out(ctx, ctx->pileup.state == 2, "pileup", "sites", "site list", ctx->pileup.sites.p, ctx->pileup.n_sites, sizeof(real_hip_pileup_site), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_pileup_end(real_hip_ctx *ctx)
@@ -1360,18 +1351,18 @@ extern "C" int real_hip_pileup_stats_get(real_hip_ctx *ctx, real_hip_pileup_stat
 // ---- variant calls (snp_call.hip): on top of the finished pileup; the reads and records are staged as the pileup stages them
 static int call_pileup_check(real_hip_ctx *ctx, const char *unfinished)
 {
-    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, unfinished, hipSuccess);
-    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+    if (ctx->pileup.state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, unfinished, hipSuccess);
+    if (!ctx->have_text || ctx->n_bases != ctx->pileup.n || ctx->fileid != ctx->pileup.fileid)
         return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: the text was replaced since the pileup's begin", hipSuccess);
     return REAL_HIP_OK;
 }
 static int call_add_check(real_hip_ctx *ctx)
 {
-    if (ctx->cl_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add without begin", hipSuccess);
-    if (ctx->cl_state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add after finish", hipSuccess);
+    if (ctx->call.state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add without begin", hipSuccess);
+    if (ctx->call.state == 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: add after finish", hipSuccess);
     return call_pileup_check(ctx, "calls: add without a finished pileup");
 }
-static const PlacementSink kCallSink = {"calls", call_add_check, &real_hip_ctx::cl_rec, rh_launch_call_add};
+static const PlacementSink kCallSink = {"calls", call_add_check, [](real_hip_ctx *c) -> DevBuf & { return c->call.rec; }, rh_launch_call_add};
 
 extern "C" int real_hip_call_begin(real_hip_ctx *ctx)
 {
@@ -1397,7 +1388,7 @@ extern "C" int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_param
 {
     RH_ENTER(ctx);
     if (!p || p->struct_size != sizeof(real_hip_call_params)) return rh_fail(ctx, REAL_HIP_E_INVALID, "call params struct_size", hipSuccess);
-    if (ctx->cl_state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: finish without begin", hipSuccess);
+    if (ctx->call.state == 0) return rh_fail(ctx, REAL_HIP_E_INVALID, "calls: finish without begin", hipSuccess);
     int rc = call_pileup_check(ctx, "calls: finish without a finished pileup");
     if (rc) return rc;
     return finish_tail(ctx, rh_sync_tail(ctx, rh_call_finish(ctx, p->min_call_qual, p->min_depth, n_calls)), rh_call_release);
@@ -1406,13 +1397,13 @@ extern "C" int real_hip_call_finish(real_hip_ctx *ctx, const real_hip_call_param
 extern "C" int real_hip_call_evidence(real_hip_ctx *ctx, real_hip_call_evidence_rec *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    return list_out(ctx, ctx->cl_state == 2, "calls", "evidence", "evidence list", ctx->cl_ev.p, ctx->pu_n_sites, sizeof(real_hip_call_evidence_rec), out, cap, n_out, on_device);
+    return list_out(ctx, ctx->call.state == 2, "calls", "evidence", "evidence list", ctx->call.ev.p, ctx->pileup.n_sites, sizeof(real_hip_call_evidence_rec), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_call_variants(real_hip_ctx *ctx, real_hip_call *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    return list_out(ctx, ctx->cl_state == 2, "calls", "variants", "variants list", ctx->cl_calls.p, ctx->cl_n_calls, sizeof(real_hip_call), out, cap, n_out, on_device);
+    return list_out(ctx, ctx->call.state == 2, "calls", "variants", "variants list", ctx->call.calls.p, ctx->call.n_calls, sizeof(real_hip_call), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_call_end(real_hip_ctx *ctx)
@@ -1446,14 +1437,14 @@ static int mismatch_run(real_hip_ctx *ctx, const RhStaging &io, const RhMismatch
     const uint64_t lists = l[0].b.n_reads * (uint64_t)n_launch;
     uint64_t *d_off = mm_offsets;
     int rc;
-    if ((rc = io.inout(ctx->mm_off, mm_offsets, lists + 1, true, d_off))) return rc; // (outputs: nothing is uploaded)
+    if ((rc = io.inout(ctx->mismatch.off, mm_offsets, lists + 1, true, d_off))) return rc; // (outputs: nothing is uploaded)
     uint64_t total = 0;
     if ((rc = rh_mismatch_count(ctx, l, n_launch, d_off, &total))) return rc;
     *n_out = total;
     if ((rc = io.back(mm_offsets, d_off, lists + 1, "download of the mismatch offsets"))) return rc;
     if (total > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "mismatch lists: the buffer needs more room", hipSuccess);
     real_hip_mismatch *d_out = out;
-    if ((rc = io.inout(ctx->mm_out, out, total, true, d_out, sizeof(real_hip_mismatch)))) return rc;
+    if ((rc = io.inout(ctx->mismatch.out, out, total, true, d_out, sizeof(real_hip_mismatch)))) return rc;
     if ((rc = rh_mismatch_emit(ctx, l, n_launch, d_off, d_out, total))) return rc;
     return io.back(out, d_out, total, "download of the mismatch lists");
 }
@@ -1466,7 +1457,7 @@ extern "C" int real_hip_mismatches(real_hip_ctx *ctx, const real_hip_batch *b, c
     int rc = batch_view(ctx, b, bv);
     if (rc || (rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, bv.on_device == 1))) return rc;
     PlacedReads p;
-    if ((rc = stage_placements(ctx, kMismatch, &bv, 1, info, nullptr, ctx->mm_rec, false, p))) return rh_sync_tail(ctx, rc);
+    if ((rc = stage_placements(ctx, kMismatch, &bv, 1, info, nullptr, ctx->mismatch.rec, false, p))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
     const RhMismatchLaunch l{p.b[0], p.info, nullptr, nullptr};
     return rh_sync_tail(ctx, mismatch_run(ctx, io, &l, 1, out, cap, n_out, mm_offsets)); // (n == 0 too: mm_offsets[0] is written)
@@ -1486,10 +1477,10 @@ extern "C" int real_hip_mismatches_pairs(real_hip_ctx *ctx, const real_hip_batch
     if (dev && (((uintptr_t)singles1 | (uintptr_t)singles2) & 15u)) return stage_invalid(ctx, kMismatch, "the single records must be 16-byte aligned");
     const uint64_t n = bv[0].n_reads;
     PlacedReads p;
-    if ((rc = stage_placements(ctx, kMismatch, bv, 2, nullptr, pairs, ctx->mm_rec, false, p))) return rh_sync_tail(ctx, rc);
+    if ((rc = stage_placements(ctx, kMismatch, bv, 2, nullptr, pairs, ctx->mismatch.rec, false, p))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
     RhMismatchLaunch l[2] = {{p.b[0], nullptr, p.pairs, singles1}, {p.b[1], nullptr, p.pairs, singles2}};
-    for (int m = 0; m < 2 && !rc && n && singles1; ++m) rc = io.in(ctx->mm_sg[m], m ? singles2 : singles1, n, l[m].singles);
+    for (int m = 0; m < 2 && !rc && n && singles1; ++m) rc = io.in(ctx->mismatch.sg[m], m ? singles2 : singles1, n, l[m].singles);
     if (!rc) rc = mismatch_run(ctx, io, l, 2, out, cap, n_out, mm_offsets);
     return rh_sync_tail(ctx, rc);
 }
@@ -1535,7 +1526,7 @@ extern "C" int real_hip_gap_rescue(real_hip_ctx *ctx, const real_hip_pair_params
     const uint64_t n = bv[0].n_reads;
     if (n && (!singles1 || !singles2 || !out)) return stage_invalid(ctx, kGap, "null singles / out");
     if (dev && (((uintptr_t)singles1 | (uintptr_t)singles2 | (uintptr_t)out) & 15u)) return stage_invalid(ctx, kGap, "the single and the gap records must be 16-byte aligned");
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     PlacedReads p;
     if ((rc = stage_placements(ctx, kGap, bv, 2, nullptr, pairs, S.rec, false, p))) return rh_sync_tail(ctx, rc);
     if (!n) return REAL_HIP_OK;
@@ -1581,7 +1572,7 @@ static int anchor_checks(real_hip_ctx *ctx, const real_hip_gap_params *gp, const
 static int anchor_stage(real_hip_ctx *ctx, const real_hip_gap_params *gp, const real_hip_gap_anchor_params *ap, const real_hip_batch &bv,
                         const uint64_t *info, int fresh, real_hip_gap_place *out, const RhStaging &io, RhAnchorRun &r)
 {
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     PlacedReads p;
     int rc;
     if ((rc = stage_placements(ctx, kAnchor, &bv, 1, info, nullptr, S.an_info, true, p, false))) return rc;
@@ -1625,7 +1616,7 @@ extern "C" int real_hip_match_gapped(real_hip_ctx *ctx, const real_hip_gap_param
     const uint64_t n = bv.n_reads;
     if (!n) return REAL_HIP_OK;
     const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream};
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     RhAnchorRun r;
     uint64_t count = 0, total = 0;
     if ((rc = anchor_stage(ctx, gp, ap, bv, info, fresh, out, io, r))) return rh_sync_tail(ctx, rc);
@@ -1673,7 +1664,7 @@ extern "C" int real_hip_mismatches_gapped(real_hip_ctx *ctx, const real_hip_batc
     const bool dev = bv[0].on_device == 1;
     if ((rc = mismatch_outputs_check(ctx, out, cap, n_out, mm_offsets, dev, kGapped)) || (rc = mates_agree(ctx, kGapped, bv, false))) return rc;
     const uint64_t n = bv[0].n_reads;
-    RhGapStage &S = rh_gap_stage(ctx);
+    RhGapStage &S = ctx->gap;
     GappedReads p;
     if ((rc = stage_gapped(ctx, kGapped, bv, gaps, S.gl_rec, false, p))) return rh_sync_tail(ctx, rc); // (n == 0 goes on: offsets of one entry)
     const RhStaging io{ctx, !dev, ctx->stream, ctx->stream};
@@ -1703,8 +1694,8 @@ extern "C" int real_hip_gapped_list_stats_get(real_hip_ctx *ctx, real_hip_gapped
 static const char *const kIndel = "indel calls";
 static int indel_pileup_check(real_hip_ctx *ctx, const char *unfinished)
 {
-    if (ctx->pu_state != 2) return stage_invalid(ctx, kIndel, unfinished);
-    if (!ctx->have_text || ctx->n_bases != ctx->pu_n || ctx->fileid != ctx->pu_fileid)
+    if (ctx->pileup.state != 2) return stage_invalid(ctx, kIndel, unfinished);
+    if (!ctx->have_text || ctx->n_bases != ctx->pileup.n || ctx->fileid != ctx->pileup.fileid)
         return stage_invalid(ctx, kIndel, "the text was replaced since the pileup's begin");
     return REAL_HIP_OK;
 }
@@ -1723,7 +1714,7 @@ extern "C" int real_hip_indel_add(real_hip_ctx *ctx, const real_hip_batch *b1, c
     real_hip_batch bv[2];
     int rc;
     if ((rc = mates_view(ctx, kIndel, b1, b2, false, bv))) return rc;
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     if (S.state == 0) return stage_invalid(ctx, kIndel, "add without begin");
     if (S.state == 2) return stage_invalid(ctx, kIndel, "add after finish");
     if ((rc = indel_pileup_check(ctx, "add without a finished pileup"))) return rc;
@@ -1737,7 +1728,7 @@ extern "C" int real_hip_indel_finish(real_hip_ctx *ctx, const real_hip_indel_par
 {
     RH_ENTER(ctx);
     if (!p || p->struct_size != sizeof(real_hip_indel_params)) return stage_invalid(ctx, kIndel, "params struct_size");
-    if (rh_indel_stage(ctx).state == 0) return stage_invalid(ctx, kIndel, "finish without begin");
+    if (ctx->indel.state == 0) return stage_invalid(ctx, kIndel, "finish without begin");
     int rc = indel_pileup_check(ctx, "finish without a finished pileup");
     if (rc) return rc;
     return finish_tail(ctx, rh_sync_tail(ctx, rh_indel_finish(ctx, *p, n_events, n_calls)), rh_indel_release);
@@ -1746,14 +1737,14 @@ extern "C" int real_hip_indel_finish(real_hip_ctx *ctx, const real_hip_indel_par
 extern "C" int real_hip_indel_events(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     return list_out(ctx, S.state == 2, kIndel, "events", "event list", S.events.p, S.n_groups, sizeof(real_hip_indel), out, cap, n_out, on_device);
 }
 
 extern "C" int real_hip_indel_calls(real_hip_ctx *ctx, real_hip_indel *out, uint64_t cap, uint64_t *n_out, int on_device)
 {
     RH_ENTER(ctx);
-    RhIndelStage &S = rh_indel_stage(ctx);
+    RhIndelStage &S = ctx->indel;
     return list_out(ctx, S.state == 2, kIndel, "calls", "call list", S.calls.p, S.n_calls, sizeof(real_hip_indel), out, cap, n_out, on_device);
 }
 
@@ -1780,7 +1771,7 @@ static int gapped_add(real_hip_ctx *ctx, const char *stage, int (*check)(real_hi
     int rc;
     if ((rc = mates_view(ctx, stage, b1, b2, false, bv)) || (rc = check(ctx))) return rc;
     GappedReads p;
-    if ((rc = stage_gapped(ctx, stage, bv, gaps, rh_pileup_gapped_stage(ctx).rec, true, p))) return rh_sync_tail(ctx, rc);
+    if ((rc = stage_gapped(ctx, stage, bv, gaps, ctx->pileup_gapped.rec, true, p))) return rh_sync_tail(ctx, rc);
     if (!bv[0].n_reads) return REAL_HIP_OK;
     return rh_sync_tail(ctx, add(ctx, p.b[0], p.b[1], p.gaps, bv[0].n_reads));
 }
@@ -1800,8 +1791,8 @@ extern "C" int real_hip_call_add_gapped(real_hip_ctx *ctx, const real_hip_batch 
 extern "C" int real_hip_pileup_depth_gapped(real_hip_ctx *ctx, uint64_t first, uint64_t count, uint32_t *depth, int on_device)
 {
     RH_ENTER(ctx);
-    if (ctx->pu_state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
-    if (first > ctx->pu_n || count > ctx->pu_n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
+    if (ctx->pileup.state != 2) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: depth before finish", hipSuccess);
+    if (first > ctx->pileup.n || count > ctx->pileup.n - first) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: the depth window reaches beyond the text", hipSuccess);
     if (!count) return REAL_HIP_OK;
     if (!depth) return rh_fail(ctx, REAL_HIP_E_INVALID, "pileup: null depth", hipSuccess);
     const uint32_t *g = rh_pileup_gapped_array(ctx);
@@ -1858,7 +1849,7 @@ extern "C" int real_hip_read_summary(real_hip_ctx *ctx, const real_hip_batch *b,
     if (bv.qual && (rc = in.in(ctx->stage[0].qual, bv.qual, total, db.qual, total ? total : 1))) return rh_sync_tail(ctx, rc);
     const RhStaging io{ctx, bv.on_device != 1, ctx->stream, ctx->stream}; // (host: the output is host memory)
     real_hip_read_sum *d_out = out;
-    rc = io.inout(ctx->dup_out, out, n, true, d_out);
+    rc = io.inout(ctx->dup.out, out, n, true, d_out);
     if (!rc) rc = rh_launch_read_summary(ctx, db, min_qual, d_out);
     if (!rc) rc = io.back(out, d_out, n, "download of the read summaries");
     return rh_sync_tail(ctx, rc);
@@ -1880,10 +1871,10 @@ static int mark_duplicates_run(real_hip_ctx *ctx, const uint64_t *info, const re
     const real_hip_gap_place *d_gaps = gaps;
     const real_hip_read_sum *d_sum[2] = {sum1, sum2};
     uint8_t *d_dup = dup;
-    int rc = info ? io.in(ctx->dup_rec, info, n, d_info) : io.in(ctx->dup_rec, pairs, n, d_pairs);
-    if (!rc && gaps) rc = io.in(rh_dup_gapped_stage(ctx).rec, gaps, n, d_gaps);
-    for (int m = 0; m < (pairs ? 2 : 1) && !rc; ++m) rc = io.in(ctx->dup_sum[m], m ? sum2 : sum1, n, d_sum[m]);
-    if (!rc) rc = io.inout(ctx->dup_out, dup, n, true, d_dup);
+    int rc = info ? io.in(ctx->dup.rec, info, n, d_info) : io.in(ctx->dup.rec, pairs, n, d_pairs);
+    if (!rc && gaps) rc = io.in(ctx->dup_gapped.rec, gaps, n, d_gaps);
+    for (int m = 0; m < (pairs ? 2 : 1) && !rc; ++m) rc = io.in(ctx->dup.sum[m], m ? sum2 : sum1, n, d_sum[m]);
+    if (!rc) rc = io.inout(ctx->dup.out, dup, n, true, d_dup);
     if (!rc) rc = gaps ? rh_launch_mark_duplicates_gapped(ctx, d_info, d_gaps, d_sum[0], n, d_dup)
                        : rh_launch_mark_duplicates(ctx, d_info, d_pairs, d_sum[0], d_sum[1], n, d_dup);
     if (!rc) rc = io.back(dup, d_dup, n, "download of the duplicate marks");
@@ -1929,36 +1920,36 @@ static int match_mates(real_hip_ctx *ctx, const real_hip_batch bv[2], bool both_
     const uint64_t n = bv[0].n_reads;
     total[0] = total[1] = 0;
     for (int m = 0; m < 2; ++m) {
-        if ((rc = rh_reserve(ctx, ctx->pair_off[m], (n + 1) * 8))) return rc;
-        if ((rc = rh_reserve(ctx, ctx->pair_len[m], n * 4))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->join.off[m], (n + 1) * 8))) return rc;
+        if ((rc = rh_reserve(ctx, ctx->join.len[m], n * 4))) return rc;
     }
     // the hit capacity is the library's problem: both buffers hold pair_cap hits; a match that needs more reports the size,
     // the buffers grow and the matches are done again
-    if (ctx->pair_cap < n + n / 4 + 1024) ctx->pair_cap = 0;
+    if (ctx->join.cap < n + n / 4 + 1024) ctx->join.cap = 0;
     for (int attempt = 0;; ++attempt) {
-        if (!ctx->pair_cap) {
+        if (!ctx->join.cap) {
             uint64_t want = n + n / 4 + 1024;
             if (total[0] > want) want = total[0];
             if (total[1] > want) want = total[1];
             for (int m = 0; m < 2; ++m)
-                if ((rc = rh_reserve(ctx, ctx->pair_hits[m], want * sizeof(real_hip_hit)))) return rc;
-            ctx->pair_cap = want;
+                if ((rc = rh_reserve(ctx, ctx->join.hits[m], want * sizeof(real_hip_hit)))) return rc;
+            ctx->join.cap = want;
         }
         bool overflow = false;
         for (int m = 0; m < 2; ++m) {
             Staged &s = st[m];
             s = Staged();
-            rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->pair_hits[m].p, ctx->pair_cap, &total[m], (uint64_t *)ctx->pair_off[m].p, &s,
+            rc = match_all_run(ctx, bv[m], true, (real_hip_hit *)ctx->join.hits[m].p, ctx->join.cap, &total[m], (uint64_t *)ctx->join.off[m].p, &s,
                                both_resident ? &ctx->stage[m] : nullptr);
             if (rc == REAL_HIP_E_OVERFLOW) { overflow = true; continue; } // (the other mate still reports its size)
             if (rc) return rc;
             // the read lengths, while this mate's offsets are staged
-            if ((rc = rh_pair_lens(ctx, s.off, s.upatl, n, (uint32_t *)ctx->pair_len[m].p))) return rc;
+            if ((rc = rh_pair_lens(ctx, s.off, s.upatl, n, (uint32_t *)ctx->join.len[m].p))) return rc;
         }
         if (!overflow) break;
         if (attempt >= 2) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffers of the pair join kept overflowing", hipSuccess);
         if (total[0] > 0xffffffffull || total[1] > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "more than 2^32 hits of one mate in one batch", hipSuccess);
-        ctx->pair_cap = 0;
+        ctx->join.cap = 0;
     }
     return REAL_HIP_OK;
 }
@@ -1984,7 +1975,7 @@ static int match_pairs_run(real_hip_ctx *ctx, const real_hip_batch *batch1, cons
     const int fresh = bv[0].fresh != 0;
     real_hip_pair *d_pairs = pairs;
     const RhStaging io{ctx, host_out, ctx->stream, ctx->stream};
-    if ((rc = io.inout(ctx->pair_rec, pairs, n, fresh != 0, d_pairs))) return rc;
+    if ((rc = io.inout(ctx->join.rec, pairs, n, fresh != 0, d_pairs))) return rc;
     rc = rh_launch_pair(ctx, *pp, L, n, ctx->fileid, fresh, d_pairs);
     real_hip_single *d_singles[2] = {nullptr, nullptr};
     if (!rc && singles) { // seed hits only: the search below adds nothing to the lists
@@ -2058,13 +2049,13 @@ static int match_resident(real_hip_ctx *ctx, const real_hip_batch &bv, uint64_t 
 {
     int rc;
     const uint64_t n = bv.n_reads;
-    if ((rc = rh_reserve(ctx, ctx->pair_off[0], (n + 1) * 8))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->join.off[0], (n + 1) * 8))) return rc;
     uint64_t want = n + n / 4 + 1024;
     for (int attempt = 0;; ++attempt) {
-        if ((rc = rh_reserve(ctx, ctx->pair_hits[0], want * sizeof(real_hip_hit)))) return rc;
-        const uint64_t cap = ctx->pair_hits[0].cap / sizeof(real_hip_hit);
+        if ((rc = rh_reserve(ctx, ctx->join.hits[0], want * sizeof(real_hip_hit)))) return rc;
+        const uint64_t cap = ctx->join.hits[0].cap / sizeof(real_hip_hit);
         Staged s;
-        rc = match_all_run(ctx, bv, true, (real_hip_hit *)ctx->pair_hits[0].p, cap, total, (uint64_t *)ctx->pair_off[0].p, &s);
+        rc = match_all_run(ctx, bv, true, (real_hip_hit *)ctx->join.hits[0].p, cap, total, (uint64_t *)ctx->join.off[0].p, &s);
         if (rc != REAL_HIP_E_OVERFLOW) return rc;
         if (attempt >= 2) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "hit buffer of the mapping quality fold kept overflowing", hipSuccess);
         if (*total > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "more than 2^32 hits in one batch", hipSuccess);
@@ -2087,7 +2078,7 @@ extern "C" int real_hip_match_mapq(real_hip_ctx *ctx, const real_hip_batch *batc
     if ((rc = match_resident(ctx, bv, &total))) return rc;
     MateLists L;
     memset(&L, 0, sizeof L);
-    L.h[0] = (const uint4 *)ctx->pair_hits[0].p; L.o[0] = (const uint64_t *)ctx->pair_off[0].p; L.total[0] = total;
+    L.h[0] = (const uint4 *)ctx->join.hits[0].p; L.o[0] = (const uint64_t *)ctx->join.off[0].p; L.total[0] = total;
     const int fresh = bv.fresh != 0;
     real_hip_mapq_acc *const av[1] = {acc};
     real_hip_mapq_acc *d_acc[2] = {nullptr, nullptr};
@@ -2117,7 +2108,7 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
     // (outputs: nothing is uploaded; without pair_offsets the scan still needs a device array)
     const RhStaging io{ctx, !dev_out, ctx->stream, ctx->stream}, off_io{ctx, !dev_out || !pair_offsets, ctx->stream, ctx->stream};
     uint64_t *d_off = pair_offsets;
-    if ((rc = off_io.inout(ctx->pa_off, pair_offsets, n + 1, true, d_off))) return rc;
+    if ((rc = off_io.inout(ctx->pair_all.off, pair_offsets, n + 1, true, d_off))) return rc;
     uint64_t found = 0;
     rc = rh_pair_all_count(ctx, pp, L, n, d_off, &found);
     rh_time_resolve(ctx);
@@ -2125,7 +2116,7 @@ static int pair_all_run(real_hip_ctx *ctx, const real_hip_pair_params &pp, const
     *n_out = found;
     if (found > cap) return rh_fail(ctx, REAL_HIP_E_OVERFLOW, "pair hit buffer too small", hipSuccess);
     real_hip_pair_hit *d_out = out;
-    if ((rc = io.inout(ctx->pa_out, out, found, true, d_out, sizeof(real_hip_pair_hit)))) return rc;
+    if ((rc = io.inout(ctx->pair_all.out, out, found, true, d_out, sizeof(real_hip_pair_hit)))) return rc;
     rc = rh_pair_all_emit(ctx, pp, L, n, fileid, d_off, d_out, dev_out ? cap : found, found);
     if (!rc) rc = io.back(out, d_out, found, "download of the pair hits");
     if (!rc && pair_offsets) rc = io.back(pair_offsets, d_off, n + 1, "download of the pair hits");

@@ -170,343 +170,3 @@ struct MatchArgs {
     double   filter_mult;
     uint32_t l, q, b_bits, seedkmax, totalkmax;
 };
-
-// ---- host context ------------------------------------------------------------
-struct DevBuf;
-struct real_hip_ctx;
-void rh_release(DevBuf &b);
-// a device allocation and its owner: it goes with whatever holds it (the ctx, a slot, a function's scope)
-struct DevBuf {
-    void  *p = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { rh_release(*this); }
-};
-
-// device copies of a host batch's four arrays: the ctx's own two sets (synchronous calls; the second holds mate 2 while
-// both mates are resident) or those of a slot (submit / wait)
-struct BatchBufs {
-    DevBuf bases, qual, off, nflags;
-};
-
-// one slot of the submit / wait pipeline: device copies of a host batch and its records
-struct RhSlot {
-    BatchBufs in;
-    DevBuf info, score;
-    hipEvent_t up = nullptr, matched = nullptr, done = nullptr;
-    uint64_t n = 0;
-    int status = 0;
-    bool busy = false, empty = false;
-};
-
-// what the ctx keeps of one paired stage: the items it was given, its launches and their event times since the last reset,
-// and the striped statistics its kernels add to (rh_stats_reserve)
-struct RhStageCount {
-    uint64_t items = 0, launches = 0;
-    double   kernel_ms = 0;
-};
-struct RhStage : RhStageCount {
-    DevBuf stats;
-};
-
-struct real_hip_ctx {
-    real_hip_params prm;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string last_error;
-
-    // text
-    DevBuf text, wild, frag;
-    uint64_t n_bases = 0;
-    uint64_t n_wild = 0;
-    uint32_t n_frag = 0, fileid = 0;
-    bool have_text = false;
-
-    // index
-    DevBuf ent[6], bkt[6];
-    uint64_t n_entries = 0;
-    uint32_t pb = 0;
-    RhLayout layout = RH_LAYOUT_STARTS;
-    bool no_rows = false; // bucket rows did not fit the device memory once: stay with directory tables
-    bool have_index = false;
-
-    // tables / counters
-    DevBuf LL, counters;
-
-    // batch staging (host batches), hand-over list of the repeat kernel
-    BatchBufs stage[2];
-    DevBuf s_info, s_score;
-    RhSlot slot[REAL_HIP_SLOTS];                    // submit / wait
-    hipStream_t copy_stream = nullptr, down_stream = nullptr;
-    DevBuf maxpatl, ovf_list, ovf2_list, ovf_count, qspill;
-    unsigned long long *h_state = nullptr; // pinned: {reads handed over, error flags} of the last launch of slot 0, slot 1, the synchronous calls
-    // read ingestion (read_parse.hip)
-    DevBuf p_text, p_nl, p_scal, p_spans, p_off, p_len1, p_bases, p_qual;
-    // matchAll workspace
-    DevBuf raw, raw_count, hit_cnt, big_list, all_cursor, keys_a, keys_b, vals_a, vals_b, sort_tmp, hit_off, s_hits;
-
-    // paired-end join (pair_kernel.hip): the two mates' hit lists, offsets and read lengths, staged records, the hand-over
-    // list of the wave kernel; its two kernels are timed under their public ids, join.launches / kernel_ms stay 0
-    DevBuf pair_hits[2], pair_off[2], pair_len[2], pair_rec, pair_list;
-    uint64_t pair_cap = 0;   // hits each of pair_hits[] holds (grown when a match overflowed it)
-    RhStage join;
-
-    // mate search (mate_search.hip): the kernel's error flags lie behind its statistics
-    RhStage search;
-    uint32_t ms_err = 0;     // the flags of the last launch, copied back behind it
-
-    // every concordant pair of a fragment (pair_all.hip): counts per fragment, their scan and the staged records when the
-    // caller's outputs are host memory
-    DevBuf pa_cnt, pa_off, pa_out;
-    RhStage pair_all;
-    uint64_t pa_pairs_out = 0;
-
-    // single placements of a mate (single_fold.hip): the staged records of the two lists when the caller's are host memory,
-    // the hand-over list of the wave kernel
-    DevBuf sg_rec[2], sg_list;
-    RhStage single;
-
-    // insert-size histogram (insert_hist.hip): the staged records, lengths and histogram when the caller's are host memory
-    DevBuf ih_rec, ih_len[2], ih_hist;
-    RhStage insert;
-
-    // pileup (pileup.hip): the depth's difference array (n + 1 u32, scanned in place by finish), the alt table (4 u32 per
-    // position), the per-block site counts and their scan, the site list, covered / max_depth of finish (striped), the
-    // staged records when the caller's are host memory
-    DevBuf pu_diff, pu_alt, pu_blk, pu_sites, pu_fin, pu_rec;
-    RhStage pileup;
-    int      pu_state = 0;   // 0 none, 1 begun (adds), 2 finished (depth / sites)
-    uint64_t pu_n = 0, pu_n_sites = 0, pu_covered = 0, pu_max_depth = 0; // the text begin saw; the last finish
-    uint32_t pu_fileid = 0, pu_min_qual = 0;
-
-    // variant calls (snp_call.hip), on top of the finished pileup: the site bitmap (a bit per text position) and its rank array
-    // (sites before each 64-bit word), the evidence table (32 bytes per site), the per-block call counts and their scan, the
-    // call list, het / hom of finish (striped), the staged records when the caller's are host memory
-    DevBuf cl_bits, cl_rank, cl_ev, cl_blk, cl_calls, cl_fin, cl_rec;
-    RhStage call;
-    int      cl_state = 0;   // 0 none, 1 begun (adds), 2 finished (evidence / variants; finish again)
-    uint64_t cl_n_calls = 0, cl_het = 0, cl_hom = 0; // the last finish
-
-    // mismatch lists (mismatch_list.hip): the counts per list, and when the caller's arrays are host memory the staged
-    // records (info or pairs, the two mates' singles), the offsets and the lists
-    DevBuf mm_cnt, mm_off, mm_out, mm_rec, mm_sg[2];
-    RhStage mismatch;
-
-    // duplicate marking (duplicates.hip): the two buffers of the sort's keys and values, the paired key's two words in record
-    // order, and when the caller's arrays are host memory the staged records, summaries and marks
-    DevBuf dup_key[2], dup_val[2], dup_lo, dup_hi, dup_rec, dup_sum[2], dup_out;
-    RhStage dup;
-
-    // where the wall time of an index build goes (real_hip_index_build_stats)
-    double   alloc_ms = 0, free_ms = 0, build_wall_ms = 0;
-    uint64_t alloc_bytes = 0, alloc_calls = 0, free_calls = 0;
-
-    // multi-GPU (gather.hip): an RCCL communicator over the ranks' devices, one process per GPU
-    void *comm = nullptr;
-    int comm_rank = 0, comm_size = 1;
-    DevBuf comm_counts, comm_scratch;
-
-    // timing
-    bool timing = true;
-    double   k_ms[REAL_HIP_K_COUNT] = {};
-    uint64_t k_n[REAL_HIP_K_COUNT] = {};
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // asynchronous timing of pipelined launches: event pairs resolved at the next synchronisation point
-    struct Pending { hipEvent_t a, b; double *ms; uint64_t *n; }; // where the time goes: a k_ms / k_n slot, or a stage's kernel_ms (n null)
-    std::vector<Pending> pending;
-    std::vector<hipEvent_t> ev_pool;
-};
-
-// error plumbing: never throw across the ABI
-int rh_fail(real_hip_ctx *ctx, int status, const char *what, hipError_t e);
-#define RH_HIP(ctx, call)                                                          \
-    do {                                                                           \
-        hipError_t _e = (call);                                                    \
-        if (_e != hipSuccess) return rh_fail((ctx), REAL_HIP_E_DEVICE, #call, _e); \
-    } while (0)
-int rh_reserve(real_hip_ctx *ctx, DevBuf &b, size_t bytes);
-void rh_release(real_hip_ctx *ctx, DevBuf &b); // (timed: real_hip_index_build_stats)
-double rh_now_ms();
-// a function-local device buffer whose release is charged to the ctx's build statistics
-struct ScopedBuf : DevBuf {
-    real_hip_ctx *c;
-    explicit ScopedBuf(real_hip_ctx *ctx) : c(ctx) {}
-    ~ScopedBuf() { rh_release(c, *this); }
-};
-
-// The one rule for an array that crosses the ABI.  host: the caller's arrays are host memory, each is copied into a DevBuf
-// of the ctx on `up` and the kernels read the copy; otherwise the caller's pointer is the device view.
-//   in     the device view of `count` elements (room: bytes to reserve where that is more than the elements take)
-//   inout  the same, the upload skipped when `fresh` (the kernel starts every record itself)
-//   back   the download on `down`; its error is returned, so that the caller's rh_sync_tail still runs
-struct RhStaging {
-    real_hip_ctx *ctx;
-    bool host;
-    hipStream_t up, down;
-    int view(DevBuf &buf, const void *src, size_t bytes, size_t room, bool upload, void **dev) const;
-    int back_bytes(void *dst, const void *dev, size_t bytes, const char *what) const;
-    template <typename T> int in(DevBuf &buf, const T *src, size_t count, const T *&dev, size_t room = 0) const
-    {
-        void *d = nullptr;
-        const int rc = view(buf, src, count * sizeof(T), room, true, &d);
-        dev = static_cast<const T *>(d);
-        return rc;
-    }
-    template <typename T> int inout(DevBuf &buf, T *src, size_t count, bool fresh, T *&dev, size_t room = 0) const
-    {
-        void *d = nullptr;
-        const int rc = view(buf, src, count * sizeof(T), room, !fresh, &d);
-        dev = static_cast<T *>(d);
-        return rc;
-    }
-    template <typename T> int back(T *dst, const T *dev, size_t count, const char *what) const
-    {
-        return back_bytes(dst, dev, count * sizeof(T), what);
-    }
-};
-
-struct RhTimer { // HIP events on the ctx stream around a group of launches
-    real_hip_ctx *c;
-    int which;
-    RhTimer(real_hip_ctx *ctx, int w);
-    ~RhTimer();
-};
-
-// the launch of a kernel that takes one thread per element, 256 to a block; nothing is launched for n = 0.  The arguments
-// convert as they do in a plain launch: implicitly, so a pointer of another type does not compile
-template <typename... P, typename... A>
-static inline void rh_launch_each(void (*kernel)(P...), uint64_t n, hipStream_t st, const A &...args)
-{
-    static_assert(sizeof...(P) == sizeof...(A), "one argument per kernel parameter");
-    if (n) hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, args...);
-}
-
-// ---- kernels launchers (match_kernels.hip) -----------------------------------
-void rh_comm_destroy(real_hip_ctx *ctx);
-int rh_launch_match(real_hip_ctx *ctx, const MatchArgs &a, bool all, int state_slot);
-int rh_match_finish(real_hip_ctx *ctx, int state_slot); // after the launch has completed: errors the kernels flagged
-
-// asynchronous kernel timing (no host synchronisation at the launch site)
-void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, int which);   // a public kernel id: k_ms / k_n
-void rh_time_begin(real_hip_ctx *ctx, hipStream_t st, RhStage &stage); // a paired stage: its kernel_ms
-void rh_time_end(real_hip_ctx *ctx, hipStream_t st);
-void rh_time_resolve(real_hip_ctx *ctx); // call after the streams were synchronised
-// the bracket as a scope: a return between begin and end (RH_HIP) still closes it, so no Pending record stays without its end
-// event.  The end is recorded where the scope ends: braces where that is before a host synchronisation.
-struct RhTimed {
-    real_hip_ctx *c;
-    hipStream_t st;
-    RhTimed(real_hip_ctx *ctx, hipStream_t s, int which) : c(ctx), st(s) { rh_time_begin(c, st, which); }
-    RhTimed(real_hip_ctx *ctx, hipStream_t s, RhStage &stage) : c(ctx), st(s) { rh_time_begin(c, st, stage); }
-    RhTimed(const RhTimed &) = delete;
-    RhTimed &operator=(const RhTimed &) = delete;
-    ~RhTimed() { rh_time_end(c, st); }
-};
-// synchronises the ctx's stream on the way out of a scope, whichever way: declared BEHIND the ScopedBufs a function's kernels
-// use, it runs before they are released
-struct RhSyncOnExit {
-    real_hip_ctx *c;
-    explicit RhSyncOnExit(real_hip_ctx *ctx) : c(ctx) {}
-    RhSyncOnExit(const RhSyncOnExit &) = delete;
-    RhSyncOnExit &operator=(const RhSyncOnExit &) = delete;
-    ~RhSyncOnExit() { (void)hipStreamSynchronize(c->stream); }
-};
-int rh_max_patl(real_hip_ctx *ctx, const uint64_t *d_off, uint64_t n_reads, uint32_t *out);
-int rh_parse_reads(real_hip_ctx *ctx, const char *d_text, uint64_t n_bytes, int fastq, int qoff, real_hip_parsed *out);
-int rh_all_finish(real_hip_ctx *ctx, uint64_t n_raw, uint64_t n_reads, real_hip_hit *d_out,
-                  uint64_t *d_hit_offsets);
-
-// ---- what the paired-end stages share ---------------------------------------------
-struct MateLists; // the two mates' hit lists on the device (pair_state.h)
-// a fixed grid of waves (four per block) takes `work` items in turn: the number of handed-over fragments stays on the
-// device, and what a block loads once (the mate search's score table) is loaded at most this often
-static inline unsigned rh_wave_blocks(uint64_t work) { return (unsigned)((work + 3) / 4 < 2048 ? (work + 3) / 4 : 2048); }
-// striped statistics: `stripes` 128-byte lines of 16 words, summed on the host (see RH_CSTRIPES), with extra_bytes behind
-// them.  rh_stats_reserve allocates and zeroes the buffer on first use; rh_stats_read sums words 0 .. n_words - 1 over the
-// stripes into out[] (zeros while there is no buffer), clears the stripes if `reset`, and synchronises the stream
-int rh_stats_reserve(real_hip_ctx *ctx, DevBuf &buf, size_t stripes, size_t extra_bytes);
-int rh_stats_read(real_hip_ctx *ctx, const DevBuf &buf, size_t stripes, int n_words, int reset, uint64_t out[]);
-// what the stages' stats functions share: the striped words into h[], the pending event times resolved, `was` = the counts
-// as they stand, which then start again if `reset`
-int rh_stage_read(real_hip_ctx *ctx, RhStage &stage, size_t stripes, int n_words, int reset, uint64_t h[], RhStageCount &was);
-
-// ---- paired-end join (pair_kernel.hip) ------------------------------------------
-int rh_pair_lens(real_hip_ctx *ctx, const uint64_t *d_off, uint32_t upatl, uint64_t n, uint32_t *d_len);
-int rh_launch_pair(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
-int rh_pair_stats(real_hip_ctx *ctx, real_hip_pair_stats *out, int reset);
-
-// ---- mate search (mate_search.hip) ----------------------------------------------
-// asynchronous on the ctx's stream; after the stream was synchronised rh_mate_search_finish reports what the kernel flagged
-int rh_launch_mate_search(real_hip_ctx *ctx, const real_hip_pair_params &pp, const real_hip_mate_search_params &sp, const DevBatch &b1,
-                          const DevBatch &b2, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_pair *d_pairs);
-int rh_mate_search_finish(real_hip_ctx *ctx);
-int rh_mate_search_stats(real_hip_ctx *ctx, real_hip_mate_search_stats *out, int reset);
-
-// ---- every concordant pair of a fragment (pair_all.hip) ---------------------------
-// count + scan into d_off (n + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
-int rh_pair_all_count(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint64_t *d_off, uint64_t *total);
-int rh_pair_all_emit(real_hip_ctx *ctx, const real_hip_pair_params &pp, const MateLists &L, uint64_t n, uint32_t fileid, const uint64_t *d_off,
-                     real_hip_pair_hit *d_out, uint64_t cap, uint64_t total);
-int rh_pair_all_stats(real_hip_ctx *ctx, real_hip_pair_all_stats *out, int reset);
-
-// ---- single placements of a mate (single_fold.hip) ---------------------------------
-int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t n, uint32_t fileid, int fresh, real_hip_single *const d_out[2]);
-int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset);
-
-// ---- insert-size histogram (insert_hist.hip) ----------------------------------------
-// d_hist += the histogram of n records, all arrays on the device; asynchronous on the ctx's stream
-int rh_launch_insert_hist(real_hip_ctx *ctx, const real_hip_pair *d_pairs, const uint32_t *d_len1, const uint32_t *d_len2, uint64_t n,
-                          uint32_t n_bins, uint64_t *d_hist);
-int rh_insert_stats(real_hip_ctx *ctx, real_hip_insert_stats *out, int reset);
-
-// ---- pileup (pileup.hip) ---------------------------------------------------------------
-int rh_pileup_begin(real_hip_ctx *ctx, uint32_t min_qual);
-// the placements of a batch (d_info) or of mate `mate` of a batch of pairs (d_pairs), all arrays on the device; asynchronous
-int rh_launch_pileup_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate);
-int rh_pileup_finish(real_hip_ctx *ctx, uint64_t *n_sites); // synchronises
-void rh_pileup_end(real_hip_ctx *ctx);
-int rh_pileup_stats(real_hip_ctx *ctx, real_hip_pileup_stats *out, int reset);
-
-// ---- variant calls (snp_call.hip) ------------------------------------------------------------
-int rh_call_begin(real_hip_ctx *ctx); // bitmap, rank array and zeroed evidence from the pileup's site list; synchronises
-// the evidence of a batch (d_info) or of mate `mate` of a batch of pairs (d_pairs), all arrays on the device; asynchronous
-int rh_launch_call_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_info, const real_hip_pair *d_pairs, uint32_t mate);
-int rh_call_finish(real_hip_ctx *ctx, uint32_t min_call_qual, uint32_t min_depth, uint64_t *n_calls); // synchronises
-void rh_call_release(real_hip_ctx *ctx); // (no synchronisation: the caller's)
-int rh_call_stats(real_hip_ctx *ctx, real_hip_call_stats *out, int reset);
-
-// ---- mismatch lists (mismatch_list.hip) -------------------------------------------------
-// one launch: the reads and the records that place them, all arrays on the device: info (single-end), or pairs and -- nullable --
-// this mate's singles
-struct RhMismatchLaunch {
-    DevBatch b;
-    const uint64_t *info;
-    const real_hip_pair *pairs;
-    const real_hip_single *singles;
-};
-// l[0] (single-end: n lists) or l[0], l[1] = mate 1, mate 2 (pairs: 2n lists, mate m of fragment i is list 2i + m).  count +
-// scan into d_off (lists + 1, device) + the total read back (synchronises); then, if it fits, the records (asynchronous)
-int rh_mismatch_count(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, uint64_t *d_off, uint64_t *total);
-int rh_mismatch_emit(real_hip_ctx *ctx, const RhMismatchLaunch l[], int n_launch, const uint64_t *d_off, real_hip_mismatch *d_out, uint64_t total);
-int rh_mismatch_stats(real_hip_ctx *ctx, real_hip_mismatch_stats *out, int reset);
-
-// ---- duplicate marking (duplicates.hip) ---------------------------------------------------
-// {len, qsum} of every read of b (qual, off, upatl, n_reads; the bases are not read), all arrays on the device; asynchronous
-int rh_launch_read_summary(real_hip_ctx *ctx, const DevBatch &b, uint32_t min_qual, real_hip_read_sum *d_out);
-// dup[] of n records, all arrays on the device: d_info and d_sum1 (single-end) or d_pairs, d_sum1 and d_sum2; asynchronous
-int rh_launch_mark_duplicates(real_hip_ctx *ctx, const uint64_t *d_info, const real_hip_pair *d_pairs, const real_hip_read_sum *d_sum1,
-                              const real_hip_read_sum *d_sum2, uint64_t n, uint8_t *d_dup);
-int rh_dup_stats(real_hip_ctx *ctx, real_hip_dup_stats *out, int reset);
-
-// ---- text + index (index_build.hip; the plan itself: index_plan.h) ---------------
-int rh_pack_text(real_hip_ctx *ctx, const uint8_t *d_sym, uint64_t n);
-int rh_count_wild(real_hip_ctx *ctx, uint64_t n); // n_wild of a text that was set packed
-int rh_index_from_host_lists(real_hip_ctx *ctx, uint64_t n, const void *const sign[6], const uint32_t *const pos[6], unsigned sig_bytes);
-int rh_index_build_device(real_hip_ctx *ctx, uint64_t first_window, uint64_t max_entries,
-                          uint64_t *n_entries, int *have_next);
-void rh_choose_tables(real_hip_ctx *ctx, uint64_t n_entries); // sets ctx->pb and ctx->layout (rh_plan_tables for this device)
-// ---- read-back of the resident index (index_readback.hip: tests, CPU baseline) ----
-int rh_rows_unpack(real_hip_ctx *ctx, int list, uint2 *d_entries, uint32_t *d_starts, bool canonical);
-int rh_index_export(real_hip_ctx *ctx, int list, void *h_sign, uint32_t *h_pos);

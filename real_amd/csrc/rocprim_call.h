@@ -3,7 +3,7 @@
 //     [&](void *tmp, size_t &bytes) { return rocprim::exclusive_scan(tmp, bytes, in, out, ...); }
 // and asked for its size (rh_prim_size) or run (rh_prim_run) through it.
 #pragma once
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 
 // the temporary bytes `call` needs, folded into a running maximum (one temporary serves several calls)
 template <typename F> static inline int rh_prim_size(real_hip_ctx *ctx, F &&call, size_t &max_bytes, const char *what)

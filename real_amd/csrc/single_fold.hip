@@ -8,7 +8,7 @@
 //
 // Nothing depends on the order of the hits, the lanes or the waves: merging two states (single_state.h) is associative and
 // commutative.  No LDS, no scratch memory; plain C++ and vector stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "single_state.h"
 
 struct SingleArgs {
@@ -94,20 +94,20 @@ int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t 
     if (!n) return REAL_HIP_OK;
     if (n > 0xffffffffull) return rh_fail(ctx, REAL_HIP_E_INVALID, "more than 2^32 reads in one call", hipSuccess);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->single.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->sg_list, (size_t)lists * n * 8 + 8))) return rc;
+    if ((rc = rh_stats_reserve(ctx, ctx->single.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->single.list, (size_t)lists * n * 8 + 8))) return rc;
     const int l1 = lists > 1 ? 1 : 0; // (one list: both slots describe it, slot 1 is never selected)
     SingleArgs A;
     A.L = L;
     A.L.h[1] = L.h[l1]; A.L.o[1] = L.o[l1]; A.L.len[1] = L.len[l1]; A.L.total[1] = L.total[l1];
     A.out[0] = (uint4 *)d_out[0]; A.out[1] = (uint4 *)d_out[l1];
     A.n = n;
-    A.list_count = (unsigned long long *)ctx->sg_list.p; A.list = (unsigned long long *)ctx->sg_list.p + 1;
-    A.stats = (unsigned long long *)ctx->single.stats.p;
+    A.list_count = (unsigned long long *)ctx->single.list.p; A.list = (unsigned long long *)ctx->single.list.p + 1;
+    A.stats = (unsigned long long *)ctx->single.stage.stats.p;
     A.filter_mult = ctx->prm.filter_mult;
     A.fresh = fresh ? 1u : 0u; A.fileid = fileid; A.scores = ctx->prm.scores ? 1u : 0u;
-    RH_HIP(ctx, hipMemsetAsync(ctx->sg_list.p, 0, 8, ctx->stream));
-    rh_time_begin(ctx, ctx->stream, ctx->single);
+    RH_HIP(ctx, hipMemsetAsync(ctx->single.list.p, 0, 8, ctx->stream));
+    rh_time_begin(ctx, ctx->stream, ctx->single.stage);
     hipLaunchKernelGGL(single_lane_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)lists), dim3(256), 0, ctx->stream, A);
     RH_HIP(ctx, hipGetLastError());
     // a fixed grid of waves takes the handed-over reads in turn (their number stays on the device)
@@ -115,8 +115,8 @@ int rh_launch_single(real_hip_ctx *ctx, int lists, const MateLists &L, uint64_t 
     hipLaunchKernelGGL(single_wave_kernel, dim3(rh_wave_blocks(work)), dim3(256), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->single.items += work;
-    ctx->single.launches += 2;
+    ctx->single.stage.items += work;
+    ctx->single.stage.launches += 2;
     return REAL_HIP_OK;
 }
 
@@ -125,7 +125,7 @@ int rh_single_stats(real_hip_ctx *ctx, real_hip_single_stats *out, int reset)
     uint64_t h[2];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->single, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->single.stage, RH_PAIR_STRIPES, 2, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->hits = h[0]; out->handed_over = h[1];

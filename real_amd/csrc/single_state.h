@@ -3,7 +3,7 @@
 // pair_state.h keeps them for the pairs.  The values are scores (floats) or small integers, so the record holds floats;
 // the fold and the state's comparison are in FP64, which holds every float exactly.
 #pragma once
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "pair_state.h"
 
 #define RH_SINGLE_LANE_BUDGET 32u /* hits a lane walks itself (the join's budget, RH_PAIR_LANE_BUDGET; not measured for the fold) */

@@ -22,7 +22,7 @@
 //
 // Everything is an integer sum or a function of one.  No LDS in the add kernel, no scratch memory; plain C++ and vector
 // stores.
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "read_walk.h"
 
 #include <rocprim/device/device_scan.hpp>
@@ -200,12 +200,12 @@ __global__ void __launch_bounds__(RH_CL_BLOCK) call_sites_kernel(const CallFinAr
 // ---- host side --------------------------------------------------------------------------------------------------
 void rh_call_release(real_hip_ctx *ctx)
 {
-    rh_release(ctx, ctx->cl_bits); rh_release(ctx, ctx->cl_rank); rh_release(ctx, ctx->cl_ev); rh_release(ctx, ctx->cl_blk);
-    rh_release(ctx, ctx->cl_calls);
-    ctx->cl_state = 0; ctx->cl_n_calls = 0; ctx->cl_het = 0; ctx->cl_hom = 0;
+    rh_release(ctx, ctx->call.bits); rh_release(ctx, ctx->call.rank); rh_release(ctx, ctx->call.ev); rh_release(ctx, ctx->call.blk);
+    rh_release(ctx, ctx->call.calls);
+    ctx->call.state = 0; ctx->call.n_calls = 0; ctx->call.het = 0; ctx->call.hom = 0;
 }
 
-static uint64_t call_bitmap_words(const real_hip_ctx *ctx) { return (ctx->pu_n >> 6) + 2; } // (one behind the last position's: the funnel shift)
+static uint64_t call_bitmap_words(const real_hip_ctx *ctx) { return (ctx->pileup.n >> 6) + 2; } // (one behind the last position's: the funnel shift)
 
 int rh_call_begin(real_hip_ctx *ctx)
 {
@@ -213,28 +213,28 @@ int rh_call_begin(real_hip_ctx *ctx)
                       offsetof(real_hip_call, ref) == 28 && offsetof(real_hip_call, gq) == 31,
                   "evidence and call records are two 16-byte stores");
     static_assert(offsetof(real_hip_pileup_site, pos) == 0 && offsetof(real_hip_pileup_site, ref) == 24, "the kernels read pos and ref of a site record");
-    const uint64_t words = call_bitmap_words(ctx), n_sites = ctx->pu_n_sites;
+    const uint64_t words = call_bitmap_words(ctx), n_sites = ctx->pileup.n_sites;
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rh_call_release(ctx);
     int rc;
-    if ((rc = rh_stats_reserve(ctx, ctx->call.stats, RH_PAIR_STRIPES, 0))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->cl_fin, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
-    if ((rc = rh_reserve(ctx, ctx->cl_bits, (size_t)words * 8)) || (rc = rh_reserve(ctx, ctx->cl_rank, (size_t)words * 4)) ||
-        (rc = rh_reserve(ctx, ctx->cl_ev, (size_t)(n_sites ? n_sites : 1) * sizeof(real_hip_call_evidence_rec)))) {
+    if ((rc = rh_stats_reserve(ctx, ctx->call.stage.stats, RH_PAIR_STRIPES, 0))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->call.fin, (size_t)RH_PAIR_STRIPES * 16 * 8))) return rc;
+    if ((rc = rh_reserve(ctx, ctx->call.bits, (size_t)words * 8)) || (rc = rh_reserve(ctx, ctx->call.rank, (size_t)words * 4)) ||
+        (rc = rh_reserve(ctx, ctx->call.ev, (size_t)(n_sites ? n_sites : 1) * sizeof(real_hip_call_evidence_rec)))) {
         rh_call_release(ctx);
         return rh_fail(ctx, REAL_HIP_E_NOMEM, "calls: the site bitmap, its rank array and the evidence (n/8 + n/16 + 32 bytes per site) do not fit the device memory",
                        hipSuccess);
     }
-    RH_HIP(ctx, hipMemsetAsync(ctx->cl_ev.p, 0, (size_t)(n_sites ? n_sites : 1) * sizeof(real_hip_call_evidence_rec), ctx->stream));
-    rh_time_begin(ctx, ctx->stream, ctx->call);
+    RH_HIP(ctx, hipMemsetAsync(ctx->call.ev.p, 0, (size_t)(n_sites ? n_sites : 1) * sizeof(real_hip_call_evidence_rec), ctx->stream));
+    rh_time_begin(ctx, ctx->stream, ctx->call.stage);
     hipLaunchKernelGGL(call_bitmap_kernel, dim3((unsigned)((words + RH_CL_BLOCK - 1) / RH_CL_BLOCK)), dim3(RH_CL_BLOCK), 0, ctx->stream,
-                       (const uint4 *)ctx->pu_sites.p, n_sites, words, (uint64_t *)ctx->cl_bits.p, (uint32_t *)ctx->cl_rank.p);
+                       (const uint4 *)ctx->pileup.sites.p, n_sites, words, (uint64_t *)ctx->call.bits.p, (uint32_t *)ctx->call.rank.p);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->call.launches += 1;
+    ctx->call.stage.launches += 1;
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     rh_time_resolve(ctx);
-    ctx->cl_state = 1;
+    ctx->call.state = 1;
     return REAL_HIP_OK;
 }
 
@@ -246,66 +246,66 @@ int rh_launch_call_add(real_hip_ctx *ctx, const DevBatch &b, const uint64_t *d_i
     memset(&A, 0, sizeof A);
     A.t = rh_dev_text(ctx, ctx->fileid);
     A.b = b;
-    A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pu_min_qual;
-    A.bits = (const uint64_t *)ctx->cl_bits.p; A.rank = (const uint32_t *)ctx->cl_rank.p; A.ev = (uint32_t *)ctx->cl_ev.p;
-    A.n_sites = ctx->pu_n_sites;
-    A.stats = (unsigned long long *)ctx->call.stats.p;
+    A.info = d_info; A.pairs = (const uint2 *)d_pairs; A.mate = mate; A.min_qual = ctx->pileup.min_qual;
+    A.bits = (const uint64_t *)ctx->call.bits.p; A.rank = (const uint32_t *)ctx->call.rank.p; A.ev = (uint32_t *)ctx->call.ev.p;
+    A.n_sites = ctx->pileup.n_sites;
+    A.stats = (unsigned long long *)ctx->call.stage.stats.p;
     const unsigned blocks = (unsigned)((n + RH_CL_BLOCK - 1) / RH_CL_BLOCK);
-    rh_time_begin(ctx, ctx->stream, ctx->call);
+    rh_time_begin(ctx, ctx->stream, ctx->call.stage);
     if (d_pairs) hipLaunchKernelGGL(call_add_kernel<true>, dim3(blocks), dim3(RH_CL_BLOCK), 0, ctx->stream, A);
     else hipLaunchKernelGGL(call_add_kernel<false>, dim3(blocks), dim3(RH_CL_BLOCK), 0, ctx->stream, A);
     rh_time_end(ctx, ctx->stream);
     RH_HIP(ctx, hipGetLastError());
-    ctx->call.items += n;
-    ctx->call.launches += 1;
+    ctx->call.stage.items += n;
+    ctx->call.stage.launches += 1;
     return REAL_HIP_OK;
 }
 
 int rh_call_finish(real_hip_ctx *ctx, uint32_t min_call_qual, uint32_t min_depth, uint64_t *n_calls)
 {
-    const uint64_t n_sites = ctx->pu_n_sites;
+    const uint64_t n_sites = ctx->pileup.n_sites;
     const uint64_t blocks = (n_sites + RH_CL_BLOCK - 1) / RH_CL_BLOCK;
     int rc;
-    ctx->cl_n_calls = 0; ctx->cl_het = 0; ctx->cl_hom = 0;
-    if (!n_sites) { ctx->cl_state = 2; if (n_calls) *n_calls = 0; return REAL_HIP_OK; } // (no kernel over an empty table)
-    if ((rc = rh_reserve(ctx, ctx->cl_blk, (size_t)(blocks + 1) * 16))) return rc;
-    uint64_t *blk = (uint64_t *)ctx->cl_blk.p, *blk_off = blk + blocks + 1;
+    ctx->call.n_calls = 0; ctx->call.het = 0; ctx->call.hom = 0;
+    if (!n_sites) { ctx->call.state = 2; if (n_calls) *n_calls = 0; return REAL_HIP_OK; } // (no kernel over an empty table)
+    if ((rc = rh_reserve(ctx, ctx->call.blk, (size_t)(blocks + 1) * 16))) return rc;
+    uint64_t *blk = (uint64_t *)ctx->call.blk.p, *blk_off = blk + blocks + 1;
     size_t tmp = 0;
     RH_HIP(ctx, rocprim::exclusive_scan(nullptr, tmp, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream));
     if ((rc = rh_reserve(ctx, ctx->sort_tmp, tmp ? tmp : 8))) return rc;
-    RH_HIP(ctx, hipMemsetAsync(ctx->cl_fin.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
+    RH_HIP(ctx, hipMemsetAsync(ctx->call.fin.p, 0, (size_t)RH_PAIR_STRIPES * 16 * 8, ctx->stream));
     CallFinArgs F;
-    F.sites = (const uint4 *)ctx->pu_sites.p; F.ev = (const uint4 *)ctx->cl_ev.p; F.n_sites = n_sites;
+    F.sites = (const uint4 *)ctx->pileup.sites.p; F.ev = (const uint4 *)ctx->call.ev.p; F.n_sites = n_sites;
     F.min_call_qual = min_call_qual; F.min_depth = min_depth;
-    F.blk = blk; F.blk_off = blk_off; F.out = nullptr; F.cap = 0; F.fin = (unsigned long long *)ctx->cl_fin.p;
-    rh_time_begin(ctx, ctx->stream, ctx->call); // (no return inside the bracket: a failing step is reported behind rh_time_end)
+    F.blk = blk; F.blk_off = blk_off; F.out = nullptr; F.cap = 0; F.fin = (unsigned long long *)ctx->call.fin.p;
+    rh_time_begin(ctx, ctx->stream, ctx->call.stage); // (no return inside the bracket: a failing step is reported behind rh_time_end)
     hipLaunchKernelGGL(call_sites_kernel<false>, dim3((unsigned)blocks), dim3(RH_CL_BLOCK), 0, ctx->stream, F);
     hipError_t e = hipGetLastError();
     size_t t = tmp;
     if (e == hipSuccess) e = rocprim::exclusive_scan(ctx->sort_tmp.p, t, blk, blk_off, (uint64_t)0, (size_t)(blocks + 1), rocprim::plus<uint64_t>(), ctx->stream);
     rh_time_end(ctx, ctx->stream);
     if (e != hipSuccess) return rh_fail(ctx, REAL_HIP_E_DEVICE, "calls: count of the calls / scan of the block counts", e);
-    ctx->call.launches += 2;
+    ctx->call.stage.launches += 2;
     uint64_t total = 0;
     std::vector<uint64_t> fin((size_t)RH_PAIR_STRIPES * 16);
     RH_HIP(ctx, hipMemcpyAsync(&total, blk_off + blocks, 8, hipMemcpyDeviceToHost, ctx->stream));
-    RH_HIP(ctx, hipMemcpyAsync(fin.data(), ctx->cl_fin.p, fin.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    RH_HIP(ctx, hipMemcpyAsync(fin.data(), ctx->call.fin.p, fin.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     uint64_t het = 0, hom = 0;
     for (size_t s = 0; s < RH_PAIR_STRIPES; ++s) { het += fin[s * 16]; hom += fin[s * 16 + 1]; }
     if (total) {
-        if ((rc = rh_reserve(ctx, ctx->cl_calls, (size_t)total * sizeof(real_hip_call)))) return rc;
-        F.out = (uint4 *)ctx->cl_calls.p; F.cap = total;
-        rh_time_begin(ctx, ctx->stream, ctx->call);
+        if ((rc = rh_reserve(ctx, ctx->call.calls, (size_t)total * sizeof(real_hip_call)))) return rc;
+        F.out = (uint4 *)ctx->call.calls.p; F.cap = total;
+        rh_time_begin(ctx, ctx->stream, ctx->call.stage);
         hipLaunchKernelGGL(call_sites_kernel<true>, dim3((unsigned)blocks), dim3(RH_CL_BLOCK), 0, ctx->stream, F);
         rh_time_end(ctx, ctx->stream);
         RH_HIP(ctx, hipGetLastError());
-        ctx->call.launches += 1;
+        ctx->call.stage.launches += 1;
         RH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     rh_time_resolve(ctx);
-    ctx->cl_n_calls = total; ctx->cl_het = het; ctx->cl_hom = hom;
-    ctx->cl_state = 2;
+    ctx->call.n_calls = total; ctx->call.het = het; ctx->call.hom = hom;
+    ctx->call.state = 2;
     if (n_calls) *n_calls = total;
     return REAL_HIP_OK;
 }
@@ -315,11 +315,11 @@ int rh_call_stats(real_hip_ctx *ctx, real_hip_call_stats *out, int reset)
     uint64_t h[5];
     RhStageCount was;
     int rc;
-    if ((rc = rh_stage_read(ctx, ctx->call, RH_PAIR_STRIPES, 5, reset, h, was))) return rc;
+    if ((rc = rh_stage_read(ctx, ctx->call.stage, RH_PAIR_STRIPES, 5, reset, h, was))) return rc;
     if (out) {
         out->reserved = 0;
         out->reads = was.items; out->placed = h[0]; out->other_file = h[1]; out->invalid = h[2]; out->site_bases = h[3]; out->low_qual = h[4];
-        out->calls = ctx->cl_n_calls; out->het = ctx->cl_het; out->hom = ctx->cl_hom;
+        out->calls = ctx->call.n_calls; out->het = ctx->call.het; out->hom = ctx->call.hom;
         out->launches = was.launches; out->kernel_ms = was.kernel_ms;
     }
     return REAL_HIP_OK;

@@ -2,7 +2,7 @@
 // statistics line and the wave's add to it, the device view of the resident text, the emit slot of a flagged lane in a
 // count / scan / emit pass; and, through final_record.h, the decoder of the records these stages consume.
 #pragma once
-#include "real_hip_internal.h"
+#include "real_hip_ctx.h"
 #include "final_record.h"
 
 #define RH_PAIR_STRIPES 256u      /* the statistics are striped over this many 128-byte lines (see RH_CSTRIPES) */

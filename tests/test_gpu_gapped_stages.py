@@ -1,7 +1,7 @@
 """The four stages that consume gap records -- the gapped mismatch lists, the pileup's and the calls' gapped adds and the indel
 calls -- agree on WHICH records they place: all four take a record to a placement with the one step of
 real_amd/csrc/read_walk.h (placed_gap, on the decoder and the geometry rule of final_record.h), stage reads and records with one
-function of real_hip_api.hip and keep their state in one record beside the ctx (ctx_side.h).
+function of real_hip_api.hip and keep their state in records of their own inside the ctx (real_hip_ctx.h).
 
 (a) the hand-written records of pileup_gapped_workloads.hand_cases -- every refused record among them -- through all four, from
     host arrays and from device arrays: `placed`, `other_file` and `invalid` equal among the stages and equal to the three
