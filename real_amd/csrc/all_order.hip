@@ -11,7 +11,7 @@
 // (operator<, matchAllImplementation.cpp:122-136: k, pos, file, frag, score, inverted;
 // file is constant inside a call and frag is a monotone function of pos).
 // The matcher appends hits in wave order and counts them per read; a read has a handful of
-// hits, so: offsets = exclusive scan of the counts, scatter every raw record into its read's
+// hits (the reads that have more, on both sides of ALL_SMALL and ALL_HUGE: tests/test_gpu_all_order.py), so: offsets = exclusive scan of the counts, scatter every raw record into its read's
 // segment, rank the records of a segment against each other (one thread per read; one
 // workgroup per read with more than ALL_SMALL hits).  No global sort.  A read with one hit -- most
 // of those that have any -- needs neither: its record goes straight from the raw list to its place.
